@@ -107,7 +107,13 @@ def parse():
     ap.add_argument("--rehearsal", action="store_true", help="TEST ONLY: every workload on the tiny model at small sizes + a sharded == unsharded check of the results; "
                                                              "the line is marked `rehearsal` and is not a measurement")
     ap.add_argument("--inject-setup-failure", type=int, default=-1, metavar="RANK", help="TEST ONLY: the set-up of every throughput workload fails on this rank")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the headline's last timed step returned (tokens, images; all ranks' shards gathered) as DIR/<name>.npy "
+                         "in float32 / float64, at most 64 MB in all (a larger output is cut to a fixed seeded sample, its flat indices in DIR/<name>_index.npy)")
+    a = ap.parse_args()
+    if a.dump_outputs is not None and a.steps < 1:
+        ap.error("--dump-outputs needs --steps >= 1 (it writes the last timed step's outputs)")
+    return a
 
 
 def self_launch(a):
@@ -177,6 +183,31 @@ def timed(fn, steps, warmup, distributed, device):
         per_rank = {"min": round(-float(t[1].item()) / max(steps, 1) * 1e3, 3), "max": round(float(t[0].item()) / max(steps, 1) * 1e3, 3)}
         dt = float(t[0].item())
     return dt, per_rank
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(directory, arrays, budget=DUMP_BUDGET_BYTES, seed=0):
+    """--dump-outputs: write {name: numpy array} as directory/<name>.npy (float32 stays float32, integers become float64, which holds every token id exactly).
+    When the arrays exceed `budget` bytes in all, every array is cut to the same fraction of its elements, drawn with a fixed seed (the same flat indices for
+    the same shapes on every run and every build), and the indices are written next to it as <name>_index.npy."""
+    import numpy as np
+    os.makedirs(directory, exist_ok=True)
+    arrays = {k: (v.astype(np.float32) if v.dtype == np.float32 else v.astype(np.float64)) for k, v in arrays.items()}
+    total = sum(v.nbytes for v in arrays.values())
+    room = budget - 2 * 4096 * len(arrays)  # .npy headers
+    frac = 1.0 if total <= room else room / float(sum(v.size * (v.itemsize + 8) for v in arrays.values()))  # + 8 bytes per sampled element: its index
+    written = {}
+    for name, v in sorted(arrays.items()):
+        flat = v.reshape(-1)
+        if frac < 1.0:
+            idx = np.sort(np.random.default_rng(seed).choice(flat.size, size=max(1, int(flat.size * frac)), replace=False))
+            np.save(os.path.join(directory, name + "_index.npy"), idx.astype(np.float64))
+            v = flat[idx]
+        np.save(os.path.join(directory, name + ".npy"), v)
+        written[name] = list(v.shape)
+    return written
 
 
 def cpu_baseline(model_cfg, vq_cfg, grid, sample_steps, unet_sd, vq_sd, cond, uncond):
@@ -369,10 +400,11 @@ class Runner:
         return toks, self.vqm.decode_indices(toks)
 
 
-def run_workload(ctx, spec, steps, warmup, seed_base, fatal, with_latency_model=False):
+def run_workload(ctx, spec, steps, warmup, seed_base, fatal, with_latency_model=False, keep_outputs=False):
     """One workload through the path the N-GPU job takes: set-up (local) -> readiness agreement -> timed steps, each = [conditioning broadcast from rank 0 +
     shard slicing] + sampler -> (rehearsal: sharded == unsharded check) -> rank 0's roofline pass -> barrier.
-    Returns a dict of measurements, or {"error": ...} when the set-up failed on ANY rank (never for fatal=True, the headline: exceptions propagate)."""
+    Returns a dict of measurements, or {"error": ...} when the set-up failed on ANY rank (never for fatal=True, the headline: exceptions propagate).
+    keep_outputs: the result also carries "outputs", host copies of what the last timed step returned (every rank's shard, gathered in row order)."""
     import torch
     import torch.distributed as dist
 
@@ -406,6 +438,7 @@ def run_workload(ctx, spec, steps, warmup, seed_base, fatal, with_latency_model=
         return {"error": err}
 
     ev = {"b": [], "r": []}  # per step: (start, after the conditioning broadcast + shard, after the sampler) events -> broadcast_ms / graph_replay_ms
+    last = []  # the latest step's return value (a reference only: nothing is copied inside the timed region)
 
     def step():
         e0, e1, e2 = (torch.cuda.Event(enable_timing=True) for _ in range(3))
@@ -419,12 +452,23 @@ def run_workload(ctx, spec, steps, warmup, seed_base, fatal, with_latency_model=
         out = run.step(c, u)
         e2.record()
         ev["b"].append((e0, e1)); ev["r"].append((e1, e2))
+        last[:] = [out]
         return out
 
     dt, per_rank = timed(step, steps, warmup, distributed, device)
+    outputs = None
+    if keep_outputs:  # right after the timed steps, before anything else runs: a graph replay returns its static buffers, which the next replay overwrites
+        toks, img = last[0]
+        outputs = {}
+        for key, t in (("tokens", toks), ("images", img)):
+            if distributed:
+                parts = [torch.empty_like(t) for _ in range(world)]
+                dist.all_gather(parts, t.contiguous())
+                t = torch.cat(parts)
+            outputs[key] = t.cpu().numpy()
     ev_ms = lambda pairs: round(sum(x.elapsed_time(y) for x, y in pairs[-steps:]) / max(steps, 1), 4)
     res = {"dt": dt, "total": total, "per_rank_ms": per_rank, "broadcast_ms": ev_ms(ev["b"]) if distributed else 0.0, "sampler_ms": ev_ms(ev["r"]),
-           "submission": run.submission, "broadcast_bytes": (layout[1] + 1) * 4 if distributed else 0}
+           "submission": run.submission, "broadcast_bytes": (layout[1] + 1) * 4 if distributed else 0, "outputs": outputs}
 
     if a.rehearsal and a.noise == "philox":  # TEST ONLY: one more step, gathered, against the unsharded request on rank 0
         toks, img = step()
@@ -476,6 +520,7 @@ def main():
             print("bench.py: --gpus %d but the launcher started %d ranks; reporting the observed world size" % (a.gpus, world), file=sys.stderr)
     device = torch.device("cuda", local)
     torch.cuda.set_device(device)
+    torch.manual_seed(0)  # --noise torch draws from the global generators: the same arguments give the same inputs on every run
 
     from paella_amd import _lib
     lib = _lib.load()  # fails loudly if the HIP library is missing
@@ -495,7 +540,8 @@ def main():
 
     # ---- the headline: BASELINE configs[1] unless flags say otherwise
     head = run_workload(ctx, (a.model, a.batch, a.grid, a.sample_steps, a.s_byt5, a.clip_image, a.inpaint, True), a.steps, a.warmup, 0, fatal=True,
-                        with_latency_model=(a.batch == 1))
+                        with_latency_model=(a.batch == 1), keep_outputs=a.dump_outputs is not None)
+    dumped = dump_outputs(a.dump_outputs, head["outputs"]) if a.dump_outputs is not None and rank == 0 else None
     total = head["total"]
     value = total * a.steps / head["dt"]
     ms_per_step = head["dt"] / a.steps * 1e3
@@ -601,6 +647,8 @@ def main():
             line["config"]["share_device"] = True
         if hooks:
             line["test_hooks"] = hooks  # A/B run: NOT the product configuration
+        if dumped is not None:
+            line["dumped_outputs"] = {"dir": a.dump_outputs, "shapes": dumped}
         print(json.dumps(line), flush=True)
     if distributed:
         dist.destroy_process_group()

@@ -99,3 +99,22 @@ def test_rehearsal_line_at_world_size_one():
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 1 and out["config"]["collective_backend"] is None and out["config"]["broadcast_ms"] == 0.0
     assert out["rehearsal"]["tokens_equal_unsharded"] and all(t["rehearsal"]["images_equal_unsharded"] for t in out["throughput"])
+
+
+def test_dump_outputs_repeat_and_equal_across_world_sizes(tmp_path):
+    """bench.py --dump-outputs writes what the headline's last timed step returned: the same arguments give the same arrays run after run, and two ranks
+    (gathered in row order) give exactly the arrays of one rank sampling the whole batch (shard-exact Philox noise, same conditioning)."""
+    import numpy as np
+    args = ["--rehearsal", "--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-extra", "--dump-outputs"]
+    dirs = [str(tmp_path / d) for d in ("a", "b", "two_ranks")]
+    for d in dirs[:2]:
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--batch", "2"] + args + [d], capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert out["dumped_outputs"]["shapes"] == {"tokens": [2, 16, 16], "images": [2, 3, 128, 128]}
+    out = _torchrun(2, [os.path.join(ROOT, "bench.py")] + REHEARSAL + ["--no-extra", "--dump-outputs", dirs[2]])
+    assert out["n_gpus"] == 2 and out["dumped_outputs"]["shapes"] == {"tokens": [2, 16, 16], "images": [2, 3, 128, 128]}
+    for name, dtype in (("tokens", np.float64), ("images", np.float32)):
+        a, b, c = (np.load(os.path.join(d, name + ".npy")) for d in dirs)
+        assert a.dtype == dtype and np.array_equal(a, b) and np.array_equal(a, c), name
+    assert len(np.unique(np.load(os.path.join(dirs[0], "tokens.npy")))) > 1

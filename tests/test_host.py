@@ -159,3 +159,31 @@ def test_bench_workload_tables_and_broadcast_layouts():
             ref = conditioning_layout([mk(2), mk(3)])
             assert lay[1] == ref[1] and [list(map(tuple, d)) for d in lay[0]] == [list(map(tuple, d)) for d in ref[0]]
         del m
+
+
+def test_bench_dump_outputs_types_budget_and_fixed_sample(tmp_path):
+    """bench.py --dump-outputs: float32 stays float32, token ids become float64 (exact); over the byte budget every array is cut to a seeded sample whose flat
+    indices are written next to it, the same ones on every call, and the files stay within the budget."""
+    import os
+
+    import numpy as np
+
+    import bench
+    toks = np.arange(24, dtype=np.int64).reshape(2, 3, 4)
+    img = np.random.default_rng(1).random((2, 3, 8, 8)).astype(np.float32)
+    shapes = bench.dump_outputs(str(tmp_path / "small"), {"tokens": toks, "images": img})
+    assert shapes == {"tokens": [2, 3, 4], "images": [2, 3, 8, 8]} and sorted(os.listdir(tmp_path / "small")) == ["images.npy", "tokens.npy"]
+    t = np.load(tmp_path / "small" / "tokens.npy")
+    assert t.dtype == np.float64 and np.array_equal(t, toks)
+    i = np.load(tmp_path / "small" / "images.npy")
+    assert i.dtype == np.float32 and np.array_equal(i, img)
+    budget = 64 << 10
+    big = {"tokens": np.arange(8192, dtype=np.int64).reshape(2, 64, 64), "images": np.random.default_rng(2).random((2, 3, 64, 64)).astype(np.float32)}
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), big, budget=budget)
+        assert sum(os.path.getsize(tmp_path / d / f) for f in os.listdir(tmp_path / d)) <= budget
+    for name in ("tokens", "images"):
+        ia, ib = np.load(tmp_path / "a" / (name + "_index.npy")), np.load(tmp_path / "b" / (name + "_index.npy"))
+        assert np.array_equal(ia, ib) and 0 < ia.size < big[name].size and np.all(np.diff(ia) > 0)
+        va = np.load(tmp_path / "a" / (name + ".npy"))
+        assert np.array_equal(va, big[name].reshape(-1)[ia.astype(np.int64)])
