@@ -95,6 +95,7 @@ SIGNATURES = {
 # exported for tests / tools only; declared in paella_amd/csrc/test_hooks.h, not in the public header
 TEST_HOOKS = {
     "paella_prof_detail": (c_int64, [c_void_p, c_void_p, c_int64]),
+    "paella_prof_epi": (c_int64, [c_void_p, c_int64]),
     "paella_prof_enable": (c_int, [c_int]),
     "paella_prof_collect": (c_int, [POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(c_int64)]),
     "paella_test_gemm_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
@@ -105,6 +106,7 @@ TEST_HOOKS = {
     "paella_test_launch_chain": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
     "paella_test_attention_variant": (c_int, [c_int]),
     "paella_test_gemm_dma": (c_int, [c_int]),
+    "paella_test_gemm_epi_specialise": (c_int, [c_int]),
     "paella_test_gemm_raster": (c_int, [c_int]),
     "paella_test_gemm_ring": (c_int, [c_int]),
     "paella_test_ring_resident": (ctypes.c_long, [c_int, c_int]),

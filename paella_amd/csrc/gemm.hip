@@ -134,7 +134,7 @@ constexpr int ring_wg_per_cu(int WM, int WN, int TM, int TN, int APRO, int RING,
     return fit < wish ? (fit < 1 ? 1 : fit) : wish;
 }
 
-template <int WM, int WN, int TM, int TN, int PD, int APRO, bool TAIL = false, int BK = 32, bool DMA = false, int RING = 0, bool BF = false>  // BK: K step (32 or 64 floats per LDS row); APRO: 0 none, 1 GRN scale/shift, 2 LayerNorm from row statistics; TAIL: fused sampling tail (head GEMM);
+template <int WM, int WN, int TM, int TN, int PD, int APRO, bool TAIL = false, int BK = 32, bool DMA = false, int RING = 0, bool BF = false, int EPI = EPI_RUNTIME>  // BK: K step (32 or 64 floats per LDS row); APRO: 0 none, 1 GRN scale/shift, 2 LayerNorm from row statistics; TAIL: fused sampling tail (head GEMM);
 // DMA: operands that need no transform (W always, A when APRO == 0) go global -> LDS directly (buffer_load ... lds), no staging registers, no ds_write pass
 // APRO 4 (ring tiles only): the GRN apply from the producer's UNFINISHED statistics -- a' = a * (1 + gamma * gx / (mean gx + 1e-6)) + shift, the mean
 // derived per workgroup from the producer's per-column-tile partial sums (no finalize launch between the two MLP GEMMs).
@@ -154,6 +154,9 @@ template <int WM, int WN, int TM, int TN, int PD, int APRO, bool TAIL = false, i
 // the LDS-DMA addressing, the ring, the stream-K decomposition, the slabs and every epilogue are shared with the fp32 instantiation: a lane's ds_read_b128 of
 // slot kk * 4 + kq holds k = kk * 32 + kq * 8 .. + 7 -- exactly its operand of ONE 16x16x32 MFMA where the fp32 kernel issues four 16x16x4 ones.  Only the
 // all-DMA variants exist (direct-to-LDS twins and ring tiles; prologues 0 and 2 -- the folded LayerNorm's operand-side guard re-reads flagged 16-row blocks from the fp32 tensor, see ln_fix).
+// EPI (gemm_device.h): the epilogue class -- EPI_RUNTIME tests every epilogue feature on the Epilogue fields; a specialised class compiles in exactly its
+// features, so the stream-K flush, the last-arriver combine and the epilogue carry no dead branches and the uniforms of absent features are never loaded
+// (the batch-1 ring kernels spilled 91-151 SGPRs into VGPR lanes behind the K loop: profiles/gemm_epilogue_isa_counts.txt).
 __global__ __launch_bounds__(64 * WM * WN, RING > 0 ? ring_wg_per_cu(WM, WN, TM, TN, APRO, RING, BF)
                                            : (TAIL && DMA) ? 4  // fused head + tail on the 64x64 direct-to-LDS tile: four independent workgroups per CU
                                            : (TAIL && WM * WN == 8 && TM * TN == 4) ? 4  // fused head + tail on 128x64 tiles: TWO+ workgroups per CU, one's Philox / log epilogue overlaps another's main loop
@@ -711,7 +714,7 @@ __global__ __launch_bounds__(64 * WM * WN, RING > 0 ? ring_wg_per_cu(WM, WN, TM,
                 for (int j = 0; j < TN; ++j) {
                     const int nn = n0 + (wn * TN + j) * 16 + kq * 4;
                     if (m < g.M && nn < g.N) {
-                        const f32x4 v = epilogue_apply(g.ep, g.N, m, nn, acc[i][j]);
+                        const f32x4 v = epilogue_apply<false, EPI>(g.ep, g.N, m, nn, acc[i][j]);
                         if (ft.mode == 1) {
 #pragma unroll
                             for (int e = 0; e < 4; ++e)
@@ -759,7 +762,7 @@ __global__ __launch_bounds__(64 * WM * WN, RING > 0 ? ring_wg_per_cu(WM, WN, TM,
             return;
         }
         f32x4 qq[GRN_FIN ? TM : 1][GRN_FIN ? TN : 1];  // ring tiles: per 16-row block, column sums of squares (GRN finished in the epilogue)
-        const bool grn_fin = GRN_FIN && g.ep.grn_gx_out != nullptr;  // kernel-uniform
+        const bool grn_fin = GRN_FIN && epi_has<EPI, EPI_GRNFIN>(g.ep.grn_gx_out != nullptr);  // kernel-uniform
         // one 16-row block of the wave tile.  `it` is the loop variable of a fully unrolled loop -- or, on the 32-block wave tile (256x256), an integral constant: a
         // loop body of that size exceeds the compiler's budget for "#pragma unroll", the accumulators would be indexed at run time and live in scratch.
         // (Measured and NOT kept, round 6: fetching the epilogue's operands ahead of its stores -- column operands once per tile, row operands per 16-row block.  gfx950
@@ -779,8 +782,8 @@ __global__ __launch_bounds__(64 * WM * WN, RING > 0 ? ring_wg_per_cu(WM, WN, TM,
                     if constexpr (APRO == 2) {
                         if (!ln_dir[i]) a = (a - *reinterpret_cast<const f32x4*>(g.ln_wsum + nn) * fr_mu[i]) * fr_rs[i];  // the folded LayerNorm (see ln_row_stats)
                     }
-                    v = epilogue_apply<BF>(g.ep, g.N, m, nn, a);
-                    epilogue_write(g.ep, g.C, g.ldc, m, nn, v);
+                    v = epilogue_apply<BF, EPI>(g.ep, g.N, m, nn, a);
+                    epilogue_write<EPI>(g.ep, g.C, g.ldc, m, nn, v);
                 }
                 if constexpr (GRN_FIN) {
                     if (grn_fin) {
@@ -789,13 +792,13 @@ __global__ __launch_bounds__(64 * WM * WN, RING > 0 ? ring_wg_per_cu(WM, WN, TM,
                         qq[i][j] = q;  // every lane of the 16-row group holds the group's column sums (columns nn .. nn + 3)
                     }
                 }
-                if (g.ep.sumsq_out) {  // kernel-uniform: per-16-row column sums of squares (GlobalResponseNorm statistics)
+                if (epi_has<EPI, EPI_SUMSQ>(g.ep.sumsq_out != nullptr)) {  // kernel-uniform: per-16-row column sums of squares (GlobalResponseNorm statistics)
                     f32x4 q = v * v;
                     q[0] = row16_sum(q[0]); q[1] = row16_sum(q[1]); q[2] = row16_sum(q[2]); q[3] = row16_sum(q[3]);
                     const int mg = m0 + (wm * TM + i) * 16;
                     if (r16 == 0 && nn < g.N && mg < g.M) *reinterpret_cast<f32x4*>(g.ep.sumsq_out + (size_t)(mg >> 4) * g.N + nn) = q;
                 }
-                if (g.ep.rowstat_out) {  // kernel-uniform: per-row (sum, centred sum of squares) over this 16-column block (LayerNorm-on-load; gemm_device.h)
+                if (epi_has<EPI, EPI_ROWSTAT>(g.ep.rowstat_out != nullptr)) {  // kernel-uniform: per-row (sum, centred sum of squares) over this 16-column block (LayerNorm-on-load; gemm_device.h)
                     float rs, rq;
                     rowstat_block(v, rs, rq);
                     const int nb = n0 + (wn * TN + j) * 16;
@@ -1517,16 +1520,67 @@ extern "C" int paella_test_gemm_raster(int gm) { g_gemm_raster_gm = gm; return P
 static std::atomic<int> g_gemm_dma{1};  // test hook (test_hooks.h): 0 = always the register-staged kernels
 extern "C" int paella_test_gemm_dma(int on) { g_gemm_dma = on != 0; return PAELLA_OK; }
 
+// ---- epilogue classes (gemm_device.h: EPI_*) ----
+// The class of a launch: the set of epilogue features it uses, or EPI_RUNTIME when it needs one that only the run-time epilogue has (alpha != 1, a D2S /
+// pixel-shuffle store, a row remap, a bf16 copy, no fp32 output).  Pure function of the arguments.  (stores == false: the fused head + tail, whose epilogue
+// only applies bias .. scale / shift and never stores the logits; recorded by the timing hook, not specialised.)
+static int epi_class(const GemmArgs& g, bool stores = true) {
+    const Epilogue& e = g.ep;
+    if (e.alpha != 1.0f || (stores && (e.store_mode != STORE_PLAIN || e.remap_in > 0 || e.c16 || !g.C))) return EPI_RUNTIME;
+    return (e.bias ? EPI_BIAS : 0) | (e.act == ACT_GELU ? EPI_GELU : 0) | (e.residual ? EPI_RESID : 0) | (e.ts ? EPI_TS : 0) |
+           (e.rowstat_out ? EPI_ROWSTAT : 0) | (e.sumsq_out ? EPI_SUMSQ : 0) | (e.grn_gx_out ? EPI_GRNFIN : 0);
+}
+static std::atomic<int> g_gemm_epi_spec{1};  // test hook: 0 = every launch takes the EPI_RUNTIME instantiation (same-binary A/B)
+extern "C" int paella_test_gemm_epi_specialise(int on) { g_gemm_epi_spec = on != 0; return PAELLA_OK; }
+static thread_local int g_last_epi = EPI_RUNTIME;  // class of the instantiation the last launch of this thread took (per-launch record of the GEMM timing hook)
+static thread_local int g_last_cfg = -1;          // and its tile config
+
+// Specialised classes of the 32x32 ring tiles (ids 30 and 31, the batch-1 workhorses), per operand prologue -- what the fp32 UNet launches on them:
+//   B      = bias                   (attention in-projection, conditioning key / value projection)
+//   BGF    = bias + GELU + GRN Gx   (MLP GEMM 1, GlobalResponseNorm finished in the epilogue)
+//   BGS    = bias + GELU + GRN sums (MLP GEMM 1, finalize-launch path)
+//   BR*    = bias + residual (+ row statistics for a LayerNorm-folding consumer) (+ TimestepBlock scale / shift)  (MLP GEMM 2, attention out-projection)
+// Every other (tile, class) pair takes EPI_RUNTIME.  Share of batch-1 GEMM time per (instantiation, class): profiles/gemm_epilogue_kernel_trace_b1.txt.
+template <int... C> struct EpiSet {};
+enum : int {
+    EPI_B = EPI_BIAS, EPI_BGF = EPI_BIAS | EPI_GELU | EPI_GRNFIN, EPI_BGS = EPI_BIAS | EPI_GELU | EPI_SUMSQ, EPI_BR = EPI_BIAS | EPI_RESID,
+    EPI_BRS = EPI_BR | EPI_ROWSTAT, EPI_BRT = EPI_BR | EPI_TS, EPI_BRST = EPI_BR | EPI_ROWSTAT | EPI_TS,
+};
+template <int APRO> struct RingEpi { using set = EpiSet<>; };
+template <> struct RingEpi<0> { using set = EpiSet<EPI_B, EPI_BGF, EPI_BGS, EPI_BR, EPI_BRS>; };
+template <> struct RingEpi<1> { using set = EpiSet<EPI_BR, EPI_BRS, EPI_BRT, EPI_BRST>; };
+template <> struct RingEpi<2> { using set = EpiSet<EPI_B>; };
+template <> struct RingEpi<4> { using set = EpiSet<EPI_BR, EPI_BRS, EPI_BRT, EPI_BRST>; };
+
+template <int TM, int TN, int APRO, int RING, int EPI>
+static bool launch_ring_if(int cls, const GemmArgs& g, const SkPlan& p, unsigned G, float* slabs, unsigned* tickets, unsigned slab_bytes, hipStream_t st) {
+    if (cls != EPI) return false;
+    hipLaunchKernelGGL((gemm_nt_kernel<2, 2, TM, TN, 1, APRO, false, 32, false, RING, false, EPI>), dim3(G), dim3(256), 0, st, g, p, slabs, tickets, slab_bytes);
+    g_last_epi = EPI;
+    return true;
+}
+template <int TM, int TN, int APRO, int RING, int... C>
+static void launch_ring_epi(EpiSet<C...>, const GemmArgs& g, const SkPlan& p, unsigned G, float* slabs, unsigned* tickets, unsigned slab_bytes, hipStream_t st) {
+    const int cls = g_gemm_epi_spec ? epi_class(g) : EPI_RUNTIME;
+    if (!(launch_ring_if<TM, TN, APRO, RING, C>(cls, g, p, G, slabs, tickets, slab_bytes, st) || ...))
+        launch_ring_if<TM, TN, APRO, RING, EPI_RUNTIME>(EPI_RUNTIME, g, p, G, slabs, tickets, slab_bytes, st);
+}
+template <int TM, int TN, int RING, int APRO>
+static void launch_ring_apro(const GemmArgs& g, const SkPlan& p, unsigned G, float* slabs, unsigned* tickets, unsigned slab_bytes, hipStream_t st) {
+    using set = typename std::conditional<TM == 1 && TN == 1, typename RingEpi<APRO>::set, EpiSet<>>::type;  // (only the 32x32 ring tiles are specialised)
+    launch_ring_epi<TM, TN, APRO, RING>(set{}, g, p, G, slabs, tickets, slab_bytes, st);
+}
+
 template <int TM, int TN, int RING>
 static void launch_ring(const GemmArgs& g, const SkPlan& p, unsigned G, float* slabs, unsigned* tickets, unsigned slab_bytes, hipStream_t st) {
     if (g.grn_gx)
-        hipLaunchKernelGGL((gemm_nt_kernel<2, 2, TM, TN, 1, 4, false, 32, false, RING>), dim3(G), dim3(256), 0, st, g, p, slabs, tickets, slab_bytes);
+        launch_ring_apro<TM, TN, RING, 4>(g, p, G, slabs, tickets, slab_bytes, st);
     else if (g.a_scale)
-        hipLaunchKernelGGL((gemm_nt_kernel<2, 2, TM, TN, 1, 1, false, 32, false, RING>), dim3(G), dim3(256), 0, st, g, p, slabs, tickets, slab_bytes);
+        launch_ring_apro<TM, TN, RING, 1>(g, p, G, slabs, tickets, slab_bytes, st);
     else if (g.ln_stats)
-        hipLaunchKernelGGL((gemm_nt_kernel<2, 2, TM, TN, 1, 2, false, 32, false, RING>), dim3(G), dim3(256), 0, st, g, p, slabs, tickets, slab_bytes);
+        launch_ring_apro<TM, TN, RING, 2>(g, p, G, slabs, tickets, slab_bytes, st);
     else
-        hipLaunchKernelGGL((gemm_nt_kernel<2, 2, TM, TN, 1, 0, false, 32, false, RING>), dim3(G), dim3(256), 0, st, g, p, slabs, tickets, slab_bytes);
+        launch_ring_apro<TM, TN, RING, 0>(g, p, G, slabs, tickets, slab_bytes, st);
 }
 
 template <int WM, int WN, int TM, int TN, int PD, int BK>
@@ -1885,6 +1939,7 @@ struct GemmProf {
     size_t used = 0;
     std::vector<double> flops, bytes;
     std::vector<int> shape;         // per launch: M, N, K, prologue (0 none, 1 GRN, 2 LayerNorm, 3 implicit conv), tail
+    std::vector<int> epi;           // per launch: tile config, epilogue class of the instantiation it took (EPI_RUNTIME or a specialised class), class of its arguments
 };
 static GemmProf g_prof;
 static std::mutex g_prof_mu;  // enable / record / collect may come from different host threads (one per device in a multi-GPU process)
@@ -1905,8 +1960,12 @@ static int prof_bracket(const GemmArgs& g, hipStream_t st, bool stores_c, F&& la
     }
     hipEvent_t e0 = g_prof.pool[g_prof.used], e1 = g_prof.pool[g_prof.used + 1];
     HIP_CHECK_RET(hipEventRecord(e0, st));
+    g_last_cfg = -1;
+    g_last_epi = EPI_RUNTIME;
     const int rc = launch();
     HIP_CHECK_RET(hipEventRecord(e1, st));
+    const int ep3[3] = {g_last_cfg, g_last_epi, epi_class(g, stores_c)};
+    g_prof.epi.insert(g_prof.epi.end(), ep3, ep3 + 3);
     g_prof.used += 2;
     g_prof.flops.push_back(2.0 * g.M * g.N * g.K);
     g_prof.bytes.push_back(4.0 * ((double)g.M * g.K + (double)g.N * g.K + (stores_c ? (double)g.M * g.N : 0.0)));
@@ -1938,7 +1997,17 @@ extern "C" int paella_prof_enable(int on) {
     g_prof.flops.clear();
     g_prof.bytes.clear();
     g_prof.shape.clear();
+    g_prof.epi.clear();
     return PAELLA_OK;
+}
+
+// Per-launch epilogue records since paella_prof_enable(1), not reset: out3[3 i ..] = tile config, class of the instantiation launch i took (EPI_RUNTIME =
+// 1 << 30 or a specialised class), class of its arguments.  Returns the number of launches (at most cap are written).
+extern "C" long long paella_prof_epi(int* out3, long long cap) {
+    std::lock_guard<std::mutex> lock(g_prof_mu);
+    const size_t n = g_prof.epi.size() / 3;
+    for (size_t i = 0; i < 3 * n && (long long)i < 3 * cap; ++i) out3[i] = g_prof.epi[i];
+    return (long long)n;
 }
 
 // Per-launch records since paella_prof_enable(1), WITHOUT resetting them (call before paella_prof_collect): us_out[i] = duration of launch i,
@@ -1975,6 +2044,7 @@ extern "C" int paella_prof_collect(double* total_ms, double* total_flops, double
     g_prof.flops.clear();
     g_prof.bytes.clear();
     g_prof.shape.clear();
+    g_prof.epi.clear();
     return PAELLA_OK;
 }
 
@@ -2047,6 +2117,7 @@ static int launch_gemm_cfg_impl(const GemmArgs& g_in, int cfg, int splitk, void*
     }
     const TileCfg& tc = kCfgs[cfg];
     const int BM = tc.wm * tc.tm * 16, BN = tc.wn * tc.tn * 16;
+    g_last_cfg = cfg;
     // the 8-wave bf16 tiles have no in-kernel operand-side guard: the pre-pass it is, whatever M; the ping-pong tile carries ONLY the pre-pass form of the row statistics
     if (bf && g.ln_stats && !g.ln_row && (tc.ring == 2 || (g.A && tc.wm * tc.wn == 8))) {
         if (!prepass_fits) { paella_set_error("gemm: a bf16 LayerNorm-consuming launch on an 8-wave tile needs a workspace (>= 80 MiB + 16 bytes per row) for the row pre-pass"); return PAELLA_ERR_WORKSPACE; }
@@ -2193,6 +2264,7 @@ static int launch_gemm_tail_impl(const GemmArgs& g, hipStream_t st) {
     const bool bf = g.A16 != nullptr || g.W16 != nullptr;
     if (bf && (!g.A16 || !g.W16 || !gemm_bf16_ok(g.K, g.lda, g.ldw))) { paella_set_error("gemm_tail: bf16 operands need A16 and W16, K %% 64 == 0, lda / ldw %% 8 == 0"); return PAELLA_ERR_ARG; }
     const int cfg = gemm_tail_config(g.M, g.N, bf);
+    g_last_cfg = cfg;
     const TileCfg& tc = kCfgs[cfg];
     const int BM = tc.wm * tc.tm * 16, BN = tc.wn * tc.tn * 16;
     SkPlan p;

@@ -56,17 +56,39 @@ __device__ __forceinline__ float gelu_fast(float x) {
     return fmaf(-(a * d), r, fmaxf(x, 0.0f));
 }
 
+// Epilogue classes: the compile-time feature set of a GEMM instantiation's epilogue (template parameter EPI of gemm_nt_kernel and of the functions below).
+// EPI_RUNTIME tests every feature on the Epilogue fields at run time (every site that has no specialised instantiation).  Any other value is a bit set of
+// the features below; each one it names is applied UNCONDITIONALLY (its pointer is known to be set) and every other one is compiled out, so the fields it
+// does not name are dead in the kernel and never loaded.  A specialised class also implies alpha == 1, STORE_PLAIN, no row remap, C != null and no bf16 copy
+// (those stay run-time features).  The host picks the class with gemm.hip: epi_class(); the arithmetic and its order are the same in every class.
+enum : int {
+    EPI_BIAS = 1,       // + bias[n]
+    EPI_GELU = 2,       // act == ACT_GELU
+    EPI_RESID = 4,      // + residual[m][n]
+    EPI_TS = 8,         // TimestepBlock scale / shift
+    EPI_ROWSTAT = 16,   // rowstat_out: per-row (sum, M2) partials
+    EPI_SUMSQ = 32,     // sumsq_out: per-16-row GRN sums of squares
+    EPI_GRNFIN = 64,    // grn_gx_out: GlobalResponseNorm's Gx finished in the epilogue (ring tiles)
+    EPI_RUNTIME = 1 << 30,
+};
+// does class EPI apply feature F?  (EPI_RUNTIME: the run-time test `rt`; otherwise a constant, and `rt` is dead code)
+template <int EPI, int F>
+__device__ __forceinline__ bool epi_has(bool rt) {
+    if constexpr (EPI == EPI_RUNTIME) return rt;
+    else return (EPI & F) != 0;
+}
+
 // bias -> activation -> alpha -> residual -> timestep scale/shift (FASTG: the bf16-operand kernels' GELU)
-template <bool FASTG = false>
+template <bool FASTG = false, int EPI = EPI_RUNTIME>
 __device__ __forceinline__ f32x4 epilogue_apply(const Epilogue& ep, int N, int m, int n, f32x4 v) {
-    if (ep.bias) v += *reinterpret_cast<const f32x4*>(ep.bias + n);
-    if (ep.act == ACT_GELU) {
+    if (epi_has<EPI, EPI_BIAS>(ep.bias != nullptr)) v += *reinterpret_cast<const f32x4*>(ep.bias + n);
+    if (epi_has<EPI, EPI_GELU>(ep.act == ACT_GELU)) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = FASTG ? gelu_fast(v[i]) : gelu_erf(v[i]);
     }
-    if (ep.alpha != 1.0f) v *= ep.alpha;
-    if (ep.residual) v += *reinterpret_cast<const f32x4*>(ep.residual + (size_t)m * ep.ldr + n);
-    if (ep.ts) {
+    if (epi_has<EPI, 0>(ep.alpha != 1.0f)) v *= ep.alpha;
+    if (epi_has<EPI, EPI_RESID>(ep.residual != nullptr)) v += *reinterpret_cast<const f32x4*>(ep.residual + (size_t)m * ep.ldr + n);
+    if (epi_has<EPI, EPI_TS>(ep.ts != nullptr)) {
         const float* t = ep.ts + (size_t)fast_div((unsigned)m, ep.rps_div) * ep.ts_stride;
         f32x4 a = *reinterpret_cast<const f32x4*>(t + n);
         f32x4 b = *reinterpret_cast<const f32x4*>(t + N + n);
@@ -75,8 +97,11 @@ __device__ __forceinline__ f32x4 epilogue_apply(const Epilogue& ep, int N, int m
     return v;
 }
 
+template <int EPI = EPI_RUNTIME>
 __device__ __forceinline__ void epilogue_write(const Epilogue& ep, float* __restrict__ C, int ldc, int m, int n, f32x4 v) {
-    if (ep.store_mode == STORE_PLAIN) {
+    if constexpr (EPI != EPI_RUNTIME) {  // specialised classes: plain store, no remap, no bf16 copy, C set
+        *reinterpret_cast<f32x4*>(C + (size_t)m * ldc + n) = v;
+    } else if (ep.store_mode == STORE_PLAIN) {
         size_t orow = m;
         if (ep.remap_in > 0) orow = (size_t)(m / ep.remap_in) * ep.remap_out + (m % ep.remap_in) + ep.remap_off;
         if (C) *reinterpret_cast<f32x4*>(C + orow * ldc + n) = v;
@@ -143,7 +168,8 @@ struct RowStatAcc {
 // depends only on the rows' statistics, so every workgroup that shares a tile takes the same path.
 static constexpr float kLnFoldMaxRatio = 4.0f;  // default of GemmArgs::ln_fold_ratio
 
+template <int EPI = EPI_RUNTIME>
 __device__ __forceinline__ void epilogue_store(const Epilogue& ep, float* __restrict__ C, int ldc, int N,
                                                int m, int n, f32x4 v) {
-    epilogue_write(ep, C, ldc, m, n, epilogue_apply(ep, N, m, n, v));
+    epilogue_write<EPI>(ep, C, ldc, m, n, epilogue_apply<false, EPI>(ep, N, m, n, v));
 }

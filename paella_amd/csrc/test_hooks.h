@@ -42,6 +42,9 @@ int paella_test_mlp_grn_fused(const float* h, const float* W1, const float* b1, 
                               float* gx, float* part, float* out, int M, int c, int rps, void* ws, size_t ws_bytes, void* stream);
 /* 0 = never use the direct-to-LDS (DMA) twins of the large GEMM tiles (A/B and parity checks); 1 = default */
 int paella_test_gemm_dma(int on);
+/* 0 = every GEMM launch takes the run-time-epilogue instantiation (EPI_RUNTIME) even where a compile-time-specialised epilogue class exists
+ * (same-binary A/B; bit-identical results either way); 1 = default */
+int paella_test_gemm_epi_specialise(int on);
 /* the LDS-DMA ring tile (config id 30..35) the launch heuristic uses for the skinny batch-1 shapes; 0 = the register-staged / 1-deep kernels (A/B) */
 int paella_test_gemm_ring(int cfg);
 /* per-launch-site workgroup count of the skinny (ring-tile) GEMM class: site = (M, N, K, prologue class 0 / 1 GRN / 2 LayerNorm, bf16 operands 0 / 1); G > 0 sets it,
@@ -74,6 +77,9 @@ int paella_prof_collect(double* total_ms, double* total_flops, double* total_byt
 /* per-launch records since enable(1), not reset (call before collect): us_out[i], shape_out[5 i ..] = M, N, K, prologue (0 none, 1 GRN, 2 LayerNorm,
  * 3 implicit convolution), fused-tail flag; returns the launch count (at most cap are written) */
 long long paella_prof_detail(float* us_out, int* shape_out, long long cap);
+/* per-launch epilogue records since enable(1), not reset: out3[3 i ..] = tile config, epilogue class of the instantiation launch i took (1 << 30 = EPI_RUNTIME,
+ * otherwise a bit set of gemm_device.h: EPI_*), epilogue class of its arguments; returns the launch count (at most cap are written) */
+long long paella_prof_epi(int* out3, long long cap);
 /* scores_out [rows, L] = the Gumbel-max scores of the counter-based sampling tail (mix(l_c, l_u) / T - log q, the kernels' own arithmetic and
  * Philox counters): tests classify a differing token by the decision margin between the two best scores of its row */
 int paella_test_tail_scores(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature,
