@@ -1861,7 +1861,12 @@ static void choose_config(int M, int N, int K, int apro, bool ring_allowed, int 
 // (profiles/r05_gemm_bf16_tile_sweep.txt).  K steps are 64 elements wide.
 static std::atomic<int> g_bf16_rule{0};  // test hook (A/B of the rules below): bit 0 = never tile 36 (the fp32 rules' tiles instead)
 extern "C" int paella_test_gemm_bf16_rule(int mask) { g_bf16_rule = mask; return PAELLA_OK; }
-static void choose_config_bf16(int M, int N, int K, int apro, size_t slab_cap_bytes, int* cfg_out, unsigned* G_out) {
+// A bf16 LayerNorm-consuming launch on this tile takes its row statistics from the row pre-pass only: the ping-pong tile always, the other 8-wave tiles when the
+// fp32 rows are there for the operand-side guard (they have no in-kernel ln_fix).  The 4-wave tiles (18, 19, 30..35) carry ln_fix and run without the pre-pass.
+static bool bf16_ln_needs_prepass(int cfg, bool a32) { return kCfgs[cfg].ring == 2 || (a32 && kCfgs[cfg].wm * kCfgs[cfg].wn == 8); }
+// no_prepass_a32: 0 = the pre-pass is available; 1 / 2 = it does not fit the workspace, for a launch without / with the fp32 rows -- the rule then never picks a
+// tile that bf16_ln_needs_prepass() (the launcher would refuse it) and takes the 64x64 direct-to-LDS tile instead
+static void choose_config_bf16(int M, int N, int K, int apro, size_t slab_cap_bytes, int no_prepass_a32, int* cfg_out, unsigned* G_out) {
     const long ktiles = K / 64;
     const double macs = (double)M * N * K;
     const long T256 = tiles_of_cfg(36, M, N), T128 = tiles_of_cfg(10, M, N), T64 = tiles_of_cfg(18, M, N), TPP = tiles_of_cfg(37, M, N);
@@ -1916,6 +1921,7 @@ static void choose_config_bf16(int M, int N, int K, int apro, size_t slab_cap_by
         if (const int gs = site_lookup(M, N, K, apro, 1)) { G = gs; if (G < Tc) G = Tc; }
         if (G > resident && G > Tc) G = resident;
     }
+    if (apro == 2 && no_prepass_a32 && bf16_ln_needs_prepass(cfg, no_prepass_a32 == 2)) { cfg = 18; G = T64; }
     const long T = tiles_of_cfg(cfg, M, N);
     const long U = T * ktiles;
     if (G > U) G = U;
@@ -2105,7 +2111,7 @@ static int launch_gemm_cfg_impl(const GemmArgs& g_in, int cfg, int splitk, void*
     }
     unsigned G = 0;
     if (cfg < 0 && bf) {
-        choose_config_bf16(g.M, g.N, g.K, g.ln_stats ? 2 : 0, slab_cap, &cfg, &G);
+        choose_config_bf16(g.M, g.N, g.K, g.ln_stats ? 2 : 0, slab_cap, (g.ln_stats && !g.ln_row && !prepass_fits) ? (g.A ? 2 : 1) : 0, &cfg, &G);
     } else if (cfg < 0) {
         choose_config(g.M, g.N, g.K, (g.a_scale || g.grn_gx) ? 1 : (g.ln_stats ? 2 : 0), ring_ok(g, 64), g.force_ring_cfg, slab_cap, &cfg, &G);
         if (g.cv.enabled && !conv_cfg(cfg)) { paella_set_error("internal: heuristic picked tile %d without a convolution variant", cfg); return PAELLA_ERR_STATE; }
@@ -2114,13 +2120,19 @@ static int launch_gemm_cfg_impl(const GemmArgs& g_in, int cfg, int splitk, void*
         const long T = tiles_of_cfg(cfg, g.M, g.N);
         G = splitk < 0 ? (unsigned)(-splitk) : (unsigned)(T * (splitk < 1 ? 1 : splitk));
         if (g.cv.enabled && !conv_cfg(cfg)) { paella_set_error("gemm: tile config %d has no implicit-convolution variant", cfg); return PAELLA_ERR_ARG; }
+        // an explicit tile that needs the bf16 row pre-pass when it does not fit (above ~1.03 M rows in the model's split-K region): the 64x64 direct-to-LDS tile
+        // with its in-kernel guard instead of a failed launch; same work split, counted in tiles of 64x64
+        if (bf && bf16_cfg(cfg) && g.ln_stats && !g.ln_row && !prepass_fits && bf16_ln_needs_prepass(cfg, g.A != nullptr)) {
+            cfg = 18;
+            if (splitk >= 0) G = (unsigned)(tiles_of_cfg(cfg, g.M, g.N) * (splitk < 1 ? 1 : splitk));
+        }
     }
     const TileCfg& tc = kCfgs[cfg];
     const int BM = tc.wm * tc.tm * 16, BN = tc.wn * tc.tn * 16;
     g_last_cfg = cfg;
     // the 8-wave bf16 tiles have no in-kernel operand-side guard: the pre-pass it is, whatever M; the ping-pong tile carries ONLY the pre-pass form of the row statistics
-    if (bf && g.ln_stats && !g.ln_row && (tc.ring == 2 || (g.A && tc.wm * tc.wn == 8))) {
-        if (!prepass_fits) { paella_set_error("gemm: a bf16 LayerNorm-consuming launch on an 8-wave tile needs a workspace (>= 80 MiB + 16 bytes per row) for the row pre-pass"); return PAELLA_ERR_WORKSPACE; }
+    if (bf && g.ln_stats && !g.ln_row && bf16_ln_needs_prepass(cfg, g.A != nullptr)) {
+        if (!prepass_fits) { paella_set_error("internal: bf16 LayerNorm-consuming launch on tile %d without room for its row pre-pass", cfg); return PAELLA_ERR_STATE; }
         const int rc = ln_prepass();
         if (rc != PAELLA_OK) return rc;
     }

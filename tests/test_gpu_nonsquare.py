@@ -45,7 +45,7 @@ def test_tiny_forward_vs_reference(golden, tiny_sd, tag, shape, seed):
     diff = (out - ref).abs().max().item()
     clear, near, n_near = argmax_report(ref, out)
     print("tiny forward %s %s vs reference: max|diff| %.3e, argmax mismatches clear=%d near-tie=%d (of %d near-tie positions)" % (tag, shape, diff, clear, near, n_near))
-    assert diff <= 2e-4 and clear == 0
+    assert diff <= 2e-5 and clear == 0   # measured 3.1e-6 ... 3.5e-6 (profiles/parity_report.txt)
 
 
 def test_sample_reproduces_reference_tokens_16x32(golden, tiny_sd):
@@ -100,6 +100,7 @@ def test_vqgan_vs_reference(golden, built_lib, name, vc, px):
     np.testing.assert_allclose(float(img.double().sum()), float(g["img_sum"]), rtol=1e-12, err_msg="the seeded test image differs from the fixture's")
     qe, lat, idx, loss = v.encode(img.to(DEV))
     assert lat.shape == g["lat"].shape and idx.shape == g["idx"].shape
+    print(name, "latents: max|diff| %.3e" % float(np.abs(lat.cpu().numpy() - g["lat"]).max()))
     np.testing.assert_allclose(lat.cpu().numpy(), g["lat"], atol=2e-5)
     mism = idx.cpu().numpy() != g["idx"]
     rows = (torch.from_numpy(g["lat"]) * vc["scale_factor"]).permute(0, 2, 3, 1).reshape(-1, vc["c_latent"]).double()
@@ -169,7 +170,7 @@ def test_570m_forward_32x64_vs_oracle(built_lib):
     diff, std = (got - ref).abs().max().item(), ref.std().item()
     clear, near, n_near = argmax_report(ref, got)
     print("570M 32x64: logit std %.3f, max|diff| %.3e, argmax mismatches clear=%d near-tie=%d (of %d near-tie positions / 2048)" % (std, diff, clear, near, n_near))
-    assert std > 0.05 and diff <= 1e-3 * max(1.0, std) and clear == 0
+    assert std > 0.05 and diff <= 5e-5 * max(1.0, std) and clear == 0   # measured 6.8e-6 (profiles/parity_report.txt)
     # and the full-size VQGAN decode of a 32x64 grid
     vc = G.VQ_F8
     v = paella_amd.VQModel(**vc)
@@ -182,4 +183,4 @@ def test_570m_forward_32x64_vs_oracle(built_lib):
     assert img.shape == (1, 3, 256, 512)
     d2 = (img - iref).abs().max().item()
     print("f8 decode 32x64 tokens: max|diff| %.3e" % d2)
-    assert d2 <= 2e-4 * max(1.0, iref.abs().max().item())
+    assert d2 <= 5e-5 * max(1.0, iref.abs().max().item())   # measured 6.0e-6 (profiles/parity_report.txt)

@@ -291,7 +291,7 @@ def test_config5_full_size_inpaint_properties(built_lib):
     weights_for(m, sum(cfg["blocks"]))
     m = m.to(DEV)
     vq = paella_amd.VQModel(levels=3)
-    weights_for(vq, 2)
+    vsd = weights_for(vq, 2)
     vq = vq.to(DEV)
     B, P = 16, 1024
     g = torch.Generator().manual_seed(12)
@@ -307,6 +307,16 @@ def test_config5_full_size_inpaint_properties(built_lib):
     mk = mask.to(DEV).bool()
     assert torch.equal(toks[~mk], orig[~mk])
     assert (toks[mk] != orig[mk]).float().mean() > 0.2
+    # orig comes from the same HIP encode the recipe used: image 15 (its activations past the 4 GiB offsets) against the oracle's encode of that image
+    vc = G.VQ_F8
+    with torch.no_grad():
+        _, olat, oidx, _ = O.vq_encode(vsd, vc, img[15:16].cpu())
+    rows = (olat * vc["scale_factor"]).permute(0, 2, 3, 1).reshape(-1, vc["c_latent"]).double()
+    top = torch.cdist(rows, vsd["vquantizer.codebook.weight"].double()).pow(2).topk(2, dim=1, largest=False).values
+    near = ((top[:, 1] - top[:, 0]) < 1e-5).view(oidx.shape)
+    mism = orig[15:16].cpu() != oidx
+    print("configs[4] inpaint, image 15 encode vs oracle: %d / %d tokens differ, all at nearest-code near-ties: %s" % (int(mism.sum()), mism.numel(), not bool((mism & ~near).any())))
+    assert not (mism & ~near).any()
     torch.cuda.empty_cache()
 
 

@@ -78,7 +78,7 @@ def test_train_step_on_device_then_hip_engine_serves_updated_weights(golden, bui
     clear, near, n_near = argmax_report(ref, after)
     print("%s: train step on device ok (loss %.5f); after optimizer.step + eval: HIP vs oracle(updated state dict) max|diff| %.2e, logits moved by %.2e, "
           "argmax mismatches clear=%d near-tie=%d" % (which, float(loss), diff, moved, clear, near))
-    assert diff <= 2e-4 * max(1.0, ref.std().item())
+    assert diff <= 2e-5 * max(1.0, ref.std().item())   # measured 3.8e-6 ... 4.1e-6 (profiles/parity_report.txt)
     assert moved > 50 * diff, "the engine still serves the pre-step weights"
     assert clear == 0
 

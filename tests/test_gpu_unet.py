@@ -1,8 +1,8 @@
 """GPU: the HIP denoiser (through the C ABI behind paella_amd.Paella) vs the golden outputs of the reference itself
 (tests/golden) and, at full size, vs the CPU oracle on the same seeded weights/inputs.
 
-Tolerance (fp32 path, different summation order than the reference's CPU BLAS): |logit diff| <= 2e-4 on logits of
-std ~1 for the small fixtures, <= 1e-3 at the 570M size; argmax equality is asserted with the near-tie policy of
+Tolerance (fp32 path, different summation order than the reference's CPU BLAS): |logit diff| <= 2e-5 on logits of
+std ~1 for the small fixtures, <= 5e-5 * std at the 570M / 1B sizes (about 5x the measured maxima: profiles/parity_report.txt); argmax equality is asserted with the near-tie policy of
 SURVEY section 4 (positions whose reference top1-top2 margin < 1e-4 are counted and reported, never dropped)."""
 import ctypes
 
@@ -35,6 +35,7 @@ def _cmp(got, ref_np, atol):
     got = got.float().cpu()
     assert got.shape == ref.shape
     diff = (got - ref).abs().max().item()
+    print("tiny fixture %s: max|logit diff| %.3e (bound %.0e)" % (tuple(ref.shape), diff, atol))
     assert diff <= atol, "max |logit diff| %.3e > %.1e" % (diff, atol)
     clear, near, n_near = argmax_report(ref, got)
     assert clear == 0, "%d argmax mismatches with a clear reference margin (near-tie: %d of %d)" % (clear, near, n_near)
@@ -48,7 +49,7 @@ def test_tiny_forward_vs_reference(golden, tiny):
     c = to_dev(cond_for(G.UNET_TINY, 2, 5, 1, G.COND_SEED), DEV)
     out = m(x, r, **c)
     assert out.shape == (2, 64, 16, 16)  # the reference's [B, num_labels, H, W]
-    _cmp(out, g["logits"], 2e-4)
+    _cmp(out, g["logits"], 2e-5)
     np.testing.assert_allclose(m.gen_r_embedding(r).cpu().numpy(), g["r_embed"], atol=2e-6)
     np.testing.assert_allclose(m.gen_c_embeddings(**c).cpu().numpy(), g["c_embed"], atol=2e-5)
     # bit-reproducible run to run (no atomics anywhere on the path)
@@ -60,9 +61,9 @@ def test_tiny_conditioning_variants(golden, tiny):
     g = golden("unet_tiny_forward")
     x, r = torch.from_numpy(g["x"]).to(DEV), torch.from_numpy(g["r"]).to(DEV)
     c2 = to_dev(cond_for(G.UNET_TINY, 2, 3, 0, G.COND_SEED + 1), DEV)
-    _cmp(m(x, r, **c2), golden("unet_tiny_forward_textonly")["logits"], 2e-4)
+    _cmp(m(x, r, **c2), golden("unet_tiny_forward_textonly")["logits"], 2e-5)
     c3 = dict(c2, byt5=c2["byt5"][:, :0])  # CLIP-only: S_byt5 = 0
-    _cmp(m(x, r, **c3), golden("unet_tiny_forward_cliponly")["logits"], 2e-4)
+    _cmp(m(x, r, **c3), golden("unet_tiny_forward_cliponly")["logits"], 2e-5)
 
 
 def test_attn_weights_and_clip_image_list(golden, tiny):
@@ -71,8 +72,8 @@ def test_attn_weights_and_clip_image_list(golden, tiny):
     paella_amd.replace_attention_layers(m)  # call-site compatibility: no-op
     x, r = torch.from_numpy(g["x"]).to(DEV), torch.from_numpy(g["r"]).to(DEV)
     c = to_dev(cond_for(G.UNET_TINY, 2, 5, 2, G.COND_SEED), DEV)
-    _cmp(m(x, r, **c, attn_weights=torch.from_numpy(g["attn_weights"]).to(DEV)), g["logits"], 2e-4)
-    _cmp(m(x, r, **c), g["logits_noaw"], 2e-4)
+    _cmp(m(x, r, **c, attn_weights=torch.from_numpy(g["attn_weights"]).to(DEV)), g["logits"], 2e-5)
+    _cmp(m(x, r, **c), g["logits_noaw"], 2e-5)
 
 
 def test_mid_forward_head_dim_80(golden, built_lib):
@@ -90,7 +91,7 @@ def test_variant_blocks(golden, built_lib):
     g = golden("unet_variant_forward")
     m, _ = _model(G.UNET_VARIANT, g)
     c = to_dev(cond_for(G.UNET_VARIANT, 2, 3, 1, G.COND_SEED), DEV)
-    _cmp(m(torch.from_numpy(g["x"]).to(DEV), torch.from_numpy(g["r"]).to(DEV), **c), g["logits"], 2e-4)
+    _cmp(m(torch.from_numpy(g["x"]).to(DEV), torch.from_numpy(g["r"]).to(DEV), **c), g["logits"], 2e-5)
 
 
 def test_batching_is_row_independent(tiny):
@@ -152,7 +153,7 @@ def test_570m_forward_vs_oracle(built_lib):
     print("570M forward: logit std %.3f, max|diff| %.3e, argmax mismatches clear=%d near-tie=%d (of %d near-tie positions / 1024)"
           % (std, diff, clear, near, n_near))
     assert std > 0.05, "degenerate logits"
-    assert diff <= 1e-3 * max(1.0, std)
+    assert diff <= 5e-5 * max(1.0, std)   # measured 6.2e-6 ... 8.8e-6 (profiles/parity_report.txt)
     assert clear == 0
 
 
@@ -173,7 +174,7 @@ def test_1b_forward_ragged_conditioning_vs_oracle(built_lib):
     diff = (got - ref).abs().max().item()
     clear, near, n_near = argmax_report(ref, got)
     print("1B forward: logit std %.3f, max|diff| %.3e, argmax mismatches clear=%d near-tie=%d" % (ref.std().item(), diff, clear, near))
-    assert diff <= 1e-3 * max(1.0, ref.std().item()) and clear == 0
+    assert diff <= 5e-5 * max(1.0, ref.std().item()) and clear == 0   # measured 6.2e-6 ... 8.8e-6 (profiles/parity_report.txt)
 
 
 def test_570m_64x64_grid_vs_oracle(built_lib):
@@ -192,12 +193,12 @@ def test_570m_64x64_grid_vs_oracle(built_lib):
     diff = (got - ref).abs().max().item()
     clear, near, n_near = argmax_report(ref, got)
     print("570M 64x64: logit std %.3f, max|diff| %.3e, argmax mismatches clear=%d near-tie=%d of %d" % (ref.std().item(), diff, clear, near, 64 * 64))
-    assert diff <= 1e-3 * max(1.0, ref.std().item()) and clear == 0
+    assert diff <= 5e-5 * max(1.0, ref.std().item()) and clear == 0   # measured 6.2e-6 ... 8.8e-6 (profiles/parity_report.txt)
 
 
 def _real_geometry_vs_oracle(cfg, grid, S_byt5, n_img, seed, what):
     """One B = 1 forward at a BASELINE configuration's REAL per-sample geometry against the CPU oracle (src/modules.py:263-275,
-    attention src/modules.py:7-19 at the real query / key counts): logits within 1e-3 * std, argmax identical except at reference
+    attention src/modules.py:7-19 at the real query / key counts): logits within 5e-5 * std, argmax identical except at reference
     near-ties (counted, printed)."""
     m = paella_amd.Paella(**cfg)
     sd = weights_for(m, sum(cfg["blocks"]))
@@ -215,7 +216,7 @@ def _real_geometry_vs_oracle(cfg, grid, S_byt5, n_img, seed, what):
     print("%s: logit std %.3f, max|diff| %.3e, argmax mismatches clear=%d near-tie=%d (of %d near-tie positions / %d)"
           % (what, std, diff, clear, near, n_near, grid * grid))
     assert std > 0.05, "degenerate logits"
-    assert diff <= 1e-3 * max(1.0, std)
+    assert diff <= 5e-5 * max(1.0, std)   # measured 6.2e-6 ... 8.8e-6 (profiles/parity_report.txt)
     assert clear == 0
     del m
     torch.cuda.empty_cache()
@@ -318,7 +319,7 @@ def test_layernorm_guard_inside_the_network(built_lib, B, grid, regime, shift):
     every TimestepBlock (the last op before each LayerNorm consumer, `x * (1 + a) + b`, src/modules.py:99-106) gets a nearly constant `b` = shift plus three
     outlier channels (+60, -45, +80) and a small `a`: the rows the consumers normalise have |mean| / std ~ 16 (shift 100) and ~ 160 (shift 1000) at all three levels.
     The whole network -- producer epilogue's centred partials -> pre-pass / in-kernel derivation -> guarded consumer -- must still match the oracle:
-    logits within 1e-3 * std, no argmax mismatch with a clear reference margin, and the guard must really have run (device counter hook)."""
+    logits within 5e-4 * std, no argmax mismatch with a clear reference margin, and the guard must really have run (device counter hook)."""
     lib = built_lib
     cfg = G.UNET_MID
     m = paella_amd.Paella(**cfg)
@@ -355,4 +356,4 @@ def test_layernorm_guard_inside_the_network(built_lib, B, grid, regime, shift):
     print("LayerNorm guard in the network (%s, TimestepBlock shift %g): %d waves took the operand-side path; logit std %.3f, max|diff| %.3e, argmax mismatches clear=%d near-tie=%d (of %d)"
           % (regime, shift, n_guard, std, diff, clear, near, n_near))
     assert n_guard > 0, "the guard never tripped: the test does not exercise the operand-side path"
-    assert std > 0.05 and diff <= 1e-3 * max(1.0, std) and clear == 0
+    assert std > 0.05 and diff <= 5e-4 * max(1.0, std) and clear == 0   # measured up to 4.4e-5 at shift 1000 (profiles/parity_report.txt)
