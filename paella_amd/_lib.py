@@ -96,6 +96,7 @@ SIGNATURES = {
 TEST_HOOKS = {
     "paella_prof_detail": (c_int64, [c_void_p, c_void_p, c_int64]),
     "paella_prof_epi": (c_int64, [c_void_p, c_int64]),
+    "paella_prof_grid": (c_int64, [c_void_p, c_int64]),
     "paella_prof_enable": (c_int, [c_int]),
     "paella_prof_collect": (c_int, [POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(ctypes.c_double), POINTER(c_int64)]),
     "paella_test_gemm_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),

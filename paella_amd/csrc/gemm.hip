@@ -1534,6 +1534,7 @@ static std::atomic<int> g_gemm_epi_spec{1};  // test hook: 0 = every launch take
 extern "C" int paella_test_gemm_epi_specialise(int on) { g_gemm_epi_spec = on != 0; return PAELLA_OK; }
 static thread_local int g_last_epi = EPI_RUNTIME;  // class of the instantiation the last launch of this thread took (per-launch record of the GEMM timing hook)
 static thread_local int g_last_cfg = -1;          // and its tile config
+static thread_local long long g_last_G = 0, g_last_T = 0, g_last_bf = 0;  // and its work split: workgroups launched, output tiles, bf16 operands (record paella_prof_grid)
 
 // Specialised classes of the 32x32 ring tiles (ids 30 and 31, the batch-1 workhorses), per operand prologue -- what the fp32 UNet launches on them:
 //   B      = bias                   (attention in-projection, conditioning key / value projection)
@@ -1946,6 +1947,7 @@ struct GemmProf {
     std::vector<double> flops, bytes;
     std::vector<int> shape;         // per launch: M, N, K, prologue (0 none, 1 GRN, 2 LayerNorm, 3 implicit conv), tail
     std::vector<int> epi;           // per launch: tile config, epilogue class of the instantiation it took (EPI_RUNTIME or a specialised class), class of its arguments
+    std::vector<long long> grid;    // per launch: tile config, workgroups launched (G), output tiles (T), bf16 operands (0 / 1)
 };
 static GemmProf g_prof;
 static std::mutex g_prof_mu;  // enable / record / collect may come from different host threads (one per device in a multi-GPU process)
@@ -1968,10 +1970,13 @@ static int prof_bracket(const GemmArgs& g, hipStream_t st, bool stores_c, F&& la
     HIP_CHECK_RET(hipEventRecord(e0, st));
     g_last_cfg = -1;
     g_last_epi = EPI_RUNTIME;
+    g_last_G = g_last_T = g_last_bf = 0;
     const int rc = launch();
     HIP_CHECK_RET(hipEventRecord(e1, st));
     const int ep3[3] = {g_last_cfg, g_last_epi, epi_class(g, stores_c)};
     g_prof.epi.insert(g_prof.epi.end(), ep3, ep3 + 3);
+    const long long gr4[4] = {g_last_cfg, g_last_G, g_last_T, g_last_bf};
+    g_prof.grid.insert(g_prof.grid.end(), gr4, gr4 + 4);
     g_prof.used += 2;
     g_prof.flops.push_back(2.0 * g.M * g.N * g.K);
     g_prof.bytes.push_back(4.0 * ((double)g.M * g.K + (double)g.N * g.K + (stores_c ? (double)g.M * g.N : 0.0)));
@@ -2004,6 +2009,7 @@ extern "C" int paella_prof_enable(int on) {
     g_prof.bytes.clear();
     g_prof.shape.clear();
     g_prof.epi.clear();
+    g_prof.grid.clear();
     return PAELLA_OK;
 }
 
@@ -2013,6 +2019,16 @@ extern "C" long long paella_prof_epi(int* out3, long long cap) {
     std::lock_guard<std::mutex> lock(g_prof_mu);
     const size_t n = g_prof.epi.size() / 3;
     for (size_t i = 0; i < 3 * n && (long long)i < 3 * cap; ++i) out3[i] = g_prof.epi[i];
+    return (long long)n;
+}
+
+// Per-launch work splits since paella_prof_enable(1), not reset: out4[4 i ..] = tile config, workgroups launched (G), output tiles (T), bf16 operands (0 / 1) of
+// launch i (G == T: one tile per workgroup; G a multiple of T: classic split-K; otherwise balanced stream-K ranges).  Returns the number of launches (at most cap
+// are written).
+extern "C" long long paella_prof_grid(long long* out4, long long cap) {
+    std::lock_guard<std::mutex> lock(g_prof_mu);
+    const size_t n = g_prof.grid.size() / 4;
+    for (size_t i = 0; i < 4 * n && (long long)i < 4 * cap; ++i) out4[i] = g_prof.grid[i];
     return (long long)n;
 }
 
@@ -2051,6 +2067,7 @@ extern "C" int paella_prof_collect(double* total_ms, double* total_flops, double
     g_prof.bytes.clear();
     g_prof.shape.clear();
     g_prof.epi.clear();
+    g_prof.grid.clear();
     return PAELLA_OK;
 }
 
@@ -2177,6 +2194,7 @@ static int launch_gemm_cfg_impl(const GemmArgs& g_in, int cfg, int splitk, void*
     p.q = p.U / G;
     p.r = p.U % G;
     p.G = G;
+    g_last_G = G; g_last_T = (long long)T; g_last_bf = bf;
     p.dKT = fast_div_of((unsigned)p.KT); p.dTM = fast_div_of((unsigned)p.tiles_m); p.dQ = fast_div_of(p.q); p.dQ1 = fast_div_of(p.q + 1);
     // grouped rasterisation for launches with many tile rows and columns (test hook: paella_test_gemm_raster)
     // (32-row tiles and skinny problems keep the plain order: their traffic is the weight panel, which m-fastest tiles share best --
@@ -2294,6 +2312,7 @@ static int launch_gemm_tail_impl(const GemmArgs& g, hipStream_t st) {
     p.q = (unsigned)(p.U / G);
     p.r = 0;
     p.G = (unsigned)G;
+    g_last_G = (long long)G; g_last_T = (long long)T; g_last_bf = bf;
     p.dKT = fast_div_of((unsigned)p.KT); p.dTM = fast_div_of((unsigned)p.tiles_m); p.dQ = fast_div_of(p.q); p.dQ1 = fast_div_of(p.q + 1);
     // grouped rasterisation as in the unfused launches: with K = c_out = 256 a tile moves 196 KB of operands for 4.2 MFLOP, and in plain m-fastest order no two
     // tiles that run together share an activation panel -- the whole activation matrix crosses the fabric once per column tile (34 GB per launch at configs[2])

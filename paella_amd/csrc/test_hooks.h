@@ -80,6 +80,9 @@ long long paella_prof_detail(float* us_out, int* shape_out, long long cap);
 /* per-launch epilogue records since enable(1), not reset: out3[3 i ..] = tile config, epilogue class of the instantiation launch i took (1 << 30 = EPI_RUNTIME,
  * otherwise a bit set of gemm_device.h: EPI_*), epilogue class of its arguments; returns the launch count (at most cap are written) */
 long long paella_prof_epi(int* out3, long long cap);
+/* per-launch work splits since enable(1), not reset: out4[4 i ..] = tile config, workgroups launched (G), output tiles (T), bf16 operands (0 / 1); G == T is one
+ * tile per workgroup, G a multiple of T a classic K split, anything else balanced stream-K ranges; returns the launch count (at most cap are written) */
+long long paella_prof_grid(long long* out4, long long cap);
 /* scores_out [rows, L] = the Gumbel-max scores of the counter-based sampling tail (mix(l_c, l_u) / T - log q, the kernels' own arithmetic and
  * Philox counters): tests classify a differing token by the decision margin between the two best scores of its row */
 int paella_test_tail_scores(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature,
