@@ -14,15 +14,19 @@ seeded synthetic weights and random embeddings, inputs resident in HBM when the 
 With N GPUs every rank generates its own batch (weak scaling); rank 0 owns the conditioning of all N*batch images and
 broadcasts it once per step over RCCL (the only collective of the path).
 
-Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).  Besides the contract fields the line carries
-`throughput`: the same path at throughput batch sizes, each with its own in-run roofline -- batch 32 / 64 / 128 at configs[1]'s model and grid (the
-BASELINE metric "256x256 @ 8 steps" at the batch where a GPU is busiest: `best_256px_8step`), BASELINE configs[2] (one GPU only), and the per-GPU shares
-of the two configurations BASELINE names for 8 GPUs: configs[3] (1B, batch 256 / 8 = 32 per GPU, 64x64 tokens, ByT5 + CLIP text + CLIP image) and
-configs[4] (1B, batch 128 / 8 = 16 per GPU, 128x128 tokens, the inpainting path).  On N GPUs every one of them goes through the SAME broadcast + shard path
-as the headline (rank 0 owns the conditioning of all N x batch images; whole-node images/s, max-over-ranks timing, per-workload broadcast_ms).
+Prints ONE JSON line on rank 0 (see DESIGN.md "Measurement" for every field).  A plain run measures the headline alone: set-up, warm-up, the timed steps,
+--dump-outputs if given, the line; `roofline`, `throughput`, `fast_mode`, `cpu_baseline` and `best_256px_8step` are null.  --full adds everything else the
+benchmark measures, each after the headline's timed steps: rank 0's event-bracketed roofline pass of the headline, `throughput` -- the same path at throughput
+batch sizes, each with its own in-run roofline: batch 32 / 64 / 128 at configs[1]'s model and grid (the BASELINE metric "256x256 @ 8 steps" at the batch where a
+GPU is busiest: `best_256px_8step`), BASELINE configs[2] (one GPU only), and the per-GPU shares of the two configurations BASELINE names for 8 GPUs: configs[3]
+(1B, batch 256 / 8 = 32 per GPU, 64x64 tokens, ByT5 + CLIP text + CLIP image) and configs[4] (1B, batch 128 / 8 = 16 per GPU, 128x128 tokens, the inpainting
+path) --, the opt-in bf16 fast mode and the CPU baseline; --no-roofline / --no-extra / --no-cpu-baseline leave parts of it out.  On N GPUs every throughput
+workload goes through the SAME broadcast + shard path as the headline (rank 0 owns the conditioning of all N x batch images; whole-node images/s,
+max-over-ranks timing, per-workload broadcast_ms).
 
 Test-only flags (tests/test_gpu_dist.py): --rehearsal (every workload on the tiny model at small sizes, plus a sharded == unsharded check of the last
-step's tokens and images), --dist-backend gloo --share-device (N ranks on ONE device: the N > 1 code paths on a 1-GPU box), --inject-setup-failure R.
+step's tokens and images; the throughput workloads with --full), --dist-backend gloo --share-device (N ranks on ONE device: the N > 1 code paths on a
+1-GPU box), --inject-setup-failure R.
 """
 import argparse
 import ctypes
@@ -89,8 +93,11 @@ def parse():
     ap.add_argument("--sample-steps", type=int, default=8)
     ap.add_argument("--noise", default="philox", choices=["philox", "torch"])
     ap.add_argument("--no-graph", action="store_true", help="eager launches instead of one captured HIP graph per image batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the throughput-batch runs (batch 32 at configs[1], BASELINE configs[2])")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also measure everything else: its roofline pass, the throughput workloads, the bf16 fast mode, the CPU baseline "
+                         "(a plain run measures the headline alone)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-extra", action="store_true", help="with --full: skip the throughput workloads and the bf16 fast mode")
     ap.add_argument("--gemm", default="fp32", choices=["fp32", "bf16"],
                     help="fp32 = the exact path (the headline); bf16 = OPT-IN fast mode outside the parity contract (bf16 MFMA operands, fp32 accumulate)")
     ap.add_argument("--hook", action="append", default=[], metavar="NAME=INT",
@@ -99,7 +106,7 @@ def parse():
     ap.add_argument("--s-byt5", type=int, default=0, help="ByT5 conditioning rows (0 = CLIP-text only, the headline; 256 for the configs[3] / configs[4] shares)")
     ap.add_argument("--clip-image", type=int, default=0, help="number of CLIP image embeddings in the conditioning (configs[3] / configs[4]: 1)")
     ap.add_argument("--inpaint", action="store_true", help="the configs[4] path: VQGAN encode -> masked renoise -> sample(init_x, t_start 0.5) -> decode (eager)")
-    ap.add_argument("--no-roofline", action="store_true", help="profiling runs only (tools/collect_profiles.sh): skip rank 0's event-bracketed roofline pass -- the profiler then sees "
+    ap.add_argument("--no-roofline", action="store_true", help="with --full, for profiling runs: skip rank 0's event-bracketed roofline passes -- the profiler then sees "
                                                                "the timed steps alone; the line's `roofline` is null")
     ap.add_argument("--force-dist", action="store_true", help="take the torch.distributed (RCCL) path even at world size 1 (launch under torchrun)")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"], help="TEST ONLY: gloo moves device tensors through the host, which lets N ranks share one GPU")
@@ -484,7 +491,7 @@ def run_workload(ctx, spec, steps, warmup, seed_base, fatal, with_latency_model=
             res["rehearsal"] = {"tokens_equal_unsharded": bool(torch.equal(toks, ft)), "images_equal_unsharded": bool(torch.equal(img, fi)),
                                 "tokens": int(toks.numel()), "row_offsets": [r * batch * grid * grid for r in range(world)]}
 
-    if rank == 0 and not a.no_roofline:  # the roofline pass (eager launches, every GEMM bracketed by events) runs on rank 0 alone; the others wait at the barrier below
+    if rank == 0 and a.full and not a.no_roofline:  # the roofline pass (eager launches, every GEMM bracketed by events) runs on rank 0 alone; the others wait at the barrier below
         c0, u0 = (cond_all, uncond_all) if not distributed else (shard_inputs(cond_all, lo, hi), shard_inputs(uncond_all, lo, hi))
         res["roofline"] = gemm_roofline(ctx.lib, lambda: run.eager(c0, u0, seed_base + 7), device, name, batch, grid, sample_steps, a.gemm, True,
                                         with_latency_model=with_latency_model)
@@ -550,7 +557,7 @@ def main():
     # ---- the same path at throughput batch sizes and on BASELINE's other configurations, each with its own in-run roofline (module docstring).  N GPUs: the
     # SAME broadcast + shard path per workload (whole-node images/s, max-over-ranks timing); a set-up failure on any rank turns the entry into an `error`. ----
     throughput = None
-    if not a.no_extra and headline_cfg:
+    if a.full and not a.no_extra and headline_cfg:
         throughput = []
         table = REHEARSAL_WORKLOADS if a.rehearsal else ([EXTRA_WORKLOADS[i] for i in EXTRA_DISTRIBUTED] if distributed else EXTRA_WORKLOADS)
         for (en, eb, eg, es, sb, nci, inp, k, w, gr) in table:
@@ -587,7 +594,7 @@ def main():
 
     # ---- the OPT-IN bf16 fast mode (per-model switch, outside the parity contract), driver-timed as a SEPARATE entry: the headline stays fp32 ----
     fast_mode = None
-    if not a.no_extra and a.gemm == "fp32" and not distributed and not a.rehearsal and headline_cfg:
+    if a.full and not a.no_extra and a.gemm == "fp32" and not distributed and not a.rehearsal and headline_cfg:
         try:
             def make_runner(eb, eg, es, seed_base):
                 r = Runner(ctx, a.model, eb, eg, es, 0, 0, False, True, seed_base)
@@ -600,7 +607,7 @@ def main():
             vq.set_gemm_precision("fp32")
 
     cpu = None
-    if rank == 0 and world == 1 and not a.no_cpu_baseline and not a.rehearsal:  # the CPU baseline is an N = 1 figure
+    if rank == 0 and world == 1 and a.full and not a.no_cpu_baseline and not a.rehearsal:  # the CPU baseline is an N = 1 figure
         try:
             c1, u1 = ctx.mk_cond(1, 2, a.model, a.s_byt5, a.clip_image), ctx.mk_cond(1, 3, a.model, a.s_byt5, a.clip_image)
             cpu = cpu_baseline(mcfg, vcfg, a.grid, a.sample_steps, unet_sd, vq_sd, c1, u1)
@@ -612,7 +619,7 @@ def main():
         # the BASELINE metric "images/sec, 256x256 @ 8 steps" at the batch where a GPU is busiest: the best of the headline and the 32x32-token
         # / 8-step throughput entries of THIS run
         best = None
-        if a.model == "570m" and (a.grid, a.sample_steps) == (32, 8):
+        if a.full and a.model == "570m" and (a.grid, a.sample_steps) == (32, 8):
             cands = [{"batch_per_gpu": a.batch, "images_per_sec": round(value, 3), "ms_per_image": round(ms_per_step / total, 3), "executed_frac": (head.get("roofline") or {}).get("executed_frac")}]
             for t in throughput or []:
                 if "error" not in t and (t["model"], t["grid"], t["sample_steps"]) == ("570m", 32, 8):

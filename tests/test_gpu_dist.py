@@ -60,13 +60,14 @@ def test_bench_runs_through_rccl_at_the_world_size_of_the_box():
 # the host; RCCL refuses two ranks on one device).  Everything that depends on rank != 0 or world > 1 runs for real: the receive buffer of the packed
 # conditioning broadcast, shard rows [B, 2B) keyed by a NON-ZERO device-resident row offset through the captured graphs (GraphSampler / GraphInpainter), the
 # all_reduce(MAX) timing, the readiness agreement before each throughput workload, the barriers around rank 0's roofline pass.  `--rehearsal` shrinks every
-# workload to the tiny model and adds the check that matters: the gathered shards equal the unsharded request bit for bit, tokens AND images.
+# workload to the tiny model and adds the check that matters: the gathered shards equal the unsharded request bit for bit, tokens AND images.  The throughput
+# workloads and the roofline passes run under `--full` only.
 # ---------------------------------------------------------------------------------------------------------------------
 REHEARSAL = ["--gpus", "2", "--rehearsal", "--dist-backend", "gloo", "--share-device", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
 
 
 def test_two_rank_rehearsal_of_the_distributed_bench_on_one_device():
-    out = _torchrun(2, [os.path.join(ROOT, "bench.py")] + REHEARSAL, timeout=900)
+    out = _torchrun(2, [os.path.join(ROOT, "bench.py")] + REHEARSAL + ["--full"], timeout=900)
     print(json.dumps(out))
     c = out["config"]
     assert out["n_gpus"] == 2 and c["world_size_observed"] == 2 and c["collective_backend"].startswith("gloo") and c["share_device"] is True
@@ -86,7 +87,7 @@ def test_two_rank_rehearsal_of_the_distributed_bench_on_one_device():
 
 
 def test_injected_setup_failure_on_rank_1_is_an_error_entry_not_a_hang():
-    out = _torchrun(2, [os.path.join(ROOT, "bench.py")] + REHEARSAL + ["--inject-setup-failure", "1"], timeout=600)
+    out = _torchrun(2, [os.path.join(ROOT, "bench.py")] + REHEARSAL + ["--full", "--inject-setup-failure", "1"], timeout=600)
     assert out["value"] > 0 and out["rehearsal"]["tokens_equal_unsharded"]          # the headline is untouched
     tp = out["throughput"]
     assert len(tp) == 3 and all(t.get("error") == "set-up failed on another rank" for t in tp), tp   # rank 0 learned it through the readiness agreement
@@ -94,11 +95,22 @@ def test_injected_setup_failure_on_rank_1_is_an_error_entry_not_a_hang():
 
 def test_rehearsal_line_at_world_size_one():
     """the same flags without a launcher: the non-distributed branch of the same code (no collective at all)"""
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rehearsal", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--rehearsal", "--full", "--steps", "2", "--warmup", "1", "--no-cpu-baseline"], capture_output=True, text=True,
+                       timeout=600, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]
     out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
     assert out["n_gpus"] == 1 and out["config"]["collective_backend"] is None and out["config"]["broadcast_ms"] == 0.0
     assert out["rehearsal"]["tokens_equal_unsharded"] and all(t["rehearsal"]["images_equal_unsharded"] for t in out["throughput"])
+
+
+def test_plain_line_measures_the_headline_alone():
+    """bench.py without --full: set-up, warm-up and timed steps of the headline, then the line -- no roofline pass, throughput workload, fast mode or CPU baseline"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1"], capture_output=True, text=True, timeout=600, cwd=ROOT)
+    assert r.returncode == 0, r.stderr[-3000:]
+    out = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+    assert out["value"] > 0 and out["unit"] == "images/sec" and out["higher_is_better"] is True and out["dtype"] == "f32"
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0 and out["config"]["submission"] == "hip-graph replay"
+    assert all(out[k] is None for k in ("roofline", "throughput", "fast_mode", "cpu_baseline", "best_256px_8step")), out
 
 
 def test_dump_outputs_repeat_and_equal_across_world_sizes(tmp_path):

@@ -8,7 +8,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${TAG}_profiles
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-COMMON="--no-cpu-baseline --no-extra --no-graph"
+COMMON="--full --no-cpu-baseline --no-extra --no-graph"  # --full: the image counts below include the roofline pass
 W_B1="python $R/bench.py"
 W_B32="python $R/bench.py --batch 32"
 W_B128="python $R/bench.py --batch 128"
@@ -97,5 +97,5 @@ bash $R/tools/two_rank_rehearsal.sh $TAG > /dev/null 2>&1; cp $R/gpurun_out/${TA
   python -m pytest tests/test_gpu_dist.py -q -s -p no:cacheprovider 2>&1 | grep "^[.F]*{\|passed\|failed" | sed 's/^[.F]*//'; } > $O/${TAG}_rccl_world1.txt
 # the headline line with in-date traffic: the traffic files of THIS run go where bench.py looks for them
 cp $O/${TAG}_pmc_traffic_*.json $R/profiles/ 2>/dev/null
-python bench.py 2> $O/log_bench_line.txt | tail -1 > $O/${TAG}_bench_line.json
+python bench.py --full 2> $O/log_bench_line.txt | tail -1 > $O/${TAG}_bench_line.json
 ls -la $O

@@ -2,9 +2,10 @@
 
 On a GPU box (counters in passes of their own, kernel-trace only -- see the guide's HBM / rocprofv3 section):
     cd /tmp && export TMPDIR=/tmp
-    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format rocpd -d $R/gpurun_out/pmc_fetch -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra --no-graph
-    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format rocpd -d $R/gpurun_out/pmc_write -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-extra --no-graph
-    python $R/tools/pmc_traffic.py $R/gpurun_out/pmc_fetch $R/gpurun_out/pmc_write $R/gpurun_out/r02_pmc_traffic.json
+    rocprofv3 --kernel-trace --pmc FETCH_SIZE --output-format rocpd -d $O/pmc_fetch -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra --no-graph
+    rocprofv3 --kernel-trace --pmc WRITE_SIZE --output-format rocpd -d $O/pmc_write -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-extra --no-graph
+    python $R/tools/pmc_traffic.py $O/pmc_fetch $O/pmc_write $O/rNN_pmc_traffic.json
+($R = the repository root, $O = any output directory; tools/collect_profiles.sh runs these passes for every workload.)
 The file is stamped with the hash of the kernel sources it was measured on; bench.py refuses a file whose stamp differs."""
 import glob
 import json
@@ -44,7 +45,7 @@ def main():
     f_kb, n_f = counter_avg(fetch_dir, "FETCH_SIZE", "gemm_nt_kernel")
     w_kb, n_w = counter_avg(write_dir, "WRITE_SIZE", "gemm_nt_kernel")
     hbm = (2.0 * f_kb + w_kb) * 1024.0
-    j = {"command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE (and a separate pass --pmc WRITE_SIZE) -- python bench.py%s --steps N --warmup 1 --no-cpu-baseline --no-extra --no-graph" % extra,
+    j = {"command": "rocprofv3 --kernel-trace --pmc FETCH_SIZE (and a separate pass --pmc WRITE_SIZE) -- python bench.py%s --full --steps N --warmup 1 --no-cpu-baseline --no-extra --no-graph" % extra,
          "workload": {"model": model, "batch_per_gpu": batch, "grid": grid, "sample_steps": sample_steps},
          "source_stamp": bench.source_stamp(), "stamped_sources": bench.TRAFFIC_SOURCES,
          "kernel": "gemm_nt_kernel (all instantiations)", "launches_profiled": n_f,

@@ -12,7 +12,7 @@ db() { find $1 -name "*.db" 2>/dev/null | head -1; }
 run() {  # name, counters, steps, more flags...
     local name=$1 ctr=$2 steps=$3; shift 3
     rm -rf $O/tmp_$name
-    rocprofv3 --kernel-trace --pmc $ctr --output-format rocpd -d $O/tmp_$name -- python $R/bench.py --model 1b --s-byt5 256 --clip-image 1 --sample-steps $steps "$@" --steps 1 --warmup 0 --no-cpu-baseline --no-extra --no-graph --no-roofline > $O/log_$name.txt 2>&1
+    rocprofv3 --kernel-trace --pmc $ctr --output-format rocpd -d $O/tmp_$name -- python $R/bench.py --model 1b --s-byt5 256 --clip-image 1 --sample-steps $steps "$@" --full --steps 1 --warmup 0 --no-cpu-baseline --no-extra --no-graph --no-roofline > $O/log_$name.txt 2>&1
 }
 one() {  # share name, batch, grid, more flags
     local share=$1 b=$2 g=$3 more=$4
@@ -22,7 +22,7 @@ one() {  # share name, batch, grid, more flags
     run w_$share WRITE_SIZE $steps --batch $b --grid $g $more
     python $R/tools/pmc_traffic.py $O/tmp_f_$share $O/tmp_w_$share $O/${TAG}_pmc_traffic_$share.json $b $g 12 1b "--s-byt5 256 --clip-image 1 $more --no-roofline (profiled at --sample-steps $steps)" > $O/log_pmc_traffic_$share.txt 2>&1
     run m_$share "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES" $steps --batch $b --grid $g $more
-    { echo "# rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES -- python bench.py --model 1b --s-byt5 256 --clip-image 1 --batch $b --grid $g --sample-steps $steps $more --steps 1 --warmup 0 --no-cpu-baseline --no-extra --no-graph --no-roofline ; python tools/pmc_summary.py <db> gemm_nt_kernel   (and attention_lds_kernel)"
+    { echo "# rocprofv3 --kernel-trace --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES -- python bench.py --model 1b --s-byt5 256 --clip-image 1 --batch $b --grid $g --sample-steps $steps $more --full --steps 1 --warmup 0 --no-cpu-baseline --no-extra --no-graph --no-roofline ; python tools/pmc_summary.py <db> gemm_nt_kernel   (and attention_lds_kernel)"
       echo "# per-launch averages; matrix-core utilisation = SQ_VALU_MFMA_BUSY_CYCLES / (4 SIMDs x SQ_BUSY_CU_CYCLES)"
       python $R/tools/pmc_summary.py $(db $O/tmp_m_$share) gemm_nt_kernel; python $R/tools/pmc_summary.py $(db $O/tmp_m_$share) attention_lds_kernel; } > $O/${TAG}_pmc_mfma_busy_$share.txt 2>&1
     rm -rf $O/tmp_f_$share $O/tmp_w_$share $O/tmp_m_$share

@@ -3,7 +3,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out/${TAG}_profiles
 mkdir -p $O
 cd /tmp && export TMPDIR=/tmp
-COMMON="--no-cpu-baseline --no-extra --no-graph"
+COMMON="--full --no-cpu-baseline --no-extra --no-graph"
 db() { find $1 -name "*.db" | head -1; }
 trace() {
     local name=$1 images=$2; shift 2

@@ -5,7 +5,7 @@ TAG=${1:-r06}
 R=${GRAFT_REPO_ROOT:-$(pwd)}
 O=$R/gpurun_out
 mkdir -p $O
-CMD="python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 $R/bench.py --gpus 2 --rehearsal --dist-backend gloo --share-device --steps 2 --warmup 1 --no-cpu-baseline"
+CMD="python -m torch.distributed.run --nnodes=1 --nproc-per-node 2 --master-addr 127.0.0.1 --master-port 29533 $R/bench.py --gpus 2 --rehearsal --dist-backend gloo --share-device --full --steps 2 --warmup 1 --no-cpu-baseline"
 { echo "# $CMD   (MI355X, ONE device shared by two ranks; TEST ONLY -- exercises every rank != 0 / world > 1 branch, not a measurement)"
   $CMD 2> $O/log_two_rank_rehearsal.txt | grep '^{'
   echo "# the same with --inject-setup-failure 1: every throughput workload must come back as an error entry on rank 0, no hang"
