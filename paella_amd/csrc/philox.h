@@ -35,15 +35,19 @@ __device__ __forceinline__ float u01_half_open(uint32_t bits) { return (float)(b
 
 // Categorical draw in the log domain (Gumbel-max): token = argmax_i (x_i - log q_i), q ~ Exp(1), i.e. log q = log(-log u).
 // == argmax softmax(x) / q == torch.multinomial(softmax(x), 1) in distribution; no exp, no division, no row max needed.
-// (hardware log2 for both logarithms: this runs once per LOGIT, 8192 x positions x steps, inside the head GEMM's epilogue)
+// Each logarithm lowers to v_log_f32 (log2) behind a denormal rescale, times ln 2 as a two-part product: about 2 ulp per logarithm,
+// a relative error that holds as u -> 1 as well (tests/test_gpu_counter_noise.py measures it against fp64 over 2^27 draws).  This runs
+// once per LOGIT, 8192 x positions x steps, inside the head GEMM's epilogue.
 __device__ __forceinline__ float log_exp1(uint32_t bits) { return __logf(-__logf(u01_open(bits))); }
-// The score both tails maximise in the counter-based mode.  ONE definition: the fused (GEMM epilogue) and unfused (tail kernel)
-// paths must round identically.  contract(off): no FMA may merge the division's multiply-free result with the subtraction.
+// The score both tails maximise in the counter-based mode: fp32(logit * inv_temperature - log_q), ONE rounding.  ONE definition: the fused
+// (GEMM epilogue) and unfused (tail kernel) paths must round identically, so the fma is written out rather than left to contraction
+// (__fmul_rn / __fsub_rn are plain operators in the HIP headers, out of reach of an including file's `#pragma clang fp contract(off)`:
+// the compiler fused them into this very fma in both tails).
 // inv_temperature = tail_inv_temperature(T), ONE correctly rounded division per thread instead of one per logit (the counter-based mode promises no bit parity with
 // torch's RNG stream, only fused == unfused, which share this function; the torch-noise parity mode keeps the reference's x / T, tail.hip).
 __device__ __forceinline__ float tail_inv_temperature(float temperature) { return __fdiv_rn(1.0f, temperature); }
 __device__ __forceinline__ float tail_score_gumbel(float logit, float inv_temperature, float log_q) {
-    return __fsub_rn(__fmul_rn(logit, inv_temperature), log_q);
+    return __builtin_fmaf(logit, inv_temperature, -log_q);
 }
 // first index wins ties (deterministic under any reduction order)
 __device__ __forceinline__ void argmax_update(float& best, int& best_i, float score, int idx) {

@@ -18,8 +18,10 @@
 
 #pragma clang fp contract(off)
 
+// two roundings, as torch's two ops: plain operators under this file's contract(off) (__fmul_rn / __fadd_rn are header functions the
+// pragma does not reach -- the score hook below had them fused into an fma)
 __device__ __forceinline__ float mix_logit(float lc, float lu, float cfg, float omc, bool has_u) {
-    return has_u ? __fadd_rn(__fmul_rn(lc, cfg), __fmul_rn(lu, omc)) : lc;
+    return has_u ? lc * cfg + lu * omc : lc;
 }
 
 // renoise (src/utils.py:54 -> src/modules.py:277-283 with random_x = init_noise): u <= t_next ? init_noise : token

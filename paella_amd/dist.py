@@ -95,8 +95,9 @@ def cond_spec_layout(model, B, S_byt5=0, S_byt5_uncond=None, clip=True, n_clip_i
 
 
 def _pack_seed(seed, device):
-    """An int64 seed as two fp32 words (bit pattern preserved): it rides at the end of the flat conditioning buffer."""
-    return torch.tensor([int(seed)], dtype=torch.int64).view(torch.float32).to(device)
+    """A 64-bit seed as two fp32 words (bit pattern preserved): it rides at the end of the flat conditioning buffer."""
+    from .sampling import seed_word
+    return torch.tensor([seed_word(seed)], dtype=torch.int64).view(torch.float32).to(device)
 
 
 def broadcast_conditioning(input_sets, src=0, device=None, group=None, layout=None, seed=None, with_seed=False, seed_on_device=False, validate=None,

@@ -91,6 +91,13 @@ def fresh_seed():
     return int(torch.randint(0, 2 ** 62, (1,), dtype=torch.int64).item())
 
 
+def seed_word(seed):
+    """The int64 with the bit pattern of a 64-bit seed: what a device-resident seed word holds (the kernels read it as uint64), so seeds
+    with bit 63 set fit an int64 tensor."""
+    s = int(seed) & 0xFFFFFFFFFFFFFFFF
+    return s - (1 << 64) if s >> 63 else s
+
+
 def start_tokens(num_labels, shape, seed, device, shard=None, out=None, seed_dev=None, row_offset_dev=None):
     """The start tokens of the counter-based noise mode (the reference draws torch.randint on the global generator,
     src/utils.py:37 -- a stream that cannot be sharded): token i of the GLOBAL [total, H, W] grid is Philox(seed, i) mod
@@ -433,7 +440,7 @@ class GraphSampler:
             if lo < 0 or lo + self.shape[0] > total:
                 raise ValueError("shard=(lo, total): rows [lo, lo + %d) must lie inside the global batch" % self.shape[0])
         self.row_offset_dev.fill_(lo * self.shape[1] * self.shape[2])
-        self.seed_dev.fill_(int(seed))
+        self.seed_dev.fill_(seed_word(seed))
 
     def __call__(self, model_inputs=None, unconditional_inputs=None, seed=None, shard=None):
         """Replay. Returns tokens (and the decoded image if a VQGAN was given); outputs live in graph-owned buffers that
