@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PAELLA_ABI_VERSION 5
+#define PAELLA_ABI_VERSION 6
 
 #define PAELLA_OK 0
 #define PAELLA_ERR_ARG -1       /* invalid argument / unsupported shape */
@@ -179,6 +179,38 @@ int paella_sample_tail_ex(const float* logits_c, const float* logits_u, int64_t 
  * n = (hi - lo) * H * W and obtains exactly its slice of the unsharded draw.  Either pointer may be NULL. */
 int paella_start_tokens(uint64_t seed, const uint64_t* seed_ptr, int64_t row_offset, const int64_t* row_offset_ptr,
                         int num_labels, int64_t n, int64_t* tokens_out, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Request batch (ABI 6): the B samples of one call are B independent REQUESTS, each with its own seed, guidance pair and
+ * temperature, read per step from DEVICE tables -- a captured graph serves any mix of them by rewriting the tables:
+ *   seeds        uint64 [B]     (an int64 tensor holding the bit patterns)
+ *   temperature  fp32   [B]     this step's row of a [steps, B] table; every entry > 0 (not checked on the device: the
+ *                               caller validates; the argmax extension is not offered per request)
+ *   pairs        fp32   [B, 2]  this step's (cfg, 1 - cfg), rounded by the caller as for the scalar entry points
+ * Sample b = row / rows_per_sample draws exactly what the scalar entry point draws for it ALONE: seed = seeds[b],
+ * row_offset = 0, rows = rows_per_sample, its own scalars -- counters are built from the position inside the sample,
+ * never from the global row, so the result does not depend on the slot or on the batch-mates.  Categorical mode and
+ * in-kernel Philox noise only.  The scalar entry points above keep their signatures and their tokens.
+ * ---------------------------------------------------------------------------------------------- */
+/* paella_sample_tail_ex per request; cfg_pairs may be NULL (no guidance: logits_u ignored as when it is NULL). */
+int paella_sample_tail_req(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs,
+                           const float* temperature, const uint64_t* seeds, int rows_per_sample, uint64_t offset,
+                           const int64_t* init_noise, float t_next, int64_t* tokens_out, int64_t* sampled_out, void* stream);
+/* paella_start_tokens per request: tokens_out[b * rows_per_sample + p] = the start token p of seeds[b]. */
+int paella_start_tokens_req(const uint64_t* seeds, int B, int rows_per_sample, int num_labels, int64_t* tokens_out, void* stream);
+/* paella_unet_forward_shared with one guidance pair per sample: mix_pairs [n_unique, 2] (required, B == 2 * n_unique);
+ * logits_out holds the n_unique mixed rows.  A pair (1, 0) reproduces the conditional logits exactly only while the
+ * unconditional activations are finite (0 * inf = NaN). */
+int paella_unet_forward_shared_req(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                   const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
+                                   float* logits_out, void* ws, size_t ws_bytes, void* stream);
+/* paella_unet_forward_sample per request: mix_pairs [n_unique, 2] with B == 2 * n_unique, or NULL (no guidance,
+ * n_unique == B); rows_per_sample must equal H * W.  Tokens are bit-identical to forward_shared_req + sample_tail_req. */
+int paella_unet_forward_sample_req(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                   const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
+                                   const uint64_t* seeds, const float* temperature, int rows_per_sample, uint64_t offset,
+                                   const int64_t* init_noise, float t_next, int64_t* tokens_out, void* ws, size_t ws_bytes,
+                                   void* stream);
 
 /* x, random_x, mask int64 [B, per_sample]; t fp32 [B].  mask_in NULL -> mask = (u <= t[b]) with u = rand_u
  * (caller noise, [B, per_sample]) or Philox; random_x NULL -> Philox randint(0, num_labels). */

@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libpaella_hip.so")
 
 MAX_LEVELS = 8
 MAX_BLOCK_TYPES = 8
-ABI_VERSION = 5
+ABI_VERSION = 6
 
 
 class UnetConfig(Structure):
@@ -65,6 +65,13 @@ SIGNATURES = {
     "paella_sample_tail_ex": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_float, c_float, c_int, c_void_p,
                                       c_uint64, c_void_p, c_uint64, c_int64, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
     "paella_start_tokens": (c_int, [c_uint64, c_void_p, c_int64, c_void_p, c_int, c_int64, c_void_p, c_void_p]),
+    "paella_sample_tail_req": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_uint64, c_void_p, c_float, c_void_p, c_void_p,
+                                       c_void_p]),
+    "paella_start_tokens_req": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p, c_void_p]),
+    "paella_unet_forward_shared_req": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                                               c_void_p, c_size_t, c_void_p]),
+    "paella_unet_forward_sample_req": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_void_p,
+                                               c_void_p, c_int, c_uint64, c_void_p, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
     "paella_add_noise": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_uint64, c_uint64, c_int, c_int,
                                  c_int64, c_void_p, c_void_p, c_void_p]),
     "paella_select_tokens": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int64, c_void_p, c_void_p]),
@@ -120,6 +127,7 @@ TEST_HOOKS = {
     "paella_test_mlp_grn_fused": (c_int, [c_void_p] * 10 + [c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "paella_test_gemm_tail_tile": (c_int, [c_int]),
     "paella_test_tail_scores": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_float, c_float, c_uint64, c_uint64, c_int64, c_void_p, c_void_p]),
+    "paella_test_tail_scores_req": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_uint64, c_void_p, c_void_p]),
     "paella_test_gemm_prologue": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
                                           c_void_p, c_size_t, c_void_p]),
 }

@@ -118,6 +118,18 @@ struct FusedTail {
     int* part_idx;               // [M, tiles_n]
 };
 
+// Request batch (the REQ forms of the tail kernels and of the TAIL instantiations of gemm_nt_kernel): the rows are B independent requests of rows_per_sample
+// positions each, and what the scalar forms take by value comes per SAMPLE from device tables -- a captured graph serves any mix of seeds, guidance scales
+// and temperatures by rewriting them.  Row m belongs to request b = m / rows_per_sample and draws what that request draws when it is sampled alone:
+// key seeds[b], counters from the position p = m - b * rows_per_sample INSIDE the sample (no global row, no row offset).
+struct ReqTables {
+    const uint64_t* seeds = nullptr;     // [B] 64-bit seeds
+    const float* temperature = nullptr;  // [B] this step's temperatures, each > 0 (1 / T by tail_inv_temperature, as the scalar forms)
+    const float* cfg_pairs = nullptr;    // [B, 2] this step's (cfg, 1 - cfg), or null (the tail kernels' own mix of logits_c / logits_u only)
+    int rows_per_sample = 0;             // > 0 selects the request form
+    FastDiv rps_div = {0u, 0u, 0xffffffffu};  // division by rows_per_sample (filled by the launchers)
+};
+
 // Implicit-GEMM convolution (VQGAN k4 s2 p1 Conv2d / the 4 output phases of the k4 s2 p1 ConvTranspose2d, reference src/vqgan.py:59-61,
 // 81-85): the A operand is never materialised.  Row m = output position (b, yo, xo) on a [Ho, Wo] grid, K index = tap * C + c,
 // A[m][tap*C + c] = x[b][yo*stride + oy(tap)][xo*stride + ox(tap)][c] (0 outside the [Hi, Wi] input grid), x = GemmArgs::A in NHWC.
@@ -162,6 +174,7 @@ struct GemmArgs {
     // K % 64 == 0, lda % 8 == 0, ldw % 8 == 0, no GRN prologue, no implicit convolution.  A / W are then unused (W may stay set for bookkeeping).
     const unsigned short* A16;
     const unsigned short* W16;
+    ReqTables rq;              // launch_gemm_tail only, rq.rows_per_sample > 0: the request form of the fused tail (ft.seed / temperature / row offsets unused).  LAST: no other field moves
 };
 
 // Launchers (each returns PAELLA_OK or an error code; all work is enqueued on `stream`).
@@ -240,6 +253,8 @@ int launch_silu(const float* x, float* y, int64_t n, hipStream_t stream);
 int launch_copy_rows(const float* src, int lds, float* dst, int ldd, int64_t rows, int cols, hipStream_t stream);
 int launch_axpby(float* x, const float* y, float a, float b, int64_t n, hipStream_t stream);  // x = a*x + b*y
 int launch_axpby16(float* x, const float* y, float a, float b, int64_t n, unsigned short* x16, hipStream_t stream);  // + optional bf16 copy of the result
+// request batch: x[s] = ab[s][0] * x[s] + ab[s][1] * y[s] over B samples of per_sample floats each, ab a DEVICE table [B, 2]; the same arithmetic per element
+int launch_axpby16_req(float* x, const float* y, const float* ab, int B, int64_t per_sample, unsigned short* x16, hipStream_t stream);
 
 // Attention over [self keys | conditioning keys] (reference src/modules.py:7-19,65-79;
 // utils/alter_attention.py:4-43). q/k/v are column blocks of row-major buffers.
@@ -275,11 +290,14 @@ struct TailArgs {
     float t_next;                 // uniform over the batch inside sample()
     int64_t* tokens_out;          // [rows]
     int64_t* sampled_out;         // [rows] pre-renoise draw (optional, may be null)
+    ReqTables rq;                 // rq.rows_per_sample > 0: request form (mode 0, Philox noise only; seed / cfg / temperature / row offsets above unused)
 };
 int launch_sample_tail(const TailArgs& a, hipStream_t stream);
 // start tokens of the counter-based mode: out[i] = Philox(seed (+ *seed_ptr), i + row_offset (+ *row_offset_ptr)) % num_labels
 int launch_start_tokens(uint64_t seed, const uint64_t* seed_ptr, int64_t row_offset, const int64_t* row_offset_ptr, int num_labels, int64_t n,
                         int64_t* out, hipStream_t stream);
+// request batch: out[b * rows_per_sample + p] = Philox(seeds[b], p) % num_labels -- what launch_start_tokens(seeds[b], ..., n = rows_per_sample) draws
+int launch_start_tokens_req(const uint64_t* seeds, int B, int rows_per_sample, int num_labels, int64_t* out, hipStream_t stream);
 
 // add_noise (reference src/modules.py:277-283)
 int launch_add_noise(const int64_t* x, const float* t, const int64_t* mask_in, const int64_t* random_x,

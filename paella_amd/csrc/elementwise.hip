@@ -521,6 +521,26 @@ __global__ __launch_bounds__(256) void axpby_kernel(float* __restrict__ x, const
         if (x16) st4h(x16 + i * 4, v);
     }
 }
+// request batch: the same mix with one (a, b) pair per SAMPLE from a device table (per4 quads per sample; blockIdx.y = sample)
+__global__ __launch_bounds__(256) void axpby_req_kernel(float* __restrict__ x, const float* __restrict__ y, const float* __restrict__ ab, int64_t per4, unsigned short* __restrict__ x16) {
+    const int s = blockIdx.y;
+    const float a = ab[2 * s], b = ab[2 * s + 1];
+    for (int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x; j < per4; j += (int64_t)gridDim.x * 256) {
+        const int64_t i = (int64_t)s * per4 + j;
+        const f32x4 v = ld4(x + i * 4) * a + ld4(y + i * 4) * b;
+        st4(x + i * 4, v);
+        if (x16) st4h(x16 + i * 4, v);
+    }
+}
+int launch_axpby16_req(float* x, const float* y, const float* ab, int B, int64_t per_sample, unsigned short* x16, hipStream_t st) {
+    if (B <= 0 || per_sample <= 0) return PAELLA_OK;
+    if (!ab || (per_sample & 3) || B > 65535) { paella_set_error("axpby_req: needs a pair table, per_sample %% 4 == 0 and at most 65535 samples"); return PAELLA_ERR_ARG; }
+    int64_t blocks = (per_sample / 4 + 255) / 256;
+    if (blocks > 1024) blocks = 1024;
+    hipLaunchKernelGGL(axpby_req_kernel, dim3((unsigned)blocks, (unsigned)B), dim3(256), 0, st, x, y, ab, per_sample / 4, x16);
+    LAUNCH_CHECK_RET();
+    return PAELLA_OK;
+}
 int launch_axpby(float* x, const float* y, float a, float b, int64_t n, hipStream_t st) { return launch_axpby16(x, y, a, b, n, nullptr, st); }
 int launch_axpby16(float* x, const float* y, float a, float b, int64_t n, unsigned short* x16, hipStream_t st) {
     if (n <= 0) return PAELLA_OK;

@@ -134,7 +134,7 @@ constexpr int ring_wg_per_cu(int WM, int WN, int TM, int TN, int APRO, int RING,
     return fit < wish ? (fit < 1 ? 1 : fit) : wish;
 }
 
-template <int WM, int WN, int TM, int TN, int PD, int APRO, bool TAIL = false, int BK = 32, bool DMA = false, int RING = 0, bool BF = false, int EPI = EPI_RUNTIME>  // BK: K step (32 or 64 floats per LDS row); APRO: 0 none, 1 GRN scale/shift, 2 LayerNorm from row statistics; TAIL: fused sampling tail (head GEMM);
+template <int WM, int WN, int TM, int TN, int PD, int APRO, bool TAIL = false, int BK = 32, bool DMA = false, int RING = 0, bool BF = false, int EPI = EPI_RUNTIME, bool REQ = false>  // REQ (TAIL only): request batch -- key, counter base and 1 / T per ROW from device tables (GemmArgs::rq); BK: K step (32 or 64 floats per LDS row); APRO: 0 none, 1 GRN scale/shift, 2 LayerNorm from row statistics; TAIL: fused sampling tail (head GEMM);
 // DMA: operands that need no transform (W always, A when APRO == 0) go global -> LDS directly (buffer_load ... lds), no staging registers, no ds_write pass
 // APRO 4 (ring tiles only): the GRN apply from the producer's UNFINISHED statistics -- a' = a * (1 + gamma * gx / (mean gx + 1e-6)) + shift, the mean
 // derived per workgroup from the producer's per-column-tile partial sums (no finalize launch between the two MLP GEMMs).
@@ -172,6 +172,7 @@ __global__ __launch_bounds__(64 * WM * WN, RING > 0 ? ring_wg_per_cu(WM, WN, TM,
     constexpr int LA = (BM * SL + NT - 1) / NT, LB = (BN * SL + NT - 1) / NT;
     constexpr int TILE_FLOATS = (BM + BN) * BK;
     static_assert(NW == 4 || NW == 8, "4 or 8 waves per workgroup");
+    static_assert(!REQ || TAIL, "the request form exists for the fused tail only");
     static_assert(PD == 1 || PD == 2, "prefetch ring depth 1 or 2");
     static_assert(BK == 32 || BK == 64, "K step of 32 or 64");
     static_assert(!BF || ((DMA || RING > 0) && (APRO == 0 || APRO == 2) && BK == 32), "bf16 operands: direct-to-LDS / ring variants, no operand transform");
@@ -665,6 +666,15 @@ __global__ __launch_bounds__(64 * WM * WN, RING > 0 ? ring_wg_per_cu(WM, WN, TM,
     float tlq[TAIL_AHEAD ? TM * TN : 1][4];
     int tlq_tile = -1;       // tile the drawn noise belongs to
     int tail_cur_tile = -1;  // tile being finished (set by flush)
+    // request form: row m (clamped into the matrix -- a tile may overhang it, the tables must not be read past their end) belongs to request b = m / rows_per_sample;
+    // its key is seeds[b], its counter row the position inside the sample.  One multiply-high per row per tile; returns b.
+    auto tail_req_row = [&](int m, uint64_t& rseed, int64_t& ctr_row) __attribute__((always_inline)) {
+        const int mc = min(m, g.M - 1);
+        const unsigned b = fast_div((unsigned)mc, g.rq.rps_div);
+        rseed = g.rq.seeds[b];
+        ctr_row = mc - (int)b * g.rq.rows_per_sample;
+        return b;
+    };
     auto tail_draw = [&](int tile) __attribute__((always_inline)) {
         if constexpr (TAIL_AHEAD) {
             if (g.ft.mode != 1) {
@@ -677,11 +687,14 @@ __global__ __launch_bounds__(64 * WM * WN, RING > 0 ? ring_wg_per_cu(WM, WN, TM,
 #pragma unroll
                 for (int i = 0; i < TM; ++i) {
                     const int m = tile_m * BM + (wm * TM + i) * 16 + r16;
+                    uint64_t rseed = seed;
+                    int64_t ctr_row = m + row_off;
+                    if constexpr (REQ) tail_req_row(m, rseed, ctr_row);
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
                         const int nn = tile_n * BN + (wn * TN + j) * 16 + kq * 4;
                         uint32_t rb[4];
-                        philox4x32(seed, (uint64_t)(m + row_off) * L4 + (nn >> 2), ft.offset, rb);
+                        philox4x32(rseed, (uint64_t)ctr_row * L4 + (nn >> 2), ft.offset, rb);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) tlq[i * TN + j][e] = log_exp1(rb[e]);
                     }
@@ -703,11 +716,14 @@ __global__ __launch_bounds__(64 * WM * WN, RING > 0 ? ring_wg_per_cu(WM, WN, TM,
             float* s_score = smem + FLAG_OFF + 16;
             int* s_idx = reinterpret_cast<int*>(s_score + BM * WN);
             const int tile_n_id = n0 / BN;
-            const float inv_t = tail_inv_temperature(ft.temperature);
+            float inv_t = REQ ? 0.f : tail_inv_temperature(ft.temperature);
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 const int mrow = (wm * TM + i) * 16 + r16;  // row inside the tile
                 const int m = m0 + mrow;
+                uint64_t rseed = seed;
+                int64_t ctr_row = m + row_off;
+                if constexpr (REQ) inv_t = tail_inv_temperature(g.rq.temperature[tail_req_row(m, rseed, ctr_row)]);
                 float best = -INFINITY;
                 int best_i = 0x7fffffff;
 #pragma unroll
@@ -726,7 +742,7 @@ __global__ __launch_bounds__(64 * WM * WN, RING > 0 ? ring_wg_per_cu(WM, WN, TM,
                                 for (int e = 0; e < 4; ++e) lq[e] = tlq[i * TN + j][e];  // (drawn ahead of the main loop: tail_draw)
                             } else {
                                 uint32_t rb[4];
-                                philox4x32(seed, (uint64_t)(m + row_off) * L4 + (nn >> 2), ft.offset, rb);
+                                philox4x32(rseed, (uint64_t)ctr_row * L4 + (nn >> 2), ft.offset, rb);
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) lq[e] = log_exp1(rb[e]);
                             }
@@ -2283,6 +2299,13 @@ int launch_gemm_tail(const GemmArgs& g_in, hipStream_t st) {
     GemmArgs g = g_in;
     g.a_rps_div = fast_div_of(1u);
     g.ep.rps_div = fast_div_of((unsigned)(g.ep.rows_per_sample > 0 ? g.ep.rows_per_sample : 1));
+    if (g.rq.rows_per_sample > 0) {  // request form: per-sample tables, rows are whole samples, categorical draw
+        if (!g.rq.seeds || !g.rq.temperature || g.M % g.rq.rows_per_sample || g.ft.mode != 0) {
+            paella_set_error("gemm_tail: the request form needs seed and temperature tables, M a multiple of rows_per_sample (%d) and the categorical mode", g.rq.rows_per_sample);
+            return PAELLA_ERR_ARG;
+        }
+        g.rq.rps_div = fast_div_of((unsigned)g.rq.rows_per_sample);
+    }
     return prof_bracket(g, st, false, [&]() { return launch_gemm_tail_impl(g, st); });  // (no logits are stored: M*N bytes not counted)
 }
 static int launch_gemm_tail_impl(const GemmArgs& g, hipStream_t st) {
@@ -2318,11 +2341,18 @@ static int launch_gemm_tail_impl(const GemmArgs& g, hipStream_t st) {
     // tiles that run together share an activation panel -- the whole activation matrix crosses the fabric once per column tile (34 GB per launch at configs[2])
     const int raster_gm = g_gemm_raster_gm;
     p.gm = (raster_gm > 0 && BM >= 64 && p.tiles_m >= 4 * raster_gm && p.tiles_n >= 4) ? raster_gm : p.tiles_m;
-    if (bf) hipLaunchKernelGGL((gemm_nt_kernel<2, 2, 2, 2, 1, 0, true, 32, true, 0, true>), dim3((unsigned)G), dim3(256), 0, st, g, p, (float*)nullptr, (unsigned*)nullptr, 0u);
-    else if (cfg == 9) hipLaunchKernelGGL((gemm_nt_kernel<4, 2, 2, 4, 1, 0, true>), dim3((unsigned)G), dim3(512), 0, st, g, p, (float*)nullptr, (unsigned*)nullptr, 0u);
-    else if (cfg == 14) hipLaunchKernelGGL((gemm_nt_kernel<4, 2, 2, 2, 2, 0, true>), dim3((unsigned)G), dim3(512), 0, st, g, p, (float*)nullptr, (unsigned*)nullptr, 0u);
-    else if (cfg == 18 && g.K % 32 == 0 && g_gemm_dma) hipLaunchKernelGGL((gemm_nt_kernel<2, 2, 2, 2, 1, 0, true, 32, true>), dim3((unsigned)G), dim3(256), 0, st, g, p, (float*)nullptr, (unsigned*)nullptr, 0u);
-    else hipLaunchKernelGGL((gemm_nt_kernel<2, 2, 2, 2, 2, 0, true>), dim3((unsigned)G), dim3(256), 0, st, g, p, (float*)nullptr, (unsigned*)nullptr, 0u);
+    // the same five tiles in the scalar and in the request form (REQ, the last template argument): a compile-time variant, the scalar instantiations keep their code
+#define TAIL_LAUNCH(THREADS, ...)                                                                                                                               \
+    do {                                                                                                                                                        \
+        if (g.rq.rows_per_sample > 0) hipLaunchKernelGGL((gemm_nt_kernel<__VA_ARGS__, EPI_RUNTIME, true>), dim3((unsigned)G), dim3(THREADS), 0, st, g, p, (float*)nullptr, (unsigned*)nullptr, 0u); \
+        else hipLaunchKernelGGL((gemm_nt_kernel<__VA_ARGS__>), dim3((unsigned)G), dim3(THREADS), 0, st, g, p, (float*)nullptr, (unsigned*)nullptr, 0u);                                            \
+    } while (0)
+    if (bf) TAIL_LAUNCH(256, 2, 2, 2, 2, 1, 0, true, 32, true, 0, true);
+    else if (cfg == 9) TAIL_LAUNCH(512, 4, 2, 2, 4, 1, 0, true, 32, false, 0, false);
+    else if (cfg == 14) TAIL_LAUNCH(512, 4, 2, 2, 2, 2, 0, true, 32, false, 0, false);
+    else if (cfg == 18 && g.K % 32 == 0 && g_gemm_dma) TAIL_LAUNCH(256, 2, 2, 2, 2, 1, 0, true, 32, true, 0, false);
+    else TAIL_LAUNCH(256, 2, 2, 2, 2, 2, 0, true, 32, false, 0, false);
+#undef TAIL_LAUNCH
     LAUNCH_CHECK_RET();
     return PAELLA_OK;
 }

@@ -872,7 +872,8 @@ extern "C" int paella_unet_forward(paella_unet* m, const int64_t* tokens, const 
 // the sampled tokens of the B (or, with the guidance mix, n_unique) output rows); logits_out is then unused.
 static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                              float mix_c, float mix_u, int H, int W, int S, const float* attn_weights,
-                             int n_attn_weights, float* logits_out, const TailArgs* tail, void* ws, size_t ws_bytes, void* stream) {
+                             int n_attn_weights, float* logits_out, const TailArgs* tail, void* ws, size_t ws_bytes, void* stream,
+                             const float* mix_pairs = nullptr) {  // request batch: a DEVICE table [n_unique, 2] of guidance pairs instead of (mix_c, mix_u)
     if (!m || !m->finalized) { paella_set_error("model not finalized"); return PAELLA_ERR_STATE; }
     if (!tokens || !r || (!logits_out && !tail)) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
     const paella_unet_config& c = m->cfg;
@@ -895,7 +896,7 @@ static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float*
     for (size_t i = 0; i < m->down.size(); ++i)
         if (m->down[i].type == BT_ATTN) { split = (int)i; break; }
     if (n_unique <= 0 || n_unique > B || B % n_unique) { paella_set_error("n_unique must divide B"); return PAELLA_ERR_ARG; }
-    const bool mix = mix_c != 0.f || mix_u != 0.f;
+    const bool mix = mix_pairs || mix_c != 0.f || mix_u != 0.f;
     if (mix && B != 2 * n_unique) { paella_set_error("guidance mix needs B == 2 * n_unique"); return PAELLA_ERR_ARG; }
     const int Bfull = B;
     if (n_unique < B) {  // tokens / r hold the n_unique distinct rows: the prefix runs on them only
@@ -1022,7 +1023,8 @@ static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float*
         else RET_IF(launch_layernorm(f.g, f.h, nt, c.c_out, 1e-6f, 1.f, 0.f, 0, 0, 0, st));
         if (mix) {  // the head is linear and bias-free: mix its input instead of its output
             nt /= 2;
-            RET_IF(launch_axpby16(f.h, f.h + (size_t)nt * c.c_out, mix_c, mix_u, nt * c.c_out, wh16 ? f.h16 : nullptr, st));
+            if (mix_pairs) RET_IF(launch_axpby16_req(f.h, f.h + (size_t)nt * c.c_out, mix_pairs, n_unique, (int64_t)H * W * c.c_out, wh16 ? f.h16 : nullptr, st));
+            else RET_IF(launch_axpby16(f.h, f.h + (size_t)nt * c.c_out, mix_c, mix_u, nt * c.c_out, wh16 ? f.h16 : nullptr, st));
         }
         GemmArgs go = gemm_args(f.h, c.c_out, T(m, "out_mapper.1.weight"), c.c_out, logits_out, c.num_labels, (int)nt, c.num_labels, c.c_out);
         if (wh16) { go.A16 = f.h16; go.W16 = wh16; }
@@ -1039,6 +1041,7 @@ static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float*
             go.C = nullptr;
             go.ft.temperature = tail->temperature; go.ft.mode = tail->mode; go.ft.seed = tail->seed; go.ft.seed_ptr = tail->seed_ptr;
             go.ft.offset = tail->offset; go.ft.row_offset = tail->row_offset; go.ft.row_offset_ptr = tail->row_offset_ptr;
+            go.rq = tail->rq;
             go.ft.part_score = f.g;
             go.ft.part_idx = reinterpret_cast<int*>(f.g + (size_t)nt * tn);
             RET_IF(launch_gemm_tail(go, st));
@@ -1076,6 +1079,45 @@ extern "C" int paella_unet_forward_sample(paella_unet* m, const int64_t* tokens,
     a.offset = offset; a.row_offset = row_offset; a.row_offset_ptr = row_offset_ptr; a.init_noise = init_noise; a.mask_u = nullptr; a.t_next = t_next;
     a.tokens_out = tokens_out; a.sampled_out = nullptr;
     return unet_forward_impl(m, tokens, r, cond, B, n_unique, mix_c, mix_u, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream);
+}
+
+// Request batch (ABI 6): the same two entry points with per-sample device tables (common.h: ReqTables).
+extern "C" int paella_unet_forward_shared_req(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                              const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
+                                              float* logits_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!logits_out || !mix_pairs) { paella_set_error("forward_shared_req: null argument (logits_out / mix_pairs)"); return PAELLA_ERR_ARG; }
+    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, logits_out, nullptr, ws, ws_bytes, stream, mix_pairs);
+}
+
+extern "C" int paella_unet_forward_sample_req(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                              const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
+                                              const uint64_t* seeds, const float* temperature, int rows_per_sample, uint64_t offset,
+                                              const int64_t* init_noise, float t_next, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!tokens_out || !seeds || !temperature) { paella_set_error("forward_sample_req: null argument (tokens_out / seeds / temperature)"); return PAELLA_ERR_ARG; }
+    if (!mix_pairs && n_unique != B) { paella_set_error("forward_sample_req without guidance pairs needs n_unique == B"); return PAELLA_ERR_ARG; }
+    if (H <= 0 || W <= 0 || rows_per_sample != H * W) { paella_set_error("forward_sample_req: rows_per_sample (%d) must equal H * W", rows_per_sample); return PAELLA_ERR_ARG; }
+    TailArgs a = {};
+    a.rows = (int64_t)(mix_pairs ? n_unique : B) * H * W;
+    a.L = m ? m->cfg.num_labels : 0;
+    a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f; a.offset = offset; a.init_noise = init_noise; a.t_next = t_next; a.tokens_out = tokens_out;
+    a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.rows_per_sample = rows_per_sample;  // (the guidance pairs ride through the head: none left for the tail)
+    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, mix_pairs);
+}
+
+extern "C" int paella_sample_tail_req(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
+                                      const uint64_t* seeds, int rows_per_sample, uint64_t offset, const int64_t* init_noise, float t_next,
+                                      int64_t* tokens_out, int64_t* sampled_out, void* stream) {
+    if (!logits_c || !tokens_out || !seeds || !temperature) { paella_set_error("sample_tail_req: null argument"); return PAELLA_ERR_ARG; }
+    if (rows_per_sample <= 0) { paella_set_error("sample_tail_req: rows_per_sample must be > 0"); return PAELLA_ERR_ARG; }
+    TailArgs a = {};
+    a.logits_c = logits_c; a.logits_u = cfg_pairs ? logits_u : nullptr; a.rows = rows; a.L = L; a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f;
+    a.offset = offset; a.init_noise = init_noise; a.t_next = t_next; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
+    a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.cfg_pairs = cfg_pairs; a.rq.rows_per_sample = rows_per_sample;
+    return launch_sample_tail(a, (hipStream_t)stream);
+}
+
+extern "C" int paella_start_tokens_req(const uint64_t* seeds, int B, int rows_per_sample, int num_labels, int64_t* tokens_out, void* stream) {
+    return launch_start_tokens_req(seeds, B, rows_per_sample, num_labels, tokens_out, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------

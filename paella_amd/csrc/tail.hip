@@ -27,14 +27,15 @@ __device__ __forceinline__ float mix_logit(float lc, float lu, float cfg, float 
 // renoise (src/utils.py:54 -> src/modules.py:277-283 with random_x = init_noise): u <= t_next ? init_noise : token
 __device__ __forceinline__ int64_t tail_row_offset(const TailArgs& a) { return a.row_offset + (a.row_offset_ptr ? *a.row_offset_ptr : 0); }
 
-__device__ __forceinline__ int64_t renoise_token(const TailArgs& a, uint64_t seed, int64_t row, int64_t tok) {
+// ctr_row: the row the Philox counter is built from -- the GLOBAL row (row + row offset), or in the request form the position inside the sample
+__device__ __forceinline__ int64_t renoise_token(const TailArgs& a, uint64_t seed, int64_t row, int64_t ctr_row, int64_t tok) {
     if (a.init_noise) {
         float u;
         if (a.mask_u) {
             u = a.mask_u[row];
         } else {
             uint32_t rb[4];
-            philox4x32(seed ^ 0x5bd1e9955bd1e995ull, (uint64_t)(row + tail_row_offset(a)), a.offset, rb);
+            philox4x32(seed ^ 0x5bd1e9955bd1e995ull, (uint64_t)ctr_row, a.offset, rb);
             u = u01_half_open(rb[0]);
         }
         if (u <= a.t_next) tok = a.init_noise[row];
@@ -42,6 +43,28 @@ __device__ __forceinline__ int64_t renoise_token(const TailArgs& a, uint64_t see
     return tok;
 }
 
+// What a row draws with.  Scalar form: the launch's seed (+ device word), counters from the global row, the launch's cfg pair and temperature.
+// Request form (REQ): everything from the tables of the row's request b = row / rows_per_sample, counters from the position inside the sample.
+struct RowKey { uint64_t seed; int64_t ctr_row; float cfg, omc, temperature; };
+template <bool REQ>
+__device__ __forceinline__ RowKey tail_row_key(const TailArgs& a, int64_t row) {
+    RowKey k;
+    if constexpr (REQ) {
+        const unsigned b = fast_div((unsigned)row, a.rq.rps_div);
+        k.seed = a.rq.seeds[b];
+        k.ctr_row = row - (int64_t)b * a.rq.rows_per_sample;
+        k.cfg = a.rq.cfg_pairs ? a.rq.cfg_pairs[2 * b] : 1.f;
+        k.omc = a.rq.cfg_pairs ? a.rq.cfg_pairs[2 * b + 1] : 0.f;
+        k.temperature = a.rq.temperature[b];
+    } else {
+        k.seed = a.seed + (a.seed_ptr ? *a.seed_ptr : 0ull);
+        k.ctr_row = row + tail_row_offset(a);
+        k.cfg = a.cfg; k.omc = a.one_minus_cfg; k.temperature = a.temperature;
+    }
+    return k;
+}
+
+template <bool REQ>
 __global__ __launch_bounds__(256) void sample_tail_kernel(TailArgs a) {
     __shared__ float red_v[4];
     __shared__ int red_i[4];
@@ -52,9 +75,9 @@ __global__ __launch_bounds__(256) void sample_tail_kernel(TailArgs a) {
     const float* lu = a.logits_u ? a.logits_u + row * L : nullptr;
     const bool has_u = lu != nullptr;
     const bool argmax_mode = a.mode == 1;
-    const uint64_t seed = a.seed + (a.seed_ptr ? *a.seed_ptr : 0ull);
+    const RowKey rk = tail_row_key<REQ>(a, row);
+    const uint64_t seed = rk.seed;
     const float* nq = a.noise_q ? a.noise_q + row * L : nullptr;
-    const int64_t row_off = tail_row_offset(a);
 
     // pass 1 (explicit-noise parity mode only): max of x = mix / T for the softmax numerator exp(x - max).
     // The argmax and the counter-based mode never need it: argmax(x - log q) is invariant to a per-row shift.
@@ -65,7 +88,7 @@ __global__ __launch_bounds__(256) void sample_tail_kernel(TailArgs a) {
             const f32x4 c = *reinterpret_cast<const f32x4*>(lc + i4 * 4);
             const f32x4 u = has_u ? *reinterpret_cast<const f32x4*>(lu + i4 * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-            for (int e = 0; e < 4; ++e) mx = fmaxf(mx, __fdiv_rn(mix_logit(c[e], u[e], a.cfg, a.one_minus_cfg, has_u), a.temperature));
+            for (int e = 0; e < 4; ++e) mx = fmaxf(mx, __fdiv_rn(mix_logit(c[e], u[e], rk.cfg, rk.omc, has_u), rk.temperature));
         }
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) mx = fmaxf(mx, __shfl_xor(mx, o, 64));
@@ -76,7 +99,7 @@ __global__ __launch_bounds__(256) void sample_tail_kernel(TailArgs a) {
     }
 
     // pass 2: best score (first index wins ties)
-    const float inv_t = tail_inv_temperature(a.temperature);  // counter-based mode (philox.h: tail_score_gumbel)
+    const float inv_t = tail_inv_temperature(rk.temperature);  // counter-based mode (philox.h: tail_score_gumbel)
     float best = -INFINITY;
     int best_i = 0x7fffffff;
     for (int i4 = tid; i4 < L4; i4 += 256) {
@@ -88,19 +111,19 @@ __global__ __launch_bounds__(256) void sample_tail_kernel(TailArgs a) {
                 q = *reinterpret_cast<const f32x4*>(nq + i4 * 4);
             } else {
                 uint32_t rb[4];
-                philox4x32(seed, (uint64_t)(row + row_off) * L4 + i4, a.offset, rb);
+                philox4x32(seed, (uint64_t)rk.ctr_row * L4 + i4, a.offset, rb);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) q[e] = log_exp1(rb[e]);
             }
         }
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            float x = mix_logit(c[e], u[e], a.cfg, a.one_minus_cfg, has_u);
+            float x = mix_logit(c[e], u[e], rk.cfg, rk.omc, has_u);
             float score;
             if (argmax_mode) {
                 score = x;
             } else if (nq) {  // parity mode: the reference's arithmetic, softmax numerator over Exp(1) noise
-                x = __fdiv_rn(x, a.temperature);
+                x = __fdiv_rn(x, rk.temperature);
                 score = __fdiv_rn(expf(__fsub_rn(x, mx)), q[e]);
             } else {          // counter-based noise: the same draw in the log domain (Gumbel-max); identical arithmetic in the
                 score = tail_score_gumbel(x, inv_t, q[e]);  // head GEMM's fused tail epilogue (gemm.hip)
@@ -121,13 +144,14 @@ __global__ __launch_bounds__(256) void sample_tail_kernel(TailArgs a) {
         if (best_i == 0x7fffffff) best_i = 0;  // all-NaN row
         int64_t tok = best_i;
         if (a.sampled_out) a.sampled_out[row] = tok;
-        a.tokens_out[row] = renoise_token(a, seed, row, tok);
+        a.tokens_out[row] = renoise_token(a, seed, row, rk.ctr_row, tok);
     }
 }
 
 // Second half of the FUSED tail: the head GEMM's epilogue (gemm.hip, TAIL instantiations) left, per row and column tile, the best
 // (score, label) of that tile; pick the row's winner (first index wins ties -> identical to the one-kernel tail under any
 // reduction order), renoise, store the token.  One wave per row: lane t reads tile t (coalesced), xor-shuffle argmax.
+template <bool REQ>
 __global__ __launch_bounds__(256) void tail_finalize_kernel(TailArgs a, const float* __restrict__ part_score, const int* __restrict__ part_idx,
                                                             int tiles_n) {
     const int lane = threadIdx.x & 63;
@@ -145,17 +169,33 @@ __global__ __launch_bounds__(256) void tail_finalize_kernel(TailArgs a, const fl
         argmax_update(best, best_i, ov, oi);
     }
     if (lane == 0) {
-        const uint64_t seed = a.seed + (a.seed_ptr ? *a.seed_ptr : 0ull);
+        const RowKey rk = tail_row_key<REQ>(a, row);
         if (best_i == 0x7fffffff) best_i = 0;
         int64_t tok = best_i;
         if (a.sampled_out) a.sampled_out[row] = tok;
-        a.tokens_out[row] = renoise_token(a, seed, row, tok);
+        a.tokens_out[row] = renoise_token(a, rk.seed, row, rk.ctr_row, tok);
     }
 }
 
+// request form: the tables must be there, the rows whole samples, the draw categorical from Philox; fills the division
+static int tail_req_prepare(TailArgs& a) {
+    const ReqTables& q = a.rq;
+    if (!q.seeds || !q.temperature || a.rows <= 0 || a.rows > 0x7fffffff || a.rows % q.rows_per_sample || a.mode != 0 || a.noise_q || a.mask_u) {
+        paella_set_error("request tail: needs seed and temperature tables, rows a multiple of rows_per_sample (%d), categorical mode and in-kernel noise", q.rows_per_sample);
+        return PAELLA_ERR_ARG;
+    }
+    a.rq.rps_div = fast_div_of((unsigned)q.rows_per_sample);
+    return PAELLA_OK;
+}
+#define RET_REQ(r) do { const int _rc = tail_req_prepare(r); if (_rc != PAELLA_OK) return _rc; } while (0)
+
 int launch_tail_finalize(const TailArgs& a, const float* part_score, const int* part_idx, int tiles_n, hipStream_t st) {
     if (a.rows <= 0) return PAELLA_OK;
-    hipLaunchKernelGGL(tail_finalize_kernel, dim3((unsigned)((a.rows + 3) / 4)), dim3(256), 0, st, a, part_score, part_idx, tiles_n);
+    if (a.rq.rows_per_sample > 0) {
+        TailArgs r = a;
+        RET_REQ(r);
+        hipLaunchKernelGGL(tail_finalize_kernel<true>, dim3((unsigned)((a.rows + 3) / 4)), dim3(256), 0, st, r, part_score, part_idx, tiles_n);
+    } else hipLaunchKernelGGL(tail_finalize_kernel<false>, dim3((unsigned)((a.rows + 3) / 4)), dim3(256), 0, st, a, part_score, part_idx, tiles_n);
     LAUNCH_CHECK_RET();
     return PAELLA_OK;
 }
@@ -164,7 +204,11 @@ int launch_sample_tail(const TailArgs& a, hipStream_t st) {
     if (a.rows <= 0) return PAELLA_OK;
     if (a.L & 3) { paella_set_error("sample_tail: num_labels %% 4 != 0"); return PAELLA_ERR_ARG; }
     if (a.rows > 0x7fffffff) { paella_set_error("sample_tail: too many rows"); return PAELLA_ERR_ARG; }
-    hipLaunchKernelGGL(sample_tail_kernel, dim3((unsigned)a.rows), dim3(256), 0, st, a);
+    if (a.rq.rows_per_sample > 0) {
+        TailArgs r = a;
+        RET_REQ(r);
+        hipLaunchKernelGGL(sample_tail_kernel<true>, dim3((unsigned)a.rows), dim3(256), 0, st, r);
+    } else hipLaunchKernelGGL(sample_tail_kernel<false>, dim3((unsigned)a.rows), dim3(256), 0, st, a);
     LAUNCH_CHECK_RET();
     return PAELLA_OK;
 }
@@ -193,6 +237,26 @@ int launch_start_tokens(uint64_t seed, const uint64_t* seed_ptr, int64_t row_off
     int64_t blocks = (n + 255) / 256;
     if (blocks > 4096) blocks = 4096;
     hipLaunchKernelGGL(start_tokens_kernel, dim3((unsigned)blocks), dim3(256), 0, st, seed, seed_ptr, row_offset, row_offset_ptr, num_labels, n, out);
+    LAUNCH_CHECK_RET();
+    return PAELLA_OK;
+}
+
+// request batch: sample b draws the start tokens of seeds[b] sampled alone (counter = the position inside the sample)
+__global__ __launch_bounds__(256) void start_tokens_req_kernel(const uint64_t* __restrict__ seeds, FastDiv rps_div, int rows_per_sample, int num_labels, int64_t n,
+                                                               int64_t* __restrict__ out) {
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const unsigned b = fast_div((unsigned)i, rps_div);
+        uint32_t rb[4];
+        philox4x32(seeds[b] ^ 0x9e3779b97f4a7c15ull, (uint64_t)(i - (int64_t)b * rows_per_sample), ~0ull, rb);
+        out[i] = (int64_t)((((uint64_t)rb[0] << 32) | rb[1]) % (uint64_t)num_labels);
+    }
+}
+int launch_start_tokens_req(const uint64_t* seeds, int B, int rows_per_sample, int num_labels, int64_t* out, hipStream_t st) {
+    const int64_t n = (int64_t)B * rows_per_sample;
+    if (!seeds || !out || B <= 0 || rows_per_sample <= 0 || num_labels <= 0 || n > 0x7fffffff) { paella_set_error("start_tokens_req: bad arguments"); return PAELLA_ERR_ARG; }
+    int64_t blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(start_tokens_req_kernel, dim3((unsigned)blocks), dim3(256), 0, st, seeds, fast_div_of((unsigned)rows_per_sample), rows_per_sample, num_labels, n, out);
     LAUNCH_CHECK_RET();
     return PAELLA_OK;
 }
@@ -263,22 +327,22 @@ int launch_select_tokens(const int64_t* a, const int64_t* b, const int64_t* mask
 // with exactly the kernels' arithmetic and Philox counters.  Lets a test classify a differing token by the decision margin
 // (top-1 minus top-2 score) instead of bounding a mismatch count.
 // ---------------------------------------------------------------------------
+template <bool REQ>
 __global__ __launch_bounds__(256) void tail_scores_kernel(TailArgs a, float* __restrict__ scores) {
     const int64_t row = blockIdx.x;
     const int L = a.L, L4 = L >> 2;
     const float* lc = a.logits_c + row * L;
     const float* lu = a.logits_u ? a.logits_u + row * L : nullptr;
     const bool has_u = lu != nullptr;
-    const uint64_t seed = a.seed + (a.seed_ptr ? *a.seed_ptr : 0ull);
-    const int64_t row_off = tail_row_offset(a);
+    const RowKey rk = tail_row_key<REQ>(a, row);
     for (int i4 = threadIdx.x; i4 < L4; i4 += 256) {
         const f32x4 c = *reinterpret_cast<const f32x4*>(lc + i4 * 4);
         const f32x4 u = has_u ? *reinterpret_cast<const f32x4*>(lu + i4 * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
         uint32_t rb[4];
-        philox4x32(seed, (uint64_t)(row + row_off) * L4 + i4, a.offset, rb);
+        philox4x32(rk.seed, (uint64_t)rk.ctr_row * L4 + i4, a.offset, rb);
         f32x4 s;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) s[e] = tail_score_gumbel(mix_logit(c[e], u[e], a.cfg, a.one_minus_cfg, has_u), tail_inv_temperature(a.temperature), log_exp1(rb[e]));
+        for (int e = 0; e < 4; ++e) s[e] = tail_score_gumbel(mix_logit(c[e], u[e], rk.cfg, rk.omc, has_u), tail_inv_temperature(rk.temperature), log_exp1(rb[e]));
         *reinterpret_cast<f32x4*>(scores + row * L + i4 * 4) = s;
     }
 }
@@ -288,7 +352,18 @@ extern "C" int paella_test_tail_scores(const float* logits_c, const float* logit
     TailArgs a = {};
     a.logits_c = logits_c; a.logits_u = logits_u; a.rows = rows; a.L = L; a.cfg = cfg; a.one_minus_cfg = one_minus_cfg; a.temperature = temperature;
     a.seed = seed; a.offset = offset; a.row_offset = row_offset;
-    hipLaunchKernelGGL(tail_scores_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, a, scores_out);
+    hipLaunchKernelGGL(tail_scores_kernel<false>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, a, scores_out);
+    LAUNCH_CHECK_RET();
+    return PAELLA_OK;
+}
+extern "C" int paella_test_tail_scores_req(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
+                                           const uint64_t* seeds, int rows_per_sample, uint64_t offset, float* scores_out, void* stream) {
+    if (!logits_c || !scores_out || (L & 3) || rows_per_sample <= 0) { paella_set_error("tail_scores_req: bad arguments"); return PAELLA_ERR_ARG; }
+    TailArgs a = {};
+    a.logits_c = logits_c; a.logits_u = logits_u; a.rows = rows; a.L = L; a.offset = offset;
+    a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.cfg_pairs = cfg_pairs; a.rq.rows_per_sample = rows_per_sample;
+    RET_REQ(a);
+    hipLaunchKernelGGL(tail_scores_kernel<true>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, a, scores_out);
     LAUNCH_CHECK_RET();
     return PAELLA_OK;
 }

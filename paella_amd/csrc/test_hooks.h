@@ -87,6 +87,9 @@ long long paella_prof_grid(long long* out4, long long cap);
  * Philox counters): tests classify a differing token by the decision margin between the two best scores of its row */
 int paella_test_tail_scores(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature,
                             uint64_t seed, uint64_t offset, int64_t row_offset, float* scores_out, void* stream);
+/* the same for a request batch (paella_sample_tail_req's tables): seed, guidance pair and temperature per sample, counters from the position inside the sample */
+int paella_test_tail_scores_req(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
+                                const uint64_t* seeds, int rows_per_sample, uint64_t offset, float* scores_out, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -313,6 +313,11 @@ class Paella(nn.Module):
     def new_workspace(self, B, H, W, S):
         return _lib.new_workspace(self.workspace_bytes(B, H, W, S), self._device())
 
+    def _check_table(self, t, shape, dtype, name):
+        """a request-batch table: a contiguous DEVICE tensor of exactly this shape and type (the kernels index it by sample)"""
+        if not torch.is_tensor(t) or t.device != self._device() or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
+            raise ValueError("%s must be a contiguous %s tensor of shape %s on the model's device" % (name, dtype, tuple(shape)))
+
     @staticmethod
     def _f32(t, name):
         if t is None:
@@ -385,12 +390,12 @@ class Paella(nn.Module):
         return out
 
     # ------------------------------------------------------------------ forward
-    def forward_prepared(self, x, r, cond, attn_weights=None, out=None, cfg_mix=None, ws=None):
+    def forward_prepared(self, x, r, cond, attn_weights=None, out=None, cfg_mix=None, ws=None, req_mix=None):
         """One denoising evaluation against a `CondCache` (see `_forward_prepared_raw`): logits with the reference's shape [B, num_labels, H, W], a channels-last
         view of the position-major buffer the kernels write."""
-        return self._forward_prepared_raw(x, r, cond, attn_weights=attn_weights, out=out, cfg_mix=cfg_mix, ws=ws).permute(0, 3, 1, 2)
+        return self._forward_prepared_raw(x, r, cond, attn_weights=attn_weights, out=out, cfg_mix=cfg_mix, ws=ws, req_mix=req_mix).permute(0, 3, 1, 2)
 
-    def _forward_prepared_raw(self, x, r, cond, attn_weights=None, out=None, cfg_mix=None, ws=None):
+    def _forward_prepared_raw(self, x, r, cond, attn_weights=None, out=None, cfg_mix=None, ws=None, req_mix=None):
         """One denoising evaluation against a `CondCache`, position-major result [B, H, W, num_labels].  x int64 [Bx,H,W]; r fp32 [Bx].
         Normally Bx == cond.B.  With Bx < cond.B (cond.B a multiple of Bx) the rows b, b + Bx, ... of the conditioning
         share the tokens and timestep of row b -- classifier-free guidance batches the conditional and unconditional pass
@@ -398,7 +403,8 @@ class Paella(nn.Module):
         cfg_mix=(a, b) with cond.B == 2*Bx additionally folds the guidance mix a*logits[:Bx] + b*logits[Bx:]
         (src/utils.py:47) through the bias-free linear head and returns only those Bx mixed rows.
         Returns logits with the reference's shape [B, num_labels, H, W] (a channels-last view of the
-        position-major buffer the kernels write; pass `out` = a [B,H,W,num_labels] fp32 tensor to reuse memory)."""
+        position-major buffer the kernels write; pass `out` = a [B,H,W,num_labels] fp32 tensor to reuse memory).
+        req_mix (request batch, instead of cfg_mix): an fp32 DEVICE tensor [Bx, 2] with one guidance pair per sample."""
         h = self._engine()
         lib = _lib.load()
         dev = self._device()
@@ -418,25 +424,36 @@ class Paella(nn.Module):
         mix = (0.0, 0.0) if cfg_mix is None else (float(cfg_mix[0]), float(cfg_mix[1]))
         if cfg_mix is not None and (B != 2 * nu or mix == (0.0, 0.0)):
             raise ValueError("cfg_mix needs a conditioning batch of twice the token batch and a non-zero mix")
-        Bo = nu if cfg_mix is not None else B
+        if req_mix is not None:
+            if cfg_mix is not None or B != 2 * nu:
+                raise ValueError("req_mix needs a conditioning batch of twice the token batch and no cfg_mix")
+            self._check_table(req_mix, (nu, 2), torch.float32, "req_mix")
+        Bo = nu if (cfg_mix is not None or req_mix is not None) else B
         if out is None:
             out = torch.empty(Bo, H, W, self.num_labels, dtype=torch.float32, device=dev)
         elif tuple(out.shape) != (Bo, H, W, self.num_labels) or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError("out must be a contiguous fp32 [B,H,W,num_labels] tensor")
         with torch.cuda.device(dev):
             ws = self._workspace(lib.paella_unet_workspace_bytes(h, B, H, W, cond.S), ws)
+            if req_mix is not None:
+                _lib.check(lib.paella_unet_forward_shared_req(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(req_mix), H, W, cond.S, _lib.ptr(aw),
+                                                              0 if aw is None else aw.numel(), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+                return out
             _lib.check(lib.paella_unet_forward_shared(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, mix[0], mix[1], H, W, cond.S, _lib.ptr(aw),
                                                       0 if aw is None else aw.numel(), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
                                                       _lib.stream_ptr(dev)))
         return out
 
     def forward_sample(self, x, r, cond, out, *, temperature, argmax=False, seed=0, seed_dev=None, offset=0, row_offset=0,
-                       row_offset_dev=None, init_noise=None, t_next=0.0, cfg_mix=None, attn_weights=None, ws=None):
+                       row_offset_dev=None, init_noise=None, t_next=0.0, cfg_mix=None, attn_weights=None, ws=None, req=None):
         """One whole sampling step in the counter-based noise mode (src/utils.py:43-54): the denoiser evaluation with the head
         GEMM and the sampling tail FUSED -- the [B, num_labels, H, W] logits are never materialised.  x int64 [Bx,H,W], r [Bx];
         cfg_mix=(a, b) with cond.B == 2*Bx folds classifier-free guidance through the head (as forward_prepared); without it
         cond.B must equal Bx.  `out` int64 [Bx,H,W] receives the tokens (renoised against init_noise with u <= t_next when
-        init_noise is given).  Bit-identical to forward_prepared + the tail kernel on the same seed."""
+        init_noise is given).  Bit-identical to forward_prepared + the tail kernel on the same seed.
+        req=(seeds, temperature, pairs) (request batch; `temperature`, `seed`, `row_offset` and `cfg_mix` are then unused): DEVICE tables with one entry per
+        sample -- int64 [Bx] seed bit patterns, fp32 [Bx] temperatures (> 0, validated by the caller), fp32 [Bx, 2] guidance pairs or None (no guidance);
+        sample b draws what it draws alone under seeds[b] (counters from the position inside the sample)."""
         h = self._engine()
         lib = _lib.load()
         dev = self._device()
@@ -447,13 +464,26 @@ class Paella(nn.Module):
         r = self._f32(r, "r")
         B = cond.B
         mix = (0.0, 0.0) if cfg_mix is None else (float(cfg_mix[0]), float(cfg_mix[1]))
-        if (cfg_mix is None and B != nu) or (cfg_mix is not None and (B != 2 * nu or mix == (0.0, 0.0))):
+        if req is not None:
+            seeds, temps, pairs = req
+            if argmax or cfg_mix is not None or B != (nu if pairs is None else 2 * nu):
+                raise ValueError("forward_sample(req=...) is categorical, takes its guidance from the pair table and needs cond.B == Bx (no pairs) or 2*Bx")
+            self._check_table(seeds, (nu,), torch.int64, "req seeds")
+            self._check_table(temps, (nu,), torch.float32, "req temperature")
+            if pairs is not None:
+                self._check_table(pairs, (nu, 2), torch.float32, "req pairs")
+        elif (cfg_mix is None and B != nu) or (cfg_mix is not None and (B != 2 * nu or mix == (0.0, 0.0))):
             raise ValueError("forward_sample needs cond.B == Bx (no guidance) or cond.B == 2*Bx with a non-zero cfg_mix")
         if tuple(out.shape) != (nu, H, W) or out.dtype != torch.int64 or not out.is_contiguous():
             raise ValueError("out must be a contiguous int64 [B,H,W] tensor")
         aw = self._f32(attn_weights, "attn_weights")
         with torch.cuda.device(dev):
             ws = self._workspace(lib.paella_unet_workspace_bytes(h, B, H, W, cond.S), ws)
+            if req is not None:
+                _lib.check(lib.paella_unet_forward_sample_req(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S, _lib.ptr(aw),
+                                                              0 if aw is None else aw.numel(), _lib.ptr(seeds), _lib.ptr(temps), H * W, int(offset), _lib.ptr(init_noise),
+                                                              float(t_next), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+                return out
             _lib.check(lib.paella_unet_forward_sample(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, mix[0], mix[1], H, W, cond.S,
                                                       _lib.ptr(aw), 0 if aw is None else aw.numel(), float(temperature), 1 if argmax else 0,
                                                       int(seed), _lib.ptr(seed_dev), int(offset), int(row_offset), _lib.ptr(row_offset_dev), _lib.ptr(init_noise),

@@ -84,6 +84,15 @@ def _tail(logits_c, logits_u, rows, L, cfg, omc, temperature, mode, noise_q, see
                                              _lib.ptr(init_noise), _lib.ptr(mask_u), t_next, _lib.ptr(out), None, _lib.stream_ptr(dev)))
 
 
+def _tail_req(lc, lu, rows, L, rows_per_sample, req, step, init_noise, t_next, out):
+    """the request form of `_tail`: seed, guidance pair and temperature per sample from the device tables of `req` (RequestTables)"""
+    dev = lc.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().paella_sample_tail_req(_lib.ptr(lc), _lib.ptr(lu), rows, L, _lib.ptr(None if lu is None else req.pairs[step]), _lib.ptr(req.temps[step]),
+                                                      _lib.ptr(req.seeds), rows_per_sample, step, _lib.ptr(init_noise), t_next, _lib.ptr(out), None,
+                                                      _lib.stream_ptr(dev)))
+
+
 def fresh_seed():
     """A 62-bit seed drawn from torch's default (CPU) generator: reproducible under torch.manual_seed, different on every
     call otherwise -- what `seed=None` means in the counter-based (Philox) noise mode.  NOTE: this consumes one draw of torch's
@@ -115,6 +124,88 @@ def start_tokens(num_labels, shape, seed, device, shard=None, out=None, seed_dev
     return out
 
 
+def start_tokens_requests(num_labels, shape, seeds_dev, out=None):
+    """Start tokens of a request batch: sample b of [B, H, W] gets the start tokens `start_tokens(num_labels, (1, H, W), seeds[b])` draws; seeds_dev is the
+    int64 DEVICE tensor [B] of seed bit patterns (paella_start_tokens_req: graph-capturable, no host work)."""
+    B, H, W = shape
+    device = seeds_dev.device
+    if out is None:
+        out = torch.empty(B, H, W, dtype=torch.int64, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().paella_start_tokens_req(_lib.ptr(seeds_dev), B, H * W, int(num_labels), _lib.ptr(out), _lib.stream_ptr(device)))
+    return out
+
+
+def request_tables(B, steps, seeds, cfg, temperature):
+    """HOST tables of a request batch, validated before anything touches a device:
+        seeds int64 [B] (bit patterns, `seed_word`), temps fp32 [steps, B], pairs fp32 [steps, B, 2] or None (cfg=None: no guidance for anyone).
+    Row b holds, bit for bit, the scalars the scalar samplers compute for that request's values: temperatures `linspace_schedule(start, end, steps)`;
+    a float guidance scale as `sample()` rounds it (fp32(cfg), fp32(1.0 - cfg), the same for every step), a (start, end) tuple as `sample_distributed`
+    does (torch.linspace, 1 - cfg in fp32).  temperature: one (start, end) pair or a list of B pairs.  cfg: None, a float (all requests), or a LIST of B
+    entries, each a float or a (start, end) tuple -- a bare tuple is refused (with B = 2 it could mean either).  Guidance is on for every request or for
+    none: a request that wants none inside a guided batch passes 1.0, which mixes with (1, 0) -- exact while the unconditional activations are finite."""
+    B, steps = int(B), int(steps)
+    if B <= 0 or steps <= 0:
+        raise ValueError("a request batch needs B > 0 and steps > 0")
+    seeds = list(seeds) if isinstance(seeds, (list, tuple)) or torch.is_tensor(seeds) else None
+    if seeds is None or len(seeds) != B:
+        raise ValueError("seeds must be a sequence of %d integers (one per request)" % B)
+    seed_t = torch.tensor([seed_word(int(v)) for v in seeds], dtype=torch.int64)
+    is_num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+    is_pair = lambda v: isinstance(v, (list, tuple)) and len(v) == 2 and all(is_num(x) for x in v)
+    if is_pair(temperature):
+        t_pairs = [temperature] * B
+    elif isinstance(temperature, (list, tuple)) and len(temperature) == B and all(is_pair(v) for v in temperature):
+        t_pairs = list(temperature)
+    else:
+        raise ValueError("temperature must be one (start, end) pair or a list of %d such pairs" % B)
+    temps = torch.tensor([linspace_schedule(float(a), float(b), steps) for a, b in t_pairs], dtype=torch.float32).t().contiguous()
+    if not bool((temps > 0).all()):
+        raise ValueError("every step temperature of a request batch must be > 0 (temperature 0, the argmax extension, is not offered per request)")
+    if cfg is None:
+        return seed_t, temps, None
+    if isinstance(cfg, tuple):
+        raise TypeError("cfg must be None, a float or a LIST with one entry per request (a float or a (start, end) tuple each); a bare tuple is ambiguous")
+    if is_num(cfg):
+        entries = [cfg] * B
+    elif isinstance(cfg, list) and len(cfg) == B:
+        entries = cfg
+    else:
+        raise ValueError("cfg must be None, a float or a list of %d entries" % B)
+    rows = []
+    for e in entries:
+        if e is None:
+            raise ValueError("guidance is on for every request of a batch or for none: cfg=None cannot be mixed with guided requests (pass 1.0 for 'no guidance')")
+        if is_num(e):
+            rows.append([[float(torch.tensor(float(e), dtype=torch.float32)), float(torch.tensor(1.0 - float(e), dtype=torch.float32))]] * steps)
+        elif isinstance(e, tuple) and is_pair(e):
+            sched = torch.linspace(e[0], e[1], steps)
+            rows.append([[float(sched[i]), float(1 - sched[i])] for i in range(steps)])
+        else:
+            raise ValueError("a cfg entry must be a float or a (start, end) tuple, got %r" % (e,))
+    pairs = torch.tensor(rows, dtype=torch.float32).permute(1, 0, 2).contiguous()
+    return seed_t, temps, pairs
+
+
+class RequestTables:
+    """the DEVICE tables of a request batch (seeds int64 [B], temps fp32 [steps, B], pairs fp32 [steps, B, 2] or None); `load` rewrites them in place, which is
+    all a captured graph needs to serve other seeds, guidance scales and temperatures"""
+
+    def __init__(self, host, device):
+        self.seeds, self.temps, self.pairs = (None if t is None else t.to(device) for t in host)
+
+    def load(self, host):
+        if (host[2] is None) != (self.pairs is None):
+            raise ValueError("guidance cannot be switched %s for a captured request batch" % ("off" if host[2] is None else "on"))
+        for dst, src in zip((self.seeds, self.temps, self.pairs), host):
+            if dst is not None:
+                dst.copy_(src)
+
+    def step(self, i):
+        """what forward_sample(req=...) takes at step i"""
+        return (self.seeds, self.temps[i], None if self.pairs is None else self.pairs[i])
+
+
 def timestep_table(t_list, steps, B, device):
     """[steps, B] fp32: row i = the timestep of step i for every sample (one upload instead of a fill kernel per step)."""
     return torch.tensor([float(v) for v in t_list[:steps]], dtype=torch.float32).to(device)[:, None].repeat(1, B).contiguous()
@@ -143,13 +234,15 @@ def select_tokens(a, b=None, mask=None, flag=None, fill=-1, out=None):
 
 def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x, steps, renoise_steps, t_list, temperatures,
                  cfgs, device, noise="torch", seed=None, attn_weights=None, seed_dev=None, init_noise_buf=None, r_all=None, shard=None,
-                 ws=None, fused_tail=True, row_offset_dev=None):
+                 ws=None, fused_tail=True, row_offset_dev=None, req=None):
     """cfgs: per-step list of (cfg_fp32, one_minus_cfg_fp32) or None (no guidance at that step).
     seed_dev / row_offset_dev / init_noise_buf / r_all: device-resident seed and row-offset words, a buffer for the start tokens
     and the [steps, B] timestep table (HIP-graph capture cannot upload from the host, see GraphSampler); ws: caller-owned
     workspace for every library call.
     shard = (lo, total): this call samples rows [lo, lo + B) of a global batch of `total`; with noise="philox" every random
-    number is keyed by the GLOBAL row, so the shard reproduces those rows of the unsharded call bit for bit."""
+    number is keyed by the GLOBAL row, so the shard reproduces those rows of the unsharded call bit for bit.
+    req (RequestTables; noise="philox" only): the B samples are independent requests -- seed, guidance pair and temperature per sample come from its device
+    tables, `seed` / `shard` are unused, `temperatures` must be positive placeholders and `cfgs` only says whether guidance is on."""
     explicit = isinstance(noise, dict)  # parity tests: {"init_noise": [B,H,W], "q": [rows,L] per step, "u": [B,H,W] per step}
     if not explicit and noise not in ("torch", "philox"):
         raise ValueError("noise must be 'torch', 'philox' or a dict of explicit noise tensors")
@@ -169,8 +262,12 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
     if shard is not None and not (philox or explicit):
         raise ValueError("shard=(lo, total) needs noise='philox' (or explicit noise tensors): torch's generator stream cannot be sharded")
     row_offset = 0 if shard is None else int(shard[0]) * H * W
+    if req is not None and not (philox and native and shard is None and init_x is None):
+        raise ValueError("a request batch needs noise='philox', a paella_amd.Paella model, no shard and no init_x")
     with torch.inference_mode():
-        if init_noise_buf is not None and philox:
+        if req is not None:
+            init_noise = start_tokens_requests(L, (B, H, W), req.seeds, out=init_noise_buf)
+        elif init_noise_buf is not None and philox:
             init_noise = start_tokens(L, (B, H, W), seed, device, shard, out=init_noise_buf, seed_dev=seed_dev, row_offset_dev=row_offset_dev)
         elif init_noise_buf is not None:
             init_noise = init_noise_buf
@@ -212,7 +309,8 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
                 model.forward_sample(sampled, r, cond_both if use_cfg else cond_c, out, temperature=temp if mode == 0 else 1.0, argmax=mode == 1,
                                      seed=seed, seed_dev=seed_dev, offset=i, row_offset=row_offset, row_offset_dev=row_offset_dev,
                                      init_noise=init_noise if renoise else None,
-                                     t_next=t_list[i + 1] if renoise else 0.0, cfg_mix=cfgs[i] if use_cfg else None, attn_weights=attn_weights, ws=ws)
+                                     t_next=t_list[i + 1] if renoise else 0.0, cfg_mix=cfgs[i] if use_cfg and req is None else None, attn_weights=attn_weights, ws=ws,
+                                     req=None if req is None else req.step(i))
                 sampled = out
                 continue
             if native:
@@ -224,7 +322,7 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
                     fold = philox and mode == 0
                     logits2 = logits_buf("both", 2 * B)
                     model.forward_prepared(sampled, r, cond_both, attn_weights=attn_weights, out=logits2[:B] if fold else logits2,
-                                           cfg_mix=cfgs[i] if fold else None, ws=ws)
+                                           cfg_mix=cfgs[i] if fold and req is None else None, ws=ws, **({} if req is None else {"req_mix": req.pairs[i]}))
                     lc, lu = logits2[:B], (None if fold else logits2[B:])
                 else:
                     lc, lu = logits_buf("c", B), None
@@ -251,6 +349,10 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
                 mask_u = noise["u"][i].to(device=device, dtype=torch.float32).contiguous()
             elif renoise and noise == "torch":
                 mask_u = torch.rand(B, H, W, dtype=torch.float32, device=device)  # == torch.rand_like(x.float())
+            if req is not None:
+                _tail_req(lc, lu, rows, L, H * W, req, i, init_noise if renoise else None, t_list[i + 1] if renoise else 0.0, out)
+                sampled = out
+                continue
             cfg, omc = cfgs[i] if use_cfg else (1.0, 0.0)
             _tail(lc, lu, rows, L, cfg, omc, temp if mode == 0 else 1.0, mode, noise_q, seed, i,
                   init_noise if renoise else None, mask_u, t_list[i + 1] if renoise else 0.0, out, seed_dev=seed_dev,
@@ -302,6 +404,30 @@ def sample_distributed(model, model_inputs, unconditional_inputs, latent_shape, 
             cfgs[i] = (float(sched[i]), float(1 - sched[i]))
     return _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x, steps, renoise_steps, t_list, temperatures,
                         cfgs, device, noise=noise, seed=seed, attn_weights=attn_weights, shard=shard, fused_tail=fused_tail)
+
+
+def _request_schedule(steps, t_start, t_end, guided):
+    """what `_sample_core` takes for a request batch: the common timestep list, placeholder temperatures (the real ones are in the tables) and whether guidance is on"""
+    return linspace_schedule(t_start, t_end, steps + 1), [1.0] * steps, [(1.0, 0.0) if guided else None] * steps
+
+
+def sample_requests(model, model_inputs, unconditional_inputs, latent_shape, seeds, cfg=8.0, temperature=(1.0, 0.2), steps=12, renoise_steps=11,
+                    t_start=1.0, t_end=0.0, device="cuda", attn_weights=None, fused_tail=True):
+    """B independent REQUESTS sampled as one batch (counter-based noise): request b has its own seed `seeds[b]`, guidance and temperature range, and its
+    tokens are a function of the request alone -- every random number it draws is the one `sample(..., latent_shape=(1, H, W), noise="philox", seed=seeds[b])`
+    draws, whatever slot it sits in and whoever shares the batch (the logits may still differ in their last bits with the batch size: the GEMMs split their
+    work by tile index).  `cfg` / `temperature`: one value for all requests or one per request, see `request_tables`.  `steps`, `renoise_steps`, `t_start` /
+    `t_end`, the grid and the conditioning layout are common to the batch.  Two requests with equal seeds draw identical noise.  Returns tokens [B, H, W]."""
+    B, H, W = (int(v) for v in latent_shape)
+    host = request_tables(B, steps, seeds, cfg, temperature)
+    if host[2] is not None and unconditional_inputs is None:
+        raise TypeError("cfg=%r requires unconditional_inputs" % (cfg,))
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError("paella_amd.sample_requests runs on a HIP device only (got device=%s); there is no CPU path" % device)
+    t_list, temps, cfgs = _request_schedule(steps, t_start, t_end, host[2] is not None)
+    return _sample_core(model, model_inputs, unconditional_inputs, (B, H, W), None, steps, renoise_steps, t_list, temps, cfgs, device, noise="philox", seed=0,
+                        attn_weights=attn_weights, fused_tail=fused_tail, req=RequestTables(host, device))
 
 
 class GraphSampler:
@@ -453,5 +579,42 @@ class GraphSampler:
         if unconditional_inputs is not None:
             self._copy_inputs(self.uncond, unconditional_inputs)
         self._set_words(seed, shard)
+        self.graph.replay()
+        return self.out
+
+
+class GraphRequestSampler(GraphSampler):
+    """`sample_requests` (optionally + the VQGAN decode) captured ONCE per shape and step count and replayed per batch of requests: the seeds, guidance
+    pairs and temperatures live in device tables the kernels read, so a replay with other values rewrites the tables and never recaptures (`captures`
+    stays 1); GraphSampler's staleness check (weights, precision) applies unchanged.  `cfg` / `temperature` given here are the defaults of a call that
+    passes none, and `cfg=None` captures an unguided batch (guidance cannot be switched per replay: it decides the launch sequence).  Replays equal the
+    eager `sample_requests` bit for bit."""
+
+    def __init__(self, model, model_inputs, unconditional_inputs, latent_shape, steps=12, renoise_steps=11, temperature=(1.0, 0.2), cfg=8.0, t_start=1.0,
+                 t_end=0.0, device="cuda", vqgan=None, attn_weights=None, on_stale="recapture"):
+        B = int(latent_shape[0])
+        self.req_defaults = dict(cfg=cfg, temperature=temperature)
+        self.req = RequestTables(request_tables(B, steps, [0] * B, cfg, temperature), torch.device(device))
+        super().__init__(model, model_inputs, unconditional_inputs, latent_shape, steps=steps, renoise_steps=renoise_steps, temperature=temperature, cfg=cfg,
+                         t_start=t_start, t_end=t_end, device=device, vqgan=vqgan, attn_weights=attn_weights, on_stale=on_stale)
+
+    def _run(self):
+        k = self.kw
+        t_list, temps, cfgs = _request_schedule(k["steps"], k["t_start"], k["t_end"], self.req.pairs is not None)
+        toks = _sample_core(self.model, self.cond, self.uncond, self.shape, None, k["steps"], k["renoise_steps"], t_list, temps, cfgs, self.device,
+                            noise="philox", seed=0, attn_weights=self.attn_weights, init_noise_buf=self.init_noise, r_all=self.r_all, ws=self.ws, req=self.req)
+        return toks if self.vqgan is None else (toks, self.vqgan.decode_indices(toks, ws=self.vq_ws))
+
+    def __call__(self, seeds, cfg=None, temperature=None, model_inputs=None, unconditional_inputs=None):
+        """Replay for the requests `seeds[b]` (cfg / temperature: as `sample_requests`; None = the constructor's).  Outputs live in graph-owned buffers that the
+        next replay overwrites."""
+        host = request_tables(self.shape[0], self.kw["steps"], seeds, self.req_defaults["cfg"] if cfg is None else cfg,
+                              self.req_defaults["temperature"] if temperature is None else temperature)
+        self._check_fresh()
+        if model_inputs is not None:
+            self._copy_inputs(self.cond, model_inputs)
+        if unconditional_inputs is not None:
+            self._copy_inputs(self.uncond, unconditional_inputs)
+        self.req.load(host)
         self.graph.replay()
         return self.out
