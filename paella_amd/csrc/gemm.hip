@@ -35,6 +35,7 @@
 #include "test_hooks.h"
 #include <atomic>
 #include <mutex>
+#include <string>
 #include <type_traits>
 #include <utility>
 #include <vector>
@@ -116,22 +117,55 @@ extern "C" int paella_probe_gemm_clock(unsigned long long* out2) {
 }
 #endif
 
-// Workgroups per CU a ring instantiation asks the register allocator for: the register-side wish (5 for the 3-stage 32x32 tile, 4 for the other one- and two-block
-// wave tiles, 3 for 64x64, 1 for the 8-wave tile) CAPPED by what its LDS footprint admits on a 160 KiB CU -- asking for more than LDS allows only shrinks the register
-// budget for nothing (twelve instantiations used to "fail to meet the occupancy target").  Mirrors the kernel's own LDS arithmetic (smem[] below);
-// tests/test_kernel_resources.py holds the compiler's numbers against it.
-constexpr int ring_lds_bytes(int WM, int WN, int TM, int TN, int APRO, int RING) {
+// ---- what a tile costs: ONE definition of its LDS image and of its workgroups per CU, as functions of the template numbers.  The kernel (smem[], __launch_bounds__)
+// and the host (ring_ok, tile_of) read these; tests/test_kernel_resources.py holds the compiler's numbers against them. ----
+struct TileRes {
+    int BM, BN;        // output tile: rows / columns
+    int tile_floats;   // the A and W tiles of one K step
+    int stage_floats;  // one LDS stage: the tiles (+ the GRN prologues' side stage on ring tiles)
+    int flag_off;      // floats in front of the ticket broadcast, i.e. all stages
+    int tail_floats;   // fused tail: per row and wave column, the best (score, label)
+    int grn_scr;       // epilogue scratch: per-wave column sums of squares when a sample spans several waves' rows
+    int lds_bytes;     // all of it
+    int side_samples;  // consecutive sample rows the GRN side stage holds
+};
+constexpr TileRes tile_res(int WM, int WN, int TM, int TN, int APRO, bool TAIL, int BK, int RING) {
     const int BM = WM * TM * 16, BN = WN * TN * 16;
-    const bool big = WM * WN == 8;
-    const int aux = (big && APRO == 1) ? 576 : (APRO == 1 ? 512 : (APRO == 4 ? 320 : 0));
-    const int scr = big ? 0 : WM * WN * TN * 16;
-    return (RING * ((BM + BN) * 32 + aux) + 16 + scr) * 4;
+    const bool big = RING > 0 && WM * WN == 8;  // (BIG in the kernel)
+    // ring stage = the A and W tiles + (GRN prologues) a side stage: 8 copies of shift[k0 .. k0 + 32) | scale rows of 8 consecutive samples (APRO 1), or
+    // (APRO 4, exec-masked DMAs that move 128 bytes each) shift[k0 .. +32) | gamma[k0 .. +32) | gx rows of 8 consecutive samples
+    // (BIG: shift[k0 .. k0 + 32) once (an exec-masked 128-byte DMA) at float 0 | scale rows of 16 consecutive samples from float 64)
+    const int aux = RING == 0 ? 0 : (big && APRO == 1) ? 576 : APRO == 1 ? 512 : APRO == 4 ? 320 : 0;
+    const int tile = (BM + BN) * BK, stage = tile + aux;
+    // one LDS object: RING stages (two tile stages without a ring) + 16 floats for the ticket broadcast (the NEXT unit's tile is already staged when a
+    // segment is flushed, so the flag cannot live inside the stages)
+    const int flag_off = RING > 0 ? RING * stage : 2 * stage;
+    const int tail = TAIL ? BM * WN * 2 : 0;
+    const int scr = (RING > 0 && !big) ? WM * WN * TN * 16 : 0;  // (GRN_FIN in the kernel)
+    return TileRes{BM, BN, tile, stage, flag_off, tail, scr, (flag_off + 16 + tail + scr) * 4, big ? 16 : 8};
 }
-constexpr int ring_wg_per_cu(int WM, int WN, int TM, int TN, int APRO, int RING, bool BF) {
-    // (the bf16 64x32 tile with the operand-side LayerNorm guard needs > 128 registers: three workgroups per CU there instead of a spill)
-    const int wish = WM * WN == 8 ? 1 : TM * TN == 1 ? (RING == 3 ? 5 : 4) : (TM * TN == 2 ? ((BF && APRO == 2 && TM == 2) ? 3 : 4) : 3);
-    const int fit = (160 * 1024) / ring_lds_bytes(WM, WN, TM, TN, APRO, RING);
-    return fit < wish ? (fit < 1 ? 1 : fit) : wish;
+// Workgroups per CU an instantiation asks the register allocator for (__launch_bounds__): one line and one reason per case.
+constexpr int tile_wg_per_cu(int WM, int WN, int TM, int TN, int PD, int APRO, bool TAIL, int BK, bool DMA, int RING, bool BF) {
+    const int NW = WM * WN, blocks = TM * TN;
+    if (RING > 0) {
+        // ring tiles: the register-side wish (5 for the 3-stage 32x32 tile, 4 for the other one- and two-block wave tiles, 3 for 64x64, 1 for the 8-wave tiles) CAPPED
+        // by what the LDS footprint admits on a 160 KiB CU -- asking for more than LDS allows only shrinks the register budget for nothing (twelve instantiations used
+        // to "fail to meet the occupancy target")
+        // (the bf16 64x32 tile with the operand-side LayerNorm guard needs > 128 registers: three workgroups per CU there instead of a spill)
+        const int wish = NW == 8 ? 1 : blocks == 1 ? (RING == 3 ? 5 : 4) : (blocks == 2 ? ((BF && APRO == 2 && TM == 2) ? 3 : 4) : 3);
+        const int fit = (160 * 1024) / tile_res(WM, WN, TM, TN, APRO, TAIL, BK, RING).lds_bytes;
+        return fit < wish ? (fit < 1 ? 1 : fit) : wish;
+    }
+    if (TAIL && DMA) return 4;                     // fused head + tail on the 64x64 direct-to-LDS tile: four independent workgroups per CU
+    if (TAIL && NW == 8 && blocks == 4) return 4;  // fused head + tail on 128x64 tiles: TWO+ workgroups per CU, one's Philox / log epilogue overlaps another's main loop
+    // The 32x32 tile is the batch-1 workhorse and wants 5 workgroups per CU (1280 resident): ask for <= 96 VGPRs there.  Not for the GRN / LayerNorm variants (two
+    // more staged operands per unit): forced under 96 registers they spill inside the unit loop (measured 33 us instead of 25 for 128x1280x5120), so they run 4
+    // workgroups per CU and the heuristic gives them at most 1024 workgroups.
+    if (WM == 2 && WN == 2 && blocks == 1 && PD == 2 && BK == 32 && (APRO == 0 || APRO == 3)) return 5;
+    if (DMA && NW == 4 && blocks == 16) return 2;  // 128x128 on 4 waves, direct-to-LDS: two independent workgroups per CU (64 KiB of LDS each)
+    // The 8-wave 128x64 tiles fit 128 VGPRs without spilling when asked to (126 / 128): two workgroups per CU instead of one.
+    if (NW == 8 && WM * TM == 8 && WN * TN == 4 && PD == 2 && BK == 32 && APRO == 0 && !TAIL) return 4;
+    return 1;
 }
 
 template <int WM, int WN, int TM, int TN, int PD, int APRO, bool TAIL = false, int BK = 32, bool DMA = false, int RING = 0, bool BF = false, int EPI = EPI_RUNTIME, bool REQ = false>  // REQ (TAIL only): request batch -- key, counter base and 1 / T per ROW from device tables (GemmArgs::rq); BK: K step (32 or 64 floats per LDS row); APRO: 0 none, 1 GRN scale/shift, 2 LayerNorm from row statistics; TAIL: fused sampling tail (head GEMM);
@@ -141,10 +175,6 @@ template <int WM, int WN, int TM, int TN, int PD, int APRO, bool TAIL = false, i
 // RING > 0 (the batch-1 kernels): BOTH operands always go global -> LDS directly into a ring of RING stages with RING - 1 units in flight per workgroup
 // (the prefetch depth costs LDS, not registers), and an A-operand prologue is applied to the MFMA FRAGMENTS after they are read back from LDS (GRN scale /
 // shift rows ride along in a 2 KB side stage; LayerNorm mean / rstd live in two registers per fragment row).  One barrier per unit, no ds_write at all.
-// The 32x32 tile is the batch-1 workhorse and wants 5 workgroups per CU (1280 resident): ask for <= 96 VGPRs there.  Not for the
-// GRN-prologue variant (two more staged operands per unit): forced under 96 registers it spills inside the unit loop (measured
-// 33 us instead of 25 for 128x1280x5120), so it runs 4 workgroups per CU and the heuristic gives it at most 1024 workgroups.
-// The 8-wave 128x64 tiles fit 128 VGPRs without spilling when asked to (126 / 128): two workgroups per CU instead of one.
 // BIG = ring variant on 8 waves with 64x64 wave tiles (tile id 36: 256x128): the throughput-regime kernel.  One workgroup per CU, three 48 KiB LDS
 // stages (two K steps in flight), fragments read one 16-wide k group ahead of the MFMAs that consume them -- including across the K-step barrier -- so
 // neither a ds_read latency nor a store phase ever sits in front of an idle matrix core; the GRN prologue is applied to the fragments from a side
@@ -157,20 +187,15 @@ template <int WM, int WN, int TM, int TN, int PD, int APRO, bool TAIL = false, i
 // EPI (gemm_device.h): the epilogue class -- EPI_RUNTIME tests every epilogue feature on the Epilogue fields; a specialised class compiles in exactly its
 // features, so the stream-K flush, the last-arriver combine and the epilogue carry no dead branches and the uniforms of absent features are never loaded
 // (the batch-1 ring kernels spilled 91-151 SGPRs into VGPR lanes behind the K loop: profiles/gemm_epilogue_isa_counts.txt).
-__global__ __launch_bounds__(64 * WM * WN, RING > 0 ? ring_wg_per_cu(WM, WN, TM, TN, APRO, RING, BF)
-                                           : (TAIL && DMA) ? 4  // fused head + tail on the 64x64 direct-to-LDS tile: four independent workgroups per CU
-                                           : (TAIL && WM * WN == 8 && TM * TN == 4) ? 4  // fused head + tail on 128x64 tiles: TWO+ workgroups per CU, one's Philox / log epilogue overlaps another's main loop
-                                           : (WM == 2 && WN == 2 && TM * TN == 1 && PD == 2 && BK == 32 && (APRO == 0 || APRO == 3)) ? 5  // (GRN / LayerNorm variants spill under 96 registers)
-                                           : (DMA && WM * WN == 4 && TM * TN == 16) ? 2  // 128x128 on 4 waves, direct-to-LDS: two independent workgroups per CU (64 KiB of LDS each)
-                                           : ((WM * WN == 8 && WM * TM == 8 && WN * TN == 4 && PD == 2 && BK == 32 && APRO == 0 && !TAIL) ? 4 : 1)) void gemm_nt_kernel(GemmArgs g, SkPlan p, float* __restrict__ slabs,
+__global__ __launch_bounds__(64 * WM * WN, tile_wg_per_cu(WM, WN, TM, TN, PD, APRO, TAIL, BK, DMA, RING, BF)) void gemm_nt_kernel(GemmArgs g, SkPlan p, float* __restrict__ slabs,
                                                                unsigned* __restrict__ tickets, unsigned slab_bytes) {
-    constexpr int BM = WM * TM * 16, BN = WN * TN * 16;
+    constexpr TileRes RES = tile_res(WM, WN, TM, TN, APRO, TAIL, BK, RING);  // the LDS image: one definition, shared with the host
+    constexpr int BM = RES.BM, BN = RES.BN;
     constexpr int SL = BK / 4;     // 16-byte slots per LDS row; slot s of row r lives at s ^ (r & (SL - 1)): conflict-free ds_write_b128 / ds_read_b128
     constexpr int KG = BK / 16;    // 16-wide k groups per K step (4 MFMA k-instructions each)
     constexpr int NW = WM * WN, NT = 64 * NW;
     constexpr int RP = NT / SL;  // rows staged per pass: SL threads (one float4 each) cover a BK-float row
     constexpr int LA = (BM * SL + NT - 1) / NT, LB = (BN * SL + NT - 1) / NT;
-    constexpr int TILE_FLOATS = (BM + BN) * BK;
     static_assert(NW == 4 || NW == 8, "4 or 8 waves per workgroup");
     static_assert(!REQ || TAIL, "the request form exists for the fused tail only");
     static_assert(PD == 1 || PD == 2, "prefetch ring depth 1 or 2");
@@ -191,18 +216,10 @@ __global__ __launch_bounds__(64 * WM * WN, RING > 0 ? ring_wg_per_cu(WM, WN, TM,
     constexpr bool BIG = RING > 0 && NW == 8;
     static_assert(!BIG || APRO != 4, "the 8-wave ring tile has no GRN-from-raw-statistics prologue");
     constexpr bool GRN_SIDE = RING > 0 && (APRO == 1 || APRO == 4);
-    // ring stage = the A and W tiles + (GRN prologues) a side stage: 8 copies of shift[k0 .. k0 + 32) | scale rows of 8 consecutive samples (APRO 1), or
-    // (APRO 4, exec-masked DMAs that move 128 bytes each) shift[k0 .. +32) | gamma[k0 .. +32) | gx rows of 8 consecutive samples
-    // (BIG: shift[k0 .. k0 + 32) once (an exec-masked 128-byte DMA) at float 0 | scale rows of 16 consecutive samples from float 64)
-    constexpr int AUX_FLOATS = (BIG && APRO == 1) ? 576 : (RING > 0 && APRO == 1) ? 512 : ((RING > 0 && APRO == 4) ? 320 : 0);
     constexpr bool GRN_FIN = RING > 0 && !BIG;  // tiles whose epilogue can finish GlobalResponseNorm's Gx (batch-1 regime only)
-    constexpr int GRN_SCR = GRN_FIN ? WM * WN * TN * 16 : 0;  // epilogue scratch: per-wave column sums of squares when a sample spans several waves' rows
-    constexpr int STAGE_FLOATS = TILE_FLOATS + AUX_FLOATS;
-    constexpr int FLAG_OFF = RING > 0 ? RING * STAGE_FLOATS : 2 * TILE_FLOATS;  // 16 floats for the ticket broadcast behind the stages
-    // one LDS object: two tile stages + 16 floats for the ticket broadcast (the NEXT unit's tile is already staged when a
-    // segment is flushed, so the flag cannot live inside the stages)
-    constexpr int TAIL_FLOATS = TAIL ? BM * WN * 2 : 0;  // fused tail: per row and wave column, the best (score, label)
-    __shared__ __attribute__((aligned(16))) float smem[FLAG_OFF + 16 + TAIL_FLOATS + GRN_SCR];
+    constexpr int TILE_FLOATS = RES.tile_floats, STAGE_FLOATS = RES.stage_floats, FLAG_OFF = RES.flag_off, TAIL_FLOATS = RES.tail_floats;
+    static_assert(RES.side_samples == (BIG ? 16 : 8) && (RES.grn_scr > 0) == GRN_FIN, "tile_res() and the kernel agree on which ring tiles are BIG");
+    __shared__ __attribute__((aligned(16))) float smem[RES.lds_bytes / 4];
 
     // ---- this workgroup's unit range ----
     // (everything up to the first operand fetch is latency on every launch: no branch -- the kernel-argument loads of the whole prologue then issue as one
@@ -1470,67 +1487,86 @@ __global__ __launch_bounds__(64 * WM * WN, RING > 0 ? ring_wg_per_cu(WM, WN, TM,
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-struct TileCfg { int wm, wn, tm, tn, pd, bk, ring; };
-// BM = wm*tm*16, BN = wn*tn*16; ids are stable (tests and tools name them)
-static const TileCfg kCfgs[] = {
-    {2, 2, 4, 4, 1, 32},  // 0: 128x128
-    {2, 2, 4, 2, 2, 32},  // 1: 128x64
-    {2, 2, 2, 2, 2, 32},  // 2: 64x64
-    {2, 2, 2, 1, 2, 32},  // 3: 64x32
-    {2, 2, 1, 2, 2, 32},  // 4: 32x64
-    {2, 2, 1, 1, 2, 32},  // 5: 32x32
-    {1, 4, 1, 1, 2, 32},  // 6: 16x64
-    {1, 4, 1, 2, 2, 32},  // 7: 16x128
-    {1, 4, 2, 2, 2, 32},  // 8: 32x128
-    {4, 2, 2, 4, 1, 32},  // 9: 128x128, 8 waves (32x64 wave tiles, fragment-first): the large-problem default
-    {2, 4, 4, 2, 1, 32},  // 10: 128x128, 8 waves (64x32 wave tiles, fragment-first)
-    {4, 1, 2, 2, 2, 32},  // 11: 128x32, waves stacked along M (32x32 wave tiles): M-covering for M <= 128
-    {4, 1, 2, 4, 2, 32},  // 12: 128x64, waves stacked along M (32x64 wave tiles)
-    {4, 1, 1, 4, 2, 32},  // 13: 64x64, waves stacked along M (16x64 wave tiles): M-covering for M <= 64
-    {4, 2, 2, 2, 2, 32},  // 14: 128x64, 8 waves (32x32 wave tiles)
-    {8, 1, 2, 2, 2, 32},  // 15: 256x32, 8 waves stacked along M
-    {8, 1, 2, 4, 1, 32},  // 16: 256x64, 8 waves stacked along M (32x64 wave tiles)
-    {8, 1, 1, 4, 2, 32},  // 17: 128x64, 8 waves stacked along M (16x64 wave tiles)
-    {2, 2, 2, 2, 1, 32},  // 18: 64x64, 1-deep prefetch
-    {2, 2, 1, 1, 1, 32},  // 19: 32x32, 1-deep prefetch
-    {4, 1, 2, 4, 1, 32},  // 20: 128x64 stacked, 1-deep prefetch
-    {4, 1, 1, 2, 2, 32},  // 21: 64x32, waves stacked along M (16x32 wave tiles)
-    {2, 2, 1, 4, 2, 32},  // 22: 32x128 (16x64 wave tiles): M-covering for M <= 32
-    {1, 4, 2, 1, 2, 32},  // 23: 32x64, waves along N (32x16 wave tiles)
-    {2, 2, 1, 1, 2, 64},  // 24: 32x32, K step 64 (half the barriers / address arithmetic per FLOP)
-    {2, 2, 1, 1, 1, 64},  // 25: 32x32, K step 64, 1-deep prefetch
-    {2, 2, 2, 2, 1, 64},  // 26: 64x64, K step 64, 1-deep prefetch
-    {4, 1, 2, 2, 1, 64},  // 27: 128x32 stacked, K step 64, 1-deep prefetch
-    {2, 2, 1, 2, 1, 64},  // 28: 32x64, K step 64, 1-deep prefetch
-    {4, 2, 2, 2, 1, 64},  // 29: 128x64, 8 waves, K step 64, 1-deep prefetch
-    // ring variants (both operands by LDS-DMA into 3 / 4 stages, prologues applied to the fragments); need K % 32 == 0
-    {2, 2, 1, 1, 1, 32, 3},  // 30: 32x32, 3 stages (2 units in flight, 5 workgroups per CU)
-    {2, 2, 1, 1, 1, 32, 4},  // 31: 32x32, 4 stages (3 units in flight, 4 workgroups per CU)
-    {2, 2, 1, 2, 1, 32, 3},  // 32: 32x64, 3 stages
-    {2, 2, 2, 1, 1, 32, 3},  // 33: 64x32, 3 stages
-    {2, 2, 2, 2, 1, 32, 3},  // 34: 64x64, 3 stages
-    {2, 2, 1, 2, 1, 32, 4},  // 35: 32x64, 4 stages
-    // the throughput-regime tile: 8 waves of 64x64 wave tiles, both operands by LDS-DMA into 3 stages, fragments read one k group ahead (BIG in the kernel)
-    {4, 2, 4, 4, 1, 32, 3},  // 36: 256x128
-    // the bf16 fast mode's throughput tile: 2 x 4 waves of 128x64 wave tiles, two 64 KiB LDS buffers, phases of 16 MFMAs with the two wave groups one barrier apart (PP in the kernel)
-    {2, 4, 8, 4, 1, 32, 2},  // 37: 256x256 (bf16 operands only)
+// The tile table: ONE row per tile id says what the tile is and which variants of it are compiled.  The host's view (tile sizes, limits, error messages) and
+// the dispatch from an id to an instantiation are derived from it: a new tile is one new row.  Ids are stable (tests, tools and profiles/ name them).
+enum : unsigned {
+    V_F32 = 1,         // the register-staged fp32 kernel (operand prologues none / GRN / LayerNorm)
+    V_CONV = 2,        // its implicit-convolution prologue -- register-staged, and on the direct-to-LDS twin when the tile has one
+    V_DMA = 4,         // the direct-to-LDS twin (needs pd 1, bk 32), taken when K % 32 == 0
+    V_DMA_PLAIN = 8,   // (with V_DMA) the twin exists for plain GEMMs only
+    V_RING = 16,       // the fp32 LDS-DMA ring kernel (ring stages > 0, 2 x 2 waves; prologues none / GRN / LayerNorm / GRN from raw statistics); needs K % 32 == 0
+    V_BF16 = 32,       // bf16 operands: on the ring when the row has stages, else on the direct-to-LDS twin
+    V_TAIL = 64,       // the fused sampling tail (scalar and request form): on the direct-to-LDS twin when the row has one (there also with bf16 operands), else register-staged
 };
-static const int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
+struct Tile {
+    int wm, wn, tm, tn;  // wave grid, wave tile in 16x16 blocks
+    int pd, bk, ring;    // register prefetch depth, K step in floats, LDS ring stages (0 = no ring)
+    unsigned var;
+    constexpr bool has(unsigned v) const { return (var & v) == v; }
+    constexpr int waves() const { return wm * wn; }
+    constexpr TileRes res(int apro = 0) const { return tile_res(wm, wn, tm, tn, apro, false, bk, ring); }
+};
+static constexpr Tile kCfgs[] = {
+    {2, 2, 4, 4, 1, 32, 0, V_F32 | V_DMA | V_DMA_PLAIN},  // 0: 128x128 (the twin: 64x64 wave tiles on 4 waves, two workgroups per CU; it spills with a prologue's extra operands)
+    {2, 2, 4, 2, 2, 32, 0, V_F32},                         // 1: 128x64
+    {2, 2, 2, 2, 2, 32, 0, V_F32 | V_CONV | V_TAIL},       // 2: 64x64 (fused tail: small heads, and tile 18's stand-in when K % 32 != 0)
+    {2, 2, 2, 1, 2, 32, 0, V_F32},                         // 3: 64x32
+    {2, 2, 1, 2, 2, 32, 0, V_F32},                         // 4: 32x64
+    {2, 2, 1, 1, 2, 32, 0, V_F32 | V_CONV},                // 5: 32x32
+    {1, 4, 1, 1, 2, 32, 0, V_F32},                         // 6: 16x64
+    {1, 4, 1, 2, 2, 32, 0, V_F32},                         // 7: 16x128
+    {1, 4, 2, 2, 2, 32, 0, V_F32},                         // 8: 32x128
+    {4, 2, 2, 4, 1, 32, 0, V_F32 | V_CONV | V_TAIL},       // 9: 128x128, 8 waves (32x64 wave tiles, fragment-first): the large-problem default
+    {2, 4, 4, 2, 1, 32, 0, V_F32 | V_CONV | V_DMA | V_BF16},  // 10: 128x128, 8 waves (64x32 wave tiles, fragment-first); large-problem workhorse behind a prologue
+    {4, 1, 2, 2, 2, 32, 0, V_F32},                         // 11: 128x32, waves stacked along M (32x32 wave tiles): M-covering for M <= 128
+    {4, 1, 2, 4, 2, 32, 0, V_F32},                         // 12: 128x64, waves stacked along M (32x64 wave tiles)
+    {4, 1, 1, 4, 2, 32, 0, V_F32},                         // 13: 64x64, waves stacked along M (16x64 wave tiles): M-covering for M <= 64
+    {4, 2, 2, 2, 2, 32, 0, V_F32 | V_CONV | V_TAIL},       // 14: 128x64, 8 waves (32x32 wave tiles)
+    {8, 1, 2, 2, 2, 32, 0, V_F32},                         // 15: 256x32, 8 waves stacked along M
+    {8, 1, 2, 4, 1, 32, 0, V_F32},                         // 16: 256x64, 8 waves stacked along M (32x64 wave tiles)
+    {8, 1, 1, 4, 2, 32, 0, V_F32},                         // 17: 128x64, 8 waves stacked along M (16x64 wave tiles)
+    {2, 2, 2, 2, 1, 32, 0, V_F32 | V_CONV | V_DMA | V_BF16 | V_TAIL},  // 18: 64x64, 1-deep prefetch; large-problem workhorse for plain operands, the product's head tile
+    {2, 2, 1, 1, 1, 32, 0, V_F32 | V_CONV | V_DMA | V_BF16},  // 19: 32x32, 1-deep prefetch
+    {4, 1, 2, 4, 1, 32, 0, V_F32},                         // 20: 128x64 stacked, 1-deep prefetch
+    {4, 1, 1, 2, 2, 32, 0, V_F32},                         // 21: 64x32, waves stacked along M (16x32 wave tiles)
+    {2, 2, 1, 4, 2, 32, 0, V_F32},                         // 22: 32x128 (16x64 wave tiles): M-covering for M <= 32
+    {1, 4, 2, 1, 2, 32, 0, V_F32},                         // 23: 32x64, waves along N (32x16 wave tiles)
+    {2, 2, 1, 1, 2, 64, 0, V_F32},                         // 24: 32x32, K step 64 (half the barriers / address arithmetic per FLOP)
+    {2, 2, 1, 1, 1, 64, 0, V_F32},                         // 25: 32x32, K step 64, 1-deep prefetch
+    {2, 2, 2, 2, 1, 64, 0, V_F32},                         // 26: 64x64, K step 64, 1-deep prefetch
+    {4, 1, 2, 2, 1, 64, 0, V_F32},                         // 27: 128x32 stacked, K step 64, 1-deep prefetch
+    {2, 2, 1, 2, 1, 64, 0, V_F32},                         // 28: 32x64, K step 64, 1-deep prefetch
+    {4, 2, 2, 2, 1, 64, 0, V_F32},                         // 29: 128x64, 8 waves, K step 64, 1-deep prefetch
+    // ring variants (both operands by LDS-DMA into 3 / 4 stages, prologues applied to the fragments); need K % 32 == 0
+    {2, 2, 1, 1, 1, 32, 3, V_RING | V_BF16},  // 30: 32x32, 3 stages (2 units in flight, 5 workgroups per CU)
+    {2, 2, 1, 1, 1, 32, 4, V_RING | V_BF16},  // 31: 32x32, 4 stages (3 units in flight, 4 workgroups per CU)
+    {2, 2, 1, 2, 1, 32, 3, V_RING | V_BF16},  // 32: 32x64, 3 stages
+    {2, 2, 2, 1, 1, 32, 3, V_RING | V_BF16},  // 33: 64x32, 3 stages
+    {2, 2, 2, 2, 1, 32, 3, V_RING | V_BF16},  // 34: 64x64, 3 stages
+    {2, 2, 1, 2, 1, 32, 4, V_RING | V_BF16},  // 35: 32x64, 4 stages
+    // the throughput-regime tile: 8 waves of 64x64 wave tiles, both operands by LDS-DMA into 3 stages, fragments read one k group ahead (BIG in the kernel)
+    {4, 2, 4, 4, 1, 32, 3, V_BF16},  // 36: 256x128 (bf16 operands only: in fp32 it measured 4-6 % behind the 64x64 tile, profiles/r04_gemm_big_tile_sweep.txt)
+    // the bf16 fast mode's throughput tile: 2 x 4 waves of 128x64 wave tiles, two 64 KiB LDS buffers, phases of 16 MFMAs with the two wave groups one barrier apart (PP in the kernel)
+    {2, 4, 8, 4, 1, 32, 2, V_BF16},  // 37: 256x256 ping-pong (bf16 operands only)
+};
+static constexpr int kNumCfgs = sizeof(kCfgs) / sizeof(kCfgs[0]);
+using TileIds = std::make_integer_sequence<int, kNumCfgs>;
 int gemm_num_tile_configs() { return kNumCfgs; }
-
-// tile configs that carry the implicit-convolution variant (ids 2, 5, 9, 10, 14, 18)
-template <int WM, int WN, int TM, int TN, int PD, int BK>
-static constexpr bool conv_tile() {
-    return BK == 32 && ((WM == 2 && WN == 2 && TM == TN && (TM == 1 || TM == 2)) || (WM * WN == 8 && WM * TM == 8 && WN * TN == 8) || (WM == 4 && WN == 2 && TM == 2 && TN == 2));
+static bool cfg_has(int cfg, unsigned v) { return cfg >= 0 && cfg < kNumCfgs && kCfgs[cfg].has(v); }
+// "10, 18, 19, 30..37": the ids that carry variant v, for the error messages
+static std::string ids_with(unsigned v) {
+    std::string s;
+    for (int i = 0; i < kNumCfgs; ++i) {
+        if (!kCfgs[i].has(v)) continue;
+        int j = i;
+        while (cfg_has(j + 1, v)) ++j;
+        s += (s.empty() ? "" : ", ") + std::to_string(i);
+        if (j > i) s += (j > i + 1 ? ".." : ", ") + std::to_string(j);
+        i = j;
+    }
+    return s;
 }
-static bool conv_cfg(int cfg) { return cfg == 2 || cfg == 5 || cfg == 9 || cfg == 10 || cfg == 14 || cfg == 18 || cfg == 19; }
 
-// tile configs that carry the direct-to-LDS (DMA) twin: the two large-problem workhorses (ids 10 and 18) and the 1-deep 32x32 tile (id 19)
-template <int WM, int WN, int TM, int TN, int PD, int BK>
-static constexpr bool dma_tile() {
-    return BK == 32 && PD == 1 && ((WM == 2 && WN == 4 && TM == 4 && TN == 2) || (WM == 2 && WN == 2 && TM == 2 && TN == 2) || (WM == 2 && WN == 2 && TM == 1 && TN == 1) ||
-                                   (WM == 2 && WN == 2 && TM == 4 && TN == 4));  // (id 0: 128x128 on 4 waves of 64x64 wave tiles, two workgroups per CU)
-}
 static std::atomic<int> g_gemm_raster_gm{8};  // tile rows per rasterisation group (0 = plain m-fastest); test hook
 extern "C" int paella_test_gemm_raster(int gm) { g_gemm_raster_gm = gm; return PAELLA_OK; }
 static std::atomic<int> g_gemm_dma{1};  // test hook (test_hooks.h): 0 = always the register-staged kernels
@@ -1569,111 +1605,109 @@ template <> struct RingEpi<1> { using set = EpiSet<EPI_BR, EPI_BRS, EPI_BRT, EPI
 template <> struct RingEpi<2> { using set = EpiSet<EPI_B>; };
 template <> struct RingEpi<4> { using set = EpiSet<EPI_BR, EPI_BRS, EPI_BRT, EPI_BRST>; };
 
-template <int TM, int TN, int APRO, int RING, int EPI>
-static bool launch_ring_if(int cls, const GemmArgs& g, const SkPlan& p, unsigned G, float* slabs, unsigned* tickets, unsigned slab_bytes, hipStream_t st) {
+// what a launch carries besides its tile: the arguments, the plan and the stream-K workspace
+struct Launch {
+    const GemmArgs& g;
+    const SkPlan& p;
+    float* slabs;
+    unsigned* tickets;
+    unsigned slab_bytes;
+    hipStream_t st;
+};
+// the ONE place where a table row becomes the kernel's template arguments
+template <int ID, int APRO, bool TAIL = false, bool DMA = false, int RING = 0, bool BF = false, int EPI = EPI_RUNTIME, bool REQ = false>
+static void launch_kernel(const Launch& l) {
+    constexpr Tile t = kCfgs[ID];
+    hipLaunchKernelGGL((gemm_nt_kernel<t.wm, t.wn, t.tm, t.tn, t.pd, APRO, TAIL, t.bk, DMA, RING, BF, EPI, REQ>), dim3(l.p.G), dim3(64 * t.waves()), 0, l.st, l.g, l.p, l.slabs,
+                       l.tickets, l.slab_bytes);
+}
+
+template <int ID, int APRO, int EPI>
+static bool launch_ring_if(int cls, const Launch& l) {
     if (cls != EPI) return false;
-    hipLaunchKernelGGL((gemm_nt_kernel<2, 2, TM, TN, 1, APRO, false, 32, false, RING, false, EPI>), dim3(G), dim3(256), 0, st, g, p, slabs, tickets, slab_bytes);
+    launch_kernel<ID, APRO, false, false, kCfgs[ID].ring, false, EPI>(l);
     g_last_epi = EPI;
     return true;
 }
-template <int TM, int TN, int APRO, int RING, int... C>
-static void launch_ring_epi(EpiSet<C...>, const GemmArgs& g, const SkPlan& p, unsigned G, float* slabs, unsigned* tickets, unsigned slab_bytes, hipStream_t st) {
-    const int cls = g_gemm_epi_spec ? epi_class(g) : EPI_RUNTIME;
-    if (!(launch_ring_if<TM, TN, APRO, RING, C>(cls, g, p, G, slabs, tickets, slab_bytes, st) || ...))
-        launch_ring_if<TM, TN, APRO, RING, EPI_RUNTIME>(EPI_RUNTIME, g, p, G, slabs, tickets, slab_bytes, st);
+template <int ID, int APRO, int... C>
+static void launch_ring_epi(EpiSet<C...>, const Launch& l) {
+    const int cls = g_gemm_epi_spec ? epi_class(l.g) : EPI_RUNTIME;
+    if (!(launch_ring_if<ID, APRO, C>(cls, l) || ...)) launch_ring_if<ID, APRO, EPI_RUNTIME>(EPI_RUNTIME, l);
 }
-template <int TM, int TN, int RING, int APRO>
-static void launch_ring_apro(const GemmArgs& g, const SkPlan& p, unsigned G, float* slabs, unsigned* tickets, unsigned slab_bytes, hipStream_t st) {
-    using set = typename std::conditional<TM == 1 && TN == 1, typename RingEpi<APRO>::set, EpiSet<>>::type;  // (only the 32x32 ring tiles are specialised)
-    launch_ring_epi<TM, TN, APRO, RING>(set{}, g, p, G, slabs, tickets, slab_bytes, st);
+template <int ID, int APRO>
+static void launch_ring_apro(const Launch& l) {
+    using set = typename std::conditional<kCfgs[ID].tm * kCfgs[ID].tn == 1, typename RingEpi<APRO>::set, EpiSet<>>::type;  // (only the 32x32 ring tiles are specialised)
+    launch_ring_epi<ID, APRO>(set{}, l);
 }
-
-template <int TM, int TN, int RING>
-static void launch_ring(const GemmArgs& g, const SkPlan& p, unsigned G, float* slabs, unsigned* tickets, unsigned slab_bytes, hipStream_t st) {
-    if (g.grn_gx)
-        launch_ring_apro<TM, TN, RING, 4>(g, p, G, slabs, tickets, slab_bytes, st);
-    else if (g.a_scale)
-        launch_ring_apro<TM, TN, RING, 1>(g, p, G, slabs, tickets, slab_bytes, st);
-    else if (g.ln_stats)
-        launch_ring_apro<TM, TN, RING, 2>(g, p, G, slabs, tickets, slab_bytes, st);
-    else
-        launch_ring_apro<TM, TN, RING, 0>(g, p, G, slabs, tickets, slab_bytes, st);
+template <int ID>
+static void launch_ring(const Launch& l) {
+    if (l.g.grn_gx) launch_ring_apro<ID, 4>(l);
+    else if (l.g.a_scale) launch_ring_apro<ID, 1>(l);
+    else if (l.g.ln_stats) launch_ring_apro<ID, 2>(l);
+    else launch_ring_apro<ID, 0>(l);
 }
 
-template <int WM, int WN, int TM, int TN, int PD, int BK>
-static void launch_one(const GemmArgs& g, const SkPlan& p, unsigned G, float* slabs, unsigned* tickets, unsigned slab_bytes, hipStream_t st) {
-    constexpr int NT = 64 * WM * WN;
-    if constexpr (dma_tile<WM, WN, TM, TN, PD, BK>()) {
-        constexpr bool plain_only = (WM * WN == 4 && TM * TN == 16);  // (the 4-wave 128x128 twin spills with a prologue's extra operands: plain GEMMs only)
-        if constexpr (plain_only) {
-            if (g_gemm_dma && g.K % BK == 0 && !g.cv.enabled && !g.a_scale && !g.ln_stats) {
-                hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, PD, 0, false, BK, true>), dim3(G), dim3(NT), 0, st, g, p, slabs, tickets, slab_bytes);
-                return;
+template <int ID>
+static void launch_one(const Launch& l) {
+    constexpr Tile t = kCfgs[ID];
+    const GemmArgs& g = l.g;
+    if constexpr (t.has(V_DMA | V_DMA_PLAIN)) {
+        if (g_gemm_dma && g.K % t.bk == 0 && !g.cv.enabled && !g.a_scale && !g.ln_stats) return launch_kernel<ID, 0, false, true>(l);
+    } else if constexpr (t.has(V_DMA)) {
+        if (g_gemm_dma && g.K % t.bk == 0) {  // no K tail: operands without a transform go global -> LDS directly
+            if constexpr (t.has(V_CONV)) {
+                if (g.cv.enabled) return launch_kernel<ID, 3, false, true>(l);
             }
-        } else if (g_gemm_dma && g.K % BK == 0) {  // no K tail: operands without a transform go global -> LDS directly
-            if (g.cv.enabled)
-                hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, PD, 3, false, BK, true>), dim3(G), dim3(NT), 0, st, g, p, slabs, tickets, slab_bytes);
-            else if (g.a_scale)
-                hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, PD, 1, false, BK, true>), dim3(G), dim3(NT), 0, st, g, p, slabs, tickets, slab_bytes);
-            else if (g.ln_stats)
-                hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, PD, 2, false, BK, true>), dim3(G), dim3(NT), 0, st, g, p, slabs, tickets, slab_bytes);
-            else
-                hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, PD, 0, false, BK, true>), dim3(G), dim3(NT), 0, st, g, p, slabs, tickets, slab_bytes);
-            return;
+            if (g.a_scale) return launch_kernel<ID, 1, false, true>(l);
+            if (g.ln_stats) return launch_kernel<ID, 2, false, true>(l);
+            return launch_kernel<ID, 0, false, true>(l);
         }
     }
-    if constexpr (conv_tile<WM, WN, TM, TN, PD, BK>()) {
-        if (g.cv.enabled) {
-            hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, PD, 3, false, BK>), dim3(G), dim3(NT), 0, st, g, p, slabs, tickets, slab_bytes);
-            return;
-        }
+    if constexpr (t.has(V_CONV)) {
+        if (g.cv.enabled) return launch_kernel<ID, 3>(l);
     }
-    if (g.a_scale)
-        hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, PD, 1, false, BK>), dim3(G), dim3(NT), 0, st, g, p, slabs, tickets, slab_bytes);
-    else if (g.ln_stats)
-        hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, PD, 2, false, BK>), dim3(G), dim3(NT), 0, st, g, p, slabs, tickets, slab_bytes);
-    else
-        hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, PD, 0, false, BK>), dim3(G), dim3(NT), 0, st, g, p, slabs, tickets, slab_bytes);
+    if (g.a_scale) launch_kernel<ID, 1>(l);
+    else if (g.ln_stats) launch_kernel<ID, 2>(l);
+    else launch_kernel<ID, 0>(l);
 }
 
-// ---- bf16 operands (GemmArgs::A16 / W16; the opt-in fast mode): the all-DMA variants of the same kernel ----
-template <int WM, int WN, int TM, int TN, bool DMAv, int RINGv>
-static void launch_bf(const GemmArgs& g, const SkPlan& p, unsigned G, float* slabs, unsigned* tickets, unsigned slab_bytes, hipStream_t st) {
-    constexpr int NT = 64 * WM * WN;
-    if (g.ln_stats)
-        hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, 1, 2, false, 32, DMAv, RINGv, true>), dim3(G), dim3(NT), 0, st, g, p, slabs, tickets, slab_bytes);
-    else
-        hipLaunchKernelGGL((gemm_nt_kernel<WM, WN, TM, TN, 1, 0, false, 32, DMAv, RINGv, true>), dim3(G), dim3(NT), 0, st, g, p, slabs, tickets, slab_bytes);
-}
-// tile configs that carry a bf16 variant: the direct-to-LDS twins (10, 18, 19), the ring tiles (30..36) and the ping-pong tile (37)
-static bool bf16_cfg(int cfg) { return cfg == 10 || cfg == 18 || cfg == 19 || (cfg >= 30 && cfg <= 37); }
-static bool launch_bf_cfg(int cfg, const GemmArgs& g, const SkPlan& p, unsigned G, float* slabs, unsigned* tickets, unsigned slab_bytes, hipStream_t st) {
-    switch (cfg) {
-        case 10: launch_bf<2, 4, 4, 2, true, 0>(g, p, G, slabs, tickets, slab_bytes, st); return true;
-        case 18: launch_bf<2, 2, 2, 2, true, 0>(g, p, G, slabs, tickets, slab_bytes, st); return true;
-        case 19: launch_bf<2, 2, 1, 1, true, 0>(g, p, G, slabs, tickets, slab_bytes, st); return true;
-        case 30: launch_bf<2, 2, 1, 1, false, 3>(g, p, G, slabs, tickets, slab_bytes, st); return true;
-        case 31: launch_bf<2, 2, 1, 1, false, 4>(g, p, G, slabs, tickets, slab_bytes, st); return true;
-        case 32: launch_bf<2, 2, 1, 2, false, 3>(g, p, G, slabs, tickets, slab_bytes, st); return true;
-        case 33: launch_bf<2, 2, 2, 1, false, 3>(g, p, G, slabs, tickets, slab_bytes, st); return true;
-        case 34: launch_bf<2, 2, 2, 2, false, 3>(g, p, G, slabs, tickets, slab_bytes, st); return true;
-        case 35: launch_bf<2, 2, 1, 2, false, 4>(g, p, G, slabs, tickets, slab_bytes, st); return true;
-        case 36: launch_bf<4, 2, 4, 4, false, 3>(g, p, G, slabs, tickets, slab_bytes, st); return true;
-        case 37: launch_bf<2, 4, 8, 4, false, 2>(g, p, G, slabs, tickets, slab_bytes, st); return true;
-        default: return false;
-    }
+// bf16 operands (GemmArgs::A16 / W16; the opt-in fast mode): the all-DMA variants of the same kernel
+template <int ID>
+static void launch_bf(const Launch& l) {
+    constexpr int RINGv = kCfgs[ID].ring;
+    if (l.g.ln_stats) launch_kernel<ID, 2, false, RINGv == 0, RINGv, true>(l);
+    else launch_kernel<ID, 0, false, RINGv == 0, RINGv, true>(l);
 }
 
-// ring tiles: both operands by LDS-DMA (whole K steps only), GRN side stage holds the scale rows of at most 8 consecutive samples
-static bool ring_ok(const GemmArgs& g, int BM) {
+// tile id -> its instantiations: a fold over the table's ids; `if constexpr` on the row's variants keeps the set of instantiations exactly what the table says
+template <int ID>
+static bool launch_tile_if(int cfg, bool bf, const Launch& l) {
+    if (cfg != ID) return false;
+    constexpr Tile t = kCfgs[ID];
+    static_assert(!t.has(V_DMA) || (t.has(V_F32) && t.pd == 1 && t.bk == 32 && t.ring == 0), "a direct-to-LDS twin belongs to a 1-deep, K-step-32 register-staged tile");
+    static_assert(!t.has(V_RING) || (t.ring > 0 && t.wm == 2 && t.wn == 2 && !t.has(V_F32)), "an fp32 ring tile has stages and 2 x 2 waves");
+    static_assert(!t.has(V_BF16) || ((t.ring > 0 || t.has(V_DMA)) && !t.has(V_DMA_PLAIN) && t.pd == 1 && t.bk == 32), "bf16 operands run on a ring or on a direct-to-LDS twin");
+    if (bf) {
+        if constexpr (t.has(V_BF16)) launch_bf<ID>(l);
+        else return false;
+    } else if constexpr (t.has(V_RING)) launch_ring<ID>(l);
+    else if constexpr (t.has(V_F32)) launch_one<ID>(l);
+    else return false;
+    return true;
+}
+template <int... ID>
+static bool launch_tile(std::integer_sequence<int, ID...>, int cfg, bool bf, const Launch& l) { return (launch_tile_if<ID>(cfg, bf, l) || ...); }
+
+// ring tiles: both operands by LDS-DMA (whole K steps only), and the GRN side stage holds the scale rows of a fixed number of consecutive samples
+static bool ring_ok(const GemmArgs& g, int cfg) {
     if (g.K % 32 || g.cv.enabled) return false;
-    const int side_samples = BM >= 256 ? 16 : 8;  // sample rows the GRN side stage holds (the 8-wave 256-row tile: 16)
-    if ((g.a_scale || g.grn_gx) && (BM - 1) / (g.a_rows_per_sample > 0 ? g.a_rows_per_sample : 1) + 2 > side_samples) return false;
+    const TileRes r = kCfgs[cfg].res();
+    if ((g.a_scale || g.grn_gx) && (r.BM - 1) / (g.a_rows_per_sample > 0 ? g.a_rows_per_sample : 1) + 2 > r.side_samples) return false;
     return true;
 }
 static inline long tiles_of_cfg(int c, int M, int N) {
-    const int BM = kCfgs[c].wm * kCfgs[c].tm * 16, BN = kCfgs[c].wn * kCfgs[c].tn * 16;
-    return (long)((M + BM - 1) / BM) * ((N + BN - 1) / BN);
+    const TileRes r = kCfgs[c].res();
+    return (long)((M + r.BM - 1) / r.BM) * ((N + r.BN - 1) / r.BN);
 }
 
 // Tile / workgroup-count choice, fitted to tools/gemm_tune.py sweeps on MI355X (profiles/r02_gemm_tile_sweep*.txt,
@@ -1791,6 +1825,22 @@ static int site_set(int M, int N, int K, int apro, int bf, int G, int cfg1) {
 // test hook (tests/test_kernel_resources.py): the table above, so that a CPU test can hold it against the occupancy the compiler actually produced
 extern "C" long paella_test_ring_resident(int cfg, int apro) { return (cfg >= 30 && cfg <= 35) ? ring_resident(cfg, apro) : -1; }
 
+// the common end of the two choosers: at most one workgroup per unit, and no more than the workspace serves
+static unsigned clamp_split(int cfg, int M, int N, long ktiles, long G, size_t slab_cap_bytes) {
+    const long T = tiles_of_cfg(cfg, M, N);
+    const long U = T * ktiles;
+    if (G > U) G = U;
+    if (G < 1) G = 1;
+    // workspace limits: partial tiles need 2 slab slots per workgroup and one ticket per tile
+    if (G != T) {
+        const TileRes r = kCfgs[cfg].res();
+        const size_t slot = (size_t)r.BM * r.BN * sizeof(float);
+        if (T > (long)kGemmMaxTickets || slot * 2 > slab_cap_bytes) G = T;
+        else if ((size_t)G * 2 * slot > slab_cap_bytes) G = (long)(slab_cap_bytes / (2 * slot));
+    }
+    return (unsigned)G;
+}
+
 static void choose_config(int M, int N, int K, int apro, bool ring_allowed, int force_ring, size_t slab_cap_bytes, int* cfg_out, unsigned* G_out) {
     // one consistent value per decision; force_ring: the caller needs THIS ring tile in the skinny class (its epilogue finishes GRN per tile)
     const int g_gemm_ring = ::g_gemm_ring.load(std::memory_order_relaxed) ? (force_ring > 0 ? force_ring : ::g_gemm_ring.load(std::memory_order_relaxed)) : 0;
@@ -1856,19 +1906,8 @@ static void choose_config(int M, int N, int K, int apro, bool ring_allowed, int 
             if (G > resident) G = resident;
         }
     }
-    const long T = tiles_of_cfg(cfg, M, N);
-    const long U = T * ktiles;
-    if (G > U) G = U;
-    if (G < 1) G = 1;
-    // workspace limits: partial tiles need 2 slab slots per workgroup and one ticket per tile
-    const int BM = kCfgs[cfg].wm * kCfgs[cfg].tm * 16, BN = kCfgs[cfg].wn * kCfgs[cfg].tn * 16;
-    if (G != T) {
-        const size_t slot = (size_t)BM * BN * sizeof(float);
-        if (T > (long)kGemmMaxTickets || slot * 2 > slab_cap_bytes) G = T;
-        else if ((size_t)G * 2 * slot > slab_cap_bytes) G = (long)(slab_cap_bytes / (2 * slot));
-    }
     *cfg_out = cfg;
-    *G_out = (unsigned)G;
+    *G_out = clamp_split(cfg, M, N, ktiles, G, slab_cap_bytes);
 }
 
 // Tile / workgroup-count choice for bf16 operands (the opt-in fast mode).  The matrix cores run 16x faster on the same LDS bytes, so what a tile costs
@@ -1880,7 +1919,7 @@ static std::atomic<int> g_bf16_rule{0};  // test hook (A/B of the rules below): 
 extern "C" int paella_test_gemm_bf16_rule(int mask) { g_bf16_rule = mask; return PAELLA_OK; }
 // A bf16 LayerNorm-consuming launch on this tile takes its row statistics from the row pre-pass only: the ping-pong tile always, the other 8-wave tiles when the
 // fp32 rows are there for the operand-side guard (they have no in-kernel ln_fix).  The 4-wave tiles (18, 19, 30..35) carry ln_fix and run without the pre-pass.
-static bool bf16_ln_needs_prepass(int cfg, bool a32) { return kCfgs[cfg].ring == 2 || (a32 && kCfgs[cfg].wm * kCfgs[cfg].wn == 8); }
+static bool bf16_ln_needs_prepass(int cfg, bool a32) { return kCfgs[cfg].ring == 2 || (a32 && kCfgs[cfg].waves() == 8); }
 // no_prepass_a32: 0 = the pre-pass is available; 1 / 2 = it does not fit the workspace, for a launch without / with the fp32 rows -- the rule then never picks a
 // tile that bf16_ln_needs_prepass() (the launcher would refuse it) and takes the 64x64 direct-to-LDS tile instead
 static void choose_config_bf16(int M, int N, int K, int apro, size_t slab_cap_bytes, int no_prepass_a32, int* cfg_out, unsigned* G_out) {
@@ -1939,18 +1978,8 @@ static void choose_config_bf16(int M, int N, int K, int apro, size_t slab_cap_by
         if (G > resident && G > Tc) G = resident;
     }
     if (apro == 2 && no_prepass_a32 && bf16_ln_needs_prepass(cfg, no_prepass_a32 == 2)) { cfg = 18; G = T64; }
-    const long T = tiles_of_cfg(cfg, M, N);
-    const long U = T * ktiles;
-    if (G > U) G = U;
-    if (G < 1) G = 1;
-    const int BM = kCfgs[cfg].wm * kCfgs[cfg].tm * 16, BN = kCfgs[cfg].wn * kCfgs[cfg].tn * 16;
-    if (G != T) {
-        const size_t slot = (size_t)BM * BN * sizeof(float);
-        if (T > (long)kGemmMaxTickets || slot * 2 > slab_cap_bytes) G = T;
-        else if ((size_t)G * 2 * slot > slab_cap_bytes) G = (long)(slab_cap_bytes / (2 * slot));
-    }
     *cfg_out = cfg;
-    *G_out = (unsigned)G;
+    *G_out = clamp_split(cfg, M, N, ktiles, G, slab_cap_bytes);
 }
 
 // ---------------------------------------------------------------------------
@@ -2087,6 +2116,53 @@ extern "C" int paella_prof_collect(double* total_ms, double* total_flops, double
     return PAELLA_OK;
 }
 
+// The stream-K plan of one launch of tile `cfg` on (at most) G workgroups, for both launch paths; the fused head + tail is the case G = tiles, stagger = 0, no
+// workspace.  Ranges that are not tile-aligned go through slabs + tickets: slab_bytes > 0 then, and the workspace must hold them.
+static int make_plan(const char* who, const GemmArgs& g, int cfg, bool bf, unsigned G, int stagger, bool have_ws, size_t slab_cap, SkPlan& p, unsigned& slab_bytes) {
+    const Tile& tc = kCfgs[cfg];
+    const int BM = tc.res().BM, BN = tc.res().BN;
+    p.tiles_m = (g.M + BM - 1) / BM;
+    p.tiles_n = (g.N + BN - 1) / BN;
+    const int bk_elems = bf ? 2 * tc.bk : tc.bk;  // a K step is tc.bk * 4 bytes per row
+    p.KT = (g.K + bk_elems - 1) / bk_elems;
+    const unsigned long long T = (unsigned long long)p.tiles_m * p.tiles_n;
+    const unsigned long long U = T * (unsigned long long)p.KT;
+    if (U >= (1ull << 31)) { paella_set_error("%s: problem too large (%llu work units)", who, U); return PAELLA_ERR_ARG; }
+    p.U = (unsigned)U;
+    if (G < 1) G = 1;
+    if (G > p.U) G = p.U;
+    if (g.ln_stats && p.tiles_m > 1) {
+        // the LayerNorm-on-load variant computes its row statistics once per workgroup: keep every range inside one tile
+        unsigned S = G / (unsigned)T;
+        if (S < 1) S = 1;
+        while (p.KT % (int)S) --S;
+        G = (unsigned)T * S;
+    }
+    slab_bytes = 0;
+    if (G != (unsigned)T) {  // ranges are not tile-aligned: partial tiles go through slabs + tickets
+        const unsigned long long need = 2ull * G * BM * BN * sizeof(float);
+        if (!have_ws || need > slab_cap || need >= (1ull << 31) || T > kGemmMaxTickets) {
+            paella_set_error("%s: split-K workspace too small (%llu slab bytes for %u workgroups, %llu tiles)", who, need, G, T);
+            return PAELLA_ERR_WORKSPACE;
+        }
+        slab_bytes = (unsigned)need;
+    }
+    p.q = p.U / G;
+    p.r = p.U % G;
+    p.G = G;
+    g_last_G = G; g_last_T = (long long)T; g_last_bf = bf;
+    p.dKT = fast_div_of((unsigned)p.KT); p.dTM = fast_div_of((unsigned)p.tiles_m); p.dQ = fast_div_of(p.q); p.dQ1 = fast_div_of(p.q + 1);
+    p.stagger = stagger;
+    // grouped rasterisation for launches with many tile rows and columns (test hook: paella_test_gemm_raster)
+    // (32-row tiles and skinny problems keep the plain order: their traffic is the weight panel, which m-fastest tiles share best --
+    // measured +2 % per image at batch 1 with groups there)
+    // The fused head + tail takes it as the unfused launches do: with K = c_out = 256 a tile moves 196 KB of operands for 4.2 MFLOP, and in plain m-fastest order no two
+    // tiles that run together share an activation panel -- the whole activation matrix crosses the fabric once per column tile (34 GB per launch at configs[2])
+    const int raster_gm = g_gemm_raster_gm;
+    p.gm = (raster_gm > 0 && BM >= 64 && p.tiles_m >= 4 * raster_gm && p.tiles_n >= 4) ? raster_gm : p.tiles_m;
+    return PAELLA_OK;
+}
+
 // `ws` = a split-K region: kGemmTicketBytes of tickets (zero when first handed over, see paella_workspace_init) followed
 // by slab space.  cfg < 0: heuristic.  splitk > 0: G = tiles * splitk (classic split-K); splitk < 0: G = -splitk workgroups.
 static const int kLnPrepassMinRows = 2048;  // from here up the LayerNorm row statistics are finished by one small launch instead of by every workgroup
@@ -2146,22 +2222,22 @@ static int launch_gemm_cfg_impl(const GemmArgs& g_in, int cfg, int splitk, void*
     if (cfg < 0 && bf) {
         choose_config_bf16(g.M, g.N, g.K, g.ln_stats ? 2 : 0, slab_cap, (g.ln_stats && !g.ln_row && !prepass_fits) ? (g.A ? 2 : 1) : 0, &cfg, &G);
     } else if (cfg < 0) {
-        choose_config(g.M, g.N, g.K, (g.a_scale || g.grn_gx) ? 1 : (g.ln_stats ? 2 : 0), ring_ok(g, 64), g.force_ring_cfg, slab_cap, &cfg, &G);
-        if (g.cv.enabled && !conv_cfg(cfg)) { paella_set_error("internal: heuristic picked tile %d without a convolution variant", cfg); return PAELLA_ERR_STATE; }
+        choose_config(g.M, g.N, g.K, (g.a_scale || g.grn_gx) ? 1 : (g.ln_stats ? 2 : 0), ring_ok(g, 34 /* the tallest ring tile the rules pick: 64 rows */), g.force_ring_cfg, slab_cap, &cfg, &G);
+        if (g.cv.enabled && !cfg_has(cfg, V_CONV)) { paella_set_error("internal: heuristic picked tile %d without a convolution variant", cfg); return PAELLA_ERR_STATE; }
     } else {
         if (cfg >= kNumCfgs) { paella_set_error("gemm: bad tile config %d", cfg); return PAELLA_ERR_ARG; }
         const long T = tiles_of_cfg(cfg, g.M, g.N);
         G = splitk < 0 ? (unsigned)(-splitk) : (unsigned)(T * (splitk < 1 ? 1 : splitk));
-        if (g.cv.enabled && !conv_cfg(cfg)) { paella_set_error("gemm: tile config %d has no implicit-convolution variant", cfg); return PAELLA_ERR_ARG; }
+        if (g.cv.enabled && !cfg_has(cfg, V_CONV)) { paella_set_error("gemm: tile config %d has no implicit-convolution variant (%s do)", cfg, ids_with(V_CONV).c_str()); return PAELLA_ERR_ARG; }
         // an explicit tile that needs the bf16 row pre-pass when it does not fit (above ~1.03 M rows in the model's split-K region): the 64x64 direct-to-LDS tile
         // with its in-kernel guard instead of a failed launch; same work split, counted in tiles of 64x64
-        if (bf && bf16_cfg(cfg) && g.ln_stats && !g.ln_row && !prepass_fits && bf16_ln_needs_prepass(cfg, g.A != nullptr)) {
+        if (bf && cfg_has(cfg, V_BF16) && g.ln_stats && !g.ln_row && !prepass_fits && bf16_ln_needs_prepass(cfg, g.A != nullptr)) {
             cfg = 18;
             if (splitk >= 0) G = (unsigned)(tiles_of_cfg(cfg, g.M, g.N) * (splitk < 1 ? 1 : splitk));
         }
     }
-    const TileCfg& tc = kCfgs[cfg];
-    const int BM = tc.wm * tc.tm * 16, BN = tc.wn * tc.tn * 16;
+    const Tile& tc = kCfgs[cfg];
+    const int BM = tc.res().BM, BN = tc.res().BN;
     g_last_cfg = cfg;
     // the 8-wave bf16 tiles have no in-kernel operand-side guard: the pre-pass it is, whatever M; the ping-pong tile carries ONLY the pre-pass form of the row statistics
     if (bf && g.ln_stats && !g.ln_row && bf16_ln_needs_prepass(cfg, g.A != nullptr)) {
@@ -2169,8 +2245,8 @@ static int launch_gemm_cfg_impl(const GemmArgs& g_in, int cfg, int splitk, void*
         const int rc = ln_prepass();
         if (rc != PAELLA_OK) return rc;
     }
-    if (bf && !bf16_cfg(cfg)) { paella_set_error("gemm: tile config %d has no bf16-operand variant (10, 18, 19, 30..37 do)", cfg); return PAELLA_ERR_ARG; }
-    if ((g.grn_gx || g.ep.grn_gx_out) && (!tc.ring || tc.wm * tc.wn == 8)) { paella_set_error("gemm: the in-epilogue / on-load GRN statistics need a ring tile (got tile %d)", cfg); return PAELLA_ERR_STATE; }
+    if (bf && !cfg_has(cfg, V_BF16)) { paella_set_error("gemm: tile config %d has no bf16-operand variant (%s do)", cfg, ids_with(V_BF16).c_str()); return PAELLA_ERR_ARG; }
+    if ((g.grn_gx || g.ep.grn_gx_out) && (!tc.ring || tc.waves() == 8)) { paella_set_error("gemm: the in-epilogue / on-load GRN statistics need a ring tile (got tile %d)", cfg); return PAELLA_ERR_STATE; }
     if (g.grn_gx && (!g.grn_gamma || !g.a_shift || !g.grn_part || g.grn_np <= 0 || g.a_scale || g.ln_stats || g.a_rows_per_sample % 16)) {
         paella_set_error("gemm: bad GRN-from-statistics operand description"); return PAELLA_ERR_ARG;
     }
@@ -2179,99 +2255,13 @@ static int launch_gemm_cfg_impl(const GemmArgs& g_in, int cfg, int splitk, void*
         paella_set_error("gemm: in-epilogue GRN needs tiles that cover whole samples (rows per sample 16 or %d, got %d) and grn_np = tiles_n * %d", BM, g.ep.grn_rps, tc.wn);
         return PAELLA_ERR_ARG;
     }
-    if (tc.ring && !ring_ok(g, BM)) { paella_set_error("gemm: tile config %d (LDS-DMA ring) needs K %% 32 == 0, no implicit convolution and <= 8 samples per tile", cfg); return PAELLA_ERR_ARG; }
+    if (tc.ring && !ring_ok(g, cfg)) { paella_set_error("gemm: tile config %d (LDS-DMA ring) needs K %% 32 == 0, no implicit convolution and <= 8 samples per tile", cfg); return PAELLA_ERR_ARG; }
     SkPlan p;
-    p.tiles_m = (g.M + BM - 1) / BM;
-    p.tiles_n = (g.N + BN - 1) / BN;
-    const int bk_elems = bf ? 2 * tc.bk : tc.bk;  // a K step is tc.bk * 4 bytes per row
-    p.KT = (g.K + bk_elems - 1) / bk_elems;
-    const unsigned long long T = (unsigned long long)p.tiles_m * p.tiles_n;
-    const unsigned long long U = T * (unsigned long long)p.KT;
-    if (U >= (1ull << 31)) { paella_set_error("gemm: problem too large (%llu work units)", U); return PAELLA_ERR_ARG; }
-    p.U = (unsigned)U;
-    if (G < 1) G = 1;
-    if (G > p.U) G = p.U;
-    if (g.ln_stats && p.tiles_m > 1) {
-        // the LayerNorm-on-load variant computes its row statistics once per workgroup: keep every range inside one tile
-        unsigned S = G / (unsigned)T;
-        if (S < 1) S = 1;
-        while (p.KT % (int)S) --S;
-        G = (unsigned)T * S;
-    }
     unsigned slab_bytes = 0;
-    if (G != (unsigned)T) {  // ranges are not tile-aligned: partial tiles go through slabs + tickets
-        const unsigned long long need = 2ull * G * BM * BN * sizeof(float);
-        if (!have_ws || need > slab_cap || need >= (1ull << 31) || T > kGemmMaxTickets) {
-            paella_set_error("gemm: split-K workspace too small (%llu slab bytes for %u workgroups, %llu tiles)", need, G, T);
-            return PAELLA_ERR_WORKSPACE;
-        }
-        slab_bytes = (unsigned)need;
-    }
-    p.q = p.U / G;
-    p.r = p.U % G;
-    p.G = G;
-    g_last_G = G; g_last_T = (long long)T; g_last_bf = bf;
-    p.dKT = fast_div_of((unsigned)p.KT); p.dTM = fast_div_of((unsigned)p.tiles_m); p.dQ = fast_div_of(p.q); p.dQ1 = fast_div_of(p.q + 1);
-    // grouped rasterisation for launches with many tile rows and columns (test hook: paella_test_gemm_raster)
-    // (32-row tiles and skinny problems keep the plain order: their traffic is the weight panel, which m-fastest tiles share best --
-    // measured +2 % per image at batch 1 with groups there)
-    p.stagger = g_gemm_big_stagger.load(std::memory_order_relaxed);
-    const int raster_gm = g_gemm_raster_gm;
-    p.gm = (raster_gm > 0 && BM >= 64 && p.tiles_m >= 4 * raster_gm && p.tiles_n >= 4) ? raster_gm : p.tiles_m;
-    unsigned* tickets = have_ws ? reinterpret_cast<unsigned*>(ws) : nullptr;
-    float* slabs = have_ws ? reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + kGemmTicketBytes) : nullptr;
-#define GEMM_CASE(id, WMv, WNv, TMv, TNv, PDv) \
-    case id: launch_one<WMv, WNv, TMv, TNv, PDv, 32>(g, p, G, slabs, tickets, slab_bytes, st); break;
-#define GEMM_CASE64(id, WMv, WNv, TMv, TNv, PDv) \
-    case id: launch_one<WMv, WNv, TMv, TNv, PDv, 64>(g, p, G, slabs, tickets, slab_bytes, st); break;
-    if (bf) {
-        (void)launch_bf_cfg(cfg, g, p, G, slabs, tickets, slab_bytes, st);
-        LAUNCH_CHECK_RET();
-        return PAELLA_OK;
-    }
-    switch (cfg) {
-        GEMM_CASE(0, 2, 2, 4, 4, 1)
-        GEMM_CASE(1, 2, 2, 4, 2, 2)
-        GEMM_CASE(2, 2, 2, 2, 2, 2)
-        GEMM_CASE(3, 2, 2, 2, 1, 2)
-        GEMM_CASE(4, 2, 2, 1, 2, 2)
-        GEMM_CASE(5, 2, 2, 1, 1, 2)
-        GEMM_CASE(6, 1, 4, 1, 1, 2)
-        GEMM_CASE(7, 1, 4, 1, 2, 2)
-        GEMM_CASE(8, 1, 4, 2, 2, 2)
-        GEMM_CASE(9, 4, 2, 2, 4, 1)
-        GEMM_CASE(10, 2, 4, 4, 2, 1)
-        GEMM_CASE(11, 4, 1, 2, 2, 2)
-        GEMM_CASE(12, 4, 1, 2, 4, 2)
-        GEMM_CASE(13, 4, 1, 1, 4, 2)
-        GEMM_CASE(14, 4, 2, 2, 2, 2)
-        GEMM_CASE(15, 8, 1, 2, 2, 2)
-        GEMM_CASE(16, 8, 1, 2, 4, 1)
-        GEMM_CASE(17, 8, 1, 1, 4, 2)
-        GEMM_CASE(18, 2, 2, 2, 2, 1)
-        GEMM_CASE(19, 2, 2, 1, 1, 1)
-        GEMM_CASE(20, 4, 1, 2, 4, 1)
-        GEMM_CASE(21, 4, 1, 1, 2, 2)
-        GEMM_CASE(22, 2, 2, 1, 4, 2)
-        GEMM_CASE(23, 1, 4, 2, 1, 2)
-        GEMM_CASE64(24, 2, 2, 1, 1, 2)
-        GEMM_CASE64(25, 2, 2, 1, 1, 1)
-        GEMM_CASE64(26, 2, 2, 2, 2, 1)
-        GEMM_CASE64(27, 4, 1, 2, 2, 1)
-        GEMM_CASE64(28, 2, 2, 1, 2, 1)
-        GEMM_CASE64(29, 4, 2, 2, 2, 1)
-        case 30: launch_ring<1, 1, 3>(g, p, G, slabs, tickets, slab_bytes, st); break;
-        case 31: launch_ring<1, 1, 4>(g, p, G, slabs, tickets, slab_bytes, st); break;
-        case 32: launch_ring<1, 2, 3>(g, p, G, slabs, tickets, slab_bytes, st); break;
-        case 33: launch_ring<2, 1, 3>(g, p, G, slabs, tickets, slab_bytes, st); break;
-        case 34: launch_ring<2, 2, 3>(g, p, G, slabs, tickets, slab_bytes, st); break;
-        case 35: launch_ring<1, 2, 4>(g, p, G, slabs, tickets, slab_bytes, st); break;
-        case 36: paella_set_error("gemm: tile config 36 (256x128) exists for bf16 operands only (in fp32 it measured 4-6 %% behind the 64x64 tile: profiles/r04_gemm_big_tile_sweep.txt)"); return PAELLA_ERR_ARG;
-        case 37: paella_set_error("gemm: tile config 37 (256x256 ping-pong) exists for bf16 operands only"); return PAELLA_ERR_ARG;
-        default: paella_set_error("gemm: bad tile config %d", cfg); return PAELLA_ERR_ARG;
-    }
-#undef GEMM_CASE
-#undef GEMM_CASE64
+    const int rc = make_plan("gemm", g, cfg, bf, G, g_gemm_big_stagger.load(std::memory_order_relaxed), have_ws, slab_cap, p, slab_bytes);
+    if (rc != PAELLA_OK) return rc;
+    const Launch l{g, p, have_ws ? reinterpret_cast<float*>(reinterpret_cast<char*>(ws) + kGemmTicketBytes) : nullptr, have_ws ? reinterpret_cast<unsigned*>(ws) : nullptr, slab_bytes, st};
+    if (!launch_tile(TileIds{}, cfg, bf, l)) { paella_set_error("gemm: tile config %d (%dx%d) exists for bf16 operands only", cfg, BM, BN); return PAELLA_ERR_ARG; }
     LAUNCH_CHECK_RET();
     return PAELLA_OK;
 }
@@ -2290,10 +2280,28 @@ extern "C" int paella_test_gemm_tail_tile(int cfg) {
 }
 int gemm_tail_config(int M, int N, bool bf) { return bf ? 18 : (tiles_of_cfg(9, M, N) >= 256 ? g_tail_tile.load() : 2); }  // (bf16 operands: the 64x64 direct-to-LDS tile only)
 int gemm_tail_tiles_n(int M, int N, bool bf) {
-    const TileCfg& tc = kCfgs[gemm_tail_config(M, N, bf)];
-    const int BN = tc.wn * tc.tn * 16;
+    const int BN = kCfgs[gemm_tail_config(M, N, bf)].res().BN;
     return (N + BN - 1) / BN;
 }
+// tile id -> its TAIL instantiations, in the scalar and in the request form (REQ, the last template argument): a compile-time variant, the scalar instantiations keep their code
+template <int ID, bool DMAv, bool BFv>
+static void launch_tail_kernel(bool req, const Launch& l) {
+    if (req) launch_kernel<ID, 0, true, DMAv, 0, BFv, EPI_RUNTIME, true>(l);
+    else launch_kernel<ID, 0, true, DMAv, 0, BFv>(l);
+}
+template <int ID>
+static bool launch_tail_if(int id, bool bf, bool req, const Launch& l) {
+    constexpr Tile t = kCfgs[ID];
+    if constexpr (t.has(V_TAIL)) {
+        static_assert(t.has(V_F32) && t.bk == 32, "a fused tail belongs to a register-staged tile with K step 32");
+        if (id != ID) return false;
+        if (!bf) { launch_tail_kernel<ID, t.has(V_DMA), false>(req, l); return true; }
+        if constexpr (t.has(V_DMA | V_BF16)) { launch_tail_kernel<ID, true, true>(req, l); return true; }
+    }
+    return false;
+}
+template <int... ID>
+static bool launch_tail(std::integer_sequence<int, ID...>, int id, bool bf, bool req, const Launch& l) { return (launch_tail_if<ID>(id, bf, req, l) || ...); }
 static int launch_gemm_tail_impl(const GemmArgs& g, hipStream_t st);
 int launch_gemm_tail(const GemmArgs& g_in, hipStream_t st) {
     GemmArgs g = g_in;
@@ -2318,41 +2326,19 @@ static int launch_gemm_tail_impl(const GemmArgs& g, hipStream_t st) {
     if (bf && (!g.A16 || !g.W16 || !gemm_bf16_ok(g.K, g.lda, g.ldw))) { paella_set_error("gemm_tail: bf16 operands need A16 and W16, K %% 64 == 0, lda / ldw %% 8 == 0"); return PAELLA_ERR_ARG; }
     const int cfg = gemm_tail_config(g.M, g.N, bf);
     g_last_cfg = cfg;
-    const TileCfg& tc = kCfgs[cfg];
-    const int BM = tc.wm * tc.tm * 16, BN = tc.wn * tc.tn * 16;
-    SkPlan p;
-    p.tiles_m = (g.M + BM - 1) / BM;
-    p.tiles_n = (g.N + BN - 1) / BN;
-    p.KT = bf ? g.K / 64 : (g.K + 31) / 32;
-    const unsigned long long T = (unsigned long long)p.tiles_m * p.tiles_n;
-    if (T * (unsigned long long)p.KT >= (1ull << 31)) { paella_set_error("gemm_tail: problem too large"); return PAELLA_ERR_ARG; }
-    p.U = (unsigned)(T * p.KT);
     // One whole tile per workgroup.  Measured and NOT kept (profiles/r04_head_tail_and_same_box_ab.txt): 512 persistent workgroups walking T / 512 tiles each (round 3: neutral),
     // and the same with the second workgroup of every CU started half a tile period late so that its Philox / log epilogue would run under the other one's main
     // loop (round 4: 20.21 vs 20.21 images/s at configs[2], 112.9-113.3 at batch 32 for every variant) -- the launch is not limited by phase alignment.
-    const unsigned long long G = T;
-    p.stagger = 0;
-    p.q = (unsigned)(p.U / G);
-    p.r = 0;
-    p.G = (unsigned)G;
-    g_last_G = (long long)G; g_last_T = (long long)T; g_last_bf = bf;
-    p.dKT = fast_div_of((unsigned)p.KT); p.dTM = fast_div_of((unsigned)p.tiles_m); p.dQ = fast_div_of(p.q); p.dQ1 = fast_div_of(p.q + 1);
-    // grouped rasterisation as in the unfused launches: with K = c_out = 256 a tile moves 196 KB of operands for 4.2 MFLOP, and in plain m-fastest order no two
-    // tiles that run together share an activation panel -- the whole activation matrix crosses the fabric once per column tile (34 GB per launch at configs[2])
-    const int raster_gm = g_gemm_raster_gm;
-    p.gm = (raster_gm > 0 && BM >= 64 && p.tiles_m >= 4 * raster_gm && p.tiles_n >= 4) ? raster_gm : p.tiles_m;
-    // the same five tiles in the scalar and in the request form (REQ, the last template argument): a compile-time variant, the scalar instantiations keep their code
-#define TAIL_LAUNCH(THREADS, ...)                                                                                                                               \
-    do {                                                                                                                                                        \
-        if (g.rq.rows_per_sample > 0) hipLaunchKernelGGL((gemm_nt_kernel<__VA_ARGS__, EPI_RUNTIME, true>), dim3((unsigned)G), dim3(THREADS), 0, st, g, p, (float*)nullptr, (unsigned*)nullptr, 0u); \
-        else hipLaunchKernelGGL((gemm_nt_kernel<__VA_ARGS__>), dim3((unsigned)G), dim3(THREADS), 0, st, g, p, (float*)nullptr, (unsigned*)nullptr, 0u);                                            \
-    } while (0)
-    if (bf) TAIL_LAUNCH(256, 2, 2, 2, 2, 1, 0, true, 32, true, 0, true);
-    else if (cfg == 9) TAIL_LAUNCH(512, 4, 2, 2, 4, 1, 0, true, 32, false, 0, false);
-    else if (cfg == 14) TAIL_LAUNCH(512, 4, 2, 2, 2, 2, 0, true, 32, false, 0, false);
-    else if (cfg == 18 && g.K % 32 == 0 && g_gemm_dma) TAIL_LAUNCH(256, 2, 2, 2, 2, 1, 0, true, 32, true, 0, false);
-    else TAIL_LAUNCH(256, 2, 2, 2, 2, 2, 0, true, 32, false, 0, false);
-#undef TAIL_LAUNCH
+    SkPlan p;
+    unsigned slab_bytes = 0;
+    const int rc = make_plan("gemm_tail", g, cfg, bf, (unsigned)tiles_of_cfg(cfg, g.M, g.N), 0, false, 0, p, slab_bytes);
+    if (rc != PAELLA_OK) return rc;
+    // tile 18 runs its tail on the direct-to-LDS twin; with a K tail (or the twin switched off) the register-staged 64x64 tile 2 stands in for it: same tile, same plan
+    const int id = (cfg == 18 && !bf && !(g.K % 32 == 0 && g_gemm_dma)) ? 2 : cfg;
+    if (!launch_tail(TileIds{}, id, bf, g.rq.rows_per_sample > 0, Launch{g, p, nullptr, nullptr, 0u, st})) {
+        paella_set_error("internal: tile %d has no fused-tail variant for these operands (%s do)", id, ids_with(V_TAIL).c_str());
+        return PAELLA_ERR_STATE;
+    }
     LAUNCH_CHECK_RET();
     return PAELLA_OK;
 }

@@ -1,4 +1,4 @@
-// Device-side epilogue shared by the GEMM kernels (gemm.hip, gemm_bf16.hip).
+// Device-side epilogue of the GEMM kernels (gemm.hip).
 #pragma once
 #include "common.h"
 

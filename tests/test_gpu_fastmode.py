@@ -18,7 +18,7 @@ from tests.helpers import cond_for, to_dev, weights_for
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 
-BF16_TILES = [10, 18, 19, 30, 31, 32, 33, 34, 35, 36, 37]  # paella_amd/csrc/gemm.hip: bf16_cfg()
+BF16_TILES = [10, 18, 19, 30, 31, 32, 33, 34, 35, 36, 37]  # paella_amd/csrc/gemm.hip: the kCfgs rows with V_BF16
 
 
 def _p(t):
