@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PAELLA_ABI_VERSION 6
+#define PAELLA_ABI_VERSION 7
 
 #define PAELLA_OK 0
 #define PAELLA_ERR_ARG -1       /* invalid argument / unsupported shape */
@@ -211,6 +211,39 @@ int paella_unet_forward_sample_req(paella_unet* m, const int64_t* tokens, const 
                                    const uint64_t* seeds, const float* temperature, int rows_per_sample, uint64_t offset,
                                    const int64_t* init_noise, float t_next, int64_t* tokens_out, void* ws, size_t ws_bytes,
                                    void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Request stream (ABI 7): continuous batching.  The B slots of a fixed-shape batch hold requests that joined at different
+ * ticks and run different numbers of steps; one tick = paella_request_step + paella_unet_forward_sample_stream, the same
+ * launches whatever the slots hold, so ONE captured graph of a tick is replayed while requests come and go.  On top of the
+ * request-batch tables, three DEVICE tables with one entry per slot replace the last per-launch scalars:
+ *   step    int32 [B]  the request's OWN step index: the Philox step word of its categorical and renoise draws (was `offset`)
+ *   t_next  fp32  [B]  its renoise threshold at this step (was `t_next`); negative = no renoise at this step (u >= 0)
+ *   active  int32 [B]  0 = the slot holds no running request: its rows are computed and NOTHING is stored for them --
+ *                      tokens_out (and sampled_out) keep their previous content, so the stream runs in place
+ *                      (tokens_out == tokens) and a finished request's tokens stay in its slot until collected
+ * All three tables and init_noise (the renoise source of every slot) are required: NULL is PAELLA_ERR_ARG.  With
+ * step[b] = i, t_next[b] = t, active[b] = 1 for every b the tokens equal the *_req call with offset = i, t_next = t.
+ * ---------------------------------------------------------------------------------------------- */
+/* One tick of the slots' programs.  program fp32 [B, max_steps, 5], row j of slot b = (r, temperature, cfg, 1 - cfg, t_next)
+ * of its step j; pos int32 [B] cursors; len int32 [B] step counts.  For every slot: active[b] = 0 <= pos[b] < min(len[b],
+ * max_steps); an active slot gets r[b], temperature[b], pairs[b] (pairs may be NULL: no guidance), t_next[b] from row pos[b]
+ * and its cursor advances; an idle one gets r 0, temperature 1, pair (1, 0), t_next -1.  step[b] = pos[b] before the advance. */
+int paella_request_step(const float* program, int max_steps, int* pos, const int* len, int B, float* r, float* temperature,
+                        float* pairs, float* t_next, int* step, int* active, void* stream);
+/* paella_sample_tail_req in the stream form. */
+int paella_sample_tail_stream(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs,
+                              const float* temperature, const uint64_t* seeds, int rows_per_sample, const int* step,
+                              const float* t_next, const int* active, const int64_t* init_noise, int64_t* tokens_out,
+                              int64_t* sampled_out, void* stream);
+/* paella_unet_forward_sample_req in the stream form; tokens_out may be `tokens` (the token gather at the head of the forward
+ * and the token store at its tail are different kernels of one stream).  Bit-identical to forward_shared_req +
+ * sample_tail_stream. */
+int paella_unet_forward_sample_stream(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                      const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
+                                      const uint64_t* seeds, const float* temperature, int rows_per_sample, const int* step,
+                                      const float* t_next, const int* active, const int64_t* init_noise, int64_t* tokens_out,
+                                      void* ws, size_t ws_bytes, void* stream);
 
 /* x, random_x, mask int64 [B, per_sample]; t fp32 [B].  mask_in NULL -> mask = (u <= t[b]) with u = rand_u
  * (caller noise, [B, per_sample]) or Philox; random_x NULL -> Philox randint(0, num_labels). */

@@ -6,6 +6,8 @@ Public surface (mirrors the reference's Python API):
     sample                    reference src/utils.py:35
     sample_distributed        reference src_distributed/utils.py:97
     sample_requests           (extension) B independent requests -- own seed, guidance, temperature -- in one batch; GraphRequestSampler = its captured form
+    RequestStream             (extension) continuous batching: requests join and leave a fixed-shape batch at step boundaries, each with its own step count,
+                              start tokens and timestep range (request_program builds one request's schedule); one captured single-step graph serves them all
     replace_attention_layers  reference utils/alter_attention.py:45
     load_conditional_models   reference src_distributed/utils.py:65 (+ embed_prompts, load_checkpoint: paella_amd/conditioning.py)
 Everything executes through libpaella_hip.so (hand-written HIP for gfx950, C ABI in include/paella_hip.h).
@@ -14,9 +16,9 @@ The opt-in bf16 fast mode is a per-model switch: `Paella.set_gemm_precision("bf1
 from .conditioning import build_paella, embed_prompts, load_checkpoint, load_conditional_models
 from .editing import GraphInpainter, inpaint
 from .modules import CondCache, DenoiseUNet, Paella, replace_attention_layers
-from .sampling import GraphRequestSampler, GraphSampler, sample, sample_distributed, sample_requests, select_tokens
+from .sampling import GraphRequestSampler, GraphSampler, RequestStream, request_program, sample, sample_distributed, sample_requests, select_tokens
 from .vqgan import VectorQuantize, VQModel
 
 
-__all__ = ["Paella", "DenoiseUNet", "CondCache", "VQModel", "VectorQuantize", "sample", "sample_distributed", "sample_requests", "GraphSampler", "GraphRequestSampler",
+__all__ = ["Paella", "DenoiseUNet", "CondCache", "VQModel", "VectorQuantize", "sample", "sample_distributed", "sample_requests", "GraphSampler", "GraphRequestSampler", "RequestStream", "request_program",
            "replace_attention_layers", "inpaint", "GraphInpainter", "select_tokens", "load_conditional_models", "embed_prompts", "load_checkpoint", "build_paella"]

@@ -127,6 +127,11 @@ struct ReqTables {
     const float* temperature = nullptr;  // [B] this step's temperatures, each > 0 (1 / T by tail_inv_temperature, as the scalar forms)
     const float* cfg_pairs = nullptr;    // [B, 2] this step's (cfg, 1 - cfg), or null (the tail kernels' own mix of logits_c / logits_u only)
     int rows_per_sample = 0;             // > 0 selects the request form
+    // stream form (continuous batching: every request of the batch is at its OWN step; tail.hip: request_step_kernel emits these per tick).  Each table is optional,
+    // null = the launch's scalar, so the request form without them keeps its tokens bit for bit:
+    const int* step = nullptr;           // [B] the request's own step index: the Philox step word of its categorical and renoise draws instead of `offset`
+    const float* t_next = nullptr;       // [B] the request's renoise threshold at this step instead of `t_next`; negative = no renoise (u >= 0 is never <= it)
+    const int* active = nullptr;         // [B] 0 = the slot holds no running request: its rows are computed (fixed launch shapes) and NOTHING is stored for them
     FastDiv rps_div = {0u, 0u, 0xffffffffu};  // division by rows_per_sample (filled by the launchers)
 };
 
@@ -293,6 +298,10 @@ struct TailArgs {
     ReqTables rq;                 // rq.rows_per_sample > 0: request form (mode 0, Philox noise only; seed / cfg / temperature / row offsets above unused)
 };
 int launch_sample_tail(const TailArgs& a, hipStream_t stream);
+// one tick of a request stream: per slot b, row pos[b] of its program [B, max_steps, 5] = (r, temperature, cfg, 1 - cfg, t_next) becomes this tick's flat tables
+// (pairs may be null), step[b] = pos[b], active[b] = pos[b] < len[b]; the cursors of the active slots advance.  Idle slots: r 0, T 1, pair (1, 0), t_next -1.
+int launch_request_step(const float* program, int max_steps, int* pos, const int* len, int B, float* r, float* temperature, float* pairs, float* t_next,
+                        int* step, int* active, hipStream_t stream);
 // start tokens of the counter-based mode: out[i] = Philox(seed (+ *seed_ptr), i + row_offset (+ *row_offset_ptr)) % num_labels
 int launch_start_tokens(uint64_t seed, const uint64_t* seed_ptr, int64_t row_offset, const int64_t* row_offset_ptr, int num_labels, int64_t n,
                         int64_t* out, hipStream_t stream);

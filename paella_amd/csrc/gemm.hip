@@ -684,12 +684,14 @@ __global__ __launch_bounds__(64 * WM * WN, tile_wg_per_cu(WM, WN, TM, TN, PD, AP
     int tlq_tile = -1;       // tile the drawn noise belongs to
     int tail_cur_tile = -1;  // tile being finished (set by flush)
     // request form: row m (clamped into the matrix -- a tile may overhang it, the tables must not be read past their end) belongs to request b = m / rows_per_sample;
-    // its key is seeds[b], its counter row the position inside the sample.  One multiply-high per row per tile; returns b.
-    auto tail_req_row = [&](int m, uint64_t& rseed, int64_t& ctr_row) __attribute__((always_inline)) {
+    // its key is seeds[b], its counter row the position inside the sample, its step word step[b] where the launch brings a step table (stream form: every request
+    // is at its own step; the null check is kernel-uniform).  One multiply-high per row per tile; returns b.
+    auto tail_req_row = [&](int m, uint64_t& rseed, int64_t& ctr_row, uint64_t& rstep) __attribute__((always_inline)) {
         const int mc = min(m, g.M - 1);
         const unsigned b = fast_div((unsigned)mc, g.rq.rps_div);
         rseed = g.rq.seeds[b];
         ctr_row = mc - (int)b * g.rq.rows_per_sample;
+        if (g.rq.step) rstep = (uint64_t)g.rq.step[b];
         return b;
     };
     auto tail_draw = [&](int tile) __attribute__((always_inline)) {
@@ -706,12 +708,13 @@ __global__ __launch_bounds__(64 * WM * WN, tile_wg_per_cu(WM, WN, TM, TN, PD, AP
                     const int m = tile_m * BM + (wm * TM + i) * 16 + r16;
                     uint64_t rseed = seed;
                     int64_t ctr_row = m + row_off;
-                    if constexpr (REQ) tail_req_row(m, rseed, ctr_row);
+                    uint64_t rstep = ft.offset;
+                    if constexpr (REQ) tail_req_row(m, rseed, ctr_row, rstep);
 #pragma unroll
                     for (int j = 0; j < TN; ++j) {
                         const int nn = tile_n * BN + (wn * TN + j) * 16 + kq * 4;
                         uint32_t rb[4];
-                        philox4x32(rseed, (uint64_t)ctr_row * L4 + (nn >> 2), ft.offset, rb);
+                        philox4x32(rseed, (uint64_t)ctr_row * L4 + (nn >> 2), rstep, rb);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) tlq[i * TN + j][e] = log_exp1(rb[e]);
                     }
@@ -740,7 +743,8 @@ __global__ __launch_bounds__(64 * WM * WN, tile_wg_per_cu(WM, WN, TM, TN, PD, AP
                 const int m = m0 + mrow;
                 uint64_t rseed = seed;
                 int64_t ctr_row = m + row_off;
-                if constexpr (REQ) inv_t = tail_inv_temperature(g.rq.temperature[tail_req_row(m, rseed, ctr_row)]);
+                uint64_t rstep = ft.offset;
+                if constexpr (REQ) inv_t = tail_inv_temperature(g.rq.temperature[tail_req_row(m, rseed, ctr_row, rstep)]);
                 float best = -INFINITY;
                 int best_i = 0x7fffffff;
 #pragma unroll
@@ -759,7 +763,7 @@ __global__ __launch_bounds__(64 * WM * WN, tile_wg_per_cu(WM, WN, TM, TN, PD, AP
                                 for (int e = 0; e < 4; ++e) lq[e] = tlq[i * TN + j][e];  // (drawn ahead of the main loop: tail_draw)
                             } else {
                                 uint32_t rb[4];
-                                philox4x32(rseed, (uint64_t)ctr_row * L4 + (nn >> 2), ft.offset, rb);
+                                philox4x32(rseed, (uint64_t)ctr_row * L4 + (nn >> 2), rstep, rb);
 #pragma unroll
                                 for (int e = 0; e < 4; ++e) lq[e] = log_exp1(rb[e]);
                             }

@@ -1116,6 +1116,52 @@ extern "C" int paella_sample_tail_req(const float* logits_c, const float* logits
     return launch_sample_tail(a, (hipStream_t)stream);
 }
 
+// Request stream (ABI 7): the request forms with the three per-request stream tables (common.h: ReqTables::step / t_next / active), all required here.
+static int stream_tables_check(const char* who, const int* step, const float* t_next_tab, const int* active, const int64_t* init_noise) {
+    if (!step || !t_next_tab || !active || !init_noise) {
+        paella_set_error("%s: null argument (the step, t_next and active tables and init_noise, the renoise source of every slot, are required)", who);
+        return PAELLA_ERR_ARG;
+    }
+    return PAELLA_OK;
+}
+
+extern "C" int paella_unet_forward_sample_stream(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                 const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
+                                                 const uint64_t* seeds, const float* temperature, int rows_per_sample, const int* step,
+                                                 const float* t_next, const int* active, const int64_t* init_noise, int64_t* tokens_out, void* ws,
+                                                 size_t ws_bytes, void* stream) {
+    if (!tokens_out || !seeds || !temperature) { paella_set_error("forward_sample_stream: null argument (tokens_out / seeds / temperature)"); return PAELLA_ERR_ARG; }
+    RET_IF(stream_tables_check("forward_sample_stream", step, t_next, active, init_noise));
+    if (!mix_pairs && n_unique != B) { paella_set_error("forward_sample_stream without guidance pairs needs n_unique == B"); return PAELLA_ERR_ARG; }
+    if (H <= 0 || W <= 0 || rows_per_sample != H * W) { paella_set_error("forward_sample_stream: rows_per_sample (%d) must equal H * W", rows_per_sample); return PAELLA_ERR_ARG; }
+    TailArgs a = {};
+    a.rows = (int64_t)(mix_pairs ? n_unique : B) * H * W;
+    a.L = m ? m->cfg.num_labels : 0;
+    a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f; a.init_noise = init_noise; a.t_next = -1.f; a.tokens_out = tokens_out;
+    a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.rows_per_sample = rows_per_sample;
+    a.rq.step = step; a.rq.t_next = t_next; a.rq.active = active;
+    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, mix_pairs);
+}
+
+extern "C" int paella_sample_tail_stream(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
+                                         const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active,
+                                         const int64_t* init_noise, int64_t* tokens_out, int64_t* sampled_out, void* stream) {
+    if (!logits_c || !tokens_out || !seeds || !temperature) { paella_set_error("sample_tail_stream: null argument"); return PAELLA_ERR_ARG; }
+    RET_IF(stream_tables_check("sample_tail_stream", step, t_next, active, init_noise));
+    if (rows_per_sample <= 0) { paella_set_error("sample_tail_stream: rows_per_sample must be > 0"); return PAELLA_ERR_ARG; }
+    TailArgs a = {};
+    a.logits_c = logits_c; a.logits_u = cfg_pairs ? logits_u : nullptr; a.rows = rows; a.L = L; a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f;
+    a.init_noise = init_noise; a.t_next = -1.f; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
+    a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.cfg_pairs = cfg_pairs; a.rq.rows_per_sample = rows_per_sample;
+    a.rq.step = step; a.rq.t_next = t_next; a.rq.active = active;
+    return launch_sample_tail(a, (hipStream_t)stream);
+}
+
+extern "C" int paella_request_step(const float* program, int max_steps, int* pos, const int* len, int B, float* r, float* temperature, float* pairs,
+                                   float* t_next, int* step, int* active, void* stream) {
+    return launch_request_step(program, max_steps, pos, len, B, r, temperature, pairs, t_next, step, active, (hipStream_t)stream);
+}
+
 extern "C" int paella_start_tokens_req(const uint64_t* seeds, int B, int rows_per_sample, int num_labels, int64_t* tokens_out, void* stream) {
     return launch_start_tokens_req(seeds, B, rows_per_sample, num_labels, tokens_out, (hipStream_t)stream);
 }

@@ -27,25 +27,26 @@ __device__ __forceinline__ float mix_logit(float lc, float lu, float cfg, float 
 // renoise (src/utils.py:54 -> src/modules.py:277-283 with random_x = init_noise): u <= t_next ? init_noise : token
 __device__ __forceinline__ int64_t tail_row_offset(const TailArgs& a) { return a.row_offset + (a.row_offset_ptr ? *a.row_offset_ptr : 0); }
 
+// What a row draws with.  Scalar form: the launch's seed (+ device word), counters from the global row, the launch's cfg pair, temperature, step word and renoise threshold.
+// Request form (REQ): everything from the tables of the row's request b = row / rows_per_sample, counters from the position inside the sample; the stream tables
+// (step word, renoise threshold, active flag per request) are optional, null = the launch's scalar (kernel-uniform checks).
+struct RowKey { uint64_t seed, step; int64_t ctr_row; float cfg, omc, temperature, t_next; bool active; };
+
 // ctr_row: the row the Philox counter is built from -- the GLOBAL row (row + row offset), or in the request form the position inside the sample
-__device__ __forceinline__ int64_t renoise_token(const TailArgs& a, uint64_t seed, int64_t row, int64_t ctr_row, int64_t tok) {
+__device__ __forceinline__ int64_t renoise_token(const TailArgs& a, const RowKey& k, int64_t row, int64_t tok) {
     if (a.init_noise) {
         float u;
         if (a.mask_u) {
             u = a.mask_u[row];
         } else {
             uint32_t rb[4];
-            philox4x32(seed ^ 0x5bd1e9955bd1e995ull, (uint64_t)ctr_row, a.offset, rb);
+            philox4x32(k.seed ^ 0x5bd1e9955bd1e995ull, (uint64_t)k.ctr_row, k.step, rb);
             u = u01_half_open(rb[0]);
         }
-        if (u <= a.t_next) tok = a.init_noise[row];
+        if (u <= k.t_next) tok = a.init_noise[row];  // a negative per-request threshold never renoises: u >= 0
     }
     return tok;
 }
-
-// What a row draws with.  Scalar form: the launch's seed (+ device word), counters from the global row, the launch's cfg pair and temperature.
-// Request form (REQ): everything from the tables of the row's request b = row / rows_per_sample, counters from the position inside the sample.
-struct RowKey { uint64_t seed; int64_t ctr_row; float cfg, omc, temperature; };
 template <bool REQ>
 __device__ __forceinline__ RowKey tail_row_key(const TailArgs& a, int64_t row) {
     RowKey k;
@@ -56,10 +57,14 @@ __device__ __forceinline__ RowKey tail_row_key(const TailArgs& a, int64_t row) {
         k.cfg = a.rq.cfg_pairs ? a.rq.cfg_pairs[2 * b] : 1.f;
         k.omc = a.rq.cfg_pairs ? a.rq.cfg_pairs[2 * b + 1] : 0.f;
         k.temperature = a.rq.temperature[b];
+        k.step = a.rq.step ? (uint64_t)a.rq.step[b] : a.offset;
+        k.t_next = a.rq.t_next ? a.rq.t_next[b] : a.t_next;
+        k.active = a.rq.active ? a.rq.active[b] != 0 : true;
     } else {
         k.seed = a.seed + (a.seed_ptr ? *a.seed_ptr : 0ull);
         k.ctr_row = row + tail_row_offset(a);
         k.cfg = a.cfg; k.omc = a.one_minus_cfg; k.temperature = a.temperature;
+        k.step = a.offset; k.t_next = a.t_next; k.active = true;
     }
     return k;
 }
@@ -111,7 +116,7 @@ __global__ __launch_bounds__(256) void sample_tail_kernel(TailArgs a) {
                 q = *reinterpret_cast<const f32x4*>(nq + i4 * 4);
             } else {
                 uint32_t rb[4];
-                philox4x32(seed, (uint64_t)rk.ctr_row * L4 + i4, a.offset, rb);
+                philox4x32(seed, (uint64_t)rk.ctr_row * L4 + i4, rk.step, rb);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) q[e] = log_exp1(rb[e]);
             }
@@ -143,8 +148,10 @@ __global__ __launch_bounds__(256) void sample_tail_kernel(TailArgs a) {
         for (int w = 1; w < 4; ++w) argmax_update(best, best_i, red_v[w], red_i[w]);
         if (best_i == 0x7fffffff) best_i = 0;  // all-NaN row
         int64_t tok = best_i;
-        if (a.sampled_out) a.sampled_out[row] = tok;
-        a.tokens_out[row] = renoise_token(a, seed, row, rk.ctr_row, tok);
+        if (rk.active) {  // an idle slot of a request stream keeps what its rows held
+            if (a.sampled_out) a.sampled_out[row] = tok;
+            a.tokens_out[row] = renoise_token(a, rk, row, tok);
+        }
     }
 }
 
@@ -172,8 +179,10 @@ __global__ __launch_bounds__(256) void tail_finalize_kernel(TailArgs a, const fl
         const RowKey rk = tail_row_key<REQ>(a, row);
         if (best_i == 0x7fffffff) best_i = 0;
         int64_t tok = best_i;
-        if (a.sampled_out) a.sampled_out[row] = tok;
-        a.tokens_out[row] = renoise_token(a, rk.seed, row, rk.ctr_row, tok);
+        if (rk.active) {
+            if (a.sampled_out) a.sampled_out[row] = tok;
+            a.tokens_out[row] = renoise_token(a, rk, row, tok);
+        }
     }
 }
 
@@ -209,6 +218,45 @@ int launch_sample_tail(const TailArgs& a, hipStream_t st) {
         RET_REQ(r);
         hipLaunchKernelGGL(sample_tail_kernel<true>, dim3((unsigned)a.rows), dim3(256), 0, st, r);
     } else hipLaunchKernelGGL(sample_tail_kernel<false>, dim3((unsigned)a.rows), dim3(256), 0, st, a);
+    LAUNCH_CHECK_RET();
+    return PAELLA_OK;
+}
+
+// ---------------------------------------------------------------------------
+// One tick of a request stream (continuous batching; paella_amd.RequestStream): every slot b of the fixed-shape batch runs its own PROGRAM, one row per step,
+//   program [B, max_steps, 5] fp32: row j = (r_j, temperature_j, cfg_j, 1 - cfg_j, t_next_j)       cursor pos[b], length len[b]
+// and this launch turns the cursors into the flat per-slot tables the forward's timestep kernel and the stream form of the tail read at this tick, then advances
+// the cursors of the running slots.  A slot whose cursor reached its length is idle: finite placeholder values, active 0 (the tail stores nothing for it).
+// One thread per slot, plain loads and stores; a slot is touched by its own thread only.  Graph-capturable: everything is device state.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void request_step_kernel(const float* __restrict__ program, int max_steps, int* __restrict__ pos, const int* __restrict__ len, int B,
+                                                           float* __restrict__ r, float* __restrict__ temperature, float* __restrict__ pairs,
+                                                           float* __restrict__ t_next, int* __restrict__ step, int* __restrict__ active) {
+    const int b = blockIdx.x * 256 + threadIdx.x;
+    if (b >= B) return;
+    const int p = pos[b];
+    const bool on = p >= 0 && p < len[b] && p < max_steps;  // (the last two conditions keep a corrupt cursor or length inside the program)
+    float v[5] = {0.f, 1.f, 1.f, 0.f, -1.f};
+    if (on) {
+        const float* row = program + ((size_t)b * max_steps + p) * 5;
+#pragma unroll
+        for (int e = 0; e < 5; ++e) v[e] = row[e];
+    }
+    r[b] = v[0];
+    temperature[b] = v[1];
+    if (pairs) { pairs[2 * b] = v[2]; pairs[2 * b + 1] = v[3]; }
+    t_next[b] = v[4];
+    step[b] = p;
+    active[b] = on ? 1 : 0;
+    if (on) pos[b] = p + 1;
+}
+int launch_request_step(const float* program, int max_steps, int* pos, const int* len, int B, float* r, float* temperature, float* pairs, float* t_next,
+                        int* step, int* active, hipStream_t st) {
+    if (!program || !pos || !len || !r || !temperature || !t_next || !step || !active || B <= 0 || max_steps <= 0) {
+        paella_set_error("request_step: null table, B <= 0 or max_steps <= 0");
+        return PAELLA_ERR_ARG;
+    }
+    hipLaunchKernelGGL(request_step_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, program, max_steps, pos, len, B, r, temperature, pairs, t_next, step, active);
     LAUNCH_CHECK_RET();
     return PAELLA_OK;
 }
@@ -339,7 +387,7 @@ __global__ __launch_bounds__(256) void tail_scores_kernel(TailArgs a, float* __r
         const f32x4 c = *reinterpret_cast<const f32x4*>(lc + i4 * 4);
         const f32x4 u = has_u ? *reinterpret_cast<const f32x4*>(lu + i4 * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
         uint32_t rb[4];
-        philox4x32(rk.seed, (uint64_t)rk.ctr_row * L4 + i4, a.offset, rb);
+        philox4x32(rk.seed, (uint64_t)rk.ctr_row * L4 + i4, rk.step, rb);
         f32x4 s;
 #pragma unroll
         for (int e = 0; e < 4; ++e) s[e] = tail_score_gumbel(mix_logit(c[e], u[e], rk.cfg, rk.omc, has_u), tail_inv_temperature(rk.temperature), log_exp1(rb[e]));

@@ -349,8 +349,14 @@ class Paella(nn.Module):
         arr = (ctypes.c_void_p * max(len(images), 1))(*[ci.data_ptr() for ci in images]) if images else None
         return byt5, clip, images, arr, B, Sb, S
 
-    def prepare_cond(self, byt5, clip=None, clip_image=None, ws=None):
-        """Hoisted conditioning work (gen_c_embeddings + kv_mapper + K/V in-projection per AttnBlock)."""
+    def cond_bytes(self, B, S):
+        """Bytes of the conditioning cache of B samples with S conditioning rows each: one row-major [B*S, kv_total] fp32 matrix, sample b's rows a contiguous slice."""
+        return int(_lib.load().paella_unet_cond_bytes(self._engine(), B, S))
+
+    def prepare_cond(self, byt5, clip=None, clip_image=None, ws=None, out=None):
+        """Hoisted conditioning work (gen_c_embeddings + kv_mapper + K/V in-projection per AttnBlock).
+        out: an optional contiguous uint8 DEVICE tensor of `cond_bytes(B, S)` bytes that receives the cache instead of a fresh buffer -- e.g. the rows of one slot
+        inside a larger cache (the cache is row-major by sample, so a request stream prepares ONE request straight into its slot)."""
         h = self._engine()
         lib = _lib.load()
         dev = self._device()
@@ -359,7 +365,12 @@ class Paella(nn.Module):
             raise ValueError("conditioning sequence is empty")
         with torch.cuda.device(dev):
             nbytes = lib.paella_unet_cond_bytes(h, B, S)
-            buf = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+            if out is None:
+                buf = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
+            elif out.device != dev or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != int(nbytes):
+                raise ValueError("out must be a contiguous uint8 tensor of %d bytes on the model's device" % int(nbytes))
+            else:
+                buf = out
             ws = self._workspace(lib.paella_unet_workspace_bytes(h, B, 0, 0, S), ws)
             _lib.check(lib.paella_unet_cond_prepare(h, _lib.ptr(byt5) if Sb > 0 else None, Sb, _lib.ptr(clip), arr, len(images), B,
                                                     _lib.ptr(buf), buf.numel(), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
@@ -445,7 +456,7 @@ class Paella(nn.Module):
         return out
 
     def forward_sample(self, x, r, cond, out, *, temperature, argmax=False, seed=0, seed_dev=None, offset=0, row_offset=0,
-                       row_offset_dev=None, init_noise=None, t_next=0.0, cfg_mix=None, attn_weights=None, ws=None, req=None):
+                       row_offset_dev=None, init_noise=None, t_next=0.0, cfg_mix=None, attn_weights=None, ws=None, req=None, stream=None):
         """One whole sampling step in the counter-based noise mode (src/utils.py:43-54): the denoiser evaluation with the head
         GEMM and the sampling tail FUSED -- the [B, num_labels, H, W] logits are never materialised.  x int64 [Bx,H,W], r [Bx];
         cfg_mix=(a, b) with cond.B == 2*Bx folds classifier-free guidance through the head (as forward_prepared); without it
@@ -453,7 +464,10 @@ class Paella(nn.Module):
         init_noise is given).  Bit-identical to forward_prepared + the tail kernel on the same seed.
         req=(seeds, temperature, pairs) (request batch; `temperature`, `seed`, `row_offset` and `cfg_mix` are then unused): DEVICE tables with one entry per
         sample -- int64 [Bx] seed bit patterns, fp32 [Bx] temperatures (> 0, validated by the caller), fp32 [Bx, 2] guidance pairs or None (no guidance);
-        sample b draws what it draws alone under seeds[b] (counters from the position inside the sample)."""
+        sample b draws what it draws alone under seeds[b] (counters from the position inside the sample).
+        stream=(step, t_next, active) (request stream, with `req`; `offset` and `t_next` are then unused and `init_noise` is required): DEVICE tables with one entry
+        per sample -- int32 [Bx] own step index (the Philox step word), fp32 [Bx] renoise threshold (negative: no renoise), int32 [Bx] active flag (0: nothing is
+        stored for the sample, `out` keeps its rows) -- every request of the batch is at its own step; `out` may be `x` (the stream runs in place)."""
         h = self._engine()
         lib = _lib.load()
         dev = self._device()
@@ -472,6 +486,14 @@ class Paella(nn.Module):
             self._check_table(temps, (nu,), torch.float32, "req temperature")
             if pairs is not None:
                 self._check_table(pairs, (nu, 2), torch.float32, "req pairs")
+            if stream is not None:
+                if init_noise is None:
+                    raise ValueError("forward_sample(stream=...) needs init_noise: it is the renoise source of every slot")
+                self._check_table(stream[0], (nu,), torch.int32, "stream step")
+                self._check_table(stream[1], (nu,), torch.float32, "stream t_next")
+                self._check_table(stream[2], (nu,), torch.int32, "stream active")
+        elif stream is not None:
+            raise ValueError("forward_sample(stream=...) needs the request tables (req=...)")
         elif (cfg_mix is None and B != nu) or (cfg_mix is not None and (B != 2 * nu or mix == (0.0, 0.0))):
             raise ValueError("forward_sample needs cond.B == Bx (no guidance) or cond.B == 2*Bx with a non-zero cfg_mix")
         if tuple(out.shape) != (nu, H, W) or out.dtype != torch.int64 or not out.is_contiguous():
@@ -479,6 +501,12 @@ class Paella(nn.Module):
         aw = self._f32(attn_weights, "attn_weights")
         with torch.cuda.device(dev):
             ws = self._workspace(lib.paella_unet_workspace_bytes(h, B, H, W, cond.S), ws)
+            if stream is not None:
+                _lib.check(lib.paella_unet_forward_sample_stream(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S, _lib.ptr(aw),
+                                                                 0 if aw is None else aw.numel(), _lib.ptr(seeds), _lib.ptr(temps), H * W, _lib.ptr(stream[0]),
+                                                                 _lib.ptr(stream[1]), _lib.ptr(stream[2]), _lib.ptr(init_noise), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                                                 _lib.stream_ptr(dev)))
+                return out
             if req is not None:
                 _lib.check(lib.paella_unet_forward_sample_req(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S, _lib.ptr(aw),
                                                               0 if aw is None else aw.numel(), _lib.ptr(seeds), _lib.ptr(temps), H * W, int(offset), _lib.ptr(init_noise),

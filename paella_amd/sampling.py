@@ -20,7 +20,7 @@ Extension (not reference behaviour): a step temperature of 0 selects 
 import torch
 
 from . import _lib
-from .modules import Paella
+from .modules import CondCache, Paella
 
 
 def linspace_schedule(start, end, n):
@@ -618,3 +618,281 @@ class GraphRequestSampler(GraphSampler):
         self.req.load(host)
         self.graph.replay()
         return self.out
+
+
+# ---------------------------------------------------------------------------------------------------------------- continuous request batching
+_IDLE_ROW = (0.0, 1.0, 1.0, 0.0, -1.0)  # what an idle slot runs with: finite, never renoising (tail.hip: request_step_kernel fills the same values)
+
+
+def request_program(steps, renoise_steps=None, temperature=(1.0, 0.2), cfg=8.0, t_start=1.0, t_end=0.0, max_steps=None, *, guided=None):
+    """The schedule of ONE request of a `RequestStream` as a HOST table: (program fp32 [max_steps, 5], steps).  Row j = (r_j, temperature_j, cfg_j, 1 - cfg_j,
+    t_next_j) is what the request runs its step j with, bit for bit the scalars the scalar samplers compute: r and the temperatures from `linspace_schedule`
+    (t_list = linspace(t_start, t_end, steps + 1)); a float `cfg` rounded as `sample()` rounds it (fp32(cfg), fp32(1.0 - cfg), every step), a (start, end) tuple
+    as `sample_distributed` does (torch.linspace, 1 - cfg in fp32), None = the pair (1, 0) of a request without guidance; t_next_j = t_list[j + 1] for
+    j < renoise_steps (None: steps - 1, as `sample_distributed`), else -1.0 -- a negative threshold never renoises.  Rows from `steps` on are padding (the idle
+    values) and never run: the slot's length is `steps`.  max_steps None = steps.
+    guided (keyword-only; what `RequestStream.admit` passes): True refuses cfg=None, False refuses any other cfg -- guidance is on for every request of a stream
+    or for none.  Raises ValueError unless 1 <= steps <= max_steps, 0 <= renoise_steps and every step temperature > 0."""
+    steps = int(steps)
+    max_steps = steps if max_steps is None else int(max_steps)
+    if not 1 <= steps <= max_steps:
+        raise ValueError("a request needs 1 <= steps <= max_steps (steps=%d, max_steps=%d)" % (steps, max_steps))
+    renoise_steps = steps - 1 if renoise_steps is None else int(renoise_steps)
+    if renoise_steps < 0:
+        raise ValueError("renoise_steps must be >= 0")
+    is_num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+    if not (isinstance(temperature, (list, tuple)) and len(temperature) == 2 and all(is_num(v) for v in temperature)):
+        raise ValueError("temperature must be a (start, end) pair")
+    t_list = linspace_schedule(t_start, t_end, steps + 1)
+    temps = linspace_schedule(float(temperature[0]), float(temperature[1]), steps)
+    if not all(t > 0 for t in temps):
+        raise ValueError("every step temperature of a request must be > 0 (temperature 0, the argmax extension, is not offered per request)")
+    if guided is not None and bool(guided) != (cfg is not None):
+        raise ValueError("guidance is on for every request of a stream or for none: " +
+                         ("cfg=None in a guided stream (pass 1.0 for 'no guidance')" if guided else "cfg=%r in an unguided stream (pass cfg=None)" % (cfg,)))
+    if cfg is None:
+        pairs = [(1.0, 0.0)] * steps
+    elif is_num(cfg):
+        pairs = [(float(torch.tensor(float(cfg), dtype=torch.float32)), float(torch.tensor(1.0 - float(cfg), dtype=torch.float32)))] * steps
+    elif isinstance(cfg, (list, tuple)) and len(cfg) == 2 and all(is_num(v) for v in cfg):
+        sched = torch.linspace(cfg[0], cfg[1], steps)
+        pairs = [(float(sched[i]), float(1 - sched[i])) for i in range(steps)]
+    else:
+        raise ValueError("cfg must be None, a float or a (start, end) tuple, got %r" % (cfg,))
+    rows = [(t_list[j], temps[j], pairs[j][0], pairs[j][1], t_list[j + 1] if j < renoise_steps else -1.0) for j in range(steps)]
+    rows += [_IDLE_ROW] * (max_steps - steps)
+    return torch.tensor(rows, dtype=torch.float32), steps
+
+
+def _cond_layout(inputs):
+    """what a conditioning dict looks like per request: key -> None, the trailing shape, or the list of trailing shapes"""
+    return {k: (None if inputs.get(k) is None else [tuple(t.shape[1:]) for t in inputs[k]] if isinstance(inputs[k], (list, tuple)) else tuple(inputs[k].shape[1:]))
+            for k in ("byt5", "clip", "clip_image")}
+
+
+class RequestStream:
+    """Continuous request batching: a fixed-shape batch of B SLOTS whose requests join and leave at step boundaries.  Every request has its own seed, step count,
+    renoise count, temperature and guidance schedule, timestep range and optionally its own start tokens (`init_x` with `t_start` -- the denoising part of an
+    image-to-image request); ONE captured graph of a single tick (`request_step` -> the stream form of `forward_sample`) is replayed while they come and go.
+
+    `model_inputs` / `unconditional_inputs` given here are EXAMPLES: they fix the conditioning layout and the number of conditioning rows S for the life of the
+    stream (callers pad prompts to that S, as they pad a batch).  guided: guidance is on for every request or for none -- it decides the launch sequence.
+
+    Contract: a request admitted to a stream draws, at its step j, exactly the random words of `sample_distributed(..., latent_shape=(1, H, W), init_x=init_x,
+    steps=steps, ..., noise="philox", seed=seed)` at step j; and whoever else is in the batch and whatever tick it was admitted at, its tokens at a given slot
+    and B are the same bit for bit.  An idle slot costs a full slot of compute: a stream with k of B slots busy runs at the speed of batch B.
+
+    The stream's device state: the in-place token grid and the start-token grid [B, H, W], the 2B-slot (unguided: B-slot) conditioning cache, per slot a program
+    (`request_program`), a cursor and a length, the seed words and the flat per-tick tables.  The host mirrors the cursors: no read-back per tick.
+    Staleness (as GraphSampler): a changed weight or precision recaptures (on_stale="recapture") or raises (on_stale="raise") while no request is in flight; with
+    requests in flight it always raises -- their conditioning was prepared with the old weights; `reset()` abandons them."""
+
+    def __init__(self, model, model_inputs, unconditional_inputs, latent_shape, max_steps=12, guided=True, device="cuda", vqgan=None, attn_weights=None,
+                 on_stale="recapture"):
+        if on_stale not in ("recapture", "raise"):
+            raise ValueError("on_stale must be 'recapture' or 'raise'")
+        if not isinstance(model, Paella):
+            raise TypeError("RequestStream needs a paella_amd.Paella model")
+        self.model, self.vqgan, self.device, self.on_stale = model, vqgan, torch.device(device), on_stale
+        if self.device.type != "cuda":
+            raise RuntimeError("paella_amd.RequestStream runs on a HIP device only (got device=%s); there is no CPU path" % self.device)
+        self.shape = tuple(int(v) for v in latent_shape)
+        B, H, W = self.shape
+        self.max_steps, self.guided, self.attn_weights = int(max_steps), bool(guided), attn_weights
+        if B <= 0 or self.max_steps <= 0:
+            raise ValueError("a request stream needs B > 0 and max_steps > 0")
+        if model_inputs is None or (self.guided and unconditional_inputs is None):
+            raise TypeError("a %s stream needs model_inputs%s" % ("guided" if self.guided else "unguided", " and unconditional_inputs" if self.guided else ""))
+        self.layout = _cond_layout(model_inputs)
+        if self.guided and _cond_layout(unconditional_inputs) != self.layout:
+            raise ValueError("the conditional and unconditional inputs of a guided stream must share one layout (they are evaluated as one 2B-row batch)")
+        self.S = _cond_seq_len(model, model_inputs)
+        if self.S <= 0:
+            raise ValueError("conditioning sequence is empty")
+        dev, nb = self.device, (2 * B if self.guided else B)
+        self._slot_bytes = model.cond_bytes(1, self.S)
+        self.cache = CondCache(torch.zeros(nb * self._slot_bytes, dtype=torch.uint8, device=dev), nb, self.S)  # (zero K/V rows: finite work for slots never filled)
+        assert self.cache.buf.numel() == model.cond_bytes(nb, self.S)
+        self.tokens = torch.zeros(self.shape, dtype=torch.int64, device=dev)    # the in-place grid: a tick reads and writes it
+        self.random_x = torch.zeros(self.shape, dtype=torch.int64, device=dev)  # per slot the start tokens of its seed: the renoise source
+        self.seeds = torch.zeros(B, dtype=torch.int64, device=dev)
+        self.program = torch.tensor(_IDLE_ROW, dtype=torch.float32).repeat(B, self.max_steps, 1).to(dev)
+        self.pos = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.len = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.r = torch.zeros(B, dtype=torch.float32, device=dev)
+        self.temps = torch.ones(B, dtype=torch.float32, device=dev)
+        self.pairs = torch.tensor([1.0, 0.0]).repeat(B, 1).to(dev) if self.guided else None
+        self.t_next = torch.full((B,), -1.0, dtype=torch.float32, device=dev)
+        self.step = torch.zeros(B, dtype=torch.int32, device=dev)
+        self.active_dev = torch.zeros(B, dtype=torch.int32, device=dev)
+        self._pos, self._len, self._held = [0] * B, [0] * B, [False] * B  # host mirror: cursor, length, slot taken (admitted and not yet collected)
+        self.captures = 0
+        self._capture()
+
+    # ---- slots
+    @property
+    def free_slots(self):
+        """slots that hold no request (neither running nor finished and waiting for `result`)"""
+        return [b for b, held in enumerate(self._held) if not held]
+
+    @property
+    def active(self):
+        """slots whose request still has steps to run"""
+        return [b for b in range(self.shape[0]) if self._held[b] and self._pos[b] < self._len[b]]
+
+    # ---- one tick on the current stream: the launches the graph holds
+    def _tick_launches(self):
+        B = self.shape[0]
+        with torch.cuda.device(self.device):
+            _lib.check(_lib.load().paella_request_step(_lib.ptr(self.program), self.max_steps, _lib.ptr(self.pos), _lib.ptr(self.len), B, _lib.ptr(self.r),
+                                                       _lib.ptr(self.temps), _lib.ptr(self.pairs), _lib.ptr(self.t_next), _lib.ptr(self.step), _lib.ptr(self.active_dev),
+                                                       _lib.stream_ptr(self.device)))
+        # in place: the token gather at the head of the forward and the token store at its tail are different kernels of one stream (as in _sample_core)
+        self.model.forward_sample(self.tokens, self.r, self.cache, self.tokens, temperature=1.0, init_noise=self.random_x, attn_weights=self.attn_weights, ws=self.ws,
+                                  req=(self.seeds, self.temps, self.pairs), stream=(self.step, self.t_next, self.active_dev))
+
+    _state = GraphSampler._state
+
+    def _capture(self):
+        """only with no request in flight: every slot is then idle on the device, and an idle tick stores nothing and moves no cursor -- the warm-up ticks and the
+        capture itself leave the state (finished tokens waiting for `result` included) as it is"""
+        assert not self.active
+        B, H, W = self.shape
+        self.graph = None
+        self.ws = _lib.new_workspace(self.model.workspace_bytes(self.cache.B, H, W, self.S), self.device)
+        self.vq_ws = None if self.vqgan is None else _lib.new_workspace(self.vqgan.workspace_bytes(1, H, W), self.device)
+        side = torch.cuda.Stream(device=self.device)
+        side.wait_stream(torch.cuda.current_stream(self.device))
+        with torch.cuda.stream(side), torch.inference_mode():
+            for _ in range(2):
+                self._tick_launches()
+        torch.cuda.current_stream(self.device).wait_stream(side)
+        torch.cuda.synchronize(self.device)
+        state = self._state()
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"), torch.inference_mode():
+            self._tick_launches()
+        torch.cuda.synchronize(self.device)
+        self.graph, self._captured_state = graph, state
+        self.captures += 1
+
+    def _check_fresh(self):
+        now = self._state()
+        if now == self._captured_state:
+            return
+        causes = ", ".join(a[0] for a, b in zip(now, self._captured_state) if a != b)
+        if self.active:
+            raise RuntimeError("RequestStream: %s changed with %d request(s) in flight -- their conditioning was prepared with the old state; let the stream run "
+                               "empty before load_state_dict / set_gemm_precision, or abandon them with reset()" % (causes, len(self.active)))
+        if self.on_stale == "raise":
+            raise RuntimeError("RequestStream: the captured graph is stale -- changed since the capture: %s.  Build a new RequestStream or construct it with "
+                               "on_stale='recapture'." % causes)
+        self._capture()
+
+    # ---- requests
+    def _check_inputs(self, inputs, what):
+        if inputs is None or _cond_layout(inputs) != self.layout:
+            raise ValueError("%s: conditioning layout or sequence length differs from the stream's (%r)" % (what, self.layout))
+        for k in ("byt5", "clip", "clip_image"):
+            v = inputs.get(k)
+            for t in ([] if v is None else v if isinstance(v, (list, tuple)) else [v]):
+                if t.size(0) != 1:
+                    raise ValueError("%s: admit takes the inputs of ONE request (leading dimension 1), got %d for %s" % (what, t.size(0), k))
+
+    def admit(self, model_inputs, unconditional_inputs=None, seed=None, steps=12, renoise_steps=None, temperature=(1.0, 0.2), cfg=8.0, t_start=1.0, t_end=0.0,
+              init_x=None):
+        """Put ONE request into a free slot; it runs from the next tick on.  Inputs: leading dimension 1, the stream's layout.  Schedule arguments as
+        `request_program` (an unguided stream takes cfg=None); init_x int64 [H, W]: the tokens the request starts from instead of its seed's start tokens.
+        Everything here is eager work on the current stream, ordered before the next tick: the conditioning of the one request is prepared straight into the
+        slot's rows of the cache.  Raises RuntimeError when no slot is free.  Returns the slot."""
+        B, H, W = self.shape
+        program, n = request_program(steps, renoise_steps, temperature, cfg, t_start, t_end, max_steps=self.max_steps, guided=self.guided)
+        self._check_inputs(model_inputs, "model_inputs")
+        if self.guided:
+            self._check_inputs(unconditional_inputs, "unconditional_inputs")
+        if init_x is not None:
+            init_x = init_x.reshape(H, W) if torch.is_tensor(init_x) and init_x.numel() == H * W else init_x
+            if not torch.is_tensor(init_x) or tuple(init_x.shape) != (H, W) or init_x.dtype != torch.int64:
+                raise ValueError("init_x must be an int64 tensor [%d, %d]" % (H, W))
+        free = self.free_slots
+        if not free:
+            raise RuntimeError("RequestStream: no free slot (%d running, %d finished and waiting for result())" % (len(self.active), B - len(self.active)))
+        self._check_fresh()
+        if seed is None:
+            seed = fresh_seed()
+        b, nbytes = free[0], self._slot_bytes
+        with torch.inference_mode():
+            # the conditioning GEMMs run on the TICK's workspace (self.ws, whose split-K tickets the captured graph also uses).  That is safe on two grounds: admit and
+            # every replay are enqueued on the same (current) stream, so the two users never run concurrently and each launch leaves the tickets zero; and the
+            # workspace was sized for the 2B-row forward, which covers the conditioning preparation of one request (prepare_cond checks the size and raises otherwise)
+            for row, inputs in ((b, model_inputs), (B + b, unconditional_inputs))[:2 if self.guided else 1]:
+                self.model.prepare_cond(**{k: inputs.get(k) for k in ("byt5", "clip", "clip_image")}, ws=self.ws, out=self.cache.buf[row * nbytes:(row + 1) * nbytes])
+            start_tokens(self.model.num_labels, (1, H, W), seed, self.device, out=self.random_x[b:b + 1])
+            self.tokens[b].copy_(self.random_x[b] if init_x is None else init_x)
+            self.seeds[b].fill_(seed_word(seed))
+            self.program[b].copy_(program)
+            self.len[b].fill_(n)
+            self.pos[b].fill_(0)
+        self._pos[b], self._len[b], self._held[b] = 0, n, True
+        return b
+
+    def reset(self):
+        """Abandon every request the stream holds, running or finished: all slots become free and idle (cursors and lengths zeroed on the device, stream-ordered
+        before the next tick); nothing is returned for them.  The way out after a weight or precision change with requests in flight -- the next admit / tick then
+        finds the stream empty and recaptures (or raises, with on_stale="raise")."""
+        B = self.shape[0]
+        self.len.zero_()
+        self.pos.zero_()
+        self._pos, self._len, self._held = [0] * B, [0] * B, [False] * B
+
+    def tick(self, graph=True):
+        """One denoising step of every running request (one graph replay; graph=False: the same launches eagerly).  Returns the slots whose request finished with
+        this tick -- collect them with `result`.  With no running request nothing is launched."""
+        running = self.active
+        if not running:
+            return []
+        self._check_fresh()
+        if graph:
+            self.graph.replay()
+        else:
+            with torch.inference_mode():
+                self._tick_launches()
+        done = []
+        for b in running:
+            self._pos[b] += 1
+            if self._pos[b] == self._len[b]:
+                done.append(b)
+        return done
+
+    def result(self, slot):
+        """The finished request of `slot`: its tokens [H, W] (a clone), with a VQGAN (tokens, image [3, f*H, f*W]) -- an eager decode of the one slot.  Frees the slot."""
+        slot = int(slot)
+        if not (0 <= slot < self.shape[0]) or not self._held[slot]:
+            raise ValueError("slot %d holds no request" % slot)
+        if self._pos[slot] < self._len[slot]:
+            raise RuntimeError("the request of slot %d has %d step(s) to run" % (slot, self._len[slot] - self._pos[slot]))
+        toks = self.tokens[slot].clone()
+        self._held[slot] = False
+        if self.vqgan is None:
+            return toks
+        with torch.inference_mode():
+            return toks, self.vqgan.decode_indices(toks[None], ws=self.vq_ws)[0].clone()
+
+    def drain(self, requests, graph=True):
+        """Serve an iterable of requests (keyword dicts for `admit`): admit as slots free up, tick until everything is collected; yields (index, tokens) -- with a
+        VQGAN (index, tokens, image) -- in completion order.  The stream must be empty: a request admitted outside this call would finish among its ticks."""
+        if any(self._held):
+            raise RuntimeError("RequestStream.drain needs an empty stream (%d slot(s) hold requests admitted elsewhere: collect them with result() first)" % sum(self._held))
+        it, index_of, more = iter(enumerate(requests)), {}, True
+        while True:
+            while more and self.free_slots:
+                nxt = next(it, None)
+                if nxt is None:
+                    more = False
+                else:
+                    index_of[self.admit(**nxt[1])] = nxt[0]
+            if not index_of:
+                return
+            for b in self.tick(graph=graph):
+                res = self.result(b)
+                yield (index_of.pop(b), *res) if isinstance(res, tuple) else (index_of.pop(b), res)

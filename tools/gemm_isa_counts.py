@@ -1,6 +1,8 @@
 """Static ISA counts of the hot gemm_nt_kernel instantiations (profiles/gemm_epilogue_isa_counts.txt).
 
     python tools/gemm_isa_counts.py <gemm.o> [<gemm.resources.txt>]
+    python tools/gemm_isa_counts.py --req-tail <gemm.o> <gemm.resources.txt>     the REQ (request form) fused-tail head tiles instead: per instantiation the
+                                                                                 instruction count and the SGPR / VGPR / scratch figures of the remarks
 
 Extracts the gfx950 code object from the object's .hip_fatbin (llvm-objcopy + clang-offload-bundler --unbundle), disassembles it with
 `llvm-objdump -d --mcpu=gfx950`, and prints per batch-1 ring instantiation: instructions after the last MFMA, v_readlane_b32 among them,
@@ -45,7 +47,32 @@ def spills(res):
     return d
 
 
+REQ_TAIL = re.compile(r"^_Z14gemm_nt_kernelI(.*)Li1073741824ELb1EEv")  # ..., EPI = EPI_RUNTIME, REQ = true
+
+
+def resources(res):
+    d = {}
+    for blk in re.split(r"remark: Function Name: ", open(res).read())[1:]:
+        get = lambda key: int(re.search(key + r": (\d+)", blk).group(1))
+        d[blk.split()[0]] = (get("TotalSGPRs"), get("VGPRs"), get("SGPRs Spill"), get(r"ScratchSize \[bytes/lane\]"))
+    return d
+
+
+def req_tail(obj, res):
+    rs = resources(res)
+    with tempfile.TemporaryDirectory() as tmp:
+        fns = functions(code_object(obj, tmp))
+    print("%-64s %8s %7s %7s %7s %8s %10s" % ("REQ head tile (template arguments WM,WN,TM,TN,PD,APRO,TAIL,BK,DMA,RING,BF)", "instr", "SGPR", "VGPR", "spill", "scratch", "v_mfma"))
+    for name, ins in sorted(fns.items()):
+        m = REQ_TAIL.match(name)
+        if m:
+            args = ",".join(re.findall(r"L[ib](\d+)E", m.group(1)))
+            print("%-64s %8d %7d %7d %7d %8d %10d" % ((args, len(ins)) + rs.get(name, (-1, -1, -1, -1)) + (sum(op.startswith("v_mfma") for op in ins),)))
+
+
 def main():
+    if sys.argv[1] == "--req-tail":
+        return req_tail(sys.argv[2], sys.argv[3])
     obj = sys.argv[1]
     res = sys.argv[2] if len(sys.argv) > 2 else None
     sp = spills(res)
