@@ -32,7 +32,7 @@
 extern "C" {
 #endif
 
-#define PAELLA_ABI_VERSION 7
+#define PAELLA_ABI_VERSION 8
 
 #define PAELLA_OK 0
 #define PAELLA_ERR_ARG -1       /* invalid argument / unsupported shape */
@@ -245,6 +245,47 @@ int paella_unet_forward_sample_stream(paella_unet* m, const int64_t* tokens, con
                                       const float* t_next, const int* active, const int64_t* init_noise, int64_t* tokens_out,
                                       void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Ragged conditioning (ABI 8): the samples of ONE launch may have different numbers of conditioning rows.  The cache is
+ * then B SLOTS of S rows each (S = the slot pitch, the `S` argument of every entry point below); sample b's real rows
+ * [byt5 | clip | clip_image...] sit at the FRONT of slot b and a DEVICE table
+ *   cond_len  int32 [B]   conditioning rows of sample b, clamped to [0, S] by the kernels
+ * says how many there are.  Two properties hold in every attention kernel: (1) sample b of a ragged launch equals, bit for
+ * bit, the same kernel launched for that sample alone with S = cond_len[b] and tightly packed rows; (2) rows >= cond_len[b]
+ * of a slot are never read (they may hold anything, NaN included).  attn_weights weigh the last n keys of each sample's OWN
+ * key sequence, so n must not exceed the shortest one (the caller validates).  cond_len == NULL is the non-ragged entry
+ * point, bit for bit; every non-ragged entry point above keeps its signature and behaviour.
+ * ---------------------------------------------------------------------------------------------- */
+/* paella_unet_cond_prepare for a group of B samples of S = S_byt5 + ... rows each, written to the front of slots slot0 ..
+ * slot0 + B - 1 (S_slot >= S rows per slot) of `cache`, a buffer of at least paella_unet_cond_bytes(slot0 + B, S_slot)
+ * bytes; cond_len[slot0 .. slot0 + B) = S (stream-ordered).  The GEMM shapes are those of the plain call: the stored rows
+ * equal its output bit for bit, and no byte outside them is written. */
+int paella_unet_cond_prepare_slots(paella_unet* m, const float* byt5, int S_byt5, const float* clip,
+                                   const float* const* clip_image, int n_clip_image, int B, int S_slot, int slot0,
+                                   void* cache, size_t cache_bytes, int* cond_len, void* ws, size_t ws_bytes, void* stream);
+/* The forward entry points with `cond_len` right after S; everything else as the entry point of the same name. */
+int paella_unet_forward_shared_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                      float mix_c, float mix_u, int H, int W, int S, const int* cond_len, const float* attn_weights,
+                                      int n_attn_weights, float* logits_out, void* ws, size_t ws_bytes, void* stream);
+int paella_unet_forward_sample_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                      float mix_c, float mix_u, int H, int W, int S, const int* cond_len, const float* attn_weights,
+                                      int n_attn_weights, float temperature, int mode, uint64_t seed, const uint64_t* seed_ptr,
+                                      uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr, const int64_t* init_noise,
+                                      float t_next, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream);
+int paella_unet_forward_shared_req_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                          const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights,
+                                          int n_attn_weights, float* logits_out, void* ws, size_t ws_bytes, void* stream);
+int paella_unet_forward_sample_req_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                          const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights,
+                                          int n_attn_weights, const uint64_t* seeds, const float* temperature, int rows_per_sample,
+                                          uint64_t offset, const int64_t* init_noise, float t_next, int64_t* tokens_out, void* ws,
+                                          size_t ws_bytes, void* stream);
+int paella_unet_forward_sample_stream_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                             const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights,
+                                             int n_attn_weights, const uint64_t* seeds, const float* temperature, int rows_per_sample,
+                                             const int* step, const float* t_next, const int* active, const int64_t* init_noise,
+                                             int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream);
+
 /* x, random_x, mask int64 [B, per_sample]; t fp32 [B].  mask_in NULL -> mask = (u <= t[b]) with u = rand_u
  * (caller noise, [B, per_sample]) or Philox; random_x NULL -> Philox randint(0, num_labels). */
 int paella_add_noise(const int64_t* x, const float* t, const int64_t* mask_in, const int64_t* random_x,
@@ -315,6 +356,10 @@ int paella_op_grn_scale(const float* g, const float* gamma, float* scale, float*
 int paella_op_attention(const float* q, const float* k_self, const float* v_self, const float* k_cond,
                         const float* v_cond, float* out, int B, int nhead, int D, int Lq, int Lself, int Lcond,
                         const float* key_weights, int n_kw, void* stream);
+/* the same over B slots of Lcond conditioning rows of which sample b attends the first cond_len[b] (int32 DEVICE table [B]; NULL = all Lcond) */
+int paella_op_attention_ragged(const float* q, const float* k_self, const float* v_self, const float* k_cond,
+                               const float* v_cond, float* out, int B, int nhead, int D, int Lq, int Lself, int Lcond,
+                               const int* cond_len, const float* key_weights, int n_kw, void* stream);
 
 #ifdef __cplusplus
 }

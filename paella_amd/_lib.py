@@ -13,7 +13,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "libpaella_hip.so")
 
 MAX_LEVELS = 8
 MAX_BLOCK_TYPES = 8
-ABI_VERSION = 7
+ABI_VERSION = 8
 
 
 class UnetConfig(Structure):
@@ -102,6 +102,23 @@ SIGNATURES = {
     "paella_op_grn_scale": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p]),
     "paella_op_attention": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                     c_int, c_int, c_void_p, c_int, c_void_p]),
+    # ragged conditioning (ABI 8): `cond_len` (int32 device table) right after S / Lcond
+    "paella_unet_cond_prepare_slots": (c_int, [c_void_p, c_void_p, c_int, c_void_p, POINTER(c_void_p), c_int, c_int, c_int, c_int, c_void_p,
+                                               c_size_t, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "paella_unet_forward_shared_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_int, c_void_p,
+                                                  c_void_p, c_int, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "paella_unet_forward_sample_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_int, c_void_p,
+                                                  c_void_p, c_int, c_float, c_int, c_uint64, c_void_p, c_uint64, c_int64, c_void_p, c_void_p, c_float, c_void_p,
+                                                  c_void_p, c_size_t, c_void_p]),
+    "paella_unet_forward_shared_req_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                                      c_void_p, c_void_p, c_size_t, c_void_p]),
+    "paella_unet_forward_sample_req_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_int,
+                                                      c_void_p, c_void_p, c_int, c_uint64, c_void_p, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "paella_unet_forward_sample_stream_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                         c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                                         c_void_p]),
+    "paella_op_attention_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
+                                           c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
 }
 
 # exported for tests / tools only; declared in paella_amd/csrc/test_hooks.h, not in the public header
@@ -116,6 +133,8 @@ TEST_HOOKS = {
     "paella_test_grn_apply16": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_void_p]),
     "paella_test_gemm_bf16_ln": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "paella_test_attention_bf16": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p, c_int, c_void_p]),
+    "paella_test_attention_bf16_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_void_p,
+                                                  c_void_p, c_int, c_void_p]),
     "paella_test_launch_chain": (c_int, [c_void_p, c_int, c_int, c_int, c_void_p]),
     "paella_test_attention_variant": (c_int, [c_int]),
     "paella_test_gemm_dma": (c_int, [c_int]),

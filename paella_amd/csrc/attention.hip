@@ -29,6 +29,16 @@ typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));  // bf16 output of th
 // masking relies on.  Every attention kernel uses this one function, so the LDS-staged and register-fed kernels stay bit-identical to each other.
 __device__ __forceinline__ float exp_fast(float x) { return __builtin_amdgcn_exp2f(x * 1.44269504088896340736f); }
 
+// Ragged conditioning (AttnArgs::cond_len): the conditioning keys of sample b are the first cond_len[b] rows of its slot of Lcond rows -- Lcond is then only
+// the slot PITCH (base pointers, descriptor origins) and every bound below (Lk, tile count, clamps, the key mask, the stage classes, the conditioning
+// descriptors' num_records, the origin of the key weights) comes from the sample's own count, so sample b computes, bit for bit, what a launch for it alone
+// with Lcond = cond_len[b] and packed K / V computes, and rows >= cond_len[b] of a slot are never read.  The count is one scalar load per workgroup behind a
+// kernel-uniform test; null keeps Lcond.  A sample must have a key: with no self keys the count is clamped to >= 1.
+__device__ __forceinline__ int attn_cond_rows(const int* cond_len, int b, int Lself, int Lcond) {
+    if (!cond_len) return Lcond;
+    return min(max(cond_len[b], Lself ? 0 : 1), Lcond);
+}
+
 // KSPLIT = true : one workgroup per 16 queries, its 4 waves split the key tiles (latency-bound small grids)
 // KSPLIT = false: one workgroup per 64 queries, each wave owns 16 queries and walks all key tiles (K/V re-read 16x less)
 template <int DT, bool KSPLIT>  // DT = head_dim / 16
@@ -40,7 +50,7 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
     const int h = blockIdx.y, b = blockIdx.z;
     const int r16 = lane & 15, kq = lane >> 4;
     constexpr int D = DT * 16;
-    const int Lk = a.Lself + a.Lcond;
+    const int Lk = a.Lself + attn_cond_rows(a.cond_len, b, a.Lself, a.Lcond);
     const int ntiles = (Lk + 15) / 16;
 
     // Q fragment: lane supplies Q[q0 + r16][16*j + 4*kq + e]  (rows past Lq are clamped; their outputs are not stored)
@@ -242,6 +252,7 @@ __global__ __launch_bounds__(256) void attention_lds_kernel(AttnArgs args) {
 
     // scalar copies of the argument fields: lambdas that capture the argument STRUCT by reference make hipcc spill it to scratch
     const int Lq = args.Lq, Lself = args.Lself, Lcond = args.Lcond, ld_self = args.ld_self, ld_cond = args.ld_cond, ldq = args.ldq, ldo = args.ldo;
+    const int ncond = attn_cond_rows(args.cond_len, blockIdx.z, Lself, Lcond);  // this sample's own conditioning keys; Lcond is the slot pitch
     const int n_kw = args.n_kw;
     const float scale = args.scale;
     const float* const key_weights = args.key_weights;
@@ -251,7 +262,7 @@ __global__ __launch_bounds__(256) void attention_lds_kernel(AttnArgs args) {
     const int q0 = (blockIdx.x * 4 + wave) * 16;
     const int h = blockIdx.y, b = blockIdx.z;
     const int r16 = lane & 15, kq = lane >> 4;
-    const int Lk = Lself + Lcond;
+    const int Lk = Lself + ncond;
     const int ntiles = (Lk + KTILE - 1) / KTILE;
 
     f32x4 qf[DT];
@@ -314,7 +325,7 @@ __global__ __launch_bounds__(256) void attention_lds_kernel(AttnArgs args) {
                 kcb[i] = vcb[i] = (unsigned)(pos * 16);
             }
         }
-        const size_t self_bytes = (size_t)max(Lself, 1) * ld_self * 4, cond_bytes = (size_t)max(Lcond, 1) * ld_cond * 4;
+        const size_t self_bytes = (size_t)max(Lself, 1) * ld_self * 4, cond_bytes = (size_t)max(ncond, 1) * ld_cond * 4;
         rs_ks = attn_rsrc(Lself ? ks_base : kc_base, self_bytes);
         rs_vs = attn_rsrc(Lself ? vs_base : vc_base, self_bytes);
         rs_kc = attn_rsrc(Lcond ? kc_base : ks_base, cond_bytes);
@@ -486,6 +497,7 @@ __global__ __launch_bounds__(256) void attention_bf16_kernel(AttnArgs args) {
     __shared__ __attribute__((aligned(16))) unsigned short smem[2 * STAGE];
 
     const int Lq = args.Lq, Lself = args.Lself, Lcond = args.Lcond, ld16 = args.ld16, ld_cond = args.ld_cond, ldo = args.ldo;
+    const int ncond = attn_cond_rows(args.cond_len, blockIdx.z, Lself, Lcond);  // this sample's own conditioning keys; Lcond is the slot pitch
     const int n_kw = args.n_kw;
     const float scale = args.scale;
     const float* const key_weights = args.key_weights;
@@ -495,7 +507,7 @@ __global__ __launch_bounds__(256) void attention_bf16_kernel(AttnArgs args) {
     const int q0 = (blockIdx.x * 4 + wave) * 16;
     const int h = blockIdx.y, b = blockIdx.z;
     const int r16 = lane & 15, kq = lane >> 4;
-    const int Lk = Lself + Lcond;
+    const int Lk = Lself + ncond;
     const int ntiles = (Lk + KTILE - 1) / KTILE;
 
     s16x4 qf[DT];  // Q[q0 + r16][16 j + 4 kq .. + 3]

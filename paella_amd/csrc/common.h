@@ -266,7 +266,7 @@ int launch_axpby16_req(float* x, const float* y, const float* ab, int B, int64_t
 struct AttnArgs {
     const float* q; int ldq;          // [B*Lq, ...], head h at columns h*D
     const float* k_self; const float* v_self; int ld_self;   // [B*Lself, ...] or null when Lself == 0
-    const float* k_cond; const float* v_cond; int ld_cond;   // [B*Lcond, ...]
+    const float* k_cond; const float* v_cond; int ld_cond;   // [B*Lcond, ...]; with cond_len: B slots of Lcond rows, sample b's keys at the front of slot b
     float* out; int ldo;              // [B*Lq, nhead*D]
     int B, nhead, D, Lq, Lself, Lcond;
     float scale;
@@ -276,6 +276,9 @@ struct AttnArgs {
     // opt-in bf16 fast mode, large query counts (attention_bf16_kernel): q / self k / self v as bf16 column blocks of one buffer (leading dimension ld16 elements),
     // both contractions on v_mfma_f32_16x16x16_bf16 (softmax in fp32; the conditioning K / V stay the fp32 cache and are rounded while staged).  q16 == null -> fp32 kernels
     const unsigned short* q16; const unsigned short* k_self16; const unsigned short* v_self16; int ld16;
+    // ragged conditioning: optional DEVICE table [B], sample b attends the first clamp(cond_len[b], 0, Lcond) rows of its slot and never reads the rest; Lcond is
+    // then the slot pitch only.  null = every sample has Lcond conditioning keys.  key_weights weigh the last n_kw keys of each sample's OWN key sequence
+    const int* cond_len;
 };
 int launch_attention(const AttnArgs& a, hipStream_t stream);
 

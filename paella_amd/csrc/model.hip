@@ -669,18 +669,26 @@ extern "C" int paella_unet_r_embedding(paella_unet* m, const float* r, int B, fl
     return launch_timestep(r, m->freqs.p, m->ts_w.p, m->ts_b.p, nullptr, B, m->cfg.c_r, 0, max_positions, r_embed_out, 1, (hipStream_t)stream);
 }
 
-extern "C" int paella_unet_cond_prepare(paella_unet* m, const float* byt5, int S_byt5, const float* clip,
-                                        const float* const* clip_image, int n_clip_image, int B, void* cond_out,
-                                        size_t cond_bytes, void* ws, size_t ws_bytes, void* stream) {
+// S_slot > 0: the slot form -- the B samples' S rows go to the front of slots slot0 .. slot0 + B - 1 (S_slot >= S rows each) of a larger cache through the
+// epilogue's row remap; the GEMM itself is the plain call's, so the stored rows are the plain call's bit for bit and no other byte of the cache is written
+static int cond_prepare_impl(paella_unet* m, const float* byt5, int S_byt5, const float* clip, const float* const* clip_image, int n_clip_image, int B,
+                             int S_slot, int slot0, void* cond_out, size_t cond_bytes, int* cond_len, void* ws, size_t ws_bytes, void* stream) {
     if (!m || !m->finalized) { paella_set_error("model not finalized"); return PAELLA_ERR_STATE; }
     hipStream_t st = (hipStream_t)stream;
     const paella_unet_config& c = m->cfg;
     const int S = S_byt5 + (clip ? c.clip_seq_len : 0) + n_clip_image * c.clip_seq_len;
     if (B <= 0 || S_byt5 < 0 || n_clip_image < 0) { paella_set_error("bad conditioning shape"); return PAELLA_ERR_ARG; }
+    const bool slots = S_slot > 0;
+    if (slots && (slot0 < 0 || S > S_slot || !cond_len)) {
+        paella_set_error("cond_prepare_slots: %d conditioning rows do not fit a slot of %d rows (or slot0 < 0 / cond_len is null)", S, S_slot);
+        return PAELLA_ERR_ARG;
+    }
+    if (S <= 0 && (slots || m->n_attn > 0)) { paella_set_error("conditioning sequence is empty"); return PAELLA_ERR_ARG; }
+    if (slots) HIP_CHECK_RET(hipMemsetD32Async((hipDeviceptr_t)(cond_len + slot0), S, (size_t)B, st));
     if (m->n_attn == 0) return PAELLA_OK;
-    if (S <= 0 ) { paella_set_error("conditioning sequence is empty"); return PAELLA_ERR_ARG; }
     if (S_byt5 > 0 && !byt5) { paella_set_error("byt5 is null"); return PAELLA_ERR_ARG; }
-    if (cond_bytes < paella_unet_cond_bytes(m, B, S) || !cond_out) { paella_set_error("cond buffer too small"); return PAELLA_ERR_WORKSPACE; }
+    const size_t need = slots ? (size_t)(slot0 + B) * S_slot * (size_t)m->kv_total * sizeof(float) : paella_unet_cond_bytes(m, B, S);
+    if (cond_bytes < need || !cond_out) { paella_set_error("cond buffer too small"); return PAELLA_ERR_WORKSPACE; }
     FwdBuffers f;
     Arena a(ws, ws_bytes);
     carve_cond(m, a, B, S, f);
@@ -694,8 +702,22 @@ extern "C" int paella_unet_cond_prepare(paella_unet* m, const float* byt5, int S
     // every AttnBlock's kv = kv_mapper(c_embed) (src/modules.py:77) and K|V in-projection of those rows in ONE GEMM over the composed weights
     GemmArgs g = gemm_args(f.c_silu, cc, m->kv_w.p, cc, (float*)cond_out, m->kv_total, B * S, m->kv_total, cc);
     g.ep.bias = m->kv_b.p;
+    if (slots) { g.ep.remap_in = S; g.ep.remap_out = S_slot; g.ep.remap_off = slot0 * S_slot; }
     RET_IF(launch_gemm(g, f.splitk, skb, st));
     return PAELLA_OK;
+}
+
+extern "C" int paella_unet_cond_prepare(paella_unet* m, const float* byt5, int S_byt5, const float* clip,
+                                        const float* const* clip_image, int n_clip_image, int B, void* cond_out,
+                                        size_t cond_bytes, void* ws, size_t ws_bytes, void* stream) {
+    return cond_prepare_impl(m, byt5, S_byt5, clip, clip_image, n_clip_image, B, 0, 0, cond_out, cond_bytes, nullptr, ws, ws_bytes, stream);
+}
+
+extern "C" int paella_unet_cond_prepare_slots(paella_unet* m, const float* byt5, int S_byt5, const float* clip, const float* const* clip_image,
+                                              int n_clip_image, int B, int S_slot, int slot0, void* cache, size_t cache_bytes, int* cond_len, void* ws,
+                                              size_t ws_bytes, void* stream) {
+    if (S_slot <= 0) { paella_set_error("cond_prepare_slots: S_slot must be > 0"); return PAELLA_ERR_ARG; }
+    return cond_prepare_impl(m, byt5, S_byt5, clip, clip_image, n_clip_image, B, S_slot, slot0, cache, cache_bytes, cond_len, ws, ws_bytes, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -709,6 +731,7 @@ struct FwdCtx {
     const float* cond;
     const float* attn_w;
     int n_aw;
+    const int* cond_len;  // ragged conditioning: device table [B] of conditioning rows per sample (S = slot pitch), or null
 };
 
 // ResBlock / FeedForwardBlock (reference src/modules.py:43-62, 82-96); x is updated in place
@@ -839,6 +862,7 @@ static int run_attn_block(FwdCtx& cx, const Block& b, float* x, int h, int w) {
     a.key_weights = cx.attn_w; a.n_kw = cx.n_aw;
     a.out16 = wo16 ? cx.f.h16 : nullptr;
     a.q16 = nullptr; a.k_self16 = nullptr; a.v_self16 = nullptr; a.ld16 = 0;
+    a.cond_len = cx.cond_len;
     if (attn16) {
         a.q16 = cx.f.g16; a.ld16 = nq;
         a.k_self16 = self ? cx.f.g16 + ch : nullptr; a.v_self16 = self ? cx.f.g16 + 2 * ch : nullptr;
@@ -873,7 +897,8 @@ extern "C" int paella_unet_forward(paella_unet* m, const int64_t* tokens, const 
 static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                              float mix_c, float mix_u, int H, int W, int S, const float* attn_weights,
                              int n_attn_weights, float* logits_out, const TailArgs* tail, void* ws, size_t ws_bytes, void* stream,
-                             const float* mix_pairs = nullptr) {  // request batch: a DEVICE table [n_unique, 2] of guidance pairs instead of (mix_c, mix_u)
+                             const float* mix_pairs = nullptr,    // request batch: a DEVICE table [n_unique, 2] of guidance pairs instead of (mix_c, mix_u)
+                             const int* cond_len = nullptr) {     // ragged conditioning: a DEVICE table [B] of conditioning rows per sample, S is then the slot pitch of `cond`
     if (!m || !m->finalized) { paella_set_error("model not finalized"); return PAELLA_ERR_STATE; }
     if (!tokens || !r || (!logits_out && !tail)) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
     const paella_unet_config& c = m->cfg;
@@ -886,7 +911,7 @@ static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float*
     if (m->n_attn > 0 && (!cond || S <= 0)) { paella_set_error("conditioning cache missing"); return PAELLA_ERR_ARG; }
     FwdCtx cx;
     cx.m = m; cx.st = (hipStream_t)stream; cx.B = B; cx.H = H; cx.W = W; cx.S = S;
-    cx.cond = (const float*)cond; cx.attn_w = attn_weights; cx.n_aw = attn_weights ? n_attn_weights : 0;
+    cx.cond = (const float*)cond; cx.attn_w = attn_weights; cx.n_aw = attn_weights ? n_attn_weights : 0; cx.cond_len = cond_len;
     Arena a(ws, ws_bytes);
     carve_forward(m, a, B, H, W, S, cx.f);
     if (!a.ok || !ws) { paella_set_error("workspace too small (%zu needed, %zu given)", a.off, ws_bytes); return PAELLA_ERR_WORKSPACE; }
@@ -1051,21 +1076,29 @@ static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float*
     return PAELLA_OK;
 }
 
+// Ragged conditioning (ABI 8): every forward entry point has a _ragged twin that takes `cond_len` right after S -- a DEVICE table [B] with the conditioning rows
+// of each sample, S then being the slot pitch of `cond` (attention.hip: attn_cond_rows).  Both forms are thin wrappers over the one unet_forward_impl.
+extern "C" int paella_unet_forward_shared_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                 float mix_c, float mix_u, int H, int W, int S, const int* cond_len, const float* attn_weights,
+                                                 int n_attn_weights, float* logits_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!logits_out) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
+    return unet_forward_impl(m, tokens, r, cond, B, n_unique, mix_c, mix_u, H, W, S, attn_weights, n_attn_weights, logits_out, nullptr, ws, ws_bytes, stream, nullptr,
+                             cond_len);
+}
 extern "C" int paella_unet_forward_shared(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                           float mix_c, float mix_u, int H, int W, int S, const float* attn_weights,
                                           int n_attn_weights, float* logits_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!logits_out) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
-    return unet_forward_impl(m, tokens, r, cond, B, n_unique, mix_c, mix_u, H, W, S, attn_weights, n_attn_weights, logits_out, nullptr, ws, ws_bytes, stream);
+    return paella_unet_forward_shared_ragged(m, tokens, r, cond, B, n_unique, mix_c, mix_u, H, W, S, nullptr, attn_weights, n_attn_weights, logits_out, ws, ws_bytes, stream);
 }
 
 // One whole sampling step for the counter-based noise mode: Paella.forward + the sampling tail (src/utils.py:43-54) with the head
 // GEMM and the tail fused -- the [rows, num_labels] logits are never written.  Output rows: n_unique with the guidance mix
 // (B == 2 * n_unique, (mix_c, mix_u) != (0, 0)), otherwise B (no guidance; n_unique must equal B).
-extern "C" int paella_unet_forward_sample(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
-                                          float mix_c, float mix_u, int H, int W, int S, const float* attn_weights, int n_attn_weights,
-                                          float temperature, int mode, uint64_t seed, const uint64_t* seed_ptr, uint64_t offset,
-                                          int64_t row_offset, const int64_t* row_offset_ptr, const int64_t* init_noise, float t_next,
-                                          int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+extern "C" int paella_unet_forward_sample_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                 float mix_c, float mix_u, int H, int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights,
+                                                 float temperature, int mode, uint64_t seed, const uint64_t* seed_ptr, uint64_t offset,
+                                                 int64_t row_offset, const int64_t* row_offset_ptr, const int64_t* init_noise, float t_next,
+                                                 int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
     if (!tokens_out) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
     const bool mix = mix_c != 0.f || mix_u != 0.f;
     if (!mix && n_unique != B) { paella_set_error("forward_sample without a guidance mix needs n_unique == B (separate cond / uncond logits take the unfused path)"); return PAELLA_ERR_ARG; }
@@ -1078,21 +1111,36 @@ extern "C" int paella_unet_forward_sample(paella_unet* m, const int64_t* tokens,
     a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = temperature; a.mode = mode; a.noise_q = nullptr; a.seed = seed; a.seed_ptr = seed_ptr;
     a.offset = offset; a.row_offset = row_offset; a.row_offset_ptr = row_offset_ptr; a.init_noise = init_noise; a.mask_u = nullptr; a.t_next = t_next;
     a.tokens_out = tokens_out; a.sampled_out = nullptr;
-    return unet_forward_impl(m, tokens, r, cond, B, n_unique, mix_c, mix_u, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream);
+    return unet_forward_impl(m, tokens, r, cond, B, n_unique, mix_c, mix_u, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, nullptr, cond_len);
+}
+extern "C" int paella_unet_forward_sample(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                          float mix_c, float mix_u, int H, int W, int S, const float* attn_weights, int n_attn_weights,
+                                          float temperature, int mode, uint64_t seed, const uint64_t* seed_ptr, uint64_t offset,
+                                          int64_t row_offset, const int64_t* row_offset_ptr, const int64_t* init_noise, float t_next,
+                                          int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+    return paella_unet_forward_sample_ragged(m, tokens, r, cond, B, n_unique, mix_c, mix_u, H, W, S, nullptr, attn_weights, n_attn_weights, temperature, mode, seed,
+                                             seed_ptr, offset, row_offset, row_offset_ptr, init_noise, t_next, tokens_out, ws, ws_bytes, stream);
 }
 
 // Request batch (ABI 6): the same two entry points with per-sample device tables (common.h: ReqTables).
+extern "C" int paella_unet_forward_shared_req_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                     const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights,
+                                                     float* logits_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!logits_out || !mix_pairs) { paella_set_error("forward_shared_req: null argument (logits_out / mix_pairs)"); return PAELLA_ERR_ARG; }
+    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, logits_out, nullptr, ws, ws_bytes, stream, mix_pairs,
+                             cond_len);
+}
 extern "C" int paella_unet_forward_shared_req(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                               const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
                                               float* logits_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!logits_out || !mix_pairs) { paella_set_error("forward_shared_req: null argument (logits_out / mix_pairs)"); return PAELLA_ERR_ARG; }
-    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, logits_out, nullptr, ws, ws_bytes, stream, mix_pairs);
+    return paella_unet_forward_shared_req_ragged(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, nullptr, attn_weights, n_attn_weights, logits_out, ws, ws_bytes,
+                                                 stream);
 }
 
-extern "C" int paella_unet_forward_sample_req(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
-                                              const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
-                                              const uint64_t* seeds, const float* temperature, int rows_per_sample, uint64_t offset,
-                                              const int64_t* init_noise, float t_next, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+extern "C" int paella_unet_forward_sample_req_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                     const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights,
+                                                     const uint64_t* seeds, const float* temperature, int rows_per_sample, uint64_t offset,
+                                                     const int64_t* init_noise, float t_next, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
     if (!tokens_out || !seeds || !temperature) { paella_set_error("forward_sample_req: null argument (tokens_out / seeds / temperature)"); return PAELLA_ERR_ARG; }
     if (!mix_pairs && n_unique != B) { paella_set_error("forward_sample_req without guidance pairs needs n_unique == B"); return PAELLA_ERR_ARG; }
     if (H <= 0 || W <= 0 || rows_per_sample != H * W) { paella_set_error("forward_sample_req: rows_per_sample (%d) must equal H * W", rows_per_sample); return PAELLA_ERR_ARG; }
@@ -1101,7 +1149,14 @@ extern "C" int paella_unet_forward_sample_req(paella_unet* m, const int64_t* tok
     a.L = m ? m->cfg.num_labels : 0;
     a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f; a.offset = offset; a.init_noise = init_noise; a.t_next = t_next; a.tokens_out = tokens_out;
     a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.rows_per_sample = rows_per_sample;  // (the guidance pairs ride through the head: none left for the tail)
-    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, mix_pairs);
+    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, mix_pairs, cond_len);
+}
+extern "C" int paella_unet_forward_sample_req(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                              const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
+                                              const uint64_t* seeds, const float* temperature, int rows_per_sample, uint64_t offset,
+                                              const int64_t* init_noise, float t_next, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+    return paella_unet_forward_sample_req_ragged(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, nullptr, attn_weights, n_attn_weights, seeds, temperature,
+                                                 rows_per_sample, offset, init_noise, t_next, tokens_out, ws, ws_bytes, stream);
 }
 
 extern "C" int paella_sample_tail_req(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
@@ -1125,11 +1180,11 @@ static int stream_tables_check(const char* who, const int* step, const float* t_
     return PAELLA_OK;
 }
 
-extern "C" int paella_unet_forward_sample_stream(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
-                                                 const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
-                                                 const uint64_t* seeds, const float* temperature, int rows_per_sample, const int* step,
-                                                 const float* t_next, const int* active, const int64_t* init_noise, int64_t* tokens_out, void* ws,
-                                                 size_t ws_bytes, void* stream) {
+extern "C" int paella_unet_forward_sample_stream_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                        const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights,
+                                                        int n_attn_weights, const uint64_t* seeds, const float* temperature, int rows_per_sample, const int* step,
+                                                        const float* t_next, const int* active, const int64_t* init_noise, int64_t* tokens_out, void* ws,
+                                                        size_t ws_bytes, void* stream) {
     if (!tokens_out || !seeds || !temperature) { paella_set_error("forward_sample_stream: null argument (tokens_out / seeds / temperature)"); return PAELLA_ERR_ARG; }
     RET_IF(stream_tables_check("forward_sample_stream", step, t_next, active, init_noise));
     if (!mix_pairs && n_unique != B) { paella_set_error("forward_sample_stream without guidance pairs needs n_unique == B"); return PAELLA_ERR_ARG; }
@@ -1140,7 +1195,15 @@ extern "C" int paella_unet_forward_sample_stream(paella_unet* m, const int64_t* 
     a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f; a.init_noise = init_noise; a.t_next = -1.f; a.tokens_out = tokens_out;
     a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.rows_per_sample = rows_per_sample;
     a.rq.step = step; a.rq.t_next = t_next; a.rq.active = active;
-    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, mix_pairs);
+    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, mix_pairs, cond_len);
+}
+extern "C" int paella_unet_forward_sample_stream(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                 const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
+                                                 const uint64_t* seeds, const float* temperature, int rows_per_sample, const int* step,
+                                                 const float* t_next, const int* active, const int64_t* init_noise, int64_t* tokens_out, void* ws,
+                                                 size_t ws_bytes, void* stream) {
+    return paella_unet_forward_sample_stream_ragged(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, nullptr, attn_weights, n_attn_weights, seeds, temperature,
+                                                    rows_per_sample, step, t_next, active, init_noise, tokens_out, ws, ws_bytes, stream);
 }
 
 extern "C" int paella_sample_tail_stream(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
@@ -1300,25 +1363,35 @@ extern "C" int paella_op_grn_scale(const float* g, const float* gamma, float* sc
                                    void* stream) {
     return launch_grn_scale(g, gamma, scale, tmp, B, rows_per_sample, C, (hipStream_t)stream);
 }
-extern "C" int paella_op_attention(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond,
-                                   float* out, int B, int nhead, int D, int Lq, int Lself, int Lcond, const float* key_weights,
-                                   int n_kw, void* stream) {
+extern "C" int paella_op_attention_ragged(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond,
+                                          float* out, int B, int nhead, int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* key_weights,
+                                          int n_kw, void* stream) {
     AttnArgs a;
     const int ld = nhead * D;
     a.q = q; a.ldq = ld; a.k_self = k_self; a.v_self = v_self; a.ld_self = ld; a.k_cond = k_cond; a.v_cond = v_cond; a.ld_cond = ld;
     a.out = out; a.ldo = ld; a.B = B; a.nhead = nhead; a.D = D; a.Lq = Lq; a.Lself = Lself; a.Lcond = Lcond;
     a.scale = 1.0f / sqrtf((float)D); a.key_weights = key_weights; a.n_kw = key_weights ? n_kw : 0; a.out16 = nullptr;
-    a.q16 = nullptr; a.k_self16 = nullptr; a.v_self16 = nullptr; a.ld16 = 0;
+    a.q16 = nullptr; a.k_self16 = nullptr; a.v_self16 = nullptr; a.ld16 = 0; a.cond_len = cond_len;
     return launch_attention(a, (hipStream_t)stream);
 }
+extern "C" int paella_op_attention(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond,
+                                   float* out, int B, int nhead, int D, int Lq, int Lself, int Lcond, const float* key_weights,
+                                   int n_kw, void* stream) {
+    return paella_op_attention_ragged(q, k_self, v_self, k_cond, v_cond, out, B, nhead, D, Lq, Lself, Lcond, nullptr, key_weights, n_kw, stream);
+}
 // test hook (test_hooks.h): the bf16 attention core of the opt-in fast mode on caller-provided operands: q16 / ks16 / vs16 bf16 [B*L, nhead*D], kc / vc fp32, out16 bf16
-extern "C" int paella_test_attention_bf16(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond, const float* v_cond,
-                                          unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond, const float* key_weights, int n_kw, void* stream) {
+extern "C" int paella_test_attention_bf16_ragged(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond,
+                                                 const float* v_cond, unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond,
+                                                 const int* cond_len, const float* key_weights, int n_kw, void* stream) {
     AttnArgs a;
     const int ld = nhead * D;
     a.q = nullptr; a.ldq = ld; a.k_self = nullptr; a.v_self = nullptr; a.ld_self = ld; a.k_cond = k_cond; a.v_cond = v_cond; a.ld_cond = ld;
     a.out = nullptr; a.ldo = ld; a.B = B; a.nhead = nhead; a.D = D; a.Lq = Lq; a.Lself = Lself; a.Lcond = Lcond;
     a.scale = 1.0f / sqrtf((float)D); a.key_weights = key_weights; a.n_kw = key_weights ? n_kw : 0; a.out16 = out16;
-    a.q16 = q16; a.k_self16 = ks16; a.v_self16 = vs16; a.ld16 = ld;
+    a.q16 = q16; a.k_self16 = ks16; a.v_self16 = vs16; a.ld16 = ld; a.cond_len = cond_len;
     return launch_attention(a, (hipStream_t)stream);
+}
+extern "C" int paella_test_attention_bf16(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond, const float* v_cond,
+                                          unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond, const float* key_weights, int n_kw, void* stream) {
+    return paella_test_attention_bf16_ragged(q16, ks16, vs16, k_cond, v_cond, out16, B, nhead, D, Lq, Lself, Lcond, nullptr, key_weights, n_kw, stream);
 }

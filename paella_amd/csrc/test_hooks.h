@@ -20,6 +20,10 @@ int paella_test_gemm_bf16_ln(const unsigned short* A16, const float* A32, const 
 /* the bf16 attention core of the opt-in fast mode (>= 256 queries in the model): q16 / ks16 / vs16 bf16 [B*L, nhead*D], conditioning k / v fp32, out16 bf16 */
 int paella_test_attention_bf16(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond, const float* v_cond,
                                unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond, const float* key_weights, int n_kw, void* stream);
+/* the same over B slots of Lcond conditioning rows of which sample b attends the first cond_len[b] (int32 device table [B]; NULL = all Lcond) */
+int paella_test_attention_bf16_ragged(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond, const float* v_cond,
+                                      unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* key_weights,
+                                      int n_kw, void* stream);
 /* the fast mode's GlobalResponseNorm apply, in place on a bf16 tensor [rows, C]: h = bf16(h * scale[row / rows_per_sample][c] + shift[c]) (fp32 arithmetic, one rounding) */
 int paella_test_grn_apply16(unsigned short* h, const float* scale, const float* shift, int64_t rows, int rows_per_sample, int C, void* stream);
 /* A/B of the bf16 tile rules: bit 0 = never the 256x128 / 256x256 tiles (the fp32 rules' tiles instead), bit 1 = no persistent ranges of the 256x128 tile,

@@ -71,10 +71,12 @@ class _InferenceOnly(torch.autograd.Function):
 
 
 class CondCache:
-    """Device-resident result of `Paella.prepare_cond` (K/V of the conditioning rows for every AttnBlock)."""
+    """Device-resident result of `Paella.prepare_cond` (K/V of the conditioning rows for every AttnBlock).
+    lens (ragged conditioning): None, or an int32 DEVICE tensor [B] -- the cache is then B slots of S rows, sample b's real rows sit at the front of slot b and
+    lens[b] says how many there are; the attention kernels bound every sample by its own count and never read the rest of a slot."""
 
-    def __init__(self, buf, B, S):
-        self.buf, self.B, self.S = buf, B, S
+    def __init__(self, buf, B, S, lens=None):
+        self.buf, self.B, self.S, self.lens = buf, B, S, lens
 
 
 class Paella(nn.Module):
@@ -353,18 +355,28 @@ class Paella(nn.Module):
         """Bytes of the conditioning cache of B samples with S conditioning rows each: one row-major [B*S, kv_total] fp32 matrix, sample b's rows a contiguous slice."""
         return int(_lib.load().paella_unet_cond_bytes(self._engine(), B, S))
 
-    def prepare_cond(self, byt5, clip=None, clip_image=None, ws=None, out=None):
+    def prepare_cond(self, byt5, clip=None, clip_image=None, ws=None, out=None, slot_rows=None, lens_out=None):
         """Hoisted conditioning work (gen_c_embeddings + kv_mapper + K/V in-projection per AttnBlock).
         out: an optional contiguous uint8 DEVICE tensor of `cond_bytes(B, S)` bytes that receives the cache instead of a fresh buffer -- e.g. the rows of one slot
-        inside a larger cache (the cache is row-major by sample, so a request stream prepares ONE request straight into its slot)."""
+        inside a larger cache (the cache is row-major by sample, so a request stream prepares ONE request straight into its slot).
+        slot_rows (ragged conditioning, with lens_out): the B samples' S rows go to the front of B slots of `slot_rows` >= S rows each -- `out` (or a fresh buffer) has
+        `cond_bytes(B, slot_rows)` bytes, the stored rows are those of the plain call bit for bit and no other byte of `out` is written; lens_out, a contiguous
+        int32 DEVICE tensor [B] (e.g. B entries of a larger cache's table), receives S.  Returns CondCache(out, B, slot_rows, lens_out)."""
         h = self._engine()
         lib = _lib.load()
         dev = self._device()
         byt5, clip, images, arr, B, Sb, S = self._cond_args(byt5, clip, clip_image)
         if S == 0:
             raise ValueError("conditioning sequence is empty")
+        if (slot_rows is None) != (lens_out is None):
+            raise ValueError("slot_rows and lens_out go together")
+        if slot_rows is not None:
+            slot_rows = int(slot_rows)
+            if S > slot_rows:
+                raise ValueError("%d conditioning rows do not fit a slot of %d rows" % (S, slot_rows))
+            self._check_table(lens_out, (B,), torch.int32, "lens_out")
         with torch.cuda.device(dev):
-            nbytes = lib.paella_unet_cond_bytes(h, B, S)
+            nbytes = lib.paella_unet_cond_bytes(h, B, S if slot_rows is None else slot_rows)
             if out is None:
                 buf = torch.empty(int(nbytes), dtype=torch.uint8, device=dev)
             elif out.device != dev or out.dtype != torch.uint8 or not out.is_contiguous() or out.numel() != int(nbytes):
@@ -372,9 +384,20 @@ class Paella(nn.Module):
             else:
                 buf = out
             ws = self._workspace(lib.paella_unet_workspace_bytes(h, B, 0, 0, S), ws)
+            if slot_rows is not None:
+                _lib.check(lib.paella_unet_cond_prepare_slots(h, _lib.ptr(byt5) if Sb > 0 else None, Sb, _lib.ptr(clip), arr, len(images), B, slot_rows, 0,
+                                                              _lib.ptr(buf), buf.numel(), _lib.ptr(lens_out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+                return CondCache(buf, B, slot_rows, lens_out)
             _lib.check(lib.paella_unet_cond_prepare(h, _lib.ptr(byt5) if Sb > 0 else None, Sb, _lib.ptr(clip), arr, len(images), B,
                                                     _lib.ptr(buf), buf.numel(), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
         return CondCache(buf, B, S)
+
+    def _cond_lens(self, cond):
+        """the `cond_len` table of a ragged cache (None for a plain one), checked"""
+        lens = getattr(cond, "lens", None)
+        if lens is not None:
+            self._check_table(lens, (cond.B,), torch.int32, "CondCache.lens")
+        return lens
 
     def gen_c_embeddings(self, byt5, clip, clip_image):
         """reference src/modules.py:223-232 -> [B, S, c_cond]"""
@@ -444,8 +467,19 @@ class Paella(nn.Module):
             out = torch.empty(Bo, H, W, self.num_labels, dtype=torch.float32, device=dev)
         elif tuple(out.shape) != (Bo, H, W, self.num_labels) or out.dtype != torch.float32 or not out.is_contiguous():
             raise ValueError("out must be a contiguous fp32 [B,H,W,num_labels] tensor")
+        lens = self._cond_lens(cond)
         with torch.cuda.device(dev):
             ws = self._workspace(lib.paella_unet_workspace_bytes(h, B, H, W, cond.S), ws)
+            if lens is not None:  # ragged conditioning: the twins with the per-sample row counts (cond.S is the slot pitch)
+                if req_mix is not None:
+                    _lib.check(lib.paella_unet_forward_shared_req_ragged(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(req_mix), H, W, cond.S,
+                                                                         _lib.ptr(lens), _lib.ptr(aw), 0 if aw is None else aw.numel(), _lib.ptr(out), _lib.ptr(ws),
+                                                                         ws.numel(), _lib.stream_ptr(dev)))
+                else:
+                    _lib.check(lib.paella_unet_forward_shared_ragged(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, mix[0], mix[1], H, W, cond.S, _lib.ptr(lens),
+                                                                     _lib.ptr(aw), 0 if aw is None else aw.numel(), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                                                     _lib.stream_ptr(dev)))
+                return out
             if req_mix is not None:
                 _lib.check(lib.paella_unet_forward_shared_req(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(req_mix), H, W, cond.S, _lib.ptr(aw),
                                                               0 if aw is None else aw.numel(), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
@@ -499,8 +533,27 @@ class Paella(nn.Module):
         if tuple(out.shape) != (nu, H, W) or out.dtype != torch.int64 or not out.is_contiguous():
             raise ValueError("out must be a contiguous int64 [B,H,W] tensor")
         aw = self._f32(attn_weights, "attn_weights")
+        lens = self._cond_lens(cond)
         with torch.cuda.device(dev):
             ws = self._workspace(lib.paella_unet_workspace_bytes(h, B, H, W, cond.S), ws)
+            if lens is not None:  # ragged conditioning: the twins with the per-sample row counts (cond.S is the slot pitch)
+                naw = 0 if aw is None else aw.numel()
+                if stream is not None:
+                    _lib.check(lib.paella_unet_forward_sample_stream_ragged(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S,
+                                                                            _lib.ptr(lens), _lib.ptr(aw), naw, _lib.ptr(seeds), _lib.ptr(temps), H * W,
+                                                                            _lib.ptr(stream[0]), _lib.ptr(stream[1]), _lib.ptr(stream[2]), _lib.ptr(init_noise),
+                                                                            _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+                elif req is not None:
+                    _lib.check(lib.paella_unet_forward_sample_req_ragged(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S,
+                                                                         _lib.ptr(lens), _lib.ptr(aw), naw, _lib.ptr(seeds), _lib.ptr(temps), H * W, int(offset),
+                                                                         _lib.ptr(init_noise), float(t_next), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                                                         _lib.stream_ptr(dev)))
+                else:
+                    _lib.check(lib.paella_unet_forward_sample_ragged(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, mix[0], mix[1], H, W, cond.S, _lib.ptr(lens),
+                                                                     _lib.ptr(aw), naw, float(temperature), 1 if argmax else 0, int(seed), _lib.ptr(seed_dev),
+                                                                     int(offset), int(row_offset), _lib.ptr(row_offset_dev), _lib.ptr(init_noise), float(t_next),
+                                                                     _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+                return out
             if stream is not None:
                 _lib.check(lib.paella_unet_forward_sample_stream(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S, _lib.ptr(aw),
                                                                  0 if aw is None else aw.numel(), _lib.ptr(seeds), _lib.ptr(temps), H * W, _lib.ptr(stream[0]),

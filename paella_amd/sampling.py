@@ -47,6 +47,17 @@ def _same_cond_layout(a, b):
     return True
 
 
+def _cond_batch(inputs):
+    """samples in a conditioning dict (None when it has no tensor)"""
+    for k in ("byt5", "clip", "clip_image"):
+        v = inputs.get(k) if inputs is not None else None
+        if isinstance(v, (list, tuple)):
+            v = v[0] if v else None
+        if v is not None:
+            return int(v.size(0))
+    return None
+
+
 def _cond_seq_len(model, inputs):
     """Conditioning rows per sample: S_byt5 + clip_seq_len * [clip] + clip_seq_len * #clip_image (src/modules.py:223-232)."""
     if inputs is None:
@@ -59,6 +70,32 @@ def _cond_seq_len(model, inputs):
     if ci is not None:
         S += n * (len(ci) if isinstance(ci, (list, tuple)) else 1)
     return S
+
+
+def ragged_slot_plan(S_c, S_u, B, row_bytes):
+    """The ONE 2B-slot cache of a guided call whose conditional and unconditional sets have S_c and S_u conditioning rows: the slot pitch max(S_c, S_u), the row
+    count of every slot (conditional group in slots [0, B), unconditional in [B, 2B)), the byte offset of each slot and of the two groups, and the cache size;
+    row_bytes = bytes of one cache row (`Paella.cond_bytes(1, 1)`).  Pure host arithmetic."""
+    S_c, S_u, B, row_bytes = int(S_c), int(S_u), int(B), int(row_bytes)
+    if S_c <= 0 or S_u <= 0 or B <= 0:
+        raise ValueError("a ragged cache needs B > 0 and at least one conditioning row on each side")
+    pitch = max(S_c, S_u)
+    slot_bytes = pitch * row_bytes
+    return dict(pitch=pitch, lens=[S_c] * B + [S_u] * B, slot_bytes=slot_bytes, offsets=[b * slot_bytes for b in range(2 * B)],
+                group_offsets=(0, B * slot_bytes), nbytes=2 * B * slot_bytes)
+
+
+def _prepare_ragged_pair(model, model_inputs, unconditional_inputs, B, ws):
+    """conditional and unconditional sets of different layouts as ONE ragged 2B-slot cache (`ragged_slot_plan`): each group is prepared straight into its slots
+    at its own length, with the GEMM shapes of the plain `prepare_cond` call"""
+    dev = model._device()
+    plan = ragged_slot_plan(_cond_seq_len(model, model_inputs), _cond_seq_len(model, unconditional_inputs), B, model.cond_bytes(1, 1))
+    buf = torch.empty(plan["nbytes"], dtype=torch.uint8, device=dev)
+    lens = torch.empty(2 * B, dtype=torch.int32, device=dev)
+    half = plan["group_offsets"][1]
+    model.prepare_cond(**model_inputs, ws=ws, out=buf[:half], slot_rows=plan["pitch"], lens_out=lens[:B])
+    model.prepare_cond(**unconditional_inputs, ws=ws, out=buf[half:], slot_rows=plan["pitch"], lens_out=lens[B:])
+    return CondCache(buf, 2 * B, plan["pitch"], lens)
 
 
 def _cat_inputs(a, b):
@@ -283,6 +320,13 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
         if native:
             if any_cfg and _same_cond_layout(model_inputs, unconditional_inputs):
                 cond_both = model.prepare_cond(**_cat_inputs(model_inputs, unconditional_inputs), ws=ws)
+                batched = True
+            elif any_cfg and philox and _cond_batch(model_inputs) == B and _cond_batch(unconditional_inputs) == B \
+                    and min(_cond_seq_len(model, model_inputs), _cond_seq_len(model, unconditional_inputs)) > 0:
+                # layouts differ (what conditioning.embed_prompts produces on real prompts): one ragged 2B-slot cache, every sample bounded by its own row count
+                # in the attention kernels -- the same one-forward path as above.  noise="torch" / explicit noise keep the two forwards: their tokens are pinned
+                # to the reference's, whose rounding is that of two separate evaluations
+                cond_both = _prepare_ragged_pair(model, model_inputs, unconditional_inputs, B, ws)
                 batched = True
             if not batched or not all(c is not None for c in cfgs):
                 cond_c = model.prepare_cond(**model_inputs, ws=ws)
@@ -670,6 +714,34 @@ def _cond_layout(inputs):
             for k in ("byt5", "clip", "clip_image")}
 
 
+def min_attention_keys(cfg, H, W, cond_rows):
+    """the shortest key sequence any attention block of a model with constructor arguments `cfg` sees on an H x W token grid when a sample has `cond_rows`
+    conditioning rows: self keys of the smallest grid that has an AttnBlock (none without self_attn) + cond_rows; None for a model without attention"""
+    p, best = int(cfg["patch_size"]), None
+    for l, lc in enumerate(cfg["level_config"]):
+        if "A" in lc:
+            n = (((H // p) >> l) * ((W // p) >> l) if cfg["self_attn"] else 0) + int(cond_rows)
+            best = n if best is None else min(best, n)
+    return best
+
+
+def check_ragged_stream_args(max_cond_rows, n_attn_weights, min_keys):
+    """host validation of `RequestStream(max_cond_rows=N)`: N a positive integer; attn_weights (n_attn_weights of them, 0 = none) weigh the LAST keys of every
+    request's own key sequence, so they must fit the shortest admissible one (min_keys = `min_attention_keys(..., cond_rows=1)`)"""
+    if isinstance(max_cond_rows, bool) or not isinstance(max_cond_rows, int) or max_cond_rows < 1:
+        raise ValueError("max_cond_rows must be None or a positive integer, got %r" % (max_cond_rows,))
+    if n_attn_weights and min_keys is not None and n_attn_weights > min_keys:
+        raise ValueError("attn_weights has %d entries, more than the %d keys of the shortest request a stream with max_cond_rows admits" % (n_attn_weights, min_keys))
+    return max_cond_rows
+
+
+def check_request_rows(rows, max_cond_rows, what):
+    """a request's conditioning rows (ByT5 length + clip + any number of clip_image) must be 1 ... max_cond_rows"""
+    if not 1 <= rows <= max_cond_rows:
+        raise ValueError("%s: %d conditioning rows, the stream admits 1 ... %d (max_cond_rows)" % (what, rows, max_cond_rows))
+    return rows
+
+
 class RequestStream:
     """Continuous request batching: a fixed-shape batch of B SLOTS whose requests join and leave at step boundaries.  Every request has its own seed, step count,
     renoise count, temperature and guidance schedule, timestep range and optionally its own start tokens (`init_x` with `t_start` -- the denoising part of an
@@ -685,10 +757,15 @@ class RequestStream:
     The stream's device state: the in-place token grid and the start-token grid [B, H, W], the 2B-slot (unguided: B-slot) conditioning cache, per slot a program
     (`request_program`), a cursor and a length, the seed words and the flat per-tick tables.  The host mirrors the cursors: no read-back per tick.
     Staleness (as GraphSampler): a changed weight or precision recaptures (on_stale="recapture") or raises (on_stale="raise") while no request is in flight; with
-    requests in flight it always raises -- their conditioning was prepared with the old weights; `reset()` abandons them."""
+    requests in flight it always raises -- their conditioning was prepared with the old weights; `reset()` abandons them.
+
+    max_cond_rows=N (ragged conditioning; None keeps the strict layout check above): the cache has slots of N rows and `admit` takes ANY request whose conditional
+    and unconditional rows (ByT5 length + clip + any number of clip_image) are each 1 ... N -- the two sides need not share a layout, prompts are not padded.  A
+    request is prepared straight into its slots at its own length and attends exactly its own rows: its tokens at a given slot do not depend on the lengths of
+    its batch-mates.  `attn_weights` longer than the shortest admissible key sequence are refused."""
 
     def __init__(self, model, model_inputs, unconditional_inputs, latent_shape, max_steps=12, guided=True, device="cuda", vqgan=None, attn_weights=None,
-                 on_stale="recapture"):
+                 on_stale="recapture", max_cond_rows=None):
         if on_stale not in ("recapture", "raise"):
             raise ValueError("on_stale must be 'recapture' or 'raise'")
         if not isinstance(model, Paella):
@@ -704,14 +781,23 @@ class RequestStream:
         if model_inputs is None or (self.guided and unconditional_inputs is None):
             raise TypeError("a %s stream needs model_inputs%s" % ("guided" if self.guided else "unguided", " and unconditional_inputs" if self.guided else ""))
         self.layout = _cond_layout(model_inputs)
-        if self.guided and _cond_layout(unconditional_inputs) != self.layout:
-            raise ValueError("the conditional and unconditional inputs of a guided stream must share one layout (they are evaluated as one 2B-row batch)")
-        self.S = _cond_seq_len(model, model_inputs)
+        self.max_cond_rows = max_cond_rows
+        if max_cond_rows is not None:
+            check_ragged_stream_args(max_cond_rows, 0 if attn_weights is None else int(attn_weights.numel()), min_attention_keys(model._cfg, H, W, 1))
+            for inputs, what in ((model_inputs, "model_inputs"), (unconditional_inputs, "unconditional_inputs"))[:2 if self.guided else 1]:
+                check_request_rows(_cond_seq_len(model, inputs), max_cond_rows, what)
+            self.S = max_cond_rows
+        else:
+            if self.guided and _cond_layout(unconditional_inputs) != self.layout:
+                raise ValueError("the conditional and unconditional inputs of a guided stream must share one layout (they are evaluated as one 2B-row batch)")
+            self.S = _cond_seq_len(model, model_inputs)
         if self.S <= 0:
             raise ValueError("conditioning sequence is empty")
         dev, nb = self.device, (2 * B if self.guided else B)
         self._slot_bytes = model.cond_bytes(1, self.S)
-        self.cache = CondCache(torch.zeros(nb * self._slot_bytes, dtype=torch.uint8, device=dev), nb, self.S)  # (zero K/V rows: finite work for slots never filled)
+        # (zero K/V rows: finite work for slots never filled; a ragged stream's never-filled slots attend all N of them)
+        lens = None if max_cond_rows is None else torch.full((nb,), self.S, dtype=torch.int32, device=dev)
+        self.cache = CondCache(torch.zeros(nb * self._slot_bytes, dtype=torch.uint8, device=dev), nb, self.S, lens)
         assert self.cache.buf.numel() == model.cond_bytes(nb, self.S)
         self.tokens = torch.zeros(self.shape, dtype=torch.int64, device=dev)    # the in-place grid: a tick reads and writes it
         self.random_x = torch.zeros(self.shape, dtype=torch.int64, device=dev)  # per slot the start tokens of its seed: the renoise source
@@ -791,7 +877,11 @@ class RequestStream:
 
     # ---- requests
     def _check_inputs(self, inputs, what):
-        if inputs is None or _cond_layout(inputs) != self.layout:
+        if self.max_cond_rows is not None:
+            if inputs is None:
+                raise ValueError("%s: missing" % what)
+            check_request_rows(_cond_seq_len(self.model, inputs), self.max_cond_rows, what)
+        elif inputs is None or _cond_layout(inputs) != self.layout:
             raise ValueError("%s: conditioning layout or sequence length differs from the stream's (%r)" % (what, self.layout))
         for k in ("byt5", "clip", "clip_image"):
             v = inputs.get(k)
@@ -826,7 +916,10 @@ class RequestStream:
             # every replay are enqueued on the same (current) stream, so the two users never run concurrently and each launch leaves the tickets zero; and the
             # workspace was sized for the 2B-row forward, which covers the conditioning preparation of one request (prepare_cond checks the size and raises otherwise)
             for row, inputs in ((b, model_inputs), (B + b, unconditional_inputs))[:2 if self.guided else 1]:
-                self.model.prepare_cond(**{k: inputs.get(k) for k in ("byt5", "clip", "clip_image")}, ws=self.ws, out=self.cache.buf[row * nbytes:(row + 1) * nbytes])
+                # ragged stream: at the request's own length into the front of its slot, and its `lens` entry with it (stream-ordered before the next tick)
+                slot = {} if self.cache.lens is None else dict(slot_rows=self.S, lens_out=self.cache.lens[row:row + 1])
+                self.model.prepare_cond(**{k: inputs.get(k) for k in ("byt5", "clip", "clip_image")}, ws=self.ws, out=self.cache.buf[row * nbytes:(row + 1) * nbytes],
+                                        **slot)
             start_tokens(self.model.num_labels, (1, H, W), seed, self.device, out=self.random_x[b:b + 1])
             self.tokens[b].copy_(self.random_x[b] if init_x is None else init_x)
             self.seeds[b].fill_(seed_word(seed))

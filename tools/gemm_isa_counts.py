@@ -4,6 +4,8 @@
     python tools/gemm_isa_counts.py --req-tail <gemm.o> <gemm.resources.txt>     the REQ (request form) fused-tail head tiles instead: per instantiation the
                                                                                  instruction count and the SGPR / VGPR / scratch figures of the remarks
 
+    python tools/gemm_isa_counts.py --attention <attention.o> <attention.resources.txt>   the attention kernels (same columns, one row per instantiation)
+
 Extracts the gfx950 code object from the object's .hip_fatbin (llvm-objcopy + clang-offload-bundler --unbundle), disassembles it with
 `llvm-objdump -d --mcpu=gfx950`, and prints per batch-1 ring instantiation: instructions after the last MFMA, v_readlane_b32 among them,
 instructions before the first buffer load, and (from the kernel-resource remarks) the SGPR spill count."""
@@ -70,9 +72,26 @@ def req_tail(obj, res):
             print("%-64s %8d %7d %7d %7d %8d %10d" % ((args, len(ins)) + rs.get(name, (-1, -1, -1, -1)) + (sum(op.startswith("v_mfma") for op in ins),)))
 
 
+ATTN = re.compile(r"^_Z\d+(attention(?:_lds|_bf16)?_kernel)I(.*)Ev")
+
+
+def attention(obj, res):
+    rs = resources(res)
+    with tempfile.TemporaryDirectory() as tmp:
+        fns = functions(code_object(obj, tmp))
+    print("%-40s %8s %7s %7s %7s %8s %10s" % ("attention kernel <template arguments>", "instr", "SGPR", "VGPR", "spill", "scratch", "v_mfma"))
+    for name, ins in sorted(fns.items()):
+        m = ATTN.match(name)
+        if m:
+            args = ",".join(re.findall(r"L[ib](\d+)E", m.group(2)))
+            print("%-40s %8d %7d %7d %7d %8d %10d" % (("%s<%s>" % (m.group(1), args), len(ins)) + rs.get(name, (-1, -1, -1, -1)) + (sum(op.startswith("v_mfma") for op in ins),)))
+
+
 def main():
     if sys.argv[1] == "--req-tail":
         return req_tail(sys.argv[2], sys.argv[3])
+    if sys.argv[1] == "--attention":
+        return attention(sys.argv[2], sys.argv[3])
     obj = sys.argv[1]
     res = sys.argv[2] if len(sys.argv) > 2 else None
     sp = spills(res)
