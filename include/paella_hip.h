@@ -286,6 +286,50 @@ int paella_unet_forward_sample_stream_ragged(paella_unet* m, const int64_t* toke
                                              const int* step, const float* t_next, const int* active, const int64_t* init_noise,
                                              int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Editing requests (ABI 8, extended ADDITIVELY: the entry points below were added without touching any existing signature, so the
+ * version stays 8 and a caller of ABI 8 keeps working unchanged).  An inpainting / outpainting / structural-editing request knows part
+ * of its token grid; the sampling tail itself re-imposes those tokens -- after the categorical draw and after the renoise:
+ *   tokens_out[row] = (the pin applies to the row's slot && pin_keep[row] == 0) ? pin_tokens[row] : renoised token
+ *   pin_keep    int64 [rows]  the mask type of paella_add_noise / paella_select_tokens: 1 = regenerate, 0 = known
+ *   pin_tokens  int64 [rows]  the known tokens (read only where pin_keep is 0)
+ *   pin_on      int32 [B]     request / stream forms only: this launch's flag per slot (paella_request_step_pin writes it); NULL =
+ *                             the pin applies to every slot.  The scalar forms pin whenever the two row tables are given.
+ * sampled_out stays the raw draw; a slot with active[b] == 0 still stores nothing, pinned or not.  pin_keep and pin_tokens come
+ * together, pin_on only with them, the pin needs categorical mode: anything else is PAELLA_ERR_ARG.  With all pin tables NULL every
+ * entry point below IS the entry point it extends -- same kernels, same launches, same tokens.
+ * ---------------------------------------------------------------------------------------------- */
+/* paella_request_step plus the pin policy of an editing stream: pin_policy int32 [B], per slot 0 = never, 1 = every step, 2 = the
+ * request's final step only (pos[b] + 1 == len[b]); pin_on int32 [B] receives 1 for an active slot whose policy applies at this tick
+ * and 0 otherwise (idle slots included).  Both NULL = paella_request_step; one without the other is PAELLA_ERR_ARG. */
+int paella_request_step_pin(const float* program, int max_steps, int* pos, const int* len, int B, float* r, float* temperature,
+                            float* pairs, float* t_next, int* step, int* active, const int* pin_policy, int* pin_on, void* stream);
+/* paella_sample_tail_ex in the counter-based noise mode (no caller-provided noise) with the pin. */
+int paella_sample_tail_pin(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg,
+                           float temperature, int mode, uint64_t seed, const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset,
+                           const int64_t* row_offset_ptr, const int64_t* init_noise, float t_next, const int64_t* pin_keep,
+                           const int64_t* pin_tokens, int64_t* tokens_out, int64_t* sampled_out, void* stream);
+/* paella_sample_tail_stream with the pin. */
+int paella_sample_tail_stream_pin(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs,
+                                  const float* temperature, const uint64_t* seeds, int rows_per_sample, const int* step,
+                                  const float* t_next, const int* active, const int64_t* init_noise, const int64_t* pin_keep,
+                                  const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, int64_t* sampled_out, void* stream);
+/* paella_unet_forward_sample_ragged with the pin (cond_len may be NULL: the non-ragged entry point). */
+int paella_unet_forward_sample_pin(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                   float mix_c, float mix_u, int H, int W, int S, const int* cond_len, const float* attn_weights,
+                                   int n_attn_weights, float temperature, int mode, uint64_t seed, const uint64_t* seed_ptr,
+                                   uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr, const int64_t* init_noise,
+                                   float t_next, const int64_t* pin_keep, const int64_t* pin_tokens, int64_t* tokens_out, void* ws,
+                                   size_t ws_bytes, void* stream);
+/* paella_unet_forward_sample_stream_ragged with the pin (cond_len may be NULL: the non-ragged entry point): the tick of an editing
+ * stream.  Bit-identical to forward_shared_req(_ragged) + sample_tail_stream_pin. */
+int paella_unet_forward_sample_stream_pin(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                          const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights,
+                                          int n_attn_weights, const uint64_t* seeds, const float* temperature, int rows_per_sample,
+                                          const int* step, const float* t_next, const int* active, const int64_t* init_noise,
+                                          const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out,
+                                          void* ws, size_t ws_bytes, void* stream);
+
 /* x, random_x, mask int64 [B, per_sample]; t fp32 [B].  mask_in NULL -> mask = (u <= t[b]) with u = rand_u
  * (caller noise, [B, per_sample]) or Philox; random_x NULL -> Philox randint(0, num_labels). */
 int paella_add_noise(const int64_t* x, const float* t, const int64_t* mask_in, const int64_t* random_x,

@@ -7,18 +7,22 @@ Public surface (mirrors the reference's Python API):
     sample_distributed        reference src_distributed/utils.py:97
     sample_requests           (extension) B independent requests -- own seed, guidance, temperature -- in one batch; GraphRequestSampler = its captured form
     RequestStream             (extension) continuous batching: requests join and leave a fixed-shape batch at step boundaries, each with its own step count,
-                              start tokens and timestep range (request_program builds one request's schedule); one captured single-step graph serves them all
+                              start tokens and timestep range (request_program builds one request's schedule); one captured single-step graph serves them all.
+                              editing=True: inpainting / outpainting / structural-editing requests (admit(known= or image=, mask=, pin="step" | "final")) share
+                              the batch and the graph with text-to-image ones; the sampling tail re-imposes their known tokens
+    inpaint / GraphInpainter  (extension) encode -> masked renoise -> sample -> decode; pin="step" keeps the known region clean at every step
+    canvas                    (extension) a token grid placed on a larger canvas -> (known, mask): the outpainting set-up
     replace_attention_layers  reference utils/alter_attention.py:45
     load_conditional_models   reference src_distributed/utils.py:65 (+ embed_prompts, load_checkpoint: paella_amd/conditioning.py)
 Everything executes through libpaella_hip.so (hand-written HIP for gfx950, C ABI in include/paella_hip.h).
 The opt-in bf16 fast mode is a per-model switch: `Paella.set_gemm_precision("bf16")` (outside the fp32 parity contract).
 """
 from .conditioning import build_paella, embed_prompts, load_checkpoint, load_conditional_models
-from .editing import GraphInpainter, inpaint
+from .editing import GraphInpainter, canvas, inpaint
 from .modules import CondCache, DenoiseUNet, Paella, replace_attention_layers
 from .sampling import GraphRequestSampler, GraphSampler, RequestStream, request_program, sample, sample_distributed, sample_requests, select_tokens
 from .vqgan import VectorQuantize, VQModel
 
 
 __all__ = ["Paella", "DenoiseUNet", "CondCache", "VQModel", "VectorQuantize", "sample", "sample_distributed", "sample_requests", "GraphSampler", "GraphRequestSampler", "RequestStream", "request_program",
-           "replace_attention_layers", "inpaint", "GraphInpainter", "select_tokens", "load_conditional_models", "embed_prompts", "load_checkpoint", "build_paella"]
+           "replace_attention_layers", "inpaint", "GraphInpainter", "canvas", "select_tokens", "load_conditional_models", "embed_prompts", "load_checkpoint", "build_paella"]

@@ -119,6 +119,19 @@ SIGNATURES = {
                                                          c_void_p]),
     "paella_op_attention_ragged": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int,
                                            c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    # editing requests (ABI 8, additive): the pin tables `pin_keep`, `pin_tokens` (and `pin_on` in the stream forms) right before the outputs
+    "paella_request_step_pin": (c_int, [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                        c_void_p]),
+    "paella_sample_tail_pin": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_float, c_float, c_int, c_uint64, c_void_p, c_uint64, c_int64, c_void_p, c_void_p,
+                                       c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "paella_sample_tail_stream_pin": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                              c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "paella_unet_forward_sample_pin": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_float, c_float, c_int, c_int, c_int, c_void_p,
+                                               c_void_p, c_int, c_float, c_int, c_uint64, c_void_p, c_uint64, c_int64, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                               c_void_p, c_void_p, c_size_t, c_void_p]),
+    "paella_unet_forward_sample_stream_pin": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p,
+                                                      c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                      c_void_p, c_size_t, c_void_p]),
 }
 
 # exported for tests / tools only; declared in paella_amd/csrc/test_hooks.h, not in the public header

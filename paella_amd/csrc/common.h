@@ -299,12 +299,20 @@ struct TailArgs {
     int64_t* tokens_out;          // [rows]
     int64_t* sampled_out;         // [rows] pre-renoise draw (optional, may be null)
     ReqTables rq;                 // rq.rows_per_sample > 0: request form (mode 0, Philox noise only; seed / cfg / temperature / row offsets above unused)
+    // optional pin (editing requests: the known tokens of an inpainting / outpainting request are re-imposed by the tail itself).  After the draw and the renoise,
+    //   tokens_out[row] = (the pin applies to the row's slot && pin_keep[row] == 0) ? pin_tokens[row] : renoised token;     sampled_out stays the raw draw.
+    // Both row tables or neither; null = the kernels of the unpinned tail (one kernel-uniform test in the storing lane).  Categorical mode, Philox noise only.
+    const int64_t* pin_keep = nullptr;    // [rows] the project's mask type: 1 = regenerate, 0 = known
+    const int64_t* pin_tokens = nullptr;  // [rows] the known tokens
+    const int* pin_on = nullptr;          // [B] request form only: this launch's per-slot flag (tail.hip: request_step_kernel emits it); null = the pin applies to every slot
 };
 int launch_sample_tail(const TailArgs& a, hipStream_t stream);
 // one tick of a request stream: per slot b, row pos[b] of its program [B, max_steps, 5] = (r, temperature, cfg, 1 - cfg, t_next) becomes this tick's flat tables
 // (pairs may be null), step[b] = pos[b], active[b] = pos[b] < len[b]; the cursors of the active slots advance.  Idle slots: r 0, T 1, pair (1, 0), t_next -1.
+// pin_policy / pin_on (both or neither; null = exactly the stores above): per slot 0 = never, 1 = every step, 2 = the request's final step only ->
+// pin_on[b] = active && (policy == 1 || (policy == 2 && pos[b] + 1 == len[b])), 0 for idle slots.
 int launch_request_step(const float* program, int max_steps, int* pos, const int* len, int B, float* r, float* temperature, float* pairs, float* t_next,
-                        int* step, int* active, hipStream_t stream);
+                        int* step, int* active, const int* pin_policy, int* pin_on, hipStream_t stream);
 // start tokens of the counter-based mode: out[i] = Philox(seed (+ *seed_ptr), i + row_offset (+ *row_offset_ptr)) % num_labels
 int launch_start_tokens(uint64_t seed, const uint64_t* seed_ptr, int64_t row_offset, const int64_t* row_offset_ptr, int num_labels, int64_t n,
                         int64_t* out, hipStream_t stream);

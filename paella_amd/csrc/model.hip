@@ -1094,12 +1094,22 @@ extern "C" int paella_unet_forward_shared(paella_unet* m, const int64_t* tokens,
 // One whole sampling step for the counter-based noise mode: Paella.forward + the sampling tail (src/utils.py:43-54) with the head
 // GEMM and the tail fused -- the [rows, num_labels] logits are never written.  Output rows: n_unique with the guidance mix
 // (B == 2 * n_unique, (mix_c, mix_u) != (0, 0)), otherwise B (no guidance; n_unique must equal B).
-extern "C" int paella_unet_forward_sample_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
-                                                 float mix_c, float mix_u, int H, int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights,
-                                                 float temperature, int mode, uint64_t seed, const uint64_t* seed_ptr, uint64_t offset,
-                                                 int64_t row_offset, const int64_t* row_offset_ptr, const int64_t* init_noise, float t_next,
-                                                 int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+// The optional pin of the sampling tail (common.h: TailArgs::pin_keep / pin_tokens / pin_on), validated BEFORE anything is enqueued: both row tables or neither,
+// the per-slot flags only with them, categorical mode only.
+static int pin_tables_check(const char* who, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on, int mode) {
+    if (!pin_keep != !pin_tokens) { paella_set_error("%s: pin_keep and pin_tokens must be given together (one pin table without the other)", who); return PAELLA_ERR_ARG; }
+    if (pin_on && !pin_keep) { paella_set_error("%s: pin_on without the pin_keep / pin_tokens row tables", who); return PAELLA_ERR_ARG; }
+    if (pin_keep && mode != 0) { paella_set_error("%s: the pin is not offered in argmax mode", who); return PAELLA_ERR_ARG; }
+    return PAELLA_OK;
+}
+
+extern "C" int paella_unet_forward_sample_pin(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                              float mix_c, float mix_u, int H, int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights,
+                                              float temperature, int mode, uint64_t seed, const uint64_t* seed_ptr, uint64_t offset,
+                                              int64_t row_offset, const int64_t* row_offset_ptr, const int64_t* init_noise, float t_next,
+                                              const int64_t* pin_keep, const int64_t* pin_tokens, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
     if (!tokens_out) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
+    RET_IF(pin_tables_check("forward_sample", pin_keep, pin_tokens, nullptr, mode));
     const bool mix = mix_c != 0.f || mix_u != 0.f;
     if (!mix && n_unique != B) { paella_set_error("forward_sample without a guidance mix needs n_unique == B (separate cond / uncond logits take the unfused path)"); return PAELLA_ERR_ARG; }
     if (mode == 0 && !(temperature > 0.f)) { paella_set_error("temperature must be > 0 in categorical mode (use mode=1 for argmax)"); return PAELLA_ERR_ARG; }
@@ -1110,8 +1120,16 @@ extern "C" int paella_unet_forward_sample_ragged(paella_unet* m, const int64_t* 
     a.L = m ? m->cfg.num_labels : 0;
     a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = temperature; a.mode = mode; a.noise_q = nullptr; a.seed = seed; a.seed_ptr = seed_ptr;
     a.offset = offset; a.row_offset = row_offset; a.row_offset_ptr = row_offset_ptr; a.init_noise = init_noise; a.mask_u = nullptr; a.t_next = t_next;
-    a.tokens_out = tokens_out; a.sampled_out = nullptr;
+    a.tokens_out = tokens_out; a.sampled_out = nullptr; a.pin_keep = pin_keep; a.pin_tokens = pin_tokens;
     return unet_forward_impl(m, tokens, r, cond, B, n_unique, mix_c, mix_u, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, nullptr, cond_len);
+}
+extern "C" int paella_unet_forward_sample_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                 float mix_c, float mix_u, int H, int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights,
+                                                 float temperature, int mode, uint64_t seed, const uint64_t* seed_ptr, uint64_t offset,
+                                                 int64_t row_offset, const int64_t* row_offset_ptr, const int64_t* init_noise, float t_next,
+                                                 int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+    return paella_unet_forward_sample_pin(m, tokens, r, cond, B, n_unique, mix_c, mix_u, H, W, S, cond_len, attn_weights, n_attn_weights, temperature, mode, seed, seed_ptr,
+                                          offset, row_offset, row_offset_ptr, init_noise, t_next, nullptr, nullptr, tokens_out, ws, ws_bytes, stream);
 }
 extern "C" int paella_unet_forward_sample(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                           float mix_c, float mix_u, int H, int W, int S, const float* attn_weights, int n_attn_weights,
@@ -1180,13 +1198,14 @@ static int stream_tables_check(const char* who, const int* step, const float* t_
     return PAELLA_OK;
 }
 
-extern "C" int paella_unet_forward_sample_stream_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
-                                                        const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights,
-                                                        int n_attn_weights, const uint64_t* seeds, const float* temperature, int rows_per_sample, const int* step,
-                                                        const float* t_next, const int* active, const int64_t* init_noise, int64_t* tokens_out, void* ws,
-                                                        size_t ws_bytes, void* stream) {
+extern "C" int paella_unet_forward_sample_stream_pin(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                     const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights,
+                                                     int n_attn_weights, const uint64_t* seeds, const float* temperature, int rows_per_sample, const int* step,
+                                                     const float* t_next, const int* active, const int64_t* init_noise, const int64_t* pin_keep,
+                                                     const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
     if (!tokens_out || !seeds || !temperature) { paella_set_error("forward_sample_stream: null argument (tokens_out / seeds / temperature)"); return PAELLA_ERR_ARG; }
     RET_IF(stream_tables_check("forward_sample_stream", step, t_next, active, init_noise));
+    RET_IF(pin_tables_check("forward_sample_stream", pin_keep, pin_tokens, pin_on, 0));
     if (!mix_pairs && n_unique != B) { paella_set_error("forward_sample_stream without guidance pairs needs n_unique == B"); return PAELLA_ERR_ARG; }
     if (H <= 0 || W <= 0 || rows_per_sample != H * W) { paella_set_error("forward_sample_stream: rows_per_sample (%d) must equal H * W", rows_per_sample); return PAELLA_ERR_ARG; }
     TailArgs a = {};
@@ -1195,7 +1214,16 @@ extern "C" int paella_unet_forward_sample_stream_ragged(paella_unet* m, const in
     a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f; a.init_noise = init_noise; a.t_next = -1.f; a.tokens_out = tokens_out;
     a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.rows_per_sample = rows_per_sample;
     a.rq.step = step; a.rq.t_next = t_next; a.rq.active = active;
+    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens; a.pin_on = pin_on;
     return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, mix_pairs, cond_len);
+}
+extern "C" int paella_unet_forward_sample_stream_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                        const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights,
+                                                        int n_attn_weights, const uint64_t* seeds, const float* temperature, int rows_per_sample, const int* step,
+                                                        const float* t_next, const int* active, const int64_t* init_noise, int64_t* tokens_out, void* ws,
+                                                        size_t ws_bytes, void* stream) {
+    return paella_unet_forward_sample_stream_pin(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, attn_weights, n_attn_weights, seeds, temperature,
+                                                 rows_per_sample, step, t_next, active, init_noise, nullptr, nullptr, nullptr, tokens_out, ws, ws_bytes, stream);
 }
 extern "C" int paella_unet_forward_sample_stream(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                                  const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
@@ -1206,23 +1234,38 @@ extern "C" int paella_unet_forward_sample_stream(paella_unet* m, const int64_t* 
                                                     rows_per_sample, step, t_next, active, init_noise, tokens_out, ws, ws_bytes, stream);
 }
 
-extern "C" int paella_sample_tail_stream(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
-                                         const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active,
-                                         const int64_t* init_noise, int64_t* tokens_out, int64_t* sampled_out, void* stream) {
+extern "C" int paella_sample_tail_stream_pin(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
+                                             const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active,
+                                             const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
+                                             int64_t* tokens_out, int64_t* sampled_out, void* stream) {
     if (!logits_c || !tokens_out || !seeds || !temperature) { paella_set_error("sample_tail_stream: null argument"); return PAELLA_ERR_ARG; }
     RET_IF(stream_tables_check("sample_tail_stream", step, t_next, active, init_noise));
+    RET_IF(pin_tables_check("sample_tail_stream", pin_keep, pin_tokens, pin_on, 0));
     if (rows_per_sample <= 0) { paella_set_error("sample_tail_stream: rows_per_sample must be > 0"); return PAELLA_ERR_ARG; }
     TailArgs a = {};
     a.logits_c = logits_c; a.logits_u = cfg_pairs ? logits_u : nullptr; a.rows = rows; a.L = L; a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f;
     a.init_noise = init_noise; a.t_next = -1.f; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
     a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.cfg_pairs = cfg_pairs; a.rq.rows_per_sample = rows_per_sample;
     a.rq.step = step; a.rq.t_next = t_next; a.rq.active = active;
+    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens; a.pin_on = pin_on;
     return launch_sample_tail(a, (hipStream_t)stream);
+}
+extern "C" int paella_sample_tail_stream(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
+                                         const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active,
+                                         const int64_t* init_noise, int64_t* tokens_out, int64_t* sampled_out, void* stream) {
+    return paella_sample_tail_stream_pin(logits_c, logits_u, rows, L, cfg_pairs, temperature, seeds, rows_per_sample, step, t_next, active, init_noise, nullptr, nullptr,
+                                         nullptr, tokens_out, sampled_out, stream);
 }
 
 extern "C" int paella_request_step(const float* program, int max_steps, int* pos, const int* len, int B, float* r, float* temperature, float* pairs,
                                    float* t_next, int* step, int* active, void* stream) {
-    return launch_request_step(program, max_steps, pos, len, B, r, temperature, pairs, t_next, step, active, (hipStream_t)stream);
+    return launch_request_step(program, max_steps, pos, len, B, r, temperature, pairs, t_next, step, active, nullptr, nullptr, (hipStream_t)stream);
+}
+// paella_request_step for an editing stream: pin_policy int32 [B] (0 never, 1 every step, 2 final step only) -> pin_on int32 [B], this tick's flags
+extern "C" int paella_request_step_pin(const float* program, int max_steps, int* pos, const int* len, int B, float* r, float* temperature, float* pairs,
+                                       float* t_next, int* step, int* active, const int* pin_policy, int* pin_on, void* stream) {
+    if (!!pin_policy != !!pin_on) { paella_set_error("request_step_pin: pin_policy and pin_on must be given together (a null output or a null policy table)"); return PAELLA_ERR_ARG; }
+    return launch_request_step(program, max_steps, pos, len, B, r, temperature, pairs, t_next, step, active, pin_policy, pin_on, (hipStream_t)stream);
 }
 
 extern "C" int paella_start_tokens_req(const uint64_t* seeds, int B, int rows_per_sample, int num_labels, int64_t* tokens_out, void* stream) {
@@ -1244,6 +1287,24 @@ extern "C" int paella_sample_tail_ex(const float* logits_c, const float* logits_
     a.temperature = temperature; a.mode = mode; a.noise_q = noise_q; a.seed = seed; a.seed_ptr = seed_ptr; a.offset = offset;
     a.row_offset = row_offset; a.row_offset_ptr = row_offset_ptr;
     a.init_noise = init_noise; a.mask_u = mask_u; a.t_next = t_next; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
+    return launch_sample_tail(a, (hipStream_t)stream);
+}
+
+// paella_sample_tail_ex in the counter-based noise mode with the optional pin: tokens_out[row] = pin_keep[row] == 0 ? pin_tokens[row] : the renoised draw
+extern "C" int paella_sample_tail_pin(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature, int mode,
+                                      uint64_t seed, const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr,
+                                      const int64_t* init_noise, float t_next, const int64_t* pin_keep, const int64_t* pin_tokens, int64_t* tokens_out,
+                                      int64_t* sampled_out, void* stream) {
+    if (!logits_c || !tokens_out) { paella_set_error("sample_tail_pin: null argument"); return PAELLA_ERR_ARG; }
+    if (mode == 0 && !(temperature > 0.f)) { paella_set_error("temperature must be > 0 in categorical mode (use mode=1 for argmax)"); return PAELLA_ERR_ARG; }
+    if (row_offset < 0) { paella_set_error("row_offset must be >= 0"); return PAELLA_ERR_ARG; }
+    RET_IF(pin_tables_check("sample_tail_pin", pin_keep, pin_tokens, nullptr, mode));
+    TailArgs a = {};
+    a.logits_c = logits_c; a.logits_u = logits_u; a.rows = rows; a.L = L; a.cfg = cfg; a.one_minus_cfg = one_minus_cfg;
+    a.temperature = temperature; a.mode = mode; a.seed = seed; a.seed_ptr = seed_ptr; a.offset = offset;
+    a.row_offset = row_offset; a.row_offset_ptr = row_offset_ptr;
+    a.init_noise = init_noise; a.t_next = t_next; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
+    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens;
     return launch_sample_tail(a, (hipStream_t)stream);
 }
 

@@ -47,6 +47,15 @@ __device__ __forceinline__ int64_t renoise_token(const TailArgs& a, const RowKey
     }
     return tok;
 }
+// the optional pin (common.h: TailArgs::pin_keep / pin_tokens / pin_on), applied by the storing lane after the renoise and only when the row tables are there:
+// the known token of a row whose mask says "known", in the request form only for the slots whose flag is set
+template <bool REQ>
+__device__ __forceinline__ int64_t pin_token(const TailArgs& a, int64_t row, int64_t tok) {
+    if constexpr (REQ) {
+        if (a.pin_on && a.pin_on[fast_div((unsigned)row, a.rq.rps_div)] == 0) return tok;
+    }
+    return a.pin_keep[row] == 0 ? a.pin_tokens[row] : tok;
+}
 template <bool REQ>
 __device__ __forceinline__ RowKey tail_row_key(const TailArgs& a, int64_t row) {
     RowKey k;
@@ -150,7 +159,9 @@ __global__ __launch_bounds__(256) void sample_tail_kernel(TailArgs a) {
         int64_t tok = best_i;
         if (rk.active) {  // an idle slot of a request stream keeps what its rows held
             if (a.sampled_out) a.sampled_out[row] = tok;
-            a.tokens_out[row] = renoise_token(a, rk, row, tok);
+            tok = renoise_token(a, rk, row, tok);
+            if (a.pin_keep) tok = pin_token<REQ>(a, row, tok);  // (kernel-uniform: null = the unpinned tail)
+            a.tokens_out[row] = tok;
         }
     }
 }
@@ -181,7 +192,9 @@ __global__ __launch_bounds__(256) void tail_finalize_kernel(TailArgs a, const fl
         int64_t tok = best_i;
         if (rk.active) {
             if (a.sampled_out) a.sampled_out[row] = tok;
-            a.tokens_out[row] = renoise_token(a, rk, row, tok);
+            tok = renoise_token(a, rk, row, tok);
+            if (a.pin_keep) tok = pin_token<REQ>(a, row, tok);  // (kernel-uniform: null = the unpinned tail)
+            a.tokens_out[row] = tok;
         }
     }
 }
@@ -198,8 +211,19 @@ static int tail_req_prepare(TailArgs& a) {
 }
 #define RET_REQ(r) do { const int _rc = tail_req_prepare(r); if (_rc != PAELLA_OK) return _rc; } while (0)
 
+// the pin tables of either form: both row tables or neither, categorical mode and in-kernel noise only; pin_on belongs to the request form
+static int tail_pin_check(const TailArgs& a) {
+    if (!a.pin_keep && !a.pin_tokens && !a.pin_on) return PAELLA_OK;
+    if (!a.pin_keep != !a.pin_tokens) { paella_set_error("sampling tail: pin_keep and pin_tokens must be given together"); return PAELLA_ERR_ARG; }
+    if (a.pin_on && (!a.pin_keep || a.rq.rows_per_sample <= 0)) { paella_set_error("sampling tail: pin_on needs the pin_keep / pin_tokens row tables and the request form"); return PAELLA_ERR_ARG; }
+    if (a.mode != 0 || a.noise_q || a.mask_u) { paella_set_error("sampling tail: the pin needs categorical mode and in-kernel noise"); return PAELLA_ERR_ARG; }
+    return PAELLA_OK;
+}
+#define RET_PIN(a) do { const int _rc = tail_pin_check(a); if (_rc != PAELLA_OK) return _rc; } while (0)
+
 int launch_tail_finalize(const TailArgs& a, const float* part_score, const int* part_idx, int tiles_n, hipStream_t st) {
     if (a.rows <= 0) return PAELLA_OK;
+    RET_PIN(a);
     if (a.rq.rows_per_sample > 0) {
         TailArgs r = a;
         RET_REQ(r);
@@ -213,6 +237,7 @@ int launch_sample_tail(const TailArgs& a, hipStream_t st) {
     if (a.rows <= 0) return PAELLA_OK;
     if (a.L & 3) { paella_set_error("sample_tail: num_labels %% 4 != 0"); return PAELLA_ERR_ARG; }
     if (a.rows > 0x7fffffff) { paella_set_error("sample_tail: too many rows"); return PAELLA_ERR_ARG; }
+    RET_PIN(a);
     if (a.rq.rows_per_sample > 0) {
         TailArgs r = a;
         RET_REQ(r);
@@ -227,15 +252,19 @@ int launch_sample_tail(const TailArgs& a, hipStream_t st) {
 //   program [B, max_steps, 5] fp32: row j = (r_j, temperature_j, cfg_j, 1 - cfg_j, t_next_j)       cursor pos[b], length len[b]
 // and this launch turns the cursors into the flat per-slot tables the forward's timestep kernel and the stream form of the tail read at this tick, then advances
 // the cursors of the running slots.  A slot whose cursor reached its length is idle: finite placeholder values, active 0 (the tail stores nothing for it).
+// Editing stream: an optional policy per slot (0 never, 1 every step, 2 the request's final step only) becomes this tick's flag pin_on[b] the pinned tail reads;
+// with a null policy table the kernel stores exactly what it stores without one.
 // One thread per slot, plain loads and stores; a slot is touched by its own thread only.  Graph-capturable: everything is device state.
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void request_step_kernel(const float* __restrict__ program, int max_steps, int* __restrict__ pos, const int* __restrict__ len, int B,
                                                            float* __restrict__ r, float* __restrict__ temperature, float* __restrict__ pairs,
-                                                           float* __restrict__ t_next, int* __restrict__ step, int* __restrict__ active) {
+                                                           float* __restrict__ t_next, int* __restrict__ step, int* __restrict__ active,
+                                                           const int* __restrict__ pin_policy, int* __restrict__ pin_on) {
     const int b = blockIdx.x * 256 + threadIdx.x;
     if (b >= B) return;
     const int p = pos[b];
-    const bool on = p >= 0 && p < len[b] && p < max_steps;  // (the last two conditions keep a corrupt cursor or length inside the program)
+    const int n = len[b];
+    const bool on = p >= 0 && p < n && p < max_steps;  // (the last two conditions keep a corrupt cursor or length inside the program)
     float v[5] = {0.f, 1.f, 1.f, 0.f, -1.f};
     if (on) {
         const float* row = program + ((size_t)b * max_steps + p) * 5;
@@ -248,15 +277,21 @@ __global__ __launch_bounds__(256) void request_step_kernel(const float* __restri
     t_next[b] = v[4];
     step[b] = p;
     active[b] = on ? 1 : 0;
+    if (pin_policy) {
+        const int pol = pin_policy[b];
+        pin_on[b] = (on && (pol == 1 || (pol == 2 && p + 1 == n))) ? 1 : 0;
+    }
     if (on) pos[b] = p + 1;
 }
 int launch_request_step(const float* program, int max_steps, int* pos, const int* len, int B, float* r, float* temperature, float* pairs, float* t_next,
-                        int* step, int* active, hipStream_t st) {
+                        int* step, int* active, const int* pin_policy, int* pin_on, hipStream_t st) {
     if (!program || !pos || !len || !r || !temperature || !t_next || !step || !active || B <= 0 || max_steps <= 0) {
         paella_set_error("request_step: null table, B <= 0 or max_steps <= 0");
         return PAELLA_ERR_ARG;
     }
-    hipLaunchKernelGGL(request_step_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, program, max_steps, pos, len, B, r, temperature, pairs, t_next, step, active);
+    if (!pin_policy != !pin_on) { paella_set_error("request_step: pin_policy and pin_on must be given together"); return PAELLA_ERR_ARG; }
+    hipLaunchKernelGGL(request_step_kernel, dim3((unsigned)((B + 255) / 256)), dim3(256), 0, st, program, max_steps, pos, len, B, r, temperature, pairs, t_next, step, active,
+                       pin_policy, pin_on);
     LAUNCH_CHECK_RET();
     return PAELLA_OK;
 }

@@ -490,7 +490,7 @@ class Paella(nn.Module):
         return out
 
     def forward_sample(self, x, r, cond, out, *, temperature, argmax=False, seed=0, seed_dev=None, offset=0, row_offset=0,
-                       row_offset_dev=None, init_noise=None, t_next=0.0, cfg_mix=None, attn_weights=None, ws=None, req=None, stream=None):
+                       row_offset_dev=None, init_noise=None, t_next=0.0, cfg_mix=None, attn_weights=None, ws=None, req=None, stream=None, pin=None):
         """One whole sampling step in the counter-based noise mode (src/utils.py:43-54): the denoiser evaluation with the head
         GEMM and the sampling tail FUSED -- the [B, num_labels, H, W] logits are never materialised.  x int64 [Bx,H,W], r [Bx];
         cfg_mix=(a, b) with cond.B == 2*Bx folds classifier-free guidance through the head (as forward_prepared); without it
@@ -501,7 +501,10 @@ class Paella(nn.Module):
         sample b draws what it draws alone under seeds[b] (counters from the position inside the sample).
         stream=(step, t_next, active) (request stream, with `req`; `offset` and `t_next` are then unused and `init_noise` is required): DEVICE tables with one entry
         per sample -- int32 [Bx] own step index (the Philox step word), fp32 [Bx] renoise threshold (negative: no renoise), int32 [Bx] active flag (0: nothing is
-        stored for the sample, `out` keeps its rows) -- every request of the batch is at its own step; `out` may be `x` (the stream runs in place)."""
+        stored for the sample, `out` keeps its rows) -- every request of the batch is at its own step; `out` may be `x` (the stream runs in place).
+        pin=(keep, known) (scalar form) or pin=(keep, known, pin_on) (with `stream`): editing requests -- int64 [Bx,H,W] DEVICE grids, keep 1 = regenerate / 0 = known;
+        after the draw and the renoise the tail stores known wherever keep == 0, with `stream` only for the samples whose int32 [Bx] flag pin_on is set.  Categorical
+        mode only; not offered with `req` alone.  Without `pin` the call reaches exactly the entry points it reaches without this argument."""
         h = self._engine()
         lib = _lib.load()
         dev = self._device()
@@ -532,10 +535,32 @@ class Paella(nn.Module):
             raise ValueError("forward_sample needs cond.B == Bx (no guidance) or cond.B == 2*Bx with a non-zero cfg_mix")
         if tuple(out.shape) != (nu, H, W) or out.dtype != torch.int64 or not out.is_contiguous():
             raise ValueError("out must be a contiguous int64 [B,H,W] tensor")
+        if pin is not None:
+            if argmax or (req is not None and stream is None) or len(pin) != (2 if stream is None else 3):
+                raise ValueError("forward_sample(pin=...) is categorical and takes (keep, known), or (keep, known, pin_on) together with stream=...; "
+                                 "it is not offered with req=... alone")
+            self._check_table(pin[0], (nu, H, W), torch.int64, "pin keep")
+            self._check_table(pin[1], (nu, H, W), torch.int64, "pin known")
+            if stream is not None:
+                self._check_table(pin[2], (nu,), torch.int32, "pin pin_on")
         aw = self._f32(attn_weights, "attn_weights")
         lens = self._cond_lens(cond)
         with torch.cuda.device(dev):
             ws = self._workspace(lib.paella_unet_workspace_bytes(h, B, H, W, cond.S), ws)
+            if pin is not None:  # editing requests: one entry point per form, `lens` (ragged conditioning) nullable
+                naw = 0 if aw is None else aw.numel()
+                if stream is not None:
+                    _lib.check(lib.paella_unet_forward_sample_stream_pin(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S,
+                                                                         _lib.ptr(lens), _lib.ptr(aw), naw, _lib.ptr(seeds), _lib.ptr(temps), H * W,
+                                                                         _lib.ptr(stream[0]), _lib.ptr(stream[1]), _lib.ptr(stream[2]), _lib.ptr(init_noise),
+                                                                         _lib.ptr(pin[0]), _lib.ptr(pin[1]), _lib.ptr(pin[2]), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                                                         _lib.stream_ptr(dev)))
+                else:
+                    _lib.check(lib.paella_unet_forward_sample_pin(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, mix[0], mix[1], H, W, cond.S, _lib.ptr(lens),
+                                                                  _lib.ptr(aw), naw, float(temperature), 0, int(seed), _lib.ptr(seed_dev), int(offset), int(row_offset),
+                                                                  _lib.ptr(row_offset_dev), _lib.ptr(init_noise), float(t_next), _lib.ptr(pin[0]), _lib.ptr(pin[1]),
+                                                                  _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+                return out
             if lens is not None:  # ragged conditioning: the twins with the per-sample row counts (cond.S is the slot pitch)
                 naw = 0 if aw is None else aw.numel()
                 if stream is not None:

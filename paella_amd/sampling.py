@@ -112,10 +112,15 @@ def _cat_inputs(a, b):
 
 
 def _tail(logits_c, logits_u, rows, L, cfg, omc, temperature, mode, noise_q, seed, offset, init_noise, mask_u, t_next, out,
-          seed_dev=None, row_offset=0, row_offset_dev=None):
+          seed_dev=None, row_offset=0, row_offset_dev=None, pin=None):
     lib = _lib.load()
     dev = logits_c.device
     with torch.cuda.device(dev):
+        if pin is not None:  # (keep, known): the tail writes known[row] wherever keep[row] == 0, after the draw and the renoise
+            _lib.check(lib.paella_sample_tail_pin(_lib.ptr(logits_c), _lib.ptr(logits_u), rows, L, cfg, omc, temperature, mode, seed, _lib.ptr(seed_dev), offset,
+                                                  row_offset, _lib.ptr(row_offset_dev), _lib.ptr(init_noise), t_next, _lib.ptr(pin[0]), _lib.ptr(pin[1]), _lib.ptr(out),
+                                                  None, _lib.stream_ptr(dev)))
+            return
         _lib.check(lib.paella_sample_tail_ex(_lib.ptr(logits_c), _lib.ptr(logits_u), rows, L, cfg, omc, temperature, mode,
                                              _lib.ptr(noise_q), seed, _lib.ptr(seed_dev), offset, row_offset, _lib.ptr(row_offset_dev),
                                              _lib.ptr(init_noise), _lib.ptr(mask_u), t_next, _lib.ptr(out), None, _lib.stream_ptr(dev)))
@@ -271,7 +276,7 @@ def select_tokens(a, b=None, mask=None, flag=None, fill=-1, out=None):
 
 def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x, steps, renoise_steps, t_list, temperatures,
                  cfgs, device, noise="torch", seed=None, attn_weights=None, seed_dev=None, init_noise_buf=None, r_all=None, shard=None,
-                 ws=None, fused_tail=True, row_offset_dev=None, req=None):
+                 ws=None, fused_tail=True, row_offset_dev=None, req=None, pin=None):
     """cfgs: per-step list of (cfg_fp32, one_minus_cfg_fp32) or None (no guidance at that step).
     seed_dev / row_offset_dev / init_noise_buf / r_all: device-resident seed and row-offset words, a buffer for the start tokens
     and the [steps, B] timestep table (HIP-graph capture cannot upload from the host, see GraphSampler); ws: caller-owned
@@ -279,7 +284,9 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
     shard = (lo, total): this call samples rows [lo, lo + B) of a global batch of `total`; with noise="philox" every random
     number is keyed by the GLOBAL row, so the shard reproduces those rows of the unsharded call bit for bit.
     req (RequestTables; noise="philox" only): the B samples are independent requests -- seed, guidance pair and temperature per sample come from its device
-    tables, `seed` / `shard` are unused, `temperatures` must be positive placeholders and `cfgs` only says whether guidance is on."""
+    tables, `seed` / `shard` are unused, `temperatures` must be positive placeholders and `cfgs` only says whether guidance is on.
+    pin=(keep, known) (noise="philox" only; int64 [B, H, W] each): after EVERY step's draw and renoise the tail writes known[row] wherever keep[row] == 0 -- the
+    known region of an editing request stays clean while the model denoises (paella_amd.editing.inpaint(pin="step"))."""
     explicit = isinstance(noise, dict)  # parity tests: {"init_noise": [B,H,W], "q": [rows,L] per step, "u": [B,H,W] per step}
     if not explicit and noise not in ("torch", "philox"):
         raise ValueError("noise must be 'torch', 'philox' or a dict of explicit noise tensors")
@@ -301,6 +308,14 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
     row_offset = 0 if shard is None else int(shard[0]) * H * W
     if req is not None and not (philox and native and shard is None and init_x is None):
         raise ValueError("a request batch needs noise='philox', a paella_amd.Paella model, no shard and no init_x")
+    if pin is not None:
+        if not philox or req is not None:
+            raise ValueError("pin=(keep, known) needs noise='philox' (the counter-based sampling tail re-imposes the known tokens) and no request tables")
+        if any(t == 0 for t in temperatures[:steps]):
+            raise ValueError("pin=(keep, known) is not offered with a step temperature of 0 (the argmax extension)")
+        for name, t in zip(("keep", "known"), pin):
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or tuple(t.shape) != (B, H, W) or t.device.type != "cuda" or not t.is_contiguous():
+                raise ValueError("pin: %s must be a contiguous int64 HIP tensor of shape %s" % (name, (B, H, W)))
     with torch.inference_mode():
         if req is not None:
             init_noise = start_tokens_requests(L, (B, H, W), req.seeds, out=init_noise_buf)
@@ -354,7 +369,7 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
                                      seed=seed, seed_dev=seed_dev, offset=i, row_offset=row_offset, row_offset_dev=row_offset_dev,
                                      init_noise=init_noise if renoise else None,
                                      t_next=t_list[i + 1] if renoise else 0.0, cfg_mix=cfgs[i] if use_cfg and req is None else None, attn_weights=attn_weights, ws=ws,
-                                     req=None if req is None else req.step(i))
+                                     req=None if req is None else req.step(i), **({} if pin is None else {"pin": pin}))
                 sampled = out
                 continue
             if native:
@@ -400,7 +415,7 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
             cfg, omc = cfgs[i] if use_cfg else (1.0, 0.0)
             _tail(lc, lu, rows, L, cfg, omc, temp if mode == 0 else 1.0, mode, noise_q, seed, i,
                   init_noise if renoise else None, mask_u, t_list[i + 1] if renoise else 0.0, out, seed_dev=seed_dev,
-                  row_offset=row_offset, row_offset_dev=row_offset_dev)
+                  row_offset=row_offset, row_offset_dev=row_offset_dev, pin=pin)
             sampled = out  # the tail never reads `sampled`, so one output buffer is enough (stream-ordered reuse)
     return sampled
 
@@ -431,8 +446,9 @@ def sample(model, model_inputs, latent_shape, unconditional_inputs=None, steps=1
 
 def sample_distributed(model, model_inputs, unconditional_inputs, latent_shape, init_x=None, steps=12, renoise_steps=None,
                        temperature=(0.7, 0.3), cfg=(8.0, 8.0), t_start=1.0, t_end=0.0, sampling_conditional_steps=None, *,
-                       noise="torch", seed=None, attn_weights=None, shard=None, fused_tail=True):
-    """Drop-in for reference src_distributed/utils.py:97 `sample` (init_x, cfg schedule, conditional-step cutoff)."""
+                       noise="torch", seed=None, attn_weights=None, shard=None, fused_tail=True, pin=None):
+    """Drop-in for reference src_distributed/utils.py:97 `sample` (init_x, cfg schedule, conditional-step cutoff).
+    Keyword-only extension pin=(keep, known) (noise="philox" only): every step's tail re-imposes known where keep == 0, see `_sample_core`."""
     device = unconditional_inputs["byt5"].device
     if sampling_conditional_steps is None:
         sampling_conditional_steps = steps
@@ -447,7 +463,7 @@ def sample_distributed(model, model_inputs, unconditional_inputs, latent_shape, 
             # `logits * cfgs[i] + logits_u * (1 - cfgs[i])` with a 0-dim fp32 tensor: (1 - cfg) is computed in fp32
             cfgs[i] = (float(sched[i]), float(1 - sched[i]))
     return _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x, steps, renoise_steps, t_list, temperatures,
-                        cfgs, device, noise=noise, seed=seed, attn_weights=attn_weights, shard=shard, fused_tail=fused_tail)
+                        cfgs, device, noise=noise, seed=seed, attn_weights=attn_weights, shard=shard, fused_tail=fused_tail, pin=pin)
 
 
 def _request_schedule(steps, t_start, t_end, guided):
@@ -557,15 +573,20 @@ class GraphSampler:
         """tokens the loop starts from (None = the Philox start tokens); GraphInpainter encodes + renoises an image here"""
         return None
 
+    def _pin(self):
+        """(keep, known) the tail of every step re-imposes (called after `_init_x`), or None; GraphInpainter(pin="step") returns its mask and encoded tokens"""
+        return None
+
     def _finish(self, toks):
         return toks
 
     def _run(self):
         k = self.kw
         t_list, temps, cfgs = self._schedule()
-        toks = _sample_core(self.model, self.cond, self.uncond, self.shape, self._init_x(), k["steps"], k["renoise_steps"], t_list, temps, cfgs,
+        init_x = self._init_x()
+        toks = _sample_core(self.model, self.cond, self.uncond, self.shape, init_x, k["steps"], k["renoise_steps"], t_list, temps, cfgs,
                             self.device, noise="philox", seed=0, attn_weights=self.attn_weights, seed_dev=self.seed_dev,
-                            init_noise_buf=self.init_noise, r_all=self.r_all, ws=self.ws, row_offset_dev=self.row_offset_dev)
+                            init_noise_buf=self.init_noise, r_all=self.r_all, ws=self.ws, row_offset_dev=self.row_offset_dev, pin=self._pin())
         toks = self._finish(toks)
         return toks if self.vqgan is None else (toks, self.vqgan.decode_indices(toks, ws=self.vq_ws))
 
@@ -666,6 +687,8 @@ class GraphRequestSampler(GraphSampler):
 
 # ---------------------------------------------------------------------------------------------------------------- continuous request batching
 _IDLE_ROW = (0.0, 1.0, 1.0, 0.0, -1.0)  # what an idle slot runs with: finite, never renoising (tail.hip: request_step_kernel fills the same values)
+# pin policy of a slot of an editing stream (tail.hip: request_step_kernel): when the tail re-imposes the slot's known tokens
+PIN_POLICY = {"never": 0, "step": 1, "final": 2}
 
 
 def request_program(steps, renoise_steps=None, temperature=(1.0, 0.2), cfg=8.0, t_start=1.0, t_end=0.0, max_steps=None, *, guided=None):
@@ -762,10 +785,21 @@ class RequestStream:
     max_cond_rows=N (ragged conditioning; None keeps the strict layout check above): the cache has slots of N rows and `admit` takes ANY request whose conditional
     and unconditional rows (ByT5 length + clip + any number of clip_image) are each 1 ... N -- the two sides need not share a layout, prompts are not padded.  A
     request is prepared straight into its slots at its own length and attends exactly its own rows: its tokens at a given slot do not depend on the lengths of
-    its batch-mates.  `attn_weights` longer than the shortest admissible key sequence are refused."""
+    its batch-mates.  `attn_weights` longer than the shortest admissible key sequence are refused.
+
+    editing=True (default False: today's launches and state, with or without max_cond_rows): the stream also serves inpainting / outpainting / structural-editing
+    requests next to text-to-image ones, in the same batch and the same captured graph.  It then owns two more grids [B, H, W] int64 -- `keep` (1 = regenerate,
+    0 = known; all ones for a plain request) and `known` -- and per slot a pin policy (`PIN_POLICY`: never / every step / final step only); its tick is
+    `paella_request_step_pin`, which turns the policies into this tick's per-slot flags `pin_on`, plus the pinned stream forward, whose tail writes known[row]
+    over the draw wherever the slot's flag is set and keep[row] == 0.  `admit(known=, mask=)` or `admit(image=, mask=)` (encoded with the stream's VQGAN at
+    admission) starts the request from `add_noise(known, t_start, mask=mask, random_x=R)`, R the salted Philox start tokens of the request's seed, as
+    `paella_amd.inpaint(noise="philox")` does.  Contract: an editing request with pin="final" produces the tokens of `inpaint(..., keep_known=True, noise="philox",
+    seed=seed, decode=False)` at batch 1, with pin="step" those of `inpaint(..., pin="step", ...)` (both for a stream of B = 1; the logits of a larger B may differ
+    in their last bits, as for every request of a stream); in both cases the tokens at a given slot and B are independent of the batch-mates and of the admission
+    tick, bit for bit.  `captures` stays 1 while text-to-image and editing requests of either policy come and go."""
 
     def __init__(self, model, model_inputs, unconditional_inputs, latent_shape, max_steps=12, guided=True, device="cuda", vqgan=None, attn_weights=None,
-                 on_stale="recapture", max_cond_rows=None):
+                 on_stale="recapture", max_cond_rows=None, editing=False):
         if on_stale not in ("recapture", "raise"):
             raise ValueError("on_stale must be 'recapture' or 'raise'")
         if not isinstance(model, Paella):
@@ -812,6 +846,13 @@ class RequestStream:
         self.step = torch.zeros(B, dtype=torch.int32, device=dev)
         self.active_dev = torch.zeros(B, dtype=torch.int32, device=dev)
         self._pos, self._len, self._held = [0] * B, [0] * B, [False] * B  # host mirror: cursor, length, slot taken (admitted and not yet collected)
+        self.editing = bool(editing)
+        self.keep = self.known = self.pin_policy = self.pin_on = None
+        if self.editing:
+            self.keep = torch.ones(self.shape, dtype=torch.int64, device=dev)    # 1 = regenerate, 0 = known (the project's mask type)
+            self.known = torch.zeros(self.shape, dtype=torch.int64, device=dev)
+            self.pin_policy = torch.zeros(B, dtype=torch.int32, device=dev)      # PIN_POLICY per slot
+            self.pin_on = torch.zeros(B, dtype=torch.int32, device=dev)          # this tick's flags, written by the step kernel
         self.captures = 0
         self._capture()
 
@@ -830,12 +871,18 @@ class RequestStream:
     def _tick_launches(self):
         B = self.shape[0]
         with torch.cuda.device(self.device):
-            _lib.check(_lib.load().paella_request_step(_lib.ptr(self.program), self.max_steps, _lib.ptr(self.pos), _lib.ptr(self.len), B, _lib.ptr(self.r),
-                                                       _lib.ptr(self.temps), _lib.ptr(self.pairs), _lib.ptr(self.t_next), _lib.ptr(self.step), _lib.ptr(self.active_dev),
-                                                       _lib.stream_ptr(self.device)))
+            if self.editing:
+                _lib.check(_lib.load().paella_request_step_pin(_lib.ptr(self.program), self.max_steps, _lib.ptr(self.pos), _lib.ptr(self.len), B, _lib.ptr(self.r),
+                                                               _lib.ptr(self.temps), _lib.ptr(self.pairs), _lib.ptr(self.t_next), _lib.ptr(self.step),
+                                                               _lib.ptr(self.active_dev), _lib.ptr(self.pin_policy), _lib.ptr(self.pin_on), _lib.stream_ptr(self.device)))
+            else:
+                _lib.check(_lib.load().paella_request_step(_lib.ptr(self.program), self.max_steps, _lib.ptr(self.pos), _lib.ptr(self.len), B, _lib.ptr(self.r),
+                                                           _lib.ptr(self.temps), _lib.ptr(self.pairs), _lib.ptr(self.t_next), _lib.ptr(self.step),
+                                                           _lib.ptr(self.active_dev), _lib.stream_ptr(self.device)))
         # in place: the token gather at the head of the forward and the token store at its tail are different kernels of one stream (as in _sample_core)
         self.model.forward_sample(self.tokens, self.r, self.cache, self.tokens, temperature=1.0, init_noise=self.random_x, attn_weights=self.attn_weights, ws=self.ws,
-                                  req=(self.seeds, self.temps, self.pairs), stream=(self.step, self.t_next, self.active_dev))
+                                  req=(self.seeds, self.temps, self.pairs), stream=(self.step, self.t_next, self.active_dev),
+                                  **({"pin": (self.keep, self.known, self.pin_on)} if self.editing else {}))
 
     _state = GraphSampler._state
 
@@ -889,13 +936,43 @@ class RequestStream:
                 if t.size(0) != 1:
                     raise ValueError("%s: admit takes the inputs of ONE request (leading dimension 1), got %d for %s" % (what, t.size(0), k))
 
+    def _check_edit(self, known, mask, image, pin):
+        """the editing arguments of `admit`, validated before anything touches the stream: (known or image, mask int64 0/1) on the device, or (None, None)"""
+        B, H, W = self.shape
+        if pin not in PIN_POLICY or pin == "never":
+            raise ValueError("pin must be 'step' or 'final', got %r" % (pin,))
+        if known is None and mask is None and image is None:
+            return None, None, None
+        if not self.editing:
+            raise ValueError("known / mask / image need an editing stream: construct RequestStream(..., editing=True)")
+        if image is not None and known is not None:
+            raise ValueError("image and known are mutually exclusive (image is encoded into known at admission)")
+        if mask is None or (known is None and image is None):
+            raise ValueError("an editing request needs a mask together with known tokens or an image (got %s)" % ("a mask alone" if mask is not None else "no mask"))
+        if not torch.is_tensor(mask) or tuple(mask.shape) != (H, W) or mask.dtype.is_floating_point or mask.dtype.is_complex:
+            raise ValueError("mask must be an integer or bool tensor [%d, %d] on the token grid (1 = regenerate)" % (H, W))
+        if known is not None and (not torch.is_tensor(known) or tuple(known.shape) != (H, W) or known.dtype != torch.int64):
+            raise ValueError("known must be an int64 tensor [%d, %d]" % (H, W))
+        if image is not None:
+            if self.vqgan is None:
+                raise ValueError("image= needs a stream with a VQGAN (RequestStream(..., vqgan=...)): it is encoded at admission")
+            f = 2 ** self.vqgan.levels
+            if not torch.is_tensor(image) or tuple(image.shape) != (3, f * H, f * W) or image.dtype != torch.float32:
+                raise ValueError("image must be an fp32 tensor [3, %d, %d] in [0, 1]" % (f * H, f * W))
+        return known, (mask != 0).to(device=self.device, dtype=torch.int64), image
+
     def admit(self, model_inputs, unconditional_inputs=None, seed=None, steps=12, renoise_steps=None, temperature=(1.0, 0.2), cfg=8.0, t_start=1.0, t_end=0.0,
-              init_x=None):
+              init_x=None, known=None, mask=None, image=None, pin="step"):
         """Put ONE request into a free slot; it runs from the next tick on.  Inputs: leading dimension 1, the stream's layout.  Schedule arguments as
         `request_program` (an unguided stream takes cfg=None); init_x int64 [H, W]: the tokens the request starts from instead of its seed's start tokens.
         Everything here is eager work on the current stream, ordered before the next tick: the conditioning of the one request is prepared straight into the
-        slot's rows of the cache.  Raises RuntimeError when no slot is free.  Returns the slot."""
+        slot's rows of the cache.  Raises RuntimeError when no slot is free.  Returns the slot.
+        Editing stream: known int64 [H, W] tokens (or image fp32 [3, f*H, f*W] in [0, 1], encoded here with the stream's VQGAN) and mask [H, W] on the token grid
+        (1 = regenerate) make this an editing request -- unless init_x is given it starts from add_noise(known, t_start, mask=mask, random_x=R), R the salted Philox
+        start tokens of `seed`; pin="step" re-imposes the known tokens after every step, pin="final" after the request's last step only.  A request without them
+        is a plain one: policy never, keep = ones."""
         B, H, W = self.shape
+        known, mask, image = self._check_edit(known, mask, image, pin)
         program, n = request_program(steps, renoise_steps, temperature, cfg, t_start, t_end, max_steps=self.max_steps, guided=self.guided)
         self._check_inputs(model_inputs, "model_inputs")
         if self.guided:
@@ -921,6 +998,20 @@ class RequestStream:
                 self.model.prepare_cond(**{k: inputs.get(k) for k in ("byt5", "clip", "clip_image")}, ws=self.ws, out=self.cache.buf[row * nbytes:(row + 1) * nbytes],
                                         **slot)
             start_tokens(self.model.num_labels, (1, H, W), seed, self.device, out=self.random_x[b:b + 1])
+            if self.editing:
+                if mask is None:
+                    self.keep[b].fill_(1)
+                    self.pin_policy[b].fill_(PIN_POLICY["never"])
+                else:
+                    if image is not None:
+                        known = self.vqgan.encode(image[None].to(self.device), ws=self.vq_ws)[2][0]
+                    self.known[b].copy_(known)
+                    self.keep[b].copy_(mask)
+                    self.pin_policy[b].fill_(PIN_POLICY[pin])
+                    if init_x is None:  # what inpaint(noise="philox") starts a batch of one from (editing.py: _philox_random_x)
+                        from .editing import RANDOM_X_SALT
+                        rx = start_tokens(self.model.num_labels, (1, H, W), (int(seed) + RANDOM_X_SALT) & 0xFFFFFFFFFFFFFFFF, self.device)
+                        init_x = self.model.add_noise(self.known[b:b + 1], torch.full((1,), float(t_start), device=self.device), mask=self.keep[b:b + 1], random_x=rx)[0][0]
             self.tokens[b].copy_(self.random_x[b] if init_x is None else init_x)
             self.seeds[b].fill_(seed_word(seed))
             self.program[b].copy_(program)
@@ -936,6 +1027,8 @@ class RequestStream:
         B = self.shape[0]
         self.len.zero_()
         self.pos.zero_()
+        if self.editing:
+            self.pin_policy.zero_()
         self._pos, self._len, self._held = [0] * B, [0] * B, [False] * B
 
     def tick(self, graph=True):
