@@ -330,6 +330,46 @@ int paella_unet_forward_sample_stream_pin(paella_unet* m, const int64_t* tokens,
                                           const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out,
                                           void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Per-request prompt weights (ABI 8, extended ADDITIVELY as the editing entry points were: no existing signature changes, the version
+ * stays 8).  attn_weights (utils/alter_attention.py:23-34: post-softmax multipliers of the LAST n keys, no renormalisation) is one
+ * vector per launch in every entry point above.  The entry points below take two DEVICE tables with one row per conditioning SLOT of
+ * the launch instead -- B rows, so the conditional and the unconditional half of a guided step (B == 2 * n_unique) carry independent
+ * rows and every request of a batch its own:
+ *   kw_table  fp32  [B, kw_pitch]  row b = the multipliers of slot b at its front
+ *   kw_len    int32 [B]            how many there are; 0 = slot b is unweighted
+ *   kw_pitch  int                  the row pitch in floats (>= 1)
+ * Slot b weighs the last n = clamp(kw_len[b], 0, min(its own key count, kw_pitch)) keys of its OWN key sequence (self keys + its conditioning rows,
+ * cond_len[b] of them in a ragged launch): key (count - n + i) is multiplied by kw_table[b * kw_pitch + i].  Three properties hold in
+ * every attention kernel: (1) slot b of a table launch equals, bit for bit, the same kernel launched for that sample alone with the
+ * shared vector = row b, n_attn_weights = n -- or with attn_weights == NULL when n == 0; (2) entries >= n of a row are never read
+ * (they may hold anything, NaN included), and a row with n == 0 is not read at all; (3) kw_len == NULL: kw_table is ignored and each
+ * entry point below IS the entry point it extends with attn_weights == NULL -- same launches, same results.  A count larger than the
+ * slot's key sequence is clamped, which shifts the meaning of the row: the caller validates (paella_amd does, at admission).
+ * Each entry point is the most general member of its family: cond_len is nullable (NULL = every slot has S rows), and so are the pin
+ * tables of the two sampling ones (all NULL = the unpinned tail).  kw_len without kw_table, or kw_pitch < 1, is PAELLA_ERR_ARG.
+ * ---------------------------------------------------------------------------------------------- */
+/* paella_unet_forward_shared_req_ragged with the table.  mix_pairs may be NULL here: no guidance mix, logits_out holds the B rows
+ * (n_unique dividing B as in paella_unet_forward_shared). */
+int paella_unet_forward_shared_req_kw(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                      const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table,
+                                      const int* kw_len, int kw_pitch, float* logits_out, void* ws, size_t ws_bytes, void* stream);
+/* paella_unet_forward_sample_req_ragged with the table and the pin tables (pin_on may be NULL alone: the pin applies to every slot).
+ * Tokens are bit-identical to forward_shared_req_kw + paella_sample_tail_req. */
+int paella_unet_forward_sample_req_kw(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                      const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table,
+                                      const int* kw_len, int kw_pitch, const uint64_t* seeds, const float* temperature,
+                                      int rows_per_sample, uint64_t offset, const int64_t* init_noise, float t_next,
+                                      const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, void* ws,
+                                      size_t ws_bytes, void* stream);
+/* paella_unet_forward_sample_stream_pin with the table: the tick of a stream whose requests carry their own prompt weights. */
+int paella_unet_forward_sample_stream_kw(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                         const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table,
+                                         const int* kw_len, int kw_pitch, const uint64_t* seeds, const float* temperature,
+                                         int rows_per_sample, const int* step, const float* t_next, const int* active,
+                                         const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
+                                         int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream);
+
 /* x, random_x, mask int64 [B, per_sample]; t fp32 [B].  mask_in NULL -> mask = (u <= t[b]) with u = rand_u
  * (caller noise, [B, per_sample]) or Philox; random_x NULL -> Philox randint(0, num_labels). */
 int paella_add_noise(const int64_t* x, const float* t, const int64_t* mask_in, const int64_t* random_x,
@@ -404,6 +444,11 @@ int paella_op_attention(const float* q, const float* k_self, const float* v_self
 int paella_op_attention_ragged(const float* q, const float* k_self, const float* v_self, const float* k_cond,
                                const float* v_cond, float* out, int B, int nhead, int D, int Lq, int Lself, int Lcond,
                                const int* cond_len, const float* key_weights, int n_kw, void* stream);
+/* the same with one key-weight row per sample (kw_table fp32 [B, kw_pitch], kw_len int32 [B]: see "Per-request prompt weights") in place of the shared
+ * vector; cond_len may be NULL, kw_len == NULL = no weights */
+int paella_op_attention_kw(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond,
+                           float* out, int B, int nhead, int D, int Lq, int Lself, int Lcond, const int* cond_len,
+                           const float* kw_table, const int* kw_len, int kw_pitch, void* stream);
 
 #ifdef __cplusplus
 }

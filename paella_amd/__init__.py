@@ -10,6 +10,8 @@ Public surface (mirrors the reference's Python API):
                               start tokens and timestep range (request_program builds one request's schedule); one captured single-step graph serves them all.
                               editing=True: inpainting / outpainting / structural-editing requests (admit(known= or image=, mask=, pin="step" | "final")) share
                               the batch and the graph with text-to-image ones; the sampling tail re-imposes their known tokens
+    KeyWeights                (extension) per-request prompt weights: one row of post-softmax key multipliers per conditioning slot instead of one attn_weights
+                              vector per launch; sample_requests / GraphRequestSampler / RequestStream.admit take attn_weights per request, per guidance side
     inpaint / GraphInpainter  (extension) encode -> masked renoise -> sample -> decode; pin="step" keeps the known region clean at every step
     canvas                    (extension) a token grid placed on a larger canvas -> (known, mask): the outpainting set-up
     replace_attention_layers  reference utils/alter_attention.py:45
@@ -19,10 +21,10 @@ The opt-in bf16 fast mode is a per-model switch: `Paella.set_gemm_precision("bf1
 """
 from .conditioning import build_paella, embed_prompts, load_checkpoint, load_conditional_models
 from .editing import GraphInpainter, canvas, inpaint
-from .modules import CondCache, DenoiseUNet, Paella, replace_attention_layers
+from .modules import CondCache, DenoiseUNet, KeyWeights, Paella, replace_attention_layers
 from .sampling import GraphRequestSampler, GraphSampler, RequestStream, request_program, sample, sample_distributed, sample_requests, select_tokens
 from .vqgan import VectorQuantize, VQModel
 
 
-__all__ = ["Paella", "DenoiseUNet", "CondCache", "VQModel", "VectorQuantize", "sample", "sample_distributed", "sample_requests", "GraphSampler", "GraphRequestSampler", "RequestStream", "request_program",
+__all__ = ["Paella", "DenoiseUNet", "CondCache", "KeyWeights", "VQModel", "VectorQuantize", "sample", "sample_distributed", "sample_requests", "GraphSampler", "GraphRequestSampler", "RequestStream", "request_program",
            "replace_attention_layers", "inpaint", "GraphInpainter", "canvas", "select_tokens", "load_conditional_models", "embed_prompts", "load_checkpoint", "build_paella"]

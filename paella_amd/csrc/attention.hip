@@ -39,6 +39,17 @@ __device__ __forceinline__ int attn_cond_rows(const int* cond_len, int b, int Ls
     return min(max(cond_len[b], Lself ? 0 : 1), Lcond);
 }
 
+// Per-sample key weights (AttnArgs::kw_table / kw_len / kw_pitch): with the count table given, sample b weighs the last n = clamp(kw_len[b], 0, Lk) keys of its own
+// sequence with the first n entries of row b -- from here on the kernels run the shared-vector code on (row b, n), so sample b computes, bit for bit, what a launch
+// for it alone with key_weights = row b, n_kw = n computes, and entries >= n of a row are never read.  n == 0 returns NO vector: the sample takes the unweighted
+// path (the gather below clamps its index to n_kw - 1, which would be -1: a read in front of the row).  The count is one scalar load per workgroup behind a
+// kernel-uniform test; null keeps the shared vector and its length, whatever kw_table holds.
+__device__ __forceinline__ const float* attn_key_weights(const float* key_weights, const float* kw_table, const int* kw_len, int kw_pitch, int b, int Lk, int& n_kw) {
+    if (!kw_len) return key_weights;
+    n_kw = min(max(kw_len[b], 0), min(Lk, kw_pitch));  // (a count beyond the row pitch is the caller's error: never a read past the row)
+    return n_kw ? kw_table + (size_t)b * kw_pitch : nullptr;
+}
+
 // KSPLIT = true : one workgroup per 16 queries, its 4 waves split the key tiles (latency-bound small grids)
 // KSPLIT = false: one workgroup per 64 queries, each wave owns 16 queries and walks all key tiles (K/V re-read 16x less)
 template <int DT, bool KSPLIT>  // DT = head_dim / 16
@@ -52,6 +63,8 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
     constexpr int D = DT * 16;
     const int Lk = a.Lself + attn_cond_rows(a.cond_len, b, a.Lself, a.Lcond);
     const int ntiles = (Lk + 15) / 16;
+    int n_kw = a.n_kw;
+    const float* const key_weights = attn_key_weights(a.key_weights, a.kw_table, a.kw_len, a.kw_pitch, b, Lk, n_kw);
 
     // Q fragment: lane supplies Q[q0 + r16][16*j + 4*kq + e]  (rows past Lq are clamped; their outputs are not stored)
     f32x4 qf[DT];
@@ -119,12 +132,12 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
         }
         l_run = l_run * alpha + psum;  // per-lane partial; lanes of equal r16 are combined at the end
         m_run = m_new;
-        if (a.key_weights) {
+        if (key_weights) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
-                const int wi = kt * 16 + kq * 4 + r - (Lk - a.n_kw);
-                const float wv = a.key_weights[min(max(wi, 0), a.n_kw - 1)];
-                if (wi >= 0 && wi < a.n_kw) p[r] *= wv;
+                const int wi = kt * 16 + kq * 4 + r - (Lk - n_kw);
+                const float wv = key_weights[min(max(wi, 0), n_kw - 1)];
+                if (wi >= 0 && wi < n_kw) p[r] *= wv;
             }
         }
 #pragma unroll
@@ -253,9 +266,7 @@ __global__ __launch_bounds__(256) void attention_lds_kernel(AttnArgs args) {
     // scalar copies of the argument fields: lambdas that capture the argument STRUCT by reference make hipcc spill it to scratch
     const int Lq = args.Lq, Lself = args.Lself, Lcond = args.Lcond, ld_self = args.ld_self, ld_cond = args.ld_cond, ldq = args.ldq, ldo = args.ldo;
     const int ncond = attn_cond_rows(args.cond_len, blockIdx.z, Lself, Lcond);  // this sample's own conditioning keys; Lcond is the slot pitch
-    const int n_kw = args.n_kw;
     const float scale = args.scale;
-    const float* const key_weights = args.key_weights;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -264,6 +275,8 @@ __global__ __launch_bounds__(256) void attention_lds_kernel(AttnArgs args) {
     const int r16 = lane & 15, kq = lane >> 4;
     const int Lk = Lself + ncond;
     const int ntiles = (Lk + KTILE - 1) / KTILE;
+    int n_kw = args.n_kw;
+    const float* const key_weights = attn_key_weights(args.key_weights, args.kw_table, args.kw_len, args.kw_pitch, b, Lk, n_kw);
 
     f32x4 qf[DT];
     {
@@ -498,9 +511,7 @@ __global__ __launch_bounds__(256) void attention_bf16_kernel(AttnArgs args) {
 
     const int Lq = args.Lq, Lself = args.Lself, Lcond = args.Lcond, ld16 = args.ld16, ld_cond = args.ld_cond, ldo = args.ldo;
     const int ncond = attn_cond_rows(args.cond_len, blockIdx.z, Lself, Lcond);  // this sample's own conditioning keys; Lcond is the slot pitch
-    const int n_kw = args.n_kw;
     const float scale = args.scale;
-    const float* const key_weights = args.key_weights;
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -509,6 +520,8 @@ __global__ __launch_bounds__(256) void attention_bf16_kernel(AttnArgs args) {
     const int r16 = lane & 15, kq = lane >> 4;
     const int Lk = Lself + ncond;
     const int ntiles = (Lk + KTILE - 1) / KTILE;
+    int n_kw = args.n_kw;
+    const float* const key_weights = attn_key_weights(args.key_weights, args.kw_table, args.kw_len, args.kw_pitch, b, Lk, n_kw);
 
     s16x4 qf[DT];  // Q[q0 + r16][16 j + 4 kq .. + 3]
     {
@@ -650,6 +663,10 @@ int launch_attention(const AttnArgs& a, hipStream_t st) {
         return PAELLA_ERR_ARG;
     }
     if (a.key_weights && (a.n_kw > a.Lself + a.Lcond || a.n_kw < 1)) { paella_set_error("attention: attn_weights longer than the key sequence"); return PAELLA_ERR_ARG; }
+    if (a.kw_len && (a.key_weights || !a.kw_table || a.kw_pitch < 1)) {
+        paella_set_error("attention: the per-sample key-weight table needs kw_table, kw_len and kw_pitch >= 1, and excludes the shared key_weights vector");
+        return PAELLA_ERR_ARG;
+    }
     if (a.q16) {  // opt-in bf16 fast mode (the model only asks for it at >= 256 queries)
         if (!a.out16 || (a.Lself && (!a.k_self16 || !a.v_self16)) || (a.ld16 & 7) || (a.Lcond && (a.ld_cond & 3)) || (a.ldo & 3) || a.D % 16) {
             paella_set_error("attention (bf16): needs out16, bf16 self K / V, ld16 %% 8 == 0");

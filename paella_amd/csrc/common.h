@@ -279,6 +279,12 @@ struct AttnArgs {
     // ragged conditioning: optional DEVICE table [B], sample b attends the first clamp(cond_len[b], 0, Lcond) rows of its slot and never reads the rest; Lcond is
     // then the slot pitch only.  null = every sample has Lcond conditioning keys.  key_weights weigh the last n_kw keys of each sample's OWN key sequence
     const int* cond_len;
+    // per-sample key weights (instead of key_weights / n_kw; giving both is an error): DEVICE tables kw_table fp32 [B, kw_pitch], row b = sample b's multipliers at
+    // its front, and kw_len int32 [B].  Sample b weighs the last n = clamp(kw_len[b], 0, min(its own key count, kw_pitch)) keys of its OWN key sequence with row b's first n
+    // entries and never reads the rest of the row; n == 0 = the sample is unweighted (no read at all).  kw_len == null: the shared vector above, kw_table unused
+    const float* kw_table = nullptr;
+    const int* kw_len = nullptr;
+    int kw_pitch = 0;
 };
 int launch_attention(const AttnArgs& a, hipStream_t stream);
 

@@ -732,6 +732,9 @@ struct FwdCtx {
     const float* attn_w;
     int n_aw;
     const int* cond_len;  // ragged conditioning: device table [B] of conditioning rows per sample (S = slot pitch), or null
+    const float* kw_table;  // per-slot key weights (AttnArgs::kw_table / kw_len / kw_pitch) instead of attn_w, or null
+    const int* kw_len;
+    int kw_pitch;
 };
 
 // ResBlock / FeedForwardBlock (reference src/modules.py:43-62, 82-96); x is updated in place
@@ -863,6 +866,7 @@ static int run_attn_block(FwdCtx& cx, const Block& b, float* x, int h, int w) {
     a.out16 = wo16 ? cx.f.h16 : nullptr;
     a.q16 = nullptr; a.k_self16 = nullptr; a.v_self16 = nullptr; a.ld16 = 0;
     a.cond_len = cx.cond_len;
+    a.kw_table = cx.kw_table; a.kw_len = cx.kw_len; a.kw_pitch = cx.kw_pitch;
     if (attn16) {
         a.q16 = cx.f.g16; a.ld16 = nq;
         a.k_self16 = self ? cx.f.g16 + ch : nullptr; a.v_self16 = self ? cx.f.g16 + 2 * ch : nullptr;
@@ -894,11 +898,24 @@ extern "C" int paella_unet_forward(paella_unet* m, const int64_t* tokens, const 
 // mix_c * LN(z_cond) + mix_u * LN(z_uncond) and logits_out receives the n_unique MIXED rows (half the head FLOPs and logits bytes).
 // `tail` != nullptr: the head GEMM runs with the fused sampling-tail epilogue (no logits are stored; tail->tokens_out receives
 // the sampled tokens of the B (or, with the guidance mix, n_unique) output rows); logits_out is then unused.
+// Per-request prompt weights: one row of post-softmax key multipliers per conditioning SLOT of the launch (B rows: a guided step's two halves carry independent
+// rows) instead of the one attn_weights vector.  len == nullptr = no table.
+struct KwTable {
+    const float* table;  // DEVICE fp32 [B, pitch]
+    const int* len;      // DEVICE int32 [B]
+    int pitch;
+};
+static int kw_table_check(const char* who, const float* kw_table, const int* kw_len, int kw_pitch) {
+    if (kw_len && (!kw_table || kw_pitch < 1)) { paella_set_error("%s: kw_len needs kw_table and kw_pitch >= 1", who); return PAELLA_ERR_ARG; }
+    return PAELLA_OK;
+}
+
 static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                              float mix_c, float mix_u, int H, int W, int S, const float* attn_weights,
                              int n_attn_weights, float* logits_out, const TailArgs* tail, void* ws, size_t ws_bytes, void* stream,
                              const float* mix_pairs = nullptr,    // request batch: a DEVICE table [n_unique, 2] of guidance pairs instead of (mix_c, mix_u)
-                             const int* cond_len = nullptr) {     // ragged conditioning: a DEVICE table [B] of conditioning rows per sample, S is then the slot pitch of `cond`
+                             const int* cond_len = nullptr,       // ragged conditioning: a DEVICE table [B] of conditioning rows per sample, S is then the slot pitch of `cond`
+                             KwTable kw = {nullptr, nullptr, 0}) {  // per-request prompt weights instead of attn_weights (which must then be null)
     if (!m || !m->finalized) { paella_set_error("model not finalized"); return PAELLA_ERR_STATE; }
     if (!tokens || !r || (!logits_out && !tail)) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
     const paella_unet_config& c = m->cfg;
@@ -912,6 +929,7 @@ static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float*
     FwdCtx cx;
     cx.m = m; cx.st = (hipStream_t)stream; cx.B = B; cx.H = H; cx.W = W; cx.S = S;
     cx.cond = (const float*)cond; cx.attn_w = attn_weights; cx.n_aw = attn_weights ? n_attn_weights : 0; cx.cond_len = cond_len;
+    cx.kw_table = kw.len ? kw.table : nullptr; cx.kw_len = kw.len; cx.kw_pitch = kw.len ? kw.pitch : 0;
     Arena a(ws, ws_bytes);
     carve_forward(m, a, B, H, W, S, cx.f);
     if (!a.ok || !ws) { paella_set_error("workspace too small (%zu needed, %zu given)", a.off, ws_bytes); return PAELLA_ERR_WORKSPACE; }
@@ -1148,6 +1166,16 @@ extern "C" int paella_unet_forward_shared_req_ragged(paella_unet* m, const int64
     return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, logits_out, nullptr, ws, ws_bytes, stream, mix_pairs,
                              cond_len);
 }
+// Per-request prompt weights: the logits entry point of the family with the key-weight table in place of (attn_weights, n_attn_weights); mix_pairs may be NULL here
+// (no guidance mix: the B rows of logits, n_unique dividing B as in paella_unet_forward_shared).  kw_len == NULL: the entry point above (or the unmixed forward).
+extern "C" int paella_unet_forward_shared_req_kw(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                 const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table, const int* kw_len,
+                                                 int kw_pitch, float* logits_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!logits_out) { paella_set_error("forward_shared_req_kw: null argument (logits_out)"); return PAELLA_ERR_ARG; }
+    RET_IF(kw_table_check("forward_shared_req_kw", kw_table, kw_len, kw_pitch));
+    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, nullptr, 0, logits_out, nullptr, ws, ws_bytes, stream, mix_pairs, cond_len,
+                             KwTable{kw_table, kw_len, kw_pitch});
+}
 extern "C" int paella_unet_forward_shared_req(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                               const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
                                               float* logits_out, void* ws, size_t ws_bytes, void* stream) {
@@ -1155,11 +1183,13 @@ extern "C" int paella_unet_forward_shared_req(paella_unet* m, const int64_t* tok
                                                  stream);
 }
 
-extern "C" int paella_unet_forward_sample_req_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
-                                                     const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights,
-                                                     const uint64_t* seeds, const float* temperature, int rows_per_sample, uint64_t offset,
-                                                     const int64_t* init_noise, float t_next, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+// the request form of the fused step; the pin tables (all nullable) and the key-weight table are what the _kw entry point adds
+static int forward_sample_req_impl(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique, const float* mix_pairs, int H, int W,
+                                   int S, const int* cond_len, const float* attn_weights, int n_attn_weights, KwTable kw, const uint64_t* seeds,
+                                   const float* temperature, int rows_per_sample, uint64_t offset, const int64_t* init_noise, float t_next, const int64_t* pin_keep,
+                                   const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
     if (!tokens_out || !seeds || !temperature) { paella_set_error("forward_sample_req: null argument (tokens_out / seeds / temperature)"); return PAELLA_ERR_ARG; }
+    RET_IF(pin_tables_check("forward_sample_req", pin_keep, pin_tokens, pin_on, 0));
     if (!mix_pairs && n_unique != B) { paella_set_error("forward_sample_req without guidance pairs needs n_unique == B"); return PAELLA_ERR_ARG; }
     if (H <= 0 || W <= 0 || rows_per_sample != H * W) { paella_set_error("forward_sample_req: rows_per_sample (%d) must equal H * W", rows_per_sample); return PAELLA_ERR_ARG; }
     TailArgs a = {};
@@ -1167,7 +1197,25 @@ extern "C" int paella_unet_forward_sample_req_ragged(paella_unet* m, const int64
     a.L = m ? m->cfg.num_labels : 0;
     a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f; a.offset = offset; a.init_noise = init_noise; a.t_next = t_next; a.tokens_out = tokens_out;
     a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.rows_per_sample = rows_per_sample;  // (the guidance pairs ride through the head: none left for the tail)
-    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, mix_pairs, cond_len);
+    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens; a.pin_on = pin_on;
+    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, mix_pairs, cond_len, kw);
+}
+extern "C" int paella_unet_forward_sample_req_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                     const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights,
+                                                     const uint64_t* seeds, const float* temperature, int rows_per_sample, uint64_t offset,
+                                                     const int64_t* init_noise, float t_next, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+    return forward_sample_req_impl(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, attn_weights, n_attn_weights, KwTable{nullptr, nullptr, 0}, seeds,
+                                   temperature, rows_per_sample, offset, init_noise, t_next, nullptr, nullptr, nullptr, tokens_out, ws, ws_bytes, stream);
+}
+// Per-request prompt weights: the key-weight table in place of (attn_weights, n_attn_weights), plus the (nullable) pin tables of the sampling tail.
+extern "C" int paella_unet_forward_sample_req_kw(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                 const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table, const int* kw_len,
+                                                 int kw_pitch, const uint64_t* seeds, const float* temperature, int rows_per_sample, uint64_t offset,
+                                                 const int64_t* init_noise, float t_next, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
+                                                 int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+    RET_IF(kw_table_check("forward_sample_req_kw", kw_table, kw_len, kw_pitch));
+    return forward_sample_req_impl(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, nullptr, 0, KwTable{kw_table, kw_len, kw_pitch}, seeds, temperature,
+                                   rows_per_sample, offset, init_noise, t_next, pin_keep, pin_tokens, pin_on, tokens_out, ws, ws_bytes, stream);
 }
 extern "C" int paella_unet_forward_sample_req(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                               const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
@@ -1198,11 +1246,11 @@ static int stream_tables_check(const char* who, const int* step, const float* t_
     return PAELLA_OK;
 }
 
-extern "C" int paella_unet_forward_sample_stream_pin(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
-                                                     const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights,
-                                                     int n_attn_weights, const uint64_t* seeds, const float* temperature, int rows_per_sample, const int* step,
-                                                     const float* t_next, const int* active, const int64_t* init_noise, const int64_t* pin_keep,
-                                                     const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+static int forward_sample_stream_impl(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique, const float* mix_pairs, int H,
+                                      int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights, KwTable kw, const uint64_t* seeds,
+                                      const float* temperature, int rows_per_sample, const int* step, const float* t_next, const int* active,
+                                      const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, void* ws,
+                                      size_t ws_bytes, void* stream) {
     if (!tokens_out || !seeds || !temperature) { paella_set_error("forward_sample_stream: null argument (tokens_out / seeds / temperature)"); return PAELLA_ERR_ARG; }
     RET_IF(stream_tables_check("forward_sample_stream", step, t_next, active, init_noise));
     RET_IF(pin_tables_check("forward_sample_stream", pin_keep, pin_tokens, pin_on, 0));
@@ -1215,7 +1263,25 @@ extern "C" int paella_unet_forward_sample_stream_pin(paella_unet* m, const int64
     a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.rows_per_sample = rows_per_sample;
     a.rq.step = step; a.rq.t_next = t_next; a.rq.active = active;
     a.pin_keep = pin_keep; a.pin_tokens = pin_tokens; a.pin_on = pin_on;
-    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, mix_pairs, cond_len);
+    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, mix_pairs, cond_len, kw);
+}
+extern "C" int paella_unet_forward_sample_stream_pin(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                     const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights,
+                                                     int n_attn_weights, const uint64_t* seeds, const float* temperature, int rows_per_sample, const int* step,
+                                                     const float* t_next, const int* active, const int64_t* init_noise, const int64_t* pin_keep,
+                                                     const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+    return forward_sample_stream_impl(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, attn_weights, n_attn_weights, KwTable{nullptr, nullptr, 0}, seeds,
+                                      temperature, rows_per_sample, step, t_next, active, init_noise, pin_keep, pin_tokens, pin_on, tokens_out, ws, ws_bytes, stream);
+}
+// Per-request prompt weights: the tick of a stream whose slots carry their own key weights -- the key-weight table in place of (attn_weights, n_attn_weights).
+extern "C" int paella_unet_forward_sample_stream_kw(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                    const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table, const int* kw_len,
+                                                    int kw_pitch, const uint64_t* seeds, const float* temperature, int rows_per_sample, const int* step,
+                                                    const float* t_next, const int* active, const int64_t* init_noise, const int64_t* pin_keep,
+                                                    const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+    RET_IF(kw_table_check("forward_sample_stream_kw", kw_table, kw_len, kw_pitch));
+    return forward_sample_stream_impl(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, nullptr, 0, KwTable{kw_table, kw_len, kw_pitch}, seeds, temperature,
+                                      rows_per_sample, step, t_next, active, init_noise, pin_keep, pin_tokens, pin_on, tokens_out, ws, ws_bytes, stream);
 }
 extern "C" int paella_unet_forward_sample_stream_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                                         const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights,
@@ -1424,16 +1490,26 @@ extern "C" int paella_op_grn_scale(const float* g, const float* gamma, float* sc
                                    void* stream) {
     return launch_grn_scale(g, gamma, scale, tmp, B, rows_per_sample, C, (hipStream_t)stream);
 }
-extern "C" int paella_op_attention_ragged(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond,
-                                          float* out, int B, int nhead, int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* key_weights,
-                                          int n_kw, void* stream) {
+static int op_attention_impl(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond, float* out, int B, int nhead, int D,
+                             int Lq, int Lself, int Lcond, const int* cond_len, const float* key_weights, int n_kw, KwTable kw, void* stream) {
     AttnArgs a;
     const int ld = nhead * D;
     a.q = q; a.ldq = ld; a.k_self = k_self; a.v_self = v_self; a.ld_self = ld; a.k_cond = k_cond; a.v_cond = v_cond; a.ld_cond = ld;
     a.out = out; a.ldo = ld; a.B = B; a.nhead = nhead; a.D = D; a.Lq = Lq; a.Lself = Lself; a.Lcond = Lcond;
     a.scale = 1.0f / sqrtf((float)D); a.key_weights = key_weights; a.n_kw = key_weights ? n_kw : 0; a.out16 = nullptr;
     a.q16 = nullptr; a.k_self16 = nullptr; a.v_self16 = nullptr; a.ld16 = 0; a.cond_len = cond_len;
+    a.kw_table = kw.table; a.kw_len = kw.len; a.kw_pitch = kw.pitch;
     return launch_attention(a, (hipStream_t)stream);
+}
+extern "C" int paella_op_attention_ragged(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond,
+                                          float* out, int B, int nhead, int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* key_weights,
+                                          int n_kw, void* stream) {
+    return op_attention_impl(q, k_self, v_self, k_cond, v_cond, out, B, nhead, D, Lq, Lself, Lcond, cond_len, key_weights, n_kw, KwTable{nullptr, nullptr, 0}, stream);
+}
+// per-sample key weights: the table (kw_table fp32 [B, kw_pitch], kw_len int32 [B]) in place of the shared vector; kw_len == NULL = no weights
+extern "C" int paella_op_attention_kw(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond, float* out, int B, int nhead,
+                                      int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* kw_table, const int* kw_len, int kw_pitch, void* stream) {
+    return op_attention_impl(q, k_self, v_self, k_cond, v_cond, out, B, nhead, D, Lq, Lself, Lcond, cond_len, nullptr, 0, KwTable{kw_table, kw_len, kw_pitch}, stream);
 }
 extern "C" int paella_op_attention(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond,
                                    float* out, int B, int nhead, int D, int Lq, int Lself, int Lcond, const float* key_weights,
@@ -1441,16 +1517,27 @@ extern "C" int paella_op_attention(const float* q, const float* k_self, const fl
     return paella_op_attention_ragged(q, k_self, v_self, k_cond, v_cond, out, B, nhead, D, Lq, Lself, Lcond, nullptr, key_weights, n_kw, stream);
 }
 // test hook (test_hooks.h): the bf16 attention core of the opt-in fast mode on caller-provided operands: q16 / ks16 / vs16 bf16 [B*L, nhead*D], kc / vc fp32, out16 bf16
-extern "C" int paella_test_attention_bf16_ragged(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond,
-                                                 const float* v_cond, unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond,
-                                                 const int* cond_len, const float* key_weights, int n_kw, void* stream) {
+static int test_attention_bf16_impl(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond, const float* v_cond,
+                                    unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* key_weights,
+                                    int n_kw, KwTable kw, void* stream) {
     AttnArgs a;
     const int ld = nhead * D;
     a.q = nullptr; a.ldq = ld; a.k_self = nullptr; a.v_self = nullptr; a.ld_self = ld; a.k_cond = k_cond; a.v_cond = v_cond; a.ld_cond = ld;
     a.out = nullptr; a.ldo = ld; a.B = B; a.nhead = nhead; a.D = D; a.Lq = Lq; a.Lself = Lself; a.Lcond = Lcond;
     a.scale = 1.0f / sqrtf((float)D); a.key_weights = key_weights; a.n_kw = key_weights ? n_kw : 0; a.out16 = out16;
     a.q16 = q16; a.k_self16 = ks16; a.v_self16 = vs16; a.ld16 = ld; a.cond_len = cond_len;
+    a.kw_table = kw.table; a.kw_len = kw.len; a.kw_pitch = kw.pitch;
     return launch_attention(a, (hipStream_t)stream);
+}
+extern "C" int paella_test_attention_bf16_ragged(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond,
+                                                 const float* v_cond, unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond,
+                                                 const int* cond_len, const float* key_weights, int n_kw, void* stream) {
+    return test_attention_bf16_impl(q16, ks16, vs16, k_cond, v_cond, out16, B, nhead, D, Lq, Lself, Lcond, cond_len, key_weights, n_kw, KwTable{nullptr, nullptr, 0}, stream);
+}
+extern "C" int paella_test_attention_bf16_kw(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond, const float* v_cond,
+                                             unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* kw_table,
+                                             const int* kw_len, int kw_pitch, void* stream) {
+    return test_attention_bf16_impl(q16, ks16, vs16, k_cond, v_cond, out16, B, nhead, D, Lq, Lself, Lcond, cond_len, nullptr, 0, KwTable{kw_table, kw_len, kw_pitch}, stream);
 }
 extern "C" int paella_test_attention_bf16(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond, const float* v_cond,
                                           unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond, const float* key_weights, int n_kw, void* stream) {

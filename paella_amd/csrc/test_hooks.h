@@ -24,6 +24,10 @@ int paella_test_attention_bf16(const unsigned short* q16, const unsigned short* 
 int paella_test_attention_bf16_ragged(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond, const float* v_cond,
                                       unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* key_weights,
                                       int n_kw, void* stream);
+/* the same with the per-sample key-weight table of paella_op_attention_kw (kw_table fp32 [B, kw_pitch], kw_len int32 [B]) in place of the shared vector */
+int paella_test_attention_bf16_kw(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond, const float* v_cond,
+                                  unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* kw_table,
+                                  const int* kw_len, int kw_pitch, void* stream);
 /* the fast mode's GlobalResponseNorm apply, in place on a bf16 tensor [rows, C]: h = bf16(h * scale[row / rows_per_sample][c] + shift[c]) (fp32 arithmetic, one rounding) */
 int paella_test_grn_apply16(unsigned short* h, const float* scale, const float* shift, int64_t rows, int rows_per_sample, int C, void* stream);
 /* A/B of the bf16 tile rules: bit 0 = never the 256x128 / 256x256 tiles (the fp32 rules' tiles instead), bit 1 = no persistent ranges of the 256x128 tile,

@@ -79,6 +79,53 @@ class CondCache:
         self.buf, self.B, self.S, self.lens = buf, B, S, lens
 
 
+class KeyWeights:
+    """Per-request prompt weights: one row of post-softmax key multipliers (`attn_weights` of utils/alter_attention.py:23-34) per conditioning SLOT of a launch
+    instead of one vector for all of them -- `buf` fp32 [nb, pitch], row b = slot b's multipliers at its front, and `lens` int32 [nb], how many there are (0 = the
+    slot is unweighted).  nb is the conditioning batch of the forward it is passed to (`cond.B`: 2 * Bx for a guided step, conditional slots first, so the two
+    halves carry independent rows).  Slot b weighs the last lens[b] keys of its OWN key sequence; entries beyond the count are never read.  `Paella.forward_prepared`
+    and `Paella.forward_sample` take a KeyWeights wherever they take a 1-D `attn_weights` tensor.  `set` writes in place, so a captured graph that reads the table
+    serves other weights without a recapture."""
+
+    def __init__(self, nb, pitch, device="cuda"):
+        nb, pitch = int(nb), int(pitch)
+        if nb < 1 or pitch < 1:
+            raise ValueError("KeyWeights needs nb >= 1 slots and pitch >= 1 weights per slot")
+        self.buf = torch.zeros(nb, pitch, dtype=torch.float32, device=device)
+        self.lens = torch.zeros(nb, dtype=torch.int32, device=device)
+
+    @property
+    def nb(self):
+        return self.buf.size(0)
+
+    @property
+    def pitch(self):
+        return self.buf.size(1)
+
+    def set(self, slot, weights):
+        """slot's weights: None (or an empty vector) = unweighted, else a 1-D tensor / sequence of at most `pitch` multipliers.  In place, stream-ordered."""
+        slot = int(slot)
+        if not 0 <= slot < self.nb:
+            raise IndexError("KeyWeights: slot %d outside 0 ... %d" % (slot, self.nb - 1))
+        n = 0
+        if weights is not None:
+            w = torch.as_tensor(weights).detach().to(torch.float32)
+            if w.dim() != 1:
+                raise ValueError("attn_weights must be 1-D (utils/alter_attention.py:27)")
+            n = w.numel()
+            if n > self.pitch:
+                raise ValueError("attn_weights has %d entries, the table holds at most %d per slot" % (n, self.pitch))
+            if n:
+                self.buf[slot, :n].copy_(w)
+        self.lens[slot].fill_(n)
+        return self
+
+    def clear(self):
+        """every slot unweighted"""
+        self.lens.zero_()
+        return self
+
+
 class Paella(nn.Module):
     """Drop-in for reference `Paella` (src/modules.py:109). Same constructor arguments and defaults."""
 
@@ -320,6 +367,18 @@ class Paella(nn.Module):
         if not torch.is_tensor(t) or t.device != self._device() or t.dtype != dtype or tuple(t.shape) != tuple(shape) or not t.is_contiguous():
             raise ValueError("%s must be a contiguous %s tensor of shape %s on the model's device" % (name, dtype, tuple(shape)))
 
+    def _key_weights(self, attn_weights, nb, one_d=True):
+        """`attn_weights` of a forward over `nb` conditioning slots -> (fp32 tensor or None, KeyWeights or None), checked; one_d=False takes a plain tensor of
+        any shape as its numel() weights (what forward_sample has always done)"""
+        if isinstance(attn_weights, KeyWeights):
+            self._check_table(attn_weights.buf, (nb, attn_weights.pitch), torch.float32, "attn_weights (KeyWeights.buf: one row per conditioning slot)")
+            self._check_table(attn_weights.lens, (nb,), torch.int32, "attn_weights (KeyWeights.lens: one count per conditioning slot)")
+            return None, attn_weights
+        aw = self._f32(attn_weights, "attn_weights")
+        if one_d and aw is not None and aw.dim() != 1:
+            raise ValueError("attn_weights must be 1-D (utils/alter_attention.py:27)")
+        return aw, None
+
     @staticmethod
     def _f32(t, name):
         if t is None:
@@ -438,7 +497,9 @@ class Paella(nn.Module):
         (src/utils.py:47) through the bias-free linear head and returns only those Bx mixed rows.
         Returns logits with the reference's shape [B, num_labels, H, W] (a channels-last view of the
         position-major buffer the kernels write; pass `out` = a [B,H,W,num_labels] fp32 tensor to reuse memory).
-        req_mix (request batch, instead of cfg_mix): an fp32 DEVICE tensor [Bx, 2] with one guidance pair per sample."""
+        req_mix (request batch, instead of cfg_mix): an fp32 DEVICE tensor [Bx, 2] with one guidance pair per sample.
+        attn_weights: a 1-D tensor (one vector for every sample) or a `KeyWeights` table with one row per conditioning slot (cond.B of them); with the table a
+        cfg_mix is uploaded as a [Bx, 2] pair table (a host-to-device copy, refused with a ValueError during a graph capture: capture such a step with req_mix)."""
         h = self._engine()
         lib = _lib.load()
         dev = self._device()
@@ -452,9 +513,7 @@ class Paella(nn.Module):
         B = cond.B
         if nu <= 0 or B % nu:
             raise ValueError("conditioning batch %d is not a multiple of the token batch %d" % (B, nu))
-        aw = self._f32(attn_weights, "attn_weights")
-        if aw is not None and aw.dim() != 1:
-            raise ValueError("attn_weights must be 1-D (utils/alter_attention.py:27)")
+        aw, kw = self._key_weights(attn_weights, B)
         mix = (0.0, 0.0) if cfg_mix is None else (float(cfg_mix[0]), float(cfg_mix[1]))
         if cfg_mix is not None and (B != 2 * nu or mix == (0.0, 0.0)):
             raise ValueError("cfg_mix needs a conditioning batch of twice the token batch and a non-zero mix")
@@ -470,6 +529,15 @@ class Paella(nn.Module):
         lens = self._cond_lens(cond)
         with torch.cuda.device(dev):
             ws = self._workspace(lib.paella_unet_workspace_bytes(h, B, H, W, cond.S), ws)
+            if kw is not None:  # per-request prompt weights: the one logits entry point that takes the table (`lens` and the pair table nullable)
+                if cfg_mix is not None and torch.cuda.is_current_stream_capturing():
+                    raise ValueError("forward_prepared with a KeyWeights table turns cfg_mix into a pair table by a host-to-device copy, which a graph capture "
+                                     "cannot hold: pass req_mix (an fp32 device tensor [Bx, 2]) instead of cfg_mix inside a capture")
+                pairs = req_mix if cfg_mix is None else torch.tensor([mix] * nu, dtype=torch.float32).to(dev)
+                _lib.check(lib.paella_unet_forward_shared_req_kw(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S, _lib.ptr(lens),
+                                                                 _lib.ptr(kw.buf), _lib.ptr(kw.lens), kw.pitch, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                                                 _lib.stream_ptr(dev)))
+                return out
             if lens is not None:  # ragged conditioning: the twins with the per-sample row counts (cond.S is the slot pitch)
                 if req_mix is not None:
                     _lib.check(lib.paella_unet_forward_shared_req_ragged(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(req_mix), H, W, cond.S,
@@ -504,7 +572,8 @@ class Paella(nn.Module):
         stored for the sample, `out` keeps its rows) -- every request of the batch is at its own step; `out` may be `x` (the stream runs in place).
         pin=(keep, known) (scalar form) or pin=(keep, known, pin_on) (with `stream`): editing requests -- int64 [Bx,H,W] DEVICE grids, keep 1 = regenerate / 0 = known;
         after the draw and the renoise the tail stores known wherever keep == 0, with `stream` only for the samples whose int32 [Bx] flag pin_on is set.  Categorical
-        mode only; not offered with `req` alone.  Without `pin` the call reaches exactly the entry points it reaches without this argument."""
+        mode only; not offered with `req` alone.  Without `pin` the call reaches exactly the entry points it reaches without this argument.
+        attn_weights: a 1-D tensor, or (with `req`) a `KeyWeights` table with one row per conditioning slot (cond.B of them)."""
         h = self._engine()
         lib = _lib.load()
         dev = self._device()
@@ -543,10 +612,26 @@ class Paella(nn.Module):
             self._check_table(pin[1], (nu, H, W), torch.int64, "pin known")
             if stream is not None:
                 self._check_table(pin[2], (nu,), torch.int32, "pin pin_on")
-        aw = self._f32(attn_weights, "attn_weights")
+        aw, kw = self._key_weights(attn_weights, B, one_d=False)
+        if kw is not None and req is None:
+            raise ValueError("forward_sample takes a KeyWeights table for attn_weights only with the request tables (req=...); the scalar form takes one 1-D vector")
         lens = self._cond_lens(cond)
         with torch.cuda.device(dev):
             ws = self._workspace(lib.paella_unet_workspace_bytes(h, B, H, W, cond.S), ws)
+            if kw is not None:  # per-request prompt weights: one entry point per form, `lens` (ragged conditioning) and the pin tables nullable
+                pk, pt, po = (None, None, None) if pin is None else pin
+                if stream is not None:
+                    _lib.check(lib.paella_unet_forward_sample_stream_kw(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S,
+                                                                        _lib.ptr(lens), _lib.ptr(kw.buf), _lib.ptr(kw.lens), kw.pitch, _lib.ptr(seeds), _lib.ptr(temps),
+                                                                        H * W, _lib.ptr(stream[0]), _lib.ptr(stream[1]), _lib.ptr(stream[2]), _lib.ptr(init_noise),
+                                                                        _lib.ptr(pk), _lib.ptr(pt), _lib.ptr(po), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
+                                                                        _lib.stream_ptr(dev)))
+                else:
+                    _lib.check(lib.paella_unet_forward_sample_req_kw(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S,
+                                                                     _lib.ptr(lens), _lib.ptr(kw.buf), _lib.ptr(kw.lens), kw.pitch, _lib.ptr(seeds), _lib.ptr(temps),
+                                                                     H * W, int(offset), _lib.ptr(init_noise), float(t_next), None, None, None, _lib.ptr(out),
+                                                                     _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+                return out
             if pin is not None:  # editing requests: one entry point per form, `lens` (ragged conditioning) nullable
                 naw = 0 if aw is None else aw.numel()
                 if stream is not None:

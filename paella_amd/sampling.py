@@ -20,7 +20,7 @@ Extension (not reference behaviour): a step temperature of 0 selects 
 import torch
 
 from . import _lib
-from .modules import CondCache, Paella
+from .modules import CondCache, KeyWeights, Paella
 
 
 def linspace_schedule(start, end, n):
@@ -246,6 +246,76 @@ class RequestTables:
     def step(self, i):
         """what forward_sample(req=...) takes at step i"""
         return (self.seeds, self.temps[i], None if self.pairs is None else self.pairs[i])
+
+
+def _weights_vector(v):
+    if v is None:
+        return None
+    if not torch.is_tensor(v) or v.dim() != 1:
+        raise ValueError("attn_weights: every vector must be a 1-D tensor (utils/alter_attention.py:27), got %r" % (type(v).__name__ if not torch.is_tensor(v) else tuple(v.shape),))
+    return v.detach().to(torch.float32)
+
+
+def request_weight_pair(entry):
+    """one request's `attn_weights` -> (conditional, unconditional), each a 1-D fp32 tensor or None: None = unweighted; a vector weighs both sides (what the one
+    vector of a whole call does); a pair (conditional, unconditional), either member None, weighs each side of the guided step on its own -- "my image rows times
+    2" addresses the conditional side only, whose last rows they are."""
+    if entry is None or torch.is_tensor(entry):
+        v = _weights_vector(entry)
+        return v, v
+    if isinstance(entry, (tuple, list)) and len(entry) == 2 and all(m is None or torch.is_tensor(m) for m in entry):
+        return _weights_vector(entry[0]), _weights_vector(entry[1])
+    raise ValueError("attn_weights: a request's entry must be None, a 1-D tensor or a pair (conditional, unconditional) of those, got %r" % (type(entry).__name__,))
+
+
+def split_request_weights(attn_weights, B):
+    """the `attn_weights` argument of a request batch -> (shared, pairs): a 1-D tensor (or None) is ONE vector for all requests, returned as `shared` -- the
+    path and the bits of a call without per-request weights; a list with one entry per request (`request_weight_pair`) comes back as `pairs`, B (conditional,
+    unconditional) pairs.  Exactly one of the two is not None, or both are for attn_weights=None."""
+    if attn_weights is None or torch.is_tensor(attn_weights):
+        if attn_weights is not None and attn_weights.dim() != 1:
+            raise ValueError("attn_weights must be 1-D (utils/alter_attention.py:27)")
+        return attn_weights, None
+    if not isinstance(attn_weights, list) or len(attn_weights) != int(B):
+        raise ValueError("attn_weights must be None, one 1-D tensor for all requests or a LIST with one entry per request (%d), got %s" %
+                         (int(B), "a list of %d" % len(attn_weights) if isinstance(attn_weights, list) else type(attn_weights).__name__))
+    return None, [request_weight_pair(e) for e in attn_weights]
+
+
+def check_weight_pair(pair, keys, guided, max_n=None, what="attn_weights"):
+    """host validation of one request's (conditional, unconditional) weights: each vector at most `max_n` long (the table's row, None = no limit) and at most
+    as long as that side's own key sequence, keys = (conditional, unconditional) from `min_attention_keys` (None = the model has no attention) -- a longer one
+    would be clamped by the kernels, which shifts what every entry means.  An unguided request has no unconditional side."""
+    c, u = pair
+    if not guided:
+        if u is not None and u is not c:
+            raise ValueError("%s: an unguided request has no unconditional side to weigh (pass one vector, or (conditional, None))" % what)
+        u = None
+    for v, k, side in ((c, keys[0], "conditional"), (u, keys[1], "unconditional")):
+        if v is None:
+            continue
+        if max_n is not None and v.numel() > max_n:
+            raise ValueError("%s: %d %s weights, the table holds at most %d per slot (max_attn_weights)" % (what, v.numel(), side, max_n))
+        if k is not None and v.numel() > k:
+            raise ValueError("%s: %d %s weights, more than the %d keys of that side's shortest key sequence" % (what, v.numel(), side, k))
+    return c, u
+
+
+def _load_key_weights(kw, pairs, keys, guided, max_n=None):
+    """validate every request's pair, then write the table in place: conditional rows in slots [0, B), unconditional ones in [B, 2B)"""
+    B = len(pairs)
+    pairs = [check_weight_pair(p, keys, guided, max_n, "attn_weights[%d]" % b) for b, p in enumerate(pairs)]
+    for b, (c, u) in enumerate(pairs):
+        kw.set(b, c)
+        if guided:
+            kw.set(B + b, u)
+    return kw
+
+
+def _request_keys(model, H, W, model_inputs, unconditional_inputs):
+    """(conditional, unconditional) shortest key sequence of a request with these conditioning sets"""
+    return (min_attention_keys(model._cfg, H, W, _cond_seq_len(model, model_inputs)),
+            min_attention_keys(model._cfg, H, W, _cond_seq_len(model, unconditional_inputs)) if unconditional_inputs is not None else None)
 
 
 def timestep_table(t_list, steps, B, device):
@@ -477,7 +547,11 @@ def sample_requests(model, model_inputs, unconditional_inputs, latent_shape, see
     tokens are a function of the request alone -- every random number it draws is the one `sample(..., latent_shape=(1, H, W), noise="philox", seed=seeds[b])`
     draws, whatever slot it sits in and whoever shares the batch (the logits may still differ in their last bits with the batch size: the GEMMs split their
     work by tile index).  `cfg` / `temperature`: one value for all requests or one per request, see `request_tables`.  `steps`, `renoise_steps`, `t_start` /
-    `t_end`, the grid and the conditioning layout are common to the batch.  Two requests with equal seeds draw identical noise.  Returns tokens [B, H, W]."""
+    `t_end`, the grid and the conditioning layout are common to the batch.  Two requests with equal seeds draw identical noise.  Returns tokens [B, H, W].
+    attn_weights: one 1-D tensor for all requests (one vector per launch, as `sample`), or a LIST with one entry per request -- None, a vector (both sides of
+    the guided step) or a pair (conditional, unconditional), either member None (`request_weight_pair`).  The list form runs on a `KeyWeights` table with one row
+    per conditioning slot: request b's tokens are those of a call in which every request carries request b's weights, bit for bit, whatever its batch-mates
+    carry.  A guided list call needs the one-forward path (both conditioning sets with B samples each)."""
     B, H, W = (int(v) for v in latent_shape)
     host = request_tables(B, steps, seeds, cfg, temperature)
     if host[2] is not None and unconditional_inputs is None:
@@ -486,6 +560,17 @@ def sample_requests(model, model_inputs, unconditional_inputs, latent_shape, see
     if device.type != "cuda":
         raise RuntimeError("paella_amd.sample_requests runs on a HIP device only (got device=%s); there is no CPU path" % device)
     t_list, temps, cfgs = _request_schedule(steps, t_start, t_end, host[2] is not None)
+    attn_weights, pairs = split_request_weights(attn_weights, B)
+    if pairs is not None:
+        guided = host[2] is not None
+        if guided and not (_cond_batch(model_inputs) == B and _cond_batch(unconditional_inputs) == B
+                           and min(_cond_seq_len(model, model_inputs), _cond_seq_len(model, unconditional_inputs)) > 0):
+            raise ValueError("attn_weights per request in a guided batch run as ONE forward over 2B conditioning slots (one table row each): model_inputs and "
+                             "unconditional_inputs must each hold %d samples with at least one conditioning row (got %r and %r samples)"
+                             % (B, _cond_batch(model_inputs), _cond_batch(unconditional_inputs)))
+        n_max = max([1] + [v.numel() for p in pairs for v in p if v is not None])
+        attn_weights = _load_key_weights(KeyWeights(2 * B if guided else B, n_max, device), pairs,
+                                         _request_keys(model, H, W, model_inputs, unconditional_inputs if guided else None), guided)
     return _sample_core(model, model_inputs, unconditional_inputs, (B, H, W), None, steps, renoise_steps, t_list, temps, cfgs, device, noise="philox", seed=0,
                         attn_weights=attn_weights, fused_tail=fused_tail, req=RequestTables(host, device))
 
@@ -653,13 +738,23 @@ class GraphRequestSampler(GraphSampler):
     pairs and temperatures live in device tables the kernels read, so a replay with other values rewrites the tables and never recaptures (`captures`
     stays 1); GraphSampler's staleness check (weights, precision) applies unchanged.  `cfg` / `temperature` given here are the defaults of a call that
     passes none, and `cfg=None` captures an unguided batch (guidance cannot be switched per replay: it decides the launch sequence).  Replays equal the
-    eager `sample_requests` bit for bit."""
+    eager `sample_requests` bit for bit.
+    max_attn_weights=N (mutually exclusive with `attn_weights`, the one vector baked into the capture): the graph reads a `KeyWeights` table of N weights per
+    conditioning slot, and `__call__(attn_weights=...)` rewrites it in place -- None (nobody weighted), one vector for all requests or a list with one entry
+    per request, as `sample_requests`; `captures` stays 1."""
 
     def __init__(self, model, model_inputs, unconditional_inputs, latent_shape, steps=12, renoise_steps=11, temperature=(1.0, 0.2), cfg=8.0, t_start=1.0,
-                 t_end=0.0, device="cuda", vqgan=None, attn_weights=None, on_stale="recapture"):
+                 t_end=0.0, device="cuda", vqgan=None, attn_weights=None, on_stale="recapture", max_attn_weights=None):
         B = int(latent_shape[0])
+        if max_attn_weights is not None:  # (validated before anything touches a device)
+            if attn_weights is not None:
+                raise ValueError("max_attn_weights (a per-request table) and attn_weights (one vector for the life of the capture) are mutually exclusive")
+            check_max_attn_weights(max_attn_weights)
         self.req_defaults = dict(cfg=cfg, temperature=temperature)
         self.req = RequestTables(request_tables(B, steps, [0] * B, cfg, temperature), torch.device(device))
+        self.key_weights = None
+        if max_attn_weights is not None:
+            attn_weights = self.key_weights = KeyWeights(2 * B if self.req.pairs is not None else B, max_attn_weights, device)
         super().__init__(model, model_inputs, unconditional_inputs, latent_shape, steps=steps, renoise_steps=renoise_steps, temperature=temperature, cfg=cfg,
                          t_start=t_start, t_end=t_end, device=device, vqgan=vqgan, attn_weights=attn_weights, on_stale=on_stale)
 
@@ -670,11 +765,21 @@ class GraphRequestSampler(GraphSampler):
                             noise="philox", seed=0, attn_weights=self.attn_weights, init_noise_buf=self.init_noise, r_all=self.r_all, ws=self.ws, req=self.req)
         return toks if self.vqgan is None else (toks, self.vqgan.decode_indices(toks, ws=self.vq_ws))
 
-    def __call__(self, seeds, cfg=None, temperature=None, model_inputs=None, unconditional_inputs=None):
+    def __call__(self, seeds, cfg=None, temperature=None, model_inputs=None, unconditional_inputs=None, attn_weights=None):
         """Replay for the requests `seeds[b]` (cfg / temperature: as `sample_requests`; None = the constructor's).  Outputs live in graph-owned buffers that the
-        next replay overwrites."""
-        host = request_tables(self.shape[0], self.kw["steps"], seeds, self.req_defaults["cfg"] if cfg is None else cfg,
+        next replay overwrites.  attn_weights (a sampler built with max_attn_weights only): this replay's prompt weights, as `sample_requests` takes them; None =
+        nobody is weighted."""
+        B, H, W = self.shape
+        host = request_tables(B, self.kw["steps"], seeds, self.req_defaults["cfg"] if cfg is None else cfg,
                               self.req_defaults["temperature"] if temperature is None else temperature)
+        if self.key_weights is None:
+            if attn_weights is not None:
+                raise ValueError("attn_weights per replay needs a sampler built with max_attn_weights=N (this one baked the constructor's attn_weights into its capture)")
+        else:
+            shared, pairs = split_request_weights(attn_weights, B)
+            guided = self.req.pairs is not None
+            _load_key_weights(self.key_weights, [request_weight_pair(shared)] * B if pairs is None else pairs,
+                              _request_keys(self.model, H, W, self.cond, self.uncond if guided else None), guided, self.key_weights.pitch)
         self._check_fresh()
         if model_inputs is not None:
             self._copy_inputs(self.cond, model_inputs)
@@ -758,6 +863,13 @@ def check_ragged_stream_args(max_cond_rows, n_attn_weights, min_keys):
     return max_cond_rows
 
 
+def check_max_attn_weights(n):
+    """`max_attn_weights=N` of a stream / a captured request sampler: the row length of its key-weight table, a positive integer"""
+    if isinstance(n, bool) or not isinstance(n, int) or n < 1:
+        raise ValueError("max_attn_weights must be None or a positive integer, got %r" % (n,))
+    return n
+
+
 def check_request_rows(rows, max_cond_rows, what):
     """a request's conditioning rows (ByT5 length + clip + any number of clip_image) must be 1 ... max_cond_rows"""
     if not 1 <= rows <= max_cond_rows:
@@ -796,10 +908,18 @@ class RequestStream:
     `paella_amd.inpaint(noise="philox")` does.  Contract: an editing request with pin="final" produces the tokens of `inpaint(..., keep_known=True, noise="philox",
     seed=seed, decode=False)` at batch 1, with pin="step" those of `inpaint(..., pin="step", ...)` (both for a stream of B = 1; the logits of a larger B may differ
     in their last bits, as for every request of a stream); in both cases the tokens at a given slot and B are independent of the batch-mates and of the admission
-    tick, bit for bit.  `captures` stays 1 while text-to-image and editing requests of either policy come and go."""
+    tick, bit for bit.  `captures` stays 1 while text-to-image and editing requests of either policy come and go.
+
+    max_attn_weights=N (per-request prompt weights; mutually exclusive with the stream-wide `attn_weights`, which stays one vector for the life of the stream):
+    the stream owns a `KeyWeights` table -- N weights per conditioning slot, 2B slots when guided, so the two sides of a request carry independent rows -- that
+    the tick reads, and `admit(attn_weights=)` takes None, one vector for both sides or a pair (conditional, unconditional), either member None.  Every admit
+    writes both of its slots' rows, count 0 included: a slot never inherits its predecessor's weights; `reset()` zeroes the counts.  A vector longer than N, or
+    longer than that side's own shortest key sequence, is refused at admission.  Contract: a request admitted with weights `w` produces, at a given slot and B,
+    exactly the tokens of a stream of the same shape built with stream-wide `attn_weights=w` serving that request -- bit for bit, independent of its
+    batch-mates' weights and of the tick it joined at.  With editing and / or max_cond_rows as well it is still one tick, one graph: `captures` stays 1."""
 
     def __init__(self, model, model_inputs, unconditional_inputs, latent_shape, max_steps=12, guided=True, device="cuda", vqgan=None, attn_weights=None,
-                 on_stale="recapture", max_cond_rows=None, editing=False):
+                 on_stale="recapture", max_cond_rows=None, editing=False, max_attn_weights=None):
         if on_stale not in ("recapture", "raise"):
             raise ValueError("on_stale must be 'recapture' or 'raise'")
         if not isinstance(model, Paella):
@@ -810,6 +930,9 @@ class RequestStream:
         self.shape = tuple(int(v) for v in latent_shape)
         B, H, W = self.shape
         self.max_steps, self.guided, self.attn_weights = int(max_steps), bool(guided), attn_weights
+        if max_attn_weights is not None and attn_weights is not None:
+            raise ValueError("max_attn_weights (per-request weights, given to admit) and attn_weights (one vector for the life of the stream) are mutually exclusive")
+        self.max_attn_weights = None if max_attn_weights is None else check_max_attn_weights(max_attn_weights)
         if B <= 0 or self.max_steps <= 0:
             raise ValueError("a request stream needs B > 0 and max_steps > 0")
         if model_inputs is None or (self.guided and unconditional_inputs is None):
@@ -853,6 +976,10 @@ class RequestStream:
             self.known = torch.zeros(self.shape, dtype=torch.int64, device=dev)
             self.pin_policy = torch.zeros(B, dtype=torch.int32, device=dev)      # PIN_POLICY per slot
             self.pin_on = torch.zeros(B, dtype=torch.int32, device=dev)          # this tick's flags, written by the step kernel
+        # per-request prompt weights: one row per conditioning slot, all counts 0 until a request brings weights; the tick reads the table instead of a vector
+        self.key_weights = None if self.max_attn_weights is None else KeyWeights(nb, self.max_attn_weights, dev)
+        if self.key_weights is not None:
+            self.attn_weights = self.key_weights
         self.captures = 0
         self._capture()
 
@@ -961,8 +1088,20 @@ class RequestStream:
                 raise ValueError("image must be an fp32 tensor [3, %d, %d] in [0, 1]" % (f * H, f * W))
         return known, (mask != 0).to(device=self.device, dtype=torch.int64), image
 
+    def _check_weights(self, attn_weights, model_inputs, unconditional_inputs):
+        """the `attn_weights` of `admit`, validated before anything touches the stream -> (conditional, unconditional) vectors or None each"""
+        if self.key_weights is None:
+            if attn_weights is not None:
+                raise ValueError("attn_weights per request need a stream built with max_attn_weights=N (this one has %s)" %
+                                 ("no prompt weights" if self.attn_weights is None else "one stream-wide attn_weights vector"))
+            return None
+        H, W = self.shape[1:]
+        rows = lambda inputs: _cond_seq_len(self.model, inputs) if self.max_cond_rows is not None else self.S
+        keys = (min_attention_keys(self.model._cfg, H, W, rows(model_inputs)), min_attention_keys(self.model._cfg, H, W, rows(unconditional_inputs)) if self.guided else None)
+        return check_weight_pair(request_weight_pair(attn_weights), keys, self.guided, self.max_attn_weights)
+
     def admit(self, model_inputs, unconditional_inputs=None, seed=None, steps=12, renoise_steps=None, temperature=(1.0, 0.2), cfg=8.0, t_start=1.0, t_end=0.0,
-              init_x=None, known=None, mask=None, image=None, pin="step"):
+              init_x=None, known=None, mask=None, image=None, pin="step", attn_weights=None):
         """Put ONE request into a free slot; it runs from the next tick on.  Inputs: leading dimension 1, the stream's layout.  Schedule arguments as
         `request_program` (an unguided stream takes cfg=None); init_x int64 [H, W]: the tokens the request starts from instead of its seed's start tokens.
         Everything here is eager work on the current stream, ordered before the next tick: the conditioning of the one request is prepared straight into the
@@ -970,13 +1109,16 @@ class RequestStream:
         Editing stream: known int64 [H, W] tokens (or image fp32 [3, f*H, f*W] in [0, 1], encoded here with the stream's VQGAN) and mask [H, W] on the token grid
         (1 = regenerate) make this an editing request -- unless init_x is given it starts from add_noise(known, t_start, mask=mask, random_x=R), R the salted Philox
         start tokens of `seed`; pin="step" re-imposes the known tokens after every step, pin="final" after the request's last step only.  A request without them
-        is a plain one: policy never, keep = ones."""
+        is a plain one: policy never, keep = ones.
+        attn_weights (a stream built with max_attn_weights): this request's prompt weights -- None, one 1-D tensor for both sides, or a pair (conditional,
+        unconditional), either member None; written to the request's two rows of the stream's table (count 0 for an unweighted side)."""
         B, H, W = self.shape
         known, mask, image = self._check_edit(known, mask, image, pin)
         program, n = request_program(steps, renoise_steps, temperature, cfg, t_start, t_end, max_steps=self.max_steps, guided=self.guided)
         self._check_inputs(model_inputs, "model_inputs")
         if self.guided:
             self._check_inputs(unconditional_inputs, "unconditional_inputs")
+        weights = self._check_weights(attn_weights, model_inputs, unconditional_inputs)
         if init_x is not None:
             init_x = init_x.reshape(H, W) if torch.is_tensor(init_x) and init_x.numel() == H * W else init_x
             if not torch.is_tensor(init_x) or tuple(init_x.shape) != (H, W) or init_x.dtype != torch.int64:
@@ -998,6 +1140,10 @@ class RequestStream:
                 self.model.prepare_cond(**{k: inputs.get(k) for k in ("byt5", "clip", "clip_image")}, ws=self.ws, out=self.cache.buf[row * nbytes:(row + 1) * nbytes],
                                         **slot)
             start_tokens(self.model.num_labels, (1, H, W), seed, self.device, out=self.random_x[b:b + 1])
+            if self.key_weights is not None:  # both rows, count 0 included: the slot's previous request leaves nothing behind
+                self.key_weights.set(b, weights[0])
+                if self.guided:
+                    self.key_weights.set(B + b, weights[1])
             if self.editing:
                 if mask is None:
                     self.keep[b].fill_(1)
@@ -1029,6 +1175,8 @@ class RequestStream:
         self.pos.zero_()
         if self.editing:
             self.pin_policy.zero_()
+        if self.key_weights is not None:
+            self.key_weights.clear()
         self._pos, self._len, self._held = [0] * B, [0] * B, [False] * B
 
     def tick(self, graph=True):
