@@ -34,6 +34,24 @@ class VqganConfig(Structure):
     ]
 
 
+class TestGemmArgs(Structure):
+    """paella_amd/csrc/test_hooks.h: paella_test_gemm_args (one fp32 GEMM launch, field by field; tests / tools only)."""
+    _fields_ = [
+        ("A", c_void_p), ("lda", c_int), ("W", c_void_p), ("ldw", c_int), ("C", c_void_p), ("ldc", c_int),
+        ("M", c_int), ("N", c_int), ("K", c_int),
+        ("bias", c_void_p), ("act", c_int), ("alpha", c_float), ("residual", c_void_p), ("ldr", c_int),
+        ("ts", c_void_p), ("ts_stride", c_int), ("rows_per_sample", c_int),
+        ("store_mode", c_int), ("sH", c_int), ("sW", c_int), ("sC", c_int), ("py", c_int), ("px", c_int), ("n_seg_x", c_int),
+        ("rowstat_out", c_void_p), ("sumsq_out", c_void_p),
+        ("remap_in", c_int), ("remap_out", c_int), ("remap_off", c_int),
+        ("c16", c_void_p),
+        ("mode", c_int), ("scale", c_void_p), ("shift", c_void_p), ("a_rows_per_sample", c_int), ("ln_stats", c_void_p),
+        ("cv_enabled", c_int), ("cv_Hi", c_int), ("cv_Wi", c_int), ("cv_C", c_int), ("cv_Ho", c_int), ("cv_Wo", c_int), ("cv_stride", c_int),
+        ("cv_ntaps", c_int), ("cv_tw_log2", c_int), ("cv_oy0", c_int), ("cv_ox0", c_int), ("cv_tsign", c_int),
+        ("c_capacity", c_size_t), ("c16_capacity", c_size_t), ("rowstat_capacity", c_size_t), ("sumsq_capacity", c_size_t),
+    ]
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 SIGNATURES = {
     "paella_abi_version": (c_int, []),
@@ -180,6 +198,8 @@ TEST_HOOKS = {
     "paella_test_tail_scores_req": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_uint64, c_void_p, c_void_p]),
     "paella_test_gemm_prologue": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
                                           c_void_p, c_size_t, c_void_p]),
+    "paella_test_gemm_desc": (c_int, [POINTER(TestGemmArgs), c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "paella_test_gemm_args_size": (c_size_t, []),
 }
 
 _lib = None

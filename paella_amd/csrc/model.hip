@@ -1406,28 +1406,98 @@ extern "C" int paella_op_gemm(const float* A, const float* W, const float* bias,
     g.ep.bias = bias; g.ep.act = act; g.ep.residual = residual; g.ep.ldr = N;
     return launch_gemm_cfg(g, tile_cfg, splitk, ws, ws_bytes, (hipStream_t)stream);
 }
+// the A-operand prologue of the two GEMM test hooks: mode 1 = GRN apply, mode 2 = LayerNorm from row statistics, with the weight's row sums summed here into a
+// cached scratch buffer (one extra M = 1 launch per call: timing loops over these hooks include it)
+static int test_gemm_set_prologue(GemmArgs& g, int mode, const float* scale, const float* shift, int rows_per_sample, const float* ln_stats, hipStream_t st) {
+    if (mode == 1) { g.a_scale = scale; g.a_shift = shift; g.a_rows_per_sample = rows_per_sample; }
+    else if (mode == 2) {
+        g.ln_stats = ln_stats; g.ln_nblk = g.K / 16; g.ln_eps = 1e-6f;
+        static DevBuf ones, wsum;
+        if (ones.n < (size_t)g.K) {
+            std::vector<float> h((size_t)g.K, 1.0f);
+            RET_IF(devbuf_alloc(ones, (size_t)g.K));
+            HIP_CHECK_RET(hipMemcpy(ones.p, h.data(), (size_t)g.K * sizeof(float), hipMemcpyHostToDevice));
+        }
+        if (wsum.n < (size_t)g.N) RET_IF(devbuf_alloc(wsum, (size_t)g.N));
+        GemmArgs gs = gemm_args(ones.p, g.K, g.W, g.ldw, wsum.p, g.N, 1, g.N, g.K);
+        RET_IF(launch_gemm_cfg(gs, 5, 1, nullptr, 0, st));
+        g.ln_wsum = wsum.p;
+    }
+    else if (mode != 0) { paella_set_error("prologue mode must be 0, 1 (scale / shift per sample) or 2 (LayerNorm from row statistics)"); return PAELLA_ERR_ARG; }
+    return PAELLA_OK;
+}
 // test hook (test_hooks.h): the A-operand prologue variants of the GEMM with an explicit tile config / workgroup count
 extern "C" int paella_test_gemm_prologue(const float* A, const float* W, float* C, int M, int N, int K, int mode, const float* scale,
                                          const float* shift, int rows_per_sample, const float* ln_stats, int tile_cfg, int splitk, void* ws,
                                          size_t ws_bytes, void* stream) {
     GemmArgs g = gemm_args(A, K, W, K, C, N, M, N, K);
-    if (mode == 1) { g.a_scale = scale; g.a_shift = shift; g.a_rows_per_sample = rows_per_sample; }
-    else if (mode == 2) {
-        g.ln_stats = ln_stats; g.ln_nblk = K / 16; g.ln_eps = 1e-6f;
-        {   // the weight's row sums, summed here into a cached scratch buffer (one extra M = 1 launch per call: timing loops over this hook include it)
-            static DevBuf ones, wsum;
-            if (ones.n < (size_t)K) {
-                std::vector<float> h((size_t)K, 1.0f);
-                RET_IF(devbuf_alloc(ones, (size_t)K));
-                HIP_CHECK_RET(hipMemcpy(ones.p, h.data(), (size_t)K * sizeof(float), hipMemcpyHostToDevice));
-            }
-            if (wsum.n < (size_t)N) RET_IF(devbuf_alloc(wsum, (size_t)N));
-            GemmArgs gs = gemm_args(ones.p, K, W, K, wsum.p, N, 1, N, K);
-            RET_IF(launch_gemm_cfg(gs, 5, 1, nullptr, 0, (hipStream_t)stream));
-            g.ln_wsum = wsum.p;
+    RET_IF(test_gemm_set_prologue(g, mode, scale, shift, rows_per_sample, ln_stats, (hipStream_t)stream));
+    return launch_gemm_cfg(g, tile_cfg, splitk, ws, ws_bytes, (hipStream_t)stream);
+}
+// test hook (test_hooks.h): any fp32 GEMM launch, described field by field.  Everything is validated on the host BEFORE the first device call: the largest element
+// index the launch can store into C / c16 (gemm_device.h: epilogue_write) and into the statistics (gemm.hip: ep_row) must fit the capacities the caller states
+extern "C" size_t paella_test_gemm_args_size(void) { return sizeof(paella_test_gemm_args); }
+static int test_gemm_max_store_index(const paella_test_gemm_args& a, long long* out) {
+    const long long M = a.M, N = a.N;
+    if (a.store_mode == STORE_PLAIN) {
+        long long row = M - 1;
+        if (a.remap_in > 0) {
+            if (a.remap_out < 0 || a.remap_off < 0) { paella_set_error("gemm_desc: negative row remap"); return PAELLA_ERR_ARG; }
+            const long long q = (M - 1) / a.remap_in, r = (M - 1) % a.remap_in;
+            row = q * a.remap_out + r;                                           // the last row, or
+            if (q > 0 && (q - 1) * a.remap_out + a.remap_in - 1 > row) row = (q - 1) * a.remap_out + a.remap_in - 1;  // the end of the last whole group (remap_out < remap_in)
+            row += a.remap_off;
         }
+        if (a.ldc < 0) { paella_set_error("gemm_desc: negative ldc"); return PAELLA_ERR_ARG; }
+        *out = row * a.ldc + N - 1;
+        return PAELLA_OK;
     }
-    else if (mode != 0) { paella_set_error("prologue mode must be 0, 1 (scale / shift per sample) or 2 (LayerNorm from row statistics)"); return PAELLA_ERR_ARG; }
+    if (a.store_mode != STORE_D2S && a.store_mode != STORE_PIXSHUF_NCHW) { paella_set_error("gemm_desc: unknown store mode %d", a.store_mode); return PAELLA_ERR_ARG; }
+    if (a.c16 || !a.C || a.remap_in > 0) { paella_set_error("gemm_desc: the bf16 copy, C == NULL and the row remap belong to the plain store"); return PAELLA_ERR_ARG; }
+    if (a.sH < 1 || a.sW < 1 || a.sC < 1 || M % ((long long)a.sH * a.sW)) {
+        paella_set_error("gemm_desc: a depth-to-space / pixel-shuffle store needs a source grid with M a multiple of sH * sW (M=%d sH=%d sW=%d sC=%d)", a.M, a.sH, a.sW, a.sC);
+        return PAELLA_ERR_ARG;
+    }
+    const long long B = M / ((long long)a.sH * a.sW), H2 = 2ll * a.sH, W2 = 2ll * a.sW;
+    if (a.store_mode == STORE_D2S) {
+        if (a.n_seg_x < 1 || N % a.sC || a.py < 0 || a.px < 0 || a.ldc < 0) { paella_set_error("gemm_desc: bad depth-to-space store (N=%d sC=%d n_seg_x=%d py=%d px=%d)", a.N, a.sC, a.n_seg_x, a.py, a.px); return PAELLA_ERR_ARG; }
+        const long long nseg = N / a.sC, dy = (nseg - 1) / a.n_seg_x, dx = (nseg < a.n_seg_x ? nseg : a.n_seg_x) - 1;
+        const long long row = ((B - 1) * H2 + H2 - 2 + dy + a.py) * W2 + W2 - 2 + dx + a.px;
+        *out = row * a.ldc + a.sC - 1;
+    } else {
+        *out = (((B - 1) * a.sC + (N - 1) / 4) * H2 + H2 - 1) * W2 + W2 - 1;
+    }
+    return PAELLA_OK;
+}
+extern "C" int paella_test_gemm_desc(const paella_test_gemm_args* a, int tile_cfg, int splitk, void* ws, size_t ws_bytes, void* stream) {
+    if (!a || a->M <= 0 || a->N <= 0 || a->K <= 0 || !a->A || !a->W || (!a->C && !a->c16)) { paella_set_error("gemm_desc: null argument or empty problem"); return PAELLA_ERR_ARG; }
+    long long last = 0;
+    RET_IF(test_gemm_max_store_index(*a, &last));
+    if ((a->C && (unsigned long long)last >= a->c_capacity) || (a->c16 && (unsigned long long)last >= a->c16_capacity)) {
+        paella_set_error("gemm_desc: the launch stores up to element %lld, past the stated capacity (C %zu, c16 %zu)", last, a->C ? a->c_capacity : (size_t)0, a->c16 ? a->c16_capacity : (size_t)0);
+        return PAELLA_ERR_ARG;
+    }
+    if (a->rowstat_out && (unsigned long long)a->M * (a->N / 16) * 2 > a->rowstat_capacity) {
+        paella_set_error("gemm_desc: rowstat_out needs M * (N / 16) * 2 = %lld elements, capacity %zu", (long long)a->M * (a->N / 16) * 2, a->rowstat_capacity);
+        return PAELLA_ERR_ARG;
+    }
+    if (a->sumsq_out && (unsigned long long)((a->M + 15) / 16) * a->N > a->sumsq_capacity) {
+        paella_set_error("gemm_desc: sumsq_out needs ceil(M / 16) * N = %lld elements, capacity %zu", (long long)((a->M + 15) / 16) * a->N, a->sumsq_capacity);
+        return PAELLA_ERR_ARG;
+    }
+    GemmArgs g = gemm_args(a->A, a->lda, a->W, a->ldw, a->C, a->ldc, a->M, a->N, a->K);
+    Epilogue& e = g.ep;
+    e.bias = a->bias; e.act = a->act; e.alpha = a->alpha; e.residual = a->residual; e.ldr = a->ldr;
+    e.ts = a->ts; e.ts_stride = a->ts_stride; e.rows_per_sample = a->rows_per_sample > 0 ? a->rows_per_sample : 1;
+    e.store_mode = a->store_mode; e.sH = a->sH; e.sW = a->sW; e.sC = a->sC; e.py = a->py; e.px = a->px; e.n_seg_x = a->n_seg_x;
+    e.rowstat_out = a->rowstat_out; e.sumsq_out = a->sumsq_out;
+    e.remap_in = a->remap_in; e.remap_out = a->remap_out; e.remap_off = a->remap_off;
+    e.c16 = a->c16;
+    if (a->cv_enabled) {
+        g.cv.enabled = 1; g.cv.Hi = a->cv_Hi; g.cv.Wi = a->cv_Wi; g.cv.C = a->cv_C; g.cv.Ho = a->cv_Ho; g.cv.Wo = a->cv_Wo; g.cv.stride = a->cv_stride; g.cv.ntaps = a->cv_ntaps;
+        g.cv.tw_log2 = a->cv_tw_log2; g.cv.oy0 = a->cv_oy0; g.cv.ox0 = a->cv_ox0; g.cv.tsign = a->cv_tsign;
+    }
+    RET_IF(test_gemm_set_prologue(g, a->mode, a->scale, a->shift, a->a_rows_per_sample, a->ln_stats, (hipStream_t)stream));
     return launch_gemm_cfg(g, tile_cfg, splitk, ws, ws_bytes, (hipStream_t)stream);
 }
 // test hook (test_hooks.h): the MLP pair of a ResBlock with GlobalResponseNorm finished inside the GEMMs (no finalize launch) -- the fused path of

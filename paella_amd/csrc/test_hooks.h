@@ -44,6 +44,34 @@ int paella_test_attention_variant(int v);
  * sum of squared deviations from the block mean) (LayerNorm folded into the consumer's EPILOGUE; the hook sums W's rows itself with one extra M = 1 launch per call) */
 int paella_test_gemm_prologue(const float* A, const float* W, float* C, int M, int N, int K, int mode, const float* scale, const float* shift,
                               int rows_per_sample, const float* ln_stats, int tile_cfg, int splitk, void* ws, size_t ws_bytes, void* stream);
+/* ONE fp32 GEMM launch described field by field (common.h: GemmArgs / Epilogue / ConvGather), for tests that drive a chosen epilogue feature or store mode on a chosen
+ * tile and work split.  Unset = 0 / NULL, except alpha (1 = none) and n_seg_x (2 in the product's k2 s2 store).  Mirrored by paella_amd/_lib.py: TestGemmArgs. */
+typedef struct paella_test_gemm_args {
+    const float* A; int lda;           /* [M, K] (cv_enabled: the NHWC image, lda unused) */
+    const float* W; int ldw;           /* [N, K] */
+    float* C; int ldc;                 /* may be NULL when c16 is set */
+    int M, N, K;
+    const float* bias; int act; float alpha;
+    const float* residual; int ldr;
+    const float* ts; int ts_stride, rows_per_sample;
+    int store_mode, sH, sW, sC, py, px, n_seg_x;
+    float* rowstat_out;                /* [M, N/16, 2] */
+    float* sumsq_out;                  /* [ceil(M/16), N] */
+    int remap_in, remap_out, remap_off;
+    unsigned short* c16;
+    /* A-operand prologue as paella_test_gemm_prologue: 0 none, 1 a * scale[row / a_rows_per_sample][k] + shift[k], 2 LayerNorm from ln_stats [M, K/16, 2] */
+    int mode;
+    const float* scale; const float* shift; int a_rows_per_sample;
+    const float* ln_stats;
+    /* implicit convolution (ConvGather) */
+    int cv_enabled, cv_Hi, cv_Wi, cv_C, cv_Ho, cv_Wo, cv_stride, cv_ntaps, cv_tw_log2, cv_oy0, cv_ox0, cv_tsign;
+    /* capacities, in ELEMENTS, of the buffers behind C, c16, rowstat_out and sumsq_out: the hook refuses a launch that could store past one of them */
+    size_t c_capacity, c16_capacity, rowstat_capacity, sumsq_capacity;
+} paella_test_gemm_args;
+/* fills a GemmArgs from *a and launches it with an explicit tile config / workgroup count (as paella_op_gemm).  Before any device call it computes, from the store mode,
+ * the row remap and ldc, the largest element index the launch can write into each output and returns PAELLA_ERR_ARG when one does not fit its capacity */
+int paella_test_gemm_desc(const paella_test_gemm_args* a, int tile_cfg, int splitk, void* ws, size_t ws_bytes, void* stream);
+size_t paella_test_gemm_args_size(void);
 /* out[M, c] = GRN(gelu(h W1^T + b1)) W2^T with GlobalResponseNorm finished inside the two GEMMs (the batch-1 path of a ResBlock's MLP: no finalize
  * launch); scratch: hidden [M, 4c], gx [M / rps, 4c], part [M / rps, 4c / 16].  Fails when the shape is outside the fused path's domain. */
 int paella_test_mlp_grn_fused(const float* h, const float* W1, const float* b1, const float* gamma, const float* beta, const float* W2, float* hidden,
