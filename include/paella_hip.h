@@ -370,6 +370,38 @@ int paella_unet_forward_sample_stream_kw(paella_unet* m, const int64_t* tokens, 
                                          const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
                                          int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Truncated sampling (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays 8): top-k, nucleus (top-p) and
+ * typical filtering of the categorical draw, on materialised logits (the fused head sees 64 columns at a time and has no row
+ * statistics; feed these from the logits-returning forwards).  Per row, with z_i = fp32(mix_i * (1 / T)):
+ *   A    = {i : z_i >= the top_k-th largest z}, ties kept; every label when top_k <= 0 or top_k >= L
+ *   p    = softmax(z) over A
+ *   top_p = P in (0, 1):        kept = {i in A : z_i >= v*},  v* the largest value with sum_{z_j >= v*} p_j >= P
+ *   typical_mass = M in (0, 1): kept = {i in A : d_i <= d*},  d_i = |-log p_i - H|, H = -sum p log p, d* the smallest value with
+ *                               sum_{d_j <= d*} p_j >= M
+ *   neither:                    kept = A.  A mass of 1 is "off"; both below 1 is PAELLA_ERR_ARG (in a table row: top_p wins).
+ *   min_tokens = n >= 1:        with a mass filter, the n first labels of A in that filter's order stay as well (ties kept)
+ * token = the first arg-max over kept of the scores of the unfiltered tail, drawn from the same Philox words: the filter removes
+ * candidates and never changes a random number, so a row whose kept set is every label yields the token of the entry point extended.
+ * A row with a NaN or without a finite maximum is not filtered; a mass target that rounding keeps out of reach keeps A.  Renoise,
+ * pin, sampled_out and active[] apply after the draw exactly as before.  Categorical mode and in-kernel noise only; L <= 16384
+ * (a row lives in LDS), L % 4 == 0; anything else is PAELLA_ERR_ARG.
+ * ---------------------------------------------------------------------------------------------- */
+/* paella_sample_tail_pin with one filter setting for the launch. */
+int paella_sample_tail_filter(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg,
+                              float temperature, int mode, uint64_t seed, const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset,
+                              const int64_t* row_offset_ptr, const int64_t* init_noise, float t_next, const int64_t* pin_keep,
+                              const int64_t* pin_tokens, int top_k, float top_p, float typical_mass, int min_tokens,
+                              int64_t* tokens_out, int64_t* sampled_out, void* stream);
+/* paella_sample_tail_stream_pin with one filter per request: DEVICE tables filter_k int32 [B, 2] = (top_k, min_tokens) and
+ * filter_mass fp32 [B, 2] = (top_p, typical_mass), both or neither.  A request whose row says "off" takes the plain arg-max loop
+ * (tokens of paella_sample_tail_stream_pin bit for bit); both NULL IS paella_sample_tail_stream_pin -- same kernel, same launch. */
+int paella_sample_tail_stream_filter(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs,
+                                     const float* temperature, const uint64_t* seeds, int rows_per_sample, const int* step,
+                                     const float* t_next, const int* active, const int64_t* init_noise, const int64_t* pin_keep,
+                                     const int64_t* pin_tokens, const int* pin_on, const int* filter_k, const float* filter_mass,
+                                     int64_t* tokens_out, int64_t* sampled_out, void* stream);
+
 /* x, random_x, mask int64 [B, per_sample]; t fp32 [B].  mask_in NULL -> mask = (u <= t[b]) with u = rand_u
  * (caller noise, [B, per_sample]) or Philox; random_x NULL -> Philox randint(0, num_labels). */
 int paella_add_noise(const int64_t* x, const float* t, const int64_t* mask_in, const int64_t* random_x,

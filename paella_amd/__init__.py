@@ -12,6 +12,10 @@ Public surface (mirrors the reference's Python API):
                               the batch and the graph with text-to-image ones; the sampling tail re-imposes their known tokens
     KeyWeights                (extension) per-request prompt weights: one row of post-softmax key multipliers per conditioning slot instead of one attn_weights
                               vector per launch; sample_requests / GraphRequestSampler / RequestStream.admit take attn_weights per request, per guidance side
+    top_k / top_p / typical_mass / min_tokens
+                              (extension, keyword-only) truncated sampling on sample, sample_distributed, GraphSampler, sample_requests (one value or one per
+                              request), GraphRequestSampler(filtering=True) and RequestStream(filtering=True).admit: the draw is restricted to a subset of the
+                              labels, the random numbers stay those of the unfiltered call (DESIGN.md 4 "Truncated sampling")
     inpaint / GraphInpainter  (extension) encode -> masked renoise -> sample -> decode; pin="step" keeps the known region clean at every step
     canvas                    (extension) a token grid placed on a larger canvas -> (known, mask): the outpainting set-up
     replace_attention_layers  reference utils/alter_attention.py:45

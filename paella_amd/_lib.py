@@ -161,6 +161,11 @@ SIGNATURES = {
     "paella_unet_forward_sample_stream_kw": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                                      c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                      c_void_p, c_size_t, c_void_p]),
+    # truncated sampling (ABI 8, additive): the filter values / tables right before the outputs
+    "paella_sample_tail_filter": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_float, c_float, c_int, c_uint64, c_void_p, c_uint64, c_int64, c_void_p, c_void_p,
+                                          c_float, c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p]),
+    "paella_sample_tail_stream_filter": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 }
 
 # exported for tests / tools only; declared in paella_amd/csrc/test_hooks.h, not in the public header
@@ -196,6 +201,8 @@ TEST_HOOKS = {
     "paella_test_gemm_tail_tile": (c_int, [c_int]),
     "paella_test_tail_scores": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_float, c_float, c_uint64, c_uint64, c_int64, c_void_p, c_void_p]),
     "paella_test_tail_scores_req": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_uint64, c_void_p, c_void_p]),
+    "paella_test_tail_filter_keep": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_float, c_float, c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "paella_test_gemm_prologue": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
                                           c_void_p, c_size_t, c_void_p]),
     "paella_test_gemm_desc": (c_int, [POINTER(TestGemmArgs), c_int, c_int, c_void_p, c_size_t, c_void_p]),

@@ -313,6 +313,22 @@ struct TailArgs {
     const int* pin_on = nullptr;          // [B] request form only: this launch's per-slot flag (tail.hip: request_step_kernel emits it); null = the pin applies to every slot
 };
 int launch_sample_tail(const TailArgs& a, hipStream_t stream);
+// Truncated sampling (tail.hip: sample_tail_filter_kernel): what restricts the draw of a row to a subset of its labels, next to -- never inside -- TailArgs.
+// With z_i = fp32(mix_i * inv_t):  A = labels with z_i >= the top_k-th largest z (ties kept; every label when top_k is off); p = softmax(z) over A;
+//   top_p P:        kept = {i in A : z_i >= v*}, v* the largest value with sum_{z_j >= v*} p_j >= P
+//   typical_mass M: kept = {i in A : d_i <= d*}, d_i = |-log p_i - H|, H the entropy of p, d* the smallest value with sum_{d_j <= d*} p_j >= M
+// and the min_tokens first labels of A in that order (ties kept) stay as well.  Off: top_k <= 0 or >= L, a mass not inside (0, 1); min_tokens counts only with a
+// mass filter.  The draw is the first arg-max of the UNFILTERED scores over kept.  A row with a NaN or a non-finite maximum is not filtered.
+struct TailFilter {
+    int top_k = 0, min_tokens = 1;            // scalar form
+    float top_p = 1.f, typical_mass = 1.f;
+    const int* filter_k = nullptr;            // request form: [B, 2] = (top_k, min_tokens) per request; both tables or neither (neither = launch_sample_tail)
+    const float* filter_mass = nullptr;       // request form: [B, 2] = (top_p, typical_mass) per request; a row with both on takes top_p
+    unsigned char* keep_out = nullptr;        // test hook only: [rows, L] keep mask; the selection alone runs, nothing is drawn or stored
+    float* rec_out = nullptr;                 // test hook only: [rows, 4] = (m, log sum exp(z - m), H, threshold)
+};
+static const int kTailFilterMaxLabels = 16384;  // the row's z lives in LDS
+int launch_sample_tail_filter(const TailArgs& a, const TailFilter& f, hipStream_t stream);
 // one tick of a request stream: per slot b, row pos[b] of its program [B, max_steps, 5] = (r, temperature, cfg, 1 - cfg, t_next) becomes this tick's flat tables
 // (pairs may be null), step[b] = pos[b], active[b] = pos[b] < len[b]; the cursors of the active slots advance.  Idle slots: r 0, T 1, pair (1, 0), t_next -1.
 // pin_policy / pin_on (both or neither; null = exactly the stores above): per slot 0 = never, 1 = every step, 2 = the request's final step only ->

@@ -1316,6 +1316,30 @@ extern "C" int paella_sample_tail_stream_pin(const float* logits_c, const float*
     a.pin_keep = pin_keep; a.pin_tokens = pin_tokens; a.pin_on = pin_on;
     return launch_sample_tail(a, (hipStream_t)stream);
 }
+// paella_sample_tail_stream_pin with the per-request filter tables (common.h: TailFilter), the most general member of the family: both tables NULL = the launch of
+// paella_sample_tail_stream_pin
+extern "C" int paella_sample_tail_stream_filter(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
+                                                const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active,
+                                                const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
+                                                const int* filter_k, const float* filter_mass, int64_t* tokens_out, int64_t* sampled_out, void* stream) {
+    if (!filter_k && !filter_mass)
+        return paella_sample_tail_stream_pin(logits_c, logits_u, rows, L, cfg_pairs, temperature, seeds, rows_per_sample, step, t_next, active, init_noise, pin_keep,
+                                             pin_tokens, pin_on, tokens_out, sampled_out, stream);
+    if (!logits_c || !tokens_out || !seeds || !temperature) { paella_set_error("sample_tail_stream_filter: null argument"); return PAELLA_ERR_ARG; }
+    if (!filter_k != !filter_mass) { paella_set_error("sample_tail_stream_filter: filter_k and filter_mass must be given together (one filter table without the other)"); return PAELLA_ERR_ARG; }
+    RET_IF(stream_tables_check("sample_tail_stream_filter", step, t_next, active, init_noise));
+    RET_IF(pin_tables_check("sample_tail_stream_filter", pin_keep, pin_tokens, pin_on, 0));
+    if (rows_per_sample <= 0) { paella_set_error("sample_tail_stream_filter: rows_per_sample must be > 0"); return PAELLA_ERR_ARG; }
+    TailArgs a = {};
+    a.logits_c = logits_c; a.logits_u = cfg_pairs ? logits_u : nullptr; a.rows = rows; a.L = L; a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f;
+    a.init_noise = init_noise; a.t_next = -1.f; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
+    a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.cfg_pairs = cfg_pairs; a.rq.rows_per_sample = rows_per_sample;
+    a.rq.step = step; a.rq.t_next = t_next; a.rq.active = active;
+    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens; a.pin_on = pin_on;
+    TailFilter f;
+    f.filter_k = filter_k; f.filter_mass = filter_mass;
+    return launch_sample_tail_filter(a, f, (hipStream_t)stream);
+}
 extern "C" int paella_sample_tail_stream(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
                                          const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active,
                                          const int64_t* init_noise, int64_t* tokens_out, int64_t* sampled_out, void* stream) {
@@ -1372,6 +1396,27 @@ extern "C" int paella_sample_tail_pin(const float* logits_c, const float* logits
     a.init_noise = init_noise; a.t_next = t_next; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
     a.pin_keep = pin_keep; a.pin_tokens = pin_tokens;
     return launch_sample_tail(a, (hipStream_t)stream);
+}
+
+// paella_sample_tail_pin with a truncation filter (common.h: TailFilter; top_k <= 0 or >= L, top_p = 1, typical_mass = 1 are "off"): categorical mode only
+extern "C" int paella_sample_tail_filter(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature, int mode,
+                                         uint64_t seed, const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr,
+                                         const int64_t* init_noise, float t_next, const int64_t* pin_keep, const int64_t* pin_tokens, int top_k, float top_p,
+                                         float typical_mass, int min_tokens, int64_t* tokens_out, int64_t* sampled_out, void* stream) {
+    if (!logits_c || !tokens_out) { paella_set_error("sample_tail_filter: null argument"); return PAELLA_ERR_ARG; }
+    if (mode != 0) { paella_set_error("sample_tail_filter: the filter is not offered in argmax mode"); return PAELLA_ERR_ARG; }
+    if (!(temperature > 0.f)) { paella_set_error("temperature must be > 0 in categorical mode (use mode=1 for argmax)"); return PAELLA_ERR_ARG; }
+    if (row_offset < 0) { paella_set_error("row_offset must be >= 0"); return PAELLA_ERR_ARG; }
+    RET_IF(pin_tables_check("sample_tail_filter", pin_keep, pin_tokens, nullptr, mode));
+    TailArgs a = {};
+    a.logits_c = logits_c; a.logits_u = logits_u; a.rows = rows; a.L = L; a.cfg = cfg; a.one_minus_cfg = one_minus_cfg;
+    a.temperature = temperature; a.mode = mode; a.seed = seed; a.seed_ptr = seed_ptr; a.offset = offset;
+    a.row_offset = row_offset; a.row_offset_ptr = row_offset_ptr;
+    a.init_noise = init_noise; a.t_next = t_next; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
+    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens;
+    TailFilter f;
+    f.top_k = top_k; f.top_p = top_p; f.typical_mass = typical_mass; f.min_tokens = min_tokens;
+    return launch_sample_tail_filter(a, f, (hipStream_t)stream);
 }
 
 extern "C" int paella_sample_tail(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg,

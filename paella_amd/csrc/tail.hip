@@ -248,6 +248,232 @@ int launch_sample_tail(const TailArgs& a, hipStream_t st) {
 }
 
 // ---------------------------------------------------------------------------
+// Truncated sampling (common.h: TailFilter): top-k, nucleus (top-p) and typical filtering of a row before the categorical draw.  A threshold filter needs whole-row
+// statistics, so this is the one-kernel tail on MATERIALISED logits with the row's z = fp32(mix * inv_t) held in LDS (L * 4 bytes, written once), one 256-thread
+// workgroup per row.  Every threshold -- the k-th largest z, the nucleus value v*, the typical distance d*, the min_tokens value -- comes from filter_threshold:
+// bitwise bisection over an order-preserving 32-bit key, one workgroup reduction per bit, weight = count or exp(z - m).  Every reduction runs in one fixed order
+// (per thread sequential over i = tid, tid + 256, ...; xor-shuffles inside the wave; one LDS hop across the 4 waves) and a label outside the tested set adds +0:
+// rounding is monotone, so the sum is monotone in the set, the bisection is well defined and the kept set is bit-reproducible.  No atomics.
+// The draw itself is the plain tail's: the same Philox words, the same scores, the same first-index arg-max -- over the kept labels only.
+// ---------------------------------------------------------------------------
+// smaller key = larger z (-0 == +0); z is never NaN here
+__device__ __forceinline__ uint32_t filter_key_desc(float z) {
+    const uint32_t b = __float_as_uint(z == 0.f ? 0.f : z);
+    return (b & 0x80000000u) ? b : ~(b | 0x80000000u);
+}
+__device__ __forceinline__ float filter_key_desc_value(uint32_t key) {
+    return __uint_as_float((key & 0x80000000u) ? key : (~key & 0x7fffffffu));
+}
+// typical filtering: d = |-log p - H| = |c - (z - m)| with c = sum (z - m) e / sum e (the log sum cancels); d >= 0, so its bit pattern is its key
+__device__ __forceinline__ uint32_t filter_key_typ(float z, float m, float c) { return __float_as_uint(fabsf(c - (z - m))); }
+
+struct FilterSums { float s, e; };
+// sum of (v, w) over the workgroup in the fixed order; red: [2][4][2] floats, `phase` alternates so one barrier per reduction is enough
+__device__ __forceinline__ FilterSums filter_reduce(float v, float w, float* red, int& phase) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) { v += __shfl_xor(v, o, 64); w += __shfl_xor(w, o, 64); }
+    float* r = red + phase * 8;
+    if ((threadIdx.x & 63) == 0) { r[(threadIdx.x >> 6) * 2] = v; r[(threadIdx.x >> 6) * 2 + 1] = w; }
+    __syncthreads();
+    phase ^= 1;
+    return FilterSums{(r[0] + r[2]) + (r[4] + r[6]), (r[1] + r[3]) + (r[5] + r[7])};
+}
+// The smallest tau such that the weight of {i in A : key_i <= tau} reaches target; 0xffffffff (= all of A) when even A does not reach it.
+// A = {i : filter_key_desc(z_i) <= tau_a}; TYP: key = the typical distance, else the descending-z key; MASS: weight = exp(z - m), else 1.  Workgroup-uniform result.
+template <bool TYP, bool MASS>
+__device__ uint32_t filter_threshold(const float* zs, int L, uint32_t tau_a, float m, float c, float target, float* red, int& phase) {
+    uint32_t prefix = 0;
+    for (int bit = 32; bit >= 0; --bit) {
+        const uint32_t t = bit == 32 ? 0xffffffffu : (prefix | ((1u << bit) - 1u));
+        float acc = 0.f;
+        for (int i = threadIdx.x; i < L; i += 256) {
+            const float z = zs[i];
+            const uint32_t ka = filter_key_desc(z);
+            const uint32_t key = TYP ? filter_key_typ(z, m, c) : ka;
+            const float w = MASS ? __expf(z - m) : 1.f;
+            acc += (ka <= tau_a && key <= t) ? w : 0.f;
+        }
+        const bool reached = filter_reduce(acc, 0.f, red, phase).s >= target;
+        if (bit == 32) { if (!reached) return 0xffffffffu; }
+        else if (!reached) prefix |= 1u << bit;
+    }
+    return prefix;
+}
+
+template <bool REQ>
+__global__ __launch_bounds__(256) void sample_tail_filter_kernel(TailArgs a, TailFilter f) {
+    extern __shared__ float zs[];  // [L]
+    __shared__ float red[16];
+    __shared__ float red_v[4];
+    __shared__ int red_i[4];
+    const int64_t row = blockIdx.x;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int L = a.L, L4 = L >> 2;
+    const float* lc = a.logits_c + row * L;
+    const float* lu = a.logits_u ? a.logits_u + row * L : nullptr;
+    const bool has_u = lu != nullptr;
+    const RowKey rk = tail_row_key<REQ>(a, row);
+    if (!rk.active) return;  // an idle slot of a request stream stores nothing (workgroup-uniform)
+    const float inv_t = tail_inv_temperature(rk.temperature);
+
+    // the row's filter, read once per workgroup
+    int top_k = f.top_k, min_tokens = f.min_tokens;
+    float top_p = f.top_p, typical = f.typical_mass;
+    if constexpr (REQ) {
+        const unsigned b = fast_div((unsigned)row, a.rq.rps_div);
+        top_k = f.filter_k[2 * b]; min_tokens = f.filter_k[2 * b + 1];
+        top_p = f.filter_mass[2 * b]; typical = f.filter_mass[2 * b + 1];
+    }
+    const bool k_on = top_k >= 1 && top_k < L;
+    const bool p_on = top_p > 0.f && top_p < 1.f;
+    const bool t_on = !p_on && typical > 0.f && typical < 1.f;
+    const bool hook = f.keep_out != nullptr;
+
+    bool use = false, typ_b = false;  // the kept set: key_desc <= tau_a && (typ_b ? key_typ : key_desc) <= tau_b
+    uint32_t tau_a = 0xffffffffu, tau_b = 0xffffffffu;
+    float m = 0.f, c = 0.f, sum = 0.f;
+    if (k_on || p_on || t_on || hook) {  // (workgroup-uniform: a row with every filter off runs the plain arg-max loop below and never touches zs)
+        float mx = -INFINITY, bad = 0.f;
+        for (int i4 = tid; i4 < L4; i4 += 256) {
+            const f32x4 cc = *reinterpret_cast<const f32x4*>(lc + i4 * 4);
+            const f32x4 uu = has_u ? *reinterpret_cast<const f32x4*>(lu + i4 * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+            f32x4 z;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                z[e] = mix_logit(cc[e], uu[e], rk.cfg, rk.omc, has_u) * inv_t;
+                mx = fmaxf(mx, z[e]);
+                if (z[e] != z[e]) bad = 1.f;
+            }
+            *reinterpret_cast<f32x4*>(zs + i4 * 4) = z;
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) { mx = fmaxf(mx, __shfl_xor(mx, o, 64)); bad = fmaxf(bad, __shfl_xor(bad, o, 64)); }
+        if (lane == 0) { red[wave * 2] = mx; red[wave * 2 + 1] = bad; }
+        __syncthreads();  // (also: zs is complete)
+        mx = fmaxf(fmaxf(red[0], red[2]), fmaxf(red[4], red[6]));
+        bad = fmaxf(fmaxf(red[1], red[3]), fmaxf(red[5], red[7]));
+        int phase = 1;  // the first reduction below writes red[8..15]; red[0..7] is rewritten only after the barrier that follows these reads
+        if (bad == 0.f && fabsf(mx) < INFINITY) {  // a NaN, or no finite maximum: the plain tail
+            use = true;
+            m = mx;
+            if (k_on) tau_a = filter_threshold<false, false>(zs, L, 0xffffffffu, m, 0.f, (float)top_k, red, phase);
+            if (p_on || t_on || hook) {
+                float s = 0.f, e = 0.f;
+                for (int i = tid; i < L; i += 256) {
+                    const float z = zs[i];
+                    const float w = filter_key_desc(z) <= tau_a ? __expf(z - m) : 0.f;
+                    s += w;
+                    e += w > 0.f ? (z - m) * w : 0.f;  // a label of probability 0 adds 0 to the entropy
+                }
+                const FilterSums st = filter_reduce(s, e, red, phase);
+                sum = st.s;
+                c = __fdiv_rn(st.e, st.s);
+                if (p_on) tau_b = filter_threshold<false, true>(zs, L, tau_a, m, c, top_p * sum, red, phase);
+                else if (t_on) { typ_b = true; tau_b = filter_threshold<true, true>(zs, L, tau_a, m, c, typical * sum, red, phase); }
+                if ((p_on || t_on) && min_tokens > 1 && tau_b != 0xffffffffu) {
+                    const float n = (float)(min_tokens < L + 1 ? min_tokens : L + 1);
+                    const uint32_t tn = typ_b ? filter_threshold<true, false>(zs, L, tau_a, m, c, n, red, phase)
+                                              : filter_threshold<false, false>(zs, L, tau_a, m, c, n, red, phase);
+                    if (tn > tau_b) tau_b = tn;
+                }
+            }
+        }
+    }
+    if (hook) {  // test hook: the selection only
+        for (int i = tid; i < L; i += 256) {
+            const float z = zs[i];
+            f.keep_out[row * L + i] = (!use || (filter_key_desc(z) <= tau_a && (typ_b ? filter_key_typ(z, m, c) : filter_key_desc(z)) <= tau_b)) ? 1 : 0;
+        }
+        if (tid == 0 && f.rec_out) {
+            const float nan = __uint_as_float(0x7fc00000u);
+            const float ls = use ? logf(sum) : nan;
+            const uint32_t tb = (p_on || t_on) ? tau_b : tau_a;
+            const bool thr = use && (k_on || p_on || t_on) && tb != 0xffffffffu;
+            f.rec_out[row * 4] = use ? m : nan;
+            f.rec_out[row * 4 + 1] = ls;
+            f.rec_out[row * 4 + 2] = ls - c;
+            f.rec_out[row * 4 + 3] = !thr ? nan : typ_b ? __uint_as_float(tb) : filter_key_desc_value(tb);
+        }
+        return;
+    }
+
+    // the plain tail's draw (sample_tail_kernel, counter-based mode), over the kept labels
+    float best = -INFINITY;
+    int best_i = 0x7fffffff;
+    for (int i4 = tid; i4 < L4; i4 += 256) {
+        const f32x4 cc = *reinterpret_cast<const f32x4*>(lc + i4 * 4);
+        const f32x4 uu = has_u ? *reinterpret_cast<const f32x4*>(lu + i4 * 4) : f32x4{0.f, 0.f, 0.f, 0.f};
+        f32x4 z = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (use) z = *reinterpret_cast<const f32x4*>(zs + i4 * 4);
+        uint32_t rb[4];
+        philox4x32(rk.seed, (uint64_t)rk.ctr_row * L4 + i4, rk.step, rb);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const bool kept = !use || (filter_key_desc(z[e]) <= tau_a && (typ_b ? filter_key_typ(z[e], m, c) : filter_key_desc(z[e])) <= tau_b);
+            const float score = tail_score_gumbel(mix_logit(cc[e], uu[e], rk.cfg, rk.omc, has_u), inv_t, log_exp1(rb[e]));
+            if (kept) argmax_update(best, best_i, score, i4 * 4 + e);
+        }
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float ov = __shfl_xor(best, o, 64);
+        const int oi = __shfl_xor(best_i, o, 64);
+        argmax_update(best, best_i, ov, oi);
+    }
+    if (lane == 0) { red_v[wave] = best; red_i[wave] = best_i; }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w = 1; w < 4; ++w) argmax_update(best, best_i, red_v[w], red_i[w]);
+        if (best_i == 0x7fffffff) best_i = 0;  // all-NaN row
+        int64_t tok = best_i;
+        if (a.sampled_out) a.sampled_out[row] = tok;
+        tok = renoise_token(a, rk, row, tok);
+        if (a.pin_keep) tok = pin_token<REQ>(a, row, tok);
+        a.tokens_out[row] = tok;
+    }
+}
+
+// the filter's own argument rules; everything here is host arithmetic, checked before anything is enqueued
+static int tail_filter_check(const TailArgs& a, const TailFilter& f) {
+    if (a.L > kTailFilterMaxLabels) {
+        paella_set_error("sampling tail: the filter holds a row in LDS, num_labels (%d) is limited to %d", a.L, kTailFilterMaxLabels);
+        return PAELLA_ERR_ARG;
+    }
+    if (a.mode != 0 || a.noise_q || a.mask_u) { paella_set_error("sampling tail: the filter needs categorical mode and in-kernel noise"); return PAELLA_ERR_ARG; }
+    if (!f.filter_k != !f.filter_mass) { paella_set_error("sampling tail: filter_k and filter_mass must be given together"); return PAELLA_ERR_ARG; }
+    if (f.filter_k && a.rq.rows_per_sample <= 0) { paella_set_error("sampling tail: the filter tables need the request form"); return PAELLA_ERR_ARG; }
+    if (a.rq.rows_per_sample <= 0) {
+        if (!(f.top_p > 0.f && f.top_p <= 1.f)) { paella_set_error("sampling tail: top_p must be in (0, 1] (1 = off)"); return PAELLA_ERR_ARG; }
+        if (!(f.typical_mass > 0.f && f.typical_mass <= 1.f)) { paella_set_error("sampling tail: typical_mass must be in (0, 1] (1 = off)"); return PAELLA_ERR_ARG; }
+        if (f.top_p < 1.f && f.typical_mass < 1.f) { paella_set_error("sampling tail: top_p and typical_mass are mutually exclusive (one mass filter at most)"); return PAELLA_ERR_ARG; }
+        if (f.min_tokens < 1) { paella_set_error("sampling tail: min_tokens must be >= 1"); return PAELLA_ERR_ARG; }
+    }
+    return PAELLA_OK;
+}
+
+int launch_sample_tail_filter(const TailArgs& a, const TailFilter& f, hipStream_t st) {
+    if (a.rows <= 0) return PAELLA_OK;
+    if (a.L <= 0 || (a.L & 3)) { paella_set_error("sample_tail: num_labels %% 4 != 0"); return PAELLA_ERR_ARG; }
+    if (a.rows > 0x7fffffff) { paella_set_error("sample_tail: too many rows"); return PAELLA_ERR_ARG; }
+    const int rc = tail_filter_check(a, f);
+    if (rc != PAELLA_OK) return rc;
+    RET_PIN(a);
+    const size_t lds = (size_t)a.L * sizeof(float);
+    if (a.rq.rows_per_sample > 0) {
+        if (!f.filter_k) return launch_sample_tail(a, st);  // no tables: the request form of the plain tail, the same launch
+        TailArgs r = a;
+        RET_REQ(r);
+        if (lds > 48 * 1024) HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_tail_filter_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(sample_tail_filter_kernel<true>, dim3((unsigned)a.rows), dim3(256), lds, st, r, f);
+    } else {
+        if (lds > 48 * 1024) HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_tail_filter_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(sample_tail_filter_kernel<false>, dim3((unsigned)a.rows), dim3(256), lds, st, a, f);
+    }
+    LAUNCH_CHECK_RET();
+    return PAELLA_OK;
+}
+
+// ---------------------------------------------------------------------------
 // One tick of a request stream (continuous batching; paella_amd.RequestStream): every slot b of the fixed-shape batch runs its own PROGRAM, one row per step,
 //   program [B, max_steps, 5] fp32: row j = (r_j, temperature_j, cfg_j, 1 - cfg_j, t_next_j)       cursor pos[b], length len[b]
 // and this launch turns the cursors into the flat per-slot tables the forward's timestep kernel and the stream form of the tail read at this tick, then advances
@@ -449,6 +675,31 @@ extern "C" int paella_test_tail_scores_req(const float* logits_c, const float* l
     hipLaunchKernelGGL(tail_scores_kernel<true>, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, a, scores_out);
     LAUNCH_CHECK_RET();
     return PAELLA_OK;
+}
+
+// test hook (test_hooks.h): the selection of the truncated-sampling tail alone -- keep_out uint8 [rows, L] = the kept set of every row, rec_out fp32 [rows, 4] =
+// (m, log sum exp(z - m), H, threshold) (NaN where the row has none: a NaN / non-finite row, no filter on, an unreachable target).  Scalar form
+// (rows_per_sample == 0: cfg pair, temperature and the four filter values by value) or request form (cfg_pairs / temps / seeds / the two filter tables per request,
+// as paella_sample_tail_req takes them; the seeds are read but nothing is drawn).
+extern "C" int paella_test_tail_filter_keep(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature,
+                                            int top_k, float top_p, float typical_mass, int min_tokens, const float* cfg_pairs, const float* temps,
+                                            const uint64_t* seeds, int rows_per_sample, const int* filter_k, const float* filter_mass, unsigned char* keep_out, float* rec_out,
+                                            void* stream) {
+    if (!logits_c || !keep_out || rows <= 0 || rows > 0x7fffffff || rows_per_sample < 0) { paella_set_error("tail_filter_keep: bad arguments"); return PAELLA_ERR_ARG; }
+    TailArgs a = {};
+    a.logits_c = logits_c; a.logits_u = logits_u; a.rows = rows; a.L = L; a.cfg = cfg; a.one_minus_cfg = one_minus_cfg; a.temperature = temperature;
+    TailFilter f;
+    f.keep_out = keep_out; f.rec_out = rec_out;
+    if (rows_per_sample > 0) {
+        if (!temps || !seeds || !filter_k || !filter_mass) { paella_set_error("tail_filter_keep: the request form needs the temperature, seed and the two filter tables"); return PAELLA_ERR_ARG; }
+        a.logits_u = cfg_pairs ? logits_u : nullptr; a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f;
+        a.rq.seeds = seeds; a.rq.temperature = temps; a.rq.cfg_pairs = cfg_pairs; a.rq.rows_per_sample = rows_per_sample;
+        f.filter_k = filter_k; f.filter_mass = filter_mass;
+    } else {
+        if (!(temperature > 0.f)) { paella_set_error("tail_filter_keep: temperature must be > 0"); return PAELLA_ERR_ARG; }
+        f.top_k = top_k; f.top_p = top_p; f.typical_mass = typical_mass; f.min_tokens = min_tokens;
+    }
+    return launch_sample_tail_filter(a, f, (hipStream_t)stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -126,6 +126,12 @@ int paella_test_tail_scores(const float* logits_c, const float* logits_u, int64_
 /* the same for a request batch (paella_sample_tail_req's tables): seed, guidance pair and temperature per sample, counters from the position inside the sample */
 int paella_test_tail_scores_req(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
                                 const uint64_t* seeds, int rows_per_sample, uint64_t offset, float* scores_out, void* stream);
+/* the selection of the truncated-sampling tail alone (tail.hip: sample_tail_filter_kernel): keep_out uint8 [rows, L] = the kept set of every row, rec_out fp32 [rows, 4]
+ * (optional) = (m, log sum exp(z - m), H, threshold), NaN where the row has none.  rows_per_sample == 0: the scalar form (cfg pair, temperature and the four filter values);
+ * > 0: the request form (cfg_pairs, temps, seeds and the filter tables filter_k int32 [B, 2], filter_mass fp32 [B, 2] per request) */
+int paella_test_tail_filter_keep(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature, int top_k,
+                                 float top_p, float typical_mass, int min_tokens, const float* cfg_pairs, const float* temps, const uint64_t* seeds,
+                                 int rows_per_sample, const int* filter_k, const float* filter_mass, unsigned char* keep_out, float* rec_out, void* stream);
 #ifdef __cplusplus
 }
 #endif

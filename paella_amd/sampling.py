@@ -112,10 +112,16 @@ def _cat_inputs(a, b):
 
 
 def _tail(logits_c, logits_u, rows, L, cfg, omc, temperature, mode, noise_q, seed, offset, init_noise, mask_u, t_next, out,
-          seed_dev=None, row_offset=0, row_offset_dev=None, pin=None):
+          seed_dev=None, row_offset=0, row_offset_dev=None, pin=None, filt=None):
     lib = _lib.load()
     dev = logits_c.device
     with torch.cuda.device(dev):
+        if filt is not None:  # truncated sampling: (top_k, top_p, typical_mass, min_tokens) of `check_filter`, the pin tables nullable
+            pk, pt = (None, None) if pin is None else pin
+            _lib.check(lib.paella_sample_tail_filter(_lib.ptr(logits_c), _lib.ptr(logits_u), rows, L, cfg, omc, temperature, mode, seed, _lib.ptr(seed_dev), offset,
+                                                     row_offset, _lib.ptr(row_offset_dev), _lib.ptr(init_noise), t_next, _lib.ptr(pk), _lib.ptr(pt), filt[0], filt[1],
+                                                     filt[2], filt[3], _lib.ptr(out), None, _lib.stream_ptr(dev)))
+            return
         if pin is not None:  # (keep, known): the tail writes known[row] wherever keep[row] == 0, after the draw and the renoise
             _lib.check(lib.paella_sample_tail_pin(_lib.ptr(logits_c), _lib.ptr(logits_u), rows, L, cfg, omc, temperature, mode, seed, _lib.ptr(seed_dev), offset,
                                                   row_offset, _lib.ptr(row_offset_dev), _lib.ptr(init_noise), t_next, _lib.ptr(pin[0]), _lib.ptr(pin[1]), _lib.ptr(out),
@@ -126,10 +132,17 @@ def _tail(logits_c, logits_u, rows, L, cfg, omc, temperature, mode, noise_q, see
                                              _lib.ptr(init_noise), _lib.ptr(mask_u), t_next, _lib.ptr(out), None, _lib.stream_ptr(dev)))
 
 
-def _tail_req(lc, lu, rows, L, rows_per_sample, req, step, init_noise, t_next, out):
-    """the request form of `_tail`: seed, guidance pair and temperature per sample from the device tables of `req` (RequestTables)"""
+def _tail_req(lc, lu, rows, L, rows_per_sample, req, step, init_noise, t_next, out, filt=None):
+    """the request form of `_tail`: seed, guidance pair and temperature per sample from the device tables of `req` (RequestTables); filt (FilterTables): the
+    filtered stream tail, fed with that step's constant step / renoise-threshold tables (the words the scalar arguments carry otherwise)"""
     dev = lc.device
     with torch.cuda.device(dev):
+        if filt is not None:
+            _lib.check(_lib.load().paella_sample_tail_stream_filter(_lib.ptr(lc), _lib.ptr(lu), rows, L, _lib.ptr(None if lu is None else req.pairs[step]),
+                                                                    _lib.ptr(req.temps[step]), _lib.ptr(req.seeds), rows_per_sample, _lib.ptr(filt.step[step]),
+                                                                    _lib.ptr(filt.t_next[step]), _lib.ptr(filt.active), _lib.ptr(init_noise), None, None,
+                                                                    None, _lib.ptr(filt.k), _lib.ptr(filt.mass), _lib.ptr(out), None, _lib.stream_ptr(dev)))
+            return
         _lib.check(_lib.load().paella_sample_tail_req(_lib.ptr(lc), _lib.ptr(lu), rows, L, _lib.ptr(None if lu is None else req.pairs[step]), _lib.ptr(req.temps[step]),
                                                       _lib.ptr(req.seeds), rows_per_sample, step, _lib.ptr(init_noise), t_next, _lib.ptr(out), None,
                                                       _lib.stream_ptr(dev)))
@@ -248,6 +261,77 @@ class RequestTables:
         return (self.seeds, self.temps[i], None if self.pairs is None else self.pairs[i])
 
 
+# ---------------------------------------------------------------------------------------------------------------- truncated sampling
+FILTER_OFF = (0, 1.0, 1.0, 1)  # (top_k, top_p, typical_mass, min_tokens) as the kernels read them: top_k <= 0, a mass of 1 = off
+
+
+def check_filter(top_k=None, top_p=None, typical_mass=None, min_tokens=1):
+    """One truncation setting -> (top_k, top_p, typical_mass, min_tokens) in the kernels' encoding (None becomes 0 / 1.0 / 1.0).  Raises a ValueError that names
+    the argument: a negative top_k, a mass outside (0, 1], min_tokens < 1, both mass filters at once (top_p=1 / typical_mass=1 are "off" and combine with anything)."""
+    is_int = lambda v: isinstance(v, int) and not isinstance(v, bool)
+    is_num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
+    if top_k is not None and (not is_int(top_k) or top_k < 0):
+        raise ValueError("top_k must be None or an integer >= 0 (0 = off), got %r" % (top_k,))
+    for name, v in (("top_p", top_p), ("typical_mass", typical_mass)):
+        if v is not None and (not is_num(v) or not 0.0 < float(v) <= 1.0):
+            raise ValueError("%s must be None or a mass in (0, 1] (1 = off), got %r" % (name, v))
+    if not is_int(min_tokens) or min_tokens < 1:
+        raise ValueError("min_tokens must be an integer >= 1, got %r" % (min_tokens,))
+    p, m = 1.0 if top_p is None else float(top_p), 1.0 if typical_mass is None else float(typical_mass)
+    if p < 1.0 and m < 1.0:
+        raise ValueError("top_p and typical_mass are mutually exclusive: one mass filter at most (got top_p=%r, typical_mass=%r)" % (top_p, typical_mass))
+    return (0 if top_k is None else int(top_k), p, m, int(min_tokens))
+
+
+def filter_on(f):
+    """does a `check_filter` tuple restrict anything (a top_k >= num_labels still counts: the kernel finds it off)"""
+    return f[0] > 0 or f[1] < 1.0 or f[2] < 1.0
+
+
+def _filter_names(top_k, top_p, typical_mass):
+    return " / ".join(n for n, v in (("top_k", top_k), ("top_p", top_p), ("typical_mass", typical_mass)) if v is not None) or "top_k / top_p / typical_mass"
+
+
+def request_filters(B, top_k=None, top_p=None, typical_mass=None, min_tokens=1):
+    """HOST tables of a request batch's filters: each argument one value for all requests or a list of B -> (k int32 [B, 2] = (top_k, min_tokens), mass fp32 [B, 2]
+    = (top_p, typical_mass), any_on); every row validated by `check_filter` (the message names the argument and the request)."""
+    B = int(B)
+    cols = []
+    for name, v in (("top_k", top_k), ("top_p", top_p), ("typical_mass", typical_mass), ("min_tokens", min_tokens)):
+        if isinstance(v, (list, tuple)):
+            if len(v) != B:
+                raise ValueError("%s must be one value or a list of %d (one per request), got %d" % (name, B, len(v)))
+            cols.append(list(v))
+        else:
+            cols.append([v] * B)
+    rows = []
+    for b in range(B):
+        try:
+            rows.append(check_filter(cols[0][b], cols[1][b], cols[2][b], cols[3][b]))
+        except ValueError as e:
+            raise ValueError("request %d: %s" % (b, e)) from None
+    k = torch.tensor([[r[0], r[3]] for r in rows], dtype=torch.int32)
+    mass = torch.tensor([[r[1], r[2]] for r in rows], dtype=torch.float32)
+    return k, mass, any(filter_on(r) for r in rows)
+
+
+class FilterTables:
+    """the DEVICE tables of a filtered request batch: k int32 [B, 2], mass fp32 [B, 2] (`request_filters`; `load` rewrites them in place, all a captured graph needs
+    to serve other filters) and, because the filtered tail of the request family is the stream form, the constant stream tables of every step of a batch whose
+    requests march in step: step [steps, B] = i, t_next [steps, B] = t_list[i + 1] (-1 from renoise_steps on: never renoises), active [B] = 1."""
+
+    def __init__(self, host, device, steps, renoise_steps, t_list):
+        B = host[0].size(0)
+        self.k, self.mass = host[0].to(device), host[1].to(device)
+        self.step = torch.arange(steps, dtype=torch.int32)[:, None].repeat(1, B).contiguous().to(device)
+        self.t_next = torch.tensor([float(t_list[i + 1]) if i < renoise_steps else -1.0 for i in range(steps)], dtype=torch.float32)[:, None].repeat(1, B).contiguous().to(device)
+        self.active = torch.ones(B, dtype=torch.int32, device=device)
+
+    def load(self, host):
+        self.k.copy_(host[0])
+        self.mass.copy_(host[1])
+
+
 def _weights_vector(v):
     if v is None:
         return None
@@ -346,7 +430,7 @@ def select_tokens(a, b=None, mask=None, flag=None, fill=-1, out=None):
 
 def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x, steps, renoise_steps, t_list, temperatures,
                  cfgs, device, noise="torch", seed=None, attn_weights=None, seed_dev=None, init_noise_buf=None, r_all=None, shard=None,
-                 ws=None, fused_tail=True, row_offset_dev=None, req=None, pin=None):
+                 ws=None, fused_tail=True, row_offset_dev=None, req=None, pin=None, filt=None):
     """cfgs: per-step list of (cfg_fp32, one_minus_cfg_fp32) or None (no guidance at that step).
     seed_dev / row_offset_dev / init_noise_buf / r_all: device-resident seed and row-offset words, a buffer for the start tokens
     and the [steps, B] timestep table (HIP-graph capture cannot upload from the host, see GraphSampler); ws: caller-owned
@@ -356,7 +440,9 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
     req (RequestTables; noise="philox" only): the B samples are independent requests -- seed, guidance pair and temperature per sample come from its device
     tables, `seed` / `shard` are unused, `temperatures` must be positive placeholders and `cfgs` only says whether guidance is on.
     pin=(keep, known) (noise="philox" only; int64 [B, H, W] each): after EVERY step's draw and renoise the tail writes known[row] wherever keep[row] == 0 -- the
-    known region of an editing request stays clean while the model denoises (paella_amd.editing.inpaint(pin="step"))."""
+    known region of an editing request stays clean while the model denoises (paella_amd.editing.inpaint(pin="step")).
+    filt (noise="philox" only): truncated sampling -- a `check_filter` tuple (one setting for the call) or, with `req`, a `FilterTables`.  Every step then takes the
+    logits forward plus the filtered tail: `fused_tail` is ignored, rows * L * 4 bytes of logits are written and read back per step."""
     explicit = isinstance(noise, dict)  # parity tests: {"init_noise": [B,H,W], "q": [rows,L] per step, "u": [B,H,W] per step}
     if not explicit and noise not in ("torch", "philox"):
         raise ValueError("noise must be 'torch', 'philox' or a dict of explicit noise tensors")
@@ -386,6 +472,13 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
         for name, t in zip(("keep", "known"), pin):
             if not torch.is_tensor(t) or t.dtype != torch.int64 or tuple(t.shape) != (B, H, W) or t.device.type != "cuda" or not t.is_contiguous():
                 raise ValueError("pin: %s must be a contiguous int64 HIP tensor of shape %s" % (name, (B, H, W)))
+    if filt is not None:
+        if not philox:
+            raise ValueError("top_k / top_p / typical_mass need noise='philox' (the counter-based sampling tail filters the draw)")
+        if any(t == 0 for t in temperatures[:steps]):
+            raise ValueError("top_k / top_p / typical_mass are not offered with a step temperature of 0 (the argmax extension)")
+        if isinstance(filt, FilterTables) != (req is not None):
+            raise ValueError("filt: one check_filter tuple for a plain call, a FilterTables with request tables")
     with torch.inference_mode():
         if req is not None:
             init_noise = start_tokens_requests(L, (B, H, W), req.seeds, out=init_noise_buf)
@@ -425,7 +518,7 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
         out = torch.empty(B, H, W, dtype=torch.int64, device=device)
         if r_all is None:
             r_all = timestep_table(t_list, steps, B, device)
-        fuse = philox and native and fused_tail  # head GEMM + tail in one launch: no logits tensor at all
+        fuse = philox and native and fused_tail and filt is None  # head GEMM + tail in one launch: no logits tensor at all (a filter needs the whole row)
         for i in range(steps):
             r = r_all[i]
             use_cfg = cfgs[i] is not None
@@ -479,20 +572,36 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
             elif renoise and noise == "torch":
                 mask_u = torch.rand(B, H, W, dtype=torch.float32, device=device)  # == torch.rand_like(x.float())
             if req is not None:
-                _tail_req(lc, lu, rows, L, H * W, req, i, init_noise if renoise else None, t_list[i + 1] if renoise else 0.0, out)
+                # (the stream form of the filtered tail wants its renoise source at every step; a step that does not renoise -- threshold -1 -- never reads it)
+                _tail_req(lc, lu, rows, L, H * W, req, i, init_noise if renoise or filt is not None else None, t_list[i + 1] if renoise else 0.0, out, filt=filt)
                 sampled = out
                 continue
             cfg, omc = cfgs[i] if use_cfg else (1.0, 0.0)
             _tail(lc, lu, rows, L, cfg, omc, temp if mode == 0 else 1.0, mode, noise_q, seed, i,
                   init_noise if renoise else None, mask_u, t_list[i + 1] if renoise else 0.0, out, seed_dev=seed_dev,
-                  row_offset=row_offset, row_offset_dev=row_offset_dev, pin=pin)
+                  row_offset=row_offset, row_offset_dev=row_offset_dev, pin=pin, filt=filt)
             sampled = out  # the tail never reads `sampled`, so one output buffer is enough (stream-ordered reuse)
     return sampled
 
 
+def _call_filter(noise, temperatures, top_k, top_p, typical_mass, min_tokens):
+    """the filter of a whole call: validated, None when nothing is on (the call then takes exactly the path it takes without these arguments)"""
+    f = check_filter(top_k, top_p, typical_mass, min_tokens)
+    if not filter_on(f):
+        return None
+    names = _filter_names(top_k, top_p, typical_mass)
+    if noise != "philox":
+        raise ValueError("%s needs noise='philox' (the counter-based sampling tail filters the draw)" % names)
+    if any(t == 0 for t in temperatures):
+        raise ValueError("%s is not offered with a step temperature of 0 (the argmax extension)" % names)
+    return f
+
+
 def sample(model, model_inputs, latent_shape, unconditional_inputs=None, steps=12, renoise_steps=11, temperature=(1.0, 0.2),
-           cfg=8.0, t_start=1.0, t_end=0.0, device="cuda", *, noise="torch", seed=None, seed_dev=None, attn_weights=None, shard=None, fused_tail=True):
+           cfg=8.0, t_start=1.0, t_end=0.0, device="cuda", *, noise="torch", seed=None, seed_dev=None, attn_weights=None, shard=None, fused_tail=True,
+           top_k=None, top_p=None, typical_mass=None, min_tokens=1):
     """Drop-in for reference src/utils.py:35 `sample` (same positional order and defaults).
+    top_k / top_p / typical_mass / min_tokens (noise="philox" only; `check_filter`): truncated sampling, one setting for the call -- see `_sample_core`.
     Keyword-only extensions: noise ("torch" = consume torch's generator exactly like the reference; "philox" = counter-based
     noise generated in the kernels, keyed by `seed` -- None draws a fresh seed from torch's generator), attn_weights
     (utils/modules.py:268), shard=(lo, total) for batch-sharded sampling (paella_amd.dist.sample_sharded), fused_tail (counter-based
@@ -511,13 +620,15 @@ def sample(model, model_inputs, latent_shape, unconditional_inputs=None, steps=1
     else:
         cfgs = [None] * steps
     return _sample_core(model, model_inputs, unconditional_inputs, latent_shape, None, steps, renoise_steps, t_list, temperatures,
-                        cfgs, device, noise=noise, seed=seed, seed_dev=seed_dev, attn_weights=attn_weights, shard=shard, fused_tail=fused_tail)
+                        cfgs, device, noise=noise, seed=seed, seed_dev=seed_dev, attn_weights=attn_weights, shard=shard, fused_tail=fused_tail,
+                        filt=_call_filter(noise, temperatures, top_k, top_p, typical_mass, min_tokens))
 
 
 def sample_distributed(model, model_inputs, unconditional_inputs, latent_shape, init_x=None, steps=12, renoise_steps=None,
                        temperature=(0.7, 0.3), cfg=(8.0, 8.0), t_start=1.0, t_end=0.0, sampling_conditional_steps=None, *,
-                       noise="torch", seed=None, attn_weights=None, shard=None, fused_tail=True, pin=None):
+                       noise="torch", seed=None, attn_weights=None, shard=None, fused_tail=True, pin=None, top_k=None, top_p=None, typical_mass=None, min_tokens=1):
     """Drop-in for reference src_distributed/utils.py:97 `sample` (init_x, cfg schedule, conditional-step cutoff).
+    top_k / top_p / typical_mass / min_tokens (noise="philox" only): truncated sampling, as `sample`.
     Keyword-only extension pin=(keep, known) (noise="philox" only): every step's tail re-imposes known where keep == 0, see `_sample_core`."""
     device = unconditional_inputs["byt5"].device
     if sampling_conditional_steps is None:
@@ -533,7 +644,8 @@ def sample_distributed(model, model_inputs, unconditional_inputs, latent_shape, 
             # `logits * cfgs[i] + logits_u * (1 - cfgs[i])` with a 0-dim fp32 tensor: (1 - cfg) is computed in fp32
             cfgs[i] = (float(sched[i]), float(1 - sched[i]))
     return _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x, steps, renoise_steps, t_list, temperatures,
-                        cfgs, device, noise=noise, seed=seed, attn_weights=attn_weights, shard=shard, fused_tail=fused_tail, pin=pin)
+                        cfgs, device, noise=noise, seed=seed, attn_weights=attn_weights, shard=shard, fused_tail=fused_tail, pin=pin,
+                        filt=_call_filter(noise, temperatures, top_k, top_p, typical_mass, min_tokens))
 
 
 def _request_schedule(steps, t_start, t_end, guided):
@@ -542,7 +654,7 @@ def _request_schedule(steps, t_start, t_end, guided):
 
 
 def sample_requests(model, model_inputs, unconditional_inputs, latent_shape, seeds, cfg=8.0, temperature=(1.0, 0.2), steps=12, renoise_steps=11,
-                    t_start=1.0, t_end=0.0, device="cuda", attn_weights=None, fused_tail=True):
+                    t_start=1.0, t_end=0.0, device="cuda", attn_weights=None, fused_tail=True, *, top_k=None, top_p=None, typical_mass=None, min_tokens=1):
     """B independent REQUESTS sampled as one batch (counter-based noise): request b has its own seed `seeds[b]`, guidance and temperature range, and its
     tokens are a function of the request alone -- every random number it draws is the one `sample(..., latent_shape=(1, H, W), noise="philox", seed=seeds[b])`
     draws, whatever slot it sits in and whoever shares the batch (the logits may still differ in their last bits with the batch size: the GEMMs split their
@@ -551,9 +663,12 @@ def sample_requests(model, model_inputs, unconditional_inputs, latent_shape, see
     attn_weights: one 1-D tensor for all requests (one vector per launch, as `sample`), or a LIST with one entry per request -- None, a vector (both sides of
     the guided step) or a pair (conditional, unconditional), either member None (`request_weight_pair`).  The list form runs on a `KeyWeights` table with one row
     per conditioning slot: request b's tokens are those of a call in which every request carries request b's weights, bit for bit, whatever its batch-mates
-    carry.  A guided list call needs the one-forward path (both conditioning sets with B samples each)."""
+    carry.  A guided list call needs the one-forward path (both conditioning sets with B samples each).
+    top_k / top_p / typical_mass / min_tokens: truncated sampling, each one value for all requests or a list with one per request (`request_filters`); request b
+    is filtered as `sample(..., seed=seeds[b], <its values>)` filters it.  With a filter on for anyone every step takes the logits forward plus the filtered tail."""
     B, H, W = (int(v) for v in latent_shape)
     host = request_tables(B, steps, seeds, cfg, temperature)
+    fhost = request_filters(B, top_k, top_p, typical_mass, min_tokens)
     if host[2] is not None and unconditional_inputs is None:
         raise TypeError("cfg=%r requires unconditional_inputs" % (cfg,))
     device = torch.device(device)
@@ -572,7 +687,8 @@ def sample_requests(model, model_inputs, unconditional_inputs, latent_shape, see
         attn_weights = _load_key_weights(KeyWeights(2 * B if guided else B, n_max, device), pairs,
                                          _request_keys(model, H, W, model_inputs, unconditional_inputs if guided else None), guided)
     return _sample_core(model, model_inputs, unconditional_inputs, (B, H, W), None, steps, renoise_steps, t_list, temps, cfgs, device, noise="philox", seed=0,
-                        attn_weights=attn_weights, fused_tail=fused_tail, req=RequestTables(host, device))
+                        attn_weights=attn_weights, fused_tail=fused_tail, req=RequestTables(host, device),
+                        filt=FilterTables(fhost, device, steps, renoise_steps, t_list) if fhost[2] else None)
 
 
 class GraphSampler:
@@ -587,6 +703,7 @@ class GraphSampler:
     inside the graph as functions of (seed, global row, step): `sampler(seed=s, shard=(lo, total))` returns exactly rows
     [lo, lo + B) of `sample(..., noise="philox", seed=s)` over the global batch (tests/test_gpu_sample.py).
     seed=None draws a fresh seed from torch's global CPU generator (one draw per call; see fresh_seed).
+    top_k / top_p / typical_mass / min_tokens (keyword-only): one truncation setting baked into the capture, as `sample` takes it.
 
     Staleness (the call site that reloads weights between sampling calls is src/train.py:40,64-69,76): a capture bakes raw pointers,
     host-side constants read from the weights (the VQGAN's ResBlock gammas) and the precision mode's kernel choice.  Every replay first compares the models'
@@ -594,9 +711,12 @@ class GraphSampler:
     default: the replay then equals a fresh eager call bit for bit) or raises a RuntimeError naming the cause (on_stale="raise")."""
 
     def __init__(self, model, model_inputs, unconditional_inputs, latent_shape, steps=12, renoise_steps=11, temperature=(1.0, 0.2),
-                 cfg=8.0, t_start=1.0, t_end=0.0, device="cuda", vqgan=None, attn_weights=None, on_stale="recapture"):
+                 cfg=8.0, t_start=1.0, t_end=0.0, device="cuda", vqgan=None, attn_weights=None, on_stale="recapture", *, top_k=None, top_p=None, typical_mass=None,
+                 min_tokens=1):
         if on_stale not in ("recapture", "raise"):
             raise ValueError("on_stale must be 'recapture' or 'raise'")
+        if not hasattr(self, "filt"):  # truncated sampling, one setting baked into the capture (GraphRequestSampler keeps device tables here instead)
+            self.filt = _call_filter("philox", linspace_schedule(temperature[0], temperature[1], steps), top_k, top_p, typical_mass, min_tokens)
         self.model, self.vqgan, self.device, self.on_stale = model, vqgan, torch.device(device), on_stale
         self.shape = tuple(int(v) for v in latent_shape)
         self.kw = dict(steps=steps, renoise_steps=renoise_steps, temperature=temperature, cfg=cfg, t_start=t_start, t_end=t_end)
@@ -671,7 +791,7 @@ class GraphSampler:
         init_x = self._init_x()
         toks = _sample_core(self.model, self.cond, self.uncond, self.shape, init_x, k["steps"], k["renoise_steps"], t_list, temps, cfgs,
                             self.device, noise="philox", seed=0, attn_weights=self.attn_weights, seed_dev=self.seed_dev,
-                            init_noise_buf=self.init_noise, r_all=self.r_all, ws=self.ws, row_offset_dev=self.row_offset_dev, pin=self._pin())
+                            init_noise_buf=self.init_noise, r_all=self.r_all, ws=self.ws, row_offset_dev=self.row_offset_dev, pin=self._pin(), filt=self.filt)
         toks = self._finish(toks)
         return toks if self.vqgan is None else (toks, self.vqgan.decode_indices(toks, ws=self.vq_ws))
 
@@ -741,11 +861,15 @@ class GraphRequestSampler(GraphSampler):
     eager `sample_requests` bit for bit.
     max_attn_weights=N (mutually exclusive with `attn_weights`, the one vector baked into the capture): the graph reads a `KeyWeights` table of N weights per
     conditioning slot, and `__call__(attn_weights=...)` rewrites it in place -- None (nobody weighted), one vector for all requests or a list with one entry
-    per request, as `sample_requests`; `captures` stays 1."""
+    per request, as `sample_requests`; `captures` stays 1.
+    filtering=True: the capture holds the logits forward plus the filtered tail and two device tables of per-request filters, every request off until
+    `__call__(top_k=, top_p=, typical_mass=, min_tokens=)` (one value or one per request) rewrites them in place; `captures` stays 1."""
 
     def __init__(self, model, model_inputs, unconditional_inputs, latent_shape, steps=12, renoise_steps=11, temperature=(1.0, 0.2), cfg=8.0, t_start=1.0,
-                 t_end=0.0, device="cuda", vqgan=None, attn_weights=None, on_stale="recapture", max_attn_weights=None):
+                 t_end=0.0, device="cuda", vqgan=None, attn_weights=None, on_stale="recapture", max_attn_weights=None, filtering=False):
         B = int(latent_shape[0])
+        # filtering=True: the capture holds the logits forward plus the filtered tail and two device tables (every request off until a call says otherwise)
+        self.filt = FilterTables(request_filters(B), torch.device(device), steps, renoise_steps, linspace_schedule(t_start, t_end, steps + 1)) if filtering else None
         if max_attn_weights is not None:  # (validated before anything touches a device)
             if attn_weights is not None:
                 raise ValueError("max_attn_weights (a per-request table) and attn_weights (one vector for the life of the capture) are mutually exclusive")
@@ -762,16 +886,22 @@ class GraphRequestSampler(GraphSampler):
         k = self.kw
         t_list, temps, cfgs = _request_schedule(k["steps"], k["t_start"], k["t_end"], self.req.pairs is not None)
         toks = _sample_core(self.model, self.cond, self.uncond, self.shape, None, k["steps"], k["renoise_steps"], t_list, temps, cfgs, self.device,
-                            noise="philox", seed=0, attn_weights=self.attn_weights, init_noise_buf=self.init_noise, r_all=self.r_all, ws=self.ws, req=self.req)
+                            noise="philox", seed=0, attn_weights=self.attn_weights, init_noise_buf=self.init_noise, r_all=self.r_all, ws=self.ws, req=self.req,
+                            filt=self.filt)
         return toks if self.vqgan is None else (toks, self.vqgan.decode_indices(toks, ws=self.vq_ws))
 
-    def __call__(self, seeds, cfg=None, temperature=None, model_inputs=None, unconditional_inputs=None, attn_weights=None):
+    def __call__(self, seeds, cfg=None, temperature=None, model_inputs=None, unconditional_inputs=None, attn_weights=None, *, top_k=None, top_p=None,
+                 typical_mass=None, min_tokens=1):
         """Replay for the requests `seeds[b]` (cfg / temperature: as `sample_requests`; None = the constructor's).  Outputs live in graph-owned buffers that the
         next replay overwrites.  attn_weights (a sampler built with max_attn_weights only): this replay's prompt weights, as `sample_requests` takes them; None =
-        nobody is weighted."""
+        nobody is weighted.  top_k / top_p / typical_mass / min_tokens (a sampler built with filtering=True only): this replay's filters, as `sample_requests`
+        takes them; the tables are rewritten in place, `captures` stays 1."""
         B, H, W = self.shape
         host = request_tables(B, self.kw["steps"], seeds, self.req_defaults["cfg"] if cfg is None else cfg,
                               self.req_defaults["temperature"] if temperature is None else temperature)
+        fhost = request_filters(B, top_k, top_p, typical_mass, min_tokens)
+        if self.filt is None and fhost[2]:
+            raise ValueError("%s per replay needs a sampler built with filtering=True" % _filter_names(top_k, top_p, typical_mass))
         if self.key_weights is None:
             if attn_weights is not None:
                 raise ValueError("attn_weights per replay needs a sampler built with max_attn_weights=N (this one baked the constructor's attn_weights into its capture)")
@@ -786,6 +916,8 @@ class GraphRequestSampler(GraphSampler):
         if unconditional_inputs is not None:
             self._copy_inputs(self.uncond, unconditional_inputs)
         self.req.load(host)
+        if self.filt is not None:
+            self.filt.load(fhost)
         self.graph.replay()
         return self.out
 
@@ -916,10 +1048,17 @@ class RequestStream:
     writes both of its slots' rows, count 0 included: a slot never inherits its predecessor's weights; `reset()` zeroes the counts.  A vector longer than N, or
     longer than that side's own shortest key sequence, is refused at admission.  Contract: a request admitted with weights `w` produces, at a given slot and B,
     exactly the tokens of a stream of the same shape built with stream-wide `attn_weights=w` serving that request -- bit for bit, independent of its
-    batch-mates' weights and of the tick it joined at.  With editing and / or max_cond_rows as well it is still one tick, one graph: `captures` stays 1."""
+    batch-mates' weights and of the tick it joined at.  With editing and / or max_cond_rows as well it is still one tick, one graph: `captures` stays 1.
+
+    filtering=True (truncated sampling; default False: exactly the entry points of today): the stream owns the two filter tables (int32 [B, 2] = (top_k, min_tokens),
+    fp32 [B, 2] = (top_p, typical_mass), every slot off) and a [B, H, W, num_labels] logits buffer; its captured tick is `request_step` -> the logits forward (guidance
+    folded through the head) -> the filtered stream tail, and `admit(top_k=, top_p=, typical_mass=, min_tokens=)` writes the slot's row, "off" included, so a slot
+    never inherits its predecessor's filter; `reset()` writes off everywhere.  A request admitted with a filter produces, at a given slot and B, the same tokens whatever
+    its batch-mates carry and whatever tick it joined at; one admitted with every filter off produces the tokens of a filtering=False stream (fused == unfused).  The
+    price is the materialised logits: B * H * W * num_labels * 4 bytes written and read back per tick.  Editing, max_cond_rows and prompt weights combine unchanged."""
 
     def __init__(self, model, model_inputs, unconditional_inputs, latent_shape, max_steps=12, guided=True, device="cuda", vqgan=None, attn_weights=None,
-                 on_stale="recapture", max_cond_rows=None, editing=False, max_attn_weights=None):
+                 on_stale="recapture", max_cond_rows=None, editing=False, max_attn_weights=None, filtering=False):
         if on_stale not in ("recapture", "raise"):
             raise ValueError("on_stale must be 'recapture' or 'raise'")
         if not isinstance(model, Paella):
@@ -980,6 +1119,13 @@ class RequestStream:
         self.key_weights = None if self.max_attn_weights is None else KeyWeights(nb, self.max_attn_weights, dev)
         if self.key_weights is not None:
             self.attn_weights = self.key_weights
+        # truncated sampling: the filter tables are stream state (every slot off), and the tick materialises the logits for the filtered stream tail
+        self.filtering = bool(filtering)
+        self.filter_k = self.filter_mass = self.logits = None
+        if self.filtering:
+            self.filter_k = torch.tensor([FILTER_OFF[0], FILTER_OFF[3]], dtype=torch.int32).repeat(B, 1).to(dev)
+            self.filter_mass = torch.tensor([FILTER_OFF[1], FILTER_OFF[2]], dtype=torch.float32).repeat(B, 1).to(dev)
+            self.logits = torch.empty(B, H, W, model.num_labels, dtype=torch.float32, device=dev)
         self.captures = 0
         self._capture()
 
@@ -1006,6 +1152,17 @@ class RequestStream:
                 _lib.check(_lib.load().paella_request_step(_lib.ptr(self.program), self.max_steps, _lib.ptr(self.pos), _lib.ptr(self.len), B, _lib.ptr(self.r),
                                                            _lib.ptr(self.temps), _lib.ptr(self.pairs), _lib.ptr(self.t_next), _lib.ptr(self.step),
                                                            _lib.ptr(self.active_dev), _lib.stream_ptr(self.device)))
+        if self.filtering:  # the logits forward (the guidance mix folded through the head: ONE [rows, L] tensor) + the filtered stream tail, in place as below
+            self.model.forward_prepared(self.tokens, self.r, self.cache, attn_weights=self.attn_weights, out=self.logits, ws=self.ws,
+                                        **({} if self.pairs is None else {"req_mix": self.pairs}))
+            pk, pt, po = (self.keep, self.known, self.pin_on) if self.editing else (None, None, None)
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.load().paella_sample_tail_stream_filter(_lib.ptr(self.logits), None, B * self.shape[1] * self.shape[2], self.model.num_labels, None,
+                                                                        _lib.ptr(self.temps), _lib.ptr(self.seeds), self.shape[1] * self.shape[2], _lib.ptr(self.step),
+                                                                        _lib.ptr(self.t_next), _lib.ptr(self.active_dev), _lib.ptr(self.random_x), _lib.ptr(pk), _lib.ptr(pt),
+                                                                        _lib.ptr(po), _lib.ptr(self.filter_k), _lib.ptr(self.filter_mass), _lib.ptr(self.tokens), None,
+                                                                        _lib.stream_ptr(self.device)))
+            return
         # in place: the token gather at the head of the forward and the token store at its tail are different kernels of one stream (as in _sample_core)
         self.model.forward_sample(self.tokens, self.r, self.cache, self.tokens, temperature=1.0, init_noise=self.random_x, attn_weights=self.attn_weights, ws=self.ws,
                                   req=(self.seeds, self.temps, self.pairs), stream=(self.step, self.t_next, self.active_dev),
@@ -1101,7 +1258,7 @@ class RequestStream:
         return check_weight_pair(request_weight_pair(attn_weights), keys, self.guided, self.max_attn_weights)
 
     def admit(self, model_inputs, unconditional_inputs=None, seed=None, steps=12, renoise_steps=None, temperature=(1.0, 0.2), cfg=8.0, t_start=1.0, t_end=0.0,
-              init_x=None, known=None, mask=None, image=None, pin="step", attn_weights=None):
+              init_x=None, known=None, mask=None, image=None, pin="step", attn_weights=None, *, top_k=None, top_p=None, typical_mass=None, min_tokens=1):
         """Put ONE request into a free slot; it runs from the next tick on.  Inputs: leading dimension 1, the stream's layout.  Schedule arguments as
         `request_program` (an unguided stream takes cfg=None); init_x int64 [H, W]: the tokens the request starts from instead of its seed's start tokens.
         Everything here is eager work on the current stream, ordered before the next tick: the conditioning of the one request is prepared straight into the
@@ -1111,9 +1268,14 @@ class RequestStream:
         start tokens of `seed`; pin="step" re-imposes the known tokens after every step, pin="final" after the request's last step only.  A request without them
         is a plain one: policy never, keep = ones.
         attn_weights (a stream built with max_attn_weights): this request's prompt weights -- None, one 1-D tensor for both sides, or a pair (conditional,
-        unconditional), either member None; written to the request's two rows of the stream's table (count 0 for an unweighted side)."""
+        unconditional), either member None; written to the request's two rows of the stream's table (count 0 for an unweighted side).
+        top_k / top_p / typical_mass / min_tokens (a stream built with filtering=True): this request's truncation filter (`check_filter`); every admit writes its
+        slot's row of the stream's filter tables, "off" included."""
         B, H, W = self.shape
         known, mask, image = self._check_edit(known, mask, image, pin)
+        filt = check_filter(top_k, top_p, typical_mass, min_tokens)
+        if filter_on(filt) and not self.filtering:
+            raise ValueError("%s needs a stream built with filtering=True (this one runs the fused tail, which sees no whole row)" % _filter_names(top_k, top_p, typical_mass))
         program, n = request_program(steps, renoise_steps, temperature, cfg, t_start, t_end, max_steps=self.max_steps, guided=self.guided)
         self._check_inputs(model_inputs, "model_inputs")
         if self.guided:
@@ -1144,6 +1306,9 @@ class RequestStream:
                 self.key_weights.set(b, weights[0])
                 if self.guided:
                     self.key_weights.set(B + b, weights[1])
+            if self.filtering:  # the slot's row, "off" included: its previous request leaves nothing behind
+                self.filter_k[b].copy_(torch.tensor([filt[0], filt[3]], dtype=torch.int32))
+                self.filter_mass[b].copy_(torch.tensor([filt[1], filt[2]], dtype=torch.float32))
             if self.editing:
                 if mask is None:
                     self.keep[b].fill_(1)
@@ -1177,6 +1342,10 @@ class RequestStream:
             self.pin_policy.zero_()
         if self.key_weights is not None:
             self.key_weights.clear()
+        if self.filtering:
+            self.filter_k[:, 0].fill_(FILTER_OFF[0])
+            self.filter_k[:, 1].fill_(FILTER_OFF[3])
+            self.filter_mass.fill_(1.0)
         self._pos, self._len, self._held = [0] * B, [0] * B, [False] * B
 
     def tick(self, graph=True):
