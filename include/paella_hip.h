@@ -371,6 +371,39 @@ int paella_unet_forward_sample_stream_kw(paella_unet* m, const int64_t* tokens, 
                                          int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Regional prompts: per-query key groups (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays 8).  In every
+ * entry point above a query sees every conditioning row of its slot.  The entry points below take two more DEVICE tables, both or
+ * neither (one alone is PAELLA_ERR_ARG), with one row per conditioning SLOT of the launch -- nb = B rows, 2 * n_unique in a guided step,
+ * conditional slots first, as for kw_table:
+ *   q_groups  int32 [nb, qg_pitch]  one bit mask per QUERY of every attention level, level-major inside a row: level l holds
+ *                                   (H / patch)(W / patch) / 4^l queries (row-major positions of that level's grid) at offset
+ *                                   off_l = sum_{j < l} (H / patch)(W / patch) / 4^j; qg_pitch >= Qtot = the sum over all levels.
+ *                                   An attention block of level l passes base + off_l with pitch qg_pitch to its kernel
+ *   k_groups  int32 [nb, kg_pitch]  one bit mask per conditioning ROW of the slot; kg_pitch >= S (the slot pitch)
+ * Conditioning key c of slot b is VISIBLE to query q iff q_groups[b][q] & k_groups[b][c] != 0; self keys are always visible.  An
+ * invisible key gets the score -inf before the softmax, like a row past cond_len.  What a bit means is the caller's business.
+ * cond_len, attn weights and kw_table keep their meaning: weights address the last n keys of the slot's own key sequence by index,
+ * visible or not, and act post-softmax on what is visible.  In every attention kernel: (1) a slot whose every conditioning key is
+ * visible to every query computes the bits of the launch without the tables; (2) a slot whose keys [n, cond_len[b]) are invisible to
+ * every query computes the bits of cond_len[b] = n -- but, unlike rows past cond_len, INVISIBLE ROWS ARE READ and multiplied by a zero
+ * probability: every row below cond_len must be finite; (3) k_groups entries at or beyond cond_len[b] are without effect, and no read
+ * leaves a row's pitch; (4) a query that sees no key at all (possible without self-attention only) gets a zero row, never NaN.
+ * fp32 kernels only: PAELLA_ERR_ARG for a model in the bf16 precision mode, for pitches smaller than Qtot / S, and for one table without
+ * the other -- all returned before anything is enqueued.  With both tables NULL each entry point IS the _kw one it extends.
+ * ---------------------------------------------------------------------------------------------- */
+int paella_unet_forward_shared_req_rg(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                      const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table,
+                                      const int* kw_len, int kw_pitch, const int* q_groups, int qg_pitch, const int* k_groups,
+                                      int kg_pitch, float* logits_out, void* ws, size_t ws_bytes, void* stream);
+int paella_unet_forward_sample_stream_rg(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                         const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table,
+                                         const int* kw_len, int kw_pitch, const int* q_groups, int qg_pitch, const int* k_groups,
+                                         int kg_pitch, const uint64_t* seeds, const float* temperature, int rows_per_sample,
+                                         const int* step, const float* t_next, const int* active, const int64_t* init_noise,
+                                         const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out,
+                                         void* ws, size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
  * Truncated sampling (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays 8): top-k, nucleus (top-p) and
  * typical filtering of the categorical draw, on materialised logits (the fused head sees 64 columns at a time and has no row
  * statistics; feed these from the logits-returning forwards).  Per row, with z_i = fp32(mix_i * (1 / T)):
@@ -481,6 +514,12 @@ int paella_op_attention_ragged(const float* q, const float* k_self, const float*
 int paella_op_attention_kw(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond,
                            float* out, int B, int nhead, int D, int Lq, int Lself, int Lcond, const int* cond_len,
                            const float* kw_table, const int* kw_len, int kw_pitch, void* stream);
+/* the same with per-query key groups (q_groups int32 [B, qg_pitch >= Lq], k_groups int32 [B, kg_pitch >= Lcond]: see "Regional prompts"); both NULL = the
+ * entry point above, one alone or a pitch too small = PAELLA_ERR_ARG */
+int paella_op_attention_rg(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond,
+                           float* out, int B, int nhead, int D, int Lq, int Lself, int Lcond, const int* cond_len,
+                           const float* kw_table, const int* kw_len, int kw_pitch, const int* q_groups, int qg_pitch,
+                           const int* k_groups, int kg_pitch, void* stream);
 
 #ifdef __cplusplus
 }

@@ -12,6 +12,8 @@ Public surface (mirrors the reference's Python API):
                               the batch and the graph with text-to-image ones; the sampling tail re-imposes their known tokens
     KeyWeights                (extension) per-request prompt weights: one row of post-softmax key multipliers per conditioning slot instead of one attn_weights
                               vector per launch; sample_requests / GraphRequestSampler / RequestStream.admit take attn_weights per request, per guidance side
+    RegionTables              (extension) regional prompts: per-query key groups in attention -- RequestStream(max_regions=R).admit(regions=[(inputs, mask), ...])
+                              gives a request a base prompt plus up to R prompts that apply where their mask says; region_query_groups builds the query side
     top_k / top_p / typical_mass / min_tokens
                               (extension, keyword-only) truncated sampling on sample, sample_distributed, GraphSampler, sample_requests (one value or one per
                               request), GraphRequestSampler(filtering=True) and RequestStream(filtering=True).admit: the draw is restricted to a subset of the
@@ -25,10 +27,10 @@ The opt-in bf16 fast mode is a per-model switch: `Paella.set_gemm_precision("bf1
 """
 from .conditioning import build_paella, embed_prompts, load_checkpoint, load_conditional_models
 from .editing import GraphInpainter, canvas, inpaint
-from .modules import CondCache, DenoiseUNet, KeyWeights, Paella, replace_attention_layers
+from .modules import CondCache, DenoiseUNet, KeyWeights, Paella, RegionTables, region_query_groups, replace_attention_layers
 from .sampling import GraphRequestSampler, GraphSampler, RequestStream, request_program, sample, sample_distributed, sample_requests, select_tokens
 from .vqgan import VectorQuantize, VQModel
 
 
-__all__ = ["Paella", "DenoiseUNet", "CondCache", "KeyWeights", "VQModel", "VectorQuantize", "sample", "sample_distributed", "sample_requests", "GraphSampler", "GraphRequestSampler", "RequestStream", "request_program",
+__all__ = ["Paella", "DenoiseUNet", "CondCache", "KeyWeights", "RegionTables", "region_query_groups", "VQModel", "VectorQuantize", "sample", "sample_distributed", "sample_requests", "GraphSampler", "GraphRequestSampler", "RequestStream", "request_program",
            "replace_attention_layers", "inpaint", "GraphInpainter", "canvas", "select_tokens", "load_conditional_models", "embed_prompts", "load_checkpoint", "build_paella"]

@@ -52,8 +52,9 @@ __device__ __forceinline__ const float* attn_key_weights(const float* key_weight
 
 // KSPLIT = true : one workgroup per 16 queries, its 4 waves split the key tiles (latency-bound small grids)
 // KSPLIT = false: one workgroup per 64 queries, each wave owns 16 queries and walks all key tiles (K/V re-read 16x less)
-template <int DT, bool KSPLIT>  // DT = head_dim / 16
-__global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
+// RG = true : the per-query key groups of AttnArgs::q_groups / k_groups (the masked form); false: the tables are never looked at
+template <int DT, bool KSPLIT, bool RG>  // DT = head_dim / 16
+__device__ __forceinline__ void attention_body(const AttnArgs a) {
     const int lane = threadIdx.x & 63;
     const int wave = threadIdx.x >> 6;
     const int q0 = KSPLIT ? blockIdx.x * 16 : (blockIdx.x * 4 + wave) * 16;
@@ -65,6 +66,14 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
     const int ntiles = (Lk + 15) / 16;
     int n_kw = a.n_kw;
     const float* const key_weights = attn_key_weights(a.key_weights, a.kw_table, a.kw_len, a.kw_pitch, b, Lk, n_kw);
+    // key groups: this lane's query mask, and the row of conditioning-key masks of the sample (entries [0, ncond) are read, clamped like the key rows)
+    const int ncond = Lk - a.Lself;
+    int qg = 0;
+    const int* kg_row = nullptr;
+    if constexpr (RG) {
+        qg = a.q_groups[(size_t)b * a.qg_pitch + min(q0 + r16, a.Lq - 1)];
+        kg_row = a.k_groups + (size_t)b * a.kg_pitch;
+    }
 
     // Q fragment: lane supplies Q[q0 + r16][16*j + 4*kq + e]  (rows past Lq are clamped; their outputs are not stored)
     f32x4 qf[DT];
@@ -88,7 +97,9 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
         return key < a.Lself ? vs_base + (size_t)key * a.ld_self : vc_base + (size_t)(key - a.Lself) * a.ld_cond;
     };
     // K operand: lane supplies K[kt*16 + r16][16*j + 4*kq + e]; V^T operand: V[kt*16 + 4*kq + e][j*16 + r16]
-    auto load_tile = [&](int kt, f32x4 (&kf)[DT], float (&vf)[DT][4]) {
+    // key groups: lane r16 also fetches the mask of key kt*16 + r16 (one load per lane and tile; process() hands it to the lanes that score the key)
+    auto load_tile = [&](int kt, f32x4 (&kf)[DT], float (&vf)[DT][4], int& kg) {
+        if constexpr (RG) kg = ncond > 0 ? kg_row[min(max(kt * 16 + r16 - a.Lself, 0), ncond - 1)] : 0;  // (wave-uniform test; a self key's entry is never looked at)
         const float* kp = krow(kt * 16 + r16) + kq * 4;
 #pragma unroll
         for (int j = 0; j < DT; ++j) kf[j] = *reinterpret_cast<const f32x4*>(kp + j * 16);
@@ -105,7 +116,7 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
     for (int j = 0; j < DT; ++j) oacc[j] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m_run = -INFINITY, l_run = 0.f;
 
-    auto process = [&](int kt, const f32x4 (&kf)[DT], const float (&vf)[DT][4]) {
+    auto process = [&](int kt, const f32x4 (&kf)[DT], const float (&vf)[DT][4], int kg) {
         f32x4 s = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int j = 0; j < DT; ++j)
@@ -117,17 +128,25 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int key = kt * 16 + kq * 4 + r;
-            p[r] = key < Lk ? s[r] * a.scale : -INFINITY;
+            bool visible = key < Lk;
+            if constexpr (RG) {
+                const int kgr = __shfl(kg, kq * 4 + r, 64);  // lane 4 kq + r holds the mask of this key (read by every lane: never under a divergent test)
+                visible = visible && (key < a.Lself || (qg & kgr) != 0);
+            }
+            p[r] = visible ? s[r] * a.scale : -INFINITY;
             mt = fmaxf(mt, p[r]);
         }
         mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
         mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
         const float m_new = fmaxf(m_run, mt);
-        const float alpha = exp_fast(m_run - m_new);  // first tile: exp(-inf) = 0
+        // key groups: a query may have met no visible key yet (m_new = -inf): exp(-inf - (-inf)) would be NaN, so the exponents are taken against 0 -- alpha and
+        // every p are then exp(-inf) = 0.  A finite m_new is used as it is: the same bits as the form without the tables
+        const float m_ref = RG && m_new == -INFINITY ? 0.f : m_new;
+        const float alpha = exp_fast(m_run - m_ref);  // first tile: exp(-inf) = 0
         float psum = 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            p[r] = exp_fast(p[r] - m_new);  // masked keys: exp(-inf) = 0, which also zeroes their (clamped) V rows
+            p[r] = exp_fast(p[r] - m_ref);  // masked keys: exp(-inf) = 0, which also zeroes their (clamped) V rows
             psum += p[r];
         }
         l_run = l_run * alpha + psum;  // per-lane partial; lanes of equal r16 are combined at the end
@@ -150,25 +169,26 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
 
     f32x4 kfA[DT], kfB[DT];
     float vfA[DT][4], vfB[DT][4];
+    int kgA = 0, kgB = 0;
     // this wave's key tiles: KSPLIT -> wave, wave + 4, ...; else all of them (software pipelined, two register sets)
     constexpr int KSTEP = KSPLIT ? 4 : 1;
     const int kt0 = KSPLIT ? wave : 0;
-    load_tile(kt0, kfA, vfA);
+    load_tile(kt0, kfA, vfA, kgA);
     for (int kt = kt0; kt < ntiles; kt += 2 * KSTEP) {
-        load_tile(kt + KSTEP, kfB, vfB);
+        load_tile(kt + KSTEP, kfB, vfB, kgB);
         __builtin_amdgcn_sched_barrier(0);
-        process(kt, kfA, vfA);
+        process(kt, kfA, vfA, kgA);
         if (kt + KSTEP < ntiles) {  // wave-uniform
-            load_tile(kt + 2 * KSTEP, kfA, vfA);
+            load_tile(kt + 2 * KSTEP, kfA, vfA, kgA);
             __builtin_amdgcn_sched_barrier(0);
-            process(kt + KSTEP, kfB, vfB);
+            process(kt + KSTEP, kfB, vfB, kgB);
         }
     }
     float l = l_run;
     l += __shfl_xor(l, 16, 64);
     l += __shfl_xor(l, 32, 64);
     if constexpr (!KSPLIT) {
-        const float inv1 = 1.0f / l;
+        const float inv1 = RG && !(l > 0.f) ? 0.f : 1.0f / l;  // key groups: a query that saw no key at all (Lself == 0 only) stores a zero row
         const int q1 = q0 + r16;
         if (q1 < a.Lq) {
             const size_t oo = ((size_t)b * a.Lq + q1) * a.ldo + h * D + kq * 4;
@@ -195,10 +215,10 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
     float l_all = 0.f, f[4];
 #pragma unroll
     for (int w = 0; w < 4; ++w) {
-        f[w] = exp_fast(mw[w] - m_all);  // empty waves: exp(-inf) = 0
+        f[w] = exp_fast(mw[w] - (RG && m_all == -INFINITY ? 0.f : m_all));  // empty waves: exp(-inf) = 0  (key groups: no wave saw a key -> against 0, as in the step)
         l_all += s_l[w][lane] * f[w];
     }
-    const float inv = 1.0f / l_all;
+    const float inv = RG && !(l_all > 0.f) ? 0.f : 1.0f / l_all;
     const int q = q0 + r16;
     // wave w finalises the output d-tiles j = w, w+4, ...
     for (int j = wave; j < DT; j += 4) {
@@ -212,6 +232,10 @@ __global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) {
         }
     }
 }
+template <int DT, bool KSPLIT>
+__global__ __launch_bounds__(256) void attention_kernel(AttnArgs a) { attention_body<DT, KSPLIT, false>(a); }
+template <int DT, bool KSPLIT>  // the masked form: per-query key groups
+__global__ __launch_bounds__(256) void attention_rg_kernel(AttnArgs a) { attention_body<DT, KSPLIT, true>(a); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // Large query counts (>= 256 queries per sample: 512 px grids and up, BASELINE configs 3-5 where attention is up to ~40 % of a
@@ -248,8 +272,9 @@ __device__ __forceinline__ void attn_dma16(__amdgpu_buffer_rsrc_t rsrc, float* l
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t attn_rsrc(const float* p, size_t bytes) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p), 0, (int)(bytes > 0x7fffffffull ? 0x7fffffffull : bytes), 0x00020000);
 }
-template <int DT, int STG>
-__global__ __launch_bounds__(256) void attention_lds_kernel(AttnArgs args) {
+template <int DT, int STG, bool RG>  // RG: per-query key groups, as in attention_body
+__device__ __forceinline__ void attention_lds_body(const AttnArgs& args) {
+    static_assert(!RG || STG != 0, "the masked form exists at the direct-to-LDS stagings only");
     constexpr int D = DT * 16, D4 = D / 4;
     constexpr int KTILE = 32;                          // keys per LDS stage
     constexpr int PITCH = STG == 2 ? D : D + 4;        // floats per LDS row
@@ -277,6 +302,13 @@ __global__ __launch_bounds__(256) void attention_lds_kernel(AttnArgs args) {
     const int ntiles = (Lk + KTILE - 1) / KTILE;
     int n_kw = args.n_kw;
     const float* const key_weights = attn_key_weights(args.key_weights, args.kw_table, args.kw_len, args.kw_pitch, b, Lk, n_kw);
+    // key groups: this lane's query mask; the row of conditioning-key masks of the sample (entries [0, ncond) are read, clamped like the key rows)
+    int qg = 0;
+    const int* kg_row = nullptr;
+    if constexpr (RG) {
+        qg = args.q_groups[(size_t)b * args.qg_pitch + min(q0 + r16, Lq - 1)];
+        kg_row = args.k_groups + (size_t)b * args.kg_pitch;
+    }
 
     f32x4 qf[DT];
     {
@@ -386,7 +418,8 @@ __global__ __launch_bounds__(256) void attention_lds_kernel(AttnArgs args) {
     float m_run = -INFINITY, l_run = 0.f;
 
     // second half of a 16-key step: online softmax over S^T (lane (r16, kq) holds the scores of query r16 against keys key0 + 4 * kq + 0..3), then O^T += V^T . P^T
-    auto softmax_pv = [&](int key0, const f32x4 s, const float* Vs) __attribute__((always_inline)) {
+    // key groups: `vis` bit r = key key0 + 4 kq + r is visible to this lane's query
+    auto softmax_pv = [&](int key0, const f32x4 s, const float* Vs, unsigned vis) __attribute__((always_inline)) {
         float vf[DT][4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
@@ -399,17 +432,20 @@ __global__ __launch_bounds__(256) void attention_lds_kernel(AttnArgs args) {
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
             const int key = key0 + kq * 4 + r;
-            p[r] = key < Lk ? s[r] * scale : -INFINITY;
+            bool visible = key < Lk;
+            if constexpr (RG) visible = visible && ((vis >> r) & 1u);
+            p[r] = visible ? s[r] * scale : -INFINITY;
             mt = fmaxf(mt, p[r]);
         }
         mt = fmaxf(mt, __shfl_xor(mt, 16, 64));
         mt = fmaxf(mt, __shfl_xor(mt, 32, 64));
         const float m_new = fmaxf(m_run, mt);
-        const float alpha = exp_fast(m_run - m_new);  // first tile: exp(-inf) = 0
+        const float m_ref = RG && m_new == -INFINITY ? 0.f : m_new;  // key groups: no visible key yet -> exponents against 0 (attention_body: the same guard)
+        const float alpha = exp_fast(m_run - m_ref);  // first tile: exp(-inf) = 0
         float psum = 0.f;
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
-            p[r] = exp_fast(p[r] - m_new);  // masked keys: exp(-inf) = 0, which also zeroes their (clamped) V rows
+            p[r] = exp_fast(p[r] - m_ref);  // masked keys: exp(-inf) = 0, which also zeroes their (clamped) V rows
             psum += p[r];
         }
         l_run = l_run * alpha + psum;
@@ -431,7 +467,7 @@ __global__ __launch_bounds__(256) void attention_lds_kernel(AttnArgs args) {
             for (int j = 0; j < DT; ++j) oacc[j] = __builtin_amdgcn_mfma_f32_16x16x4f32(vf[j][e], p[e], oacc[j], 0, 0, 0);
     };
     // a whole 32-key stage: both S chains first (two accumulators, alternating), then the two softmax / PV halves in key order
-    auto process32 = [&](int key0, const float* Ks, const float* Vs, bool second) __attribute__((always_inline)) {
+    auto process32 = [&](int key0, const float* Ks, const float* Vs, bool second, unsigned vis) __attribute__((always_inline)) {
         f32x4 kf0[DT], kf1[DT];
         const float* kp = Ks + kfrag;
 #pragma unroll
@@ -444,13 +480,35 @@ __global__ __launch_bounds__(256) void attention_lds_kernel(AttnArgs args) {
                 s0 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf0[j][e], qf[j][e], s0, 0, 0, 0);
                 s1 = __builtin_amdgcn_mfma_f32_16x16x4f32(kf1[j][e], qf[j][e], s1, 0, 0, 0);
             }
-        softmax_pv(key0, s0, Vs);
-        if (second) softmax_pv(key0 + 16, s1, Vs + 16 * PITCH);
+        softmax_pv(key0, s0, Vs, vis & 15u);
+        if (second) softmax_pv(key0 + 16, s1, Vs + 16 * PITCH, vis >> 4);
+    };
+    // key groups, one stage ahead like the tiles: lane l fetches the mask of key kt*32 + (l & 31) BEFORE the stage's DMA is issued, so that it has landed by the
+    // s_waitcnt that ends the previous stage (no wait of its own, and none behind the DMA of the stage after); stage_vis then turns it into this lane's 8 visibility
+    // bits (bit 4 i + r = key kt*32 + 16 i + 4 kq + r against this lane's query) with 8 cross-lane reads.  A stage of self keys alone skips both (wave-uniform).
+    int kg_next = 0;
+    unsigned vis = 0xffu;
+    auto load_groups = [&](int kt) __attribute__((always_inline)) {
+        if (kt * KTILE + KTILE > Lself && ncond > 0) kg_next = kg_row[min(max(kt * KTILE + (lane & 31) - Lself, 0), ncond - 1)];
+    };
+    auto stage_vis = [&](int kt) __attribute__((always_inline)) {
+        vis = 0xffu;
+        if (kt * KTILE + KTILE > Lself && ncond > 0) {
+            vis = 0u;
+#pragma unroll
+            for (int i = 0; i < 8; ++i) {
+                const int src = (i >> 2) * 16 + kq * 4 + (i & 3);
+                const int kgs = __shfl(kg_next, src, 64);  // (read by every lane: never under a divergent test)
+                vis |= (kt * KTILE + src < Lself || (qg & kgs) != 0) ? 1u << i : 0u;
+            }
+        }
     };
 
     if constexpr (STG != 0) {
+        if constexpr (RG) load_groups(0);
         dma_stage(0, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        if constexpr (RG) stage_vis(0);
     } else {
         load_tile(0);
         store_tile(0);
@@ -459,22 +517,24 @@ __global__ __launch_bounds__(256) void attention_lds_kernel(AttnArgs args) {
     for (int kt = 0; kt < ntiles; ++kt) {
         const int slot = kt & 1;
         if constexpr (STG != 0) {
+            if constexpr (RG) { if (kt + 1 < ntiles) load_groups(kt + 1); }
             if (kt + 1 < ntiles) dma_stage(kt + 1, slot ^ 1);  // lands while this stage computes; slot ^ 1 was released by the barrier that ended stage kt - 1
         } else {
             load_tile(min(kt + 1, ntiles - 1));  // the last iteration re-reads its own tile (L1/L2 hit, never consumed)
         }
         __builtin_amdgcn_sched_barrier(0);
         const float* Ks = smem + slot * STAGE;
-        process32(kt * KTILE, Ks, Ks + VT_OFF, kt * KTILE + 16 < Lk);  // (a fully masked second half is multiplied -- clamped rows -- and dropped)
+        process32(kt * KTILE, Ks, Ks + VT_OFF, kt * KTILE + 16 < Lk, vis);  // (a fully masked second half is multiplied -- clamped rows -- and dropped)
         __builtin_amdgcn_sched_barrier(0);
         if constexpr (STG != 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // this wave's part of the next stage has landed before the barrier that publishes it
         else store_tile(slot ^ 1);
+        if constexpr (RG) { if (kt + 1 < ntiles) stage_vis(kt + 1); }
         __syncthreads();
     }
     float l = l_run;
     l += __shfl_xor(l, 16, 64);
     l += __shfl_xor(l, 32, 64);
-    const float inv = 1.0f / l;
+    const float inv = RG && !(l > 0.f) ? 0.f : 1.0f / l;  // key groups: a query that saw no key at all (Lself == 0 only) stores a zero row
     const int q = q0 + r16;
     if (q < Lq) {
         const size_t oo = ((size_t)b * Lq + q) * ldo + h * D + kq * 4;
@@ -486,6 +546,10 @@ __global__ __launch_bounds__(256) void attention_lds_kernel(AttnArgs args) {
         }
     }
 }
+template <int DT, int STG>
+__global__ __launch_bounds__(256) void attention_lds_kernel(AttnArgs args) { attention_lds_body<DT, STG, false>(args); }
+template <int DT, int STG>  // the masked form: per-query key groups (product stagings only)
+__global__ __launch_bounds__(256) void attention_lds_rg_kernel(AttnArgs args) { attention_lds_body<DT, STG, true>(args); }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
 // OPT-IN bf16 fast mode (outside the fp32 parity contract), >= 256 queries: the LDS-staged kernel with both contractions on v_mfma_f32_16x16x16_bf16.
@@ -667,6 +731,13 @@ int launch_attention(const AttnArgs& a, hipStream_t st) {
         paella_set_error("attention: the per-sample key-weight table needs kw_table, kw_len and kw_pitch >= 1, and excludes the shared key_weights vector");
         return PAELLA_ERR_ARG;
     }
+    const bool rg = a.q_groups || a.k_groups;
+    if (rg && (!a.q_groups || !a.k_groups)) { paella_set_error("attention: q_groups and k_groups must be given together (one key-group table without the other)"); return PAELLA_ERR_ARG; }
+    if (rg && (a.qg_pitch < a.Lq || a.kg_pitch < a.Lcond)) {
+        paella_set_error("attention: key-group pitches too small (qg_pitch %d < Lq %d or kg_pitch %d < Lcond %d)", a.qg_pitch, a.Lq, a.kg_pitch, a.Lcond);
+        return PAELLA_ERR_ARG;
+    }
+    if (rg && a.q16) { paella_set_error("attention (bf16): the key-group tables are not offered in the bf16 fast mode"); return PAELLA_ERR_ARG; }
     if (a.q16) {  // opt-in bf16 fast mode (the model only asks for it at >= 256 queries)
         if (!a.out16 || (a.Lself && (!a.k_self16 || !a.v_self16)) || (a.ld16 & 7) || (a.Lcond && (a.ld_cond & 3)) || (a.ldo & 3) || a.D % 16) {
             paella_set_error("attention (bf16): needs out16, bf16 self K / V, ld16 %% 8 == 0");
@@ -693,6 +764,25 @@ int launch_attention(const AttnArgs& a, hipStream_t st) {
     const bool span32 = (size_t)a.Lself * (size_t)a.ld_self * 4 < ((size_t)1 << 31) && (size_t)a.Lcond * (size_t)a.ld_cond * 4 < ((size_t)1 << 31);
     const bool lds = !ksplit && variant != 1 && variant != 22 && span32;
     dim3 grid(ksplit ? (a.Lq + 15) / 16 : (a.Lq + 63) / 64, a.nhead, a.B);
+    // the masked form (per-query key groups): its own kernels, at the product staging only (variants 10 / 11 have no masked twin)
+#define ATT_RG_CASE(n)                                                                                                     \
+    case n:                                                                                                                \
+        if (ksplit) hipLaunchKernelGGL((attention_rg_kernel<n, true>), grid, dim3(256), 0, st, a);                         \
+        else if (lds) hipLaunchKernelGGL((attention_lds_rg_kernel<n, (n & 1) ? 2 : 1>), grid, dim3(256), 0, st, a);        \
+        else hipLaunchKernelGGL((attention_rg_kernel<n, false>), grid, dim3(256), 0, st, a);                               \
+        break;
+    if (rg) {
+        switch (a.D / 16) {
+            case 1:
+                if (ksplit) hipLaunchKernelGGL((attention_rg_kernel<1, true>), grid, dim3(256), 0, st, a);
+                else hipLaunchKernelGGL((attention_rg_kernel<1, false>), grid, dim3(256), 0, st, a);
+                break;
+            ATT_RG_CASE(2) ATT_RG_CASE(3) ATT_RG_CASE(4) ATT_RG_CASE(5) ATT_RG_CASE(6) ATT_RG_CASE(7) ATT_RG_CASE(8)
+        }
+        LAUNCH_CHECK_RET();
+        return PAELLA_OK;
+    }
+#undef ATT_RG_CASE
 #define ATT_CASE(n)                                                                                                     \
     case n:                                                                                                             \
         if (ksplit) hipLaunchKernelGGL((attention_kernel<n, true>), grid, dim3(256), 0, st, a);                         \

@@ -285,6 +285,18 @@ struct AttnArgs {
     const float* kw_table = nullptr;
     const int* kw_len = nullptr;
     int kw_pitch = 0;
+    // per-query key groups (regional prompts; both tables or neither): DEVICE tables q_groups int32 [B, qg_pitch >= Lq], one bit mask per query of sample b, and
+    // k_groups int32 [B, kg_pitch >= Lcond], one per CONDITIONING key of sample b's slot.  Conditioning key c is visible to query q iff
+    // q_groups[b][q] & k_groups[b][c] != 0; self keys are always visible; an invisible key gets score -inf before the softmax, like a key >= Lk.  What the bits mean
+    // is the host's business.  cond_len, key_weights and kw_table keep their meaning: the weights address the last n keys of the sample's own key sequence by index
+    // (visible or not) and act post-softmax.  A sample whose every key is visible computes the bits of the launch without the tables; conditioning keys [n, cond_len[b])
+    // invisible to every query compute the bits of cond_len[b] = n.  Invisible rows ARE read and multiplied by a zero probability (unlike the rows past cond_len,
+    // which are never read): K / V rows below cond_len must be FINITE.  k_groups entries at or beyond cond_len[b] are without effect; reads stay inside the row
+    // pitch.  A query that sees no key at all (possible only with Lself == 0) gets a zero row.  fp32 kernels only: refused together with q16.  null = the kernels
+    // without the tables, untouched
+    const int* q_groups = nullptr;
+    const int* k_groups = nullptr;
+    int qg_pitch = 0, kg_pitch = 0;
 };
 int launch_attention(const AttnArgs& a, hipStream_t stream);
 

@@ -735,6 +735,9 @@ struct FwdCtx {
     const float* kw_table;  // per-slot key weights (AttnArgs::kw_table / kw_len / kw_pitch) instead of attn_w, or null
     const int* kw_len;
     int kw_pitch;
+    const int* q_groups;  // per-query key groups (AttnArgs::q_groups / k_groups): [B, qg_pitch] with every level's queries in one row (level-major), [B, S]; or null
+    const int* k_groups;
+    int qg_pitch;
 };
 
 // ResBlock / FeedForwardBlock (reference src/modules.py:43-62, 82-96); x is updated in place
@@ -867,6 +870,13 @@ static int run_attn_block(FwdCtx& cx, const Block& b, float* x, int h, int w) {
     a.q16 = nullptr; a.k_self16 = nullptr; a.v_self16 = nullptr; a.ld16 = 0;
     a.cond_len = cx.cond_len;
     a.kw_table = cx.kw_table; a.kw_len = cx.kw_len; a.kw_pitch = cx.kw_pitch;
+    if (cx.q_groups) {  // this level's queries sit at off = sum over the finer levels of their query counts inside a row of the table
+        const int p = m->cfg.patch_size;
+        int off = 0;
+        for (int l = 0; l < b.level; ++l) off += ((cx.H / p) >> l) * ((cx.W / p) >> l);
+        a.q_groups = cx.q_groups + off; a.qg_pitch = cx.qg_pitch;
+        a.k_groups = cx.k_groups; a.kg_pitch = cx.S;
+    }
     if (attn16) {
         a.q16 = cx.f.g16; a.ld16 = nq;
         a.k_self16 = self ? cx.f.g16 + ch : nullptr; a.v_self16 = self ? cx.f.g16 + 2 * ch : nullptr;
@@ -909,13 +919,44 @@ static int kw_table_check(const char* who, const float* kw_table, const int* kw_
     if (kw_len && (!kw_table || kw_pitch < 1)) { paella_set_error("%s: kw_len needs kw_table and kw_pitch >= 1", who); return PAELLA_ERR_ARG; }
     return PAELLA_OK;
 }
+// Regional prompts: per-query key groups (AttnArgs::q_groups / k_groups) for every attention block of a forward.  q [nb, q_pitch] holds one row per conditioning
+// slot of the launch with the queries of all levels, level-major (level l at offset sum_{j<l} (H/patch)(W/patch)/4^j); k [nb, k_pitch] one mask per row of a slot.
+// q == nullptr = no tables.
+struct RgTable {
+    const int* q;  // DEVICE int32 [nb, q_pitch]
+    int q_pitch;
+    const int* k;  // DEVICE int32 [nb, k_pitch]
+    int k_pitch;
+};
+static int unet_query_total(const paella_unet* m, int H, int W) {
+    const int p = m->cfg.patch_size;
+    int tot = 0;
+    for (int l = 0; l < m->cfg.n_levels; ++l) tot += ((H / p) >> l) * ((W / p) >> l);
+    return tot;
+}
+// validated BEFORE anything is enqueued (the model may be null here: the checks that need it come after the ones that do not)
+static int rg_table_check(const char* who, const paella_unet* m, RgTable rg, int H, int W, int S) {
+    if (!rg.q && !rg.k) return PAELLA_OK;
+    if (!rg.q || !rg.k) { paella_set_error("%s: q_groups and k_groups must be given together (one key-group table without the other)", who); return PAELLA_ERR_ARG; }
+    if (rg.k_pitch < S || rg.q_pitch < 1) { paella_set_error("%s: key-group pitches too small (kg_pitch %d < S %d, or qg_pitch %d < 1)", who, rg.k_pitch, S, rg.q_pitch); return PAELLA_ERR_ARG; }
+    if (!m) { paella_set_error("%s: null model", who); return PAELLA_ERR_ARG; }
+    if (m->precision == 1) { paella_set_error("%s: the key-group tables are not offered in the bf16 precision mode", who); return PAELLA_ERR_ARG; }
+    const int p = m->cfg.patch_size, div = p << (m->cfg.n_levels - 1);
+    if (H <= 0 || W <= 0 || H % div || W % div) { paella_set_error("%s: token grid %dx%d must be a positive multiple of %d", who, H, W, div); return PAELLA_ERR_ARG; }
+    if (rg.q_pitch < unet_query_total(m, H, W)) {
+        paella_set_error("%s: qg_pitch %d smaller than the %d queries of all levels of a %dx%d grid", who, rg.q_pitch, unet_query_total(m, H, W), H, W);
+        return PAELLA_ERR_ARG;
+    }
+    return PAELLA_OK;
+}
 
 static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                              float mix_c, float mix_u, int H, int W, int S, const float* attn_weights,
                              int n_attn_weights, float* logits_out, const TailArgs* tail, void* ws, size_t ws_bytes, void* stream,
                              const float* mix_pairs = nullptr,    // request batch: a DEVICE table [n_unique, 2] of guidance pairs instead of (mix_c, mix_u)
                              const int* cond_len = nullptr,       // ragged conditioning: a DEVICE table [B] of conditioning rows per sample, S is then the slot pitch of `cond`
-                             KwTable kw = {nullptr, nullptr, 0}) {  // per-request prompt weights instead of attn_weights (which must then be null)
+                             KwTable kw = {nullptr, nullptr, 0},  // per-request prompt weights instead of attn_weights (which must then be null)
+                             RgTable rg = {nullptr, 0, nullptr, 0}) {  // regional prompts: per-query key groups (checked by the caller: rg_table_check)
     if (!m || !m->finalized) { paella_set_error("model not finalized"); return PAELLA_ERR_STATE; }
     if (!tokens || !r || (!logits_out && !tail)) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
     const paella_unet_config& c = m->cfg;
@@ -930,6 +971,7 @@ static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float*
     cx.m = m; cx.st = (hipStream_t)stream; cx.B = B; cx.H = H; cx.W = W; cx.S = S;
     cx.cond = (const float*)cond; cx.attn_w = attn_weights; cx.n_aw = attn_weights ? n_attn_weights : 0; cx.cond_len = cond_len;
     cx.kw_table = kw.len ? kw.table : nullptr; cx.kw_len = kw.len; cx.kw_pitch = kw.len ? kw.pitch : 0;
+    cx.q_groups = rg.q; cx.k_groups = rg.q ? rg.k : nullptr; cx.qg_pitch = rg.q_pitch;
     Arena a(ws, ws_bytes);
     carve_forward(m, a, B, H, W, S, cx.f);
     if (!a.ok || !ws) { paella_set_error("workspace too small (%zu needed, %zu given)", a.off, ws_bytes); return PAELLA_ERR_WORKSPACE; }
@@ -1176,6 +1218,19 @@ extern "C" int paella_unet_forward_shared_req_kw(paella_unet* m, const int64_t* 
     return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, nullptr, 0, logits_out, nullptr, ws, ws_bytes, stream, mix_pairs, cond_len,
                              KwTable{kw_table, kw_len, kw_pitch});
 }
+// Regional prompts: the most general logits entry point -- the _kw one plus the key-group tables (both NULL: exactly the _kw entry point)
+extern "C" int paella_unet_forward_shared_req_rg(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                 const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table, const int* kw_len,
+                                                 int kw_pitch, const int* q_groups, int qg_pitch, const int* k_groups, int kg_pitch, float* logits_out, void* ws,
+                                                 size_t ws_bytes, void* stream) {
+    if (!q_groups && !k_groups)
+        return paella_unet_forward_shared_req_kw(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, kw_table, kw_len, kw_pitch, logits_out, ws, ws_bytes, stream);
+    if (!logits_out) { paella_set_error("forward_shared_req_rg: null argument (logits_out)"); return PAELLA_ERR_ARG; }
+    RET_IF(kw_table_check("forward_shared_req_rg", kw_table, kw_len, kw_pitch));
+    RET_IF(rg_table_check("forward_shared_req_rg", m, RgTable{q_groups, qg_pitch, k_groups, kg_pitch}, H, W, S));
+    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, nullptr, 0, logits_out, nullptr, ws, ws_bytes, stream, mix_pairs, cond_len,
+                             KwTable{kw_table, kw_len, kw_pitch}, RgTable{q_groups, qg_pitch, k_groups, kg_pitch});
+}
 extern "C" int paella_unet_forward_shared_req(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                               const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
                                               float* logits_out, void* ws, size_t ws_bytes, void* stream) {
@@ -1250,7 +1305,7 @@ static int forward_sample_stream_impl(paella_unet* m, const int64_t* tokens, con
                                       int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights, KwTable kw, const uint64_t* seeds,
                                       const float* temperature, int rows_per_sample, const int* step, const float* t_next, const int* active,
                                       const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, void* ws,
-                                      size_t ws_bytes, void* stream) {
+                                      size_t ws_bytes, void* stream, RgTable rg = {nullptr, 0, nullptr, 0}) {
     if (!tokens_out || !seeds || !temperature) { paella_set_error("forward_sample_stream: null argument (tokens_out / seeds / temperature)"); return PAELLA_ERR_ARG; }
     RET_IF(stream_tables_check("forward_sample_stream", step, t_next, active, init_noise));
     RET_IF(pin_tables_check("forward_sample_stream", pin_keep, pin_tokens, pin_on, 0));
@@ -1263,7 +1318,7 @@ static int forward_sample_stream_impl(paella_unet* m, const int64_t* tokens, con
     a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.rows_per_sample = rows_per_sample;
     a.rq.step = step; a.rq.t_next = t_next; a.rq.active = active;
     a.pin_keep = pin_keep; a.pin_tokens = pin_tokens; a.pin_on = pin_on;
-    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, mix_pairs, cond_len, kw);
+    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, mix_pairs, cond_len, kw, rg);
 }
 extern "C" int paella_unet_forward_sample_stream_pin(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                                      const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights,
@@ -1282,6 +1337,22 @@ extern "C" int paella_unet_forward_sample_stream_kw(paella_unet* m, const int64_
     RET_IF(kw_table_check("forward_sample_stream_kw", kw_table, kw_len, kw_pitch));
     return forward_sample_stream_impl(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, nullptr, 0, KwTable{kw_table, kw_len, kw_pitch}, seeds, temperature,
                                       rows_per_sample, step, t_next, active, init_noise, pin_keep, pin_tokens, pin_on, tokens_out, ws, ws_bytes, stream);
+}
+// Regional prompts: the most general tick of a stream -- the _kw one plus the key-group tables (both NULL: exactly the _kw entry point)
+extern "C" int paella_unet_forward_sample_stream_rg(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                    const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table, const int* kw_len,
+                                                    int kw_pitch, const int* q_groups, int qg_pitch, const int* k_groups, int kg_pitch, const uint64_t* seeds,
+                                                    const float* temperature, int rows_per_sample, const int* step, const float* t_next, const int* active,
+                                                    const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
+                                                    int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+    if (!q_groups && !k_groups)
+        return paella_unet_forward_sample_stream_kw(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, kw_table, kw_len, kw_pitch, seeds, temperature,
+                                                    rows_per_sample, step, t_next, active, init_noise, pin_keep, pin_tokens, pin_on, tokens_out, ws, ws_bytes, stream);
+    RET_IF(kw_table_check("forward_sample_stream_rg", kw_table, kw_len, kw_pitch));
+    RET_IF(rg_table_check("forward_sample_stream_rg", m, RgTable{q_groups, qg_pitch, k_groups, kg_pitch}, H, W, S));
+    return forward_sample_stream_impl(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, nullptr, 0, KwTable{kw_table, kw_len, kw_pitch}, seeds, temperature,
+                                      rows_per_sample, step, t_next, active, init_noise, pin_keep, pin_tokens, pin_on, tokens_out, ws, ws_bytes, stream,
+                                      RgTable{q_groups, qg_pitch, k_groups, kg_pitch});
 }
 extern "C" int paella_unet_forward_sample_stream_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                                         const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights,
@@ -1606,7 +1677,8 @@ extern "C" int paella_op_grn_scale(const float* g, const float* gamma, float* sc
     return launch_grn_scale(g, gamma, scale, tmp, B, rows_per_sample, C, (hipStream_t)stream);
 }
 static int op_attention_impl(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond, float* out, int B, int nhead, int D,
-                             int Lq, int Lself, int Lcond, const int* cond_len, const float* key_weights, int n_kw, KwTable kw, void* stream) {
+                             int Lq, int Lself, int Lcond, const int* cond_len, const float* key_weights, int n_kw, KwTable kw, void* stream,
+                             RgTable rg = {nullptr, 0, nullptr, 0}) {
     AttnArgs a;
     const int ld = nhead * D;
     a.q = q; a.ldq = ld; a.k_self = k_self; a.v_self = v_self; a.ld_self = ld; a.k_cond = k_cond; a.v_cond = v_cond; a.ld_cond = ld;
@@ -1614,6 +1686,7 @@ static int op_attention_impl(const float* q, const float* k_self, const float* v
     a.scale = 1.0f / sqrtf((float)D); a.key_weights = key_weights; a.n_kw = key_weights ? n_kw : 0; a.out16 = nullptr;
     a.q16 = nullptr; a.k_self16 = nullptr; a.v_self16 = nullptr; a.ld16 = 0; a.cond_len = cond_len;
     a.kw_table = kw.table; a.kw_len = kw.len; a.kw_pitch = kw.pitch;
+    a.q_groups = rg.q; a.qg_pitch = rg.q_pitch; a.k_groups = rg.k; a.kg_pitch = rg.k_pitch;
     return launch_attention(a, (hipStream_t)stream);
 }
 extern "C" int paella_op_attention_ragged(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond,
@@ -1625,6 +1698,13 @@ extern "C" int paella_op_attention_ragged(const float* q, const float* k_self, c
 extern "C" int paella_op_attention_kw(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond, float* out, int B, int nhead,
                                       int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* kw_table, const int* kw_len, int kw_pitch, void* stream) {
     return op_attention_impl(q, k_self, v_self, k_cond, v_cond, out, B, nhead, D, Lq, Lself, Lcond, cond_len, nullptr, 0, KwTable{kw_table, kw_len, kw_pitch}, stream);
+}
+// per-query key groups on top of it (q_groups int32 [B, qg_pitch >= Lq], k_groups int32 [B, kg_pitch >= Lcond]; both NULL = the entry point above)
+extern "C" int paella_op_attention_rg(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond, float* out, int B, int nhead,
+                                      int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* kw_table, const int* kw_len, int kw_pitch,
+                                      const int* q_groups, int qg_pitch, const int* k_groups, int kg_pitch, void* stream) {
+    return op_attention_impl(q, k_self, v_self, k_cond, v_cond, out, B, nhead, D, Lq, Lself, Lcond, cond_len, nullptr, 0, KwTable{kw_table, kw_len, kw_pitch}, stream,
+                             RgTable{q_groups, qg_pitch, k_groups, kg_pitch});
 }
 extern "C" int paella_op_attention(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond,
                                    float* out, int B, int nhead, int D, int Lq, int Lself, int Lcond, const float* key_weights,

@@ -126,6 +126,85 @@ class KeyWeights:
         return self
 
 
+MAX_REGIONS = 30  # bit 0 = "everywhere", bit r + 1 = region r; the sign bit of the int32 masks stays unused
+
+
+def region_query_total(cfg, H, W):
+    """Qtot: the queries of every level of a model with constructor arguments `cfg` on an H x W token grid -- the row length of `RegionTables.q_groups`"""
+    p = int(cfg["patch_size"])
+    return sum(((H // p) >> l) * ((W // p) >> l) for l in range(len(cfg["c_hidden"])))
+
+
+def region_query_groups(masks, cfg, H, W):
+    """The query-side group masks of one request: bool masks [R, H, W] on the token grid (mask r = where region r's prompt applies) -> int32 [Qtot], level-major
+    (level l: the (H/patch >> l) x (W/patch >> l) positions row-major, after all finer levels).  Position (y, x) of level l stands for the patch * 2^l square
+    block of token positions under it and carries bit r + 1 iff ANY of them lies in mask r (OR-pooling), and always bit 0 ("everywhere").  Pure, runs anywhere."""
+    masks = torch.as_tensor(masks)
+    if masks.dim() != 3 or tuple(masks.shape[1:]) != (H, W) or masks.dtype.is_floating_point or masks.dtype.is_complex:
+        raise ValueError("regions: masks must be a bool / integer tensor [R, %d, %d] on the token grid" % (H, W))
+    R, p, n_levels = masks.size(0), int(cfg["patch_size"]), len(cfg["c_hidden"])
+    if R > MAX_REGIONS:
+        raise ValueError("regions: %d masks, at most %d fit the group bits" % (R, MAX_REGIONS))
+    if H % (p << (n_levels - 1)) or W % (p << (n_levels - 1)):
+        raise ValueError("regions: the token grid %dx%d must be a multiple of %d" % (H, W, p << (n_levels - 1)))
+    m = (masks != 0)
+    out = []
+    for l in range(n_levels):
+        f = p << l
+        g = torch.ones((H // f) * (W // f), dtype=torch.int32, device=m.device)
+        if R:
+            pooled = m.reshape(R, H // f, f, W // f, f).any(dim=4).any(dim=2).reshape(R, -1).to(torch.int32)
+            bits = torch.tensor([1 << (r + 1) for r in range(R)], dtype=torch.int32, device=m.device)
+            g = g | (pooled * bits[:, None]).sum(dim=0, dtype=torch.int32)
+        out.append(g)
+    return torch.cat(out)
+
+
+class RegionTables:
+    """Regional prompts: per-query key groups for every attention block of a forward (include/paella_hip.h, "Regional prompts") -- `q_groups` int32 [nb, Qtot], one
+    bit mask per query of every level (level-major, `region_query_groups` builds a row), and `k_groups` int32 [nb, S_slot], one per conditioning row of a slot; nb
+    is the conditioning batch of the forward (cond.B, conditional slots first).  Row c of slot b is visible to query q iff q_groups[b, q] & k_groups[b, c] != 0.
+    The default content is 1 everywhere: everything visible, which computes the bits of the forward without the tables.  Written in place, so a captured graph
+    that reads the tables serves other regions without a recapture.  Every conditioning row below the slot's count must be finite: invisible rows are read."""
+
+    def __init__(self, nb, Qtot, S_slot, device="cuda"):
+        nb, Qtot, S_slot = int(nb), int(Qtot), int(S_slot)
+        if nb < 1 or Qtot < 1 or S_slot < 1:
+            raise ValueError("RegionTables needs nb >= 1 slots, Qtot >= 1 queries and S_slot >= 1 rows per slot")
+        self.q_groups = torch.ones(nb, Qtot, dtype=torch.int32, device=device)
+        self.k_groups = torch.ones(nb, S_slot, dtype=torch.int32, device=device)
+
+    @property
+    def nb(self):
+        return self.q_groups.size(0)
+
+    def set(self, slot, q_row=None, k_row=None):
+        """slot's rows: q_row int32 [Qtot] and k_row int32 [n <= S_slot] (the rest of the row becomes 1); None = all ones.  In place, stream-ordered."""
+        slot = int(slot)
+        if not 0 <= slot < self.nb:
+            raise IndexError("RegionTables: slot %d outside 0 ... %d" % (slot, self.nb - 1))
+        if q_row is None:
+            self.q_groups[slot].fill_(1)
+        else:
+            q_row = torch.as_tensor(q_row)
+            if tuple(q_row.shape) != (self.q_groups.size(1),) or q_row.dtype != torch.int32:
+                raise ValueError("regions: q_row must be an int32 tensor [%d]" % self.q_groups.size(1))
+            self.q_groups[slot].copy_(q_row)
+        self.k_groups[slot].fill_(1)
+        if k_row is not None:
+            k_row = torch.as_tensor(k_row)
+            if k_row.dim() != 1 or k_row.numel() > self.k_groups.size(1) or k_row.dtype != torch.int32:
+                raise ValueError("regions: k_row must be an int32 tensor of at most %d entries" % self.k_groups.size(1))
+            self.k_groups[slot, :k_row.numel()].copy_(k_row)
+        return self
+
+    def clear(self):
+        """every slot: everything visible"""
+        self.q_groups.fill_(1)
+        self.k_groups.fill_(1)
+        return self
+
+
 class Paella(nn.Module):
     """Drop-in for reference `Paella` (src/modules.py:109). Same constructor arguments and defaults."""
 
@@ -379,6 +458,18 @@ class Paella(nn.Module):
             raise ValueError("attn_weights must be 1-D (utils/alter_attention.py:27)")
         return aw, None
 
+    def _regions(self, regions, nb, H, W, S):
+        """`regions` of a forward over `nb` conditioning slots of S rows on an H x W grid, checked (None passes through)"""
+        if regions is None:
+            return None
+        if not isinstance(regions, RegionTables):
+            raise ValueError("regions must be a paella_amd.RegionTables")
+        if self._precision == 1:
+            raise ValueError("regions are not offered in the bf16 precision mode (the bf16 attention core has no masked form)")
+        self._check_table(regions.q_groups, (nb, region_query_total(self._cfg, H, W)), torch.int32, "regions (RegionTables.q_groups: one row per conditioning slot)")
+        self._check_table(regions.k_groups, (nb, S), torch.int32, "regions (RegionTables.k_groups: one row per conditioning slot)")
+        return regions
+
     @staticmethod
     def _f32(t, name):
         if t is None:
@@ -483,12 +574,12 @@ class Paella(nn.Module):
         return out
 
     # ------------------------------------------------------------------ forward
-    def forward_prepared(self, x, r, cond, attn_weights=None, out=None, cfg_mix=None, ws=None, req_mix=None):
+    def forward_prepared(self, x, r, cond, attn_weights=None, out=None, cfg_mix=None, ws=None, req_mix=None, regions=None):
         """One denoising evaluation against a `CondCache` (see `_forward_prepared_raw`): logits with the reference's shape [B, num_labels, H, W], a channels-last
         view of the position-major buffer the kernels write."""
-        return self._forward_prepared_raw(x, r, cond, attn_weights=attn_weights, out=out, cfg_mix=cfg_mix, ws=ws, req_mix=req_mix).permute(0, 3, 1, 2)
+        return self._forward_prepared_raw(x, r, cond, attn_weights=attn_weights, out=out, cfg_mix=cfg_mix, ws=ws, req_mix=req_mix, regions=regions).permute(0, 3, 1, 2)
 
-    def _forward_prepared_raw(self, x, r, cond, attn_weights=None, out=None, cfg_mix=None, ws=None, req_mix=None):
+    def _forward_prepared_raw(self, x, r, cond, attn_weights=None, out=None, cfg_mix=None, ws=None, req_mix=None, regions=None):
         """One denoising evaluation against a `CondCache`, position-major result [B, H, W, num_labels].  x int64 [Bx,H,W]; r fp32 [Bx].
         Normally Bx == cond.B.  With Bx < cond.B (cond.B a multiple of Bx) the rows b, b + Bx, ... of the conditioning
         share the tokens and timestep of row b -- classifier-free guidance batches the conditional and unconditional pass
@@ -499,7 +590,9 @@ class Paella(nn.Module):
         position-major buffer the kernels write; pass `out` = a [B,H,W,num_labels] fp32 tensor to reuse memory).
         req_mix (request batch, instead of cfg_mix): an fp32 DEVICE tensor [Bx, 2] with one guidance pair per sample.
         attn_weights: a 1-D tensor (one vector for every sample) or a `KeyWeights` table with one row per conditioning slot (cond.B of them); with the table a
-        cfg_mix is uploaded as a [Bx, 2] pair table (a host-to-device copy, refused with a ValueError during a graph capture: capture such a step with req_mix)."""
+        cfg_mix is uploaded as a [Bx, 2] pair table (a host-to-device copy, refused with a ValueError during a graph capture: capture such a step with req_mix).
+        regions: a `RegionTables` with one row per conditioning slot (regional prompts: per-query key groups); attn_weights is then None or a `KeyWeights` table,
+        and a cfg_mix is uploaded as a pair table as above.  None = exactly the entry points of the call without it."""
         h = self._engine()
         lib = _lib.load()
         dev = self._device()
@@ -514,6 +607,9 @@ class Paella(nn.Module):
         if nu <= 0 or B % nu:
             raise ValueError("conditioning batch %d is not a multiple of the token batch %d" % (B, nu))
         aw, kw = self._key_weights(attn_weights, B)
+        rg = self._regions(regions, B, H, W, cond.S)
+        if rg is not None and aw is not None:
+            raise ValueError("regions take prompt weights as a KeyWeights table, not as one attn_weights vector")
         mix = (0.0, 0.0) if cfg_mix is None else (float(cfg_mix[0]), float(cfg_mix[1]))
         if cfg_mix is not None and (B != 2 * nu or mix == (0.0, 0.0)):
             raise ValueError("cfg_mix needs a conditioning batch of twice the token batch and a non-zero mix")
@@ -529,11 +625,17 @@ class Paella(nn.Module):
         lens = self._cond_lens(cond)
         with torch.cuda.device(dev):
             ws = self._workspace(lib.paella_unet_workspace_bytes(h, B, H, W, cond.S), ws)
-            if kw is not None:  # per-request prompt weights: the one logits entry point that takes the table (`lens` and the pair table nullable)
+            if kw is not None or rg is not None:  # per-request prompt weights / regions: the logits entry points that take the tables (`lens` and the pair table nullable)
                 if cfg_mix is not None and torch.cuda.is_current_stream_capturing():
                     raise ValueError("forward_prepared with a KeyWeights table turns cfg_mix into a pair table by a host-to-device copy, which a graph capture "
                                      "cannot hold: pass req_mix (an fp32 device tensor [Bx, 2]) instead of cfg_mix inside a capture")
                 pairs = req_mix if cfg_mix is None else torch.tensor([mix] * nu, dtype=torch.float32).to(dev)
+                if rg is not None:
+                    _lib.check(lib.paella_unet_forward_shared_req_rg(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S, _lib.ptr(lens),
+                                                                     None if kw is None else _lib.ptr(kw.buf), None if kw is None else _lib.ptr(kw.lens),
+                                                                     0 if kw is None else kw.pitch, _lib.ptr(rg.q_groups), rg.q_groups.size(1), _lib.ptr(rg.k_groups),
+                                                                     rg.k_groups.size(1), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+                    return out
                 _lib.check(lib.paella_unet_forward_shared_req_kw(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S, _lib.ptr(lens),
                                                                  _lib.ptr(kw.buf), _lib.ptr(kw.lens), kw.pitch, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
                                                                  _lib.stream_ptr(dev)))
@@ -558,7 +660,7 @@ class Paella(nn.Module):
         return out
 
     def forward_sample(self, x, r, cond, out, *, temperature, argmax=False, seed=0, seed_dev=None, offset=0, row_offset=0,
-                       row_offset_dev=None, init_noise=None, t_next=0.0, cfg_mix=None, attn_weights=None, ws=None, req=None, stream=None, pin=None):
+                       row_offset_dev=None, init_noise=None, t_next=0.0, cfg_mix=None, attn_weights=None, ws=None, req=None, stream=None, pin=None, regions=None):
         """One whole sampling step in the counter-based noise mode (src/utils.py:43-54): the denoiser evaluation with the head
         GEMM and the sampling tail FUSED -- the [B, num_labels, H, W] logits are never materialised.  x int64 [Bx,H,W], r [Bx];
         cfg_mix=(a, b) with cond.B == 2*Bx folds classifier-free guidance through the head (as forward_prepared); without it
@@ -573,7 +675,8 @@ class Paella(nn.Module):
         pin=(keep, known) (scalar form) or pin=(keep, known, pin_on) (with `stream`): editing requests -- int64 [Bx,H,W] DEVICE grids, keep 1 = regenerate / 0 = known;
         after the draw and the renoise the tail stores known wherever keep == 0, with `stream` only for the samples whose int32 [Bx] flag pin_on is set.  Categorical
         mode only; not offered with `req` alone.  Without `pin` the call reaches exactly the entry points it reaches without this argument.
-        attn_weights: a 1-D tensor, or (with `req`) a `KeyWeights` table with one row per conditioning slot (cond.B of them)."""
+        attn_weights: a 1-D tensor, or (with `req`) a `KeyWeights` table with one row per conditioning slot (cond.B of them).
+        regions (with `stream` only): a `RegionTables` with one row per conditioning slot -- regional prompts; attn_weights is then None or a `KeyWeights` table."""
         h = self._engine()
         lib = _lib.load()
         dev = self._device()
@@ -615,9 +718,21 @@ class Paella(nn.Module):
         aw, kw = self._key_weights(attn_weights, B, one_d=False)
         if kw is not None and req is None:
             raise ValueError("forward_sample takes a KeyWeights table for attn_weights only with the request tables (req=...); the scalar form takes one 1-D vector")
+        rg = self._regions(regions, B, H, W, cond.S)
+        if rg is not None and (stream is None or aw is not None):
+            raise ValueError("forward_sample takes regions only with the stream tables (stream=...), and prompt weights next to them as a KeyWeights table")
         lens = self._cond_lens(cond)
         with torch.cuda.device(dev):
             ws = self._workspace(lib.paella_unet_workspace_bytes(h, B, H, W, cond.S), ws)
+            if rg is not None:  # regional prompts: the most general stream tick (`lens`, the key-weight table and the pin tables nullable)
+                pk, pt, po = (None, None, None) if pin is None else pin
+                _lib.check(lib.paella_unet_forward_sample_stream_rg(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S,
+                                                                    _lib.ptr(lens), None if kw is None else _lib.ptr(kw.buf), None if kw is None else _lib.ptr(kw.lens),
+                                                                    0 if kw is None else kw.pitch, _lib.ptr(rg.q_groups), rg.q_groups.size(1), _lib.ptr(rg.k_groups),
+                                                                    rg.k_groups.size(1), _lib.ptr(seeds), _lib.ptr(temps), H * W, _lib.ptr(stream[0]), _lib.ptr(stream[1]),
+                                                                    _lib.ptr(stream[2]), _lib.ptr(init_noise), _lib.ptr(pk), _lib.ptr(pt), _lib.ptr(po), _lib.ptr(out),
+                                                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+                return out
             if kw is not None:  # per-request prompt weights: one entry point per form, `lens` (ragged conditioning) and the pin tables nullable
                 pk, pt, po = (None, None, None) if pin is None else pin
                 if stream is not None:

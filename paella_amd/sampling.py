@@ -20,7 +20,7 @@ Extension (not reference behaviour): a step temperature of 0 selects 
 import torch
 
 from . import _lib
-from .modules import CondCache, KeyWeights, Paella
+from .modules import MAX_REGIONS, CondCache, KeyWeights, Paella, RegionTables, region_query_groups, region_query_total
 
 
 def linspace_schedule(start, end, n):
@@ -1002,6 +1002,20 @@ def check_max_attn_weights(n):
     return n
 
 
+def check_max_regions(n, max_cond_rows, attn_weights, model):
+    """`max_regions=R` of a stream: 1 ... 30 region prompts per request, on a ragged stream (the region rows sit behind the base rows of a slot), without the
+    stream-wide weight vector (the entry points that take the group tables take prompt weights as a table) and outside the bf16 precision mode"""
+    if isinstance(n, bool) or not isinstance(n, int) or not 1 <= n <= MAX_REGIONS:
+        raise ValueError("max_regions must be None or an integer 1 ... %d, got %r" % (MAX_REGIONS, n))
+    if max_cond_rows is None:
+        raise ValueError("max_regions needs max_cond_rows: the rows of a request's regions go behind its base rows in a slot of max_cond_rows rows")
+    if attn_weights is not None:
+        raise ValueError("max_regions excludes the stream-wide attn_weights vector: give prompt weights per request (max_attn_weights=N)")
+    if model.get_gemm_precision() == "bf16":
+        raise ValueError("max_regions is not offered in the bf16 precision mode (the bf16 attention core has no masked form)")
+    return n
+
+
 def check_request_rows(rows, max_cond_rows, what):
     """a request's conditioning rows (ByT5 length + clip + any number of clip_image) must be 1 ... max_cond_rows"""
     if not 1 <= rows <= max_cond_rows:
@@ -1055,10 +1069,20 @@ class RequestStream:
     folded through the head) -> the filtered stream tail, and `admit(top_k=, top_p=, typical_mass=, min_tokens=)` writes the slot's row, "off" included, so a slot
     never inherits its predecessor's filter; `reset()` writes off everywhere.  A request admitted with a filter produces, at a given slot and B, the same tokens whatever
     its batch-mates carry and whatever tick it joined at; one admitted with every filter off produces the tokens of a filtering=False stream (fused == unfused).  The
-    price is the materialised logits: B * H * W * num_labels * 4 bytes written and read back per tick.  Editing, max_cond_rows and prompt weights combine unchanged."""
+    price is the materialised logits: B * H * W * num_labels * 4 bytes written and read back per tick.  Editing, max_cond_rows and prompt weights combine unchanged.
+
+    max_regions=R (regional prompts, 1 ... 30; needs max_cond_rows, and excludes the stream-wide `attn_weights` vector -- use max_attn_weights): the stream owns a
+    `RegionTables` for its conditioning slots and its tick -- fused or filtered -- runs the masked attention kernels through the `_rg` entry points.
+    `admit(regions=[(inputs_r, mask_r), ...])` gives the request up to R more prompts next to `model_inputs`, which stays the base prompt, visible everywhere:
+    region r's rows are prepared into the conditional slot behind the base rows (and behind the regions before it), carry group bit r + 1, and are visible to the
+    positions of every level whose patch * 2^level block of token positions touches mask_r (`region_query_groups`).  Base rows, every row of the unconditional
+    side and every query carry bit 0.  Base + region rows must fit max_cond_rows.  Every admit writes both of its slots' rows of both tables, the all-visible
+    default included, so a slot never inherits its predecessor's regions; `reset()` restores the default.  Contracts: a request's tokens at a given slot and B do
+    not depend on its batch-mates' regions or on the tick it joined at; a request admitted with regions=None produces the tokens of the same stream built
+    without max_regions; a region whose mask is all zero changes nothing.  `captures` stays 1.  Not offered in the bf16 precision mode."""
 
     def __init__(self, model, model_inputs, unconditional_inputs, latent_shape, max_steps=12, guided=True, device="cuda", vqgan=None, attn_weights=None,
-                 on_stale="recapture", max_cond_rows=None, editing=False, max_attn_weights=None, filtering=False):
+                 on_stale="recapture", max_cond_rows=None, editing=False, max_attn_weights=None, filtering=False, max_regions=None):
         if on_stale not in ("recapture", "raise"):
             raise ValueError("on_stale must be 'recapture' or 'raise'")
         if not isinstance(model, Paella):
@@ -1072,6 +1096,7 @@ class RequestStream:
         if max_attn_weights is not None and attn_weights is not None:
             raise ValueError("max_attn_weights (per-request weights, given to admit) and attn_weights (one vector for the life of the stream) are mutually exclusive")
         self.max_attn_weights = None if max_attn_weights is None else check_max_attn_weights(max_attn_weights)
+        self.max_regions = None if max_regions is None else check_max_regions(max_regions, max_cond_rows, attn_weights, model)
         if B <= 0 or self.max_steps <= 0:
             raise ValueError("a request stream needs B > 0 and max_steps > 0")
         if model_inputs is None or (self.guided and unconditional_inputs is None):
@@ -1119,6 +1144,8 @@ class RequestStream:
         self.key_weights = None if self.max_attn_weights is None else KeyWeights(nb, self.max_attn_weights, dev)
         if self.key_weights is not None:
             self.attn_weights = self.key_weights
+        # regional prompts: the key-group tables are stream state (everything visible until a request brings regions); the tick reads them through the _rg entry points
+        self.regions = None if self.max_regions is None else RegionTables(nb, region_query_total(model._cfg, H, W), self.S, dev)
         # truncated sampling: the filter tables are stream state (every slot off), and the tick materialises the logits for the filtered stream tail
         self.filtering = bool(filtering)
         self.filter_k = self.filter_mass = self.logits = None
@@ -1154,7 +1181,7 @@ class RequestStream:
                                                            _lib.ptr(self.active_dev), _lib.stream_ptr(self.device)))
         if self.filtering:  # the logits forward (the guidance mix folded through the head: ONE [rows, L] tensor) + the filtered stream tail, in place as below
             self.model.forward_prepared(self.tokens, self.r, self.cache, attn_weights=self.attn_weights, out=self.logits, ws=self.ws,
-                                        **({} if self.pairs is None else {"req_mix": self.pairs}))
+                                        **({} if self.pairs is None else {"req_mix": self.pairs}), **({} if self.regions is None else {"regions": self.regions}))
             pk, pt, po = (self.keep, self.known, self.pin_on) if self.editing else (None, None, None)
             with torch.cuda.device(self.device):
                 _lib.check(_lib.load().paella_sample_tail_stream_filter(_lib.ptr(self.logits), None, B * self.shape[1] * self.shape[2], self.model.num_labels, None,
@@ -1166,7 +1193,7 @@ class RequestStream:
         # in place: the token gather at the head of the forward and the token store at its tail are different kernels of one stream (as in _sample_core)
         self.model.forward_sample(self.tokens, self.r, self.cache, self.tokens, temperature=1.0, init_noise=self.random_x, attn_weights=self.attn_weights, ws=self.ws,
                                   req=(self.seeds, self.temps, self.pairs), stream=(self.step, self.t_next, self.active_dev),
-                                  **({"pin": (self.keep, self.known, self.pin_on)} if self.editing else {}))
+                                  **({"pin": (self.keep, self.known, self.pin_on)} if self.editing else {}), **({} if self.regions is None else {"regions": self.regions}))
 
     _state = GraphSampler._state
 
@@ -1257,8 +1284,42 @@ class RequestStream:
         keys = (min_attention_keys(self.model._cfg, H, W, rows(model_inputs)), min_attention_keys(self.model._cfg, H, W, rows(unconditional_inputs)) if self.guided else None)
         return check_weight_pair(request_weight_pair(attn_weights), keys, self.guided, self.max_attn_weights)
 
+    def _check_regions(self, regions, model_inputs):
+        """the `regions` of `admit`, validated before anything touches the stream -> [(inputs_r, rows_r)], bool masks [R, H, W] on the host (None, None without)"""
+        if regions is None:
+            return None, None
+        B, H, W = self.shape
+        if self.max_regions is None:
+            raise ValueError("regions need a stream built with max_regions=R (and max_cond_rows)")
+        if self.model.get_gemm_precision() == "bf16":
+            raise ValueError("regions are not offered in the bf16 precision mode")
+        regions = list(regions)
+        if len(regions) > self.max_regions:
+            raise ValueError("regions: %d given, the stream admits at most %d (max_regions)" % (len(regions), self.max_regions))
+        total, plan, masks = _cond_seq_len(self.model, model_inputs), [], []
+        for i, item in enumerate(regions):
+            if not isinstance(item, (tuple, list)) or len(item) != 2 or not isinstance(item[0], dict):
+                raise ValueError("regions: entry %d must be a pair (inputs, mask)" % i)
+            inputs, m = item
+            if not torch.is_tensor(m) or tuple(m.shape) != (H, W) or m.dtype.is_floating_point or m.dtype.is_complex:
+                raise ValueError("regions: the mask of region %d must be an integer or bool tensor [%d, %d] on the token grid (1 = the prompt applies here)" % (i, H, W))
+            for k in ("byt5", "clip", "clip_image"):
+                v = inputs.get(k)
+                for t in ([] if v is None else v if isinstance(v, (list, tuple)) else [v]):
+                    if t.size(0) != 1:
+                        raise ValueError("regions: region %d takes the inputs of ONE prompt (leading dimension 1), got %d for %s" % (i, t.size(0), k))
+            rows = _cond_seq_len(self.model, inputs)
+            if rows < 1:
+                raise ValueError("regions: region %d has no conditioning rows" % i)
+            total += rows
+            plan.append((inputs, rows))
+            masks.append((m != 0).cpu())
+        if total > self.max_cond_rows:
+            raise ValueError("regions: %d base + region conditioning rows, the stream's slots hold %d (max_cond_rows)" % (total, self.max_cond_rows))
+        return plan, (torch.stack(masks) if masks else torch.zeros(0, H, W, dtype=torch.bool))
+
     def admit(self, model_inputs, unconditional_inputs=None, seed=None, steps=12, renoise_steps=None, temperature=(1.0, 0.2), cfg=8.0, t_start=1.0, t_end=0.0,
-              init_x=None, known=None, mask=None, image=None, pin="step", attn_weights=None, *, top_k=None, top_p=None, typical_mass=None, min_tokens=1):
+              init_x=None, known=None, mask=None, image=None, pin="step", attn_weights=None, *, top_k=None, top_p=None, typical_mass=None, min_tokens=1, regions=None):
         """Put ONE request into a free slot; it runs from the next tick on.  Inputs: leading dimension 1, the stream's layout.  Schedule arguments as
         `request_program` (an unguided stream takes cfg=None); init_x int64 [H, W]: the tokens the request starts from instead of its seed's start tokens.
         Everything here is eager work on the current stream, ordered before the next tick: the conditioning of the one request is prepared straight into the
@@ -1270,8 +1331,12 @@ class RequestStream:
         attn_weights (a stream built with max_attn_weights): this request's prompt weights -- None, one 1-D tensor for both sides, or a pair (conditional,
         unconditional), either member None; written to the request's two rows of the stream's table (count 0 for an unweighted side).
         top_k / top_p / typical_mass / min_tokens (a stream built with filtering=True): this request's truncation filter (`check_filter`); every admit writes its
-        slot's row of the stream's filter tables, "off" included."""
+        slot's row of the stream's filter tables, "off" included.
+        regions (a stream built with max_regions): [(inputs_r, mask_r), ...] -- more prompts of this request, each a conditioning dict of ONE prompt and a bool /
+        integer mask [H, W] (1 = the prompt applies here); `model_inputs` stays the base prompt, visible everywhere.  Masks may overlap; an all-zero mask is a
+        no-op.  The unconditional side is never regional."""
         B, H, W = self.shape
+        region_plan, region_masks = self._check_regions(regions, model_inputs)
         known, mask, image = self._check_edit(known, mask, image, pin)
         filt = check_filter(top_k, top_p, typical_mass, min_tokens)
         if filter_on(filt) and not self.filtering:
@@ -1301,6 +1366,24 @@ class RequestStream:
                 slot = {} if self.cache.lens is None else dict(slot_rows=self.S, lens_out=self.cache.lens[row:row + 1])
                 self.model.prepare_cond(**{k: inputs.get(k) for k in ("byt5", "clip", "clip_image")}, ws=self.ws, out=self.cache.buf[row * nbytes:(row + 1) * nbytes],
                                         **slot)
+            if self.regions is not None:  # both slots' rows of both tables, the all-visible default included: nothing is inherited
+                k_row = None
+                if region_plan:
+                    # region r's rows behind the base rows (and the regions before it): the preparation writes S rows from ANY row offset of the slot, and the slot's
+                    # count becomes the total.  Conditioning rows are per-row functions of their inputs, so these are the rows of the prompt prepared alone
+                    row_bytes, off = nbytes // self.S, _cond_seq_len(self.model, model_inputs)
+                    k_row = [1] * off
+                    scratch_len = torch.zeros(1, dtype=torch.int32, device=self.device)
+                    for i, (inputs, rows) in enumerate(region_plan):
+                        self.model.prepare_cond(**{k: inputs.get(k) for k in ("byt5", "clip", "clip_image")}, ws=self.ws,
+                                                out=self.cache.buf[b * nbytes + off * row_bytes:b * nbytes + (off + rows) * row_bytes], slot_rows=rows, lens_out=scratch_len)
+                        k_row += [1 << (i + 1)] * rows
+                        off += rows
+                    self.cache.lens[b].fill_(off)
+                    k_row = torch.tensor(k_row, dtype=torch.int32)
+                self.regions.set(b, None if not region_plan else region_query_groups(region_masks, self.model._cfg, H, W), k_row)
+                if self.guided:
+                    self.regions.set(B + b)
             start_tokens(self.model.num_labels, (1, H, W), seed, self.device, out=self.random_x[b:b + 1])
             if self.key_weights is not None:  # both rows, count 0 included: the slot's previous request leaves nothing behind
                 self.key_weights.set(b, weights[0])
@@ -1342,6 +1425,8 @@ class RequestStream:
             self.pin_policy.zero_()
         if self.key_weights is not None:
             self.key_weights.clear()
+        if self.regions is not None:
+            self.regions.clear()
         if self.filtering:
             self.filter_k[:, 0].fill_(FILTER_OFF[0])
             self.filter_k[:, 1].fill_(FILTER_OFF[3])
