@@ -435,6 +435,58 @@ int paella_sample_tail_stream_filter(const float* logits_c, const float* logits_
                                      const int64_t* pin_tokens, const int* pin_on, const int* filter_k, const float* filter_mass,
                                      int64_t* tokens_out, int64_t* sampled_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Confidence-ordered renoise and per-token confidence maps (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays
+ * 8).  Two additions, both categorical mode and in-kernel Philox noise only.
+ * (1) Statistics of the draw.  With z, A, m and p = softmax(z) over A as under "Truncated sampling" (A = every label unless top_k is on),
+ *     S = sum_A exp(z - m), E = sum_A (z - m) exp(z - m) and t the drawn label (always in A):
+ *       logprob_out[row] = (z_t - m) - log S        entropy_out[row] = log S - E / S         fp32 [rows] each, either may be NULL
+ *     from the sums the filter kernel forms, in their fixed order.  A row the filter would not filter (a NaN, no finite maximum) reports
+ *     -inf / NaN.  Asking for them never changes a token: the draw is the filter tail's, bit for bit, any filter on or off; renoise, pin,
+ *     sampled_out and active[] act as before (an inactive slot's statistics are not stored either).
+ * (2) The renoise stage: which positions of a sample go back to init_noise after a step, decided per SAMPLE of rows_per_sample = H * W
+ *     positions (1 ... 16384: a sample's keys live in LDS).  It runs after a tail called WITHOUT init_noise and WITHOUT the pin tables, on
+ *     its raw draw.  free = the positions the pin does not own at this launch (pinned: pin_keep[row] == 0 and, stream form, pin_on[b] != 0).
+ *       policy 0 (random):     tok = u <= t_next ? init_noise : drawn -- the coin of the tails above (same Philox words, same arithmetic):
+ *                              tail without renoise + this stage == tail with init_noise, bit for bit
+ *       policy 1 (confidence): exactly n = clamp(rint(t_next * |free|), 0, |free|) free positions are renoised (fp32 product, round to nearest
+ *                              even; a negative t_next gives 0), the n smallest in (key(score), position index): score = logprob, or with
+ *                              g = confidence_noise > 0, fma(-(g * t_next), log(-log u'), logprob) -- a Gumbel perturbation annealed with
+ *                              t_next, u' from word 1 of the very Philox call whose word 0 is policy 0's coin (no new random stream: shards
+ *                              and slots stay exact); key = the ascending order-preserving 32-bit key of the fp32 score, -0 == +0, NaN
+ *                              first (the least confident), ties to the lower index
+ *     then the pin: tokens_out[row] = pin_tokens[row] on a pinned position.  A slot with active[b] == 0 stores nothing.  tokens_out may
+ *     alias drawn.  PAELLA_ERR_ARG, before anything is enqueued: rows not a multiple of rows_per_sample, rows_per_sample outside 1 ... 16384,
+ *     one pin table without the other, policy 1 (stream form: a policy table) without logprob; scalar form: a policy other than 0 / 1, a
+ *     negative or non-finite confidence_noise.
+ * ---------------------------------------------------------------------------------------------- */
+/* paella_sample_tail_filter plus the statistics; both outputs NULL IS paella_sample_tail_filter -- same kernel, same launch. */
+int paella_sample_tail_stats(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg,
+                             float temperature, int mode, uint64_t seed, const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset,
+                             const int64_t* row_offset_ptr, const int64_t* init_noise, float t_next, const int64_t* pin_keep,
+                             const int64_t* pin_tokens, int top_k, float top_p, float typical_mass, int min_tokens, int64_t* tokens_out,
+                             int64_t* sampled_out, float* logprob_out, float* entropy_out, void* stream);
+/* paella_sample_tail_stream_filter plus the statistics; both outputs NULL IS that entry point.  With an output the filter tables stay
+ * optional (both NULL = every request off). */
+int paella_sample_tail_stream_stats(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs,
+                                    const float* temperature, const uint64_t* seeds, int rows_per_sample, const int* step,
+                                    const float* t_next, const int* active, const int64_t* init_noise, const int64_t* pin_keep,
+                                    const int64_t* pin_tokens, const int* pin_on, const int* filter_k, const float* filter_mass,
+                                    int64_t* tokens_out, int64_t* sampled_out, float* logprob_out, float* entropy_out, void* stream);
+/* The renoise stage, scalar form: seed (+ *seed_ptr), step word `offset`, GLOBAL row offset (+ *row_offset_ptr; a multiple of
+ * rows_per_sample for a batch shard, which then equals its rows of the unsharded call) and t_next as paella_sample_tail_ex takes them.
+ * drawn int64 [rows], logprob fp32 [rows] (may be NULL with policy 0), init_noise int64 [rows]. */
+int paella_renoise_select(const int64_t* drawn, const float* logprob, const int64_t* init_noise, int64_t rows, int rows_per_sample,
+                          uint64_t seed, const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr,
+                          float t_next, int policy, float confidence_noise, const int64_t* pin_keep, const int64_t* pin_tokens,
+                          int64_t* tokens_out, void* stream);
+/* The renoise stage, request / stream form: seeds, step, t_next, active per slot as paella_sample_tail_stream takes them (all required);
+ * policy int32 [B] (1 = confidence, anything else random; NULL = every slot random) and confidence_noise fp32 [B] (NULL = 0). */
+int paella_renoise_select_stream(const int64_t* drawn, const float* logprob, const int64_t* init_noise, int64_t rows, int rows_per_sample,
+                                 const uint64_t* seeds, const int* step, const float* t_next, const int* active, const int* policy,
+                                 const float* confidence_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
+                                 int64_t* tokens_out, void* stream);
+
 /* x, random_x, mask int64 [B, per_sample]; t fp32 [B].  mask_in NULL -> mask = (u <= t[b]) with u = rand_u
  * (caller noise, [B, per_sample]) or Philox; random_x NULL -> Philox randint(0, num_labels). */
 int paella_add_noise(const int64_t* x, const float* t, const int64_t* mask_in, const int64_t* random_x,

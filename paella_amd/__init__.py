@@ -18,6 +18,12 @@ Public surface (mirrors the reference's Python API):
                               (extension, keyword-only) truncated sampling on sample, sample_distributed, GraphSampler, sample_requests (one value or one per
                               request), GraphRequestSampler(filtering=True) and RequestStream(filtering=True).admit: the draw is restricted to a subset of the
                               labels, the random numbers stay those of the unfiltered call (DESIGN.md 4 "Truncated sampling")
+    renoise / confidence_noise / return_stats
+                              (extension, keyword-only) confidence-ordered renoise and per-token confidence maps on sample, sample_distributed, GraphSampler,
+                              sample_requests (renoise / confidence_noise: one value or one per request) and RequestStream(confidence=True).admit /
+                              .result(stats=True): renoise="confidence" sends exactly rint(t_next * free positions) tokens per sample back to noise, the least
+                              confident first; return_stats adds the log p(token) and entropy maps of the final draw; check_renoise validates one setting
+                              (DESIGN.md 4 "Confidence-ordered renoise")
     inpaint / GraphInpainter  (extension) encode -> masked renoise -> sample -> decode; pin="step" keeps the known region clean at every step
     canvas                    (extension) a token grid placed on a larger canvas -> (known, mask): the outpainting set-up
     replace_attention_layers  reference utils/alter_attention.py:45
@@ -28,9 +34,9 @@ The opt-in bf16 fast mode is a per-model switch: `Paella.set_gemm_precision("bf1
 from .conditioning import build_paella, embed_prompts, load_checkpoint, load_conditional_models
 from .editing import GraphInpainter, canvas, inpaint
 from .modules import CondCache, DenoiseUNet, KeyWeights, Paella, RegionTables, region_query_groups, replace_attention_layers
-from .sampling import GraphRequestSampler, GraphSampler, RequestStream, request_program, sample, sample_distributed, sample_requests, select_tokens
+from .sampling import GraphRequestSampler, GraphSampler, RequestStream, check_renoise, request_program, sample, sample_distributed, sample_requests, select_tokens
 from .vqgan import VectorQuantize, VQModel
 
 
-__all__ = ["Paella", "DenoiseUNet", "CondCache", "KeyWeights", "RegionTables", "region_query_groups", "VQModel", "VectorQuantize", "sample", "sample_distributed", "sample_requests", "GraphSampler", "GraphRequestSampler", "RequestStream", "request_program",
+__all__ = ["Paella", "DenoiseUNet", "CondCache", "KeyWeights", "RegionTables", "region_query_groups", "VQModel", "VectorQuantize", "sample", "sample_distributed", "sample_requests", "GraphSampler", "GraphRequestSampler", "RequestStream", "request_program", "check_renoise",
            "replace_attention_layers", "inpaint", "GraphInpainter", "canvas", "select_tokens", "load_conditional_models", "embed_prompts", "load_checkpoint", "build_paella"]

@@ -174,6 +174,15 @@ SIGNATURES = {
                                           c_float, c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p]),
     "paella_sample_tail_stream_filter": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                  c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # confidence-ordered renoise (ABI 8, additive): the _filter tails plus (logprob_out, entropy_out) before the stream, and the renoise stage in both forms
+    "paella_sample_tail_stats": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_float, c_float, c_int, c_uint64, c_void_p, c_uint64, c_int64, c_void_p, c_void_p,
+                                         c_float, c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "paella_sample_tail_stream_stats": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "paella_renoise_select": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_uint64, c_void_p, c_uint64, c_int64, c_void_p, c_float, c_int, c_float, c_void_p,
+                                      c_void_p, c_void_p, c_void_p]),
+    "paella_renoise_select_stream": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                             c_void_p, c_void_p, c_void_p]),
 }
 
 # exported for tests / tools only; declared in paella_amd/csrc/test_hooks.h, not in the public header
@@ -211,6 +220,8 @@ TEST_HOOKS = {
     "paella_test_tail_scores_req": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_uint64, c_void_p, c_void_p]),
     "paella_test_tail_filter_keep": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_float, c_float, c_float, c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p,
                                              c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "paella_test_renoise_scores": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_uint64, c_uint64, c_int64, c_float, c_int, c_float, c_void_p, c_void_p, c_void_p,
+                                           c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "paella_test_gemm_prologue": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_int,
                                           c_void_p, c_size_t, c_void_p]),
     "paella_test_gemm_desc": (c_int, [POINTER(TestGemmArgs), c_int, c_int, c_void_p, c_size_t, c_void_p]),

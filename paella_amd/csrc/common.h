@@ -341,6 +341,34 @@ struct TailFilter {
 };
 static const int kTailFilterMaxLabels = 16384;  // the row's z lives in LDS
 int launch_sample_tail_filter(const TailArgs& a, const TailFilter& f, hipStream_t stream);
+// Per-row statistics of the draw (tail.hip: sample_tail_stats_kernel, the STATS form of the filter kernel), next to -- never inside -- TailArgs / TailFilter.  With
+// A, m, S = sum_A exp(z - m), E = sum_A (z - m) exp(z - m) as the filter kernel forms them (every label when top_k is off) and t the drawn label:
+//   logprob_out[row] = (z_t - m) - log S,   entropy_out[row] = log S - E / S;     a row the filter would not filter (NaN / no finite maximum): -inf and NaN.
+// Either pointer may be null.  The draw is the filter tail's, bit for bit; an inactive slot stores nothing.
+struct TailStats {
+    float* logprob_out = nullptr;   // [rows]
+    float* entropy_out = nullptr;   // [rows]
+};
+int launch_sample_tail_stats(const TailArgs& a, const TailFilter& f, const TailStats& s, hipStream_t stream);
+// Renoise stage (tail.hip: renoise_select_kernel): which positions of a sample go back to init_noise after a draw, chosen per sample.  Runs after a tail launched
+// without init_noise and without the pin tables; one 256-thread workgroup per sample of HW = rows_per_sample positions (1 ... kTailFilterMaxLabels: the sample's keys
+// live in HW * 4 bytes of LDS).  free = the positions the pin does not own at this launch (pin_keep[row] == 0 and, request form, pin_on[b] != 0 -> pinned).
+//   policy 0 (random):     tok = u01_half_open(rb[0]) <= t_next ? init_noise : drawn, rb = philox4x32(seed ^ renoise salt, ctr_row, step): renoise_token's words
+//   policy 1 (confidence): n = clamp(rint(t_next * n_free), 0, n_free) positions, the n free ones smallest in (key(score), index); score = logprob, or with
+//                          g = confidence_noise > 0 fmaf(-(g * t_next), log_exp1(rb[1]), logprob); key = the ascending order-preserving key of the fp32 score
+//                          (-0 == +0, NaN -> 0 = the least confident)
+// then the pin as pin_token applies it.  Scalar form (rq.rows_per_sample == 0 in `a`; rows_per_sample below): seed / offset / row offsets / t_next of `a`, one policy
+// and g.  Request form: rq tables (seeds, step, t_next, active) of `a`, policy int32 [B] and g fp32 [B].  Of `a` only rows, the seed / counter words, init_noise,
+// t_next, the pin tables, rq and tokens_out are read; tokens_out may alias drawn.  scores_out: test hook, the fp32 scores [rows] (policy-0 and pinned rows: logprob).
+struct RenoiseArgs {
+    const int64_t* drawn = nullptr;       // [rows] the tail's raw draw
+    const float* logprob = nullptr;       // [rows] required by policy 1
+    int rows_per_sample = 0;
+    int policy = 0; float confidence_noise = 0.f;                   // scalar form
+    const int* policy_tab = nullptr; const float* noise_tab = nullptr;  // request form: [B] each
+    float* scores_out = nullptr;          // test hook only
+};
+int launch_renoise_select(const TailArgs& a, const RenoiseArgs& r, hipStream_t stream);
 // one tick of a request stream: per slot b, row pos[b] of its program [B, max_steps, 5] = (r, temperature, cfg, 1 - cfg, t_next) becomes this tick's flat tables
 // (pairs may be null), step[b] = pos[b], active[b] = pos[b] < len[b]; the cursors of the active slots advance.  Idle slots: r 0, T 1, pair (1, 0), t_next -1.
 // pin_policy / pin_on (both or neither; null = exactly the stores above): per slot 0 = never, 1 = every step, 2 = the request's final step only ->

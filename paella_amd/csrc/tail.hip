@@ -14,6 +14,7 @@
 #include "common.h"
 #include "test_hooks.h"
 #include "philox.h"
+#include "../../include/paella_hip.h"
 #include <math.h>
 
 #pragma clang fp contract(off)
@@ -300,12 +301,10 @@ __device__ uint32_t filter_threshold(const float* zs, int L, uint32_t tau_a, flo
     return prefix;
 }
 
-template <bool REQ>
-__global__ __launch_bounds__(256) void sample_tail_filter_kernel(TailArgs a, TailFilter f) {
-    extern __shared__ float zs[];  // [L]
-    __shared__ float red[16];
-    __shared__ float red_v[4];
-    __shared__ int red_i[4];
+// The kernel's body, shared by its two forms.  STATS (common.h: TailStats): the row's sums are formed whatever the filter says -- with every filter off too -- and
+// the storing lane writes log p(token) and the entropy from them; the draw is the same draw.  zs [L] dynamic LDS, red [16], red_v / red_i [4] static LDS of the kernel.
+template <bool REQ, bool STATS>
+__device__ __forceinline__ void sample_tail_filter_body(const TailArgs& a, const TailFilter& f, const TailStats& st_out, float* zs, float* red, float* red_v, int* red_i) {
     const int64_t row = blockIdx.x;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int L = a.L, L4 = L >> 2;
@@ -320,9 +319,11 @@ __global__ __launch_bounds__(256) void sample_tail_filter_kernel(TailArgs a, Tai
     int top_k = f.top_k, min_tokens = f.min_tokens;
     float top_p = f.top_p, typical = f.typical_mass;
     if constexpr (REQ) {
-        const unsigned b = fast_div((unsigned)row, a.rq.rps_div);
-        top_k = f.filter_k[2 * b]; min_tokens = f.filter_k[2 * b + 1];
-        top_p = f.filter_mass[2 * b]; typical = f.filter_mass[2 * b + 1];
+        if (!STATS || f.filter_k) {  // (the statistics form runs without the filter tables as well: every request off)
+            const unsigned b = fast_div((unsigned)row, a.rq.rps_div);
+            top_k = f.filter_k[2 * b]; min_tokens = f.filter_k[2 * b + 1];
+            top_p = f.filter_mass[2 * b]; typical = f.filter_mass[2 * b + 1];
+        }
     }
     const bool k_on = top_k >= 1 && top_k < L;
     const bool p_on = top_p > 0.f && top_p < 1.f;
@@ -332,7 +333,7 @@ __global__ __launch_bounds__(256) void sample_tail_filter_kernel(TailArgs a, Tai
     bool use = false, typ_b = false;  // the kept set: key_desc <= tau_a && (typ_b ? key_typ : key_desc) <= tau_b
     uint32_t tau_a = 0xffffffffu, tau_b = 0xffffffffu;
     float m = 0.f, c = 0.f, sum = 0.f;
-    if (k_on || p_on || t_on || hook) {  // (workgroup-uniform: a row with every filter off runs the plain arg-max loop below and never touches zs)
+    if (k_on || p_on || t_on || hook || STATS) {  // (workgroup-uniform: a row with every filter off runs the plain arg-max loop below and never touches zs)
         float mx = -INFINITY, bad = 0.f;
         for (int i4 = tid; i4 < L4; i4 += 256) {
             const f32x4 cc = *reinterpret_cast<const f32x4*>(lc + i4 * 4);
@@ -357,7 +358,7 @@ __global__ __launch_bounds__(256) void sample_tail_filter_kernel(TailArgs a, Tai
             use = true;
             m = mx;
             if (k_on) tau_a = filter_threshold<false, false>(zs, L, 0xffffffffu, m, 0.f, (float)top_k, red, phase);
-            if (p_on || t_on || hook) {
+            if (p_on || t_on || hook || STATS) {
                 float s = 0.f, e = 0.f;
                 for (int i = tid; i < L; i += 256) {
                     const float z = zs[i];
@@ -426,11 +427,34 @@ __global__ __launch_bounds__(256) void sample_tail_filter_kernel(TailArgs a, Tai
         for (int w = 1; w < 4; ++w) argmax_update(best, best_i, red_v[w], red_i[w]);
         if (best_i == 0x7fffffff) best_i = 0;  // all-NaN row
         int64_t tok = best_i;
+        if constexpr (STATS) {  // log p(token) = (z_t - m) - log S and H = log S - E / S from the sums above, in their fixed order; the drawn label is always in A
+            const float ls = logf(sum);
+            if (st_out.logprob_out) st_out.logprob_out[row] = use ? (zs[best_i] - m) - ls : -INFINITY;
+            if (st_out.entropy_out) st_out.entropy_out[row] = use ? ls - c : __uint_as_float(0x7fc00000u);
+        }
         if (a.sampled_out) a.sampled_out[row] = tok;
         tok = renoise_token(a, rk, row, tok);
         if (a.pin_keep) tok = pin_token<REQ>(a, row, tok);
         a.tokens_out[row] = tok;
     }
+}
+
+template <bool REQ>
+__global__ __launch_bounds__(256) void sample_tail_filter_kernel(TailArgs a, TailFilter f) {
+    extern __shared__ float zs[];  // [L]
+    __shared__ float red[16];
+    __shared__ float red_v[4];
+    __shared__ int red_i[4];
+    sample_tail_filter_body<REQ, false>(a, f, TailStats{}, zs, red, red_v, red_i);
+}
+// the statistics form: the same body, two more stores in the storing lane
+template <bool REQ>
+__global__ __launch_bounds__(256) void sample_tail_stats_kernel(TailArgs a, TailFilter f, TailStats s) {
+    extern __shared__ float zs[];  // [L]
+    __shared__ float red[16];
+    __shared__ float red_v[4];
+    __shared__ int red_i[4];
+    sample_tail_filter_body<REQ, true>(a, f, s, zs, red, red_v, red_i);
 }
 
 // the filter's own argument rules; everything here is host arithmetic, checked before anything is enqueued
@@ -471,6 +495,284 @@ int launch_sample_tail_filter(const TailArgs& a, const TailFilter& f, hipStream_
     }
     LAUNCH_CHECK_RET();
     return PAELLA_OK;
+}
+
+// the statistics form of the filtered tail: the filter launcher's rules; in the request form the filter tables are optional (none = every request off)
+int launch_sample_tail_stats(const TailArgs& a, const TailFilter& f, const TailStats& s, hipStream_t st) {
+    if (a.rows <= 0) return PAELLA_OK;
+    if (a.L <= 0 || (a.L & 3)) { paella_set_error("sample_tail: num_labels %% 4 != 0"); return PAELLA_ERR_ARG; }
+    if (a.rows > 0x7fffffff) { paella_set_error("sample_tail: too many rows"); return PAELLA_ERR_ARG; }
+    const int rc = tail_filter_check(a, f);
+    if (rc != PAELLA_OK) return rc;
+    RET_PIN(a);
+    const size_t lds = (size_t)a.L * sizeof(float);
+    if (a.rq.rows_per_sample > 0) {
+        TailArgs r = a;
+        RET_REQ(r);
+        if (lds > 48 * 1024) HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_tail_stats_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(sample_tail_stats_kernel<true>, dim3((unsigned)a.rows), dim3(256), lds, st, r, f, s);
+    } else {
+        if (lds > 48 * 1024) HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(&sample_tail_stats_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(sample_tail_stats_kernel<false>, dim3((unsigned)a.rows), dim3(256), lds, st, a, f, s);
+    }
+    LAUNCH_CHECK_RET();
+    return PAELLA_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Renoise stage (common.h: RenoiseArgs): per SAMPLE, which positions go back to init_noise after the draw.  One 256-thread workgroup per sample; policy 0 is
+// renoise_token's independent coin per position, policy 1 renoises exactly n = rint(t_next * free positions) positions, the least confident first.  The sample's
+// 32-bit keys live in LDS (HW * 4 bytes, written once); the n-th smallest (key, index) pair comes from two bitwise bisections with INTEGER counts -- 32 steps over
+// the key for the threshold tau, then over the index among key == tau -- one workgroup reduction each, in filter_threshold's manner.  No atomics, no scratch, no
+// per-thread arrays; plain loads and stores.  Everything a workgroup branches on (active, policy, n) is uniform over it.
+// ---------------------------------------------------------------------------
+// ascending order-preserving key of an fp32 score: smaller key = less confident; -0 == +0, NaN -> 0 (the least confident).  No score maps to 0xffffffff
+__device__ __forceinline__ uint32_t renoise_key(float s) {
+    if (s != s) return 0u;
+    const uint32_t b = __float_as_uint(s == 0.f ? 0.f : s);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+static const uint32_t kRenoiseExcluded = 0xffffffffu;  // a position the pin owns: never counted, never selected
+// sum of v over the workgroup; red: [2][4] ints, `phase` alternates so one barrier per reduction is enough
+__device__ __forceinline__ int renoise_count(int v, int* red, int& phase) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    int* r = red + phase * 4;
+    if ((threadIdx.x & 63) == 0) r[threadIdx.x >> 6] = v;
+    __syncthreads();
+    phase ^= 1;
+    return (r[0] + r[1]) + (r[2] + r[3]);
+}
+
+template <bool REQ>
+__global__ __launch_bounds__(256) void renoise_select_kernel(TailArgs a, RenoiseArgs r) {
+    extern __shared__ uint32_t keys[];  // [HW]
+    __shared__ int red[8];
+    const unsigned b = blockIdx.x;
+    const int tid = threadIdx.x, HW = r.rows_per_sample;
+    const int64_t row0 = (int64_t)b * HW;
+    // what the sample draws with: renoise_token's key, counter and step words (tail_row_key without the categorical draw's tables)
+    uint64_t seed, step;
+    int64_t ctr0;
+    float t_next, g;
+    int policy;
+    bool pin = a.pin_keep != nullptr;
+    if constexpr (REQ) {
+        if (a.rq.active[b] == 0) return;  // an idle slot keeps what its rows held
+        seed = a.rq.seeds[b]; ctr0 = 0; step = (uint64_t)a.rq.step[b]; t_next = a.rq.t_next[b];
+        policy = r.policy_tab ? r.policy_tab[b] : 0;
+        g = r.noise_tab ? r.noise_tab[b] : 0.f;
+        if (pin && a.pin_on && a.pin_on[b] == 0) pin = false;
+    } else {
+        seed = a.seed + (a.seed_ptr ? *a.seed_ptr : 0ull); ctr0 = row0 + tail_row_offset(a); step = a.offset; t_next = a.t_next;
+        policy = r.policy; g = r.confidence_noise;
+    }
+    seed ^= 0x5bd1e9955bd1e995ull;
+
+    if (policy != 1) {  // random: renoise_token's coin, then the pin
+        for (int p = tid; p < HW; p += 256) {
+            const int64_t row = row0 + p;
+            uint32_t rb[4];
+            philox4x32(seed, (uint64_t)(ctr0 + p), step, rb);
+            int64_t tok = u01_half_open(rb[0]) <= t_next ? a.init_noise[row] : r.drawn[row];
+            if (pin && a.pin_keep[row] == 0) tok = a.pin_tokens[row];
+            if (r.scores_out) r.scores_out[row] = r.logprob ? r.logprob[row] : 0.f;
+            a.tokens_out[row] = tok;
+        }
+        return;
+    }
+
+    // confidence: the keys of the free positions, and how many there are
+    const float gt = g * t_next;
+    int mine = 0;
+    for (int p = tid; p < HW; p += 256) {
+        const int64_t row = row0 + p;
+        float score = r.logprob[row];
+        const bool pinned = pin && a.pin_keep[row] == 0;
+        if (g != 0.f && !pinned) {
+            uint32_t rb[4];
+            philox4x32(seed, (uint64_t)(ctr0 + p), step, rb);
+            score = __builtin_fmaf(-gt, log_exp1(rb[1]), score);
+        }
+        if (r.scores_out) r.scores_out[row] = score;
+        keys[p] = pinned ? kRenoiseExcluded : renoise_key(score);
+        mine += pinned ? 0 : 1;
+    }
+    int phase = 0;
+    const int n_free = renoise_count(mine, red, phase);  // (the barrier inside also completes `keys`)
+    int n = __float2int_rn(t_next * (float)n_free);      // (a NaN threshold converts to 0)
+    n = n < 0 ? 0 : (n > n_free ? n_free : n);
+
+    uint32_t tau = 0u;
+    int cut = -1;  // selected = key < tau || (key == tau && index <= cut)
+    if (n > 0) {
+        // the smallest tau with |{free : key <= tau}| >= n
+        for (int bit = 31; bit >= 0; --bit) {
+            const uint32_t t = tau | ((1u << bit) - 1u);
+            int cnt = 0;
+            for (int p = tid; p < HW; p += 256) { const uint32_t k = keys[p]; cnt += (k != kRenoiseExcluded && k <= t) ? 1 : 0; }
+            if (renoise_count(cnt, red, phase) < n) tau |= 1u << bit;
+        }
+        // of the positions with key == tau the first `need` by index: the smallest cut with |{key == tau, index <= cut}| >= need
+        int below = 0;
+        for (int p = tid; p < HW; p += 256) below += keys[p] < tau ? 1 : 0;
+        const int need = n - renoise_count(below, red, phase);
+        int top = 0;
+        while ((1 << top) < HW) ++top;
+        cut = 0;
+        for (int bit = top - 1; bit >= 0; --bit) {
+            const int t = cut | ((1 << bit) - 1);
+            int cnt = 0;
+            for (int p = tid; p < HW; p += 256) cnt += (keys[p] == tau && p <= t) ? 1 : 0;
+            if (renoise_count(cnt, red, phase) < need) cut |= 1 << bit;
+        }
+    }
+    for (int p = tid; p < HW; p += 256) {
+        const int64_t row = row0 + p;
+        const uint32_t k = keys[p];
+        int64_t tok;
+        if (k == kRenoiseExcluded) tok = a.pin_tokens[row];
+        else tok = (k < tau || (k == tau && p <= cut)) ? a.init_noise[row] : r.drawn[row];
+        a.tokens_out[row] = tok;
+    }
+}
+
+int launch_renoise_select(const TailArgs& a, const RenoiseArgs& r, hipStream_t st) {
+    const bool req = a.rq.rows_per_sample > 0;
+    if (!r.drawn || !a.init_noise || !a.tokens_out) { paella_set_error("renoise_select: null argument (drawn / init_noise / tokens_out)"); return PAELLA_ERR_ARG; }
+    if (r.rows_per_sample < 1 || r.rows_per_sample > kTailFilterMaxLabels) {
+        paella_set_error("renoise_select: a sample's keys live in LDS, rows_per_sample (%d) must be 1 ... %d", r.rows_per_sample, kTailFilterMaxLabels);
+        return PAELLA_ERR_ARG;
+    }
+    if (a.rows < 0 || a.rows % r.rows_per_sample || a.rows / r.rows_per_sample > 0x7fffffff) {
+        paella_set_error("renoise_select: rows (%lld) must be a multiple of rows_per_sample (%d): the selection is per sample", (long long)a.rows, r.rows_per_sample);
+        return PAELLA_ERR_ARG;
+    }
+    if (!a.pin_keep != !a.pin_tokens) { paella_set_error("renoise_select: pin_keep and pin_tokens must be given together (one pin table without the other)"); return PAELLA_ERR_ARG; }
+    if (a.pin_on && !a.pin_keep) { paella_set_error("renoise_select: pin_on without the pin_keep / pin_tokens row tables"); return PAELLA_ERR_ARG; }
+    if (req) {
+        if (!a.rq.seeds || !a.rq.step || !a.rq.t_next || !a.rq.active) { paella_set_error("renoise_select_stream: null argument (the seeds, step, t_next and active tables are required)"); return PAELLA_ERR_ARG; }
+        if (r.policy_tab && !r.logprob) { paella_set_error("renoise_select_stream: a policy table (policy 1 = confidence) needs logprob"); return PAELLA_ERR_ARG; }
+    } else {
+        if (a.row_offset < 0) { paella_set_error("renoise_select: row_offset must be >= 0"); return PAELLA_ERR_ARG; }
+        if (r.policy != 0 && r.policy != 1) { paella_set_error("renoise_select: policy must be 0 (random) or 1 (confidence), got %d", r.policy); return PAELLA_ERR_ARG; }
+        if (!(r.confidence_noise >= 0.f) || !(r.confidence_noise < INFINITY)) { paella_set_error("renoise_select: confidence_noise must be finite and >= 0"); return PAELLA_ERR_ARG; }
+        if (r.policy == 1 && !r.logprob) { paella_set_error("renoise_select: policy 1 (confidence) needs logprob"); return PAELLA_ERR_ARG; }
+    }
+    if (a.rows == 0) return PAELLA_OK;
+    const size_t lds = (size_t)r.rows_per_sample * sizeof(uint32_t);
+    const dim3 grid((unsigned)(a.rows / r.rows_per_sample));
+    if (req) {
+        if (lds > 48 * 1024) HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(&renoise_select_kernel<true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(renoise_select_kernel<true>, grid, dim3(256), lds, st, a, r);
+    } else {
+        if (lds > 48 * 1024) HIP_CHECK_RET(hipFuncSetAttribute(reinterpret_cast<const void*>(&renoise_select_kernel<false>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+        hipLaunchKernelGGL(renoise_select_kernel<false>, grid, dim3(256), lds, st, a, r);
+    }
+    LAUNCH_CHECK_RET();
+    return PAELLA_OK;
+}
+
+// ---- C entry points of the statistics tail and the renoise stage (include/paella_hip.h: "Confidence-ordered renoise")
+// paella_sample_tail_filter plus the two statistics outputs; both NULL = paella_sample_tail_filter, the same launch
+extern "C" int paella_sample_tail_stats(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature, int mode,
+                                        uint64_t seed, const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr,
+                                        const int64_t* init_noise, float t_next, const int64_t* pin_keep, const int64_t* pin_tokens, int top_k, float top_p,
+                                        float typical_mass, int min_tokens, int64_t* tokens_out, int64_t* sampled_out, float* logprob_out, float* entropy_out,
+                                        void* stream) {
+    if (!logprob_out && !entropy_out)
+        return paella_sample_tail_filter(logits_c, logits_u, rows, L, cfg, one_minus_cfg, temperature, mode, seed, seed_ptr, offset, row_offset, row_offset_ptr, init_noise,
+                                         t_next, pin_keep, pin_tokens, top_k, top_p, typical_mass, min_tokens, tokens_out, sampled_out, stream);
+    if (!logits_c || !tokens_out) { paella_set_error("sample_tail_stats: null argument"); return PAELLA_ERR_ARG; }
+    if (mode != 0) { paella_set_error("sample_tail_stats: the statistics are not offered in argmax mode"); return PAELLA_ERR_ARG; }
+    if (!(temperature > 0.f)) { paella_set_error("temperature must be > 0 in categorical mode (use mode=1 for argmax)"); return PAELLA_ERR_ARG; }
+    if (row_offset < 0) { paella_set_error("row_offset must be >= 0"); return PAELLA_ERR_ARG; }
+    TailArgs a = {};
+    a.logits_c = logits_c; a.logits_u = logits_u; a.rows = rows; a.L = L; a.cfg = cfg; a.one_minus_cfg = one_minus_cfg;
+    a.temperature = temperature; a.mode = mode; a.seed = seed; a.seed_ptr = seed_ptr; a.offset = offset;
+    a.row_offset = row_offset; a.row_offset_ptr = row_offset_ptr;
+    a.init_noise = init_noise; a.t_next = t_next; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
+    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens;
+    TailFilter f;
+    f.top_k = top_k; f.top_p = top_p; f.typical_mass = typical_mass; f.min_tokens = min_tokens;
+    TailStats s;
+    s.logprob_out = logprob_out; s.entropy_out = entropy_out;
+    return launch_sample_tail_stats(a, f, s, (hipStream_t)stream);
+}
+// paella_sample_tail_stream_filter plus the two statistics outputs (the filter tables stay optional: none = every request off); both NULL = that entry point
+extern "C" int paella_sample_tail_stream_stats(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
+                                               const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active,
+                                               const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
+                                               const int* filter_k, const float* filter_mass, int64_t* tokens_out, int64_t* sampled_out, float* logprob_out,
+                                               float* entropy_out, void* stream) {
+    if (!logprob_out && !entropy_out)
+        return paella_sample_tail_stream_filter(logits_c, logits_u, rows, L, cfg_pairs, temperature, seeds, rows_per_sample, step, t_next, active, init_noise, pin_keep,
+                                                pin_tokens, pin_on, filter_k, filter_mass, tokens_out, sampled_out, stream);
+    if (!logits_c || !tokens_out || !seeds || !temperature) { paella_set_error("sample_tail_stream_stats: null argument"); return PAELLA_ERR_ARG; }
+    if (!filter_k != !filter_mass) { paella_set_error("sample_tail_stream_stats: filter_k and filter_mass must be given together (one filter table without the other)"); return PAELLA_ERR_ARG; }
+    if (!step || !t_next || !active || !init_noise) {
+        paella_set_error("sample_tail_stream_stats: null argument (the step, t_next and active tables and init_noise, the renoise source of every slot, are required)");
+        return PAELLA_ERR_ARG;
+    }
+    if (rows_per_sample <= 0) { paella_set_error("sample_tail_stream_stats: rows_per_sample must be > 0"); return PAELLA_ERR_ARG; }
+    TailArgs a = {};
+    a.logits_c = logits_c; a.logits_u = cfg_pairs ? logits_u : nullptr; a.rows = rows; a.L = L; a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f;
+    a.init_noise = init_noise; a.t_next = -1.f; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
+    a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.cfg_pairs = cfg_pairs; a.rq.rows_per_sample = rows_per_sample;
+    a.rq.step = step; a.rq.t_next = t_next; a.rq.active = active;
+    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens; a.pin_on = pin_on;
+    TailFilter f;
+    f.filter_k = filter_k; f.filter_mass = filter_mass;
+    TailStats s;
+    s.logprob_out = logprob_out; s.entropy_out = entropy_out;
+    return launch_sample_tail_stats(a, f, s, (hipStream_t)stream);
+}
+
+static int renoise_select_scalar(const int64_t* drawn, const float* logprob, const int64_t* init_noise, int64_t rows, int rows_per_sample, uint64_t seed,
+                                 const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr, float t_next, int policy,
+                                 float confidence_noise, const int64_t* pin_keep, const int64_t* pin_tokens, int64_t* tokens_out, float* scores_out, void* stream) {
+    TailArgs a = {};
+    a.rows = rows; a.seed = seed; a.seed_ptr = seed_ptr; a.offset = offset; a.row_offset = row_offset; a.row_offset_ptr = row_offset_ptr;
+    a.init_noise = init_noise; a.t_next = t_next; a.tokens_out = tokens_out; a.pin_keep = pin_keep; a.pin_tokens = pin_tokens;
+    RenoiseArgs r;
+    r.drawn = drawn; r.logprob = logprob; r.rows_per_sample = rows_per_sample; r.policy = policy; r.confidence_noise = confidence_noise; r.scores_out = scores_out;
+    return launch_renoise_select(a, r, (hipStream_t)stream);
+}
+static int renoise_select_stream(const int64_t* drawn, const float* logprob, const int64_t* init_noise, int64_t rows, int rows_per_sample, const uint64_t* seeds,
+                                 const int* step, const float* t_next, const int* active, const int* policy, const float* confidence_noise, const int64_t* pin_keep,
+                                 const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, float* scores_out, void* stream) {
+    TailArgs a = {};
+    a.rows = rows; a.init_noise = init_noise; a.t_next = -1.f; a.tokens_out = tokens_out; a.pin_keep = pin_keep; a.pin_tokens = pin_tokens; a.pin_on = pin_on;
+    a.rq.seeds = seeds; a.rq.step = step; a.rq.t_next = t_next; a.rq.active = active; a.rq.rows_per_sample = rows_per_sample > 0 ? rows_per_sample : 1;
+    RenoiseArgs r;
+    r.drawn = drawn; r.logprob = logprob; r.rows_per_sample = rows_per_sample; r.policy_tab = policy; r.noise_tab = confidence_noise; r.scores_out = scores_out;
+    return launch_renoise_select(a, r, (hipStream_t)stream);
+}
+extern "C" int paella_renoise_select(const int64_t* drawn, const float* logprob, const int64_t* init_noise, int64_t rows, int rows_per_sample, uint64_t seed,
+                                     const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr, float t_next, int policy,
+                                     float confidence_noise, const int64_t* pin_keep, const int64_t* pin_tokens, int64_t* tokens_out, void* stream) {
+    return renoise_select_scalar(drawn, logprob, init_noise, rows, rows_per_sample, seed, seed_ptr, offset, row_offset, row_offset_ptr, t_next, policy, confidence_noise,
+                                 pin_keep, pin_tokens, tokens_out, nullptr, stream);
+}
+extern "C" int paella_renoise_select_stream(const int64_t* drawn, const float* logprob, const int64_t* init_noise, int64_t rows, int rows_per_sample,
+                                            const uint64_t* seeds, const int* step, const float* t_next, const int* active, const int* policy,
+                                            const float* confidence_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out,
+                                            void* stream) {
+    return renoise_select_stream(drawn, logprob, init_noise, rows, rows_per_sample, seeds, step, t_next, active, policy, confidence_noise, pin_keep, pin_tokens, pin_on,
+                                 tokens_out, nullptr, stream);
+}
+// test hook (test_hooks.h): the renoise stage with its fp32 scores written out -- scores_out [rows] = what the kernel ranked (policy-0 slots: logprob, 0 without one).
+// seeds == NULL: the scalar form (seed, offset, row_offset, t_next, policy, confidence_noise by value); otherwise the stream form's tables.
+extern "C" int paella_test_renoise_scores(const int64_t* drawn, const float* logprob, const int64_t* init_noise, int64_t rows, int rows_per_sample, uint64_t seed,
+                                          uint64_t offset, int64_t row_offset, float t_next, int policy, float confidence_noise, const uint64_t* seeds, const int* step,
+                                          const float* t_next_tab, const int* active, const int* policy_tab, const float* noise_tab, const int64_t* pin_keep,
+                                          const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, float* scores_out, void* stream) {
+    if (!scores_out) { paella_set_error("renoise_scores: scores_out is required"); return PAELLA_ERR_ARG; }
+    if (seeds)
+        return renoise_select_stream(drawn, logprob, init_noise, rows, rows_per_sample, seeds, step, t_next_tab, active, policy_tab, noise_tab, pin_keep, pin_tokens, pin_on,
+                                     tokens_out, scores_out, stream);
+    return renoise_select_scalar(drawn, logprob, init_noise, rows, rows_per_sample, seed, nullptr, offset, row_offset, nullptr, t_next, policy, confidence_noise, pin_keep,
+                                 pin_tokens, tokens_out, scores_out, stream);
 }
 
 // ---------------------------------------------------------------------------

@@ -132,6 +132,13 @@ int paella_test_tail_scores_req(const float* logits_c, const float* logits_u, in
 int paella_test_tail_filter_keep(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature, int top_k,
                                  float top_p, float typical_mass, int min_tokens, const float* cfg_pairs, const float* temps, const uint64_t* seeds,
                                  int rows_per_sample, const int* filter_k, const float* filter_mass, unsigned char* keep_out, float* rec_out, void* stream);
+/* the renoise stage (tail.hip: renoise_select_kernel) with the fp32 scores it ranked written out: scores_out fp32 [rows] (a policy-0 slot and a pinned position
+ * under g != 0: the logprob input).  seeds == NULL: the scalar form (seed, offset, row_offset, t_next, policy, confidence_noise by value); otherwise the stream form
+ * (seeds, step, t_next_tab, active, policy_tab, noise_tab per slot).  Tokens as paella_renoise_select / paella_renoise_select_stream store them. */
+int paella_test_renoise_scores(const int64_t* drawn, const float* logprob, const int64_t* init_noise, int64_t rows, int rows_per_sample, uint64_t seed,
+                               uint64_t offset, int64_t row_offset, float t_next, int policy, float confidence_noise, const uint64_t* seeds, const int* step,
+                               const float* t_next_tab, const int* active, const int* policy_tab, const float* noise_tab, const int64_t* pin_keep,
+                               const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, float* scores_out, void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -332,6 +332,88 @@ class FilterTables:
         self.mass.copy_(host[1])
 
 
+# ---------------------------------------------------------------------------------------------------------------- confidence-ordered renoise
+RENOISE_POLICY = {"random": 0, "confidence": 1}  # as the renoise stage reads it (tail.hip: renoise_select_kernel)
+
+
+def check_renoise(renoise="random", confidence_noise=0.0):
+    """One renoise setting -> (policy, confidence_noise) in the kernels' encoding.  renoise: "random" (an independent coin u <= t_next per position, the
+    reference's policy) or "confidence" (after each step exactly rint(t_next * free positions) tokens go back to noise, the least confident first);
+    confidence_noise g >= 0: the scale of the annealed Gumbel perturbation of the confidence scores (score = logprob + g * t_next * Gumbel; 0 = none), which only
+    acts under "confidence".  Raises a ValueError that names the argument."""
+    if not isinstance(renoise, str) or renoise not in RENOISE_POLICY:
+        raise ValueError("renoise must be 'random' or 'confidence', got %r" % (renoise,))
+    g = confidence_noise
+    if isinstance(g, bool) or not isinstance(g, (int, float)) or not 0.0 <= float(g) < float("inf"):
+        raise ValueError("confidence_noise must be a finite number >= 0, got %r" % (g,))
+    return RENOISE_POLICY[renoise], float(g)
+
+
+def _call_renoise(noise, temperatures, renoise, confidence_noise, return_stats):
+    """the renoise setting of a whole call: validated, None with the defaults (the call then takes exactly the path it takes without these arguments), else
+    (policy, confidence_noise, return_stats)"""
+    policy, g = check_renoise(renoise, confidence_noise)
+    if policy == 0 and not return_stats:
+        return None
+    names = "renoise='confidence'" if policy else "return_stats"
+    if noise != "philox":
+        raise ValueError("%s needs noise='philox' (the counter-based sampling tail reports the statistics the selection ranks)" % names)
+    if any(t == 0 for t in temperatures):
+        raise ValueError("%s is not offered with a step temperature of 0 (the argmax extension)" % names)
+    return policy, g, bool(return_stats)
+
+
+def request_renoise(B, renoise="random", confidence_noise=0.0):
+    """HOST tables of a request batch's renoise settings: each argument one value for all requests or a list of B -> (policy int32 [B], confidence_noise fp32 [B],
+    any_confidence); every entry validated by `check_renoise` (the message names the argument and the request)."""
+    B = int(B)
+    cols = []
+    for name, v in (("renoise", renoise), ("confidence_noise", confidence_noise)):
+        if isinstance(v, (list, tuple)):
+            if len(v) != B:
+                raise ValueError("%s must be one value or a list of %d (one per request), got %d" % (name, B, len(v)))
+            cols.append(list(v))
+        else:
+            cols.append([v] * B)
+    rows = []
+    for b in range(B):
+        try:
+            rows.append(check_renoise(cols[0][b], cols[1][b]))
+        except ValueError as e:
+            raise ValueError("request %d: %s" % (b, e)) from None
+    return torch.tensor([r[0] for r in rows], dtype=torch.int32), torch.tensor([r[1] for r in rows], dtype=torch.float32), any(r[0] for r in rows)
+
+
+class ConfidenceTables:
+    """the DEVICE tables of a request batch that renoises per request: policy int32 [B], noise fp32 [B] (`request_renoise`) and `never` fp32 [B] = -1, the renoise
+    threshold the statistics tail runs with (the renoise stage after it does the renoising)"""
+
+    def __init__(self, host, device):
+        self.policy, self.noise = host[0].to(device), host[1].to(device)
+        self.never = torch.full((host[0].numel(),), -1.0, dtype=torch.float32, device=device)
+
+
+def _stats_tail(lc, lu, rows, L, cfg, omc, temperature, seed, offset, out, logprob, entropy, seed_dev=None, row_offset=0, row_offset_dev=None, pin=None, filt=None):
+    """the statistics form of the filtered tail, scalar form, without renoise: the draw of `_tail(filt=...)` plus log p(token) and the row entropy"""
+    f = FILTER_OFF if filt is None else filt
+    pk, pt = (None, None) if pin is None else pin
+    dev = lc.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().paella_sample_tail_stats(_lib.ptr(lc), _lib.ptr(lu), rows, L, cfg, omc, temperature, 0, seed, _lib.ptr(seed_dev), offset, row_offset,
+                                                        _lib.ptr(row_offset_dev), None, 0.0, _lib.ptr(pk), _lib.ptr(pt), f[0], f[1], f[2], f[3], _lib.ptr(out), None,
+                                                        _lib.ptr(logprob), _lib.ptr(entropy), _lib.stream_ptr(dev)))
+
+
+def _renoise_stage(drawn, logprob, init_noise, rows, rows_per_sample, seed, offset, t_next, policy, g, out, seed_dev=None, row_offset=0, row_offset_dev=None, pin=None):
+    """the renoise stage, scalar form (`out` may be `drawn`)"""
+    pk, pt = (None, None) if pin is None else pin
+    dev = drawn.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().paella_renoise_select(_lib.ptr(drawn), _lib.ptr(logprob), _lib.ptr(init_noise), rows, rows_per_sample, seed, _lib.ptr(seed_dev), offset,
+                                                     row_offset, _lib.ptr(row_offset_dev), t_next, policy, g, _lib.ptr(pk), _lib.ptr(pt), _lib.ptr(out),
+                                                     _lib.stream_ptr(dev)))
+
+
 def _weights_vector(v):
     if v is None:
         return None
@@ -430,7 +512,7 @@ def select_tokens(a, b=None, mask=None, flag=None, fill=-1, out=None):
 
 def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x, steps, renoise_steps, t_list, temperatures,
                  cfgs, device, noise="torch", seed=None, attn_weights=None, seed_dev=None, init_noise_buf=None, r_all=None, shard=None,
-                 ws=None, fused_tail=True, row_offset_dev=None, req=None, pin=None, filt=None):
+                 ws=None, fused_tail=True, row_offset_dev=None, req=None, pin=None, filt=None, conf=None):
     """cfgs: per-step list of (cfg_fp32, one_minus_cfg_fp32) or None (no guidance at that step).
     seed_dev / row_offset_dev / init_noise_buf / r_all: device-resident seed and row-offset words, a buffer for the start tokens
     and the [steps, B] timestep table (HIP-graph capture cannot upload from the host, see GraphSampler); ws: caller-owned
@@ -442,7 +524,11 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
     pin=(keep, known) (noise="philox" only; int64 [B, H, W] each): after EVERY step's draw and renoise the tail writes known[row] wherever keep[row] == 0 -- the
     known region of an editing request stays clean while the model denoises (paella_amd.editing.inpaint(pin="step")).
     filt (noise="philox" only): truncated sampling -- a `check_filter` tuple (one setting for the call) or, with `req`, a `FilterTables`.  Every step then takes the
-    logits forward plus the filtered tail: `fused_tail` is ignored, rows * L * 4 bytes of logits are written and read back per step."""
+    logits forward plus the filtered tail: `fused_tail` is ignored, rows * L * 4 bytes of logits are written and read back per step.
+    conf (noise="philox" only): confidence-ordered renoise / statistics -- (policy, confidence_noise, return_stats) of `_call_renoise` or, with `req`, a
+    `ConfidenceTables` (then `filt` carries the stream tables).  Every step is then the logits forward, the statistics tail (the filtered tail's draw plus log p(token)
+    and the row entropy, no renoise) and, on a renoising step, the renoise stage; `fused_tail` is ignored.  With return_stats the result is (tokens, {"logprob",
+    "entropy"}), fp32 [B, H, W] maps of the final step's draw."""
     explicit = isinstance(noise, dict)  # parity tests: {"init_noise": [B,H,W], "q": [rows,L] per step, "u": [B,H,W] per step}
     if not explicit and noise not in ("torch", "philox"):
         raise ValueError("noise must be 'torch', 'philox' or a dict of explicit noise tensors")
@@ -479,6 +565,13 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
             raise ValueError("top_k / top_p / typical_mass are not offered with a step temperature of 0 (the argmax extension)")
         if isinstance(filt, FilterTables) != (req is not None):
             raise ValueError("filt: one check_filter tuple for a plain call, a FilterTables with request tables")
+    if conf is not None:
+        if not philox:
+            raise ValueError("renoise='confidence' / return_stats need noise='philox' (the counter-based sampling tail reports the statistics)")
+        if any(t == 0 for t in temperatures[:steps]):
+            raise ValueError("renoise='confidence' / return_stats are not offered with a step temperature of 0 (the argmax extension)")
+        if isinstance(conf, ConfidenceTables) != (req is not None) or (req is not None and filt is None):
+            raise ValueError("conf: one (policy, confidence_noise, return_stats) tuple for a plain call, a ConfidenceTables next to a FilterTables with request tables")
     with torch.inference_mode():
         if req is not None:
             init_noise = start_tokens_requests(L, (B, H, W), req.seeds, out=init_noise_buf)
@@ -518,7 +611,10 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
         out = torch.empty(B, H, W, dtype=torch.int64, device=device)
         if r_all is None:
             r_all = timestep_table(t_list, steps, B, device)
-        fuse = philox and native and fused_tail and filt is None  # head GEMM + tail in one launch: no logits tensor at all (a filter needs the whole row)
+        fuse = philox and native and fused_tail and filt is None and conf is None  # head GEMM + tail in one launch: no logits tensor at all (a filter needs the whole row)
+        logprob = entropy = None
+        if conf is not None:
+            logprob, entropy = (torch.empty(B, H, W, dtype=torch.float32, device=device) for _ in range(2))
         for i in range(steps):
             r = r_all[i]
             use_cfg = cfgs[i] is not None
@@ -571,6 +667,29 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
                 mask_u = noise["u"][i].to(device=device, dtype=torch.float32).contiguous()
             elif renoise and noise == "torch":
                 mask_u = torch.rand(B, H, W, dtype=torch.float32, device=device)  # == torch.rand_like(x.float())
+            if conf is not None and req is not None:
+                # the statistics tail in the stream form, never renoising (threshold table -1), then the renoise stage with the step's real thresholds
+                with torch.cuda.device(device):
+                    _lib.check(_lib.load().paella_sample_tail_stream_stats(_lib.ptr(lc), _lib.ptr(lu), rows, L, _lib.ptr(None if lu is None else req.pairs[i]),
+                                                                           _lib.ptr(req.temps[i]), _lib.ptr(req.seeds), H * W, _lib.ptr(filt.step[i]), _lib.ptr(conf.never),
+                                                                           _lib.ptr(filt.active), _lib.ptr(init_noise), None, None, None, _lib.ptr(filt.k), _lib.ptr(filt.mass),
+                                                                           _lib.ptr(out), None, _lib.ptr(logprob), _lib.ptr(entropy), _lib.stream_ptr(device)))
+                    if renoise:
+                        _lib.check(_lib.load().paella_renoise_select_stream(_lib.ptr(out), _lib.ptr(logprob), _lib.ptr(init_noise), rows, H * W, _lib.ptr(req.seeds),
+                                                                            _lib.ptr(filt.step[i]), _lib.ptr(filt.t_next[i]), _lib.ptr(filt.active), _lib.ptr(conf.policy),
+                                                                            _lib.ptr(conf.noise), None, None, None, _lib.ptr(out), _lib.stream_ptr(device)))
+                sampled = out
+                continue
+            if conf is not None:
+                # a renoising step: the raw draw and its statistics, then the renoise stage (which also applies the pin); the last steps: the pin rides in the tail
+                cfg, omc = cfgs[i] if use_cfg else (1.0, 0.0)
+                _stats_tail(lc, lu, rows, L, cfg, omc, temp, seed, i, out, logprob, entropy, seed_dev=seed_dev, row_offset=row_offset, row_offset_dev=row_offset_dev,
+                            pin=None if renoise else pin, filt=filt)
+                if renoise:
+                    _renoise_stage(out, logprob, init_noise, rows, H * W, seed, i, t_list[i + 1], conf[0], conf[1], out, seed_dev=seed_dev, row_offset=row_offset,
+                                   row_offset_dev=row_offset_dev, pin=pin)
+                sampled = out
+                continue
             if req is not None:
                 # (the stream form of the filtered tail wants its renoise source at every step; a step that does not renoise -- threshold -1 -- never reads it)
                 _tail_req(lc, lu, rows, L, H * W, req, i, init_noise if renoise or filt is not None else None, t_list[i + 1] if renoise else 0.0, out, filt=filt)
@@ -581,6 +700,8 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
                   init_noise if renoise else None, mask_u, t_list[i + 1] if renoise else 0.0, out, seed_dev=seed_dev,
                   row_offset=row_offset, row_offset_dev=row_offset_dev, pin=pin, filt=filt)
             sampled = out  # the tail never reads `sampled`, so one output buffer is enough (stream-ordered reuse)
+    if conf is not None and req is None and conf[2]:
+        return sampled, {"logprob": logprob, "entropy": entropy}
     return sampled
 
 
@@ -599,9 +720,12 @@ def _call_filter(noise, temperatures, top_k, top_p, typical_mass, min_tokens):
 
 def sample(model, model_inputs, latent_shape, unconditional_inputs=None, steps=12, renoise_steps=11, temperature=(1.0, 0.2),
            cfg=8.0, t_start=1.0, t_end=0.0, device="cuda", *, noise="torch", seed=None, seed_dev=None, attn_weights=None, shard=None, fused_tail=True,
-           top_k=None, top_p=None, typical_mass=None, min_tokens=1):
+           top_k=None, top_p=None, typical_mass=None, min_tokens=1, renoise="random", confidence_noise=0.0, return_stats=False):
     """Drop-in for reference src/utils.py:35 `sample` (same positional order and defaults).
     top_k / top_p / typical_mass / min_tokens (noise="philox" only; `check_filter`): truncated sampling, one setting for the call -- see `_sample_core`.
+    renoise / confidence_noise / return_stats (noise="philox" only; `check_renoise`): renoise="confidence" sends exactly rint(t_next * free positions) tokens per
+    sample back to noise after each renoising step, the least confident first (confidence_noise: the annealed Gumbel perturbation of the ranking); return_stats=True
+    returns (tokens, {"logprob", "entropy"}), fp32 [B, H, W] maps of the final step's draw.  With the defaults the call is today's call -- see `_sample_core`.
     Keyword-only extensions: noise ("torch" = consume torch's generator exactly like the reference; "philox" = counter-based
     noise generated in the kernels, keyed by `seed` -- None draws a fresh seed from torch's generator), attn_weights
     (utils/modules.py:268), shard=(lo, total) for batch-sharded sampling (paella_amd.dist.sample_sharded), fused_tail (counter-based
@@ -621,14 +745,18 @@ def sample(model, model_inputs, latent_shape, unconditional_inputs=None, steps=1
         cfgs = [None] * steps
     return _sample_core(model, model_inputs, unconditional_inputs, latent_shape, None, steps, renoise_steps, t_list, temperatures,
                         cfgs, device, noise=noise, seed=seed, seed_dev=seed_dev, attn_weights=attn_weights, shard=shard, fused_tail=fused_tail,
-                        filt=_call_filter(noise, temperatures, top_k, top_p, typical_mass, min_tokens))
+                        filt=_call_filter(noise, temperatures, top_k, top_p, typical_mass, min_tokens),
+                        conf=_call_renoise(noise, temperatures, renoise, confidence_noise, return_stats))
 
 
 def sample_distributed(model, model_inputs, unconditional_inputs, latent_shape, init_x=None, steps=12, renoise_steps=None,
                        temperature=(0.7, 0.3), cfg=(8.0, 8.0), t_start=1.0, t_end=0.0, sampling_conditional_steps=None, *,
-                       noise="torch", seed=None, attn_weights=None, shard=None, fused_tail=True, pin=None, top_k=None, top_p=None, typical_mass=None, min_tokens=1):
+                       noise="torch", seed=None, attn_weights=None, shard=None, fused_tail=True, pin=None, top_k=None, top_p=None, typical_mass=None, min_tokens=1,
+                       renoise="random", confidence_noise=0.0, return_stats=False):
     """Drop-in for reference src_distributed/utils.py:97 `sample` (init_x, cfg schedule, conditional-step cutoff).
     top_k / top_p / typical_mass / min_tokens (noise="philox" only): truncated sampling, as `sample`.
+    renoise / confidence_noise / return_stats (noise="philox" only): confidence-ordered renoise and the statistics maps, as `sample`; with pin= the count is taken over
+    the positions the pin does not own.
     Keyword-only extension pin=(keep, known) (noise="philox" only): every step's tail re-imposes known where keep == 0, see `_sample_core`."""
     device = unconditional_inputs["byt5"].device
     if sampling_conditional_steps is None:
@@ -645,7 +773,8 @@ def sample_distributed(model, model_inputs, unconditional_inputs, latent_shape, 
             cfgs[i] = (float(sched[i]), float(1 - sched[i]))
     return _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x, steps, renoise_steps, t_list, temperatures,
                         cfgs, device, noise=noise, seed=seed, attn_weights=attn_weights, shard=shard, fused_tail=fused_tail, pin=pin,
-                        filt=_call_filter(noise, temperatures, top_k, top_p, typical_mass, min_tokens))
+                        filt=_call_filter(noise, temperatures, top_k, top_p, typical_mass, min_tokens),
+                        conf=_call_renoise(noise, temperatures, renoise, confidence_noise, return_stats))
 
 
 def _request_schedule(steps, t_start, t_end, guided):
@@ -654,7 +783,8 @@ def _request_schedule(steps, t_start, t_end, guided):
 
 
 def sample_requests(model, model_inputs, unconditional_inputs, latent_shape, seeds, cfg=8.0, temperature=(1.0, 0.2), steps=12, renoise_steps=11,
-                    t_start=1.0, t_end=0.0, device="cuda", attn_weights=None, fused_tail=True, *, top_k=None, top_p=None, typical_mass=None, min_tokens=1):
+                    t_start=1.0, t_end=0.0, device="cuda", attn_weights=None, fused_tail=True, *, top_k=None, top_p=None, typical_mass=None, min_tokens=1,
+                    renoise="random", confidence_noise=0.0):
     """B independent REQUESTS sampled as one batch (counter-based noise): request b has its own seed `seeds[b]`, guidance and temperature range, and its
     tokens are a function of the request alone -- every random number it draws is the one `sample(..., latent_shape=(1, H, W), noise="philox", seed=seeds[b])`
     draws, whatever slot it sits in and whoever shares the batch (the logits may still differ in their last bits with the batch size: the GEMMs split their
@@ -665,10 +795,14 @@ def sample_requests(model, model_inputs, unconditional_inputs, latent_shape, see
     per conditioning slot: request b's tokens are those of a call in which every request carries request b's weights, bit for bit, whatever its batch-mates
     carry.  A guided list call needs the one-forward path (both conditioning sets with B samples each).
     top_k / top_p / typical_mass / min_tokens: truncated sampling, each one value for all requests or a list with one per request (`request_filters`); request b
-    is filtered as `sample(..., seed=seeds[b], <its values>)` filters it.  With a filter on for anyone every step takes the logits forward plus the filtered tail."""
+    is filtered as `sample(..., seed=seeds[b], <its values>)` filters it.  With a filter on for anyone every step takes the logits forward plus the filtered tail.
+    renoise / confidence_noise: each one value for all requests or a list with one per request (`request_renoise`); request b renoises as
+    `sample(..., seed=seeds[b], <its values>)` does, whatever its batch-mates carry.  With renoise="confidence" for anyone every step takes the logits forward, the
+    statistics tail and the renoise stage, all in their request form."""
     B, H, W = (int(v) for v in latent_shape)
     host = request_tables(B, steps, seeds, cfg, temperature)
     fhost = request_filters(B, top_k, top_p, typical_mass, min_tokens)
+    chost = request_renoise(B, renoise, confidence_noise)
     if host[2] is not None and unconditional_inputs is None:
         raise TypeError("cfg=%r requires unconditional_inputs" % (cfg,))
     device = torch.device(device)
@@ -688,7 +822,8 @@ def sample_requests(model, model_inputs, unconditional_inputs, latent_shape, see
                                          _request_keys(model, H, W, model_inputs, unconditional_inputs if guided else None), guided)
     return _sample_core(model, model_inputs, unconditional_inputs, (B, H, W), None, steps, renoise_steps, t_list, temps, cfgs, device, noise="philox", seed=0,
                         attn_weights=attn_weights, fused_tail=fused_tail, req=RequestTables(host, device),
-                        filt=FilterTables(fhost, device, steps, renoise_steps, t_list) if fhost[2] else None)
+                        filt=FilterTables(fhost, device, steps, renoise_steps, t_list) if fhost[2] or chost[2] else None,
+                        conf=ConfidenceTables(chost, device) if chost[2] else None)
 
 
 class GraphSampler:
@@ -704,6 +839,8 @@ class GraphSampler:
     [lo, lo + B) of `sample(..., noise="philox", seed=s)` over the global batch (tests/test_gpu_sample.py).
     seed=None draws a fresh seed from torch's global CPU generator (one draw per call; see fresh_seed).
     top_k / top_p / typical_mass / min_tokens (keyword-only): one truncation setting baked into the capture, as `sample` takes it.
+    renoise / confidence_noise / return_stats (keyword-only): one renoise setting baked into the capture, as `sample` takes it; with return_stats a replay returns
+    (tokens, {"logprob", "entropy"}) -- with a VQGAN (tokens, image, {...}) -- in graph-owned buffers.
 
     Staleness (the call site that reloads weights between sampling calls is src/train.py:40,64-69,76): a capture bakes raw pointers,
     host-side constants read from the weights (the VQGAN's ResBlock gammas) and the precision mode's kernel choice.  Every replay first compares the models'
@@ -712,9 +849,11 @@ class GraphSampler:
 
     def __init__(self, model, model_inputs, unconditional_inputs, latent_shape, steps=12, renoise_steps=11, temperature=(1.0, 0.2),
                  cfg=8.0, t_start=1.0, t_end=0.0, device="cuda", vqgan=None, attn_weights=None, on_stale="recapture", *, top_k=None, top_p=None, typical_mass=None,
-                 min_tokens=1):
+                 min_tokens=1, renoise="random", confidence_noise=0.0, return_stats=False):
         if on_stale not in ("recapture", "raise"):
             raise ValueError("on_stale must be 'recapture' or 'raise'")
+        # confidence-ordered renoise / statistics, one setting baked into the capture (None = today's capture)
+        self.conf = _call_renoise("philox", linspace_schedule(temperature[0], temperature[1], steps), renoise, confidence_noise, return_stats)
         if not hasattr(self, "filt"):  # truncated sampling, one setting baked into the capture (GraphRequestSampler keeps device tables here instead)
             self.filt = _call_filter("philox", linspace_schedule(temperature[0], temperature[1], steps), top_k, top_p, typical_mass, min_tokens)
         self.model, self.vqgan, self.device, self.on_stale = model, vqgan, torch.device(device), on_stale
@@ -791,9 +930,15 @@ class GraphSampler:
         init_x = self._init_x()
         toks = _sample_core(self.model, self.cond, self.uncond, self.shape, init_x, k["steps"], k["renoise_steps"], t_list, temps, cfgs,
                             self.device, noise="philox", seed=0, attn_weights=self.attn_weights, seed_dev=self.seed_dev,
-                            init_noise_buf=self.init_noise, r_all=self.r_all, ws=self.ws, row_offset_dev=self.row_offset_dev, pin=self._pin(), filt=self.filt)
+                            init_noise_buf=self.init_noise, r_all=self.r_all, ws=self.ws, row_offset_dev=self.row_offset_dev, pin=self._pin(), filt=self.filt,
+                            conf=self.conf)
+        stats = ()
+        if self.conf is not None and self.conf[2]:
+            toks, stats = toks[0], (toks[1],)
         toks = self._finish(toks)
-        return toks if self.vqgan is None else (toks, self.vqgan.decode_indices(toks, ws=self.vq_ws))
+        if self.vqgan is None:
+            return (toks, *stats) if stats else toks
+        return (toks, self.vqgan.decode_indices(toks, ws=self.vq_ws), *stats)
 
     @staticmethod
     def _copy_inputs(dst, src):
@@ -1079,10 +1224,18 @@ class RequestStream:
     side and every query carry bit 0.  Base + region rows must fit max_cond_rows.  Every admit writes both of its slots' rows of both tables, the all-visible
     default included, so a slot never inherits its predecessor's regions; `reset()` restores the default.  Contracts: a request's tokens at a given slot and B do
     not depend on its batch-mates' regions or on the tick it joined at; a request admitted with regions=None produces the tokens of the same stream built
-    without max_regions; a region whose mask is all zero changes nothing.  `captures` stays 1.  Not offered in the bf16 precision mode."""
+    without max_regions; a region whose mask is all zero changes nothing.  `captures` stays 1.  Not offered in the bf16 precision mode.
+
+    confidence=True (confidence-ordered renoise and statistics maps; default False: today's entry points and state): the stream owns policy int32 [B] and
+    confidence_noise fp32 [B] (every slot random), the logprob / entropy maps fp32 [B, H, W] and a [B, H, W, num_labels] logits buffer; its captured tick is
+    `request_step[_pin]` -> the logits forward -> the statistics tail (the filtered tail's draw plus the two maps; no renoise, no pin) -> the renoise stage, which
+    renoises every slot by its own policy and applies the pin.  `admit(renoise=, confidence_noise=)` writes the slot's row of both tables every time, the random
+    default included, so a slot never inherits its predecessor's policy; `reset()` writes the default everywhere; `result(slot, stats=True)` also returns the slot's
+    maps of its final draw.  A request's tokens and maps at a given slot and B do not depend on its batch-mates' policies or on the tick it joined at; a
+    renoise="random" request produces the tokens of a confidence=False stream.  Editing, filtering, max_cond_rows, max_attn_weights and max_regions combine unchanged."""
 
     def __init__(self, model, model_inputs, unconditional_inputs, latent_shape, max_steps=12, guided=True, device="cuda", vqgan=None, attn_weights=None,
-                 on_stale="recapture", max_cond_rows=None, editing=False, max_attn_weights=None, filtering=False, max_regions=None):
+                 on_stale="recapture", max_cond_rows=None, editing=False, max_attn_weights=None, filtering=False, max_regions=None, confidence=False):
         if on_stale not in ("recapture", "raise"):
             raise ValueError("on_stale must be 'recapture' or 'raise'")
         if not isinstance(model, Paella):
@@ -1153,6 +1306,16 @@ class RequestStream:
             self.filter_k = torch.tensor([FILTER_OFF[0], FILTER_OFF[3]], dtype=torch.int32).repeat(B, 1).to(dev)
             self.filter_mass = torch.tensor([FILTER_OFF[1], FILTER_OFF[2]], dtype=torch.float32).repeat(B, 1).to(dev)
             self.logits = torch.empty(B, H, W, model.num_labels, dtype=torch.float32, device=dev)
+        # confidence-ordered renoise: the policy tables and the statistics maps are stream state (every slot random); the tick materialises the logits as well
+        self.confidence = bool(confidence)
+        self.policy = self.confidence_noise = self.logprob = self.entropy = self._never = None
+        if self.confidence:
+            self.policy = torch.zeros(B, dtype=torch.int32, device=dev)
+            self.confidence_noise = torch.zeros(B, dtype=torch.float32, device=dev)
+            self.logprob, self.entropy = (torch.zeros(self.shape, dtype=torch.float32, device=dev) for _ in range(2))
+            self._never = torch.full((B,), -1.0, dtype=torch.float32, device=dev)  # the threshold table of the statistics tail: the renoise stage renoises
+            if self.logits is None:
+                self.logits = torch.empty(B, H, W, model.num_labels, dtype=torch.float32, device=dev)
         self.captures = 0
         self._capture()
 
@@ -1179,6 +1342,22 @@ class RequestStream:
                 _lib.check(_lib.load().paella_request_step(_lib.ptr(self.program), self.max_steps, _lib.ptr(self.pos), _lib.ptr(self.len), B, _lib.ptr(self.r),
                                                            _lib.ptr(self.temps), _lib.ptr(self.pairs), _lib.ptr(self.t_next), _lib.ptr(self.step),
                                                            _lib.ptr(self.active_dev), _lib.stream_ptr(self.device)))
+        if self.confidence:  # the logits forward + the statistics tail (raw draw, no pin) + the renoise stage (every slot's own policy, then the pin), in place
+            self.model.forward_prepared(self.tokens, self.r, self.cache, attn_weights=self.attn_weights, out=self.logits, ws=self.ws,
+                                        **({} if self.pairs is None else {"req_mix": self.pairs}), **({} if self.regions is None else {"regions": self.regions}))
+            pk, pt, po = (self.keep, self.known, self.pin_on) if self.editing else (None, None, None)
+            rows, hw = B * self.shape[1] * self.shape[2], self.shape[1] * self.shape[2]
+            with torch.cuda.device(self.device):
+                _lib.check(_lib.load().paella_sample_tail_stream_stats(_lib.ptr(self.logits), None, rows, self.model.num_labels, None, _lib.ptr(self.temps),
+                                                                       _lib.ptr(self.seeds), hw, _lib.ptr(self.step), _lib.ptr(self._never), _lib.ptr(self.active_dev),
+                                                                       _lib.ptr(self.random_x), None, None, None, _lib.ptr(self.filter_k), _lib.ptr(self.filter_mass),
+                                                                       _lib.ptr(self.tokens), None, _lib.ptr(self.logprob), _lib.ptr(self.entropy),
+                                                                       _lib.stream_ptr(self.device)))
+                _lib.check(_lib.load().paella_renoise_select_stream(_lib.ptr(self.tokens), _lib.ptr(self.logprob), _lib.ptr(self.random_x), rows, hw, _lib.ptr(self.seeds),
+                                                                    _lib.ptr(self.step), _lib.ptr(self.t_next), _lib.ptr(self.active_dev), _lib.ptr(self.policy),
+                                                                    _lib.ptr(self.confidence_noise), _lib.ptr(pk), _lib.ptr(pt), _lib.ptr(po), _lib.ptr(self.tokens),
+                                                                    _lib.stream_ptr(self.device)))
+            return
         if self.filtering:  # the logits forward (the guidance mix folded through the head: ONE [rows, L] tensor) + the filtered stream tail, in place as below
             self.model.forward_prepared(self.tokens, self.r, self.cache, attn_weights=self.attn_weights, out=self.logits, ws=self.ws,
                                         **({} if self.pairs is None else {"req_mix": self.pairs}), **({} if self.regions is None else {"regions": self.regions}))
@@ -1319,7 +1498,8 @@ class RequestStream:
         return plan, (torch.stack(masks) if masks else torch.zeros(0, H, W, dtype=torch.bool))
 
     def admit(self, model_inputs, unconditional_inputs=None, seed=None, steps=12, renoise_steps=None, temperature=(1.0, 0.2), cfg=8.0, t_start=1.0, t_end=0.0,
-              init_x=None, known=None, mask=None, image=None, pin="step", attn_weights=None, *, top_k=None, top_p=None, typical_mass=None, min_tokens=1, regions=None):
+              init_x=None, known=None, mask=None, image=None, pin="step", attn_weights=None, *, top_k=None, top_p=None, typical_mass=None, min_tokens=1, regions=None,
+              renoise="random", confidence_noise=0.0):
         """Put ONE request into a free slot; it runs from the next tick on.  Inputs: leading dimension 1, the stream's layout.  Schedule arguments as
         `request_program` (an unguided stream takes cfg=None); init_x int64 [H, W]: the tokens the request starts from instead of its seed's start tokens.
         Everything here is eager work on the current stream, ordered before the next tick: the conditioning of the one request is prepared straight into the
@@ -1334,13 +1514,18 @@ class RequestStream:
         slot's row of the stream's filter tables, "off" included.
         regions (a stream built with max_regions): [(inputs_r, mask_r), ...] -- more prompts of this request, each a conditioning dict of ONE prompt and a bool /
         integer mask [H, W] (1 = the prompt applies here); `model_inputs` stays the base prompt, visible everywhere.  Masks may overlap; an all-zero mask is a
-        no-op.  The unconditional side is never regional."""
+        no-op.  The unconditional side is never regional.
+        renoise / confidence_noise (`check_renoise`; renoise="confidence" needs a stream built with confidence=True): this request's renoise policy; every admit
+        writes its slot's row of the stream's two tables, the random default included."""
         B, H, W = self.shape
         region_plan, region_masks = self._check_regions(regions, model_inputs)
         known, mask, image = self._check_edit(known, mask, image, pin)
         filt = check_filter(top_k, top_p, typical_mass, min_tokens)
         if filter_on(filt) and not self.filtering:
             raise ValueError("%s needs a stream built with filtering=True (this one runs the fused tail, which sees no whole row)" % _filter_names(top_k, top_p, typical_mass))
+        policy, conf_g = check_renoise(renoise, confidence_noise)
+        if policy and not getattr(self, "confidence", False):
+            raise ValueError("renoise='confidence' needs a stream built with confidence=True (this one renoises inside its tail, one coin per position)")
         program, n = request_program(steps, renoise_steps, temperature, cfg, t_start, t_end, max_steps=self.max_steps, guided=self.guided)
         self._check_inputs(model_inputs, "model_inputs")
         if self.guided:
@@ -1392,6 +1577,9 @@ class RequestStream:
             if self.filtering:  # the slot's row, "off" included: its previous request leaves nothing behind
                 self.filter_k[b].copy_(torch.tensor([filt[0], filt[3]], dtype=torch.int32))
                 self.filter_mass[b].copy_(torch.tensor([filt[1], filt[2]], dtype=torch.float32))
+            if self.confidence:  # the slot's row, the random default included: its previous request leaves nothing behind
+                self.policy[b].fill_(policy)
+                self.confidence_noise[b].fill_(conf_g)
             if self.editing:
                 if mask is None:
                     self.keep[b].fill_(1)
@@ -1431,6 +1619,9 @@ class RequestStream:
             self.filter_k[:, 0].fill_(FILTER_OFF[0])
             self.filter_k[:, 1].fill_(FILTER_OFF[3])
             self.filter_mass.fill_(1.0)
+        if self.confidence:
+            self.policy.zero_()
+            self.confidence_noise.zero_()
         self._pos, self._len, self._held = [0] * B, [0] * B, [False] * B
 
     def tick(self, graph=True):
@@ -1452,19 +1643,23 @@ class RequestStream:
                 done.append(b)
         return done
 
-    def result(self, slot):
-        """The finished request of `slot`: its tokens [H, W] (a clone), with a VQGAN (tokens, image [3, f*H, f*W]) -- an eager decode of the one slot.  Frees the slot."""
+    def result(self, slot, stats=False):
+        """The finished request of `slot`: its tokens [H, W] (a clone), with a VQGAN (tokens, image [3, f*H, f*W]) -- an eager decode of the one slot.  Frees the slot.
+        stats=True (a stream built with confidence=True): the slot's {"logprob", "entropy"} maps fp32 [H, W] of its final draw (clones) come last in the result."""
         slot = int(slot)
         if not (0 <= slot < self.shape[0]) or not self._held[slot]:
             raise ValueError("slot %d holds no request" % slot)
         if self._pos[slot] < self._len[slot]:
             raise RuntimeError("the request of slot %d has %d step(s) to run" % (slot, self._len[slot] - self._pos[slot]))
+        if stats and not self.confidence:
+            raise ValueError("stats=True needs a stream built with confidence=True")
         toks = self.tokens[slot].clone()
+        maps = ({"logprob": self.logprob[slot].clone(), "entropy": self.entropy[slot].clone()},) if stats else ()
         self._held[slot] = False
         if self.vqgan is None:
-            return toks
+            return (toks, *maps) if maps else toks
         with torch.inference_mode():
-            return toks, self.vqgan.decode_indices(toks[None], ws=self.vq_ws)[0].clone()
+            return (toks, self.vqgan.decode_indices(toks[None], ws=self.vq_ws)[0].clone(), *maps)
 
     def drain(self, requests, graph=True):
         """Serve an iterable of requests (keyword dicts for `admit`): admit as slots free up, tick until everything is collected; yields (index, tokens) -- with a
