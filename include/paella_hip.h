@@ -487,6 +487,47 @@ int paella_renoise_select_stream(const int64_t* drawn, const float* logprob, con
                                  const float* confidence_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
                                  int64_t* tokens_out, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Argument blocks (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays 8): ONE forward and ONE sampling tail,
+ * each taking everything its family takes in a struct.  Zero / NULL = "not given"; which form runs follows from what is present, and
+ * every paella_unet_forward_shared*, paella_unet_forward_sample* and paella_sample_tail* entry point above is a fixed-form convenience
+ * that fills a block and calls the same runner -- same rules, same kernels, same launch arguments.  Both entry points refuse an
+ * args_bytes other than the library's sizeof(block) with PAELLA_ERR_ARG before reading anything else, read the block during the call
+ * only (no pointer to it is kept: it may live on the caller's stack, also while a graph is captured) and validate every rule before
+ * anything is enqueued.
+ * ---------------------------------------------------------------------------------------------- */
+/* A sampling tail.  rows_per_sample > 0 = the request form (seeds, temperature_tab required; the scalar-form fields other than offset and
+ * t_next are not read); step != NULL = its stream form (step, t_next_tab, active and init_noise all required; offset and t_next not read).
+ * Filter: the scalar form filters when any of the four values is non-zero (they are then the values of paella_sample_tail_filter:
+ * 1 = a mass that is off, min_tokens >= 1), the request form when the two tables are given.  A statistics output selects the statistics
+ * tail, a filter the filter tail, neither the plain (pin) tail. */
+typedef struct paella_tail_args {
+    const float *logits_c, *logits_u; int64_t rows; int32_t L;                                                      /* inputs [rows, L]; logits_u NULL = no guidance */
+    float cfg, one_minus_cfg, temperature; int32_t mode; uint64_t seed; const uint64_t* seed_ptr; uint64_t offset;  /* scalar form */
+    int64_t row_offset; const int64_t* row_offset_ptr; float t_next; const float *noise_q, *mask_u;
+    const uint64_t* seeds; const float *temperature_tab, *cfg_pairs; int32_t rows_per_sample;                       /* request tables */
+    const int32_t* step; const float* t_next_tab; const int32_t* active;                                            /* stream tables */
+    const int64_t *init_noise, *pin_keep, *pin_tokens; const int32_t* pin_on;                                       /* renoise source; pin */
+    int32_t top_k; float top_p, typical_mass; int32_t min_tokens; const int32_t* filter_k; const float* filter_mass; /* filter */
+    int64_t *tokens_out, *sampled_out; float *logprob_out, *entropy_out;                                            /* outputs */
+} paella_tail_args;
+
+/* One forward.  tail == NULL: the logits go to logits_out (mix_pairs, or a non-zero (mix_c, mix_u), folds the guidance mix through the
+ * head).  tail != NULL: the fused step of paella_unet_forward_sample*; the library fills the block's rows and L, reads neither its logits,
+ * cfg pair, caller-provided noise nor sampled_out, and refuses a filter or a statistics output (they need materialised logits); the
+ * request form needs rows_per_sample == H * W.  attn_weights (one vector) or kw_len / kw_table (one row per slot), not both; q_groups
+ * and k_groups both or neither. */
+typedef struct paella_step_args {
+    const int64_t* tokens; const float* r; const void* cond; int32_t B, n_unique; float mix_c, mix_u; const float* mix_pairs; int32_t H, W, S; const int32_t* cond_len;
+    const float* attn_weights; int32_t n_attn_weights;
+    const float* kw_table; const int32_t* kw_len; int32_t kw_pitch;
+    const int32_t* q_groups; int32_t qg_pitch; const int32_t* k_groups; int32_t kg_pitch;
+    float* logits_out; const paella_tail_args* tail;
+} paella_step_args;
+
+int paella_unet_step(paella_unet* m, const paella_step_args* args, size_t args_bytes, void* ws, size_t ws_bytes, void* stream);
+int paella_sample_tail_args(const paella_tail_args* args, size_t args_bytes, void* stream);
+
 /* x, random_x, mask int64 [B, per_sample]; t fp32 [B].  mask_in NULL -> mask = (u <= t[b]) with u = rand_u
  * (caller noise, [B, per_sample]) or Philox; random_x NULL -> Philox randint(0, num_labels). */
 int paella_add_noise(const int64_t* x, const float* t, const int64_t* mask_in, const int64_t* random_x,

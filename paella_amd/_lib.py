@@ -52,6 +52,39 @@ class TestGemmArgs(Structure):
     ]
 
 
+class TailArgs(Structure):
+    """include/paella_hip.h: paella_tail_args -- everything a sampling tail can take; zero / None = not given, the form follows from what is present"""
+    _fields_ = [
+        ("logits_c", c_void_p), ("logits_u", c_void_p), ("rows", c_int64), ("L", c_int32),
+        ("cfg", c_float), ("one_minus_cfg", c_float), ("temperature", c_float), ("mode", c_int32), ("seed", c_uint64), ("seed_ptr", c_void_p), ("offset", c_uint64),
+        ("row_offset", c_int64), ("row_offset_ptr", c_void_p), ("t_next", c_float), ("noise_q", c_void_p), ("mask_u", c_void_p),
+        ("seeds", c_void_p), ("temperature_tab", c_void_p), ("cfg_pairs", c_void_p), ("rows_per_sample", c_int32),
+        ("step", c_void_p), ("t_next_tab", c_void_p), ("active", c_void_p),
+        ("init_noise", c_void_p), ("pin_keep", c_void_p), ("pin_tokens", c_void_p), ("pin_on", c_void_p),
+        ("top_k", c_int32), ("top_p", c_float), ("typical_mass", c_float), ("min_tokens", c_int32), ("filter_k", c_void_p), ("filter_mass", c_void_p),
+        ("tokens_out", c_void_p), ("sampled_out", c_void_p), ("logprob_out", c_void_p), ("entropy_out", c_void_p),
+    ]
+
+
+class StepArgs(Structure):
+    """include/paella_hip.h: paella_step_args -- one forward; tail = None: logits to logits_out, otherwise the fused step"""
+    _fields_ = [
+        ("tokens", c_void_p), ("r", c_void_p), ("cond", c_void_p), ("B", c_int32), ("n_unique", c_int32), ("mix_c", c_float), ("mix_u", c_float), ("mix_pairs", c_void_p),
+        ("H", c_int32), ("W", c_int32), ("S", c_int32), ("cond_len", c_void_p),
+        ("attn_weights", c_void_p), ("n_attn_weights", c_int32),
+        ("kw_table", c_void_p), ("kw_len", c_void_p), ("kw_pitch", c_int32),
+        ("q_groups", c_void_p), ("qg_pitch", c_int32), ("k_groups", c_void_p), ("kg_pitch", c_int32),
+        ("logits_out", c_void_p), ("tail", POINTER(TailArgs)),
+    ]
+
+
+def tensor_fields(block, **tensors):
+    """set pointer fields of an argument block from tensors (None = not given)"""
+    for name, t in tensors.items():
+        setattr(block, name, None if t is None else t.data_ptr())
+    return block
+
+
 # name -> (restype, argtypes); this table is also what tests/test_abi.py checks against the header
 SIGNATURES = {
     "paella_abi_version": (c_int, []),
@@ -179,6 +212,9 @@ SIGNATURES = {
                                          c_float, c_void_p, c_void_p, c_int, c_float, c_float, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
     "paella_sample_tail_stream_stats": (c_int, [c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # the argument blocks (ABI 8, additive): one forward, one sampling tail; every forward_shared* / forward_sample* / sample_tail* above is a fixed form of these
+    "paella_unet_step": (c_int, [c_void_p, POINTER(StepArgs), c_size_t, c_void_p, c_size_t, c_void_p]),
+    "paella_sample_tail_args": (c_int, [POINTER(TailArgs), c_size_t, c_void_p]),
     "paella_renoise_select": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_uint64, c_void_p, c_uint64, c_int64, c_void_p, c_float, c_int, c_float, c_void_p,
                                       c_void_p, c_void_p, c_void_p]),
     "paella_renoise_select_stream": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,

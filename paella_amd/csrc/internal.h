@@ -1,6 +1,7 @@
 // Host-side helpers shared by model.hip (UNet) and vqmodel.hip (VQGAN).
 #pragma once
 #include "common.h"
+#include "../../include/paella_hip.h"
 #include <vector>
 
 #define RET_IF(expr)                      \
@@ -47,6 +48,32 @@ enum Repack {
     RP_CLF_W, RP_CLF_B, RP_TS_W, RP_TS_B  // handled by the UNet loader
 };
 int repack_into(Repack kind, const float* src, const std::vector<int64_t>& shape, DevBuf& dst, hipStream_t st);
+
+// Argument blocks (include/paella_hip.h: paella_tail_args / paella_step_args; tail.hip, model.hip).  What a fixed-form entry point's NAME promises on top of what
+// its block holds (a block alone takes its form from what is present): the request form, its stream tables, the scalar filter values, a guidance pair table.
+enum { kNeedRequest = 1, kNeedStream = 2, kNeedFilter = 4, kNeedPairs = 8 };
+int tail_pin_check(const char* who, const TailArgs& a);
+int tail_block_convert(const char* who, const paella_tail_args& t, int need, bool fused, TailArgs& a, TailFilter& f, TailStats& s, int* kind);
+// the two fillers of a tail block, from the parameter lists of the scalar and of the request / stream entry points (absent tables null)
+static inline paella_tail_args tail_block_scalar(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature, int mode,
+                                                 uint64_t seed, const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr,
+                                                 const int64_t* init_noise, float t_next, const int64_t* pin_keep, const int64_t* pin_tokens, int64_t* tokens_out,
+                                                 int64_t* sampled_out) {
+    paella_tail_args t = {};
+    t.logits_c = logits_c; t.logits_u = logits_u; t.rows = rows; t.L = L; t.cfg = cfg; t.one_minus_cfg = one_minus_cfg; t.temperature = temperature; t.mode = mode;
+    t.seed = seed; t.seed_ptr = seed_ptr; t.offset = offset; t.row_offset = row_offset; t.row_offset_ptr = row_offset_ptr; t.init_noise = init_noise; t.t_next = t_next;
+    t.pin_keep = pin_keep; t.pin_tokens = pin_tokens; t.tokens_out = tokens_out; t.sampled_out = sampled_out;
+    return t;
+}
+static inline paella_tail_args tail_block_stream(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
+                                                 const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active, const int64_t* init_noise,
+                                                 const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, int64_t* sampled_out) {
+    paella_tail_args t = {};
+    t.logits_c = logits_c; t.logits_u = logits_u; t.rows = rows; t.L = L; t.cfg_pairs = cfg_pairs; t.temperature_tab = temperature; t.seeds = seeds;
+    t.rows_per_sample = rows_per_sample; t.step = step; t.t_next_tab = t_next; t.active = active; t.init_noise = init_noise;
+    t.pin_keep = pin_keep; t.pin_tokens = pin_tokens; t.pin_on = pin_on; t.tokens_out = tokens_out; t.sampled_out = sampled_out;
+    return t;
+}
 
 static inline GemmArgs gemm_args(const float* A, int lda, const float* Wt, int ldw, float* C, int ldc, int M, int N, int K) {
     GemmArgs g;

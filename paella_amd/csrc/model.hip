@@ -915,10 +915,6 @@ struct KwTable {
     const int* len;      // DEVICE int32 [B]
     int pitch;
 };
-static int kw_table_check(const char* who, const float* kw_table, const int* kw_len, int kw_pitch) {
-    if (kw_len && (!kw_table || kw_pitch < 1)) { paella_set_error("%s: kw_len needs kw_table and kw_pitch >= 1", who); return PAELLA_ERR_ARG; }
-    return PAELLA_OK;
-}
 // Regional prompts: per-query key groups (AttnArgs::q_groups / k_groups) for every attention block of a forward.  q [nb, q_pitch] holds one row per conditioning
 // slot of the launch with the queries of all levels, level-major (level l at offset sum_{j<l} (H/patch)(W/patch)/4^j); k [nb, k_pitch] one mask per row of a slot.
 // q == nullptr = no tables.
@@ -1136,14 +1132,64 @@ static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float*
     return PAELLA_OK;
 }
 
-// Ragged conditioning (ABI 8): every forward entry point has a _ragged twin that takes `cond_len` right after S -- a DEVICE table [B] with the conditioning rows
-// of each sample, S then being the slot pitch of `cond` (attention.hip: attn_cond_rows).  Both forms are thin wrappers over the one unet_forward_impl.
+// ---------------------------------------------------------------------------
+// The argument block of one forward (include/paella_hip.h: paella_step_args).  run_step_block is the one place where a block's rules are checked -- all before anything is
+// enqueued, the model may still be null there -- and where it becomes a call of unet_forward_impl; a fused step's tail block goes through tail.hip: tail_block_convert.
+// Every paella_unet_forward_shared* / _sample* entry point below fills a block, names itself and runs it; need (internal.h: kNeed*) = what its name promises beyond the block.
+// ---------------------------------------------------------------------------
+static int run_step_block(const char* who, paella_unet* m, const paella_step_args& s, int need, void* ws, size_t ws_bytes, void* stream) {
+    if ((!s.tail && !s.logits_out) || ((need & kNeedPairs) && !s.mix_pairs)) { paella_set_error("%s: null argument (logits_out / mix_pairs)", who); return PAELLA_ERR_ARG; }
+    if (s.mix_pairs && (s.mix_c != 0.f || s.mix_u != 0.f)) { paella_set_error("%s: a guidance pair table and a scalar mix exclude each other", who); return PAELLA_ERR_ARG; }
+    if (s.kw_len && (!s.kw_table || s.kw_pitch < 1)) { paella_set_error("%s: kw_len needs kw_table and kw_pitch >= 1", who); return PAELLA_ERR_ARG; }
+    if (s.kw_len && s.attn_weights) { paella_set_error("%s: one attn_weights vector and the key-weight table exclude each other", who); return PAELLA_ERR_ARG; }
+    const RgTable rg = {s.q_groups, s.qg_pitch, s.k_groups, s.kg_pitch};
+    RET_IF(rg_table_check(who, m, rg, s.H, s.W, s.S));
+    TailArgs a;
+    if (s.tail) {
+        TailFilter f;
+        TailStats st;
+        int kind = 0;
+        RET_IF(tail_block_convert(who, *s.tail, need, true, a, f, st, &kind));
+        const bool mix = s.mix_pairs || s.mix_c != 0.f || s.mix_u != 0.f;
+        if (!mix && s.n_unique != s.B) {
+            paella_set_error("%s without a guidance mix needs n_unique == B (separate cond / uncond logits take the unfused path)", who);
+            return PAELLA_ERR_ARG;
+        }
+        if (a.rq.rows_per_sample > 0 && (s.H <= 0 || s.W <= 0 || a.rq.rows_per_sample != s.H * s.W)) {
+            paella_set_error("%s: rows_per_sample (%d) must equal H * W", who, a.rq.rows_per_sample);
+            return PAELLA_ERR_ARG;
+        }
+        a.rows = (int64_t)(mix ? s.n_unique : s.B) * s.H * s.W;  // with the guidance mix the head emits the n_unique mixed rows
+        a.L = m ? m->cfg.num_labels : 0;
+    }
+    return unet_forward_impl(m, s.tokens, s.r, s.cond, s.B, s.n_unique, s.mix_c, s.mix_u, s.H, s.W, s.S, s.attn_weights, s.n_attn_weights, s.tail ? nullptr : s.logits_out,
+                             s.tail ? &a : nullptr, ws, ws_bytes, stream, s.mix_pairs, s.cond_len, KwTable{s.kw_table, s.kw_len, s.kw_pitch}, rg);
+}
+
+extern "C" int paella_unet_step(paella_unet* m, const paella_step_args* args, size_t args_bytes, void* ws, size_t ws_bytes, void* stream) {
+    if (args_bytes != sizeof(paella_step_args)) { paella_set_error("unet_step: args_bytes %zu is not this library's sizeof(paella_step_args) = %zu", args_bytes, sizeof(paella_step_args)); return PAELLA_ERR_ARG; }
+    if (!args) { paella_set_error("unet_step: null argument"); return PAELLA_ERR_ARG; }
+    return run_step_block("unet_step", m, *args, 0, ws, ws_bytes, stream);
+}
+
+// ---- the fixed-form entry points.  One that extends another IS that one when what it adds is absent: it then reports under the other's name.
+// what every form takes; the guidance mix is (mix_c, mix_u) in the scalar forms and the pair table in the request forms
+static paella_step_args step_block(const int64_t* tokens, const float* r, const void* cond, int B, int n_unique, float mix_c, float mix_u, const float* mix_pairs, int H,
+                                   int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights) {
+    paella_step_args s = {};
+    s.tokens = tokens; s.r = r; s.cond = cond; s.B = B; s.n_unique = n_unique; s.mix_c = mix_c; s.mix_u = mix_u; s.mix_pairs = mix_pairs; s.H = H; s.W = W; s.S = S;
+    s.cond_len = cond_len; s.attn_weights = attn_weights; s.n_attn_weights = n_attn_weights;
+    return s;
+}
+
+// Ragged conditioning (ABI 8): `cond_len` right after S -- a DEVICE table [B] with the conditioning rows of each sample, S then being the slot pitch of `cond`
+// (attention.hip: attn_cond_rows)
 extern "C" int paella_unet_forward_shared_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                                  float mix_c, float mix_u, int H, int W, int S, const int* cond_len, const float* attn_weights,
                                                  int n_attn_weights, float* logits_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!logits_out) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
-    return unet_forward_impl(m, tokens, r, cond, B, n_unique, mix_c, mix_u, H, W, S, attn_weights, n_attn_weights, logits_out, nullptr, ws, ws_bytes, stream, nullptr,
-                             cond_len);
+    paella_step_args s = step_block(tokens, r, cond, B, n_unique, mix_c, mix_u, nullptr, H, W, S, cond_len, attn_weights, n_attn_weights);
+    s.logits_out = logits_out;
+    return run_step_block("forward_shared", m, s, 0, ws, ws_bytes, stream);
 }
 extern "C" int paella_unet_forward_shared(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                           float mix_c, float mix_u, int H, int W, int S, const float* attn_weights,
@@ -1153,35 +1199,17 @@ extern "C" int paella_unet_forward_shared(paella_unet* m, const int64_t* tokens,
 
 // One whole sampling step for the counter-based noise mode: Paella.forward + the sampling tail (src/utils.py:43-54) with the head
 // GEMM and the tail fused -- the [rows, num_labels] logits are never written.  Output rows: n_unique with the guidance mix
-// (B == 2 * n_unique, (mix_c, mix_u) != (0, 0)), otherwise B (no guidance; n_unique must equal B).
-// The optional pin of the sampling tail (common.h: TailArgs::pin_keep / pin_tokens / pin_on), validated BEFORE anything is enqueued: both row tables or neither,
-// the per-slot flags only with them, categorical mode only.
-static int pin_tables_check(const char* who, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on, int mode) {
-    if (!pin_keep != !pin_tokens) { paella_set_error("%s: pin_keep and pin_tokens must be given together (one pin table without the other)", who); return PAELLA_ERR_ARG; }
-    if (pin_on && !pin_keep) { paella_set_error("%s: pin_on without the pin_keep / pin_tokens row tables", who); return PAELLA_ERR_ARG; }
-    if (pin_keep && mode != 0) { paella_set_error("%s: the pin is not offered in argmax mode", who); return PAELLA_ERR_ARG; }
-    return PAELLA_OK;
-}
-
+// (B == 2 * n_unique, (mix_c, mix_u) != (0, 0)), otherwise B (no guidance; n_unique must equal B).  The pin tables (common.h: TailArgs::pin_keep / pin_tokens) optional.
 extern "C" int paella_unet_forward_sample_pin(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                               float mix_c, float mix_u, int H, int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights,
                                               float temperature, int mode, uint64_t seed, const uint64_t* seed_ptr, uint64_t offset,
                                               int64_t row_offset, const int64_t* row_offset_ptr, const int64_t* init_noise, float t_next,
                                               const int64_t* pin_keep, const int64_t* pin_tokens, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!tokens_out) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
-    RET_IF(pin_tables_check("forward_sample", pin_keep, pin_tokens, nullptr, mode));
-    const bool mix = mix_c != 0.f || mix_u != 0.f;
-    if (!mix && n_unique != B) { paella_set_error("forward_sample without a guidance mix needs n_unique == B (separate cond / uncond logits take the unfused path)"); return PAELLA_ERR_ARG; }
-    if (mode == 0 && !(temperature > 0.f)) { paella_set_error("temperature must be > 0 in categorical mode (use mode=1 for argmax)"); return PAELLA_ERR_ARG; }
-    if (row_offset < 0) { paella_set_error("row_offset must be >= 0"); return PAELLA_ERR_ARG; }
-    TailArgs a;
-    a.logits_c = nullptr; a.logits_u = nullptr;
-    a.rows = (int64_t)(mix ? n_unique : B) * H * W;
-    a.L = m ? m->cfg.num_labels : 0;
-    a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = temperature; a.mode = mode; a.noise_q = nullptr; a.seed = seed; a.seed_ptr = seed_ptr;
-    a.offset = offset; a.row_offset = row_offset; a.row_offset_ptr = row_offset_ptr; a.init_noise = init_noise; a.mask_u = nullptr; a.t_next = t_next;
-    a.tokens_out = tokens_out; a.sampled_out = nullptr; a.pin_keep = pin_keep; a.pin_tokens = pin_tokens;
-    return unet_forward_impl(m, tokens, r, cond, B, n_unique, mix_c, mix_u, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, nullptr, cond_len);
+    const paella_tail_args t = tail_block_scalar(nullptr, nullptr, 0, 0, 1.f, 0.f, temperature, mode, seed, seed_ptr, offset, row_offset, row_offset_ptr, init_noise, t_next,
+                                                 pin_keep, pin_tokens, tokens_out, nullptr);
+    paella_step_args s = step_block(tokens, r, cond, B, n_unique, mix_c, mix_u, nullptr, H, W, S, cond_len, attn_weights, n_attn_weights);
+    s.tail = &t;
+    return run_step_block("forward_sample", m, s, 0, ws, ws_bytes, stream);
 }
 extern "C" int paella_unet_forward_sample_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                                  float mix_c, float mix_u, int H, int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights,
@@ -1200,36 +1228,13 @@ extern "C" int paella_unet_forward_sample(paella_unet* m, const int64_t* tokens,
                                              seed_ptr, offset, row_offset, row_offset_ptr, init_noise, t_next, tokens_out, ws, ws_bytes, stream);
 }
 
-// Request batch (ABI 6): the same two entry points with per-sample device tables (common.h: ReqTables).
+// Request batch (ABI 6): the logits forward with one guidance pair per sample (required here)
 extern "C" int paella_unet_forward_shared_req_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                                      const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights,
                                                      float* logits_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!logits_out || !mix_pairs) { paella_set_error("forward_shared_req: null argument (logits_out / mix_pairs)"); return PAELLA_ERR_ARG; }
-    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, logits_out, nullptr, ws, ws_bytes, stream, mix_pairs,
-                             cond_len);
-}
-// Per-request prompt weights: the logits entry point of the family with the key-weight table in place of (attn_weights, n_attn_weights); mix_pairs may be NULL here
-// (no guidance mix: the B rows of logits, n_unique dividing B as in paella_unet_forward_shared).  kw_len == NULL: the entry point above (or the unmixed forward).
-extern "C" int paella_unet_forward_shared_req_kw(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
-                                                 const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table, const int* kw_len,
-                                                 int kw_pitch, float* logits_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!logits_out) { paella_set_error("forward_shared_req_kw: null argument (logits_out)"); return PAELLA_ERR_ARG; }
-    RET_IF(kw_table_check("forward_shared_req_kw", kw_table, kw_len, kw_pitch));
-    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, nullptr, 0, logits_out, nullptr, ws, ws_bytes, stream, mix_pairs, cond_len,
-                             KwTable{kw_table, kw_len, kw_pitch});
-}
-// Regional prompts: the most general logits entry point -- the _kw one plus the key-group tables (both NULL: exactly the _kw entry point)
-extern "C" int paella_unet_forward_shared_req_rg(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
-                                                 const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table, const int* kw_len,
-                                                 int kw_pitch, const int* q_groups, int qg_pitch, const int* k_groups, int kg_pitch, float* logits_out, void* ws,
-                                                 size_t ws_bytes, void* stream) {
-    if (!q_groups && !k_groups)
-        return paella_unet_forward_shared_req_kw(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, kw_table, kw_len, kw_pitch, logits_out, ws, ws_bytes, stream);
-    if (!logits_out) { paella_set_error("forward_shared_req_rg: null argument (logits_out)"); return PAELLA_ERR_ARG; }
-    RET_IF(kw_table_check("forward_shared_req_rg", kw_table, kw_len, kw_pitch));
-    RET_IF(rg_table_check("forward_shared_req_rg", m, RgTable{q_groups, qg_pitch, k_groups, kg_pitch}, H, W, S));
-    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, nullptr, 0, logits_out, nullptr, ws, ws_bytes, stream, mix_pairs, cond_len,
-                             KwTable{kw_table, kw_len, kw_pitch}, RgTable{q_groups, qg_pitch, k_groups, kg_pitch});
+    paella_step_args s = step_block(tokens, r, cond, B, n_unique, 0.f, 0.f, mix_pairs, H, W, S, cond_len, attn_weights, n_attn_weights);
+    s.logits_out = logits_out;
+    return run_step_block("forward_shared_req", m, s, kNeedPairs, ws, ws_bytes, stream);
 }
 extern "C" int paella_unet_forward_shared_req(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                               const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
@@ -1237,40 +1242,35 @@ extern "C" int paella_unet_forward_shared_req(paella_unet* m, const int64_t* tok
     return paella_unet_forward_shared_req_ragged(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, nullptr, attn_weights, n_attn_weights, logits_out, ws, ws_bytes,
                                                  stream);
 }
-
-// the request form of the fused step; the pin tables (all nullable) and the key-weight table are what the _kw entry point adds
-static int forward_sample_req_impl(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique, const float* mix_pairs, int H, int W,
-                                   int S, const int* cond_len, const float* attn_weights, int n_attn_weights, KwTable kw, const uint64_t* seeds,
-                                   const float* temperature, int rows_per_sample, uint64_t offset, const int64_t* init_noise, float t_next, const int64_t* pin_keep,
-                                   const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!tokens_out || !seeds || !temperature) { paella_set_error("forward_sample_req: null argument (tokens_out / seeds / temperature)"); return PAELLA_ERR_ARG; }
-    RET_IF(pin_tables_check("forward_sample_req", pin_keep, pin_tokens, pin_on, 0));
-    if (!mix_pairs && n_unique != B) { paella_set_error("forward_sample_req without guidance pairs needs n_unique == B"); return PAELLA_ERR_ARG; }
-    if (H <= 0 || W <= 0 || rows_per_sample != H * W) { paella_set_error("forward_sample_req: rows_per_sample (%d) must equal H * W", rows_per_sample); return PAELLA_ERR_ARG; }
-    TailArgs a = {};
-    a.rows = (int64_t)(mix_pairs ? n_unique : B) * H * W;
-    a.L = m ? m->cfg.num_labels : 0;
-    a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f; a.offset = offset; a.init_noise = init_noise; a.t_next = t_next; a.tokens_out = tokens_out;
-    a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.rows_per_sample = rows_per_sample;  // (the guidance pairs ride through the head: none left for the tail)
-    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens; a.pin_on = pin_on;
-    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, mix_pairs, cond_len, kw);
+// Per-request prompt weights and regional prompts: the most general logits entry point -- the key-weight table in place of (attn_weights, n_attn_weights) and the
+// key-group tables; mix_pairs may be NULL here (no guidance mix: the B rows of logits, n_unique dividing B as in paella_unet_forward_shared)
+extern "C" int paella_unet_forward_shared_req_rg(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                 const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table, const int* kw_len,
+                                                 int kw_pitch, const int* q_groups, int qg_pitch, const int* k_groups, int kg_pitch, float* logits_out, void* ws,
+                                                 size_t ws_bytes, void* stream) {
+    paella_step_args s = step_block(tokens, r, cond, B, n_unique, 0.f, 0.f, mix_pairs, H, W, S, cond_len, nullptr, 0);
+    s.kw_table = kw_table; s.kw_len = kw_len; s.kw_pitch = kw_pitch; s.q_groups = q_groups; s.qg_pitch = qg_pitch; s.k_groups = k_groups; s.kg_pitch = kg_pitch;
+    s.logits_out = logits_out;
+    return run_step_block(q_groups || k_groups ? "forward_shared_req_rg" : "forward_shared_req_kw", m, s, 0, ws, ws_bytes, stream);
 }
+extern "C" int paella_unet_forward_shared_req_kw(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                 const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table, const int* kw_len,
+                                                 int kw_pitch, float* logits_out, void* ws, size_t ws_bytes, void* stream) {
+    return paella_unet_forward_shared_req_rg(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, kw_table, kw_len, kw_pitch, nullptr, 0, nullptr, 0, logits_out, ws,
+                                             ws_bytes, stream);
+}
+
+// the request form of the fused step (the guidance pairs ride through the head: none left for the tail)
 extern "C" int paella_unet_forward_sample_req_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                                      const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights,
                                                      const uint64_t* seeds, const float* temperature, int rows_per_sample, uint64_t offset,
                                                      const int64_t* init_noise, float t_next, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
-    return forward_sample_req_impl(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, attn_weights, n_attn_weights, KwTable{nullptr, nullptr, 0}, seeds,
-                                   temperature, rows_per_sample, offset, init_noise, t_next, nullptr, nullptr, nullptr, tokens_out, ws, ws_bytes, stream);
-}
-// Per-request prompt weights: the key-weight table in place of (attn_weights, n_attn_weights), plus the (nullable) pin tables of the sampling tail.
-extern "C" int paella_unet_forward_sample_req_kw(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
-                                                 const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table, const int* kw_len,
-                                                 int kw_pitch, const uint64_t* seeds, const float* temperature, int rows_per_sample, uint64_t offset,
-                                                 const int64_t* init_noise, float t_next, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
-                                                 int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
-    RET_IF(kw_table_check("forward_sample_req_kw", kw_table, kw_len, kw_pitch));
-    return forward_sample_req_impl(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, nullptr, 0, KwTable{kw_table, kw_len, kw_pitch}, seeds, temperature,
-                                   rows_per_sample, offset, init_noise, t_next, pin_keep, pin_tokens, pin_on, tokens_out, ws, ws_bytes, stream);
+    paella_tail_args t = tail_block_stream(nullptr, nullptr, 0, 0, nullptr, temperature, seeds, rows_per_sample, nullptr, nullptr, nullptr, init_noise, nullptr, nullptr,
+                                           nullptr, tokens_out, nullptr);
+    t.offset = offset; t.t_next = t_next;
+    paella_step_args s = step_block(tokens, r, cond, B, n_unique, 0.f, 0.f, mix_pairs, H, W, S, cond_len, attn_weights, n_attn_weights);
+    s.tail = &t;
+    return run_step_block("forward_sample_req", m, s, kNeedRequest, ws, ws_bytes, stream);
 }
 extern "C" int paella_unet_forward_sample_req(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                               const float* mix_pairs, int H, int W, int S, const float* attn_weights, int n_attn_weights,
@@ -1279,80 +1279,32 @@ extern "C" int paella_unet_forward_sample_req(paella_unet* m, const int64_t* tok
     return paella_unet_forward_sample_req_ragged(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, nullptr, attn_weights, n_attn_weights, seeds, temperature,
                                                  rows_per_sample, offset, init_noise, t_next, tokens_out, ws, ws_bytes, stream);
 }
-
-extern "C" int paella_sample_tail_req(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
-                                      const uint64_t* seeds, int rows_per_sample, uint64_t offset, const int64_t* init_noise, float t_next,
-                                      int64_t* tokens_out, int64_t* sampled_out, void* stream) {
-    if (!logits_c || !tokens_out || !seeds || !temperature) { paella_set_error("sample_tail_req: null argument"); return PAELLA_ERR_ARG; }
-    if (rows_per_sample <= 0) { paella_set_error("sample_tail_req: rows_per_sample must be > 0"); return PAELLA_ERR_ARG; }
-    TailArgs a = {};
-    a.logits_c = logits_c; a.logits_u = cfg_pairs ? logits_u : nullptr; a.rows = rows; a.L = L; a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f;
-    a.offset = offset; a.init_noise = init_noise; a.t_next = t_next; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
-    a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.cfg_pairs = cfg_pairs; a.rq.rows_per_sample = rows_per_sample;
-    return launch_sample_tail(a, (hipStream_t)stream);
+// Per-request prompt weights: the key-weight table in place of (attn_weights, n_attn_weights), plus the (nullable) pin tables of the sampling tail.
+extern "C" int paella_unet_forward_sample_req_kw(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                 const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table, const int* kw_len,
+                                                 int kw_pitch, const uint64_t* seeds, const float* temperature, int rows_per_sample, uint64_t offset,
+                                                 const int64_t* init_noise, float t_next, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
+                                                 int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+    paella_tail_args t = tail_block_stream(nullptr, nullptr, 0, 0, nullptr, temperature, seeds, rows_per_sample, nullptr, nullptr, nullptr, init_noise, pin_keep, pin_tokens,
+                                           pin_on, tokens_out, nullptr);
+    t.offset = offset; t.t_next = t_next;
+    paella_step_args s = step_block(tokens, r, cond, B, n_unique, 0.f, 0.f, mix_pairs, H, W, S, cond_len, nullptr, 0);
+    s.kw_table = kw_table; s.kw_len = kw_len; s.kw_pitch = kw_pitch; s.tail = &t;
+    return run_step_block("forward_sample_req_kw", m, s, kNeedRequest, ws, ws_bytes, stream);
 }
 
-// Request stream (ABI 7): the request forms with the three per-request stream tables (common.h: ReqTables::step / t_next / active), all required here.
-static int stream_tables_check(const char* who, const int* step, const float* t_next_tab, const int* active, const int64_t* init_noise) {
-    if (!step || !t_next_tab || !active || !init_noise) {
-        paella_set_error("%s: null argument (the step, t_next and active tables and init_noise, the renoise source of every slot, are required)", who);
-        return PAELLA_ERR_ARG;
-    }
-    return PAELLA_OK;
-}
-
-static int forward_sample_stream_impl(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique, const float* mix_pairs, int H,
-                                      int W, int S, const int* cond_len, const float* attn_weights, int n_attn_weights, KwTable kw, const uint64_t* seeds,
-                                      const float* temperature, int rows_per_sample, const int* step, const float* t_next, const int* active,
-                                      const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, void* ws,
-                                      size_t ws_bytes, void* stream, RgTable rg = {nullptr, 0, nullptr, 0}) {
-    if (!tokens_out || !seeds || !temperature) { paella_set_error("forward_sample_stream: null argument (tokens_out / seeds / temperature)"); return PAELLA_ERR_ARG; }
-    RET_IF(stream_tables_check("forward_sample_stream", step, t_next, active, init_noise));
-    RET_IF(pin_tables_check("forward_sample_stream", pin_keep, pin_tokens, pin_on, 0));
-    if (!mix_pairs && n_unique != B) { paella_set_error("forward_sample_stream without guidance pairs needs n_unique == B"); return PAELLA_ERR_ARG; }
-    if (H <= 0 || W <= 0 || rows_per_sample != H * W) { paella_set_error("forward_sample_stream: rows_per_sample (%d) must equal H * W", rows_per_sample); return PAELLA_ERR_ARG; }
-    TailArgs a = {};
-    a.rows = (int64_t)(mix_pairs ? n_unique : B) * H * W;
-    a.L = m ? m->cfg.num_labels : 0;
-    a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f; a.init_noise = init_noise; a.t_next = -1.f; a.tokens_out = tokens_out;
-    a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.rows_per_sample = rows_per_sample;
-    a.rq.step = step; a.rq.t_next = t_next; a.rq.active = active;
-    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens; a.pin_on = pin_on;
-    return unet_forward_impl(m, tokens, r, cond, B, n_unique, 0.f, 0.f, H, W, S, attn_weights, n_attn_weights, nullptr, &a, ws, ws_bytes, stream, mix_pairs, cond_len, kw, rg);
-}
+// Request stream (ABI 7): the request form with the three per-request stream tables (common.h: ReqTables::step / t_next / active), all required here; the pin tables
+// optional
 extern "C" int paella_unet_forward_sample_stream_pin(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                                      const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights,
                                                      int n_attn_weights, const uint64_t* seeds, const float* temperature, int rows_per_sample, const int* step,
                                                      const float* t_next, const int* active, const int64_t* init_noise, const int64_t* pin_keep,
                                                      const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
-    return forward_sample_stream_impl(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, attn_weights, n_attn_weights, KwTable{nullptr, nullptr, 0}, seeds,
-                                      temperature, rows_per_sample, step, t_next, active, init_noise, pin_keep, pin_tokens, pin_on, tokens_out, ws, ws_bytes, stream);
-}
-// Per-request prompt weights: the tick of a stream whose slots carry their own key weights -- the key-weight table in place of (attn_weights, n_attn_weights).
-extern "C" int paella_unet_forward_sample_stream_kw(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
-                                                    const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table, const int* kw_len,
-                                                    int kw_pitch, const uint64_t* seeds, const float* temperature, int rows_per_sample, const int* step,
-                                                    const float* t_next, const int* active, const int64_t* init_noise, const int64_t* pin_keep,
-                                                    const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
-    RET_IF(kw_table_check("forward_sample_stream_kw", kw_table, kw_len, kw_pitch));
-    return forward_sample_stream_impl(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, nullptr, 0, KwTable{kw_table, kw_len, kw_pitch}, seeds, temperature,
-                                      rows_per_sample, step, t_next, active, init_noise, pin_keep, pin_tokens, pin_on, tokens_out, ws, ws_bytes, stream);
-}
-// Regional prompts: the most general tick of a stream -- the _kw one plus the key-group tables (both NULL: exactly the _kw entry point)
-extern "C" int paella_unet_forward_sample_stream_rg(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
-                                                    const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table, const int* kw_len,
-                                                    int kw_pitch, const int* q_groups, int qg_pitch, const int* k_groups, int kg_pitch, const uint64_t* seeds,
-                                                    const float* temperature, int rows_per_sample, const int* step, const float* t_next, const int* active,
-                                                    const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
-                                                    int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
-    if (!q_groups && !k_groups)
-        return paella_unet_forward_sample_stream_kw(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, kw_table, kw_len, kw_pitch, seeds, temperature,
-                                                    rows_per_sample, step, t_next, active, init_noise, pin_keep, pin_tokens, pin_on, tokens_out, ws, ws_bytes, stream);
-    RET_IF(kw_table_check("forward_sample_stream_rg", kw_table, kw_len, kw_pitch));
-    RET_IF(rg_table_check("forward_sample_stream_rg", m, RgTable{q_groups, qg_pitch, k_groups, kg_pitch}, H, W, S));
-    return forward_sample_stream_impl(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, nullptr, 0, KwTable{kw_table, kw_len, kw_pitch}, seeds, temperature,
-                                      rows_per_sample, step, t_next, active, init_noise, pin_keep, pin_tokens, pin_on, tokens_out, ws, ws_bytes, stream,
-                                      RgTable{q_groups, qg_pitch, k_groups, kg_pitch});
+    const paella_tail_args t = tail_block_stream(nullptr, nullptr, 0, 0, nullptr, temperature, seeds, rows_per_sample, step, t_next, active, init_noise, pin_keep,
+                                                 pin_tokens, pin_on, tokens_out, nullptr);
+    paella_step_args s = step_block(tokens, r, cond, B, n_unique, 0.f, 0.f, mix_pairs, H, W, S, cond_len, attn_weights, n_attn_weights);
+    s.tail = &t;
+    return run_step_block("forward_sample_stream", m, s, kNeedStream, ws, ws_bytes, stream);
 }
 extern "C" int paella_unet_forward_sample_stream_ragged(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
                                                         const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* attn_weights,
@@ -1370,52 +1322,28 @@ extern "C" int paella_unet_forward_sample_stream(paella_unet* m, const int64_t* 
     return paella_unet_forward_sample_stream_ragged(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, nullptr, attn_weights, n_attn_weights, seeds, temperature,
                                                     rows_per_sample, step, t_next, active, init_noise, tokens_out, ws, ws_bytes, stream);
 }
-
-extern "C" int paella_sample_tail_stream_pin(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
-                                             const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active,
-                                             const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
-                                             int64_t* tokens_out, int64_t* sampled_out, void* stream) {
-    if (!logits_c || !tokens_out || !seeds || !temperature) { paella_set_error("sample_tail_stream: null argument"); return PAELLA_ERR_ARG; }
-    RET_IF(stream_tables_check("sample_tail_stream", step, t_next, active, init_noise));
-    RET_IF(pin_tables_check("sample_tail_stream", pin_keep, pin_tokens, pin_on, 0));
-    if (rows_per_sample <= 0) { paella_set_error("sample_tail_stream: rows_per_sample must be > 0"); return PAELLA_ERR_ARG; }
-    TailArgs a = {};
-    a.logits_c = logits_c; a.logits_u = cfg_pairs ? logits_u : nullptr; a.rows = rows; a.L = L; a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f;
-    a.init_noise = init_noise; a.t_next = -1.f; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
-    a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.cfg_pairs = cfg_pairs; a.rq.rows_per_sample = rows_per_sample;
-    a.rq.step = step; a.rq.t_next = t_next; a.rq.active = active;
-    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens; a.pin_on = pin_on;
-    return launch_sample_tail(a, (hipStream_t)stream);
+// Per-request prompt weights and regional prompts: the most general tick of a stream -- the key-weight table in place of (attn_weights, n_attn_weights) and the
+// key-group tables
+extern "C" int paella_unet_forward_sample_stream_rg(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                    const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table, const int* kw_len,
+                                                    int kw_pitch, const int* q_groups, int qg_pitch, const int* k_groups, int kg_pitch, const uint64_t* seeds,
+                                                    const float* temperature, int rows_per_sample, const int* step, const float* t_next, const int* active,
+                                                    const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
+                                                    int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+    const paella_tail_args t = tail_block_stream(nullptr, nullptr, 0, 0, nullptr, temperature, seeds, rows_per_sample, step, t_next, active, init_noise, pin_keep,
+                                                 pin_tokens, pin_on, tokens_out, nullptr);
+    paella_step_args s = step_block(tokens, r, cond, B, n_unique, 0.f, 0.f, mix_pairs, H, W, S, cond_len, nullptr, 0);
+    s.kw_table = kw_table; s.kw_len = kw_len; s.kw_pitch = kw_pitch; s.q_groups = q_groups; s.qg_pitch = qg_pitch; s.k_groups = k_groups; s.kg_pitch = kg_pitch;
+    s.tail = &t;
+    return run_step_block(q_groups || k_groups ? "forward_sample_stream_rg" : "forward_sample_stream_kw", m, s, kNeedStream, ws, ws_bytes, stream);
 }
-// paella_sample_tail_stream_pin with the per-request filter tables (common.h: TailFilter), the most general member of the family: both tables NULL = the launch of
-// paella_sample_tail_stream_pin
-extern "C" int paella_sample_tail_stream_filter(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
-                                                const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active,
-                                                const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
-                                                const int* filter_k, const float* filter_mass, int64_t* tokens_out, int64_t* sampled_out, void* stream) {
-    if (!filter_k && !filter_mass)
-        return paella_sample_tail_stream_pin(logits_c, logits_u, rows, L, cfg_pairs, temperature, seeds, rows_per_sample, step, t_next, active, init_noise, pin_keep,
-                                             pin_tokens, pin_on, tokens_out, sampled_out, stream);
-    if (!logits_c || !tokens_out || !seeds || !temperature) { paella_set_error("sample_tail_stream_filter: null argument"); return PAELLA_ERR_ARG; }
-    if (!filter_k != !filter_mass) { paella_set_error("sample_tail_stream_filter: filter_k and filter_mass must be given together (one filter table without the other)"); return PAELLA_ERR_ARG; }
-    RET_IF(stream_tables_check("sample_tail_stream_filter", step, t_next, active, init_noise));
-    RET_IF(pin_tables_check("sample_tail_stream_filter", pin_keep, pin_tokens, pin_on, 0));
-    if (rows_per_sample <= 0) { paella_set_error("sample_tail_stream_filter: rows_per_sample must be > 0"); return PAELLA_ERR_ARG; }
-    TailArgs a = {};
-    a.logits_c = logits_c; a.logits_u = cfg_pairs ? logits_u : nullptr; a.rows = rows; a.L = L; a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f;
-    a.init_noise = init_noise; a.t_next = -1.f; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
-    a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.cfg_pairs = cfg_pairs; a.rq.rows_per_sample = rows_per_sample;
-    a.rq.step = step; a.rq.t_next = t_next; a.rq.active = active;
-    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens; a.pin_on = pin_on;
-    TailFilter f;
-    f.filter_k = filter_k; f.filter_mass = filter_mass;
-    return launch_sample_tail_filter(a, f, (hipStream_t)stream);
-}
-extern "C" int paella_sample_tail_stream(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
-                                         const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active,
-                                         const int64_t* init_noise, int64_t* tokens_out, int64_t* sampled_out, void* stream) {
-    return paella_sample_tail_stream_pin(logits_c, logits_u, rows, L, cfg_pairs, temperature, seeds, rows_per_sample, step, t_next, active, init_noise, nullptr, nullptr,
-                                         nullptr, tokens_out, sampled_out, stream);
+extern "C" int paella_unet_forward_sample_stream_kw(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
+                                                    const float* mix_pairs, int H, int W, int S, const int* cond_len, const float* kw_table, const int* kw_len,
+                                                    int kw_pitch, const uint64_t* seeds, const float* temperature, int rows_per_sample, const int* step,
+                                                    const float* t_next, const int* active, const int64_t* init_noise, const int64_t* pin_keep,
+                                                    const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, void* ws, size_t ws_bytes, void* stream) {
+    return paella_unet_forward_sample_stream_rg(m, tokens, r, cond, B, n_unique, mix_pairs, H, W, S, cond_len, kw_table, kw_len, kw_pitch, nullptr, 0, nullptr, 0, seeds,
+                                                temperature, rows_per_sample, step, t_next, active, init_noise, pin_keep, pin_tokens, pin_on, tokens_out, ws, ws_bytes, stream);
 }
 
 extern "C" int paella_request_step(const float* program, int max_steps, int* pos, const int* len, int B, float* r, float* temperature, float* pairs,
@@ -1434,70 +1362,8 @@ extern "C" int paella_start_tokens_req(const uint64_t* seeds, int B, int rows_pe
 }
 
 // ---------------------------------------------------------------------------
-// sampling tail / add_noise / single-op entry points
+// start tokens / add_noise / single-op entry points (the sampling tails: tail.hip)
 // ---------------------------------------------------------------------------
-extern "C" int paella_sample_tail_ex(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg,
-                                     float temperature, int mode, const float* noise_q, uint64_t seed, const uint64_t* seed_ptr,
-                                     uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr, const int64_t* init_noise, const float* mask_u,
-                                     float t_next, int64_t* tokens_out, int64_t* sampled_out, void* stream) {
-    if (!logits_c || !tokens_out) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
-    if (mode == 0 && !(temperature > 0.f)) { paella_set_error("temperature must be > 0 in categorical mode (use mode=1 for argmax)"); return PAELLA_ERR_ARG; }
-    if (row_offset < 0) { paella_set_error("row_offset must be >= 0"); return PAELLA_ERR_ARG; }
-    TailArgs a;
-    a.logits_c = logits_c; a.logits_u = logits_u; a.rows = rows; a.L = L; a.cfg = cfg; a.one_minus_cfg = one_minus_cfg;
-    a.temperature = temperature; a.mode = mode; a.noise_q = noise_q; a.seed = seed; a.seed_ptr = seed_ptr; a.offset = offset;
-    a.row_offset = row_offset; a.row_offset_ptr = row_offset_ptr;
-    a.init_noise = init_noise; a.mask_u = mask_u; a.t_next = t_next; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
-    return launch_sample_tail(a, (hipStream_t)stream);
-}
-
-// paella_sample_tail_ex in the counter-based noise mode with the optional pin: tokens_out[row] = pin_keep[row] == 0 ? pin_tokens[row] : the renoised draw
-extern "C" int paella_sample_tail_pin(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature, int mode,
-                                      uint64_t seed, const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr,
-                                      const int64_t* init_noise, float t_next, const int64_t* pin_keep, const int64_t* pin_tokens, int64_t* tokens_out,
-                                      int64_t* sampled_out, void* stream) {
-    if (!logits_c || !tokens_out) { paella_set_error("sample_tail_pin: null argument"); return PAELLA_ERR_ARG; }
-    if (mode == 0 && !(temperature > 0.f)) { paella_set_error("temperature must be > 0 in categorical mode (use mode=1 for argmax)"); return PAELLA_ERR_ARG; }
-    if (row_offset < 0) { paella_set_error("row_offset must be >= 0"); return PAELLA_ERR_ARG; }
-    RET_IF(pin_tables_check("sample_tail_pin", pin_keep, pin_tokens, nullptr, mode));
-    TailArgs a = {};
-    a.logits_c = logits_c; a.logits_u = logits_u; a.rows = rows; a.L = L; a.cfg = cfg; a.one_minus_cfg = one_minus_cfg;
-    a.temperature = temperature; a.mode = mode; a.seed = seed; a.seed_ptr = seed_ptr; a.offset = offset;
-    a.row_offset = row_offset; a.row_offset_ptr = row_offset_ptr;
-    a.init_noise = init_noise; a.t_next = t_next; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
-    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens;
-    return launch_sample_tail(a, (hipStream_t)stream);
-}
-
-// paella_sample_tail_pin with a truncation filter (common.h: TailFilter; top_k <= 0 or >= L, top_p = 1, typical_mass = 1 are "off"): categorical mode only
-extern "C" int paella_sample_tail_filter(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature, int mode,
-                                         uint64_t seed, const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr,
-                                         const int64_t* init_noise, float t_next, const int64_t* pin_keep, const int64_t* pin_tokens, int top_k, float top_p,
-                                         float typical_mass, int min_tokens, int64_t* tokens_out, int64_t* sampled_out, void* stream) {
-    if (!logits_c || !tokens_out) { paella_set_error("sample_tail_filter: null argument"); return PAELLA_ERR_ARG; }
-    if (mode != 0) { paella_set_error("sample_tail_filter: the filter is not offered in argmax mode"); return PAELLA_ERR_ARG; }
-    if (!(temperature > 0.f)) { paella_set_error("temperature must be > 0 in categorical mode (use mode=1 for argmax)"); return PAELLA_ERR_ARG; }
-    if (row_offset < 0) { paella_set_error("row_offset must be >= 0"); return PAELLA_ERR_ARG; }
-    RET_IF(pin_tables_check("sample_tail_filter", pin_keep, pin_tokens, nullptr, mode));
-    TailArgs a = {};
-    a.logits_c = logits_c; a.logits_u = logits_u; a.rows = rows; a.L = L; a.cfg = cfg; a.one_minus_cfg = one_minus_cfg;
-    a.temperature = temperature; a.mode = mode; a.seed = seed; a.seed_ptr = seed_ptr; a.offset = offset;
-    a.row_offset = row_offset; a.row_offset_ptr = row_offset_ptr;
-    a.init_noise = init_noise; a.t_next = t_next; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
-    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens;
-    TailFilter f;
-    f.top_k = top_k; f.top_p = top_p; f.typical_mass = typical_mass; f.min_tokens = min_tokens;
-    return launch_sample_tail_filter(a, f, (hipStream_t)stream);
-}
-
-extern "C" int paella_sample_tail(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg,
-                                  float temperature, int mode, const float* noise_q, uint64_t seed, uint64_t offset,
-                                  const int64_t* init_noise, const float* mask_u, float t_next, int64_t* tokens_out,
-                                  int64_t* sampled_out, void* stream) {
-    return paella_sample_tail_ex(logits_c, logits_u, rows, L, cfg, one_minus_cfg, temperature, mode, noise_q, seed, nullptr, offset, 0, nullptr,
-                                 init_noise, mask_u, t_next, tokens_out, sampled_out, stream);
-}
-
 extern "C" int paella_start_tokens(uint64_t seed, const uint64_t* seed_ptr, int64_t row_offset, const int64_t* row_offset_ptr, int num_labels,
                                    int64_t n, int64_t* tokens_out, void* stream) {
     return launch_start_tokens(seed, seed_ptr, row_offset, row_offset_ptr, num_labels, n, tokens_out, (hipStream_t)stream);

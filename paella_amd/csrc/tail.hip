@@ -11,7 +11,7 @@
 // lanes; max / argmax reductions are wave64 shuffles plus one LDS hop across the 4 waves.
 // Noise comes either from caller-provided tensors (parity mode: bit-identical draws to torch given the
 // same q / u) or from an in-kernel Philox4x32-10 stream keyed by (seed, offset).
-#include "common.h"
+#include "internal.h"
 #include "test_hooks.h"
 #include "philox.h"
 #include "../../include/paella_hip.h"
@@ -212,15 +212,15 @@ static int tail_req_prepare(TailArgs& a) {
 }
 #define RET_REQ(r) do { const int _rc = tail_req_prepare(r); if (_rc != PAELLA_OK) return _rc; } while (0)
 
-// the pin tables of either form: both row tables or neither, categorical mode and in-kernel noise only; pin_on belongs to the request form
-static int tail_pin_check(const TailArgs& a) {
+// the pin tables of either form, checked here only (launchers and argument-block runners): both row tables or neither, categorical mode and in-kernel noise; pin_on belongs to the request form
+int tail_pin_check(const char* who, const TailArgs& a) {
     if (!a.pin_keep && !a.pin_tokens && !a.pin_on) return PAELLA_OK;
-    if (!a.pin_keep != !a.pin_tokens) { paella_set_error("sampling tail: pin_keep and pin_tokens must be given together"); return PAELLA_ERR_ARG; }
-    if (a.pin_on && (!a.pin_keep || a.rq.rows_per_sample <= 0)) { paella_set_error("sampling tail: pin_on needs the pin_keep / pin_tokens row tables and the request form"); return PAELLA_ERR_ARG; }
-    if (a.mode != 0 || a.noise_q || a.mask_u) { paella_set_error("sampling tail: the pin needs categorical mode and in-kernel noise"); return PAELLA_ERR_ARG; }
+    if (!a.pin_keep != !a.pin_tokens) { paella_set_error("%s: pin_keep and pin_tokens must be given together (one pin table without the other)", who); return PAELLA_ERR_ARG; }
+    if (a.pin_on && (!a.pin_keep || a.rq.rows_per_sample <= 0)) { paella_set_error("%s: pin_on without the pin_keep / pin_tokens row tables, or outside the request form", who); return PAELLA_ERR_ARG; }
+    if (a.mode != 0 || a.noise_q || a.mask_u) { paella_set_error("%s: the pin needs categorical mode and in-kernel noise (it is not offered in argmax mode)", who); return PAELLA_ERR_ARG; }
     return PAELLA_OK;
 }
-#define RET_PIN(a) do { const int _rc = tail_pin_check(a); if (_rc != PAELLA_OK) return _rc; } while (0)
+#define RET_PIN(a) do { const int _rc = tail_pin_check("sampling tail", a); if (_rc != PAELLA_OK) return _rc; } while (0)
 
 int launch_tail_finalize(const TailArgs& a, const float* part_score, const int* part_idx, int tiles_n, hipStream_t st) {
     if (a.rows <= 0) return PAELLA_OK;
@@ -673,59 +673,59 @@ int launch_renoise_select(const TailArgs& a, const RenoiseArgs& r, hipStream_t s
     return PAELLA_OK;
 }
 
-// ---- C entry points of the statistics tail and the renoise stage (include/paella_hip.h: "Confidence-ordered renoise")
-// paella_sample_tail_filter plus the two statistics outputs; both NULL = paella_sample_tail_filter, the same launch
-extern "C" int paella_sample_tail_stats(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature, int mode,
-                                        uint64_t seed, const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr,
-                                        const int64_t* init_noise, float t_next, const int64_t* pin_keep, const int64_t* pin_tokens, int top_k, float top_p,
-                                        float typical_mass, int min_tokens, int64_t* tokens_out, int64_t* sampled_out, float* logprob_out, float* entropy_out,
-                                        void* stream) {
-    if (!logprob_out && !entropy_out)
-        return paella_sample_tail_filter(logits_c, logits_u, rows, L, cfg, one_minus_cfg, temperature, mode, seed, seed_ptr, offset, row_offset, row_offset_ptr, init_noise,
-                                         t_next, pin_keep, pin_tokens, top_k, top_p, typical_mass, min_tokens, tokens_out, sampled_out, stream);
-    if (!logits_c || !tokens_out) { paella_set_error("sample_tail_stats: null argument"); return PAELLA_ERR_ARG; }
-    if (mode != 0) { paella_set_error("sample_tail_stats: the statistics are not offered in argmax mode"); return PAELLA_ERR_ARG; }
-    if (!(temperature > 0.f)) { paella_set_error("temperature must be > 0 in categorical mode (use mode=1 for argmax)"); return PAELLA_ERR_ARG; }
-    if (row_offset < 0) { paella_set_error("row_offset must be >= 0"); return PAELLA_ERR_ARG; }
-    TailArgs a = {};
-    a.logits_c = logits_c; a.logits_u = logits_u; a.rows = rows; a.L = L; a.cfg = cfg; a.one_minus_cfg = one_minus_cfg;
-    a.temperature = temperature; a.mode = mode; a.seed = seed; a.seed_ptr = seed_ptr; a.offset = offset;
-    a.row_offset = row_offset; a.row_offset_ptr = row_offset_ptr;
-    a.init_noise = init_noise; a.t_next = t_next; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
-    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens;
-    TailFilter f;
-    f.top_k = top_k; f.top_p = top_p; f.typical_mass = typical_mass; f.min_tokens = min_tokens;
-    TailStats s;
-    s.logprob_out = logprob_out; s.entropy_out = entropy_out;
-    return launch_sample_tail_stats(a, f, s, (hipStream_t)stream);
-}
-// paella_sample_tail_stream_filter plus the two statistics outputs (the filter tables stay optional: none = every request off); both NULL = that entry point
-extern "C" int paella_sample_tail_stream_stats(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
-                                               const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active,
-                                               const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
-                                               const int* filter_k, const float* filter_mass, int64_t* tokens_out, int64_t* sampled_out, float* logprob_out,
-                                               float* entropy_out, void* stream) {
-    if (!logprob_out && !entropy_out)
-        return paella_sample_tail_stream_filter(logits_c, logits_u, rows, L, cfg_pairs, temperature, seeds, rows_per_sample, step, t_next, active, init_noise, pin_keep,
-                                                pin_tokens, pin_on, filter_k, filter_mass, tokens_out, sampled_out, stream);
-    if (!logits_c || !tokens_out || !seeds || !temperature) { paella_set_error("sample_tail_stream_stats: null argument"); return PAELLA_ERR_ARG; }
-    if (!filter_k != !filter_mass) { paella_set_error("sample_tail_stream_stats: filter_k and filter_mass must be given together (one filter table without the other)"); return PAELLA_ERR_ARG; }
-    if (!step || !t_next || !active || !init_noise) {
-        paella_set_error("sample_tail_stream_stats: null argument (the step, t_next and active tables and init_noise, the renoise source of every slot, are required)");
+// ---------------------------------------------------------------------------
+// The argument block of a sampling tail (include/paella_hip.h: paella_tail_args): tail_block_convert is the one place where a block's rules are checked and where it becomes
+// TailArgs / TailFilter / TailStats; every paella_sample_tail* entry point (end of this file) and every fused step of model.hip fills a block, names itself and goes through it.
+// need (internal.h: kNeed*): what a fixed-form entry point's NAME promises on top of what its block holds; a block alone takes its form from what is present.  fused: the tail
+// of a fused step (the head GEMM holds the logits and the guidance mix; the caller fills a.rows / a.L).  *kind: 0 launch_sample_tail, 1 ..._filter, 2 ..._stats
+// ---------------------------------------------------------------------------
+int tail_block_convert(const char* who, const paella_tail_args& t, int need, bool fused, TailArgs& a, TailFilter& f, TailStats& s, int* kind) {
+    const bool tables = t.seeds || t.temperature_tab || t.cfg_pairs || t.step || t.t_next_tab || t.active;
+    if (t.rows_per_sample < 0 || (t.rows_per_sample == 0 && (tables || (need & (kNeedRequest | kNeedStream))))) {
+        paella_set_error("%s: rows_per_sample must be > 0 (the request tables need the request form)", who);
         return PAELLA_ERR_ARG;
     }
-    if (rows_per_sample <= 0) { paella_set_error("sample_tail_stream_stats: rows_per_sample must be > 0"); return PAELLA_ERR_ARG; }
-    TailArgs a = {};
-    a.logits_c = logits_c; a.logits_u = cfg_pairs ? logits_u : nullptr; a.rows = rows; a.L = L; a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f;
-    a.init_noise = init_noise; a.t_next = -1.f; a.tokens_out = tokens_out; a.sampled_out = sampled_out;
-    a.rq.seeds = seeds; a.rq.temperature = temperature; a.rq.cfg_pairs = cfg_pairs; a.rq.rows_per_sample = rows_per_sample;
-    a.rq.step = step; a.rq.t_next = t_next; a.rq.active = active;
-    a.pin_keep = pin_keep; a.pin_tokens = pin_tokens; a.pin_on = pin_on;
-    TailFilter f;
-    f.filter_k = filter_k; f.filter_mass = filter_mass;
-    TailStats s;
-    s.logprob_out = logprob_out; s.entropy_out = entropy_out;
-    return launch_sample_tail_stats(a, f, s, (hipStream_t)stream);
+    const bool req = t.rows_per_sample > 0, strm = t.step || t.t_next_tab || t.active || (need & kNeedStream);
+    if ((!fused && !t.logits_c) || !t.tokens_out || (req && (!t.seeds || !t.temperature_tab))) {
+        paella_set_error("%s: null argument (%stokens_out%s)", who, fused ? "" : "logits_c / ", req ? " / seeds / temperature" : "");
+        return PAELLA_ERR_ARG;
+    }
+    if (strm && (!t.step || !t.t_next_tab || !t.active || !t.init_noise)) {
+        paella_set_error("%s: null argument (the step, t_next and active tables and init_noise, the renoise source of every slot, are required)", who);
+        return PAELLA_ERR_ARG;
+    }
+    if (!req && t.mode == 0 && !(t.temperature > 0.f)) { paella_set_error("%s: temperature must be > 0 in categorical mode (use mode=1 for argmax)", who); return PAELLA_ERR_ARG; }
+    if (!req && t.row_offset < 0) { paella_set_error("%s: row_offset must be >= 0", who); return PAELLA_ERR_ARG; }
+    a = TailArgs{};
+    a.logits_c = fused ? nullptr : t.logits_c; a.rows = t.rows; a.L = t.L;
+    a.noise_q = fused ? nullptr : t.noise_q; a.mask_u = fused ? nullptr : t.mask_u;
+    a.cfg = 1.f; a.one_minus_cfg = 0.f; a.temperature = 1.f;
+    a.offset = strm ? 0 : t.offset; a.t_next = strm ? -1.f : t.t_next;
+    a.init_noise = t.init_noise; a.tokens_out = t.tokens_out; a.sampled_out = fused ? nullptr : t.sampled_out;
+    a.pin_keep = t.pin_keep; a.pin_tokens = t.pin_tokens; a.pin_on = t.pin_on;
+    if (req) {
+        if (!fused) { a.logits_u = t.cfg_pairs ? t.logits_u : nullptr; a.rq.cfg_pairs = t.cfg_pairs; }  // (fused: the pairs ride through the head, none left for the tail)
+        a.rq.seeds = t.seeds; a.rq.temperature = t.temperature_tab; a.rq.rows_per_sample = t.rows_per_sample;
+        a.rq.step = t.step; a.rq.t_next = t.t_next_tab; a.rq.active = t.active;
+    } else {
+        if (!fused) { a.logits_u = t.logits_u; a.cfg = t.cfg; a.one_minus_cfg = t.one_minus_cfg; }
+        a.temperature = t.temperature; a.mode = t.mode; a.seed = t.seed; a.seed_ptr = t.seed_ptr; a.row_offset = t.row_offset; a.row_offset_ptr = t.row_offset_ptr;
+    }
+    RET_IF(tail_pin_check(who, a));
+    f = TailFilter{}; s = TailStats{};
+    const bool stats = t.logprob_out || t.entropy_out;
+    bool filter = t.filter_k || t.filter_mass;
+    if (!req && ((need & kNeedFilter) || t.top_k != 0 || t.top_p != 0.f || t.typical_mass != 0.f || t.min_tokens != 0)) {
+        filter = true;
+        f.top_k = t.top_k; f.top_p = t.top_p; f.typical_mass = t.typical_mass; f.min_tokens = t.min_tokens;
+    }
+    if ((filter || stats) && fused) { paella_set_error("%s: the filter and the statistics need materialised logits (a logits forward + paella_sample_tail_args)", who); return PAELLA_ERR_ARG; }
+    if ((filter || stats) && a.mode != 0) { paella_set_error("%s: the filter and the statistics are not offered in argmax mode", who); return PAELLA_ERR_ARG; }
+    if (!t.filter_k != !t.filter_mass) { paella_set_error("%s: filter_k and filter_mass must be given together (one filter table without the other)", who); return PAELLA_ERR_ARG; }
+    f.filter_k = t.filter_k; f.filter_mass = t.filter_mass;
+    s.logprob_out = t.logprob_out; s.entropy_out = t.entropy_out;
+    *kind = stats ? 2 : filter ? 1 : 0;
+    return PAELLA_OK;
 }
 
 static int renoise_select_scalar(const int64_t* drawn, const float* logprob, const int64_t* init_noise, int64_t rows, int rows_per_sample, uint64_t seed,
@@ -1015,4 +1015,109 @@ extern "C" int paella_test_launch_chain(float* buf, int n_elems, int blocks, int
     for (int i = 0; i < n_launches; ++i) hipLaunchKernelGGL(chain_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, buf, n_elems);
     LAUNCH_CHECK_RET();
     return PAELLA_OK;
+}
+
+// ---- C entry points of the sampling tails (include/paella_hip.h): the argument block, and the fixed forms over it
+static int run_tail_block(const char* who, const paella_tail_args& t, int need, void* stream) {
+    TailArgs a; TailFilter f; TailStats s;
+    int kind = 0;
+    RET_IF(tail_block_convert(who, t, need, false, a, f, s, &kind));
+    if (kind == 2) return launch_sample_tail_stats(a, f, s, (hipStream_t)stream);
+    if (kind == 1) return launch_sample_tail_filter(a, f, (hipStream_t)stream);
+    return launch_sample_tail(a, (hipStream_t)stream);
+}
+
+extern "C" int paella_sample_tail_args(const paella_tail_args* args, size_t args_bytes, void* stream) {
+    if (args_bytes != sizeof(paella_tail_args)) { paella_set_error("sample_tail_args: args_bytes %zu is not this library's sizeof(paella_tail_args) = %zu", args_bytes, sizeof(paella_tail_args)); return PAELLA_ERR_ARG; }
+    if (!args) { paella_set_error("sample_tail_args: null argument"); return PAELLA_ERR_ARG; }
+    return run_tail_block("sample_tail_args", *args, 0, stream);
+}
+
+// ---- the fixed-form entry points: each fills a block (internal.h: tail_block_scalar / tail_block_stream), names itself and runs it; one that extends another IS that
+// one when what it adds is absent, and then reports under the other's name
+extern "C" int paella_sample_tail_ex(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg,
+                                     float temperature, int mode, const float* noise_q, uint64_t seed, const uint64_t* seed_ptr,
+                                     uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr, const int64_t* init_noise, const float* mask_u,
+                                     float t_next, int64_t* tokens_out, int64_t* sampled_out, void* stream) {
+    paella_tail_args t = tail_block_scalar(logits_c, logits_u, rows, L, cfg, one_minus_cfg, temperature, mode, seed, seed_ptr, offset, row_offset, row_offset_ptr,
+                                           init_noise, t_next, nullptr, nullptr, tokens_out, sampled_out);
+    t.noise_q = noise_q; t.mask_u = mask_u;
+    return run_tail_block("sample_tail_ex", t, 0, stream);
+}
+extern "C" int paella_sample_tail(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg,
+                                  float temperature, int mode, const float* noise_q, uint64_t seed, uint64_t offset,
+                                  const int64_t* init_noise, const float* mask_u, float t_next, int64_t* tokens_out,
+                                  int64_t* sampled_out, void* stream) {
+    return paella_sample_tail_ex(logits_c, logits_u, rows, L, cfg, one_minus_cfg, temperature, mode, noise_q, seed, nullptr, offset, 0, nullptr,
+                                 init_noise, mask_u, t_next, tokens_out, sampled_out, stream);
+}
+// paella_sample_tail_ex in the counter-based noise mode with the optional pin: tokens_out[row] = pin_keep[row] == 0 ? pin_tokens[row] : the renoised draw
+extern "C" int paella_sample_tail_pin(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature, int mode,
+                                      uint64_t seed, const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr,
+                                      const int64_t* init_noise, float t_next, const int64_t* pin_keep, const int64_t* pin_tokens, int64_t* tokens_out,
+                                      int64_t* sampled_out, void* stream) {
+    return run_tail_block("sample_tail_pin", tail_block_scalar(logits_c, logits_u, rows, L, cfg, one_minus_cfg, temperature, mode, seed, seed_ptr, offset, row_offset,
+                                                               row_offset_ptr, init_noise, t_next, pin_keep, pin_tokens, tokens_out, sampled_out), 0, stream);
+}
+// paella_sample_tail_pin with a truncation filter (common.h: TailFilter; top_k <= 0 or >= L, top_p = 1, typical_mass = 1 are "off"): categorical mode only
+extern "C" int paella_sample_tail_filter(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature, int mode,
+                                         uint64_t seed, const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr,
+                                         const int64_t* init_noise, float t_next, const int64_t* pin_keep, const int64_t* pin_tokens, int top_k, float top_p,
+                                         float typical_mass, int min_tokens, int64_t* tokens_out, int64_t* sampled_out, void* stream) {
+    return paella_sample_tail_stats(logits_c, logits_u, rows, L, cfg, one_minus_cfg, temperature, mode, seed, seed_ptr, offset, row_offset, row_offset_ptr, init_noise,
+                                    t_next, pin_keep, pin_tokens, top_k, top_p, typical_mass, min_tokens, tokens_out, sampled_out, nullptr, nullptr, stream);
+}
+// paella_sample_tail_filter plus the two statistics outputs; both NULL = paella_sample_tail_filter, the same launch
+extern "C" int paella_sample_tail_stats(const float* logits_c, const float* logits_u, int64_t rows, int L, float cfg, float one_minus_cfg, float temperature, int mode,
+                                        uint64_t seed, const uint64_t* seed_ptr, uint64_t offset, int64_t row_offset, const int64_t* row_offset_ptr,
+                                        const int64_t* init_noise, float t_next, const int64_t* pin_keep, const int64_t* pin_tokens, int top_k, float top_p,
+                                        float typical_mass, int min_tokens, int64_t* tokens_out, int64_t* sampled_out, float* logprob_out, float* entropy_out,
+                                        void* stream) {
+    paella_tail_args t = tail_block_scalar(logits_c, logits_u, rows, L, cfg, one_minus_cfg, temperature, mode, seed, seed_ptr, offset, row_offset, row_offset_ptr,
+                                           init_noise, t_next, pin_keep, pin_tokens, tokens_out, sampled_out);
+    t.top_k = top_k; t.top_p = top_p; t.typical_mass = typical_mass; t.min_tokens = min_tokens; t.logprob_out = logprob_out; t.entropy_out = entropy_out;
+    return run_tail_block(logprob_out || entropy_out ? "sample_tail_stats" : "sample_tail_filter", t, kNeedFilter, stream);
+}
+
+// Request batch (ABI 6) and request stream (ABI 7): the per-sample device tables (common.h: ReqTables)
+extern "C" int paella_sample_tail_req(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
+                                      const uint64_t* seeds, int rows_per_sample, uint64_t offset, const int64_t* init_noise, float t_next,
+                                      int64_t* tokens_out, int64_t* sampled_out, void* stream) {
+    paella_tail_args t = tail_block_stream(logits_c, logits_u, rows, L, cfg_pairs, temperature, seeds, rows_per_sample, nullptr, nullptr, nullptr, init_noise, nullptr,
+                                           nullptr, nullptr, tokens_out, sampled_out);
+    t.offset = offset; t.t_next = t_next;
+    return run_tail_block("sample_tail_req", t, kNeedRequest, stream);
+}
+// paella_sample_tail_stream_filter (the per-request filter tables, common.h: TailFilter) plus the two statistics outputs, the most general member of the family.
+// Both outputs NULL = that entry point; both filter tables NULL as well = paella_sample_tail_stream(_pin), whose name then answers
+extern "C" int paella_sample_tail_stream_stats(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
+                                               const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active,
+                                               const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
+                                               const int* filter_k, const float* filter_mass, int64_t* tokens_out, int64_t* sampled_out, float* logprob_out,
+                                               float* entropy_out, void* stream) {
+    paella_tail_args t = tail_block_stream(logits_c, logits_u, rows, L, cfg_pairs, temperature, seeds, rows_per_sample, step, t_next, active, init_noise, pin_keep,
+                                           pin_tokens, pin_on, tokens_out, sampled_out);
+    t.filter_k = filter_k; t.filter_mass = filter_mass; t.logprob_out = logprob_out; t.entropy_out = entropy_out;
+    const char* who = logprob_out || entropy_out ? "sample_tail_stream_stats" : filter_k || filter_mass ? "sample_tail_stream_filter" : "sample_tail_stream";
+    return run_tail_block(who, t, kNeedStream, stream);
+}
+extern "C" int paella_sample_tail_stream_filter(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
+                                                const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active,
+                                                const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
+                                                const int* filter_k, const float* filter_mass, int64_t* tokens_out, int64_t* sampled_out, void* stream) {
+    return paella_sample_tail_stream_stats(logits_c, logits_u, rows, L, cfg_pairs, temperature, seeds, rows_per_sample, step, t_next, active, init_noise, pin_keep,
+                                           pin_tokens, pin_on, filter_k, filter_mass, tokens_out, sampled_out, nullptr, nullptr, stream);
+}
+extern "C" int paella_sample_tail_stream_pin(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
+                                             const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active,
+                                             const int64_t* init_noise, const int64_t* pin_keep, const int64_t* pin_tokens, const int* pin_on,
+                                             int64_t* tokens_out, int64_t* sampled_out, void* stream) {
+    return paella_sample_tail_stream_stats(logits_c, logits_u, rows, L, cfg_pairs, temperature, seeds, rows_per_sample, step, t_next, active, init_noise, pin_keep,
+                                           pin_tokens, pin_on, nullptr, nullptr, tokens_out, sampled_out, nullptr, nullptr, stream);
+}
+extern "C" int paella_sample_tail_stream(const float* logits_c, const float* logits_u, int64_t rows, int L, const float* cfg_pairs, const float* temperature,
+                                         const uint64_t* seeds, int rows_per_sample, const int* step, const float* t_next, const int* active,
+                                         const int64_t* init_noise, int64_t* tokens_out, int64_t* sampled_out, void* stream) {
+    return paella_sample_tail_stream_pin(logits_c, logits_u, rows, L, cfg_pairs, temperature, seeds, rows_per_sample, step, t_next, active, init_noise, nullptr, nullptr,
+                                         nullptr, tokens_out, sampled_out, stream);
 }

@@ -592,7 +592,7 @@ class Paella(nn.Module):
         attn_weights: a 1-D tensor (one vector for every sample) or a `KeyWeights` table with one row per conditioning slot (cond.B of them); with the table a
         cfg_mix is uploaded as a [Bx, 2] pair table (a host-to-device copy, refused with a ValueError during a graph capture: capture such a step with req_mix).
         regions: a `RegionTables` with one row per conditioning slot (regional prompts: per-query key groups); attn_weights is then None or a `KeyWeights` table,
-        and a cfg_mix is uploaded as a pair table as above.  None = exactly the entry points of the call without it."""
+        and a cfg_mix is uploaded as a pair table as above.  None = the same kernels with the same arguments as the call without it."""
         h = self._engine()
         lib = _lib.load()
         dev = self._device()
@@ -625,39 +625,29 @@ class Paella(nn.Module):
         lens = self._cond_lens(cond)
         with torch.cuda.device(dev):
             ws = self._workspace(lib.paella_unet_workspace_bytes(h, B, H, W, cond.S), ws)
-            if kw is not None or rg is not None:  # per-request prompt weights / regions: the logits entry points that take the tables (`lens` and the pair table nullable)
-                if cfg_mix is not None and torch.cuda.is_current_stream_capturing():
+            pairs = req_mix
+            if (kw is not None or rg is not None) and cfg_mix is not None:  # next to a per-slot table the guidance mix is a pair table as well
+                if torch.cuda.is_current_stream_capturing():
                     raise ValueError("forward_prepared with a KeyWeights table turns cfg_mix into a pair table by a host-to-device copy, which a graph capture "
                                      "cannot hold: pass req_mix (an fp32 device tensor [Bx, 2]) instead of cfg_mix inside a capture")
-                pairs = req_mix if cfg_mix is None else torch.tensor([mix] * nu, dtype=torch.float32).to(dev)
-                if rg is not None:
-                    _lib.check(lib.paella_unet_forward_shared_req_rg(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S, _lib.ptr(lens),
-                                                                     None if kw is None else _lib.ptr(kw.buf), None if kw is None else _lib.ptr(kw.lens),
-                                                                     0 if kw is None else kw.pitch, _lib.ptr(rg.q_groups), rg.q_groups.size(1), _lib.ptr(rg.k_groups),
-                                                                     rg.k_groups.size(1), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-                    return out
-                _lib.check(lib.paella_unet_forward_shared_req_kw(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S, _lib.ptr(lens),
-                                                                 _lib.ptr(kw.buf), _lib.ptr(kw.lens), kw.pitch, _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                                                 _lib.stream_ptr(dev)))
-                return out
-            if lens is not None:  # ragged conditioning: the twins with the per-sample row counts (cond.S is the slot pitch)
-                if req_mix is not None:
-                    _lib.check(lib.paella_unet_forward_shared_req_ragged(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(req_mix), H, W, cond.S,
-                                                                         _lib.ptr(lens), _lib.ptr(aw), 0 if aw is None else aw.numel(), _lib.ptr(out), _lib.ptr(ws),
-                                                                         ws.numel(), _lib.stream_ptr(dev)))
-                else:
-                    _lib.check(lib.paella_unet_forward_shared_ragged(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, mix[0], mix[1], H, W, cond.S, _lib.ptr(lens),
-                                                                     _lib.ptr(aw), 0 if aw is None else aw.numel(), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                                                     _lib.stream_ptr(dev)))
-                return out
-            if req_mix is not None:
-                _lib.check(lib.paella_unet_forward_shared_req(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(req_mix), H, W, cond.S, _lib.ptr(aw),
-                                                              0 if aw is None else aw.numel(), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-                return out
-            _lib.check(lib.paella_unet_forward_shared(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, mix[0], mix[1], H, W, cond.S, _lib.ptr(aw),
-                                                      0 if aw is None else aw.numel(), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                                      _lib.stream_ptr(dev)))
+                pairs, mix = torch.tensor([mix] * nu, dtype=torch.float32).to(dev), (0.0, 0.0)
+            s = self._step_block(x, r, cond, mix, pairs, lens, aw, kw, rg)
+            s.logits_out = out.data_ptr()
+            _lib.check(lib.paella_unet_step(h, ctypes.byref(s), ctypes.sizeof(s), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
         return out
+
+    @staticmethod
+    def _step_block(x, r, cond, mix, pairs, lens, aw, kw, rg):
+        """the argument block of one forward (include/paella_hip.h: paella_step_args) without its output: the caller sets logits_out or tail.  It holds raw
+        pointers: the tensors passed here stay alive in the caller until the call returns"""
+        s = _lib.StepArgs(B=cond.B, n_unique=x.size(0), mix_c=mix[0], mix_u=mix[1], H=x.size(1), W=x.size(2), S=cond.S, n_attn_weights=0 if aw is None else aw.numel())
+        _lib.tensor_fields(s, tokens=x, r=r, cond=cond.buf, mix_pairs=pairs, cond_len=lens, attn_weights=aw)
+        if kw is not None:
+            _lib.tensor_fields(s, kw_table=kw.buf, kw_len=kw.lens).kw_pitch = kw.pitch
+        if rg is not None:
+            _lib.tensor_fields(s, q_groups=rg.q_groups, k_groups=rg.k_groups)
+            s.qg_pitch, s.kg_pitch = rg.q_groups.size(1), rg.k_groups.size(1)
+        return s
 
     def forward_sample(self, x, r, cond, out, *, temperature, argmax=False, seed=0, seed_dev=None, offset=0, row_offset=0,
                        row_offset_dev=None, init_noise=None, t_next=0.0, cfg_mix=None, attn_weights=None, ws=None, req=None, stream=None, pin=None, regions=None):
@@ -674,7 +664,7 @@ class Paella(nn.Module):
         stored for the sample, `out` keeps its rows) -- every request of the batch is at its own step; `out` may be `x` (the stream runs in place).
         pin=(keep, known) (scalar form) or pin=(keep, known, pin_on) (with `stream`): editing requests -- int64 [Bx,H,W] DEVICE grids, keep 1 = regenerate / 0 = known;
         after the draw and the renoise the tail stores known wherever keep == 0, with `stream` only for the samples whose int32 [Bx] flag pin_on is set.  Categorical
-        mode only; not offered with `req` alone.  Without `pin` the call reaches exactly the entry points it reaches without this argument.
+        mode only; not offered with `req` alone.  Without `pin` the call launches the same kernels with the same arguments as without this argument.
         attn_weights: a 1-D tensor, or (with `req`) a `KeyWeights` table with one row per conditioning slot (cond.B of them).
         regions (with `stream` only): a `RegionTables` with one row per conditioning slot -- regional prompts; attn_weights is then None or a `KeyWeights` table."""
         h = self._engine()
@@ -724,76 +714,20 @@ class Paella(nn.Module):
         lens = self._cond_lens(cond)
         with torch.cuda.device(dev):
             ws = self._workspace(lib.paella_unet_workspace_bytes(h, B, H, W, cond.S), ws)
-            if rg is not None:  # regional prompts: the most general stream tick (`lens`, the key-weight table and the pin tables nullable)
-                pk, pt, po = (None, None, None) if pin is None else pin
-                _lib.check(lib.paella_unet_forward_sample_stream_rg(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S,
-                                                                    _lib.ptr(lens), None if kw is None else _lib.ptr(kw.buf), None if kw is None else _lib.ptr(kw.lens),
-                                                                    0 if kw is None else kw.pitch, _lib.ptr(rg.q_groups), rg.q_groups.size(1), _lib.ptr(rg.k_groups),
-                                                                    rg.k_groups.size(1), _lib.ptr(seeds), _lib.ptr(temps), H * W, _lib.ptr(stream[0]), _lib.ptr(stream[1]),
-                                                                    _lib.ptr(stream[2]), _lib.ptr(init_noise), _lib.ptr(pk), _lib.ptr(pt), _lib.ptr(po), _lib.ptr(out),
-                                                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-                return out
-            if kw is not None:  # per-request prompt weights: one entry point per form, `lens` (ragged conditioning) and the pin tables nullable
-                pk, pt, po = (None, None, None) if pin is None else pin
-                if stream is not None:
-                    _lib.check(lib.paella_unet_forward_sample_stream_kw(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S,
-                                                                        _lib.ptr(lens), _lib.ptr(kw.buf), _lib.ptr(kw.lens), kw.pitch, _lib.ptr(seeds), _lib.ptr(temps),
-                                                                        H * W, _lib.ptr(stream[0]), _lib.ptr(stream[1]), _lib.ptr(stream[2]), _lib.ptr(init_noise),
-                                                                        _lib.ptr(pk), _lib.ptr(pt), _lib.ptr(po), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                                                        _lib.stream_ptr(dev)))
-                else:
-                    _lib.check(lib.paella_unet_forward_sample_req_kw(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S,
-                                                                     _lib.ptr(lens), _lib.ptr(kw.buf), _lib.ptr(kw.lens), kw.pitch, _lib.ptr(seeds), _lib.ptr(temps),
-                                                                     H * W, int(offset), _lib.ptr(init_noise), float(t_next), None, None, None, _lib.ptr(out),
-                                                                     _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-                return out
-            if pin is not None:  # editing requests: one entry point per form, `lens` (ragged conditioning) nullable
-                naw = 0 if aw is None else aw.numel()
-                if stream is not None:
-                    _lib.check(lib.paella_unet_forward_sample_stream_pin(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S,
-                                                                         _lib.ptr(lens), _lib.ptr(aw), naw, _lib.ptr(seeds), _lib.ptr(temps), H * W,
-                                                                         _lib.ptr(stream[0]), _lib.ptr(stream[1]), _lib.ptr(stream[2]), _lib.ptr(init_noise),
-                                                                         _lib.ptr(pin[0]), _lib.ptr(pin[1]), _lib.ptr(pin[2]), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                                                         _lib.stream_ptr(dev)))
-                else:
-                    _lib.check(lib.paella_unet_forward_sample_pin(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, mix[0], mix[1], H, W, cond.S, _lib.ptr(lens),
-                                                                  _lib.ptr(aw), naw, float(temperature), 0, int(seed), _lib.ptr(seed_dev), int(offset), int(row_offset),
-                                                                  _lib.ptr(row_offset_dev), _lib.ptr(init_noise), float(t_next), _lib.ptr(pin[0]), _lib.ptr(pin[1]),
-                                                                  _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-                return out
-            if lens is not None:  # ragged conditioning: the twins with the per-sample row counts (cond.S is the slot pitch)
-                naw = 0 if aw is None else aw.numel()
-                if stream is not None:
-                    _lib.check(lib.paella_unet_forward_sample_stream_ragged(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S,
-                                                                            _lib.ptr(lens), _lib.ptr(aw), naw, _lib.ptr(seeds), _lib.ptr(temps), H * W,
-                                                                            _lib.ptr(stream[0]), _lib.ptr(stream[1]), _lib.ptr(stream[2]), _lib.ptr(init_noise),
-                                                                            _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-                elif req is not None:
-                    _lib.check(lib.paella_unet_forward_sample_req_ragged(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S,
-                                                                         _lib.ptr(lens), _lib.ptr(aw), naw, _lib.ptr(seeds), _lib.ptr(temps), H * W, int(offset),
-                                                                         _lib.ptr(init_noise), float(t_next), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                                                         _lib.stream_ptr(dev)))
-                else:
-                    _lib.check(lib.paella_unet_forward_sample_ragged(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, mix[0], mix[1], H, W, cond.S, _lib.ptr(lens),
-                                                                     _lib.ptr(aw), naw, float(temperature), 1 if argmax else 0, int(seed), _lib.ptr(seed_dev),
-                                                                     int(offset), int(row_offset), _lib.ptr(row_offset_dev), _lib.ptr(init_noise), float(t_next),
-                                                                     _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-                return out
+            t = _lib.TailArgs(offset=int(offset), t_next=float(t_next))  # (the stream form reads neither: its step and t_next tables carry them)
+            _lib.tensor_fields(t, init_noise=init_noise, tokens_out=out)
+            if req is None:
+                t.temperature, t.mode, t.seed, t.row_offset = float(temperature), 1 if argmax else 0, int(seed), int(row_offset)
+                _lib.tensor_fields(t, seed_ptr=seed_dev, row_offset_ptr=row_offset_dev)
+            else:
+                _lib.tensor_fields(t, seeds=seeds, temperature_tab=temps).rows_per_sample = H * W
             if stream is not None:
-                _lib.check(lib.paella_unet_forward_sample_stream(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S, _lib.ptr(aw),
-                                                                 0 if aw is None else aw.numel(), _lib.ptr(seeds), _lib.ptr(temps), H * W, _lib.ptr(stream[0]),
-                                                                 _lib.ptr(stream[1]), _lib.ptr(stream[2]), _lib.ptr(init_noise), _lib.ptr(out), _lib.ptr(ws), ws.numel(),
-                                                                 _lib.stream_ptr(dev)))
-                return out
-            if req is not None:
-                _lib.check(lib.paella_unet_forward_sample_req(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, _lib.ptr(pairs), H, W, cond.S, _lib.ptr(aw),
-                                                              0 if aw is None else aw.numel(), _lib.ptr(seeds), _lib.ptr(temps), H * W, int(offset), _lib.ptr(init_noise),
-                                                              float(t_next), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-                return out
-            _lib.check(lib.paella_unet_forward_sample(h, _lib.ptr(x), _lib.ptr(r), _lib.ptr(cond.buf), B, nu, mix[0], mix[1], H, W, cond.S,
-                                                      _lib.ptr(aw), 0 if aw is None else aw.numel(), float(temperature), 1 if argmax else 0,
-                                                      int(seed), _lib.ptr(seed_dev), int(offset), int(row_offset), _lib.ptr(row_offset_dev), _lib.ptr(init_noise),
-                                                      float(t_next), _lib.ptr(out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+                _lib.tensor_fields(t, step=stream[0], t_next_tab=stream[1], active=stream[2])
+            if pin is not None:
+                _lib.tensor_fields(t, pin_keep=pin[0], pin_tokens=pin[1], pin_on=None if stream is None else pin[2])
+            s = self._step_block(x, r, cond, mix, None if req is None else pairs, lens, aw, kw, rg)
+            s.tail = ctypes.pointer(t)
+            _lib.check(lib.paella_unet_step(h, ctypes.byref(s), ctypes.sizeof(s), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
         return out
 
     def forward(self, x, r, byt5, clip=None, clip_image=None, x_cat=None, **kwargs):

@@ -17,6 +17,8 @@ the tail kernel (Philox4x32-10 keyed by `seed`), which removes the [B*H*W, num_l
 
 Extension (not reference behaviour): a step temperature of 0 selects argmax of the mixed logits.
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -111,41 +113,47 @@ def _cat_inputs(a, b):
     return out
 
 
+def _run_tail(lc, lu, rows, L, out, *, scalar=None, req=None, stream=None, offset=0, init_noise=None, t_next=0.0, pin=None, filt=None, stats=None):
+    """ONE sampling tail on materialised logits through its argument block (include/paella_hip.h: paella_tail_args); None = not given, and which tail runs follows
+    from what is given.  scalar=(cfg, omc, temperature, mode, seed, seed_dev, row_offset, row_offset_dev, noise_q, mask_u) or req=(pairs, temps, seeds,
+    rows_per_sample) DEVICE tables, with stream=(step, t_next, active) tables in place of `offset` / `t_next`; pin=(keep, known[, pin_on]);
+    filt=(top_k, top_p, typical_mass, min_tokens) of `check_filter` next to `scalar`, the (filter_k, filter_mass) tables next to `req`; stats=(logprob, entropy)"""
+    t = _lib.TailArgs(rows=rows, L=L, offset=offset, t_next=t_next)
+    _lib.tensor_fields(t, logits_c=lc, logits_u=lu, init_noise=init_noise, tokens_out=out)
+    if req is None:
+        t.cfg, t.one_minus_cfg, t.temperature, t.mode, t.seed, seed_dev, t.row_offset, row_offset_dev, noise_q, mask_u = scalar
+        _lib.tensor_fields(t, seed_ptr=seed_dev, row_offset_ptr=row_offset_dev, noise_q=noise_q, mask_u=mask_u)
+        if filt is not None:
+            t.top_k, t.top_p, t.typical_mass, t.min_tokens = filt
+    else:
+        _lib.tensor_fields(t, cfg_pairs=None if lu is None else req[0], temperature_tab=req[1], seeds=req[2]).rows_per_sample = req[3]
+        if filt is not None:
+            _lib.tensor_fields(t, filter_k=filt[0], filter_mass=filt[1])
+    if stream is not None:
+        _lib.tensor_fields(t, step=stream[0], t_next_tab=stream[1], active=stream[2])
+    if pin is not None:
+        _lib.tensor_fields(t, pin_keep=pin[0], pin_tokens=pin[1], pin_on=pin[2] if len(pin) > 2 else None)
+    if stats is not None:
+        _lib.tensor_fields(t, logprob_out=stats[0], entropy_out=stats[1])
+    with torch.cuda.device(lc.device):
+        _lib.check(_lib.load().paella_sample_tail_args(ctypes.byref(t), ctypes.sizeof(t), _lib.stream_ptr(lc.device)))
+
+
 def _tail(logits_c, logits_u, rows, L, cfg, omc, temperature, mode, noise_q, seed, offset, init_noise, mask_u, t_next, out,
           seed_dev=None, row_offset=0, row_offset_dev=None, pin=None, filt=None):
-    lib = _lib.load()
-    dev = logits_c.device
-    with torch.cuda.device(dev):
-        if filt is not None:  # truncated sampling: (top_k, top_p, typical_mass, min_tokens) of `check_filter`, the pin tables nullable
-            pk, pt = (None, None) if pin is None else pin
-            _lib.check(lib.paella_sample_tail_filter(_lib.ptr(logits_c), _lib.ptr(logits_u), rows, L, cfg, omc, temperature, mode, seed, _lib.ptr(seed_dev), offset,
-                                                     row_offset, _lib.ptr(row_offset_dev), _lib.ptr(init_noise), t_next, _lib.ptr(pk), _lib.ptr(pt), filt[0], filt[1],
-                                                     filt[2], filt[3], _lib.ptr(out), None, _lib.stream_ptr(dev)))
-            return
-        if pin is not None:  # (keep, known): the tail writes known[row] wherever keep[row] == 0, after the draw and the renoise
-            _lib.check(lib.paella_sample_tail_pin(_lib.ptr(logits_c), _lib.ptr(logits_u), rows, L, cfg, omc, temperature, mode, seed, _lib.ptr(seed_dev), offset,
-                                                  row_offset, _lib.ptr(row_offset_dev), _lib.ptr(init_noise), t_next, _lib.ptr(pin[0]), _lib.ptr(pin[1]), _lib.ptr(out),
-                                                  None, _lib.stream_ptr(dev)))
-            return
-        _lib.check(lib.paella_sample_tail_ex(_lib.ptr(logits_c), _lib.ptr(logits_u), rows, L, cfg, omc, temperature, mode,
-                                             _lib.ptr(noise_q), seed, _lib.ptr(seed_dev), offset, row_offset, _lib.ptr(row_offset_dev),
-                                             _lib.ptr(init_noise), _lib.ptr(mask_u), t_next, _lib.ptr(out), None, _lib.stream_ptr(dev)))
+    """the scalar form; pin=(keep, known): the tail writes known[row] wherever keep[row] == 0, after the draw and the renoise; filt: truncated sampling"""
+    _run_tail(logits_c, logits_u, rows, L, out, scalar=(cfg, omc, temperature, mode, seed, seed_dev, row_offset, row_offset_dev, noise_q, mask_u), offset=offset,
+              init_noise=init_noise, t_next=t_next, pin=pin, filt=filt)
 
 
 def _tail_req(lc, lu, rows, L, rows_per_sample, req, step, init_noise, t_next, out, filt=None):
     """the request form of `_tail`: seed, guidance pair and temperature per sample from the device tables of `req` (RequestTables); filt (FilterTables): the
     filtered stream tail, fed with that step's constant step / renoise-threshold tables (the words the scalar arguments carry otherwise)"""
-    dev = lc.device
-    with torch.cuda.device(dev):
-        if filt is not None:
-            _lib.check(_lib.load().paella_sample_tail_stream_filter(_lib.ptr(lc), _lib.ptr(lu), rows, L, _lib.ptr(None if lu is None else req.pairs[step]),
-                                                                    _lib.ptr(req.temps[step]), _lib.ptr(req.seeds), rows_per_sample, _lib.ptr(filt.step[step]),
-                                                                    _lib.ptr(filt.t_next[step]), _lib.ptr(filt.active), _lib.ptr(init_noise), None, None,
-                                                                    None, _lib.ptr(filt.k), _lib.ptr(filt.mass), _lib.ptr(out), None, _lib.stream_ptr(dev)))
-            return
-        _lib.check(_lib.load().paella_sample_tail_req(_lib.ptr(lc), _lib.ptr(lu), rows, L, _lib.ptr(None if lu is None else req.pairs[step]), _lib.ptr(req.temps[step]),
-                                                      _lib.ptr(req.seeds), rows_per_sample, step, _lib.ptr(init_noise), t_next, _lib.ptr(out), None,
-                                                      _lib.stream_ptr(dev)))
+    tabs = (None if lu is None else req.pairs[step], req.temps[step], req.seeds, rows_per_sample)
+    if filt is not None:
+        _run_tail(lc, lu, rows, L, out, req=tabs, stream=(filt.step[step], filt.t_next[step], filt.active), init_noise=init_noise, filt=(filt.k, filt.mass))
+    else:
+        _run_tail(lc, lu, rows, L, out, req=tabs, offset=step, init_noise=init_noise, t_next=t_next)
 
 
 def fresh_seed():
@@ -391,17 +399,6 @@ class ConfidenceTables:
     def __init__(self, host, device):
         self.policy, self.noise = host[0].to(device), host[1].to(device)
         self.never = torch.full((host[0].numel(),), -1.0, dtype=torch.float32, device=device)
-
-
-def _stats_tail(lc, lu, rows, L, cfg, omc, temperature, seed, offset, out, logprob, entropy, seed_dev=None, row_offset=0, row_offset_dev=None, pin=None, filt=None):
-    """the statistics form of the filtered tail, scalar form, without renoise: the draw of `_tail(filt=...)` plus log p(token) and the row entropy"""
-    f = FILTER_OFF if filt is None else filt
-    pk, pt = (None, None) if pin is None else pin
-    dev = lc.device
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().paella_sample_tail_stats(_lib.ptr(lc), _lib.ptr(lu), rows, L, cfg, omc, temperature, 0, seed, _lib.ptr(seed_dev), offset, row_offset,
-                                                        _lib.ptr(row_offset_dev), None, 0.0, _lib.ptr(pk), _lib.ptr(pt), f[0], f[1], f[2], f[3], _lib.ptr(out), None,
-                                                        _lib.ptr(logprob), _lib.ptr(entropy), _lib.stream_ptr(dev)))
 
 
 def _renoise_stage(drawn, logprob, init_noise, rows, rows_per_sample, seed, offset, t_next, policy, g, out, seed_dev=None, row_offset=0, row_offset_dev=None, pin=None):
@@ -669,11 +666,9 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
                 mask_u = torch.rand(B, H, W, dtype=torch.float32, device=device)  # == torch.rand_like(x.float())
             if conf is not None and req is not None:
                 # the statistics tail in the stream form, never renoising (threshold table -1), then the renoise stage with the step's real thresholds
+                _run_tail(lc, lu, rows, L, out, req=(None if lu is None else req.pairs[i], req.temps[i], req.seeds, H * W), stream=(filt.step[i], conf.never, filt.active),
+                          init_noise=init_noise, filt=(filt.k, filt.mass), stats=(logprob, entropy))
                 with torch.cuda.device(device):
-                    _lib.check(_lib.load().paella_sample_tail_stream_stats(_lib.ptr(lc), _lib.ptr(lu), rows, L, _lib.ptr(None if lu is None else req.pairs[i]),
-                                                                           _lib.ptr(req.temps[i]), _lib.ptr(req.seeds), H * W, _lib.ptr(filt.step[i]), _lib.ptr(conf.never),
-                                                                           _lib.ptr(filt.active), _lib.ptr(init_noise), None, None, None, _lib.ptr(filt.k), _lib.ptr(filt.mass),
-                                                                           _lib.ptr(out), None, _lib.ptr(logprob), _lib.ptr(entropy), _lib.stream_ptr(device)))
                     if renoise:
                         _lib.check(_lib.load().paella_renoise_select_stream(_lib.ptr(out), _lib.ptr(logprob), _lib.ptr(init_noise), rows, H * W, _lib.ptr(req.seeds),
                                                                             _lib.ptr(filt.step[i]), _lib.ptr(filt.t_next[i]), _lib.ptr(filt.active), _lib.ptr(conf.policy),
@@ -683,8 +678,8 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
             if conf is not None:
                 # a renoising step: the raw draw and its statistics, then the renoise stage (which also applies the pin); the last steps: the pin rides in the tail
                 cfg, omc = cfgs[i] if use_cfg else (1.0, 0.0)
-                _stats_tail(lc, lu, rows, L, cfg, omc, temp, seed, i, out, logprob, entropy, seed_dev=seed_dev, row_offset=row_offset, row_offset_dev=row_offset_dev,
-                            pin=None if renoise else pin, filt=filt)
+                _run_tail(lc, lu, rows, L, out, scalar=(cfg, omc, temp, 0, seed, seed_dev, row_offset, row_offset_dev, None, None), offset=i, pin=None if renoise else pin,
+                          filt=FILTER_OFF if filt is None else filt, stats=(logprob, entropy))
                 if renoise:
                     _renoise_stage(out, logprob, init_noise, rows, H * W, seed, i, t_list[i + 1], conf[0], conf[1], out, seed_dev=seed_dev, row_offset=row_offset,
                                    row_offset_dev=row_offset_dev, pin=pin)
@@ -1347,12 +1342,9 @@ class RequestStream:
                                         **({} if self.pairs is None else {"req_mix": self.pairs}), **({} if self.regions is None else {"regions": self.regions}))
             pk, pt, po = (self.keep, self.known, self.pin_on) if self.editing else (None, None, None)
             rows, hw = B * self.shape[1] * self.shape[2], self.shape[1] * self.shape[2]
+            _run_tail(self.logits, None, rows, self.model.num_labels, self.tokens, req=(None, self.temps, self.seeds, hw), stream=(self.step, self._never, self.active_dev),
+                      init_noise=self.random_x, filt=(self.filter_k, self.filter_mass), stats=(self.logprob, self.entropy))
             with torch.cuda.device(self.device):
-                _lib.check(_lib.load().paella_sample_tail_stream_stats(_lib.ptr(self.logits), None, rows, self.model.num_labels, None, _lib.ptr(self.temps),
-                                                                       _lib.ptr(self.seeds), hw, _lib.ptr(self.step), _lib.ptr(self._never), _lib.ptr(self.active_dev),
-                                                                       _lib.ptr(self.random_x), None, None, None, _lib.ptr(self.filter_k), _lib.ptr(self.filter_mass),
-                                                                       _lib.ptr(self.tokens), None, _lib.ptr(self.logprob), _lib.ptr(self.entropy),
-                                                                       _lib.stream_ptr(self.device)))
                 _lib.check(_lib.load().paella_renoise_select_stream(_lib.ptr(self.tokens), _lib.ptr(self.logprob), _lib.ptr(self.random_x), rows, hw, _lib.ptr(self.seeds),
                                                                     _lib.ptr(self.step), _lib.ptr(self.t_next), _lib.ptr(self.active_dev), _lib.ptr(self.policy),
                                                                     _lib.ptr(self.confidence_noise), _lib.ptr(pk), _lib.ptr(pt), _lib.ptr(po), _lib.ptr(self.tokens),
@@ -1361,13 +1353,9 @@ class RequestStream:
         if self.filtering:  # the logits forward (the guidance mix folded through the head: ONE [rows, L] tensor) + the filtered stream tail, in place as below
             self.model.forward_prepared(self.tokens, self.r, self.cache, attn_weights=self.attn_weights, out=self.logits, ws=self.ws,
                                         **({} if self.pairs is None else {"req_mix": self.pairs}), **({} if self.regions is None else {"regions": self.regions}))
-            pk, pt, po = (self.keep, self.known, self.pin_on) if self.editing else (None, None, None)
-            with torch.cuda.device(self.device):
-                _lib.check(_lib.load().paella_sample_tail_stream_filter(_lib.ptr(self.logits), None, B * self.shape[1] * self.shape[2], self.model.num_labels, None,
-                                                                        _lib.ptr(self.temps), _lib.ptr(self.seeds), self.shape[1] * self.shape[2], _lib.ptr(self.step),
-                                                                        _lib.ptr(self.t_next), _lib.ptr(self.active_dev), _lib.ptr(self.random_x), _lib.ptr(pk), _lib.ptr(pt),
-                                                                        _lib.ptr(po), _lib.ptr(self.filter_k), _lib.ptr(self.filter_mass), _lib.ptr(self.tokens), None,
-                                                                        _lib.stream_ptr(self.device)))
+            _run_tail(self.logits, None, B * self.shape[1] * self.shape[2], self.model.num_labels, self.tokens, req=(None, self.temps, self.seeds, self.shape[1] * self.shape[2]),
+                      stream=(self.step, self.t_next, self.active_dev), init_noise=self.random_x, pin=(self.keep, self.known, self.pin_on) if self.editing else None,
+                      filt=(self.filter_k, self.filter_mass))
             return
         # in place: the token gather at the head of the forward and the token store at its tail are different kernels of one stream (as in _sample_core)
         self.model.forward_sample(self.tokens, self.r, self.cache, self.tokens, temperature=1.0, init_noise=self.random_x, attn_weights=self.attn_weights, ws=self.ws,
