@@ -360,6 +360,30 @@ __global__ __launch_bounds__(64 * WM * WN, tile_wg_per_cu(WM, WN, TM, TN, PD, AP
     bool ln_any = false;
     int ln_row0 = 0;  // first row of the (only) tile row this launch's LayerNorm statistics belong to
     const int ln_tile0 = ltile;
+    // fp32 ring tiles (2 x 2 waves): the partials are fetched AHEAD of the ring's prefetch DMAs (ln_issue), all of a lane's chunks in one batch.  gfx950 returns
+    // loads in order under one counter, so partial loads issued BEHIND the DMAs wait for every prefetched stage, and the former "4 loads in flight" loops were four
+    // dependent L2 round trips at K = 1280 on top of that.  The 8 lanes that hold a fragment row in the tile's two wave columns split its chunks (lane (wn, kq):
+    // chunks kq + 4 wn + 8 c, merged in increasing c), xor-reduce inside the wave and add the other column's fp64 triple from LDS (the ring's last stage is still
+    // free here): a + b == b + a bit for bit, so both waves -- and every workgroup of the launch -- hold the same statistics and take the same guard decision.
+    constexpr bool LN_AHEAD = APRO == 2 && RING > 0 && NW == 4 && WN == 2 && !BF;
+    constexpr int LN_NP = TM == 1 ? 5 : 2;  // chunks per lane fetched ahead (5 x 8 lanes x 32 columns = K 1280 whole); a longer row's rest is fetched behind the DMAs
+    f32x4 ln_pre[LN_AHEAD ? TM : 1][LN_AHEAD ? LN_NP : 1];
+    auto ln_issue = [&]() __attribute__((always_inline)) {
+        if constexpr (LN_AHEAD) {
+            if (!g.ln_row) {
+                int ln_tm, ln_tn;
+                sk_tile_coords<(BM >= 64)>(p, ln_tile0, ln_tm, ln_tn);
+                const int nch = g.ln_nblk >> 1;  // (a ring tile's K is a multiple of 32: ln_nblk is even and every row of pairs is 16-byte aligned)
+#pragma unroll
+                for (int i = 0; i < TM; ++i) {
+                    const int gmc = min(ln_tm * BM + (wm * TM + i) * 16 + r16, g.M - 1);
+                    const f32x4* stp = reinterpret_cast<const f32x4*>(g.ln_stats + (size_t)gmc * g.ln_nblk * 2);
+#pragma unroll
+                    for (int c = 0; c < LN_NP; ++c) ln_pre[i][c] = stp[min(kq + 4 * wn + 8 * c, nch - 1)];  // unconditional from a clamped address; masked at the merge
+                }
+            }
+        }
+    };
     auto ln_row_stats = [&]() __attribute__((always_inline)) {
         if constexpr (APRO == 2) {
             // the 4 lanes that hold one fragment row (kq = 0..3) split the producer's per-16-column (sum, M2) pairs as 16-byte chunks (two blocks each; a last odd
@@ -392,6 +416,51 @@ __global__ __launch_bounds__(64 * WM * WN, tile_wg_per_cu(WM, WN, TM, TN, PD, AP
                 return;
             }
             const int nch = g.ln_nblk >> 1;
+            if constexpr (LN_AHEAD) {
+                RowStatAcc part[TM];
+                double* const xch = reinterpret_cast<double*>(smem + (RING - 1) * STAGE_FLOATS);  // [wave column][tile row][S, Q, M]
+#pragma unroll
+                for (int i = 0; i < TM; ++i) {
+                    RowStatAcc acc;
+#pragma unroll
+                    for (int c = 0; c < LN_NP; ++c) {
+                        const bool in = kq + 4 * wn + 8 * c < nch;  // (a chunk past the row: + 0.0 leaves the three sums as they are)
+                        const f32x4 v = ln_pre[i][c];
+                        acc.add(in ? v[0] : 0.f, in ? v[1] : 0.f); acc.add(in ? v[2] : 0.f, in ? v[3] : 0.f);
+                    }
+                    if (kq + 4 * wn + 8 * LN_NP < nch) {  // rows longer than the batch fetched ahead
+                        const int gmc = min(ln_tm * BM + (wm * TM + i) * 16 + r16, g.M - 1);
+                        const f32x4* stp = reinterpret_cast<const f32x4*>(g.ln_stats + (size_t)gmc * g.ln_nblk * 2);
+                        for (int j = kq + 4 * wn + 8 * LN_NP; j < nch; j += 8) {
+                            const f32x4 v = stp[j];
+                            acc.add(v[0], v[1]); acc.add(v[2], v[3]);
+                        }
+                    }
+                    acc.S += __shfl_xor(acc.S, 16, 64); acc.Q += __shfl_xor(acc.Q, 16, 64); acc.M += __shfl_xor(acc.M, 16, 64);
+                    acc.S += __shfl_xor(acc.S, 32, 64); acc.Q += __shfl_xor(acc.Q, 32, 64); acc.M += __shfl_xor(acc.M, 32, 64);
+                    if (kq == 0) {
+                        double* dst = xch + (wn * BM + (wm * TM + i) * 16 + r16) * 3;
+                        dst[0] = acc.S; dst[1] = acc.Q; dst[2] = acc.M;
+                    }
+                    part[i] = acc;
+                }
+                // a bare barrier (see the unit loop): the prefetch DMAs stay in flight across it
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+                __builtin_amdgcn_s_barrier();
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int i = 0; i < TM; ++i) {
+                    const double* src = xch + ((wn ^ 1) * BM + (wm * TM + i) * 16 + r16) * 3;
+                    RowStatAcc acc = part[i];
+                    acc.S += src[0]; acc.Q += src[1]; acc.M += src[2];
+                    acc.finish(g.K, g.ln_eps, fr_mu[i], fr_rs[i]);
+                    fr_mu_lo[i] = (float)(acc.S / (double)g.K - (double)fr_mu[i]);
+                    ln_dir[i] = __builtin_amdgcn_ballot_w64(fabsf(fr_mu[i]) * fr_rs[i] > g.ln_fold_ratio) != 0;  // wave-uniform, a function of the block's 16 rows only
+                    ln_any = ln_any || ln_dir[i];
+                }
+                if (g.ln_guard_count && ln_any && lane_k == 0) atomicAdd(g.ln_guard_count, 1u);  // test hook only (null in the product)
+                return;
+            }
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 const int gmc = min(ln_tm * BM + (wm * TM + i) * 16 + r16, g.M - 1);
@@ -1256,6 +1325,7 @@ __global__ __launch_bounds__(64 * WM * WN, tile_wg_per_cu(WM, WN, TM, TN, PD, AP
             }
             return;
         }
+        ln_issue();  // fp32 4-wave tiles: the LayerNorm partials, ahead of the DMAs (they sit in L2; the weights come from HBM)
 #pragma unroll
         for (int j = 0; j < RING - 1; ++j) fetch_ring(j);
         if constexpr (!BIG) ln_row_stats();  // while the first units are in flight (the 8-wave tile: before its flush -- 16 more registers across its main loop spill)
@@ -1892,8 +1962,12 @@ static void choose_config(int M, int N, int K, int apro, bool ring_allowed, int 
             // epilogue round trips) on top of a K loop that runs at ~130 TFLOP/s.  The workgroup count was fitted IN THE MODEL (profiles/r03_ring_rules_ab.txt:
             // isolated launches with L2-warm activations preferred fewer workgroups and did not predict the model):
             //  * ~10 K-steps per workgroup, up to every resident slot (1280);
-            //  * LayerNorm prologue: every workgroup re-derives its rows' statistics from the producer's partials, which costs more than a K split
-            //    saves -- one tile per workgroup from 160 tiles up (128x3840x1280: 21.0 us against 25.2 with a 2-way split), 2-way below; 4-stage tile.
+            //  * LayerNorm prologue: one tile per workgroup from 160 tiles up, 2-way below; 4-stage tile.  Fitted when every workgroup re-derived its rows'
+            //    statistics behind the prefetch (128x3840x1280: 21.0 us against 25.2 with a 2-way split).  The partials are now fetched ahead of it and the merge
+            //    runs under the weight fetch (ln_issue), and the rule was swept again in the captured graph (tools/site_tune.py --apro 2, all five LayerNorm sites of
+            //    the batch-1 image, profiles/prologue_surcharge_ab.txt): 128x3840x1280 is flat from 480 (one tile each) to 768 workgroups and 0.4 ms per image
+            //    worse from 960 up, 32x3840x1280 keeps its 2-way split (one tile each: +0.2 ms), no candidate of any site beat the rule by the tuner's 30 us
+            //    margin in a way the final re-measurement confirmed -- the rule stands and the site table gets no LayerNorm entry.
             cfg = (g_gemm_ring == 30 && apro == 2) ? 31 : g_gemm_ring;
             resident = ring_resident(cfg, apro);
             const long Tc = tiles_of_cfg(cfg, M, N);

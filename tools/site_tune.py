@@ -1,7 +1,7 @@
 """Per-launch-site tuning of the workgroup count of the batch-1 GEMMs INSIDE the captured graph: for every distinct skinny site
 (M, N, K, operand prologue) of the headline image, coordinate descent over G -- re-capture the GraphSampler with the candidate installed through the test hook,
 time graph replays, keep the best -- two passes.  Prints a table and the C initialiser for gemm.hip's g_sites.
-Usage (GPU box): python tools/site_tune.py [--gemm bf16] [--reps 12] [--passes 2]"""
+Usage (GPU box): python tools/site_tune.py [--gemm bf16] [--reps 12] [--passes 2] [--apro 2]"""
 import argparse
 import collections
 import ctypes
@@ -22,6 +22,7 @@ ap.add_argument("--gemm", default="fp32", choices=["fp32", "bf16"])
 ap.add_argument("--reps", type=int, default=12)
 ap.add_argument("--passes", type=int, default=2)
 ap.add_argument("--max-macs", type=float, default=1.2e9, help="only sites of the skinny class (M*N*K below this)")
+ap.add_argument("--apro", type=int, default=None, choices=[0, 1, 2], help="only the sites of this operand-prologue class (0 none, 1 GRN, 2 LayerNorm)")
 a = ap.parse_args()
 lib = _lib.load()
 dev = torch.device("cuda")
@@ -54,6 +55,8 @@ for t, s5 in zip(us[:n], shp[:n * 5].reshape(n, 5)):
     if tail or pro == 3 or M < 16 or float(M) * N * K >= a.max_macs or K % (64 if bf else 32):  # (M < 16: load-time launches of finalize, not part of an image)
         continue
     key = (M, N, K, 1 if pro in (1, 4) else (2 if pro == 2 else 0))
+    if a.apro is not None and key[3] != a.apro:
+        continue
     sites.setdefault(key, [0, 0.0])
     sites[key][0] += 1
     sites[key][1] += float(t)
