@@ -614,6 +614,43 @@ int paella_op_attention_rg(const float* q, const float* k_self, const float* v_s
                            const float* kw_table, const int* kw_len, int kw_pitch, const int* q_groups, int qg_pitch,
                            const int* k_groups, int kg_pitch, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training loss head (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays 8): the classifier
+ * head (out_mapper: 1x1 convolution, no bias) with the label-smoothed cross-entropy of the reference's training loops
+ * (src/train.py:63-71: nn.CrossEntropyLoss(label_smoothing=0.1, reduction='none')) fused into it, forward and backward.
+ * The [rows, N] logits are never stored: the forward reduces every 64 x 64 logit tile in its epilogue, the backward
+ * recomputes the tiles from h, w and lse.
+ *   h fp32 [rows, K] row-major (the rows of the last LayerNorm2d in NHWC order), w fp32 [N, K] (out_mapper.1.weight),
+ *   target int64 [rows], eps = label_smoothing in [0, 1).  With l[m, n] = sum_k h[m, k] w[n, k] on the exact fp32 path:
+ *     lse[m]    = log sum_n exp(l[m, n])          (running maximum: finite for any finite logits)
+ *     loss[m]   = (1 - eps) (lse[m] - l[m, target[m]]) + eps (lse[m] - (1 / N) sum_n l[m, n])
+ *     argmax[m] = the label of the largest l[m, .], the LOWEST label on ties
+ *   A target outside [0, N) (negative values included: what ignore_index = -100 amounts to under reduction = 'none')
+ *   marks an IGNORED row: loss 0, no contribution to either gradient, lse and argmax still produced; w and the
+ *   workspace are never indexed with it.  Nothing is validated on the host, nothing synchronises.
+ *   Backward, g = grad_loss fp32 [rows]:  d[m, n] = g[m] (exp(l[m, n] - lse[m]) - (1 - eps) [n == target[m]] - eps / N),
+ *   0 on an ignored row;  dh[m, k] = sum_n d[m, n] w[n, k],  dw[n, k] = sum_m d[m, n] h[m, k].  Both are WRITTEN, not
+ *   accumulated into; dh_out or dw_out NULL = that kernel is not launched (a frozen head, inputs without gradient).
+ * Shapes: K a multiple of 16 in 16...256, N a multiple of 16 in 16...65536 (not necessarily of the 64-label tile: the
+ * tail columns are masked), rows in 1...2^24.  Anything else, a NULL required pointer, eps outside [0, 1) or not
+ * finite: PAELLA_ERR_ARG; a workspace smaller than paella_head_loss_workspace_bytes: PAELLA_ERR_WORKSPACE -- both
+ * before anything is enqueued.  The workspace holds one partial per (row, 64-label tile) in the forward; in the
+ * backward one number per (row, tile) -- the row sums that renormalise exp(l - lse), so that the rounding of the ONE
+ * fp32 lse per row does not reach the probabilities -- and a bounded number of [N, K] slabs (a split of the row range
+ * of dw); never anything of rows x N: from 4096 rows up it stays below rows * N bytes, a quarter of one logits tensor.  One workspace serves both calls; it carries no
+ * state between them and needs no initialisation.  Deterministic: no float atomics, every combine (partials in
+ * ascending tile order, slabs in ascending share order) in an order fixed by the shape alone, so two runs give the
+ * same bits.  No allocation, no synchronisation, capturable in a graph.
+ * ---------------------------------------------------------------------------------------------- */
+size_t paella_head_loss_workspace_bytes(int64_t rows, int N, int K); /* 0 for an unsupported shape */
+int paella_head_loss_forward(const float* h, const float* w, const int64_t* target, int64_t rows, int N, int K,
+                             float label_smoothing, float* loss_out, float* lse_out, int* argmax_out /* may be NULL */,
+                             void* ws, size_t ws_bytes, void* stream);
+int paella_head_loss_backward(const float* h, const float* w, const int64_t* target, const float* lse,
+                              const float* grad_loss, int64_t rows, int N, int K, float label_smoothing,
+                              float* dh_out /* may be NULL */, float* dw_out /* may be NULL */, void* ws,
+                              size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -219,6 +219,11 @@ SIGNATURES = {
                                       c_void_p, c_void_p, c_void_p]),
     "paella_renoise_select_stream": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
                                              c_void_p, c_void_p, c_void_p]),
+    # training loss head (ABI 8, additive): classifier + label-smoothed cross-entropy, forward and backward, no logits tensor
+    "paella_head_loss_workspace_bytes": (c_size_t, [c_int64, c_int, c_int]),
+    "paella_head_loss_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "paella_head_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t,
+                                          c_void_p]),
 }
 
 # exported for tests / tools only; declared in paella_amd/csrc/test_hooks.h, not in the public header

@@ -2,7 +2,7 @@
 
 SURVEY 8(f) rank 3: the reference's training loops (src/train.py:59-66, src_distributed/train.py:104-114) call
 `model.train(); pred = model(noised, t, byt5...); loss.backward()`.  The HIP engine behind `Paella.forward` is an inference
-engine (no saved activations, no backward kernels), so in TRAIN mode -- `model.train()`, exactly the switch the reference's
+engine (no saved activations; its only backward kernels are the loss head's, below), so in TRAIN mode -- `model.train()`, exactly the switch the reference's
 loops flip -- `forward` routes here instead: the same network written as autograd-tracked torch ops (dropout active, as in the
 reference).  `model.eval()` (the state a `paella_amd.Paella` is constructed in, and what the sampling path requires) never
 reaches this file: sampling always runs the hand-written HIP kernels and fails loudly without them.
@@ -109,8 +109,9 @@ def c_embeddings(model, byt5, clip, clip_image):
     return F.layer_norm(seq, (c_cond,), None, None, 1e-6)
 
 
-def forward_autograd(model, x, r, byt5, clip=None, clip_image=None, x_cat=None, attn_weights=None):
-    """Paella.forward (src/modules.py:263-275) as autograd-tracked torch ops.  Returns logits [B, num_labels, H, W]."""
+def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None, attn_weights=None):
+    """Paella.forward (src/modules.py:263-275) as autograd-tracked torch ops, up to and including the LayerNorm2d in front of out_mapper's convolution:
+    [B, c_out, H, W] as the permuted view of an NHWC tensor that `_ln_nchw` returns."""
     cfg = model._cfg
     training = model.training
     p_drop = float(model.dropout) if not isinstance(model.dropout, (list, tuple)) else None
@@ -155,4 +156,103 @@ def forward_autograd(model, x, r, byt5, clip=None, clip_image=None, x_cat=None, 
             h = run(blk, i, h, level_outputs[u] if (j == 0 and u > 0 and blk.kind == 'C') else None)
     clf = model.clf._modules["1"]
     h = F.pixel_shuffle(F.conv2d(_ln_nchw(h), clf.weight, clf.bias), patch)
-    return F.conv2d(_ln_nchw(h), model.out_mapper._modules["1"].weight)
+    return _ln_nchw(h)
+
+
+def forward_autograd(model, x, r, byt5, clip=None, clip_image=None, x_cat=None, attn_weights=None):
+    """Paella.forward (src/modules.py:263-275) as autograd-tracked torch ops.  Returns logits [B, num_labels, H, W]."""
+    return F.conv2d(_forward_features(model, x, r, byt5, clip, clip_image, x_cat, attn_weights), model.out_mapper._modules["1"].weight)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# Training loss head: out_mapper's convolution + label-smoothed cross-entropy as ONE HIP op, forward and backward (paella_amd/csrc/loss.hip,
+# include/paella_hip.h "Training loss head").  The [rows, num_labels] logits, their log-softmax and their gradient are never stored: the forward keeps
+# five numbers per row, the backward recomputes the logit tiles from h, the weight and the saved lse.
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+HEAD_MAX_K, HEAD_MAX_LABELS, HEAD_MAX_ROWS = 256, 65536, 1 << 24
+
+
+class _HeadCrossEntropy(torch.autograd.Function):
+    """(h [rows, K], weight [N, K], target [rows]) -> (loss fp32 [rows], argmax int32 [rows]); saves h, weight, target and lse [rows]."""
+
+    @staticmethod
+    def forward(ctx, h, weight, target, eps):
+        from . import _lib
+        lib = _lib.load()
+        rows, K = h.shape
+        N = weight.size(0)
+        dev = h.device
+        loss = torch.empty(rows, dtype=torch.float32, device=dev)
+        lse = torch.empty(rows, dtype=torch.float32, device=dev)
+        argmax = torch.empty(rows, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            ws = _lib.new_workspace(lib.paella_head_loss_workspace_bytes(rows, N, K), dev)
+            _lib.check(lib.paella_head_loss_forward(_lib.ptr(h), _lib.ptr(weight), _lib.ptr(target), rows, N, K, eps, _lib.ptr(loss), _lib.ptr(lse), _lib.ptr(argmax),
+                                                    _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        ctx.save_for_backward(h, weight, target, lse)
+        ctx.eps = eps
+        ctx.mark_non_differentiable(argmax)
+        return loss, argmax
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_argmax):
+        from . import _lib
+        lib = _lib.load()
+        h, weight, target, lse = ctx.saved_tensors
+        rows, K = h.shape
+        N = weight.size(0)
+        dev = h.device
+        g = grad_loss.to(torch.float32).contiguous()
+        dh = torch.empty_like(h) if ctx.needs_input_grad[0] else None  # a NULL output = that kernel is not launched
+        dw = torch.empty_like(weight) if ctx.needs_input_grad[1] else None
+        if dh is not None or dw is not None:
+            with torch.cuda.device(dev):
+                ws = _lib.new_workspace(lib.paella_head_loss_workspace_bytes(rows, N, K), dev)
+                _lib.check(lib.paella_head_loss_backward(_lib.ptr(h), _lib.ptr(weight), _lib.ptr(target), _lib.ptr(lse), _lib.ptr(g), rows, N, K, ctx.eps,
+                                                         _lib.ptr(dh), _lib.ptr(dw), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        return dh, dw, None, None
+
+
+def head_cross_entropy(h, weight, target, label_smoothing=0.0):
+    """Classifier head + cross-entropy without a logits tensor: with l = h @ weight^T,
+        loss   = nn.CrossEntropyLoss(label_smoothing=label_smoothing, reduction='none')(l, target)     (fp32, the shape of `target`; differentiable in h and weight)
+        argmax = l.argmax(-1), the lowest label on ties                                                  (int32, not differentiable)
+    h fp32 [..., K]; weight fp32 [N, K] or [N, K, 1, 1] (out_mapper.1.weight); target int64 with the leading shape of h.  A target outside [0, N) marks an
+    ignored position (loss 0, no gradient), as ignore_index does.  K a multiple of 16 up to 256, N a multiple of 16 up to 65536, at most 2^24 positions.
+    HIP only and exact fp32 only: anything else raises ValueError -- there is no torch fallback."""
+    if not (torch.is_tensor(h) and torch.is_tensor(weight) and torch.is_tensor(target)):
+        raise ValueError("head_cross_entropy takes tensors")
+    if not h.is_cuda or weight.device != h.device or target.device != h.device:
+        raise ValueError("head_cross_entropy runs on the HIP device only: h, weight and target must live on the same cuda device (got %s, %s, %s)"
+                         % (h.device, weight.device, target.device))
+    if h.dtype != torch.float32 or weight.dtype != torch.float32 or target.dtype != torch.int64:
+        raise ValueError("head_cross_entropy takes fp32 h and weight and int64 target (got %s, %s, %s)" % (h.dtype, weight.dtype, target.dtype))
+    if weight.dim() == 4 and weight.size(2) == 1 and weight.size(3) == 1:
+        weight = weight.reshape(weight.size(0), weight.size(1))
+    if weight.dim() != 2 or h.dim() < 1 or h.size(-1) != weight.size(1):
+        raise ValueError("weight must be [N, K] or [N, K, 1, 1] with K = h.size(-1) (got h %s, weight %s)" % (tuple(h.shape), tuple(weight.shape)))
+    N, K = weight.shape
+    lead = h.shape[:-1]
+    if tuple(target.shape) != tuple(lead):
+        raise ValueError("target must have the leading shape of h, %s (got %s)" % (tuple(lead), tuple(target.shape)))
+    rows = target.numel()
+    if K % 16 or not 16 <= K <= HEAD_MAX_K:
+        raise ValueError("K = %d: the fused head takes a multiple of 16 in 16...%d" % (K, HEAD_MAX_K))
+    if N % 16 or not 16 <= N <= HEAD_MAX_LABELS:
+        raise ValueError("N = %d labels: the fused head takes a multiple of 16 in 16...%d" % (N, HEAD_MAX_LABELS))
+    if not 1 <= rows <= HEAD_MAX_ROWS:
+        raise ValueError("%d positions: the fused head takes 1...%d" % (rows, HEAD_MAX_ROWS))
+    eps = float(label_smoothing)
+    if not 0.0 <= eps < 1.0:  # (false for NaN)
+        raise ValueError("label_smoothing = %r: must lie in [0, 1)" % (label_smoothing,))
+    # rows must be contiguous; the NHWC view behind `_ln_nchw`'s result already is (no copy)
+    h2 = h.view(rows, K) if h.is_contiguous() else h.contiguous().view(rows, K)
+    loss, argmax = _HeadCrossEntropy.apply(h2, weight.contiguous(), target.contiguous().view(rows), eps)
+    return loss.view(lead), argmax.view(lead)
+
+
+def forward_loss(model, x, r, target, byt5, clip=None, clip_image=None, x_cat=None, attn_weights=None, label_smoothing=0.1):
+    """One training forward with the loss head fused: (loss [B, H, W], correct [B, H, W] bool) instead of logits [B, num_labels, H, W]."""
+    feat = _forward_features(model, x, r, byt5, clip, clip_image, x_cat, attn_weights)
+    loss, argmax = head_cross_entropy(feat.permute(0, 2, 3, 1), model.out_mapper._modules["1"].weight, target, label_smoothing)
+    return loss, argmax == target
