@@ -559,7 +559,8 @@ int paella_vqgan_finalize(paella_vqgan* v, void* stream); /* synchronises the st
  * multiple of 64 on bf16-operand MFMA with fp32 accumulation (bf16 shadow weights, bf16 LayerNorm output and hidden tensor); everything else stays fp32.
  * Mode 0 (default) is the exact path.  Size workspaces (paella_vqgan_workspace_bytes) AFTER switching. */
 int paella_vqgan_set_precision(paella_vqgan* v, int mode, void* stream); /* mode 1 on a finalized model converts the shadows and waits for them; mode 0 frees nothing and never synchronises */
-/* h, w = latent grid; covers decode and encode of the matching image size */
+/* h, w = latent grid; covers decode and encode of the matching image size.  Exactly this many bytes suffice; fewer is PAELLA_ERR_WORKSPACE before
+ * anything is enqueued */
 size_t paella_vqgan_workspace_bytes(const paella_vqgan* v, int B, int h, int w);
 /* decode_indices (src/vqgan.py:103-107): idx int64 [B,h,w] -> image fp32 NCHW [B,3,f*h,f*w], f = 2^levels */
 int paella_vqgan_decode_indices(paella_vqgan* v, const int64_t* idx, int B, int h, int w, float* img_out, void* ws,
@@ -576,7 +577,8 @@ int paella_vqgan_encode(paella_vqgan* v, const float* img, int B, int Hp, int Wp
  * the stand-in's vq_loss == commit_loss). */
 int paella_vqgan_quantize_rows(paella_vqgan* v, const float* x, int64_t rows, int64_t* idx_out, float* qe_out,
                                float* mse_out, void* stream);
-/* VectorQuantize.idx2vq (src/vqgan.py:104): out fp32 [rows, c_latent] = codebook[idx] */
+/* VectorQuantize.idx2vq (src/vqgan.py:104): out fp32 [rows, c_latent] = codebook[idx].  An index outside [0, codebook_size) is CLAMPED to the nearest
+ * valid one (negative -> row 0, >= codebook_size -> the last row), here and in paella_vqgan_decode_indices: no error, never a read outside the codebook. */
 int paella_vqgan_lookup_rows(paella_vqgan* v, const int64_t* idx, int64_t rows, float* out, void* stream);
 
 /* ------------------------------------------------------------------------------------------------

@@ -379,7 +379,8 @@ static int vq_prepare(paella_vqgan* v, VqBuffers& f, int B, int h, int w, void* 
     if (B <= 0 || h <= 0 || w <= 0) { paella_set_error("bad latent grid"); return PAELLA_ERR_ARG; }
     Arena a(ws, ws_bytes);
     vq_carve(v, a, B, h, w, f);
-    if (!a.ok || !ws) { paella_set_error("workspace too small (%zu needed, %zu given)", a.off, ws_bytes); return PAELLA_ERR_WORKSPACE; }
+    // the documented size is what is required (paella_vqgan_workspace_bytes = the carve + 256): a buffer even one byte short of it is refused
+    if (!a.ok || !ws || ws_bytes < a.off + 256) { paella_set_error("workspace too small (%zu needed, %zu given)", a.off + 256, ws_bytes); return PAELLA_ERR_WORKSPACE; }
     return PAELLA_OK;
 }
 
