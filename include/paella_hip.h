@@ -653,6 +653,43 @@ int paella_head_loss_backward(const float* h, const float* w, const int64_t* tar
                               float* dh_out /* may be NULL */, float* dw_out /* may be NULL */, void* ws,
                               size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training MLP activation (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays 8): the
+ * middle of every ResBlock / FeedForwardBlock MLP in train mode -- GELU -> GlobalResponseNorm -> Dropout
+ * (reference src/modules.py:30-40, 49-53) -- as one op, forward and backward (paella_amd/csrc/grn_act.hip).
+ *   u fp32 [B, P, C]: the rows of the first Linear in NHWC order, P = H * W positions per sample; gamma, beta fp32 [C].
+ *   With h = GELU(u) by the engine's exact-path erf form (train and eval agree on the activation):
+ *     G[b, c] = sqrt(sum_p h^2),  M[b] = mean_c G[b, c],  n = G / (M + 1e-6),
+ *     y = h (1 + gamma_c n[b, c]) + beta_c,  z = keep y (1 / (1 - p_drop)).
+ *   gx_out receives G as [B, C]: with u and gamma it is ALL the backward needs -- h, y and the mask are recomputed.
+ *   Dropout: p_drop == 0 draws nothing and z == y.  Otherwise element e (its flat index in [B, P, C]) takes word e & 3
+ *   of philox4x32(seed ^ 0xa0761d6478bd642f, counter (e >> 2, 0)) and is kept iff (word >> 8) * 2^-24 >= p_drop; the
+ *   scale is the one fp32 division 1.0f / (1.0f - p_drop).  The backward regenerates the mask from (seed, e).
+ *   Backward for a given dz fp32 [B, P, C]:  dy = keep dz / (1 - p),  dbeta_c = sum_{b, p} dy,  S[b, c] = sum_p dy h,
+ *     dgamma_c = sum_b n[b, c] S[b, c],  dn = gamma_c S,  dG = dn / (M + eps) - (sum_c' dn[b, c'] G[b, c']) / (C (M + eps)^2),
+ *     dh = dy (1 + gamma_c n) + (G > 0 ? dG / G : 0) h,  du = dh (Phi(u) + u phi(u)).
+ *   du, dgamma and dbeta are WRITTEN, not accumulated into; each may be NULL, and with all three NULL nothing is
+ *   launched.  A channel that is identically zero in a sample (G = 0) gets torch.norm's gradient there, 0.
+ * Shapes: C a multiple of 4 in 4...16384, P in 1...2^20, B in 1...65535; every tensor and the workspace 16-byte
+ * aligned; all element offsets are 64-bit.  Anything else, a NULL required pointer, p_drop outside [0, 1) or not
+ * finite: PAELLA_ERR_ARG; a workspace smaller than paella_grn_act_workspace_bytes: PAELLA_ERR_WORKSPACE -- both
+ * before anything is enqueued.  Each direction makes two passes over the tensor (column sums over strips of rows;
+ * the apply) around small finalize launches.  The workspace holds the per-strip partials [B, strips, C] (one set in
+ * the forward, two in the backward; a strip is at least 8 rows, so at most a quarter of one activation tensor) and four
+ * [B, C] / [B] tables.  One workspace serves both calls; it carries no state between them and needs no
+ * initialisation.  Deterministic: no float atomics, no tickets; partials are combined in ascending strip order,
+ * the per-sample terms of dgamma / dbeta in ascending b, the sums over channels by a fixed tree, and the strip
+ * count depends on (P, C) only -- two runs and two devices give the same bits, and the values of a sample depend
+ * neither on its index b nor on the batch size.  No allocation, no synchronisation, capturable in a graph.
+ * ---------------------------------------------------------------------------------------------- */
+size_t paella_grn_act_workspace_bytes(int B, int P, int C); /* 0 for an unsupported shape */
+int paella_grn_act_forward(const float* u, const float* gamma, const float* beta, int B, int P, int C, float p_drop,
+                           uint64_t seed, float* z_out, float* gx_out, void* ws, size_t ws_bytes, void* stream);
+int paella_grn_act_backward(const float* u, const float* gamma, const float* gx, const float* dz, int B, int P, int C,
+                            float p_drop, uint64_t seed, float* du_out /* may be NULL */,
+                            float* dgamma_out /* may be NULL */, float* dbeta_out /* may be NULL */, void* ws,
+                            size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

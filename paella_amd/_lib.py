@@ -224,6 +224,11 @@ SIGNATURES = {
     "paella_head_loss_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "paella_head_loss_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int64, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t,
                                           c_void_p]),
+    # training MLP activation (ABI 8, additive): GELU -> GlobalResponseNorm -> dropout, forward and backward, only u and G [B, C] kept
+    "paella_grn_act_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "paella_grn_act_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_uint64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "paella_grn_act_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                        c_void_p]),
 }
 
 # exported for tests / tools only; declared in paella_amd/csrc/test_hooks.h, not in the public header

@@ -272,6 +272,7 @@ class Paella(nn.Module):
         self._loaded_sig = None
         self._ws = None
         self._precision = 0
+        self._train_activation = "torch"
         # Constructed in EVAL mode (an nn.Module normally starts in train mode): eval = the hand-written HIP engine, which is what
         # sampling needs; `model.train()` -- the switch the reference's training loops flip (src/train.py:47,
         # src_distributed/train.py:73,140,172) -- selects the differentiable torch-op evaluation of paella_amd/training.py.
@@ -411,6 +412,17 @@ class Paella(nn.Module):
 
     def get_gemm_precision(self):
         return "bf16" if self._precision == 1 else "fp32"
+
+    def set_training_activation(self, mode):
+        """How the TRAIN-mode forward (`forward` and `forward_loss` after `model.train()`) runs the GELU -> GlobalResponseNorm -> Dropout stretch of every
+        ResBlock / FeedForwardBlock MLP: "torch" (default) is the chain of torch ops, op for op as before; "hip" runs it as one HIP op in both directions
+        (`paella_amd.training.gelu_grn_dropout`) when the module is on a cuda device -- autograd then keeps the MLP's pre-activation and one [B, 4c] table
+        instead of four or five [B, H, W, 4c] tensors, and the dropout masks come from one 64-bit seed per MLP drawn from torch's default CPU generator
+        (`torch.manual_seed` reproduces a run; the masks are not the torch chain's).  Eval mode -- the HIP inference engine -- never sees the switch."""
+        if mode not in ("torch", "hip"):
+            raise ValueError("training activation must be 'torch' or 'hip'")
+        self._train_activation = mode
+        return self
 
     def __del__(self):
         h = getattr(self, "_handle", None)

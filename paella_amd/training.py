@@ -2,7 +2,7 @@
 
 SURVEY 8(f) rank 3: the reference's training loops (src/train.py:59-66, src_distributed/train.py:104-114) call
 `model.train(); pred = model(noised, t, byt5...); loss.backward()`.  The HIP engine behind `Paella.forward` is an inference
-engine (no saved activations; its only backward kernels are the loss head's, below), so in TRAIN mode -- `model.train()`, exactly the switch the reference's
+engine (no saved activations; its only backward kernels are the loss head's and the MLP activation's, below), so in TRAIN mode -- `model.train()`, exactly the switch the reference's
 loops flip -- `forward` routes here instead: the same network written as autograd-tracked torch ops (dropout active, as in the
 reference).  `model.eval()` (the state a `paella_amd.Paella` is constructed in, and what the sampling path requires) never
 reaches this file: sampling always runs the hand-written HIP kernels and fails loudly without them.
@@ -22,9 +22,13 @@ def _ln_nchw(x, eps=1e-6):
     return F.layer_norm(x.permute(0, 2, 3, 1), (x.size(1),), None, None, eps).permute(0, 3, 1, 2)
 
 
-def _channelwise(blk, x_nhwc, p_drop, training):
-    """Linear -> GELU -> GlobalResponseNorm -> Dropout -> Linear (src/modules.py:49-53 / 30-40)."""
+def _channelwise(blk, x_nhwc, p_drop, training, hip_act=False):
+    """Linear -> GELU -> GlobalResponseNorm -> Dropout -> Linear (src/modules.py:49-53 / 30-40).  hip_act (Paella.set_training_activation("hip"), train mode on a cuda
+    device): the three middle stages run as one HIP op in both directions (`gelu_grn_dropout` below)."""
     cw = blk.channelwise._modules
+    if hip_act:
+        h = gelu_grn_dropout(F.linear(x_nhwc, cw["0"].weight, cw["0"].bias), cw["2"].gamma, cw["2"].beta, p_drop)
+        return F.linear(h, cw["4"].weight, cw["4"].bias)
     h = F.gelu(F.linear(x_nhwc, cw["0"].weight, cw["0"].bias))
     gx = torch.norm(h, p=2, dim=(1, 2), keepdim=True)
     nx = gx / (gx.mean(dim=-1, keepdim=True) + 1e-6)
@@ -33,7 +37,7 @@ def _channelwise(blk, x_nhwc, p_drop, training):
     return F.linear(h, cw["4"].weight, cw["4"].bias)
 
 
-def _res_block(blk, x, skip, p_drop, training):
+def _res_block(blk, x, skip, p_drop, training, hip_act=False):
     """ResBlock (src/modules.py:43-62): depthwise 3x3 (groups = c, over cat([x, skip]) when a skip arrives) -> LN -> MLP -> + x."""
     res = x
     if skip is not None:
@@ -41,12 +45,12 @@ def _res_block(blk, x, skip, p_drop, training):
     dw = blk.depthwise
     c = dw.weight.size(0)
     x = _ln_nchw(F.conv2d(x, dw.weight, dw.bias, padding=dw.weight.size(-1) // 2, groups=c)).permute(0, 2, 3, 1)
-    return _channelwise(blk, x, p_drop, training).permute(0, 3, 1, 2) + res
+    return _channelwise(blk, x, p_drop, training, hip_act).permute(0, 3, 1, 2) + res
 
 
-def _ff_block(blk, x, p_drop, training):
+def _ff_block(blk, x, p_drop, training, hip_act=False):
     """FeedForwardBlock (src/modules.py:82-96)."""
-    return x + _channelwise(blk, _ln_nchw(x).permute(0, 2, 3, 1), p_drop, training).permute(0, 3, 1, 2)
+    return x + _channelwise(blk, _ln_nchw(x).permute(0, 2, 3, 1), p_drop, training, hip_act).permute(0, 3, 1, 2)
 
 
 def _timestep_block(blk, x, r_embed):
@@ -127,15 +131,18 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
     emb = model.embedding._modules["1"]
     h = _ln_nchw(F.conv2d(F.pixel_unshuffle(h, patch), emb.weight, emb.bias))
 
+    # Paella.set_training_activation: the switch acts in train mode on a cuda device only; its default leaves every call below as it is
+    hip_act = training and getattr(model, "_train_activation", "torch") == "hip" and x.is_cuda
+
     def run(blk, level, h, skip=None):
         if blk.kind == 'C':
-            return _res_block(blk, h, skip, drop(level), training)
+            return _res_block(blk, h, skip, drop(level), training, hip_act)
         if blk.kind == 'A':
             return _attn_block(blk, h, c_embed, cfg["nhead"][level], cfg["self_attn"], drop(level), training, attn_weights)
         if blk.kind == 'T':
             return _timestep_block(blk, h, r_embed)
         if blk.kind == 'F':
-            return _ff_block(blk, h, drop(level), training)
+            return _ff_block(blk, h, drop(level), training, hip_act)
         if blk.kind == 'D':  # LayerNorm2d + Conv2d(k2, s2)   (src/modules.py:153-156)
             cv = blk._modules["1"]
             return F.conv2d(_ln_nchw(h), cv.weight, cv.bias, stride=2)
@@ -256,3 +263,92 @@ def forward_loss(model, x, r, target, byt5, clip=None, clip_image=None, x_cat=No
     feat = _forward_features(model, x, r, byt5, clip, clip_image, x_cat, attn_weights)
     loss, argmax = head_cross_entropy(feat.permute(0, 2, 3, 1), model.out_mapper._modules["1"].weight, target, label_smoothing)
     return loss, argmax == target
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# Training MLP activation: GELU -> GlobalResponseNorm -> Dropout of `_channelwise` as ONE HIP op, forward and backward (paella_amd/csrc/grn_act.hip,
+# include/paella_hip.h "Training MLP activation").  Of the widest activation of the network, [B, H, W, 4c], autograd keeps the pre-activation only (plus
+# G [B, 4c]): the GELU output, h * nx, the dropout mask and the dropout input are recomputed, the mask from a (seed, element index) counter.
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+ACT_MAX_B, ACT_MAX_P, ACT_MAX_C = 65535, 1 << 20, 16384
+
+
+class _GeluGrnDropout(torch.autograd.Function):
+    """(u [B, P, C], gamma [C], beta [C]) -> z [B, P, C]; saves u, gamma and gx [B, C]."""
+
+    @staticmethod
+    def forward(ctx, u, gamma, beta, p, seed):
+        from . import _lib
+        lib = _lib.load()
+        B, P, C = u.shape
+        dev = u.device
+        z = torch.empty_like(u)
+        gx = torch.empty(B, C, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            ws = torch.empty(lib.paella_grn_act_workspace_bytes(B, P, C), dtype=torch.uint8, device=dev)  # no state, no initialisation
+            _lib.check(lib.paella_grn_act_forward(_lib.ptr(u), _lib.ptr(gamma), _lib.ptr(beta), B, P, C, p, seed, _lib.ptr(z), _lib.ptr(gx), _lib.ptr(ws), ws.numel(),
+                                                  _lib.stream_ptr(dev)))
+        ctx.save_for_backward(u, gamma, gx)
+        ctx.p, ctx.seed = p, seed
+        return z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dz):
+        from . import _lib
+        lib = _lib.load()
+        u, gamma, gx = ctx.saved_tensors
+        B, P, C = u.shape
+        dev = u.device
+        dz = _aligned(dz.to(torch.float32).contiguous())
+        du = torch.empty_like(u) if ctx.needs_input_grad[0] else None  # a NULL output is not computed
+        dgamma = torch.empty_like(gamma) if ctx.needs_input_grad[1] else None
+        dbeta = torch.empty_like(gamma) if ctx.needs_input_grad[2] else None
+        if du is not None or dgamma is not None or dbeta is not None:
+            with torch.cuda.device(dev):
+                ws = torch.empty(lib.paella_grn_act_workspace_bytes(B, P, C), dtype=torch.uint8, device=dev)
+                _lib.check(lib.paella_grn_act_backward(_lib.ptr(u), _lib.ptr(gamma), _lib.ptr(gx), _lib.ptr(dz), B, P, C, ctx.p, ctx.seed, _lib.ptr(du), _lib.ptr(dgamma),
+                                                       _lib.ptr(dbeta), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        return du, dgamma, dbeta, None, None
+
+
+def _aligned(t):
+    """the kernels move 16-byte vectors: a contiguous view that starts off that grain is copied"""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+def gelu_grn_dropout(u, gamma, beta, p=0.0, seed=None):
+    """The middle of a ResBlock / FeedForwardBlock MLP in train mode as one op: with h = gelu(u),
+        z = dropout(gamma * (h * nx) + beta + h, p),   nx = Gx / (mean_c Gx + 1e-6),   Gx = ||h||_2 over the positions of a sample
+    (src/modules.py:30-40, 49-53).  u fp32 [B, ..., C] (the dimensions between the first and the last are the positions of a sample); gamma, beta fp32 with C
+    elements (the module's [1, 1, 1, C] parameters as they are).  Once differentiable in u, gamma and beta; autograd keeps u, gamma and Gx [B, C] only.  p in
+    [0, 1); p = 0 draws nothing.  The dropout mask is a function of (seed, element index): seed = None with p > 0 draws one 64-bit seed from torch's default CPU
+    generator, so torch.manual_seed reproduces a run.  C a multiple of 4 up to 16384, at most 2^20 positions per sample, B up to 65535.  HIP only and exact fp32
+    only: anything else raises ValueError -- there is no torch fallback."""
+    if not (torch.is_tensor(u) and torch.is_tensor(gamma) and torch.is_tensor(beta)):
+        raise ValueError("gelu_grn_dropout takes tensors")
+    if u.dtype != torch.float32 or gamma.dtype != torch.float32 or beta.dtype != torch.float32:
+        raise ValueError("gelu_grn_dropout takes fp32 u, gamma and beta (got %s, %s, %s)" % (u.dtype, gamma.dtype, beta.dtype))
+    if u.dim() < 2:
+        raise ValueError("u must be [B, ..., C] (got %s)" % (tuple(u.shape),))
+    B, C = u.size(0), u.size(-1)
+    if gamma.numel() != C or beta.numel() != C:
+        raise ValueError("gamma and beta must have C = u.size(-1) = %d elements (got %s, %s)" % (C, tuple(gamma.shape), tuple(beta.shape)))
+    if C % 4 or not 4 <= C <= ACT_MAX_C:
+        raise ValueError("C = %d: the fused activation takes a multiple of 4 in 4...%d" % (C, ACT_MAX_C))
+    P = u.numel() // (B * C) if B else 0
+    if not 1 <= B <= ACT_MAX_B or not 1 <= P <= ACT_MAX_P:
+        raise ValueError("u %s: the fused activation takes 1...%d samples of 1...%d positions" % (tuple(u.shape), ACT_MAX_B, ACT_MAX_P))
+    p = float(p)
+    if not 0.0 <= p < 1.0:  # (false for NaN)
+        raise ValueError("p = %r: must lie in [0, 1)" % (p,))
+    if not u.is_cuda or gamma.device != u.device or beta.device != u.device:
+        raise ValueError("gelu_grn_dropout runs on the HIP device only: u, gamma and beta must live on the same cuda device (got %s, %s, %s)"
+                         % (u.device, gamma.device, beta.device))
+    if p == 0.0:
+        seed = 0
+    elif seed is None:
+        seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    z = _GeluGrnDropout.apply(_aligned(u.contiguous()).view(B, P, C), _aligned(gamma.contiguous().view(C)), _aligned(beta.contiguous().view(C)), p, seed)
+    return z.view(u.shape)
