@@ -690,6 +690,49 @@ int paella_grn_act_backward(const float* u, const float* gamma, const float* gx,
                             float* dgamma_out /* may be NULL */, float* dbeta_out /* may be NULL */, void* ws,
                             size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training ResBlock front (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays 8): the
+ * front of every ResBlock in train mode -- [cat with the skip ->] depthwise Conv2d(k 3, zero padding, groups C) ->
+ * LayerNorm2d(C, no affine) (reference src/modules.py:46-47, 55-58) -- as one op, forward and backward
+ * (paella_amd/csrc/dwconv_train.hip).  Everything fp32.
+ *   x [B, H, W, C] NHWC; skip [B, H, W, C] NHWC or NULL; w [C, J, 3, 3] exactly as the parameter is stored, J = 2
+ *   with a skip, else 1; bias [C].  Output channel g reads concatenated channels J g + j; concatenated channel
+ *   cc < C lives in x, cc >= C in skip at cc - C -- the concatenation is never formed.
+ *   Forward:  a = conv3x3_zero_pad(xcat, w) + bias;  per position mean and var over C (two-pass, as the eval
+ *     kernel), rstd = 1 / sqrt(var + eps);  y = (a - mean) rstd, NHWC.  rstd_out [B H W] (one float per position)
+ *     is, with x, skip, w and y, ALL the backward needs.
+ *   Backward for a given dy [B, H, W, C]:  c1 = mean_c dy,  c2 = mean_c(dy y),  da = rstd (dy - c1 - y c2);
+ *     dbias[c] = sum_pos da;  dw[c][j][ky][kx] = sum_pos da[pos][c] xcat[pos + (ky - 1, kx - 1)][J c + j];
+ *     dxcat[pos][J c + j] = sum_taps da[pos - (ky - 1, kx - 1)][c] w[c][j][ky][kx], split back into dx and dskip;
+ *     positions outside the image contribute 0.  dx, dskip, dw (in the parameter's layout) and dbias are WRITTEN,
+ *     not accumulated into; each may be NULL and is then not computed; with all four NULL nothing is launched.
+ * Shapes: C a multiple of 4 in 4...8192, with a skip a multiple of 8 in 8...4096 (the eval kernel's limits);
+ * B, H, W >= 1 with B H W <= 2^31 - 1; 3 x 3 only; every tensor and the workspace 16-byte aligned; eps positive
+ * and finite; all element offsets are 64-bit.  Anything else, a NULL required pointer, dskip without skip:
+ * PAELLA_ERR_ARG; a workspace too small for the call: PAELLA_ERR_WORKSPACE -- both before anything is enqueued.
+ * Workspace (no state between calls, no initialisation):
+ *   forward : the weights repacked to [J, 9, C]: 36 J C bytes rounded up to 256 -- which is what
+ *             paella_dwconv_ln_train_workspace_bytes(1, 1, 1, C, has_skip) returns, and all the forward asks for;
+ *   backward: da [B, H, W, C] (one activation tensor, rounded up to 256 bytes) and, when the positions fall into
+ *             more than one strip, the per-strip partials of dw and dbias, strips x (9 J + 1) x C floats in two
+ *             blocks rounded up to 256.  A strip is max(8 (9 J + 1), ceil(B H W / 1024)) positions, so the partials
+ *             stay under a quarter of an activation tensor: at most 1.25 activation tensors + 768 bytes in all.
+ *   paella_dwconv_ln_train_workspace_bytes returns the larger of the two; one workspace of that size serves both.
+ * Deterministic: no float atomics, no tickets, every combine is a launch.  y, dx and dskip of a sample depend
+ * neither on its index nor on the batch around it; dw and dbias are summed in fp64 inside a strip of consecutive
+ * positions (b, y, x ascending) and the strips in ascending order, strips fixed by (B, H, W, C, J) alone.
+ * No allocation, no synchronisation, capturable in a graph.
+ * ---------------------------------------------------------------------------------------------- */
+size_t paella_dwconv_ln_train_workspace_bytes(int B, int H, int W, int C, int has_skip); /* 0 for an unsupported shape */
+int paella_dwconv_ln_train_forward(const float* x, const float* skip /* may be NULL */, const float* w,
+                                   const float* bias, int B, int H, int W, int C, float eps, float* y_out,
+                                   float* rstd_out, void* ws, size_t ws_bytes, void* stream);
+int paella_dwconv_ln_train_backward(const float* x, const float* skip /* may be NULL */, const float* w,
+                                    const float* y, const float* rstd, const float* dy, int B, int H, int W, int C,
+                                    float* dx_out /* may be NULL */, float* dskip_out /* may be NULL */,
+                                    float* dw_out /* may be NULL */, float* dbias_out /* may be NULL */, void* ws,
+                                    size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -229,6 +229,11 @@ SIGNATURES = {
     "paella_grn_act_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_uint64, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "paella_grn_act_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                         c_void_p]),
+    # training ResBlock front (ABI 8, additive): depthwise 3x3 (+ skip read in place) + LayerNorm, forward and backward, only rstd [B H W] kept besides y
+    "paella_dwconv_ln_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "paella_dwconv_ln_train_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "paella_dwconv_ln_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                c_void_p, c_size_t, c_void_p]),
 }
 
 # exported for tests / tools only; declared in paella_amd/csrc/test_hooks.h, not in the public header

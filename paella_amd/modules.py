@@ -273,6 +273,7 @@ class Paella(nn.Module):
         self._ws = None
         self._precision = 0
         self._train_activation = "torch"
+        self._train_depthwise = "torch"
         # Constructed in EVAL mode (an nn.Module normally starts in train mode): eval = the hand-written HIP engine, which is what
         # sampling needs; `model.train()` -- the switch the reference's training loops flip (src/train.py:47,
         # src_distributed/train.py:73,140,172) -- selects the differentiable torch-op evaluation of paella_amd/training.py.
@@ -422,6 +423,20 @@ class Paella(nn.Module):
         if mode not in ("torch", "hip"):
             raise ValueError("training activation must be 'torch' or 'hip'")
         self._train_activation = mode
+        return self
+
+    def set_training_depthwise(self, mode):
+        """How the TRAIN-mode forward (`forward` and `forward_loss` after `model.train()`) runs the front of every ResBlock -- the concatenation with the skip,
+        the depthwise 3x3 convolution, the LayerNorm2d and the change to NHWC: "torch" (default) is the chain of torch ops, op for op as before; "hip" runs it as
+        one HIP op in both directions (`paella_amd.training.dwconv_layernorm`) when the module is on a cuda device -- x and the skip are read in place, the trunk
+        is kept in channels_last memory, and besides the block's input and the MLP's input autograd keeps one float per position.  Independent of
+        `set_training_activation`.  The op is 3 x 3 only: "hip" on a module built with another kernel_size raises ValueError.  Eval mode -- the HIP inference
+        engine -- never sees the switch."""
+        if mode not in ("torch", "hip"):
+            raise ValueError("training depthwise must be 'torch' or 'hip'")
+        if mode == "hip" and int(self._cfg["kernel_size"]) != 3:
+            raise ValueError("training depthwise 'hip' takes kernel_size 3 only (this module has %d)" % int(self._cfg["kernel_size"]))
+        self._train_depthwise = mode
         return self
 
     def __del__(self):

@@ -37,9 +37,14 @@ def _channelwise(blk, x_nhwc, p_drop, training, hip_act=False):
     return F.linear(h, cw["4"].weight, cw["4"].bias)
 
 
-def _res_block(blk, x, skip, p_drop, training, hip_act=False):
-    """ResBlock (src/modules.py:43-62): depthwise 3x3 (groups = c, over cat([x, skip]) when a skip arrives) -> LN -> MLP -> + x."""
+def _res_block(blk, x, skip, p_drop, training, hip_act=False, hip_dw=False):
+    """ResBlock (src/modules.py:43-62): depthwise 3x3 (groups = c, over cat([x, skip]) when a skip arrives) -> LN -> MLP -> + x.  hip_dw
+    (Paella.set_training_depthwise("hip"), train mode on a cuda device): everything in front of the MLP runs as one HIP op in both directions
+    (`dwconv_layernorm` below), x and skip handed over separately -- no torch.cat."""
     res = x
+    if hip_dw:
+        y = dwconv_layernorm(x, blk.depthwise.weight, blk.depthwise.bias, skip)
+        return _channelwise(blk, y, p_drop, training, hip_act).permute(0, 3, 1, 2) + res
     if skip is not None:
         x = torch.cat([x, skip], dim=1)
     dw = blk.depthwise
@@ -133,10 +138,14 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
 
     # Paella.set_training_activation: the switch acts in train mode on a cuda device only; its default leaves every call below as it is
     hip_act = training and getattr(model, "_train_activation", "torch") == "hip" and x.is_cuda
+    # Paella.set_training_depthwise: likewise.  Under it the trunk is made channels_last once, here, so that the blocks hand each other NHWC memory
+    hip_dw = training and getattr(model, "_train_depthwise", "torch") == "hip" and x.is_cuda
+    if hip_dw:
+        h = h.contiguous(memory_format=torch.channels_last)
 
     def run(blk, level, h, skip=None):
         if blk.kind == 'C':
-            return _res_block(blk, h, skip, drop(level), training, hip_act)
+            return _res_block(blk, h, skip, drop(level), training, hip_act, hip_dw)
         if blk.kind == 'A':
             return _attn_block(blk, h, c_embed, cfg["nhead"][level], cfg["self_attn"], drop(level), training, attn_weights)
         if blk.kind == 'T':
@@ -352,3 +361,104 @@ def gelu_grn_dropout(u, gamma, beta, p=0.0, seed=None):
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     z = _GeluGrnDropout.apply(_aligned(u.contiguous()).view(B, P, C), _aligned(gamma.contiguous().view(C)), _aligned(beta.contiguous().view(C)), p, seed)
     return z.view(u.shape)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# Training ResBlock front: [cat with the skip ->] depthwise 3x3 -> LayerNorm2d -> NHWC as ONE HIP op, forward and backward (paella_amd/csrc/dwconv_train.hip,
+# include/paella_hip.h "Training ResBlock front").  x and skip are read in place (no concatenation), the weight is used and its gradient returned in the
+# parameter's layout, and besides the op's inputs and its output autograd keeps one float per position (rstd): the concatenated input, the convolution output and
+# the LayerNorm's contiguous copy of the torch chain never exist.
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+DW_MAX_C, DW_MAX_C_SKIP, DW_MAX_POSITIONS = 8192, 4096, 2 ** 31 - 1
+# diagnostic: how often `dwconv_layernorm` ran and how many of its x / skip arguments were not dense NHWC memory and had to be copied (tools/bench_train_dwconv.py)
+DW_COUNTERS = {"calls": 0, "copied": 0}
+
+
+class _DwconvLayerNorm(torch.autograd.Function):
+    """(x [B, H, W, C], skip [B, H, W, C] or None, weight [C, J, 3, 3], bias [C]) -> y [B, H, W, C]; saves x, skip, weight, y and rstd [B, H, W]."""
+
+    @staticmethod
+    def forward(ctx, x, skip, weight, bias, eps):
+        from . import _lib
+        lib = _lib.load()
+        B, H, W, C = x.shape
+        dev = x.device
+        y = torch.empty_like(x)
+        rstd = torch.empty(B, H, W, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            # the forward asks for the repacked weights only, which is what the sizing call returns for one position
+            ws = torch.empty(lib.paella_dwconv_ln_train_workspace_bytes(1, 1, 1, C, int(skip is not None)), dtype=torch.uint8, device=dev)
+            _lib.check(lib.paella_dwconv_ln_train_forward(_lib.ptr(x), _lib.ptr(skip), _lib.ptr(weight), _lib.ptr(bias), B, H, W, C, eps, _lib.ptr(y), _lib.ptr(rstd),
+                                                          _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
+        ctx.save_for_backward(x, skip, weight, y, rstd)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        from . import _lib
+        lib = _lib.load()
+        x, skip, weight, y, rstd = ctx.saved_tensors
+        B, H, W, C = x.shape
+        dev = x.device
+        dy = _aligned(dy.to(torch.float32).contiguous())
+        need = ctx.needs_input_grad
+        dx = torch.empty_like(x) if need[0] else None  # a NULL output is not computed
+        dskip = torch.empty_like(skip) if skip is not None and need[1] else None
+        dw = torch.empty_like(weight) if need[2] else None
+        dbias = torch.empty(C, dtype=torch.float32, device=dev) if need[3] else None
+        if dx is not None or dskip is not None or dw is not None or dbias is not None:
+            with torch.cuda.device(dev):
+                ws = torch.empty(lib.paella_dwconv_ln_train_workspace_bytes(B, H, W, C, int(skip is not None)), dtype=torch.uint8, device=dev)
+                _lib.check(lib.paella_dwconv_ln_train_backward(_lib.ptr(x), _lib.ptr(skip), _lib.ptr(weight), _lib.ptr(y), _lib.ptr(rstd), _lib.ptr(dy), B, H, W, C,
+                                                               _lib.ptr(dx), _lib.ptr(dskip), _lib.ptr(dw), _lib.ptr(dbias), _lib.ptr(ws), ws.numel(),
+                                                               _lib.stream_ptr(dev)))
+        return dx, dskip, dw, dbias, None
+
+
+def _nhwc(t):
+    """[B, C, H, W] of any strides -> its [B, H, W, C] view when the memory is already dense NHWC and 16-byte aligned, else one copy"""
+    v = t.permute(0, 2, 3, 1)
+    if v.is_contiguous() and v.data_ptr() % 16 == 0:
+        return v
+    DW_COUNTERS["copied"] += 1
+    return v.contiguous() if not v.is_contiguous() else v.clone()
+
+
+def dwconv_layernorm(x, weight, bias, skip=None, eps=1e-6):
+    """The front of a ResBlock in train mode as one op (src/modules.py:46-47, 55-58):
+        y = layer_norm(conv2d(cat([x, skip], 1) if skip is not None else x, weight, bias, padding=1, groups=C).permute(0, 2, 3, 1), (C,), eps=eps)
+    x and skip fp32 with logical shape [B, C, H, W] and any strides: memory that is already dense NHWC (`x.permute(0, 2, 3, 1).is_contiguous()`) is used in place,
+    anything else is copied once.  weight fp32 [C, 1, 3, 3], or [C, 2, 3, 3] with a skip, and bias fp32 [C]: the module's parameters as they are.  Returns y
+    [B, H, W, C], contiguous -- what `_channelwise` consumes.  Once differentiable in x, skip, weight and bias; the gradients of x and skip come back with logical
+    shape [B, C, H, W] over NHWC memory, the weight's in the parameter's layout.  Besides its inputs and y autograd keeps one float per position.  C a multiple of
+    4 up to 8192, with a skip a multiple of 8 up to 4096; at most 2^31 - 1 positions.  HIP only, exact fp32 only, 3 x 3 only: anything else raises ValueError --
+    there is no torch fallback."""
+    if not (torch.is_tensor(x) and torch.is_tensor(weight) and torch.is_tensor(bias)) or not (skip is None or torch.is_tensor(skip)):
+        raise ValueError("dwconv_layernorm takes tensors")
+    if x.dtype != torch.float32 or weight.dtype != torch.float32 or bias.dtype != torch.float32 or (skip is not None and skip.dtype != torch.float32):
+        raise ValueError("dwconv_layernorm takes fp32 x, skip, weight and bias (got %s, %s, %s, %s)" % (x.dtype, None if skip is None else skip.dtype, weight.dtype, bias.dtype))
+    if x.dim() != 4:
+        raise ValueError("x must be [B, C, H, W] (got %s)" % (tuple(x.shape),))
+    B, C, H, W = x.shape
+    if skip is not None and tuple(skip.shape) != tuple(x.shape):
+        raise ValueError("skip must have the shape of x, %s (got %s)" % (tuple(x.shape), tuple(skip.shape)))
+    J = 1 if skip is None else 2
+    if weight.dim() != 4 or weight.size(2) != 3 or weight.size(3) != 3:
+        raise ValueError("weight %s: the fused ResBlock front takes a 3 x 3 depthwise kernel only" % (tuple(weight.shape),))
+    if tuple(weight.shape) != (C, J, 3, 3) or bias.numel() != C:
+        raise ValueError("weight must be [C, %d, 3, 3] %s a skip and bias [C] with C = x.size(1) = %d (got %s, %s)"
+                         % (J, "with" if J == 2 else "without", C, tuple(weight.shape), tuple(bias.shape)))
+    cmax, grain = (DW_MAX_C, 4) if skip is None else (DW_MAX_C_SKIP, 8)
+    if C % grain or not grain <= C <= cmax:
+        raise ValueError("C = %d: the fused ResBlock front takes a multiple of %d in %d...%d%s" % (C, grain, grain, cmax, "" if skip is None else " with a skip"))
+    if B < 1 or H < 1 or W < 1 or B * H * W > DW_MAX_POSITIONS:
+        raise ValueError("x %s: the fused ResBlock front takes 1...2^31 - 1 positions" % (tuple(x.shape),))
+    eps = float(eps)
+    if not 0.0 < eps < 1e30:  # (false for NaN)
+        raise ValueError("eps = %r: must be positive and finite" % (eps,))
+    if not x.is_cuda or weight.device != x.device or bias.device != x.device or (skip is not None and skip.device != x.device):
+        raise ValueError("dwconv_layernorm runs on the HIP device only: x, skip, weight and bias must live on the same cuda device (got %s, %s, %s, %s)"
+                         % (x.device, None if skip is None else skip.device, weight.device, bias.device))
+    DW_COUNTERS["calls"] += 1
+    return _DwconvLayerNorm.apply(_nhwc(x), None if skip is None else _nhwc(skip), _aligned(weight.contiguous()), _aligned(bias.contiguous().view(C)), eps)

@@ -1,0 +1,266 @@
+"""The training ResBlock front ([cat with the skip ->] depthwise 3x3 -> LayerNorm2d -> NHWC), two ways, on the same seeded inputs in ONE process:
+
+    torch   what `training._res_block` runs in front of its MLP by default: torch.cat -> F.conv2d(groups=C) -> F.layer_norm over a permuted view, and autograd's
+            backward through that chain
+    fused   paella_amd.training.dwconv_layernorm (paella_amd/csrc/dwconv_train.hip): the same stretch as one HIP op in both directions, x and skip read in place
+
+Every part is one process and one GPU step; run each under its own time limit:
+
+    timeout 300 python tools/bench_train_dwconv.py op   [--shapes 16x16x16x640 16x8x8x1280 16x4x4x1280] [--rounds 7] [--iters 5] [--out FILE]
+    timeout 300 python tools/bench_train_dwconv.py step [--step-model 570m] [--step-batch 16] [--step-grid 32] [--step-rounds 5] [--out FILE]
+    timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d DIR_OFF -- python tools/bench_train_dwconv.py trace-step --setting torch --steps 3
+    timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d DIR_ON  -- python tools/bench_train_dwconv.py trace-step --setting hip --steps 3
+    timeout 300 rocprofv3 --kernel-trace --stats --output-format csv -d DIR_OP  -- python tools/bench_train_dwconv.py op --rounds 2 --iters 3
+    python tools/bench_train_dwconv.py diff DIR_OFF DIR_ON --steps 4 [--out FILE]        (no device needed: reads the two traces; steps = warm-up + --steps)
+    python tools/bench_train_dwconv.py kernels DIR_OP [--match REGEX] [--out FILE]       (no device needed: dispatches grouped by kernel name and grid)
+
+op: per shape [B, H, W, C], without and with a skip: one warm-up round of each path, then `rounds` rounds in which the two paths take turns; a round is `iters`
+back-to-back forward + backward passes between two device synchronisations, timed on the host clock; reported is the median (min, max) per pass.  Memory:
+torch.cuda.max_memory_allocated over one pass minus what was allocated before it (x, skip, weight, bias and the incoming gradient).  The inputs are NHWC-dense, as the
+trunk is under the switch.  The script also checks that the two paths agree at the shapes it times.
+step: one full training step (`forward_loss` + backward of the weighted mean loss, parameter gradients freed in between) with set_training_activation("hip") under
+either `set_training_depthwise` setting, the settings taking turns: median time per step, peak memory above what is allocated before the step (weights and inputs;
+no parameter gradients exist then under either setting, so the peak includes the step's own), what autograd holds between the forward and the backward, and how
+many of one step's op calls had to copy an input that was not NHWC-dense.  "torch" is the parent commit's code op for op.
+diff: kernel time per step by kernel name in the two traces; the rows that differ are the front of the ResBlocks (and whatever else the layout change moved).
+Nothing is timed without a HIP device."""
+import argparse
+import csv
+import glob
+import os
+import re
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+
+
+def _rows(directory, suffix):
+    files = sorted(glob.glob(os.path.join(directory, "**", "*" + suffix), recursive=True))
+    if not files:
+        sys.exit("no *%s under %s" % (suffix, directory))
+    for f in files:
+        with open(f, newline="") as fh:
+            for r in csv.DictReader(fh):
+                yield r
+
+
+def _short(name, n=96):
+    name = re.sub(r"\s+", " ", name)
+    return name if len(name) <= n else name[:n - 3] + "..."
+
+
+def by_name(directory):
+    """kernel name -> (calls, total us) from a rocprofv3 --kernel-trace csv"""
+    out = {}
+    for r in _rows(directory, "kernel_trace.csv"):
+        c, t = out.get(r["Kernel_Name"], (0, 0.0))
+        out[r["Kernel_Name"]] = (c + 1, t + (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("part", choices=["op", "step", "trace-step", "diff", "kernels"])
+    ap.add_argument("dirs", nargs="*")
+    ap.add_argument("--shapes", nargs="+", default=["16x16x16x640", "16x8x8x1280", "16x4x4x1280"])
+    ap.add_argument("--rounds", type=int, default=7)
+    ap.add_argument("--iters", type=int, default=5)
+    ap.add_argument("--step-model", default="570m")
+    ap.add_argument("--step-batch", type=int, default=16)
+    ap.add_argument("--step-grid", type=int, default=32)
+    ap.add_argument("--step-rounds", type=int, default=5)
+    ap.add_argument("--setting", default="torch", choices=["torch", "hip"])
+    ap.add_argument("--steps", type=int, default=3)
+    ap.add_argument("--match", default="dwconv")
+    ap.add_argument("--out", default=None)
+    a = ap.parse_args()
+    lines = []
+
+    def say(s):
+        print(s, flush=True)
+        lines.append(s)
+
+    def finish():
+        if a.out:
+            with open(a.out, "w") as f:
+                f.write("\n".join(lines) + "\n")
+
+    if a.part == "diff":
+        off, on = by_name(a.dirs[0]), by_name(a.dirs[1])
+        n = float(a.steps)
+        tot_off, tot_on = sum(t for _, t in off.values()) / n, sum(t for _, t in on.values()) / n
+        say("kernel time per training step by kernel name, depthwise switch off -> on (%d steps per trace; us per step; calls per step)" % a.steps)
+        say("%10s %8s %10s %8s %10s  %s" % ("off us", "calls", "on us", "calls", "on - off", "kernel"))
+        rows = []
+        for k in set(off) | set(on):
+            c0, t0 = off.get(k, (0, 0.0))
+            c1, t1 = on.get(k, (0, 0.0))
+            rows.append((t1 / n - t0 / n, t0 / n, c0 / n, t1 / n, c1 / n, k))
+        rows.sort()
+        gone = sum(-r[0] for r in rows if r[0] < 0)
+        came = sum(r[0] for r in rows if r[0] > 0)
+        for d, t0, c0, t1, c1, k in rows:
+            if abs(d) >= 0.002 * tot_off:
+                say("%10.1f %8.1f %10.1f %8.1f %+10.1f  %s" % (t0, c0, t1, c1, d, _short(k)))
+        say("sum of all kernels: off %.1f us, on %.1f us per step; rows that shrank: -%.1f us (%.1f %% of the off step's kernel time), rows that grew: +%.1f us"
+            % (tot_off, tot_on, gone, 100.0 * gone / tot_off, came))
+        return finish()
+
+    if a.part == "kernels":
+        groups = {}
+        for r in _rows(a.dirs[0], "kernel_trace.csv"):
+            if not re.search(a.match, r["Kernel_Name"]):
+                continue
+            wg = int(r["Workgroup_Size_X"]) * int(r["Workgroup_Size_Y"]) * int(r["Workgroup_Size_Z"])
+            key = (r["Kernel_Name"], "%dx%dx%d/%d" % (int(r["Grid_Size_X"]), int(r["Grid_Size_Y"]), int(r["Grid_Size_Z"]), wg))
+            groups.setdefault(key, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+        say("%-18s %6s %9s %9s %9s  %s" % ("grid (threads)/wg", "calls", "avg us", "min us", "max us", "kernel"))
+        for (k, g), v in sorted(groups.items(), key=lambda kv: (kv[0][0], kv[0][1])):
+            say("%-18s %6d %9.1f %9.1f %9.1f  %s" % (g, len(v), sum(v) / len(v), min(v), max(v), _short(k)))
+        return finish()
+
+    import torch
+    import torch.nn.functional as F
+
+    import paella_amd
+    from paella_amd import synth, training
+    if not torch.cuda.is_available():
+        sys.exit("bench_train_dwconv.py needs a HIP device: nothing is timed without one")
+    dev = torch.device("cuda", 0)
+
+    def median(v):
+        v = sorted(v)
+        return v[len(v) // 2], v[0], v[-1]
+
+    def alternate(paths, rounds, iters):
+        times = {n: [] for n in paths}
+        for _ in range(rounds):
+            for name, fn in paths.items():
+                torch.cuda.synchronize(dev)
+                t0 = time.perf_counter()
+                for _ in range(iters):
+                    fn()
+                torch.cuda.synchronize(dev)
+                times[name].append((time.perf_counter() - t0) * 1e3 / iters)
+        return times
+
+    def peak_of(fn):
+        torch.cuda.empty_cache()
+        torch.cuda.synchronize(dev)
+        base = torch.cuda.memory_allocated(dev)
+        torch.cuda.reset_peak_memory_stats(dev)
+        out = fn()
+        torch.cuda.synchronize(dev)
+        peak = torch.cuda.max_memory_allocated(dev) - base
+        del out
+        return peak
+
+    if a.part == "op":
+        say("training ResBlock front, forward + backward: %d rounds of %d passes per path after one warm-up round, paths alternating" % (a.rounds, a.iters))
+        say("%16s %5s %6s %12s %12s %12s %18s %16s" % ("[B, H, W, C]", "skip", "path", "median ms", "min ms", "max ms", "peak MiB > inputs", "one tensor MiB"))
+        for spec in a.shapes:
+            B, H, W, C = (int(v) for v in spec.split("x"))
+            for skip in (False, True):
+                J = 2 if skip else 1
+                gen = torch.Generator().manual_seed(B * H * W + C + J)
+                nchw = lambda t: t.to(dev).permute(0, 3, 1, 2).requires_grad_(True)    # logical NCHW over NHWC memory, as the trunk is under the switch
+                x = nchw(torch.randn(B, H, W, C, generator=gen))
+                s = nchw(torch.randn(B, H, W, C, generator=gen)) if skip else None
+                w = (torch.randn(C, J, 3, 3, generator=gen) * 0.3).to(dev).requires_grad_(True)
+                bias = (torch.randn(C, generator=gen) * 0.5).to(dev).requires_grad_(True)
+                dy = torch.randn(B, H, W, C, generator=gen).to(dev)
+                leaves = (x, s, w, bias) if skip else (x, w, bias)
+
+                def torch_pass():
+                    xc = torch.cat([x, s], dim=1) if skip else x
+                    y = F.layer_norm(F.conv2d(xc, w, bias, padding=1, groups=C).permute(0, 2, 3, 1), (C,), None, None, 1e-6)
+                    return (y.detach(),) + torch.autograd.grad(y, leaves, dy)
+
+                def fused_pass():
+                    y = training.dwconv_layernorm(x, w, bias, s)
+                    return (y.detach(),) + torch.autograd.grad(y, leaves, dy)
+
+                paths = {"torch": torch_pass, "fused": fused_pass}
+                res = {name: fn() for name, fn in paths.items()}   # warm-up, and agreement
+                torch.cuda.synchronize(dev)
+                for i, what in enumerate(("y", "dx", "dskip", "dw", "dbias") if skip else ("y", "dx", "dw", "dbias")):
+                    d = float((res["torch"][i].double() - res["fused"][i].double()).abs().max())
+                    m = float(res["torch"][i].double().abs().max())
+                    say("#   %s%s: max |torch - fused| of %s: %.3e (max |torch| %.3e)" % (spec, " skip" if skip else "", what, d, m))
+                    assert d <= 1e-4 * max(m, 1.0), "the two paths disagree"
+                del res
+                peak = {name: peak_of(fn) for name, fn in paths.items()}
+                times = alternate(paths, a.rounds, a.iters)
+                one = B * H * W * C * 4 / 2 ** 20
+                for name in paths:
+                    say("%16s %5s %6s %12.3f %12.3f %12.3f %18.1f %16.1f" % ((spec, "yes" if skip else "no", name) + median(times[name]) + (peak[name] / 2 ** 20, one)))
+                del x, s, w, bias, dy
+                torch.cuda.empty_cache()
+        return finish()
+
+    import bench
+    cfg = bench.MODELS[a.step_model]
+    m = paella_amd.Paella(**cfg)
+    synth.randomize_(m, seed=0)
+    m = m.to(dev)
+    m.train()
+    m.set_training_activation("hip")
+    Bs, g = a.step_batch, a.step_grid
+    gen = torch.Generator().manual_seed(7)
+    latents = torch.randint(0, cfg["num_labels"], (Bs, g, g), generator=gen).to(dev)
+    t = torch.rand(Bs, generator=gen).to(dev)
+    mask = (torch.rand(Bs, g, g, generator=gen) < t.cpu()[:, None, None]).long().to(dev)
+    random_x = torch.randint(0, cfg["num_labels"], (Bs, g, g), generator=gen).to(dev)
+    cond = synth.synth_conditioning(Bs, 4, cfg["byt5_embd"], cfg["clip_embd"], seed=2, device=dev)
+    noised = latents * (1 - mask) + random_x * mask
+    lw = m.get_loss_weight(t, mask)
+
+    held = {}
+
+    def step_with(mode):
+        def step():
+            m.set_training_depthwise(mode)
+            m.zero_grad(set_to_none=True)
+            base = torch.cuda.memory_allocated(dev)
+            loss, _ = m.forward_loss(noised, t, latents, **cond)
+            loss = ((loss * lw).sum(dim=[1, 2]) / lw.sum(dim=[1, 2])).mean()
+            held[mode] = torch.cuda.memory_allocated(dev) - base   # what autograd holds between the forward and the backward
+            loss.backward()
+            return loss.detach()
+        return step
+
+    what = "model %s (%.1fM parameters), %d x %dx%d tokens, dropout %s, set_training_activation(\"hip\")" % (
+        a.step_model, sum(p.numel() for p in m.parameters()) / 1e6, Bs, g, g, m.dropout)
+    if a.part == "trace-step":
+        fn = step_with(a.setting)
+        fn()   # warm-up (traced as well: divide the totals by 1 + --steps)
+        for _ in range(a.steps):
+            fn()
+        torch.cuda.synchronize(dev)
+        say("traced %d + 1 training steps with set_training_depthwise(\"%s\"): %s" % (a.steps, a.setting, what))
+        return finish()
+
+    paths = {"torch": step_with("torch"), "hip": step_with("hip")}
+    say("one training step (forward_loss + backward), %s; %d rounds of 1 step per set_training_depthwise setting after one warm-up, settings alternating" % (what, a.step_rounds))
+    losses, counts = {}, {}
+    for name, fn in paths.items():   # warm-up
+        c0 = dict(training.DW_COUNTERS)
+        losses[name] = float(fn())
+        counts[name] = (training.DW_COUNTERS["calls"] - c0["calls"], training.DW_COUNTERS["copied"] - c0["copied"])
+    peak = {}
+    for name, fn in paths.items():
+        m.zero_grad(set_to_none=True)   # the base of EITHER setting holds no parameter gradients: the peak includes the step's own
+        peak[name] = peak_of(fn)
+    m.zero_grad(set_to_none=True)
+    times = alternate(paths, a.step_rounds, 1)
+    say("peak = max allocated during the step above weights and inputs, the step's parameter gradients (%.1f MiB once all exist) included under either setting; "
+        "held = allocated between the forward and the backward above weights and inputs (what autograd keeps)" % (sum(p.numel() for p in m.parameters()) * 4 / 2 ** 20))
+    say("%10s %12s %12s %12s %10s %10s %12s %10s %14s" % ("setting", "median ms", "min ms", "max ms", "peak MiB", "held MiB", "loss", "op calls", "inputs copied"))
+    for name in paths:
+        say("%10s %12.2f %12.2f %12.2f %10.1f %10.1f %12.5f %10d %14d" % ((name,) + median(times[name]) + (peak[name] / 2 ** 20, held[name] / 2 ** 20, losses[name]) + counts[name]))
+    finish()
+
+
+if __name__ == "__main__":
+    main()
