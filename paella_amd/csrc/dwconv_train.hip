@@ -14,18 +14,17 @@
 // (4) the partials in ASCENDING strip order.  A tensor of one strip writes (3) straight into dw / dbias.
 // No float atomics, no tickets: every combine is a launch.  The strips depend on (B, H, W, C, J) only (make_plan), never on the device; y, da, dx and dskip of a
 // position depend on its own sample only, so a sample's bits depend neither on its index nor on the batch around it.
-#include "common.h"
-#include "../../include/paella_hip.h"
+#include "train_common.h"
 
 namespace {
+
+using namespace train;
 
 constexpr int kThreads = 256;
 constexpr int kSumThreads = 64;   // (3): channels per workgroup (x 9 taps)
 constexpr int kMaxStrips = 1024;  // bounds the finalize loop of a long tensor
 constexpr int kRun = 8;           // (2): positions along a row per thread
 constexpr int kMaxC = 8192, kMaxCSkip = 4096;
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 bool shape_ok(int B, int H, int W, int C, int has_skip) {
     if (B < 1 || H < 1 || W < 1 || (int64_t)B * H * W > 0x7fffffffll) return false;
@@ -46,11 +45,9 @@ Plan make_plan(int B, int H, int W, int C, int has_skip) {
     Plan p = {};
     p.J = has_skip ? 2 : 1;
     p.N = (int64_t)B * H * W;
-    int64_t rows = 8 * (9 * p.J + 1);
-    const int64_t floor_rows = (p.N + kMaxStrips - 1) / kMaxStrips;
-    if (rows < floor_rows) rows = floor_rows;
-    p.rows_per_strip = (int)rows;
-    p.strips = (int)((p.N + rows - 1) / rows);
+    const Strips s = plan_strips(p.N, 8 * (9 * p.J + 1), kMaxStrips);
+    p.rows_per_strip = s.rows;
+    p.strips = s.count;
     const size_t da = align256((size_t)p.N * C * sizeof(float));
     const size_t pw = p.strips > 1 ? align256((size_t)p.strips * C * 9 * p.J * sizeof(float)) : 0;
     const size_t pb = p.strips > 1 ? align256((size_t)p.strips * C * sizeof(float)) : 0;
@@ -305,8 +302,6 @@ __global__ __launch_bounds__(kThreads) void dwconv_ln_train_dw_finalize_kernel(c
     out[i] = (float)s;
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 int check_shape(const char* who, int B, int H, int W, int C, int has_skip) {
     if (shape_ok(B, H, W, C, has_skip)) return PAELLA_OK;
     paella_set_error("%s: unsupported shape B=%d H=%d W=%d C=%d%s (B, H, W >= 1 with B H W <= 2^31 - 1; C a multiple of 4 in 4...8192, with a skip a multiple of 8 in 8...4096)",
@@ -315,16 +310,7 @@ int check_shape(const char* who, int B, int H, int W, int C, int has_skip) {
 }
 
 int check_ws(const char* who, const void* ws, size_t ws_bytes, size_t need) {
-    if (!ws || ws_bytes < need) {
-        paella_set_error("%s: workspace of %zu bytes, this call needs %zu (paella_dwconv_ln_train_workspace_bytes covers both directions)", who, ws ? ws_bytes : (size_t)0,
-                         need);
-        return PAELLA_ERR_WORKSPACE;
-    }
-    if (!aligned16(ws)) {
-        paella_set_error("%s: the workspace must be 16-byte aligned", who);
-        return PAELLA_ERR_ARG;
-    }
-    return PAELLA_OK;
+    return check_workspace(who, ws, ws_bytes, need, "this call needs", " (paella_dwconv_ln_train_workspace_bytes covers both directions)");
 }
 
 }  // namespace
@@ -344,14 +330,9 @@ extern "C" int paella_dwconv_ln_train_forward(const float* x, const float* skip,
         paella_set_error("%s: eps must be positive and finite (got %g)", who, (double)eps);
         return PAELLA_ERR_ARG;
     }
-    if (!x || !w || !bias || !y || !rstd) {
-        paella_set_error("%s: x, w, bias, y and rstd are required", who);
-        return PAELLA_ERR_ARG;
-    }
-    if (!aligned16(x) || !aligned16(skip) || !aligned16(w) || !aligned16(bias) || !aligned16(y) || !aligned16(rstd)) {
-        paella_set_error("%s: every tensor must be 16-byte aligned", who);
-        return PAELLA_ERR_ARG;
-    }
+    rc = check_required(who, x && w && bias && y && rstd, "x, w, bias, y and rstd");
+    if (rc == PAELLA_OK) rc = check_tensors_aligned16(who, x, skip, w, bias, y, rstd);
+    if (rc != PAELLA_OK) return rc;
     const Plan pl = make_plan(B, H, W, C, skip != nullptr);
     rc = check_ws(who, ws, ws_bytes, pl.fwd_bytes);
     if (rc != PAELLA_OK) return rc;
@@ -380,20 +361,14 @@ extern "C" int paella_dwconv_ln_train_backward(const float* x, const float* skip
                                                int C, float* dx, float* dskip, float* dw, float* dbias, void* ws, size_t ws_bytes, void* stream) {
     const char* who = "dwconv_ln_train_backward";
     int rc = check_shape(who, B, H, W, C, skip != nullptr);
+    if (rc == PAELLA_OK) rc = check_required(who, x && w && y && rstd && dy, "x, w, y, rstd and dy");
     if (rc != PAELLA_OK) return rc;
-    if (!x || !w || !y || !rstd || !dy) {
-        paella_set_error("%s: x, w, y, rstd and dy are required", who);
-        return PAELLA_ERR_ARG;
-    }
     if (dskip && !skip) {
         paella_set_error("%s: dskip without a skip", who);
         return PAELLA_ERR_ARG;
     }
-    if (!aligned16(x) || !aligned16(skip) || !aligned16(w) || !aligned16(y) || !aligned16(rstd) || !aligned16(dy) || !aligned16(dx) || !aligned16(dskip) || !aligned16(dw) ||
-        !aligned16(dbias)) {
-        paella_set_error("%s: every tensor must be 16-byte aligned", who);
-        return PAELLA_ERR_ARG;
-    }
+    rc = check_tensors_aligned16(who, x, skip, w, y, rstd, dy, dx, dskip, dw, dbias);
+    if (rc != PAELLA_OK) return rc;
     const Plan pl = make_plan(B, H, W, C, skip != nullptr);
     rc = check_ws(who, ws, ws_bytes, pl.bwd_bytes);
     if (rc != PAELLA_OK) return rc;

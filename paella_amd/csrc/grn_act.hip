@@ -20,10 +20,12 @@
 // of the device or of the batch, so two runs and two devices give the same bits, and the arithmetic of a sample depends neither on its index b nor on B.
 #include "gemm_device.h"
 #include "philox.h"
-#include "../../include/paella_hip.h"
+#include "train_common.h"
 #include <math.h>
 
 namespace {
+
+using namespace train;
 
 constexpr int kThreads = 256;
 constexpr int kWaves = 4;
@@ -43,8 +45,6 @@ struct Plan {
     size_t part1_off, ns_off, d_off, k_off, m_off, bytes;  // part0 at 0
 };
 
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 bool shape_ok(int B, int P, int C) { return B >= 1 && B <= kMaxB && P >= 1 && P <= kMaxP && C >= 4 && C <= kMaxC && (C & 3) == 0; }
 
 // Everything here depends on the shape only, and the strips on (P, C) only: the same sample always gets the same strips, hence the same summation order and the
@@ -54,12 +54,10 @@ Plan make_plan(int B, int P, int C) {
     p.C4 = C >> 2;
     p.nblk_c = (p.C4 + kVecPerBlock - 1) / kVecPerBlock;
     const int want = (kTargetBlocks + p.nblk_c - 1) / p.nblk_c;  // strips that would reach the target
-    int64_t rows = (P + want - 1) / want;
-    if (rows < kMinStripRows) rows = kMinStripRows;
-    const int64_t floor_rows = (P + kMaxStrips - 1) / kMaxStrips;
-    if (rows < floor_rows) rows = floor_rows;
-    p.rows_per_strip = (int)rows;
-    p.strips = (int)((P + rows - 1) / rows);
+    const int target_rows = (P + want - 1) / want;
+    const Strips s = plan_strips(P, target_rows > kMinStripRows ? target_rows : kMinStripRows, kMaxStrips);
+    p.rows_per_strip = s.rows;
+    p.strips = s.count;
     const size_t part = align256((size_t)B * p.strips * C * sizeof(float));
     const size_t tab = align256((size_t)B * C * sizeof(float));
     p.part1_off = part;
@@ -302,22 +300,12 @@ __global__ __launch_bounds__(kThreads) void grn_act_apply_kernel(const float* __
     }
 }
 
-bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
-
 int check_common(const char* who, float p_drop, const Plan& pl, const void* ws, size_t ws_bytes) {
     if (!(p_drop >= 0.f && p_drop < 1.f)) {  // false for NaN as well
         paella_set_error("%s: p_drop must lie in [0, 1) (got %g)", who, (double)p_drop);
         return PAELLA_ERR_ARG;
     }
-    if (!ws || ws_bytes < pl.bytes) {
-        paella_set_error("%s: workspace of %zu bytes, paella_grn_act_workspace_bytes asks for %zu", who, ws ? ws_bytes : (size_t)0, pl.bytes);
-        return PAELLA_ERR_WORKSPACE;
-    }
-    if (!aligned16(ws)) {
-        paella_set_error("%s: the workspace must be 16-byte aligned", who);
-        return PAELLA_ERR_ARG;
-    }
-    return PAELLA_OK;
+    return check_workspace(who, ws, ws_bytes, pl.bytes, "paella_grn_act_workspace_bytes asks for");
 }
 
 int check_shape(const char* who, int B, int P, int C) {
@@ -337,15 +325,9 @@ extern "C" int paella_grn_act_forward(const float* u, const float* gamma, const 
                                       size_t ws_bytes, void* stream) {
     const char* who = "grn_act_forward";
     int rc = check_shape(who, B, P, C);
+    if (rc == PAELLA_OK) rc = check_required(who, u && gamma && beta && z && gx, "u, gamma, beta, z and gx");
+    if (rc == PAELLA_OK) rc = check_tensors_aligned16(who, u, gamma, beta, z, gx);
     if (rc != PAELLA_OK) return rc;
-    if (!u || !gamma || !beta || !z || !gx) {
-        paella_set_error("%s: u, gamma, beta, z and gx are required", who);
-        return PAELLA_ERR_ARG;
-    }
-    if (!aligned16(u) || !aligned16(gamma) || !aligned16(beta) || !aligned16(z) || !aligned16(gx)) {
-        paella_set_error("%s: every tensor must be 16-byte aligned", who);
-        return PAELLA_ERR_ARG;
-    }
     const Plan pl = make_plan(B, P, C);
     rc = check_common(who, p_drop, pl, ws, ws_bytes);
     if (rc != PAELLA_OK) return rc;
@@ -374,15 +356,9 @@ extern "C" int paella_grn_act_backward(const float* u, const float* gamma, const
                                        float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream) {
     const char* who = "grn_act_backward";
     int rc = check_shape(who, B, P, C);
+    if (rc == PAELLA_OK) rc = check_required(who, u && gamma && gx && dz, "u, gamma, gx and dz");
+    if (rc == PAELLA_OK) rc = check_tensors_aligned16(who, u, gamma, gx, dz, du, dgamma, dbeta);
     if (rc != PAELLA_OK) return rc;
-    if (!u || !gamma || !gx || !dz) {
-        paella_set_error("%s: u, gamma, gx and dz are required", who);
-        return PAELLA_ERR_ARG;
-    }
-    if (!aligned16(u) || !aligned16(gamma) || !aligned16(gx) || !aligned16(dz) || !aligned16(du) || !aligned16(dgamma) || !aligned16(dbeta)) {
-        paella_set_error("%s: every tensor must be 16-byte aligned", who);
-        return PAELLA_ERR_ARG;
-    }
     const Plan pl = make_plan(B, P, C);
     rc = check_common(who, p_drop, pl, ws, ws_bytes);
     if (rc != PAELLA_OK) return rc;

@@ -11,11 +11,12 @@
 // Nothing proportional to rows x N is ever stored; logits, probabilities and d live in registers and LDS.  No float atomics, no tickets: every combine runs in
 // an order fixed by the shape alone (the row split of dw is a function of (rows, N, K), never of the device), so two runs give the same bits.
 // A target outside [0, N) marks an ignored row: loss 0, d = 0, and neither w nor a partial is ever indexed with it.
-#include "common.h"
-#include "../../include/paella_hip.h"
+#include "train_common.h"
 #include <math.h>
 
 namespace {
+
+using namespace train;
 
 constexpr int kTile = 64;        // rows and labels of a logit tile (4 waves, each a 32 x 32 quarter)
 constexpr int kThreads = 256;
@@ -36,8 +37,6 @@ struct Plan {
     size_t slab_bytes, bwd_bytes;         // ... and `split` slabs of [N, K] (split > 1 only)
     size_t bytes;
 };
-
-inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 bool shape_ok(int64_t rows, int N, int K) {
     return rows >= 1 && rows <= kMaxRows && K >= 16 && K <= 256 && (K & 15) == 0 && N >= 16 && N <= 65536 && (N & 15) == 0;
@@ -481,20 +480,11 @@ int check_common(const char* who, const void* h, const void* w, const void* targ
         paella_set_error("%s: label_smoothing must lie in [0, 1) (got %g)", who, (double)eps);
         return PAELLA_ERR_ARG;
     }
-    if (!h || !w || !target) {
-        paella_set_error("%s: h, w and target are required", who);
-        return PAELLA_ERR_ARG;
-    }
-    return PAELLA_OK;
+    return check_required(who, h && w && target, "h, w and target");
 }
 
-int check_ws(const char* who, const Plan& p, size_t need, const void* ws, size_t ws_bytes) {
-    if (need == 0) return PAELLA_OK;
-    if (!ws || ws_bytes < p.bytes) {
-        paella_set_error("%s: workspace of %zu bytes, paella_head_loss_workspace_bytes asks for %zu", who, ws ? ws_bytes : (size_t)0, p.bytes);
-        return PAELLA_ERR_WORKSPACE;
-    }
-    return PAELLA_OK;
+int check_ws(const char* who, const Plan& p, const void* ws, size_t ws_bytes) {
+    return check_workspace_size(who, ws, ws_bytes, p.bytes, "paella_head_loss_workspace_bytes asks for");
 }
 
 template <bool DW>
@@ -529,15 +519,13 @@ extern "C" size_t paella_head_loss_workspace_bytes(int64_t rows, int N, int K) {
 
 extern "C" int paella_head_loss_forward(const float* h, const float* w, const int64_t* target, int64_t rows, int N, int K, float label_smoothing, float* loss_out,
                                         float* lse_out, int* argmax_out, void* ws, size_t ws_bytes, void* stream) {
-    const int rc = check_common("head_loss_forward", h, w, target, rows, N, K, label_smoothing);
+    const char* who = "head_loss_forward";
+    int rc = check_common(who, h, w, target, rows, N, K, label_smoothing);
+    if (rc == PAELLA_OK) rc = check_required(who, loss_out && lse_out, "loss_out and lse_out");
     if (rc != PAELLA_OK) return rc;
-    if (!loss_out || !lse_out) {
-        paella_set_error("head_loss_forward: loss_out and lse_out are required");
-        return PAELLA_ERR_ARG;
-    }
     const Plan p = make_plan(rows, N, K);
-    const int rw = check_ws("head_loss_forward", p, p.bytes, ws, ws_bytes);
-    if (rw != PAELLA_OK) return rw;
+    rc = check_ws(who, p, ws, ws_bytes);
+    if (rc != PAELLA_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     float* tgt_ws = (float*)((char*)ws + p.tgt_off);
     float* part = (float*)((char*)ws + p.part_off);
@@ -554,15 +542,13 @@ extern "C" int paella_head_loss_forward(const float* h, const float* w, const in
 
 extern "C" int paella_head_loss_backward(const float* h, const float* w, const int64_t* target, const float* lse, const float* grad_loss, int64_t rows, int N, int K,
                                          float label_smoothing, float* dh_out, float* dw_out, void* ws, size_t ws_bytes, void* stream) {
-    const int rc = check_common("head_loss_backward", h, w, target, rows, N, K, label_smoothing);
+    const char* who = "head_loss_backward";
+    int rc = check_common(who, h, w, target, rows, N, K, label_smoothing);
+    if (rc == PAELLA_OK) rc = check_required(who, lse && grad_loss, "lse and grad_loss");
     if (rc != PAELLA_OK) return rc;
-    if (!lse || !grad_loss) {
-        paella_set_error("head_loss_backward: lse and grad_loss are required");
-        return PAELLA_ERR_ARG;
-    }
     const Plan p = make_plan(rows, N, K);
-    const int rw = check_ws("head_loss_backward", p, p.bytes, ws, ws_bytes);
-    if (rw != PAELLA_OK) return rw;
+    rc = check_ws(who, p, ws, ws_bytes);
+    if (rc != PAELLA_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     if (!dh_out && !dw_out) return PAELLA_OK;
     float* corr = (float*)((char*)ws + p.corr_off);

@@ -1,0 +1,272 @@
+"""The training ops: stretches of the train-mode network (paella_amd/training.py) that run as ONE HIP op in both directions, each a `torch.autograd.Function`
+over a pair of C entry points plus the public function that validates its arguments and hands dense, aligned tensors over.  HIP only: there is no torch fallback.
+
+Every op is written against the same scaffold, the helpers right below (the host side of the same scaffold is paella_amd/csrc/train_common.h):
+    _call          one checked library call under the tensors' device, with a fresh workspace of plain bytes -- the ops keep no state in it and initialise nothing
+    _grad_outputs  the backward's outputs from `needs_input_grad`: a NULL output is not computed, and when none is wanted the call is skipped
+    _refuse_*      the refusals every op makes -- not tensors, not the right dtype, not one cuda device, a scalar outside its range -- each op in its own order
+`paella_amd.training` imports the public names into its own namespace and the network calls them through those module globals."""
+import torch
+
+from . import _lib
+
+
+def _call(entry, dev, ws_bytes, *args):
+    """lib.<entry>(*args, workspace, its size, the current stream of dev): tensors go as their addresses (None as NULL), a non-zero return raises"""
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+        _lib.check(getattr(lib, entry)(*[a.data_ptr() if isinstance(a, torch.Tensor) else a for a in args], ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev)))
+
+
+def _grad_outputs(ctx, *like):
+    """one entry per input of the Function, in order: an empty tensor like like[i] (a shape: of that shape, otherwise like like[0]) where autograd wants that
+    gradient, else None; like[i] = None for an input that has no gradient.  -> (the list, whether anything is wanted at all)"""
+    outs = [None if t is None or not need else torch.empty_like(t) if isinstance(t, torch.Tensor) else like[0].new_empty(t) for t, need in zip(like, ctx.needs_input_grad)]
+    return outs, any(o is not None for o in outs)
+
+
+def _refuse_non_tensors(op, *tensors):
+    if not all(torch.is_tensor(t) for t in tensors):
+        raise ValueError("%s takes tensors" % op)
+
+
+def _got(tensors, field):
+    return ", ".join(str(None if t is None else getattr(t, field)) for t in tensors)
+
+
+def _refuse_dtypes(op, what, tensors, dtypes=None):
+    """tensors (None = an absent optional one) must have the given dtypes, fp32 unless said otherwise; `what` reads "fp32 u, gamma and beta" """
+    if any(t is not None and t.dtype != d for t, d in zip(tensors, dtypes or [torch.float32] * len(tensors))):
+        raise ValueError("%s takes %s (got %s)" % (op, what, _got(tensors, "dtype")))
+
+
+def _refuse_off_device(op, what, tensors):
+    """the first tensor must be on a cuda device and the others (None = absent) on the same one; `what` reads "u, gamma and beta" """
+    if not tensors[0].is_cuda or any(t is not None and t.device != tensors[0].device for t in tensors[1:]):
+        raise ValueError("%s runs on the HIP device only: %s must live on the same cuda device (got %s)" % (op, what, _got(tensors, "device")))
+
+
+def _refuse_out_of_range(name, shown, ok, rule):
+    if not ok:  # (a comparison chain is false for NaN)
+        raise ValueError("%s = %r: %s" % (name, shown, rule))
+
+
+def _aligned(t):
+    """the kernels move 16-byte vectors: a contiguous view that starts off that grain is copied"""
+    return t if t.data_ptr() % 16 == 0 else t.clone()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# Training loss head: out_mapper's convolution + label-smoothed cross-entropy as ONE HIP op, forward and backward (paella_amd/csrc/loss.hip,
+# include/paella_hip.h "Training loss head").  The [rows, num_labels] logits, their log-softmax and their gradient are never stored: the forward keeps
+# five numbers per row, the backward recomputes the logit tiles from h, the weight and the saved lse.
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+HEAD_MAX_K, HEAD_MAX_LABELS, HEAD_MAX_ROWS = 256, 65536, 1 << 24
+
+
+class _HeadCrossEntropy(torch.autograd.Function):
+    """(h [rows, K], weight [N, K], target [rows]) -> (loss fp32 [rows], argmax int32 [rows]); saves h, weight, target and lse [rows]."""
+
+    @staticmethod
+    def forward(ctx, h, weight, target, eps):
+        rows, K = h.shape
+        N = weight.size(0)
+        loss = h.new_empty(rows)
+        lse = h.new_empty(rows)
+        argmax = torch.empty(rows, dtype=torch.int32, device=h.device)
+        _call("paella_head_loss_forward", h.device, _lib.load().paella_head_loss_workspace_bytes(rows, N, K), h, weight, target, rows, N, K, eps, loss, lse, argmax)
+        ctx.save_for_backward(h, weight, target, lse)
+        ctx.eps = eps
+        ctx.mark_non_differentiable(argmax)
+        return loss, argmax
+
+    @staticmethod
+    def backward(ctx, grad_loss, _grad_argmax):
+        h, weight, target, lse = ctx.saved_tensors
+        rows, K = h.shape
+        N = weight.size(0)
+        g = grad_loss.to(torch.float32).contiguous()
+        (dh, dw, _, _), wanted = _grad_outputs(ctx, h, weight, None, None)
+        if wanted:
+            _call("paella_head_loss_backward", h.device, _lib.load().paella_head_loss_workspace_bytes(rows, N, K), h, weight, target, lse, g, rows, N, K, ctx.eps, dh, dw)
+        return dh, dw, None, None
+
+
+def head_cross_entropy(h, weight, target, label_smoothing=0.0):
+    """Classifier head + cross-entropy without a logits tensor: with l = h @ weight^T,
+        loss   = nn.CrossEntropyLoss(label_smoothing=label_smoothing, reduction='none')(l, target)     (fp32, the shape of `target`; differentiable in h and weight)
+        argmax = l.argmax(-1), the lowest label on ties                                                  (int32, not differentiable)
+    h fp32 [..., K]; weight fp32 [N, K] or [N, K, 1, 1] (out_mapper.1.weight); target int64 with the leading shape of h.  A target outside [0, N) marks an
+    ignored position (loss 0, no gradient), as ignore_index does.  K a multiple of 16 up to 256, N a multiple of 16 up to 65536, at most 2^24 positions.
+    HIP only and exact fp32 only: anything else raises ValueError -- there is no torch fallback."""
+    _refuse_non_tensors("head_cross_entropy", h, weight, target)
+    _refuse_off_device("head_cross_entropy", "h, weight and target", (h, weight, target))
+    _refuse_dtypes("head_cross_entropy", "fp32 h and weight and int64 target", (h, weight, target), (torch.float32, torch.float32, torch.int64))
+    if weight.dim() == 4 and weight.size(2) == 1 and weight.size(3) == 1:
+        weight = weight.reshape(weight.size(0), weight.size(1))
+    if weight.dim() != 2 or h.dim() < 1 or h.size(-1) != weight.size(1):
+        raise ValueError("weight must be [N, K] or [N, K, 1, 1] with K = h.size(-1) (got h %s, weight %s)" % (tuple(h.shape), tuple(weight.shape)))
+    N, K = weight.shape
+    lead = h.shape[:-1]
+    if tuple(target.shape) != tuple(lead):
+        raise ValueError("target must have the leading shape of h, %s (got %s)" % (tuple(lead), tuple(target.shape)))
+    rows = target.numel()
+    if K % 16 or not 16 <= K <= HEAD_MAX_K:
+        raise ValueError("K = %d: the fused head takes a multiple of 16 in 16...%d" % (K, HEAD_MAX_K))
+    if N % 16 or not 16 <= N <= HEAD_MAX_LABELS:
+        raise ValueError("N = %d labels: the fused head takes a multiple of 16 in 16...%d" % (N, HEAD_MAX_LABELS))
+    if not 1 <= rows <= HEAD_MAX_ROWS:
+        raise ValueError("%d positions: the fused head takes 1...%d" % (rows, HEAD_MAX_ROWS))
+    eps = float(label_smoothing)
+    _refuse_out_of_range("label_smoothing", label_smoothing, 0.0 <= eps < 1.0, "must lie in [0, 1)")
+    # rows must be contiguous; the NHWC view behind `_ln_nchw`'s result already is (no copy)
+    h2 = h.view(rows, K) if h.is_contiguous() else h.contiguous().view(rows, K)
+    loss, argmax = _HeadCrossEntropy.apply(h2, weight.contiguous(), target.contiguous().view(rows), eps)
+    return loss.view(lead), argmax.view(lead)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# Training MLP activation: GELU -> GlobalResponseNorm -> Dropout of `_channelwise` as ONE HIP op, forward and backward (paella_amd/csrc/grn_act.hip,
+# include/paella_hip.h "Training MLP activation").  Of the widest activation of the network, [B, H, W, 4c], autograd keeps the pre-activation only (plus
+# G [B, 4c]): the GELU output, h * nx, the dropout mask and the dropout input are recomputed, the mask from a (seed, element index) counter.
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+ACT_MAX_B, ACT_MAX_P, ACT_MAX_C = 65535, 1 << 20, 16384
+
+
+class _GeluGrnDropout(torch.autograd.Function):
+    """(u [B, P, C], gamma [C], beta [C]) -> z [B, P, C]; saves u, gamma and gx [B, C]."""
+
+    @staticmethod
+    def forward(ctx, u, gamma, beta, p, seed):
+        B, P, C = u.shape
+        z = torch.empty_like(u)
+        gx = u.new_empty(B, C)
+        _call("paella_grn_act_forward", u.device, _lib.load().paella_grn_act_workspace_bytes(B, P, C), u, gamma, beta, B, P, C, p, seed, z, gx)
+        ctx.save_for_backward(u, gamma, gx)
+        ctx.p, ctx.seed = p, seed
+        return z
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dz):
+        u, gamma, gx = ctx.saved_tensors
+        B, P, C = u.shape
+        dz = _aligned(dz.to(torch.float32).contiguous())
+        (du, dgamma, dbeta, _, _), wanted = _grad_outputs(ctx, u, gamma, gamma, None, None)
+        if wanted:
+            _call("paella_grn_act_backward", u.device, _lib.load().paella_grn_act_workspace_bytes(B, P, C), u, gamma, gx, dz, B, P, C, ctx.p, ctx.seed, du, dgamma, dbeta)
+        return du, dgamma, dbeta, None, None
+
+
+def gelu_grn_dropout(u, gamma, beta, p=0.0, seed=None):
+    """The middle of a ResBlock / FeedForwardBlock MLP in train mode as one op: with h = gelu(u),
+        z = dropout(gamma * (h * nx) + beta + h, p),   nx = Gx / (mean_c Gx + 1e-6),   Gx = ||h||_2 over the positions of a sample
+    (src/modules.py:30-40, 49-53).  u fp32 [B, ..., C] (the dimensions between the first and the last are the positions of a sample); gamma, beta fp32 with C
+    elements (the module's [1, 1, 1, C] parameters as they are).  Once differentiable in u, gamma and beta; autograd keeps u, gamma and Gx [B, C] only.  p in
+    [0, 1); p = 0 draws nothing.  The dropout mask is a function of (seed, element index): seed = None with p > 0 draws one 64-bit seed from torch's default CPU
+    generator, so torch.manual_seed reproduces a run.  C a multiple of 4 up to 16384, at most 2^20 positions per sample, B up to 65535.  HIP only and exact fp32
+    only: anything else raises ValueError -- there is no torch fallback."""
+    _refuse_non_tensors("gelu_grn_dropout", u, gamma, beta)
+    _refuse_dtypes("gelu_grn_dropout", "fp32 u, gamma and beta", (u, gamma, beta))
+    if u.dim() < 2:
+        raise ValueError("u must be [B, ..., C] (got %s)" % (tuple(u.shape),))
+    B, C = u.size(0), u.size(-1)
+    if gamma.numel() != C or beta.numel() != C:
+        raise ValueError("gamma and beta must have C = u.size(-1) = %d elements (got %s, %s)" % (C, tuple(gamma.shape), tuple(beta.shape)))
+    if C % 4 or not 4 <= C <= ACT_MAX_C:
+        raise ValueError("C = %d: the fused activation takes a multiple of 4 in 4...%d" % (C, ACT_MAX_C))
+    P = u.numel() // (B * C) if B else 0
+    if not 1 <= B <= ACT_MAX_B or not 1 <= P <= ACT_MAX_P:
+        raise ValueError("u %s: the fused activation takes 1...%d samples of 1...%d positions" % (tuple(u.shape), ACT_MAX_B, ACT_MAX_P))
+    p = float(p)
+    _refuse_out_of_range("p", p, 0.0 <= p < 1.0, "must lie in [0, 1)")
+    _refuse_off_device("gelu_grn_dropout", "u, gamma and beta", (u, gamma, beta))
+    if p == 0.0:
+        seed = 0
+    elif seed is None:
+        seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    z = _GeluGrnDropout.apply(_aligned(u.contiguous()).view(B, P, C), _aligned(gamma.contiguous().view(C)), _aligned(beta.contiguous().view(C)), p, seed)
+    return z.view(u.shape)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# Training ResBlock front: [cat with the skip ->] depthwise 3x3 -> LayerNorm2d -> NHWC as ONE HIP op, forward and backward (paella_amd/csrc/dwconv_train.hip,
+# include/paella_hip.h "Training ResBlock front").  x and skip are read in place (no concatenation), the weight is used and its gradient returned in the
+# parameter's layout, and besides the op's inputs and its output autograd keeps one float per position (rstd): the concatenated input, the convolution output and
+# the LayerNorm's contiguous copy of the torch chain never exist.
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+DW_MAX_C, DW_MAX_C_SKIP, DW_MAX_POSITIONS = 8192, 4096, 2 ** 31 - 1
+# diagnostic: how often `dwconv_layernorm` ran and how many of its x / skip arguments were not dense NHWC memory and had to be copied (tools/bench_train_dwconv.py)
+DW_COUNTERS = {"calls": 0, "copied": 0}
+
+
+class _DwconvLayerNorm(torch.autograd.Function):
+    """(x [B, H, W, C], skip [B, H, W, C] or None, weight [C, J, 3, 3], bias [C]) -> y [B, H, W, C]; saves x, skip, weight, y and rstd [B, H, W]."""
+
+    @staticmethod
+    def forward(ctx, x, skip, weight, bias, eps):
+        B, H, W, C = x.shape
+        y = torch.empty_like(x)
+        rstd = x.new_empty(B, H, W)
+        # the forward asks for the repacked weights only, which is what the sizing call returns for one position
+        _call("paella_dwconv_ln_train_forward", x.device, _lib.load().paella_dwconv_ln_train_workspace_bytes(1, 1, 1, C, int(skip is not None)), x, skip, weight, bias,
+              B, H, W, C, eps, y, rstd)
+        ctx.save_for_backward(x, skip, weight, y, rstd)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, skip, weight, y, rstd = ctx.saved_tensors
+        B, H, W, C = x.shape
+        dy = _aligned(dy.to(torch.float32).contiguous())
+        (dx, dskip, dw, dbias, _), wanted = _grad_outputs(ctx, x, skip, weight, (C,), None)
+        if wanted:
+            _call("paella_dwconv_ln_train_backward", x.device, _lib.load().paella_dwconv_ln_train_workspace_bytes(B, H, W, C, int(skip is not None)), x, skip, weight, y,
+                  rstd, dy, B, H, W, C, dx, dskip, dw, dbias)
+        return dx, dskip, dw, dbias, None
+
+
+def _nhwc(t):
+    """[B, C, H, W] of any strides -> its [B, H, W, C] view when the memory is already dense NHWC and 16-byte aligned, else one copy"""
+    v = t.permute(0, 2, 3, 1)
+    if v.is_contiguous() and v.data_ptr() % 16 == 0:
+        return v
+    DW_COUNTERS["copied"] += 1
+    return v.contiguous() if not v.is_contiguous() else v.clone()
+
+
+def dwconv_layernorm(x, weight, bias, skip=None, eps=1e-6):
+    """The front of a ResBlock in train mode as one op (src/modules.py:46-47, 55-58):
+        y = layer_norm(conv2d(cat([x, skip], 1) if skip is not None else x, weight, bias, padding=1, groups=C).permute(0, 2, 3, 1), (C,), eps=eps)
+    x and skip fp32 with logical shape [B, C, H, W] and any strides: memory that is already dense NHWC (`x.permute(0, 2, 3, 1).is_contiguous()`) is used in place,
+    anything else is copied once.  weight fp32 [C, 1, 3, 3], or [C, 2, 3, 3] with a skip, and bias fp32 [C]: the module's parameters as they are.  Returns y
+    [B, H, W, C], contiguous -- what `_channelwise` consumes.  Once differentiable in x, skip, weight and bias; the gradients of x and skip come back with logical
+    shape [B, C, H, W] over NHWC memory, the weight's in the parameter's layout.  Besides its inputs and y autograd keeps one float per position.  C a multiple of
+    4 up to 8192, with a skip a multiple of 8 up to 4096; at most 2^31 - 1 positions.  HIP only, exact fp32 only, 3 x 3 only: anything else raises ValueError --
+    there is no torch fallback."""
+    _refuse_non_tensors("dwconv_layernorm", x, weight, bias, *(() if skip is None else (skip,)))
+    _refuse_dtypes("dwconv_layernorm", "fp32 x, skip, weight and bias", (x, skip, weight, bias))
+    if x.dim() != 4:
+        raise ValueError("x must be [B, C, H, W] (got %s)" % (tuple(x.shape),))
+    B, C, H, W = x.shape
+    if skip is not None and tuple(skip.shape) != tuple(x.shape):
+        raise ValueError("skip must have the shape of x, %s (got %s)" % (tuple(x.shape), tuple(skip.shape)))
+    J = 1 if skip is None else 2
+    if weight.dim() != 4 or weight.size(2) != 3 or weight.size(3) != 3:
+        raise ValueError("weight %s: the fused ResBlock front takes a 3 x 3 depthwise kernel only" % (tuple(weight.shape),))
+    if tuple(weight.shape) != (C, J, 3, 3) or bias.numel() != C:
+        raise ValueError("weight must be [C, %d, 3, 3] %s a skip and bias [C] with C = x.size(1) = %d (got %s, %s)"
+                         % (J, "with" if J == 2 else "without", C, tuple(weight.shape), tuple(bias.shape)))
+    cmax, grain = (DW_MAX_C, 4) if skip is None else (DW_MAX_C_SKIP, 8)
+    if C % grain or not grain <= C <= cmax:
+        raise ValueError("C = %d: the fused ResBlock front takes a multiple of %d in %d...%d%s" % (C, grain, grain, cmax, "" if skip is None else " with a skip"))
+    if B < 1 or H < 1 or W < 1 or B * H * W > DW_MAX_POSITIONS:
+        raise ValueError("x %s: the fused ResBlock front takes 1...2^31 - 1 positions" % (tuple(x.shape),))
+    eps = float(eps)
+    _refuse_out_of_range("eps", eps, 0.0 < eps < 1e30, "must be positive and finite")
+    _refuse_off_device("dwconv_layernorm", "x, skip, weight and bias", (x, skip, weight, bias))
+    DW_COUNTERS["calls"] += 1
+    return _DwconvLayerNorm.apply(_nhwc(x), None if skip is None else _nhwc(skip), _aligned(weight.contiguous()), _aligned(bias.contiguous().view(C)), eps)

@@ -11,6 +11,7 @@ import paella_amd
 from oracle import golden_configs as G
 from paella_amd import training
 from tests import dwconv_ln_model as M
+from tests import train_op_checks as T
 
 ERR_ARG, ERR_WORKSPACE = -1, -3
 
@@ -194,16 +195,4 @@ def test_set_training_depthwise():
 
 @pytest.mark.parametrize("act", ["torch", "hip"])
 def test_the_switch_leaves_a_cpu_train_step_alone(act):
-    """the switch acts on a cuda device only: on the CPU a train-mode forward is the torch chain under either setting, bit for bit"""
-    m = paella_amd.Paella(**G.UNET_TINY)
-    from tests.helpers import weights_for
-    weights_for(m, sum(G.UNET_TINY["blocks"]))
-    latents, t, mask, random_x, c = G.train_step_inputs(G.UNET_TINY)
-    noised = latents * (1 - mask) + random_x * mask
-    m.train()
-    m.dropout = 0.0
-    m.set_training_activation(act)
-    a = m(noised, t, **c)
-    m.set_training_depthwise("hip")
-    b = m(noised, t, **c)
-    assert torch.equal(a, b)
+    T.assert_switch_leaves_a_cpu_train_step_alone(lambda m: m.set_training_depthwise("hip"), before=lambda m: m.set_training_activation(act))

@@ -7,17 +7,14 @@ fp32 result can avoid.  The measured pairs are kept in profiles/train_dwconv_par
 import functools
 import itertools
 
-import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
 from torch import nn
 
-import paella_amd
-from oracle import golden_configs as G
 from paella_amd import _lib, training
 from tests import dwconv_ln_model as M
-from tests.helpers import cond_for, to_dev, weights_for
+from tests import train_op_checks as T
 from tests.test_gpu_training import _train_step
 
 pytestmark = pytest.mark.gpu
@@ -26,7 +23,8 @@ DEV = "cuda"
 # more than 256 float4 slots per row; the real level-2 width
 SHAPES = [(1, 1, 1, 8), (2, 1, 5, 8), (2, 5, 1, 8), (2, 3, 2, 24), (3, 5, 13, 136), (1, 8, 8, 1032), (2, 4, 4, 1280)]
 CASES = [s + (k,) for s in SHAPES for k in (False, True)] + [(1, 1, 1, 4, False), (2, 3, 2, 20, False)]
-FACTOR = 4.0
+FACTOR = T.FACTOR
+_err, _ulp = T.err, T.ulp
 EPS = 1e-6
 OUTS = ("y", "dx", "dskip", "dw", "dbias")
 ids = lambda s: "x".join(map(str, s[:4])) + ("-skip" if s[4] else "")
@@ -91,14 +89,6 @@ def torch_chain(x, s, w, bias, dy):
     return (y.detach(),) + tuple(None if t is None else t.grad for t in leaves)
 
 
-def _err(a, ref):
-    return float((a.double() - ref).abs().max())
-
-
-def _ulp(ref):
-    return float(np.spacing(np.float32(float(ref.abs().max()))))
-
-
 def _check_accuracy(tag, out, ref, model):
     pairs = []
     for name, b, m in zip(OUTS, ref, model):
@@ -108,7 +98,7 @@ def _check_accuracy(tag, out, ref, model):
         pairs.append((name, _err(out[name], m), _err(b, m), _ulp(m)))
     print("train_dwconv parity %s: " % tag + "  ".join("%s fused %.3e torch %.3e ulp %.3e" % q for q in pairs))
     for name, e_fused, e_torch, ulp in pairs:
-        assert e_fused <= FACTOR * max(e_torch, ulp), "%s %s: fused error %.3e exceeds %gx max(torch fp32 chain %.3e, ulp %.3e)" % (tag, name, e_fused, FACTOR, e_torch, ulp)
+        assert T.within_yardstick(e_fused, e_torch, ulp), "%s %s: fused error %.3e exceeds %gx max(torch fp32 chain %.3e, ulp %.3e)" % (tag, name, e_fused, FACTOR, e_torch, ulp)
 
 
 @pytest.mark.parametrize("case", CASES, ids=ids)
@@ -257,20 +247,12 @@ def test_autograd_function_and_saved_state(built_lib, skip):
         training.dwconv_layernorm(torch.zeros(1, 6, 2, 2, device=DEV), torch.zeros(6, 1, 3, 3, device=DEV), torch.zeros(6, device=DEV))
 
 
-def _model_for(which, golden):
-    cfg = G.UNET_TINY if which == "tiny" else G.UNET_VARIANT
-    m = paella_amd.Paella(**cfg)
-    weights_for(m, sum(cfg["blocks"]), golden("unet_%s_forward" % which))
-    return cfg, m.to(DEV)
-
-
 @pytest.mark.parametrize("act", ["torch", "hip"])
 @pytest.mark.parametrize("which", ["tiny", "variant"])
 def test_train_step_with_hip_depthwise_reproduces_the_reference(golden, built_lib, which, act):
     """_train_step of tests/test_gpu_training.py under set_training_depthwise("hip"), alone and together with set_training_activation("hip"), against the
     reference's recorded step and under that test's tolerances; then the hand-over to the HIP engine, which never sees the switch"""
-    cfg, m = _model_for(which, golden)
-    g = golden("train_%s_step" % which)
+    cfg, m = T.model_for(which, golden, DEV)
     m.set_training_depthwise("hip").set_training_activation(act)
     calls = []
     real = training.dwconv_layernorm
@@ -287,37 +269,5 @@ def test_train_step_with_hip_depthwise_reproduces_the_reference(golden, built_li
     c_blocks = [b for lv in list(m.down_blocks) + list(m.up_blocks) for b in lv if b.kind == "C"]
     assert len(calls) == len(c_blocks), "the train-mode forward did not route every ResBlock through the HIP op"
     assert sum(calls) == sum(1 for b in c_blocks if b.depthwise.weight.size(1) == 2), "the up-path blocks did not hand their skip to the op"
-    np.testing.assert_allclose(float(loss), float(g["nodrop_loss"]), rtol=2e-5)
-    np.testing.assert_allclose(pred[:, ::4, ::2, ::2].cpu().numpy(), g["nodrop_pred_sub"], atol=5e-5, rtol=1e-4)
-    params = dict(m.named_parameters())
-    names = g["names"].tolist()
-    norms = np.array([float(params[k].grad.norm()) for k in names])
-    np.testing.assert_allclose(norms, g["nodrop_grad_norms"], rtol=5e-4, atol=1e-6)
-    for k in [k for k in g.files if k.startswith("nodrop_grad:")]:
-        ref = g[k]
-        np.testing.assert_allclose(params[k.split(":", 1)[1]].grad.cpu().numpy(), ref, rtol=5e-4, atol=5e-4 * max(float(np.abs(ref).max()), 1e-6), err_msg=k)
-    # forward_loss takes the same route
-    latents, t, mask, random_x, c = G.train_step_inputs(cfg)
-    latents, t, mask, random_x = latents.to(DEV), t.to(DEV), mask.to(DEV), random_x.to(DEV)
-    noised = latents * (1 - mask) + random_x * mask
-    lw = m.get_loss_weight(t, mask)
-    n0 = training.DW_COUNTERS["calls"]
-    fl, _ = m.forward_loss(noised, t, latents, **to_dev(c, DEV))
-    assert training.DW_COUNTERS["calls"] == n0 + len(c_blocks)
-    np.testing.assert_allclose(float(((fl.detach() * lw).sum(dim=[1, 2]) / lw.sum(dim=[1, 2])).mean()), float(g["nodrop_loss"]), rtol=2e-5)
-    # optimizer step, back to eval: the engine's logits do not depend on the switch
-    opt = torch.optim.AdamW(m.parameters(), lr=2e-3)
-    nn.utils.clip_grad_norm_(m.parameters(), 1.0)
-    opt.step()
-    m.eval()
-    gen = torch.Generator().manual_seed(17)
-    x = torch.randint(0, cfg["num_labels"], (2, 16, 16), generator=gen).to(DEV)
-    r = torch.tensor([0.8, 0.3]).to(DEV)
-    cc = to_dev(cond_for(cfg, 2, 3, 1, G.COND_SEED + 3), DEV)
-    with torch.no_grad():
-        n0 = training.DW_COUNTERS["calls"]
-        with_hip = m(x, r, **cc).clone()
-        m.set_training_depthwise("torch")
-        with_torch = m(x, r, **cc)
-        assert training.DW_COUNTERS["calls"] == n0   # eval mode never reaches the op
-    assert torch.isfinite(with_hip).all() and torch.equal(with_hip, with_torch)
+    T.assert_switched_step_and_handover(m, cfg, golden("train_%s_step" % which), pred, loss, lambda: m.set_training_depthwise("torch"),
+                                        op_calls=lambda: training.DW_COUNTERS["calls"], calls_per_forward=len(c_blocks))

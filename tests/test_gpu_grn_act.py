@@ -10,20 +10,18 @@ import numpy as np
 import pytest
 import torch
 import torch.nn.functional as F
-from torch import nn
 
-import paella_amd
-from oracle import golden_configs as G
 from paella_amd import _lib, training
 from tests import grn_act_model as M
-from tests.helpers import cond_for, to_dev, weights_for
+from tests import train_op_checks as T
 from tests.test_gpu_training import _train_step
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 # one row; strip tails; C off the 64- and 256-channel grain; more than one channel block; the real level-2 width
 SHAPES = [(1, 1, 4), (2, 7, 20), (3, 65, 132), (2, 256, 128), (1, 300, 1028), (4, 16, 5120)]
-FACTOR = 4.0
+FACTOR = T.FACTOR
+_err, _ulp = T.err, T.ulp
 SEED = (0xC0FFEE << 40) + 977   # high key word in use
 ids = lambda s: "x".join(map(str, s))
 
@@ -85,14 +83,6 @@ def torch_chain(u, gamma, beta, dz, keep, p):
     return z.detach().view(B, P, C), uu.grad.view(B, P, C), g4.grad.view(C), b4.grad.view(C)
 
 
-def _err(a, ref):
-    return float((a.double() - ref).abs().max())
-
-
-def _ulp(ref):
-    return float(np.spacing(np.float32(float(ref.abs().max()))))
-
-
 @pytest.mark.parametrize("p", [0.0, 0.1])
 @pytest.mark.parametrize("shape", SHAPES, ids=ids)
 def test_accuracy_against_the_fp64_model(built_lib, shape, p):
@@ -109,7 +99,7 @@ def test_accuracy_against_the_fp64_model(built_lib, shape, p):
     # G sums P squares of a GELU whose documented error is 5.5e-7 per value (gemm_device.h: gelu_erf): |dG| <= sqrt(P) 5.5e-7, plus the fp32 rounding of G itself
     torch.testing.assert_close(out["gx"].double(), gx64, rtol=2e-6, atol=5.5e-7 * shape[1] ** 0.5)
     for name, e_fused, e_torch, ulp in pairs:
-        assert e_fused <= FACTOR * max(e_torch, ulp), "%s p=%g %s: fused error %.3e exceeds %gx max(torch fp32 chain %.3e, ulp %.3e)" % (shape, p, name, e_fused, FACTOR, e_torch, ulp)
+        assert T.within_yardstick(e_fused, e_torch, ulp), "%s p=%g %s: fused error %.3e exceeds %gx max(torch fp32 chain %.3e, ulp %.3e)" % (shape, p, name, e_fused, FACTOR, e_torch, ulp)
 
 
 @pytest.mark.parametrize("shape", [(3, 65, 132), (1, 300, 1028), (4, 16, 5120)], ids=ids)
@@ -248,18 +238,10 @@ def test_autograd_function_and_saved_state(built_lib):
         training.gelu_grn_dropout(torch.zeros(2, 3, 6, device=DEV), torch.zeros(6, device=DEV), torch.zeros(6, device=DEV))
 
 
-def _tiny(golden):
-    cfg = G.UNET_TINY
-    m = paella_amd.Paella(**cfg)
-    weights_for(m, sum(cfg["blocks"]), golden("unet_tiny_forward"))
-    return cfg, m.to(DEV)
-
-
 def test_train_step_with_hip_activation_reproduces_the_reference(golden, built_lib):
     """_train_step of tests/test_gpu_training.py under set_training_activation("hip"), against the reference's recorded step and under that test's tolerances; then
     the hand-over to the HIP engine, which never sees the switch"""
-    cfg, m = _tiny(golden)
-    g = golden("train_tiny_step")
+    cfg, m = T.model_for("tiny", golden, DEV)
     m.set_training_activation("hip")
     calls = []
     real = training.gelu_grn_dropout
@@ -269,36 +251,7 @@ def test_train_step_with_hip_activation_reproduces_the_reference(golden, built_l
     finally:
         training.gelu_grn_dropout = real
     assert len(calls) == sum(1 for lv in list(m.down_blocks) + list(m.up_blocks) for b in lv if b.kind in "CF"), "the train-mode forward did not route through the HIP op"
-    np.testing.assert_allclose(float(loss), float(g["nodrop_loss"]), rtol=2e-5)
-    np.testing.assert_allclose(pred[:, ::4, ::2, ::2].cpu().numpy(), g["nodrop_pred_sub"], atol=5e-5, rtol=1e-4)
-    params = dict(m.named_parameters())
-    names = g["names"].tolist()
-    norms = np.array([float(params[k].grad.norm()) for k in names])
-    np.testing.assert_allclose(norms, g["nodrop_grad_norms"], rtol=5e-4, atol=1e-6)
-    for k in [k for k in g.files if k.startswith("nodrop_grad:")]:
-        ref = g[k]
-        np.testing.assert_allclose(params[k.split(":", 1)[1]].grad.cpu().numpy(), ref, rtol=5e-4, atol=5e-4 * max(float(np.abs(ref).max()), 1e-6), err_msg=k)
-    # forward_loss takes the same route
-    latents, t, mask, random_x, c = G.train_step_inputs(cfg)
-    latents, t, mask, random_x = latents.to(DEV), t.to(DEV), mask.to(DEV), random_x.to(DEV)
-    noised = latents * (1 - mask) + random_x * mask
-    lw = m.get_loss_weight(t, mask)
-    fl, _ = m.forward_loss(noised, t, latents, **to_dev(c, DEV))
-    np.testing.assert_allclose(float(((fl.detach() * lw).sum(dim=[1, 2]) / lw.sum(dim=[1, 2])).mean()), float(g["nodrop_loss"]), rtol=2e-5)
-    # optimizer step, back to eval: the engine's logits do not depend on the switch
-    opt = torch.optim.AdamW(m.parameters(), lr=2e-3)
-    nn.utils.clip_grad_norm_(m.parameters(), 1.0)
-    opt.step()
-    m.eval()
-    gen = torch.Generator().manual_seed(17)
-    x = torch.randint(0, cfg["num_labels"], (2, 16, 16), generator=gen).to(DEV)
-    r = torch.tensor([0.8, 0.3]).to(DEV)
-    cc = to_dev(cond_for(cfg, 2, 3, 1, G.COND_SEED + 3), DEV)
-    with torch.no_grad():
-        with_hip = m(x, r, **cc).clone()
-        m.set_training_activation("torch")
-        with_torch = m(x, r, **cc)
-    assert torch.isfinite(with_hip).all() and torch.equal(with_hip, with_torch)
+    T.assert_switched_step_and_handover(m, cfg, golden("train_tiny_step"), pred, loss, lambda: m.set_training_activation("torch"))
 
 
 def test_train_step_with_dropout_is_reproducible_under_manual_seed(golden, built_lib):
@@ -306,7 +259,7 @@ def test_train_step_with_dropout_is_reproducible_under_manual_seed(golden, built
     generator and everything it computes has a fixed order.  torch's OWN backward kernels do not by default: under EITHER setting, with or without dropout, 135 of
     the 136 gradients of this step move by 1e-9 ... 1e-8 between two runs on MI355X, and under torch.use_deterministic_algorithms they repeat exactly (measured for
     both settings).  So the rest of the step runs under that switch here, and what the comparison then holds to account is the op."""
-    cfg, m = _tiny(golden)
+    cfg, m = T.model_for("tiny", golden, DEV)
     m.set_training_activation("hip")
     runs = []
     was, was_warn = torch.are_deterministic_algorithms_enabled(), torch.is_deterministic_algorithms_warn_only_enabled()

@@ -14,9 +14,9 @@ Nothing is timed without a HIP device."""
 import argparse
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import train_ab as AB  # noqa: E402
 
 
 def main():
@@ -38,12 +38,8 @@ def main():
         sys.exit("bench_head_loss.py needs a HIP device: nothing is timed without one")
     dev = torch.device("cuda", 0)
     N, K, eps = a.labels, a.k, a.eps
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
-
+    report = AB.Report(a.out)
+    say = report.say
     say("training loss head, forward + backward: K = %d, N = %d, label_smoothing = %g; %d rounds of %d passes per path after one warm-up round, paths alternating"
         % (K, N, eps, a.rounds, a.iters))
     say("%8s %6s %12s %12s %12s %16s %22s %18s" % ("rows", "path", "median ms", "min ms", "max ms", "peak MiB > inputs", "peak MiB > in + outputs", "one logits MiB"))
@@ -65,50 +61,28 @@ def main():
             return (loss.detach(),) + torch.autograd.grad(loss, (h, w), g)
 
         paths = {"torch": torch_pass, "fused": fused_pass}
-        res = {}
-        peak = {}
-        for name, fn in paths.items():   # warm-up, agreement and memory
-            res[name] = fn()
-            torch.cuda.synchronize(dev)
-        for name in paths:
-            torch.cuda.empty_cache()
-            torch.cuda.synchronize(dev)
-            base = torch.cuda.memory_allocated(dev)
-            torch.cuda.reset_peak_memory_stats(dev)
-            out = paths[name]()
-            torch.cuda.synchronize(dev)
-            outputs = sum(o.numel() * o.element_size() for o in out) + rows * 4  # + the int32 argmax of the fused op (the torch path has none: its figure is not used)
-            peak[name] = (torch.cuda.max_memory_allocated(dev) - base, outputs)
-            del out
+        res = {name: fn() for name, fn in paths.items()}   # warm-up, agreement and memory
+        torch.cuda.synchronize(dev)
+        # outputs: + the int32 argmax of the fused op (the torch path has none: its figure is not used)
+        peak = {name: (AB.peak_of(dev, fn), sum(o.numel() * o.element_size() for o in res[name]) + rows * 4) for name, fn in paths.items()}
         for i, what in enumerate(("loss", "dh", "dw")):
             d = float((res["torch"][i].double() - res["fused"][i].double()).abs().max())
             s = float(res["torch"][i].double().abs().max())
             say("#   rows %d: max |torch - fused| of %s = %.3e (max |torch| %.3e)" % (rows, what, d, s))
             assert d <= 1e-4 * max(s, 1.0), "the two paths disagree"
         del res
-        times = {n: [] for n in paths}
-        for _ in range(a.rounds):
-            for name, fn in paths.items():
-                torch.cuda.synchronize(dev)
-                t0 = time.perf_counter()
-                for _ in range(a.iters):
-                    fn()
-                torch.cuda.synchronize(dev)
-                times[name].append((time.perf_counter() - t0) * 1e3 / a.iters)
+        times = AB.alternate(dev, paths, a.rounds, a.iters)
         logits_mib = rows * N * 4 / 2 ** 20
         for name in paths:
-            v = sorted(times[name])
             p, o = peak[name]
-            say("%8d %6s %12.3f %12.3f %12.3f %16.1f %22s %18.1f" % (rows, name, v[len(v) // 2], v[0], v[-1], p / 2 ** 20,
-                                                                  "%.1f" % ((p - o) / 2 ** 20) if name == "fused" else "-", logits_mib))
+            say("%8d %6s %12.3f %12.3f %12.3f %16.1f %22s %18.1f" % ((rows, name) + AB.median(times[name]) + (p / 2 ** 20,
+                                                                  "%.1f" % ((p - o) / 2 ** 20) if name == "fused" else "-", logits_mib)))
         p, o = peak["fused"]
         say("#   rows %d: fused peak above inputs and outputs %.1f MiB, bound (a quarter of one logits tensor) %.1f MiB: %s; torch peak %.2f logits tensors"
             % (rows, (p - o) / 2 ** 20, logits_mib / 4, "under" if p - o < rows * N else "OVER", peak["torch"][0] / (rows * N * 4)))
         del h, w, t, g
         torch.cuda.empty_cache()
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    report.finish()
 
 
 if __name__ == "__main__":

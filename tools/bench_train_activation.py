@@ -19,9 +19,9 @@ Nothing is timed without a HIP device."""
 import argparse
 import os
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import train_ab as AB  # noqa: E402
 
 
 def main():
@@ -40,44 +40,12 @@ def main():
     import torch
     import torch.nn.functional as F
 
-    import paella_amd
-    from paella_amd import synth, training
+    from paella_amd import training
     if not torch.cuda.is_available():
         sys.exit("bench_train_activation.py needs a HIP device: nothing is timed without one")
     dev = torch.device("cuda", 0)
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    def median(v):
-        v = sorted(v)
-        return v[len(v) // 2], v[0], v[-1]
-
-    def alternate(paths, rounds, iters):
-        times = {n: [] for n in paths}
-        for _ in range(rounds):
-            for name, fn in paths.items():
-                torch.cuda.synchronize(dev)
-                t0 = time.perf_counter()
-                for _ in range(iters):
-                    fn()
-                torch.cuda.synchronize(dev)
-                times[name].append((time.perf_counter() - t0) * 1e3 / iters)
-        return times
-
-    def peak_of(fn):
-        torch.cuda.empty_cache()
-        torch.cuda.synchronize(dev)
-        base = torch.cuda.memory_allocated(dev)
-        torch.cuda.reset_peak_memory_stats(dev)
-        out = fn()
-        torch.cuda.synchronize(dev)
-        peak = torch.cuda.max_memory_allocated(dev) - base
-        del out
-        return peak
-
+    report = AB.Report(a.out)
+    say, median = report.say, AB.median
     say("training MLP activation, forward + backward: dropout p = %g; %d rounds of %d passes per path after one warm-up round, paths alternating" % (a.p, a.rounds, a.iters))
     say("%16s %6s %12s %12s %12s %18s %16s" % ("[B, P, C]", "path", "median ms", "min ms", "max ms", "peak MiB > inputs", "one tensor MiB"))
     for spec in a.shapes:
@@ -110,8 +78,8 @@ def main():
         del res
         for fn in paths.values():   # warm-up at the timed p
             fn()
-        peak = {name: peak_of(fn) for name, fn in paths.items()}
-        times = alternate(paths, a.rounds, a.iters)
+        peak = {name: AB.peak_of(dev, fn) for name, fn in paths.items()}
+        times = AB.alternate(dev, paths, a.rounds, a.iters)
         one = B * P * C * 4 / 2 ** 20
         for name in paths:
             say("%16s %6s %12.3f %12.3f %12.3f %18.1f %16.1f" % ((spec, name) + median(times[name]) + (peak[name] / 2 ** 20, one)))
@@ -121,46 +89,19 @@ def main():
         torch.cuda.empty_cache()
 
     if not a.no_step:
-        import bench
-        cfg = bench.MODELS[a.step_model]
-        m = paella_amd.Paella(**cfg)
-        synth.randomize_(m, seed=0)
-        m = m.to(dev)
-        m.train()
-        Bs, g = a.step_batch, a.step_grid
-        gen = torch.Generator().manual_seed(7)
-        latents = torch.randint(0, cfg["num_labels"], (Bs, g, g), generator=gen).to(dev)
-        t = torch.rand(Bs, generator=gen).to(dev)
-        mask = (torch.rand(Bs, g, g, generator=gen) < t.cpu()[:, None, None]).long().to(dev)
-        random_x = torch.randint(0, cfg["num_labels"], (Bs, g, g), generator=gen).to(dev)
-        cond = synth.synth_conditioning(Bs, 4, cfg["byt5_embd"], cfg["clip_embd"], seed=2, device=dev)
-        noised = latents * (1 - mask) + random_x * mask
-        lw = m.get_loss_weight(t, mask)
-
-        def step_with(mode):
-            def step():
-                m.set_training_activation(mode)
-                m.zero_grad(set_to_none=True)
-                loss, _ = m.forward_loss(noised, t, latents, **cond)
-                loss = ((loss * lw).sum(dim=[1, 2]) / lw.sum(dim=[1, 2])).mean()
-                loss.backward()
-                return loss.detach()
-            return step
-
-        paths = {"torch": step_with("torch"), "hip": step_with("hip")}
-        say("one training step (forward_loss + backward), model %s (%.1fM parameters), %d x %dx%d tokens, dropout %s; %d rounds of 1 step per setting after one warm-up, "
-            "settings alternating" % (a.step_model, sum(p.numel() for p in m.parameters()) / 1e6, Bs, g, g, m.dropout, a.step_rounds))
+        S = AB.TrainStep(a.step_model, a.step_batch, a.step_grid, dev)
+        m = S.m
+        paths = {mode: S.under(m.set_training_activation, mode) for mode in ("torch", "hip")}
+        say("one training step (forward_loss + backward), %s; %d rounds of 1 step per setting after one warm-up, settings alternating" % (S.what, a.step_rounds))
         losses = {name: float(fn()) for name, fn in paths.items()}   # warm-up
         m.zero_grad(set_to_none=True)
-        peak = {name: peak_of(fn) for name, fn in paths.items()}
+        peak = {name: AB.peak_of(dev, fn) for name, fn in paths.items()}
         m.zero_grad(set_to_none=True)
-        times = alternate(paths, a.step_rounds, 1)
+        times = AB.alternate(dev, paths, a.step_rounds, 1)
         say("%10s %12s %12s %12s %26s %12s" % ("setting", "median ms", "min ms", "max ms", "peak MiB > weights + inputs", "loss"))
         for name in paths:
             say("%10s %12.2f %12.2f %12.2f %26.1f %12.5f" % ((name,) + median(times[name]) + (peak[name] / 2 ** 20, losses[name])))
-    if a.out:
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    report.finish()
 
 
 if __name__ == "__main__":

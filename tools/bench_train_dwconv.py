@@ -30,9 +30,9 @@ import glob
 import os
 import re
 import sys
-import time
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import train_ab as AB  # noqa: E402
 
 
 def _rows(directory, suffix):
@@ -75,16 +75,8 @@ def main():
     ap.add_argument("--match", default="dwconv")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
-    lines = []
-
-    def say(s):
-        print(s, flush=True)
-        lines.append(s)
-
-    def finish():
-        if a.out:
-            with open(a.out, "w") as f:
-                f.write("\n".join(lines) + "\n")
+    report = AB.Report(a.out)
+    say, finish, median = report.say, report.finish, AB.median
 
     if a.part == "diff":
         off, on = by_name(a.dirs[0]), by_name(a.dirs[1])
@@ -123,38 +115,10 @@ def main():
     import torch
     import torch.nn.functional as F
 
-    import paella_amd
-    from paella_amd import synth, training
+    from paella_amd import training
     if not torch.cuda.is_available():
         sys.exit("bench_train_dwconv.py needs a HIP device: nothing is timed without one")
     dev = torch.device("cuda", 0)
-
-    def median(v):
-        v = sorted(v)
-        return v[len(v) // 2], v[0], v[-1]
-
-    def alternate(paths, rounds, iters):
-        times = {n: [] for n in paths}
-        for _ in range(rounds):
-            for name, fn in paths.items():
-                torch.cuda.synchronize(dev)
-                t0 = time.perf_counter()
-                for _ in range(iters):
-                    fn()
-                torch.cuda.synchronize(dev)
-                times[name].append((time.perf_counter() - t0) * 1e3 / iters)
-        return times
-
-    def peak_of(fn):
-        torch.cuda.empty_cache()
-        torch.cuda.synchronize(dev)
-        base = torch.cuda.memory_allocated(dev)
-        torch.cuda.reset_peak_memory_stats(dev)
-        out = fn()
-        torch.cuda.synchronize(dev)
-        peak = torch.cuda.max_memory_allocated(dev) - base
-        del out
-        return peak
 
     if a.part == "op":
         say("training ResBlock front, forward + backward: %d rounds of %d passes per path after one warm-up round, paths alternating" % (a.rounds, a.iters))
@@ -190,8 +154,8 @@ def main():
                     say("#   %s%s: max |torch - fused| of %s: %.3e (max |torch| %.3e)" % (spec, " skip" if skip else "", what, d, m))
                     assert d <= 1e-4 * max(m, 1.0), "the two paths disagree"
                 del res
-                peak = {name: peak_of(fn) for name, fn in paths.items()}
-                times = alternate(paths, a.rounds, a.iters)
+                peak = {name: AB.peak_of(dev, fn) for name, fn in paths.items()}
+                times = AB.alternate(dev, paths, a.rounds, a.iters)
                 one = B * H * W * C * 4 / 2 ** 20
                 for name in paths:
                     say("%16s %5s %6s %12.3f %12.3f %12.3f %18.1f %16.1f" % ((spec, "yes" if skip else "no", name) + median(times[name]) + (peak[name] / 2 ** 20, one)))
@@ -199,41 +163,13 @@ def main():
                 torch.cuda.empty_cache()
         return finish()
 
-    import bench
-    cfg = bench.MODELS[a.step_model]
-    m = paella_amd.Paella(**cfg)
-    synth.randomize_(m, seed=0)
-    m = m.to(dev)
-    m.train()
+    S = AB.TrainStep(a.step_model, a.step_batch, a.step_grid, dev)
+    m = S.m
     m.set_training_activation("hip")
-    Bs, g = a.step_batch, a.step_grid
-    gen = torch.Generator().manual_seed(7)
-    latents = torch.randint(0, cfg["num_labels"], (Bs, g, g), generator=gen).to(dev)
-    t = torch.rand(Bs, generator=gen).to(dev)
-    mask = (torch.rand(Bs, g, g, generator=gen) < t.cpu()[:, None, None]).long().to(dev)
-    random_x = torch.randint(0, cfg["num_labels"], (Bs, g, g), generator=gen).to(dev)
-    cond = synth.synth_conditioning(Bs, 4, cfg["byt5_embd"], cfg["clip_embd"], seed=2, device=dev)
-    noised = latents * (1 - mask) + random_x * mask
-    lw = m.get_loss_weight(t, mask)
-
     held = {}
-
-    def step_with(mode):
-        def step():
-            m.set_training_depthwise(mode)
-            m.zero_grad(set_to_none=True)
-            base = torch.cuda.memory_allocated(dev)
-            loss, _ = m.forward_loss(noised, t, latents, **cond)
-            loss = ((loss * lw).sum(dim=[1, 2]) / lw.sum(dim=[1, 2])).mean()
-            held[mode] = torch.cuda.memory_allocated(dev) - base   # what autograd holds between the forward and the backward
-            loss.backward()
-            return loss.detach()
-        return step
-
-    what = "model %s (%.1fM parameters), %d x %dx%d tokens, dropout %s, set_training_activation(\"hip\")" % (
-        a.step_model, sum(p.numel() for p in m.parameters()) / 1e6, Bs, g, g, m.dropout)
+    what = S.what + ", set_training_activation(\"hip\")"
     if a.part == "trace-step":
-        fn = step_with(a.setting)
+        fn = S.under(m.set_training_depthwise, a.setting)
         fn()   # warm-up (traced as well: divide the totals by 1 + --steps)
         for _ in range(a.steps):
             fn()
@@ -241,7 +177,7 @@ def main():
         say("traced %d + 1 training steps with set_training_depthwise(\"%s\"): %s" % (a.steps, a.setting, what))
         return finish()
 
-    paths = {"torch": step_with("torch"), "hip": step_with("hip")}
+    paths = {mode: S.under(m.set_training_depthwise, mode, held) for mode in ("torch", "hip")}
     say("one training step (forward_loss + backward), %s; %d rounds of 1 step per set_training_depthwise setting after one warm-up, settings alternating" % (what, a.step_rounds))
     losses, counts = {}, {}
     for name, fn in paths.items():   # warm-up
@@ -251,11 +187,11 @@ def main():
     peak = {}
     for name, fn in paths.items():
         m.zero_grad(set_to_none=True)   # the base of EITHER setting holds no parameter gradients: the peak includes the step's own
-        peak[name] = peak_of(fn)
+        peak[name] = AB.peak_of(dev, fn)
     m.zero_grad(set_to_none=True)
-    times = alternate(paths, a.step_rounds, 1)
+    times = AB.alternate(dev, paths, a.step_rounds, 1)
     say("peak = max allocated during the step above weights and inputs, the step's parameter gradients (%.1f MiB once all exist) included under either setting; "
-        "held = allocated between the forward and the backward above weights and inputs (what autograd keeps)" % (sum(p.numel() for p in m.parameters()) * 4 / 2 ** 20))
+        "held = allocated between the forward and the backward above weights and inputs (what autograd keeps)" % (S.parameters() * 4 / 2 ** 20))
     say("%10s %12s %12s %12s %10s %10s %12s %10s %14s" % ("setting", "median ms", "min ms", "max ms", "peak MiB", "held MiB", "loss", "op calls", "inputs copied"))
     for name in paths:
         say("%10s %12.2f %12.2f %12.2f %10.1f %10.1f %12.5f %10d %14d" % ((name,) + median(times[name]) + (peak[name] / 2 ** 20, held[name] / 2 ** 20, losses[name]) + counts[name]))
