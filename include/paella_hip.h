@@ -733,6 +733,49 @@ int paella_dwconv_ln_train_backward(const float* x, const float* skip /* may be 
                                     float* dw_out /* may be NULL */, float* dbias_out /* may be NULL */, void* ws,
                                     size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training attention (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays 8): the attention
+ * core of every AttnBlock in train mode -- softmax(Q K^T / sqrt(D)) V with dropout on the probabilities
+ * (nn.MultiheadAttention between its in- and out-projection; reference src/modules.py:7-19) -- as one op, forward and
+ * backward, flash style (paella_amd/csrc/attn_train.hip).  Everything fp32.
+ *   q [B, P, .], k and v [B, L, .]: head h occupies floats [h D, (h + 1) D) of a row; rows are ld* floats apart
+ *   (each ld* a multiple of 4 and at least nhead D) and sample b starts at b * rows * ld -- so k and v may be the two
+ *   halves of one [B, L, 2 nhead D] projection output, and dk and dv may be written into one such buffer, without a
+ *   copy.  o and do are dense [B, P, nhead D]; lse is [B, nhead, P].
+ *   Forward:  s = q k^T / sqrt(D);  lse = logsumexp_j s, computed over key tiles with the running row maximum
+ *     subtracted;  pr = exp(s - lse);  o = (keep pr / (1 - p_drop)) v.  o_out and lse_out are ALL the forward leaves:
+ *     no [P, L] array is ever in global memory.
+ *   Dropout: p_drop == 0 draws nothing, the seed is then without meaning.  Otherwise element e, the flat index in
+ *     [B, nhead, P, L4] with L4 = 4 ceil(L / 4) (a quad never straddles a row; 64-bit arithmetic), takes word e & 3
+ *     of philox4x32(seed ^ 0xe7037ed1a0b428db, counter (e >> 2, 0)) and is kept iff (word >> 8) * 2^-24 >= p_drop;
+ *     the scale is the one fp32 division 1.0f / (1.0f - p_drop).  The backward regenerates the mask from (seed, e).
+ *   Backward for a given do:  delta_i = sum_c do_ic o_ic (= sum_j pr_ij keep_ij dpd_ij / (1 - p): why o is an
+ *     input);  dpd = do v^T;  dp = keep dpd / (1 - p);  ds = pr (dp - delta);  dq = ds k / sqrt(D);
+ *     dk = ds^T q / sqrt(D);  dv = (keep pr / (1 - p))^T do.  pr is recomputed from q, k and lse.  dq, dk and dv
+ *     are WRITTEN, not accumulated into (the floats of a row outside [0, nhead D) are left untouched); each may be
+ *     NULL and is then not computed; with all three NULL nothing is launched.
+ * Shapes: D a multiple of 16 in 16...128; B and nhead in 1...65535; P and L in 1...2^20; B nhead P <= 2^31 - 1;
+ * nhead D <= 2^24; every pointer and the workspace 16-byte aligned; 0 <= p_drop < 1; all element offsets are 64-bit.
+ * Anything else or a NULL required pointer (q, k, v, o, lse, do): PAELLA_ERR_ARG; a workspace smaller than
+ * paella_attn_train_workspace_bytes: PAELLA_ERR_WORKSPACE -- both before anything is enqueued.
+ * Kernels: every workgroup is one wave that owns 16 queries (forward, dq) or 16 keys (dk / dv) of one
+ * (sample, head) and walks the other axis in ascending 16-wide tiles on the exact-fp32 matrix cores; both backward
+ * kernels recompute the score tile; delta comes from a pre-pass.  Tails in P and L are bounds, not padding.
+ * Workspace: delta [B, nhead, P], rounded up to 256 bytes (the forward uses none of it); no state between calls, no
+ * initialisation.  Deterministic: no float atomics, no tickets, no sum crosses a workgroup; the order of every sum
+ * is fixed by (B, nhead, P, L, D) alone, and what a (sample, head) computes depends on that sample's data only.
+ * No allocation, no synchronisation, capturable in a graph.
+ * ---------------------------------------------------------------------------------------------- */
+size_t paella_attn_train_workspace_bytes(int B, int nhead, int P, int L, int D); /* 0 for an unsupported shape */
+int paella_attn_train_forward(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B,
+                              int nhead, int P, int L, int D, float p_drop, uint64_t seed, float* o_out,
+                              float* lse_out, void* ws, size_t ws_bytes, void* stream);
+int paella_attn_train_backward(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                               const float* o, const float* lse, const float* d_o, int B, int nhead, int P, int L,
+                               int D, float p_drop, uint64_t seed, float* dq_out /* may be NULL */, int lddq,
+                               float* dk_out /* may be NULL */, int lddk, float* dv_out /* may be NULL */, int lddv,
+                               void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

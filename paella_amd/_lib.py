@@ -234,6 +234,12 @@ SIGNATURES = {
     "paella_dwconv_ln_train_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "paella_dwconv_ln_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p,
                                                 c_void_p, c_size_t, c_void_p]),
+    # training attention (ABI 8, additive): softmax(q k^T) v with dropout, forward and backward, only lse [B, nhead, P] kept besides o
+    "paella_attn_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "paella_attn_train_forward": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_uint64, c_void_p, c_void_p,
+                                          c_void_p, c_size_t, c_void_p]),
+    "paella_attn_train_backward": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
+                                           c_uint64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
 }
 
 # exported for tests / tools only; declared in paella_amd/csrc/test_hooks.h, not in the public header

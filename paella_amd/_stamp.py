@@ -6,7 +6,7 @@ import hashlib
 import os
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-SOURCES = ["gemm.hip", "elementwise.hip", "dwconv.hip", "attention.hip", "tail.hip", "vqgan.hip", "model.hip", "vqmodel.hip", "loss.hip", "grn_act.hip", "dwconv_train.hip"]
+SOURCES = ["gemm.hip", "elementwise.hip", "dwconv.hip", "attention.hip", "tail.hip", "vqgan.hip", "model.hip", "vqmodel.hip", "loss.hip", "grn_act.hip", "dwconv_train.hip", "attn_train.hip"]
 HEADERS = ["common.h", "internal.h", "gemm_device.h", "philox.h", "test_hooks.h", "train_common.h", os.path.join("..", "..", "include", "paella_hip.h")]
 
 
@@ -19,7 +19,8 @@ ARCH = "gfx950"
 FLAGS = ["--offload-arch=" + ARCH, "-O3", "-std=c++17", "-fPIC", "-Wall", "-Wno-unused-function"]
 # per-unit extras.  attention.hip: keep the MFMA accumulators in VGPRs -- the online softmax rescales O^T between every two MFMA blocks, and with AGPR accumulators
 # hipcc moved all 20 of them out and back per 16-key step (148 v_accvgpr_* per 32 keys; profiles/r05_attention_pmc_and_probe.txt)
-UNIT_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
+# attn_train.hip: the same for its forward (the same online softmax), and its backward kernels scale their accumulators before the store
+UNIT_FLAGS = {"attention.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"], "attn_train.hip": ["-mllvm", "-amdgpu-mfma-vgpr-form=1"]}
 
 
 def source_stamp():

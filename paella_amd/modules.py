@@ -274,6 +274,7 @@ class Paella(nn.Module):
         self._precision = 0
         self._train_activation = "torch"
         self._train_depthwise = "torch"
+        self._train_attention = "torch"
         # Constructed in EVAL mode (an nn.Module normally starts in train mode): eval = the hand-written HIP engine, which is what
         # sampling needs; `model.train()` -- the switch the reference's training loops flip (src/train.py:47,
         # src_distributed/train.py:73,140,172) -- selects the differentiable torch-op evaluation of paella_amd/training.py.
@@ -437,6 +438,19 @@ class Paella(nn.Module):
         if mode == "hip" and int(self._cfg["kernel_size"]) != 3:
             raise ValueError("training depthwise 'hip' takes kernel_size 3 only (this module has %d)" % int(self._cfg["kernel_size"]))
         self._train_depthwise = mode
+        return self
+
+    def set_training_attention(self, mode):
+        """How the TRAIN-mode forward (`forward` and `forward_loss` after `model.train()`) runs the attention core of every AttnBlock -- scores, softmax, dropout
+        and the product with the values, between the in-projection and the out-projection: "torch" (default) is `F.multi_head_attention_forward`, op for op as
+        before; "hip" runs it as one HIP op in both directions (`paella_amd.training.attention_dropout`) when the module is on a cuda device -- autograd then
+        keeps one float per (sample, head, query) instead of the [B, nhead, P, L] probabilities and their dropout mask, and the masks come from one 64-bit seed
+        per block drawn from torch's default CPU generator (`torch.manual_seed` reproduces a run; the masks are not the torch chain's).  Independent of
+        `set_training_activation` and `set_training_depthwise`.  A train-mode call with `attn_weights` runs the torch ops under either setting: the key-weight
+        table stays an inference feature.  Eval mode -- the HIP inference engine -- never sees the switch."""
+        if mode not in ("torch", "hip"):
+            raise ValueError("training attention must be 'torch' or 'hip'")
+        self._train_attention = mode
         return self
 
     def __del__(self):

@@ -270,3 +270,80 @@ def dwconv_layernorm(x, weight, bias, skip=None, eps=1e-6):
     _refuse_off_device("dwconv_layernorm", "x, skip, weight and bias", (x, skip, weight, bias))
     DW_COUNTERS["calls"] += 1
     return _DwconvLayerNorm.apply(_nhwc(x), None if skip is None else _nhwc(skip), _aligned(weight.contiguous()), _aligned(bias.contiguous().view(C)), eps)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# Training attention: softmax(q k^T / sqrt(D)) v with dropout on the probabilities as ONE HIP op, forward and backward, flash style
+# (paella_amd/csrc/attn_train.hip, include/paella_hip.h "Training attention").  Besides its inputs and its output autograd keeps one float per (sample, head,
+# query): the [B, nhead, P, L] scores, probabilities and dropout mask of the torch chain never exist -- the backward recomputes the probabilities from q, k and
+# lse, the mask from a (seed, element index) counter.
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+ATTN_MAX_B, ATTN_MAX_HEADS, ATTN_MAX_P, ATTN_MAX_L, ATTN_MAX_ROWS = 65535, 65535, 1 << 20, 1 << 20, 2 ** 31 - 1
+# diagnostic: how often `attention_dropout` ran (tests, tools/bench_train_attention.py)
+ATTN_COUNTERS = {"calls": 0}
+
+
+class _AttentionDropout(torch.autograd.Function):
+    """(q [B, P, C], kv [B, L, 2C]) -> o [B, P, C]; saves q, kv, o and lse [B, nhead, P].  k and v are the two halves of kv's rows and dk, dv the two halves of
+    dkv's: the strides of the C entry points take them in place."""
+
+    @staticmethod
+    def forward(ctx, q, kv, nhead, p, seed):
+        B, P, C = q.shape
+        L, D = kv.size(1), C // nhead
+        o = torch.empty_like(q)
+        lse = q.new_empty(B, nhead, P)
+        _call("paella_attn_train_forward", q.device, _lib.load().paella_attn_train_workspace_bytes(B, nhead, P, L, D), q, C, kv[..., :C], 2 * C, kv[..., C:], 2 * C,
+              B, nhead, P, L, D, p, seed, o, lse)
+        ctx.save_for_backward(q, kv, o, lse)
+        ctx.nhead, ctx.p, ctx.seed = nhead, p, seed
+        return o
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, do):
+        q, kv, o, lse = ctx.saved_tensors
+        B, P, C = q.shape
+        nhead, L, D = ctx.nhead, kv.size(1), C // ctx.nhead
+        do = _aligned(do.to(torch.float32).contiguous())
+        (dq, dkv, _, _, _), wanted = _grad_outputs(ctx, q, kv, None, None, None)
+        if wanted:
+            dk, dv = (None, None) if dkv is None else (dkv[..., :C], dkv[..., C:])
+            _call("paella_attn_train_backward", q.device, _lib.load().paella_attn_train_workspace_bytes(B, nhead, P, L, D), q, C, kv[..., :C], 2 * C, kv[..., C:], 2 * C,
+                  o, lse, do, B, nhead, P, L, D, ctx.p, ctx.seed, dq, C, dk, 2 * C, dv, 2 * C)
+        return dq, dkv, None, None, None
+
+
+def attention_dropout(q, kv, nhead, p=0.0, seed=None):
+    """The attention core of an AttnBlock in train mode as one op (nn.MultiheadAttention between its in-projection and its out-projection): per head h, with
+    D = C / nhead, qh = q[..., hD:(h+1)D], kh = kv[..., hD:(h+1)D], vh = kv[..., C + hD:C + (h+1)D],
+        o[..., hD:(h+1)D] = dropout(softmax(qh kh^T / sqrt(D)), p) vh
+    q fp32 [B, P, C]; kv fp32 [B, L, 2C], keys in channels [0, C) and values in [C, 2C) -- what one F.linear(rows, in_proj_weight[C:], in_proj_bias[C:]) produces.
+    Returns o [B, P, C], contiguous.  Once differentiable in q and kv; the gradient of kv comes back as one [B, L, 2C] tensor.  Besides q, kv and o autograd keeps
+    lse [B, nhead, P] only.  p in [0, 1); p = 0 draws nothing.  The dropout mask is a function of (seed, element index): seed = None with p > 0 draws one 64-bit seed
+    from torch's default CPU generator, so torch.manual_seed reproduces a run.  D a multiple of 16 in 16...128, B and nhead up to 65535, P and L up to 2^20,
+    B nhead P up to 2^31 - 1.  HIP only and exact fp32 only: anything else raises ValueError -- there is no torch fallback."""
+    _refuse_non_tensors("attention_dropout", q, kv)
+    _refuse_dtypes("attention_dropout", "fp32 q and kv", (q, kv))
+    if q.dim() != 3 or kv.dim() != 3 or kv.size(0) != q.size(0) or kv.size(2) != 2 * q.size(2):
+        raise ValueError("q must be [B, P, C] and kv [B, L, 2C] (got %s, %s)" % (tuple(q.shape), tuple(kv.shape)))
+    B, P, C = q.shape
+    L = kv.size(1)
+    if isinstance(nhead, bool) or not isinstance(nhead, int) or not 1 <= nhead <= ATTN_MAX_HEADS or C % nhead:
+        raise ValueError("nhead = %r: must be an integer in 1...%d that divides C = %d" % (nhead, ATTN_MAX_HEADS, C))
+    D = C // nhead
+    if D % 16 or not 16 <= D <= 128:
+        raise ValueError("head width D = C / nhead = %d: the fused attention takes a multiple of 16 in 16...128" % D)
+    if not 1 <= B <= ATTN_MAX_B or not 1 <= P <= ATTN_MAX_P or not 1 <= L <= ATTN_MAX_L or B * nhead * P > ATTN_MAX_ROWS:
+        raise ValueError("q %s, kv %s: the fused attention takes 1...%d samples, 1...%d queries and 1...%d keys per sample, B nhead P <= 2^31 - 1"
+                         % (tuple(q.shape), tuple(kv.shape), ATTN_MAX_B, ATTN_MAX_P, ATTN_MAX_L))
+    p = float(p)
+    _refuse_out_of_range("p", p, 0.0 <= p < 1.0, "must lie in [0, 1)")
+    _refuse_off_device("attention_dropout", "q and kv", (q, kv))
+    if p == 0.0:
+        seed = 0
+    elif seed is None:
+        seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    ATTN_COUNTERS["calls"] += 1
+    return _AttentionDropout.apply(_aligned(q.contiguous()), _aligned(kv.contiguous()), nhead, p, seed)

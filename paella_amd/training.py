@@ -18,13 +18,14 @@ import torch
 import torch.nn.functional as F
 
 # the training ops and their limits live in train_ops.py; the network below calls them through THESE module globals (which is also where tests and tools look)
-from .train_ops import (ACT_MAX_B, ACT_MAX_C, ACT_MAX_P, DW_COUNTERS, DW_MAX_C, DW_MAX_C_SKIP, DW_MAX_POSITIONS, HEAD_MAX_K, HEAD_MAX_LABELS,  # noqa: F401
-                        HEAD_MAX_ROWS, dwconv_layernorm, gelu_grn_dropout, head_cross_entropy)
+from .train_ops import (ACT_MAX_B, ACT_MAX_C, ACT_MAX_P, ATTN_COUNTERS, ATTN_MAX_B, ATTN_MAX_HEADS, ATTN_MAX_L, ATTN_MAX_P, ATTN_MAX_ROWS, DW_COUNTERS,  # noqa: F401
+                        DW_MAX_C, DW_MAX_C_SKIP, DW_MAX_POSITIONS, HEAD_MAX_K, HEAD_MAX_LABELS, HEAD_MAX_ROWS, attention_dropout, dwconv_layernorm,
+                        gelu_grn_dropout, head_cross_entropy)
 
 # which stretches of a block run as one HIP op: act = the middle of the MLP (Paella.set_training_activation), dw = the front of a ResBlock
-# (Paella.set_training_depthwise).  `_forward_features` decides it once per forward
-_Route = namedtuple("_Route", "act dw")
-_TORCH = _Route(False, False)
+# (Paella.set_training_depthwise), attn = the attention core of an AttnBlock (Paella.set_training_attention).  `_forward_features` decides it once per forward
+_Route = namedtuple("_Route", "act dw attn")
+_TORCH = _Route(False, False, False)
 
 
 def _ln_nchw(x, eps=1e-6):
@@ -74,9 +75,12 @@ def _timestep_block(blk, x, r_embed):
     return x * (1 + a) + b
 
 
-def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, training, attn_weights=None):
+def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, training, attn_weights=None, route=_TORCH):
     """AttnBlock (src/modules.py:65-79) around nn.MultiheadAttention semantics (Attention2D :7-19): queries = LN(x) positions,
-    keys = values = [LN(x) positions | kv_mapper(SiLU(c_embed))], residual on the un-normed x."""
+    keys = values = [LN(x) positions | kv_mapper(SiLU(c_embed))], residual on the un-normed x.  route.attn (Paella.set_training_attention("hip"), train mode
+    on a cuda device): between the in-projection (one F.linear for the queries, one for keys and values together) and the out-projection the block runs as one HIP
+    op in both directions (`attention_dropout`).  With attn_weights the torch branch below runs under either setting: the key-weight table stays an inference
+    feature."""
     kvm = blk.kv_mapper._modules["1"]
     kv = F.linear(F.silu(c_embed), kvm.weight, kvm.bias)
     B, C, H, W = x.shape
@@ -84,7 +88,11 @@ def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, training, attn_weight
     if self_attn:
         kv = torch.cat([q, kv], dim=1)
     at = blk.attention.attn
-    if attn_weights is None:
+    if attn_weights is None and route.attn:
+        w, bias = at.in_proj_weight, at.in_proj_bias
+        out = attention_dropout(F.linear(q, w[:C], bias[:C]), F.linear(kv, w[C:], bias[C:]), nhead, p_drop)
+        out = F.linear(out, at.out_proj.weight, at.out_proj.bias)
+    elif attn_weights is None:
         # torch's own functional form of nn.MultiheadAttention.forward (batch_first handled by the transposes): identical
         # arithmetic and identical dropout-stream consumption to the module the reference instantiates
         out, _ = F.multi_head_attention_forward(q.transpose(0, 1), kv.transpose(0, 1), kv.transpose(0, 1), C, nhead, at.in_proj_weight, at.in_proj_bias,
@@ -146,9 +154,10 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
     emb = model.embedding._modules["1"]
     h = _ln_nchw(F.conv2d(F.pixel_unshuffle(h, patch), emb.weight, emb.bias))
 
-    # Paella.set_training_activation / set_training_depthwise: a switch acts in train mode on a cuda device only; its default leaves every call below as it is
+    # Paella.set_training_activation / set_training_depthwise / set_training_attention: a switch acts in train mode on a cuda device only; its default leaves every call below as it is
     on = training and x.is_cuda
-    route = _Route(on and getattr(model, "_train_activation", "torch") == "hip", on and getattr(model, "_train_depthwise", "torch") == "hip")
+    route = _Route(on and getattr(model, "_train_activation", "torch") == "hip", on and getattr(model, "_train_depthwise", "torch") == "hip",
+                   on and getattr(model, "_train_attention", "torch") == "hip")
     if route.dw:  # the trunk is made channels_last once, here, so that the blocks hand each other NHWC memory
         h = h.contiguous(memory_format=torch.channels_last)
 
@@ -156,7 +165,7 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
         if blk.kind == 'C':
             return _res_block(blk, h, skip, drop(level), training, route)
         if blk.kind == 'A':
-            return _attn_block(blk, h, c_embed, cfg["nhead"][level], cfg["self_attn"], drop(level), training, attn_weights)
+            return _attn_block(blk, h, c_embed, cfg["nhead"][level], cfg["self_attn"], drop(level), training, attn_weights, route)
         if blk.kind == 'T':
             return _timestep_block(blk, h, r_embed)
         if blk.kind == 'F':

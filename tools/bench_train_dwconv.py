@@ -25,38 +25,11 @@ many of one step's op calls had to copy an input that was not NHWC-dense.  "torc
 diff: kernel time per step by kernel name in the two traces; the rows that differ are the front of the ResBlocks (and whatever else the layout change moved).
 Nothing is timed without a HIP device."""
 import argparse
-import csv
-import glob
 import os
-import re
 import sys
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import train_ab as AB  # noqa: E402
-
-
-def _rows(directory, suffix):
-    files = sorted(glob.glob(os.path.join(directory, "**", "*" + suffix), recursive=True))
-    if not files:
-        sys.exit("no *%s under %s" % (suffix, directory))
-    for f in files:
-        with open(f, newline="") as fh:
-            for r in csv.DictReader(fh):
-                yield r
-
-
-def _short(name, n=96):
-    name = re.sub(r"\s+", " ", name)
-    return name if len(name) <= n else name[:n - 3] + "..."
-
-
-def by_name(directory):
-    """kernel name -> (calls, total us) from a rocprofv3 --kernel-trace csv"""
-    out = {}
-    for r in _rows(directory, "kernel_trace.csv"):
-        c, t = out.get(r["Kernel_Name"], (0, 0.0))
-        out[r["Kernel_Name"]] = (c + 1, t + (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
-    return out
 
 
 def main():
@@ -79,37 +52,11 @@ def main():
     say, finish, median = report.say, report.finish, AB.median
 
     if a.part == "diff":
-        off, on = by_name(a.dirs[0]), by_name(a.dirs[1])
-        n = float(a.steps)
-        tot_off, tot_on = sum(t for _, t in off.values()) / n, sum(t for _, t in on.values()) / n
-        say("kernel time per training step by kernel name, depthwise switch off -> on (%d steps per trace; us per step; calls per step)" % a.steps)
-        say("%10s %8s %10s %8s %10s  %s" % ("off us", "calls", "on us", "calls", "on - off", "kernel"))
-        rows = []
-        for k in set(off) | set(on):
-            c0, t0 = off.get(k, (0, 0.0))
-            c1, t1 = on.get(k, (0, 0.0))
-            rows.append((t1 / n - t0 / n, t0 / n, c0 / n, t1 / n, c1 / n, k))
-        rows.sort()
-        gone = sum(-r[0] for r in rows if r[0] < 0)
-        came = sum(r[0] for r in rows if r[0] > 0)
-        for d, t0, c0, t1, c1, k in rows:
-            if abs(d) >= 0.002 * tot_off:
-                say("%10.1f %8.1f %10.1f %8.1f %+10.1f  %s" % (t0, c0, t1, c1, d, _short(k)))
-        say("sum of all kernels: off %.1f us, on %.1f us per step; rows that shrank: -%.1f us (%.1f %% of the off step's kernel time), rows that grew: +%.1f us"
-            % (tot_off, tot_on, gone, 100.0 * gone / tot_off, came))
+        AB.trace_diff(say, a.dirs[0], a.dirs[1], a.steps, "depthwise")
         return finish()
 
     if a.part == "kernels":
-        groups = {}
-        for r in _rows(a.dirs[0], "kernel_trace.csv"):
-            if not re.search(a.match, r["Kernel_Name"]):
-                continue
-            wg = int(r["Workgroup_Size_X"]) * int(r["Workgroup_Size_Y"]) * int(r["Workgroup_Size_Z"])
-            key = (r["Kernel_Name"], "%dx%dx%d/%d" % (int(r["Grid_Size_X"]), int(r["Grid_Size_Y"]), int(r["Grid_Size_Z"]), wg))
-            groups.setdefault(key, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
-        say("%-18s %6s %9s %9s %9s  %s" % ("grid (threads)/wg", "calls", "avg us", "min us", "max us", "kernel"))
-        for (k, g), v in sorted(groups.items(), key=lambda kv: (kv[0][0], kv[0][1])):
-            say("%-18s %6d %9.1f %9.1f %9.1f  %s" % (g, len(v), sum(v) / len(v), min(v), max(v), _short(k)))
+        AB.trace_kernels(say, a.dirs[0], a.match)
         return finish()
 
     import torch

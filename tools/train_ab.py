@@ -1,6 +1,11 @@
-"""What the A/B tools of the training ops (bench_head_loss.py, bench_train_activation.py, bench_train_dwconv.py) do the same way: the report that is printed and
-kept for --out, the timing of paths that take turns, peak memory of one pass, and the set-up of one training step of a bench.py model.  torch is imported on use:
-the parts of the tools that only read traces need no device."""
+"""What the A/B tools of the training ops (bench_head_loss.py, bench_train_activation.py, bench_train_dwconv.py, bench_train_attention.py) do the same way: the report
+that is printed and kept for --out, the timing of paths that take turns, peak memory of one pass, the set-up of one training step of a bench.py model, and the two
+tables read from rocprofv3 kernel traces.  torch is imported on use: the parts of the tools that only read traces need no device."""
+import csv
+import glob
+import os
+import re
+import sys
 import time
 
 
@@ -99,3 +104,64 @@ class TrainStep:
             loss.backward()
             return loss.detach()
         return step
+
+
+def _rows(directory, suffix):
+    files = sorted(glob.glob(os.path.join(directory, "**", "*" + suffix), recursive=True))
+    if not files:
+        sys.exit("no *%s under %s" % (suffix, directory))
+    for f in files:
+        with open(f, newline="") as fh:
+            for r in csv.DictReader(fh):
+                yield r
+
+
+def _short(name, n=96):
+    name = re.sub(r"\s+", " ", name)
+    return name if len(name) <= n else name[:n - 3] + "..."
+
+
+def by_name(directory):
+    """kernel name -> (calls, total us) from a rocprofv3 --kernel-trace csv"""
+    out = {}
+    for r in _rows(directory, "kernel_trace.csv"):
+        c, t = out.get(r["Kernel_Name"], (0, 0.0))
+        out[r["Kernel_Name"]] = (c + 1, t + (int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    return out
+
+
+def trace_diff(say, dir_off, dir_on, steps, switch, share=0.002, calls_too=False):
+    """kernel time per step by kernel name in two traces of `steps` steps each, `switch` off -> on: the rows that move by at least `share` of the off step's kernel
+    time (calls_too: or whose call count differs), then the sums"""
+    off, on = by_name(dir_off), by_name(dir_on)
+    n = float(steps)
+    tot_off, tot_on = sum(t for _, t in off.values()) / n, sum(t for _, t in on.values()) / n
+    say("kernel time per training step by kernel name, %s switch off -> on (%d steps per trace; us per step; calls per step)" % (switch, steps))
+    say("%10s %8s %10s %8s %10s  %s" % ("off us", "calls", "on us", "calls", "on - off", "kernel"))
+    rows = []
+    for k in set(off) | set(on):
+        c0, t0 = off.get(k, (0, 0.0))
+        c1, t1 = on.get(k, (0, 0.0))
+        rows.append((t1 / n - t0 / n, t0 / n, c0 / n, t1 / n, c1 / n, k))
+    rows.sort()
+    gone = sum(-r[0] for r in rows if r[0] < 0)
+    came = sum(r[0] for r in rows if r[0] > 0)
+    for d, t0, c0, t1, c1, k in rows:
+        if abs(d) >= share * tot_off or (calls_too and c0 != c1):
+            say("%10.1f %8.1f %10.1f %8.1f %+10.1f  %s" % (t0, c0, t1, c1, d, _short(k)))
+    say("sum of all kernels: off %.1f us, on %.1f us per step; rows that shrank: -%.1f us (%.1f %% of the off step's kernel time), rows that grew: +%.1f us"
+        % (tot_off, tot_on, gone, 100.0 * gone / tot_off, came))
+
+
+def trace_kernels(say, directory, match):
+    """the dispatches of a trace whose kernel name matches, grouped by kernel name and grid"""
+    groups = {}
+    for r in _rows(directory, "kernel_trace.csv"):
+        if not re.search(match, r["Kernel_Name"]):
+            continue
+        wg = int(r["Workgroup_Size_X"]) * int(r["Workgroup_Size_Y"]) * int(r["Workgroup_Size_Z"])
+        key = (r["Kernel_Name"], "%dx%dx%d/%d" % (int(r["Grid_Size_X"]), int(r["Grid_Size_Y"]), int(r["Grid_Size_Z"]), wg))
+        groups.setdefault(key, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
+    say("%-18s %6s %9s %9s %9s  %s" % ("grid (threads)/wg", "calls", "avg us", "min us", "max us", "kernel"))
+    for (k, g), v in sorted(groups.items(), key=lambda kv: (kv[0][0], kv[0][1])):
+        say("%-18s %6d %9.1f %9.1f %9.1f  %s" % (g, len(v), sum(v) / len(v), min(v), max(v), _short(k)))
