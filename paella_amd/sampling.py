@@ -151,9 +151,28 @@ def _tail_req(lc, lu, rows, L, rows_per_sample, req, step, init_noise, t_next, o
     filtered stream tail, fed with that step's constant step / renoise-threshold tables (the words the scalar arguments carry otherwise)"""
     tabs = (None if lu is None else req.pairs[step], req.temps[step], req.seeds, rows_per_sample)
     if filt is not None:
-        _run_tail(lc, lu, rows, L, out, req=tabs, stream=(filt.step[step], filt.t_next[step], filt.active), init_noise=init_noise, filt=(filt.k, filt.mass))
+        _stream_draw(lc, lu, rows, L, out, tabs, filt.step[step], filt.t_next[step], filt.active, init_noise, (filt.k, filt.mass))
     else:
         _run_tail(lc, lu, rows, L, out, req=tabs, offset=step, init_noise=init_noise, t_next=t_next)
+
+
+def _stream_draw(lc, lu, rows, L, out, req, step, t_next, active, init_noise, filt, pin=None, conf=None, renoise=True):
+    """The tail sequences of the stream-table form, issued here for the request batch (`_sample_core`) and for the request stream's tick alike.  req=(pairs, temps,
+    seeds, rows_per_sample), step / t_next / active and filt=(filter_k, filter_mass) are DEVICE tables, pin=(keep, known, pin_on).  conf=None: the filtered stream
+    tail, the pin riding in it.  conf=(never, policy, noise, logprob, entropy): the statistics tail in the stream form, never renoising (threshold table `never` =
+    -1) and unpinned, then -- unless renoise=False: a step of a request batch past its renoising ones -- the renoise stage with the real thresholds `t_next`,
+    every sample by its own policy, which also applies the pin (`out` in place)."""
+    if conf is None:
+        _run_tail(lc, lu, rows, L, out, req=req, stream=(step, t_next, active), init_noise=init_noise, pin=pin, filt=filt)
+        return
+    never, policy, noise, logprob, entropy = conf
+    _run_tail(lc, lu, rows, L, out, req=req, stream=(step, never, active), init_noise=init_noise, filt=filt, stats=(logprob, entropy))
+    if renoise:
+        pk, pt, po = (None, None, None) if pin is None else pin
+        with torch.cuda.device(out.device):
+            _lib.check(_lib.load().paella_renoise_select_stream(_lib.ptr(out), _lib.ptr(logprob), _lib.ptr(init_noise), rows, req[3], _lib.ptr(req[2]), _lib.ptr(step),
+                                                                _lib.ptr(t_next), _lib.ptr(active), _lib.ptr(policy), _lib.ptr(noise), _lib.ptr(pk), _lib.ptr(pt),
+                                                                _lib.ptr(po), _lib.ptr(out), _lib.stream_ptr(out.device)))
 
 
 def fresh_seed():
@@ -199,6 +218,28 @@ def start_tokens_requests(num_labels, shape, seeds_dev, out=None):
     return out
 
 
+def _per_request(v, B, message, one=None, seq=(list, tuple)):
+    """an argument that is one value for all requests or a sequence of B, as a list of B.  one(v): is v a single value (default: anything that is no `seq`);
+    message(v): the caller's text for anything else"""
+    if one(v) if one is not None else not isinstance(v, seq):
+        return [v] * B
+    if not isinstance(v, seq) or len(v) != B:
+        raise ValueError(message(v))
+    return list(v)
+
+
+def _request_rows(B, check, **columns):
+    """[check(request b's values) for every b], each keyword one value for all requests or a list of B; an error names the argument and the request"""
+    cols = [_per_request(v, B, lambda v, name=name: "%s must be one value or a list of %d (one per request), got %d" % (name, B, len(v))) for name, v in columns.items()]
+    rows = []
+    for b, values in enumerate(zip(*cols)):
+        try:
+            rows.append(check(*values))
+        except ValueError as e:
+            raise ValueError("request %d: %s" % (b, e)) from None
+    return rows
+
+
 def request_tables(B, steps, seeds, cfg, temperature):
     """HOST tables of a request batch, validated before anything touches a device:
         seeds int64 [B] (bit patterns, `seed_word`), temps fp32 [steps, B], pairs fp32 [steps, B, 2] or None (cfg=None: no guidance for anyone).
@@ -216,12 +257,10 @@ def request_tables(B, steps, seeds, cfg, temperature):
     seed_t = torch.tensor([seed_word(int(v)) for v in seeds], dtype=torch.int64)
     is_num = lambda v: isinstance(v, (int, float)) and not isinstance(v, bool)
     is_pair = lambda v: isinstance(v, (list, tuple)) and len(v) == 2 and all(is_num(x) for x in v)
-    if is_pair(temperature):
-        t_pairs = [temperature] * B
-    elif isinstance(temperature, (list, tuple)) and len(temperature) == B and all(is_pair(v) for v in temperature):
-        t_pairs = list(temperature)
-    else:
-        raise ValueError("temperature must be one (start, end) pair or a list of %d such pairs" % B)
+    t_message = lambda v: "temperature must be one (start, end) pair or a list of %d such pairs" % B
+    t_pairs = _per_request(temperature, B, t_message, one=is_pair)
+    if not all(is_pair(v) for v in t_pairs):
+        raise ValueError(t_message(temperature))
     temps = torch.tensor([linspace_schedule(float(a), float(b), steps) for a, b in t_pairs], dtype=torch.float32).t().contiguous()
     if not bool((temps > 0).all()):
         raise ValueError("every step temperature of a request batch must be > 0 (temperature 0, the argmax extension, is not offered per request)")
@@ -229,14 +268,8 @@ def request_tables(B, steps, seeds, cfg, temperature):
         return seed_t, temps, None
     if isinstance(cfg, tuple):
         raise TypeError("cfg must be None, a float or a LIST with one entry per request (a float or a (start, end) tuple each); a bare tuple is ambiguous")
-    if is_num(cfg):
-        entries = [cfg] * B
-    elif isinstance(cfg, list) and len(cfg) == B:
-        entries = cfg
-    else:
-        raise ValueError("cfg must be None, a float or a list of %d entries" % B)
     rows = []
-    for e in entries:
+    for e in _per_request(cfg, B, lambda v: "cfg must be None, a float or a list of %d entries" % B, one=is_num, seq=list):
         if e is None:
             raise ValueError("guidance is on for every request of a batch or for none: cfg=None cannot be mixed with guided requests (pass 1.0 for 'no guidance')")
         if is_num(e):
@@ -300,24 +333,18 @@ def _filter_names(top_k, top_p, typical_mass):
     return " / ".join(n for n, v in (("top_k", top_k), ("top_p", top_p), ("typical_mass", typical_mass)) if v is not None) or "top_k / top_p / typical_mass"
 
 
+def _philox_only(names, why, noise, temperatures):
+    """the two refusals of a whole call's filter and renoise settings: every call that can carry one passes `_call_filter` / `_call_renoise` on its way to `_sample_core`"""
+    if noise != "philox":
+        raise ValueError("%s needs noise='philox' (the counter-based sampling tail %s)" % (names, why))
+    if any(t == 0 for t in temperatures):
+        raise ValueError("%s is not offered with a step temperature of 0 (the argmax extension)" % names)
+
+
 def request_filters(B, top_k=None, top_p=None, typical_mass=None, min_tokens=1):
     """HOST tables of a request batch's filters: each argument one value for all requests or a list of B -> (k int32 [B, 2] = (top_k, min_tokens), mass fp32 [B, 2]
     = (top_p, typical_mass), any_on); every row validated by `check_filter` (the message names the argument and the request)."""
-    B = int(B)
-    cols = []
-    for name, v in (("top_k", top_k), ("top_p", top_p), ("typical_mass", typical_mass), ("min_tokens", min_tokens)):
-        if isinstance(v, (list, tuple)):
-            if len(v) != B:
-                raise ValueError("%s must be one value or a list of %d (one per request), got %d" % (name, B, len(v)))
-            cols.append(list(v))
-        else:
-            cols.append([v] * B)
-    rows = []
-    for b in range(B):
-        try:
-            rows.append(check_filter(cols[0][b], cols[1][b], cols[2][b], cols[3][b]))
-        except ValueError as e:
-            raise ValueError("request %d: %s" % (b, e)) from None
+    rows = _request_rows(int(B), check_filter, top_k=top_k, top_p=top_p, typical_mass=typical_mass, min_tokens=min_tokens)
     k = torch.tensor([[r[0], r[3]] for r in rows], dtype=torch.int32)
     mass = torch.tensor([[r[1], r[2]] for r in rows], dtype=torch.float32)
     return k, mass, any(filter_on(r) for r in rows)
@@ -363,32 +390,14 @@ def _call_renoise(noise, temperatures, renoise, confidence_noise, return_stats):
     policy, g = check_renoise(renoise, confidence_noise)
     if policy == 0 and not return_stats:
         return None
-    names = "renoise='confidence'" if policy else "return_stats"
-    if noise != "philox":
-        raise ValueError("%s needs noise='philox' (the counter-based sampling tail reports the statistics the selection ranks)" % names)
-    if any(t == 0 for t in temperatures):
-        raise ValueError("%s is not offered with a step temperature of 0 (the argmax extension)" % names)
+    _philox_only("renoise='confidence'" if policy else "return_stats", "reports the statistics the selection ranks", noise, temperatures)
     return policy, g, bool(return_stats)
 
 
 def request_renoise(B, renoise="random", confidence_noise=0.0):
     """HOST tables of a request batch's renoise settings: each argument one value for all requests or a list of B -> (policy int32 [B], confidence_noise fp32 [B],
     any_confidence); every entry validated by `check_renoise` (the message names the argument and the request)."""
-    B = int(B)
-    cols = []
-    for name, v in (("renoise", renoise), ("confidence_noise", confidence_noise)):
-        if isinstance(v, (list, tuple)):
-            if len(v) != B:
-                raise ValueError("%s must be one value or a list of %d (one per request), got %d" % (name, B, len(v)))
-            cols.append(list(v))
-        else:
-            cols.append([v] * B)
-    rows = []
-    for b in range(B):
-        try:
-            rows.append(check_renoise(cols[0][b], cols[1][b]))
-        except ValueError as e:
-            raise ValueError("request %d: %s" % (b, e)) from None
+    rows = _request_rows(int(B), check_renoise, renoise=renoise, confidence_noise=confidence_noise)
     return torch.tensor([r[0] for r in rows], dtype=torch.int32), torch.tensor([r[1] for r in rows], dtype=torch.float32), any(r[0] for r in rows)
 
 
@@ -526,178 +535,184 @@ def _sample_core(model, model_inputs, unconditional_inputs, latent_shape, init_x
     `ConfidenceTables` (then `filt` carries the stream tables).  Every step is then the logits forward, the statistics tail (the filtered tail's draw plus log p(token)
     and the row entropy, no renoise) and, on a renoising step, the renoise stage; `fused_tail` is ignored.  With return_stats the result is (tokens, {"logprob",
     "entropy"}), fp32 [B, H, W] maps of the final step's draw."""
+    device = torch.device(device)
+    B, H, W = shape = tuple(int(v) for v in latent_shape)
+    L = model.num_labels
+    native = isinstance(model, Paella)
+    _refuse_core_args(noise, device, native, shape, temperatures[:steps], init_x, shard, req, pin)
+    philox = noise == "philox"
+    if seed is None:
+        # GraphSampler keeps the live seed in device memory; without the counter-based generator it is unused: every random number comes from torch's generator
+        # or from explicit tensors
+        seed = fresh_seed() if philox and seed_dev is None else 0
+    row_offset = 0 if shard is None else int(shard[0]) * H * W
+    with torch.inference_mode():
+        init_noise = _start_noise(noise, L, shape, seed, device, shard, req, init_noise_buf, seed_dev, row_offset_dev)
+        sampled = init_noise.clone() if init_x is None else init_x.to(device=device, dtype=torch.int64).contiguous()
+        cond_c, cond_u, cond_both, batched = _prepare_conditioning(model, model_inputs, unconditional_inputs, B, cfgs, philox, ws) if native else (None, None, None, False)
+        bufs = {}  # logits buffers exist only for steps that take the unfused path (allocated on first use: 8.6 GB each at BASELINE configs[2])
+        out = torch.empty(B, H, W, dtype=torch.int64, device=device)
+        if r_all is None:
+            r_all = timestep_table(t_list, steps, B, device)
+        fuse = philox and native and fused_tail and filt is None and conf is None  # head GEMM + tail in one launch: no logits tensor at all (a filter needs the whole row)
+        stats = None if conf is None else tuple(torch.empty(B, H, W, dtype=torch.float32, device=device) for _ in range(2))  # (logprob, entropy)
+        for i in range(steps):
+            cfg, temp = cfgs[i], temperatures[i]  # cfg None: no guidance at this step; temp 0: argmax
+            t_next = t_list[i + 1] if i < renoise_steps else None  # None: this step does not renoise
+            if fuse and (cfg is None or (batched and temp != 0)):
+                # in place is safe: the token gather at the head of the forward and the token store at its tail are different kernels
+                # of one stream
+                model.forward_sample(sampled, r_all[i], cond_c if cfg is None else cond_both, out, temperature=temp if temp != 0 else 1.0, argmax=temp == 0,
+                                     seed=seed, seed_dev=seed_dev, offset=i, row_offset=row_offset, row_offset_dev=row_offset_dev,
+                                     init_noise=None if t_next is None else init_noise, t_next=0.0 if t_next is None else t_next,
+                                     cfg_mix=cfg if req is None else None, attn_weights=attn_weights, ws=ws,
+                                     req=None if req is None else req.step(i), **({} if pin is None else {"pin": pin}))
+            else:
+                lc, lu = _step_logits(model, sampled, r_all[i], i, cfg, philox and temp != 0, (cond_c, cond_u, cond_both, batched), bufs,
+                                      (model_inputs, unconditional_inputs), attn_weights, ws, req)
+                noise_q, mask_u = _step_noise(noise, i, shape, L, device, temp != 0, t_next is not None)
+                _draw(lc, lu, out, i, temp, cfg, t_next, init_noise, (seed, seed_dev, row_offset, row_offset_dev), noise_q, mask_u, req, pin, filt, conf, stats)
+            sampled = out  # no tail reads `sampled`, so one output buffer is enough (stream-ordered reuse)
+    if conf is not None and req is None and conf[2]:
+        return sampled, {"logprob": stats[0], "entropy": stats[1]}
+    return sampled
+
+
+def _refuse_core_args(noise, device, native, shape, temperatures, init_x, shard, req, pin):
+    """what `_sample_core` refuses, before anything touches the device (the library is loaded on the way).  `filt` and `conf` are not looked at: a whole call's
+    settings were checked against the noise mode and the temperatures where they were built (`_philox_only`), the tables of a request batch need neither check."""
     explicit = isinstance(noise, dict)  # parity tests: {"init_noise": [B,H,W], "q": [rows,L] per step, "u": [B,H,W] per step}
     if not explicit and noise not in ("torch", "philox"):
         raise ValueError("noise must be 'torch', 'philox' or a dict of explicit noise tensors")
-    device = torch.device(device)
     if device.type != "cuda":
         raise RuntimeError("paella_amd.sample runs on a HIP device only (got device=%s); there is no CPU path" % device)
     _lib.load()
-    B, H, W = (int(v) for v in latent_shape)
-    L = model.num_labels
-    rows = B * H * W
-    native = isinstance(model, Paella)
-    philox = (not explicit) and noise == "philox"
-    if philox and seed is None:
-        seed = 0 if seed_dev is not None else fresh_seed()  # GraphSampler keeps the live seed in device memory
-    if seed is None:
-        seed = 0  # unused: every random number comes from torch's generator or from explicit tensors
+    philox = noise == "philox"
     if shard is not None and not (philox or explicit):
         raise ValueError("shard=(lo, total) needs noise='philox' (or explicit noise tensors): torch's generator stream cannot be sharded")
-    row_offset = 0 if shard is None else int(shard[0]) * H * W
     if req is not None and not (philox and native and shard is None and init_x is None):
         raise ValueError("a request batch needs noise='philox', a paella_amd.Paella model, no shard and no init_x")
     if pin is not None:
         if not philox or req is not None:
             raise ValueError("pin=(keep, known) needs noise='philox' (the counter-based sampling tail re-imposes the known tokens) and no request tables")
-        if any(t == 0 for t in temperatures[:steps]):
+        if any(t == 0 for t in temperatures):
             raise ValueError("pin=(keep, known) is not offered with a step temperature of 0 (the argmax extension)")
         for name, t in zip(("keep", "known"), pin):
-            if not torch.is_tensor(t) or t.dtype != torch.int64 or tuple(t.shape) != (B, H, W) or t.device.type != "cuda" or not t.is_contiguous():
-                raise ValueError("pin: %s must be a contiguous int64 HIP tensor of shape %s" % (name, (B, H, W)))
-    if filt is not None:
-        if not philox:
-            raise ValueError("top_k / top_p / typical_mass need noise='philox' (the counter-based sampling tail filters the draw)")
-        if any(t == 0 for t in temperatures[:steps]):
-            raise ValueError("top_k / top_p / typical_mass are not offered with a step temperature of 0 (the argmax extension)")
-        if isinstance(filt, FilterTables) != (req is not None):
-            raise ValueError("filt: one check_filter tuple for a plain call, a FilterTables with request tables")
-    if conf is not None:
-        if not philox:
-            raise ValueError("renoise='confidence' / return_stats need noise='philox' (the counter-based sampling tail reports the statistics)")
-        if any(t == 0 for t in temperatures[:steps]):
-            raise ValueError("renoise='confidence' / return_stats are not offered with a step temperature of 0 (the argmax extension)")
-        if isinstance(conf, ConfidenceTables) != (req is not None) or (req is not None and filt is None):
-            raise ValueError("conf: one (policy, confidence_noise, return_stats) tuple for a plain call, a ConfidenceTables next to a FilterTables with request tables")
-    with torch.inference_mode():
-        if req is not None:
-            init_noise = start_tokens_requests(L, (B, H, W), req.seeds, out=init_noise_buf)
-        elif init_noise_buf is not None and philox:
-            init_noise = start_tokens(L, (B, H, W), seed, device, shard, out=init_noise_buf, seed_dev=seed_dev, row_offset_dev=row_offset_dev)
-        elif init_noise_buf is not None:
-            init_noise = init_noise_buf
-        elif explicit:
-            init_noise = noise["init_noise"].to(device=device, dtype=torch.int64).contiguous()
-        elif philox:
-            init_noise = start_tokens(L, (B, H, W), seed, device, shard, seed_dev=seed_dev, row_offset_dev=row_offset_dev)
+            if not torch.is_tensor(t) or t.dtype != torch.int64 or tuple(t.shape) != shape or t.device.type != "cuda" or not t.is_contiguous():
+                raise ValueError("pin: %s must be a contiguous int64 HIP tensor of shape %s" % (name, shape))
+
+
+def _start_noise(noise, L, shape, seed, device, shard, req, buf, seed_dev, row_offset_dev):
+    """the start tokens of a call, which are also the renoise source of its steps; buf: where a captured graph keeps them (GraphSampler)"""
+    if req is not None:
+        return start_tokens_requests(L, shape, req.seeds, out=buf)
+    if noise == "philox":
+        return start_tokens(L, shape, seed, device, shard, out=buf, seed_dev=seed_dev, row_offset_dev=row_offset_dev)
+    if buf is not None:
+        return buf
+    if isinstance(noise, dict):
+        return noise["init_noise"].to(device=device, dtype=torch.int64).contiguous()
+    return torch.randint(0, L, size=shape, device=device)
+
+
+def _prepare_conditioning(model, model_inputs, unconditional_inputs, B, cfgs, philox, ws):
+    """the step-invariant conditioning work of a call -> (cond_c, cond_u, cond_both, batched): the prepared conditional and unconditional caches (None where no
+    step needs one), the 2B-slot cache that holds both, and whether guided steps run as ONE forward against it"""
+    any_cfg = any(c is not None for c in cfgs)
+    cond_c = cond_u = cond_both = None
+    if any_cfg and _same_cond_layout(model_inputs, unconditional_inputs):
+        cond_both = model.prepare_cond(**_cat_inputs(model_inputs, unconditional_inputs), ws=ws)
+    elif any_cfg and philox and _cond_batch(model_inputs) == B and _cond_batch(unconditional_inputs) == B \
+            and min(_cond_seq_len(model, model_inputs), _cond_seq_len(model, unconditional_inputs)) > 0:
+        # layouts differ (what conditioning.embed_prompts produces on real prompts): one ragged 2B-slot cache, every sample bounded by its own row count
+        # in the attention kernels -- the same one-forward path as above.  noise="torch" / explicit noise keep the two forwards: their tokens are pinned
+        # to the reference's, whose rounding is that of two separate evaluations
+        cond_both = _prepare_ragged_pair(model, model_inputs, unconditional_inputs, B, ws)
+    batched = cond_both is not None
+    if not batched or not all(c is not None for c in cfgs):
+        cond_c = model.prepare_cond(**model_inputs, ws=ws)
+        cond_u = model.prepare_cond(**unconditional_inputs, ws=ws) if any_cfg and not batched else None
+    return cond_c, cond_u, cond_both, batched
+
+
+def _step_logits(model, sampled, r, i, cfg, fold, conds, bufs, inputs, attn_weights, ws, req):
+    """the logits forward of ONE unfused step -> (lc, lu), fp32 [B, H, W, L] each; lu None: the step is unguided or its guidance mix is already in lc.
+    conds: what `_prepare_conditioning` returned; bufs: the call's logits buffers by name, allocated here on first use; inputs: the two conditioning dicts"""
+    cond_c, cond_u, cond_both, batched = conds
+    B, H, W = sampled.shape
+
+    def logits_buf(name, rows_b):
+        if name not in bufs:
+            bufs[name] = torch.empty(rows_b, H, W, model.num_labels, dtype=torch.float32, device=sampled.device)
+        return bufs[name]
+    if not isinstance(model, Paella):  # any other callable with the reference's signature; logits come back [B, L, H, W]
+        lc = model(sampled, r, **inputs[0]).permute(0, 2, 3, 1).float().contiguous()
+        return lc, (model(sampled, r, **inputs[1]).permute(0, 2, 3, 1).float().contiguous() if cfg is not None else None)
+    if cfg is not None and batched:
+        # one evaluation against the 2B-row conditioning cache: tokens / r are passed once, the library computes
+        # the conditioning-free prefix for them and replicates it where the two passes diverge.  With the
+        # counter-based generator (no bit-parity promise towards torch's RNG stream) a categorical step (`fold`) also lets
+        # the guidance mix ride through the linear head: one mixed logits tensor comes back.
+        logits2 = logits_buf("both", 2 * B)
+        model.forward_prepared(sampled, r, cond_both, attn_weights=attn_weights, out=logits2[:B] if fold else logits2,
+                               cfg_mix=cfg if fold and req is None else None, ws=ws, **({} if req is None else {"req_mix": req.pairs[i]}))
+        return logits2[:B], (None if fold else logits2[B:])
+    lc, lu = logits_buf("c", B), None
+    model.forward_prepared(sampled, r, cond_c, attn_weights=attn_weights, out=lc, ws=ws)
+    if cfg is not None:
+        lu = logits_buf("u", B)
+        model.forward_prepared(sampled, r, cond_u, attn_weights=attn_weights, out=lu, ws=ws)
+    return lc, lu
+
+
+def _step_noise(noise, i, shape, L, device, categorical, renoise):
+    """the noise tensors of ONE unfused step that the tail does not generate itself -> (noise_q, mask_u), both None with noise="philox"; drawn in the reference's order"""
+    if noise == "philox":
+        return None, None
+    if isinstance(noise, dict):
+        given = lambda t: t.to(device=device, dtype=torch.float32).contiguous()
+        return given(noise["q"][i]) if categorical else None, given(noise["u"][i]) if renoise else None
+    B, H, W = shape
+    rows = B * H * W
+    noise_q = mask_u = None
+    if categorical:
+        # what torch.multinomial(scores, 1) draws internally: q = empty_like(scores).exponential_(1)
+        # in the memory order of the reference's `scores.permute(0,2,3,1).reshape(-1, L)`: row-major copy for
+        # B > 1, but a column-major VIEW of the NCHW softmax output for B == 1
+        if B == 1:
+            noise_q = torch.empty(L, rows, dtype=torch.float32, device=device).exponential_(1).t().contiguous()
         else:
-            init_noise = torch.randint(0, L, size=(B, H, W), device=device)
-        sampled = init_noise.clone() if init_x is None else init_x.to(device=device, dtype=torch.int64).contiguous()
-        any_cfg = any(c is not None for c in cfgs)
-        batched = False
-        if native:
-            if any_cfg and _same_cond_layout(model_inputs, unconditional_inputs):
-                cond_both = model.prepare_cond(**_cat_inputs(model_inputs, unconditional_inputs), ws=ws)
-                batched = True
-            elif any_cfg and philox and _cond_batch(model_inputs) == B and _cond_batch(unconditional_inputs) == B \
-                    and min(_cond_seq_len(model, model_inputs), _cond_seq_len(model, unconditional_inputs)) > 0:
-                # layouts differ (what conditioning.embed_prompts produces on real prompts): one ragged 2B-slot cache, every sample bounded by its own row count
-                # in the attention kernels -- the same one-forward path as above.  noise="torch" / explicit noise keep the two forwards: their tokens are pinned
-                # to the reference's, whose rounding is that of two separate evaluations
-                cond_both = _prepare_ragged_pair(model, model_inputs, unconditional_inputs, B, ws)
-                batched = True
-            if not batched or not all(c is not None for c in cfgs):
-                cond_c = model.prepare_cond(**model_inputs, ws=ws)
-                cond_u = model.prepare_cond(**unconditional_inputs, ws=ws) if any_cfg and not batched else None
-        # logits buffers exist only for steps that take the unfused path (allocated on first use: 8.6 GB each at BASELINE configs[2])
-        bufs = {}
-        def logits_buf(name, rows_b):
-            if name not in bufs:
-                bufs[name] = torch.empty(rows_b, H, W, L, dtype=torch.float32, device=device)
-            return bufs[name]
-        out = torch.empty(B, H, W, dtype=torch.int64, device=device)
-        if r_all is None:
-            r_all = timestep_table(t_list, steps, B, device)
-        fuse = philox and native and fused_tail and filt is None and conf is None  # head GEMM + tail in one launch: no logits tensor at all (a filter needs the whole row)
-        logprob = entropy = None
-        if conf is not None:
-            logprob, entropy = (torch.empty(B, H, W, dtype=torch.float32, device=device) for _ in range(2))
-        for i in range(steps):
-            r = r_all[i]
-            use_cfg = cfgs[i] is not None
-            temp = temperatures[i]
-            mode = 1 if temp == 0 else 0
-            renoise = i < renoise_steps
-            if fuse and ((use_cfg and batched and mode == 0) or not use_cfg):
-                # in place is safe: the token gather at the head of the forward and the token store at its tail are different kernels
-                # of one stream
-                model.forward_sample(sampled, r, cond_both if use_cfg else cond_c, out, temperature=temp if mode == 0 else 1.0, argmax=mode == 1,
-                                     seed=seed, seed_dev=seed_dev, offset=i, row_offset=row_offset, row_offset_dev=row_offset_dev,
-                                     init_noise=init_noise if renoise else None,
-                                     t_next=t_list[i + 1] if renoise else 0.0, cfg_mix=cfgs[i] if use_cfg and req is None else None, attn_weights=attn_weights, ws=ws,
-                                     req=None if req is None else req.step(i), **({} if pin is None else {"pin": pin}))
-                sampled = out
-                continue
-            if native:
-                if use_cfg and batched:
-                    # one evaluation against the 2B-row conditioning cache: tokens / r are passed once, the library computes
-                    # the conditioning-free prefix for them and replicates it where the two passes diverge.  With the
-                    # counter-based generator (no bit-parity promise towards torch's RNG stream) a categorical step also lets
-                    # the guidance mix ride through the linear head: one mixed logits tensor comes back.
-                    fold = philox and mode == 0
-                    logits2 = logits_buf("both", 2 * B)
-                    model.forward_prepared(sampled, r, cond_both, attn_weights=attn_weights, out=logits2[:B] if fold else logits2,
-                                           cfg_mix=cfgs[i] if fold and req is None else None, ws=ws, **({} if req is None else {"req_mix": req.pairs[i]}))
-                    lc, lu = logits2[:B], (None if fold else logits2[B:])
-                else:
-                    lc, lu = logits_buf("c", B), None
-                    model.forward_prepared(sampled, r, cond_c, attn_weights=attn_weights, out=lc, ws=ws)
-                    if use_cfg:
-                        lu = logits_buf("u", B)
-                        model.forward_prepared(sampled, r, cond_u, attn_weights=attn_weights, out=lu, ws=ws)
-            else:  # any other callable with the reference's signature; logits come back [B, L, H, W]
-                lc = model(sampled, r, **model_inputs).permute(0, 2, 3, 1).float().contiguous()
-                lu = model(sampled, r, **unconditional_inputs).permute(0, 2, 3, 1).float().contiguous() if use_cfg else None
-            noise_q = None
-            if explicit and mode == 0:
-                noise_q = noise["q"][i].to(device=device, dtype=torch.float32).contiguous()
-            elif noise == "torch" and mode == 0:
-                # what torch.multinomial(scores, 1) draws internally: q = empty_like(scores).exponential_(1)
-                # in the memory order of the reference's `scores.permute(0,2,3,1).reshape(-1, L)`: row-major copy for
-                # B > 1, but a column-major VIEW of the NCHW softmax output for B == 1
-                if B == 1:
-                    noise_q = torch.empty(L, rows, dtype=torch.float32, device=device).exponential_(1).t().contiguous()
-                else:
-                    noise_q = torch.empty(rows, L, dtype=torch.float32, device=device).exponential_(1)
-            mask_u = None
-            if renoise and explicit:
-                mask_u = noise["u"][i].to(device=device, dtype=torch.float32).contiguous()
-            elif renoise and noise == "torch":
-                mask_u = torch.rand(B, H, W, dtype=torch.float32, device=device)  # == torch.rand_like(x.float())
-            if conf is not None and req is not None:
-                # the statistics tail in the stream form, never renoising (threshold table -1), then the renoise stage with the step's real thresholds
-                _run_tail(lc, lu, rows, L, out, req=(None if lu is None else req.pairs[i], req.temps[i], req.seeds, H * W), stream=(filt.step[i], conf.never, filt.active),
-                          init_noise=init_noise, filt=(filt.k, filt.mass), stats=(logprob, entropy))
-                with torch.cuda.device(device):
-                    if renoise:
-                        _lib.check(_lib.load().paella_renoise_select_stream(_lib.ptr(out), _lib.ptr(logprob), _lib.ptr(init_noise), rows, H * W, _lib.ptr(req.seeds),
-                                                                            _lib.ptr(filt.step[i]), _lib.ptr(filt.t_next[i]), _lib.ptr(filt.active), _lib.ptr(conf.policy),
-                                                                            _lib.ptr(conf.noise), None, None, None, _lib.ptr(out), _lib.stream_ptr(device)))
-                sampled = out
-                continue
-            if conf is not None:
-                # a renoising step: the raw draw and its statistics, then the renoise stage (which also applies the pin); the last steps: the pin rides in the tail
-                cfg, omc = cfgs[i] if use_cfg else (1.0, 0.0)
-                _run_tail(lc, lu, rows, L, out, scalar=(cfg, omc, temp, 0, seed, seed_dev, row_offset, row_offset_dev, None, None), offset=i, pin=None if renoise else pin,
-                          filt=FILTER_OFF if filt is None else filt, stats=(logprob, entropy))
-                if renoise:
-                    _renoise_stage(out, logprob, init_noise, rows, H * W, seed, i, t_list[i + 1], conf[0], conf[1], out, seed_dev=seed_dev, row_offset=row_offset,
-                                   row_offset_dev=row_offset_dev, pin=pin)
-                sampled = out
-                continue
-            if req is not None:
-                # (the stream form of the filtered tail wants its renoise source at every step; a step that does not renoise -- threshold -1 -- never reads it)
-                _tail_req(lc, lu, rows, L, H * W, req, i, init_noise if renoise or filt is not None else None, t_list[i + 1] if renoise else 0.0, out, filt=filt)
-                sampled = out
-                continue
-            cfg, omc = cfgs[i] if use_cfg else (1.0, 0.0)
-            _tail(lc, lu, rows, L, cfg, omc, temp if mode == 0 else 1.0, mode, noise_q, seed, i,
-                  init_noise if renoise else None, mask_u, t_list[i + 1] if renoise else 0.0, out, seed_dev=seed_dev,
-                  row_offset=row_offset, row_offset_dev=row_offset_dev, pin=pin, filt=filt)
-            sampled = out  # the tail never reads `sampled`, so one output buffer is enough (stream-ordered reuse)
-    if conf is not None and req is None and conf[2]:
-        return sampled, {"logprob": logprob, "entropy": entropy}
-    return sampled
+            noise_q = torch.empty(rows, L, dtype=torch.float32, device=device).exponential_(1)
+    if renoise:
+        mask_u = torch.rand(B, H, W, dtype=torch.float32, device=device)  # == torch.rand_like(x.float())
+    return noise_q, mask_u
+
+
+def _draw(lc, lu, out, i, temp, cfg, t_next, init_noise, words, noise_q, mask_u, req, pin, filt, conf, stats):
+    """The tail launches of ONE unfused step on its logits, in the one of the four tail forms the call has: scalar (`_tail`); scalar with statistics, then
+    `_renoise_stage` (conf a tuple); request (`_tail_req`); request with statistics, then the stream form of the renoise stage (conf a ConfidenceTables).
+    t_next None: the step does not renoise; words = (seed, seed_dev, row_offset, row_offset_dev); stats = (logprob, entropy) with conf."""
+    rows, L = out.numel(), lc.size(-1)
+    hw = rows // out.size(0)
+    renoise = t_next is not None
+    seed, seed_dev, row_offset, row_offset_dev = words
+    cfg, omc = (1.0, 0.0) if cfg is None else cfg
+    if conf is not None and req is not None:
+        _stream_draw(lc, lu, rows, L, out, (None if lu is None else req.pairs[i], req.temps[i], req.seeds, hw), filt.step[i], filt.t_next[i] if renoise else None,
+                     filt.active, init_noise, (filt.k, filt.mass), conf=(conf.never, conf.policy, conf.noise, *stats), renoise=renoise)
+    elif conf is not None:
+        # a renoising step: the raw draw and its statistics, then the renoise stage (which also applies the pin); the last steps: the pin rides in the tail
+        _run_tail(lc, lu, rows, L, out, scalar=(cfg, omc, temp, 0, seed, seed_dev, row_offset, row_offset_dev, None, None), offset=i, pin=None if renoise else pin,
+                  filt=FILTER_OFF if filt is None else filt, stats=stats)
+        if renoise:
+            _renoise_stage(out, stats[0], init_noise, rows, hw, seed, i, t_next, conf[0], conf[1], out, seed_dev=seed_dev, row_offset=row_offset,
+                           row_offset_dev=row_offset_dev, pin=pin)
+    elif req is not None:
+        # (the stream form of the filtered tail wants its renoise source at every step; a step that does not renoise -- threshold -1 -- never reads it)
+        _tail_req(lc, lu, rows, L, hw, req, i, init_noise if renoise or filt is not None else None, t_next if renoise else 0.0, out, filt=filt)
+    else:
+        _tail(lc, lu, rows, L, cfg, omc, temp if temp != 0 else 1.0, int(temp == 0), noise_q, seed, i, init_noise if renoise else None, mask_u,
+              t_next if renoise else 0.0, out, seed_dev=seed_dev, row_offset=row_offset, row_offset_dev=row_offset_dev, pin=pin, filt=filt)
 
 
 def _call_filter(noise, temperatures, top_k, top_p, typical_mass, min_tokens):
@@ -705,11 +720,7 @@ def _call_filter(noise, temperatures, top_k, top_p, typical_mass, min_tokens):
     f = check_filter(top_k, top_p, typical_mass, min_tokens)
     if not filter_on(f):
         return None
-    names = _filter_names(top_k, top_p, typical_mass)
-    if noise != "philox":
-        raise ValueError("%s needs noise='philox' (the counter-based sampling tail filters the draw)" % names)
-    if any(t == 0 for t in temperatures):
-        raise ValueError("%s is not offered with a step temperature of 0 (the argmax extension)" % names)
+    _philox_only(_filter_names(top_k, top_p, typical_mass), "filters the draw", noise, temperatures)
     return f
 
 
@@ -730,14 +741,7 @@ def sample(model, model_inputs, latent_shape, unconditional_inputs=None, steps=1
     if cfg and unconditional_inputs is None:
         # the reference raises TypeError at src/utils.py:46 (`**None`); keep the failure, make it readable
         raise TypeError("cfg=%r requires unconditional_inputs" % (cfg,))
-    t_list = linspace_schedule(t_start, t_end, steps + 1)
-    temperatures = linspace_schedule(temperature[0], temperature[1], steps)
-    if cfg:
-        # `logits * cfg + logits_u * (1 - cfg)` with python-float cfg: both scalars are rounded to fp32 by torch
-        pair = (float(torch.tensor(float(cfg), dtype=torch.float32)), float(torch.tensor(1.0 - float(cfg), dtype=torch.float32)))
-        cfgs = [pair] * steps
-    else:
-        cfgs = [None] * steps
+    t_list, temperatures, cfgs = _scalar_schedule(steps, temperature, cfg, t_start, t_end)
     return _sample_core(model, model_inputs, unconditional_inputs, latent_shape, None, steps, renoise_steps, t_list, temperatures,
                         cfgs, device, noise=noise, seed=seed, seed_dev=seed_dev, attn_weights=attn_weights, shard=shard, fused_tail=fused_tail,
                         filt=_call_filter(noise, temperatures, top_k, top_p, typical_mass, min_tokens),
@@ -770,6 +774,15 @@ def sample_distributed(model, model_inputs, unconditional_inputs, latent_shape, 
                         cfgs, device, noise=noise, seed=seed, attn_weights=attn_weights, shard=shard, fused_tail=fused_tail, pin=pin,
                         filt=_call_filter(noise, temperatures, top_k, top_p, typical_mass, min_tokens),
                         conf=_call_renoise(noise, temperatures, renoise, confidence_noise, return_stats))
+
+
+def _scalar_schedule(steps, temperature, cfg, t_start, t_end):
+    """(t_list, temperatures, per-step guidance pairs) of the src/utils.py:35 signature, for `sample` and for the capture of it (GraphSampler)"""
+    pair = None
+    if cfg:
+        # `logits * cfg + logits_u * (1 - cfg)` with python-float cfg: both scalars are rounded to fp32 by torch
+        pair = (float(torch.tensor(float(cfg), dtype=torch.float32)), float(torch.tensor(1.0 - float(cfg), dtype=torch.float32)))
+    return linspace_schedule(t_start, t_end, steps + 1), linspace_schedule(temperature[0], temperature[1], steps), [pair] * steps
 
 
 def _request_schedule(steps, t_start, t_end, guided):
@@ -819,6 +832,27 @@ def sample_requests(model, model_inputs, unconditional_inputs, latent_shape, see
                         attn_weights=attn_weights, fused_tail=fused_tail, req=RequestTables(host, device),
                         filt=FilterTables(fhost, device, steps, renoise_steps, t_list) if fhost[2] or chost[2] else None,
                         conf=ConfidenceTables(chost, device) if chost[2] else None)
+
+
+def _capture_graph(owner, run):
+    """run() captured into a HIP graph on owner.device -> what run() returned inside the capture; sets owner.graph and owner._captured_state, counts owner.captures"""
+    dev = owner.device
+    side = torch.cuda.Stream(device=dev)
+    side.wait_stream(torch.cuda.current_stream(dev))
+    with torch.cuda.stream(side):
+        for _ in range(2):  # warm-up: weights (re)loaded, workspaces sized, allocator pools populated
+            run()
+    torch.cuda.current_stream(dev).wait_stream(side)
+    torch.cuda.synchronize(dev)
+    state = owner._state()  # AFTER the warm-up: the engines are loaded with exactly these tensors
+    graph = torch.cuda.CUDAGraph()
+    # thread_local: a process-group watchdog thread polling events must not invalidate the capture
+    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+        out = run()
+    torch.cuda.synchronize(dev)
+    owner.graph, owner._captured_state = graph, state
+    owner.captures += 1
+    return out
 
 
 class GraphSampler:
@@ -880,33 +914,12 @@ class GraphSampler:
         self.graph = self.out = None
         self.ws = _lib.new_workspace(self.model.workspace_bytes(2 * B, H, W, S), self.device)
         self.vq_ws = None if self.vqgan is None else _lib.new_workspace(self.vqgan.workspace_bytes(B, H, W), self.device)
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side):
-            for _ in range(2):  # warm-up: weights (re)loaded, workspaces sized, allocator pools populated
-                self._run()
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        torch.cuda.synchronize(self.device)
-        state = self._state()  # AFTER the warm-up: the engines are loaded with exactly these tensors
-        graph = torch.cuda.CUDAGraph()
-        # thread_local: a process-group watchdog thread polling events must not invalidate the capture
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            out = self._run()
-        torch.cuda.synchronize(self.device)
-        self.graph, self.out, self._captured_state = graph, out, state
-        self.captures += 1
+        self.out = _capture_graph(self, self._run)
 
     def _schedule(self):
         """(t_list, temperatures, per-step guidance pairs) of the src/utils.py:35 signature"""
         k = self.kw
-        t_list = linspace_schedule(k["t_start"], k["t_end"], k["steps"] + 1)
-        temps = linspace_schedule(k["temperature"][0], k["temperature"][1], k["steps"])
-        if k["cfg"]:
-            pair = (float(torch.tensor(float(k["cfg"]), dtype=torch.float32)), float(torch.tensor(1.0 - float(k["cfg"]), dtype=torch.float32)))
-            cfgs = [pair] * k["steps"]
-        else:
-            cfgs = [None] * k["steps"]
-        return t_list, temps, cfgs
+        return _scalar_schedule(k["steps"], k["temperature"], k["cfg"], k["t_start"], k["t_end"])
 
     def _init_x(self):
         """tokens the loop starts from (None = the Philox start tokens); GraphInpainter encodes + renoises an image here"""
@@ -957,15 +970,26 @@ class GraphSampler:
                     raise ValueError("conditioning shape differs from the captured one (%s)" % key)
                 d.copy_(s)
 
+    def _stale(self):
+        """what the capture depends on and has changed since, by name (empty: the capture is fresh)"""
+        return [a[0] for a, b in zip(self._state(), self._captured_state) if a != b]
+
     def _check_fresh(self):
-        now = self._state()
-        if now == self._captured_state:
+        causes = self._stale()
+        if not causes:
             return
-        causes = [a[0] for a, b in zip(now, self._captured_state) if a != b]
         if self.on_stale == "raise":
             raise RuntimeError("GraphSampler: the captured graph is stale -- changed since the capture: %s (load_state_dict / optimizer step / .to() / set_gemm_precision). "
                                "Build a new GraphSampler or construct it with on_stale='recapture'." % ", ".join(causes))
         self._capture()
+
+    def _refresh(self, model_inputs, unconditional_inputs):
+        """what every replay starts with: a capture that matches the weights, then this call's conditioning in the graph's input buffers (None = keep)"""
+        self._check_fresh()
+        if model_inputs is not None:
+            self._copy_inputs(self.cond, model_inputs)
+        if unconditional_inputs is not None:
+            self._copy_inputs(self.uncond, unconditional_inputs)
 
     def _set_words(self, seed, shard):
         if seed is None:
@@ -983,11 +1007,7 @@ class GraphSampler:
         the next replay overwrites.  seed=None draws a fresh seed from torch's CPU generator; the start tokens and all per-step
         noise are functions of the seed and of the GLOBAL row: shard=(lo, total) makes this replay rows [lo, lo + B) of a
         global batch of `total` (bit-identical to those rows of the unsharded call with the same seed)."""
-        self._check_fresh()
-        if model_inputs is not None:
-            self._copy_inputs(self.cond, model_inputs)
-        if unconditional_inputs is not None:
-            self._copy_inputs(self.uncond, unconditional_inputs)
+        self._refresh(model_inputs, unconditional_inputs)
         self._set_words(seed, shard)
         self.graph.replay()
         return self.out
@@ -1050,11 +1070,7 @@ class GraphRequestSampler(GraphSampler):
             guided = self.req.pairs is not None
             _load_key_weights(self.key_weights, [request_weight_pair(shared)] * B if pairs is None else pairs,
                               _request_keys(self.model, H, W, self.cond, self.uncond if guided else None), guided, self.key_weights.pitch)
-        self._check_fresh()
-        if model_inputs is not None:
-            self._copy_inputs(self.cond, model_inputs)
-        if unconditional_inputs is not None:
-            self._copy_inputs(self.uncond, unconditional_inputs)
+        self._refresh(model_inputs, unconditional_inputs)
         self.req.load(host)
         if self.filt is not None:
             self.filt.load(fhost)
@@ -1328,39 +1344,28 @@ class RequestStream:
     # ---- one tick on the current stream: the launches the graph holds
     def _tick_launches(self):
         B = self.shape[0]
+        tables = (_lib.ptr(self.program), self.max_steps, _lib.ptr(self.pos), _lib.ptr(self.len), B, _lib.ptr(self.r), _lib.ptr(self.temps), _lib.ptr(self.pairs),
+                  _lib.ptr(self.t_next), _lib.ptr(self.step), _lib.ptr(self.active_dev))
         with torch.cuda.device(self.device):
             if self.editing:
-                _lib.check(_lib.load().paella_request_step_pin(_lib.ptr(self.program), self.max_steps, _lib.ptr(self.pos), _lib.ptr(self.len), B, _lib.ptr(self.r),
-                                                               _lib.ptr(self.temps), _lib.ptr(self.pairs), _lib.ptr(self.t_next), _lib.ptr(self.step),
-                                                               _lib.ptr(self.active_dev), _lib.ptr(self.pin_policy), _lib.ptr(self.pin_on), _lib.stream_ptr(self.device)))
+                _lib.check(_lib.load().paella_request_step_pin(*tables, _lib.ptr(self.pin_policy), _lib.ptr(self.pin_on), _lib.stream_ptr(self.device)))
             else:
-                _lib.check(_lib.load().paella_request_step(_lib.ptr(self.program), self.max_steps, _lib.ptr(self.pos), _lib.ptr(self.len), B, _lib.ptr(self.r),
-                                                           _lib.ptr(self.temps), _lib.ptr(self.pairs), _lib.ptr(self.t_next), _lib.ptr(self.step),
-                                                           _lib.ptr(self.active_dev), _lib.stream_ptr(self.device)))
-        if self.confidence:  # the logits forward + the statistics tail (raw draw, no pin) + the renoise stage (every slot's own policy, then the pin), in place
-            self.model.forward_prepared(self.tokens, self.r, self.cache, attn_weights=self.attn_weights, out=self.logits, ws=self.ws,
-                                        **({} if self.pairs is None else {"req_mix": self.pairs}), **({} if self.regions is None else {"regions": self.regions}))
-            pk, pt, po = (self.keep, self.known, self.pin_on) if self.editing else (None, None, None)
-            rows, hw = B * self.shape[1] * self.shape[2], self.shape[1] * self.shape[2]
-            _run_tail(self.logits, None, rows, self.model.num_labels, self.tokens, req=(None, self.temps, self.seeds, hw), stream=(self.step, self._never, self.active_dev),
-                      init_noise=self.random_x, filt=(self.filter_k, self.filter_mass), stats=(self.logprob, self.entropy))
-            with torch.cuda.device(self.device):
-                _lib.check(_lib.load().paella_renoise_select_stream(_lib.ptr(self.tokens), _lib.ptr(self.logprob), _lib.ptr(self.random_x), rows, hw, _lib.ptr(self.seeds),
-                                                                    _lib.ptr(self.step), _lib.ptr(self.t_next), _lib.ptr(self.active_dev), _lib.ptr(self.policy),
-                                                                    _lib.ptr(self.confidence_noise), _lib.ptr(pk), _lib.ptr(pt), _lib.ptr(po), _lib.ptr(self.tokens),
-                                                                    _lib.stream_ptr(self.device)))
+                _lib.check(_lib.load().paella_request_step(*tables, _lib.stream_ptr(self.device)))
+        pin = (self.keep, self.known, self.pin_on) if self.editing else None
+        if not (self.confidence or self.filtering):
+            # in place: the token gather at the head of the forward and the token store at its tail are different kernels of one stream (as in _sample_core)
+            self.model.forward_sample(self.tokens, self.r, self.cache, self.tokens, temperature=1.0, init_noise=self.random_x, attn_weights=self.attn_weights, ws=self.ws,
+                                      req=(self.seeds, self.temps, self.pairs), stream=(self.step, self.t_next, self.active_dev),
+                                      **({} if pin is None else {"pin": pin}), **({} if self.regions is None else {"regions": self.regions}))
             return
-        if self.filtering:  # the logits forward (the guidance mix folded through the head: ONE [rows, L] tensor) + the filtered stream tail, in place as below
-            self.model.forward_prepared(self.tokens, self.r, self.cache, attn_weights=self.attn_weights, out=self.logits, ws=self.ws,
-                                        **({} if self.pairs is None else {"req_mix": self.pairs}), **({} if self.regions is None else {"regions": self.regions}))
-            _run_tail(self.logits, None, B * self.shape[1] * self.shape[2], self.model.num_labels, self.tokens, req=(None, self.temps, self.seeds, self.shape[1] * self.shape[2]),
-                      stream=(self.step, self.t_next, self.active_dev), init_noise=self.random_x, pin=(self.keep, self.known, self.pin_on) if self.editing else None,
-                      filt=(self.filter_k, self.filter_mass))
-            return
-        # in place: the token gather at the head of the forward and the token store at its tail are different kernels of one stream (as in _sample_core)
-        self.model.forward_sample(self.tokens, self.r, self.cache, self.tokens, temperature=1.0, init_noise=self.random_x, attn_weights=self.attn_weights, ws=self.ws,
-                                  req=(self.seeds, self.temps, self.pairs), stream=(self.step, self.t_next, self.active_dev),
-                                  **({"pin": (self.keep, self.known, self.pin_on)} if self.editing else {}), **({} if self.regions is None else {"regions": self.regions}))
+        # the logits forward (the guidance mix folded through the head: ONE [rows, L] tensor), then in place as above the filtered stream tail, the pin riding in it --
+        # or, in a confidence stream, the statistics tail (raw draw, no pin) + the renoise stage (every slot's own policy, then the pin)
+        self.model.forward_prepared(self.tokens, self.r, self.cache, attn_weights=self.attn_weights, out=self.logits, ws=self.ws,
+                                    **({} if self.pairs is None else {"req_mix": self.pairs}), **({} if self.regions is None else {"regions": self.regions}))
+        hw = self.shape[1] * self.shape[2]
+        _stream_draw(self.logits, None, B * hw, self.model.num_labels, self.tokens, (None, self.temps, self.seeds, hw), self.step, self.t_next, self.active_dev,
+                     self.random_x, (self.filter_k, self.filter_mass), pin=pin,
+                     conf=(self._never, self.policy, self.confidence_noise, self.logprob, self.entropy) if self.confidence else None)
 
     _state = GraphSampler._state
 
@@ -1372,26 +1377,14 @@ class RequestStream:
         self.graph = None
         self.ws = _lib.new_workspace(self.model.workspace_bytes(self.cache.B, H, W, self.S), self.device)
         self.vq_ws = None if self.vqgan is None else _lib.new_workspace(self.vqgan.workspace_bytes(1, H, W), self.device)
-        side = torch.cuda.Stream(device=self.device)
-        side.wait_stream(torch.cuda.current_stream(self.device))
-        with torch.cuda.stream(side), torch.inference_mode():
-            for _ in range(2):
-                self._tick_launches()
-        torch.cuda.current_stream(self.device).wait_stream(side)
-        torch.cuda.synchronize(self.device)
-        state = self._state()
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"), torch.inference_mode():
-            self._tick_launches()
-        torch.cuda.synchronize(self.device)
-        self.graph, self._captured_state = graph, state
-        self.captures += 1
+        _capture_graph(self, torch.inference_mode()(self._tick_launches))
+
+    _stale = GraphSampler._stale
 
     def _check_fresh(self):
-        now = self._state()
-        if now == self._captured_state:
+        causes = ", ".join(self._stale())
+        if not causes:
             return
-        causes = ", ".join(a[0] for a, b in zip(now, self._captured_state) if a != b)
         if self.active:
             raise RuntimeError("RequestStream: %s changed with %d request(s) in flight -- their conditioning was prepared with the old state; let the stream run "
                                "empty before load_state_dict / set_gemm_precision, or abandon them with reset()" % (causes, len(self.active)))
