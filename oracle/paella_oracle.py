@@ -39,26 +39,29 @@ def grn(x, gamma, beta):
     return gamma * (x * nx) + beta + x
 
 
-def mlp(sd, p, x_nhwc):
-    """channelwise Sequential: Linear, GELU, GRN, Dropout(eval), Linear (reference src/modules.py:48-54)."""
+def mlp(sd, p, x_nhwc, drop=None):
+    """channelwise Sequential: Linear, GELU, GRN, Dropout, Linear (reference src/modules.py:48-54).  drop (train-mode tests only): the Dropout as a callback,
+    drop("act", h) on the [B, H, W, 4c] tensor right after the GRN; None is eval mode."""
     h = F.linear(x_nhwc, sd[p + ".channelwise.0.weight"], sd[p + ".channelwise.0.bias"])
     h = F.gelu(h)
     h = grn(h, sd[p + ".channelwise.2.gamma"], sd[p + ".channelwise.2.beta"])
+    if drop is not None:
+        h = drop("act", h)
     return F.linear(h, sd[p + ".channelwise.4.weight"], sd[p + ".channelwise.4.bias"])
 
 
-def res_block(sd, p, x, skip=None):
+def res_block(sd, p, x, skip=None, drop=None):
     """ResBlock (reference src/modules.py:55-62): depthwise (grouped over cat([x, skip])) -> LN -> MLP -> + x."""
     w = sd[p + ".depthwise.weight"]
     inp = x if skip is None else torch.cat([x, skip], dim=1)
     h = F.conv2d(inp, w, sd[p + ".depthwise.bias"], padding=w.size(-1) // 2, groups=x.size(1))
     h = ln_channels(h).permute(0, 2, 3, 1)
-    return x + mlp(sd, p, h).permute(0, 3, 1, 2)
+    return x + mlp(sd, p, h, drop).permute(0, 3, 1, 2)
 
 
-def ff_block(sd, p, x):
+def ff_block(sd, p, x, drop=None):
     """FeedForwardBlock (reference src/modules.py:94-96)."""
-    return x + mlp(sd, p, ln_channels(x).permute(0, 2, 3, 1)).permute(0, 3, 1, 2)
+    return x + mlp(sd, p, ln_channels(x).permute(0, 2, 3, 1), drop).permute(0, 3, 1, 2)
 
 
 def timestep_block(sd, p, x, r_embed):
@@ -68,8 +71,9 @@ def timestep_block(sd, p, x, r_embed):
     return x * (1 + a) + b
 
 
-def mha(sd, p, q_in, kv_in, nhead, attn_weights=None):
-    """nn.MultiheadAttention(batch_first, bias) written out as utils/alter_attention.py:15-36 does."""
+def mha(sd, p, q_in, kv_in, nhead, attn_weights=None, drop=None):
+    """nn.MultiheadAttention(batch_first, bias) written out as utils/alter_attention.py:15-36 does.  drop (train-mode tests only): the module's dropout as a
+    callback, drop("attn", att) on the [B, nhead, Lq, Lk] probabilities (after the attn_weights multiply, where nn.MultiheadAttention drops); None is eval mode."""
     w = sd[p + ".in_proj_weight"].chunk(3, dim=0)
     b = sd[p + ".in_proj_bias"].chunk(3, dim=0)
     B, Lq, C = q_in.shape
@@ -82,18 +86,21 @@ def mha(sd, p, q_in, kv_in, nhead, attn_weights=None):
         wts = torch.ones(Lq, Lk, dtype=att.dtype)
         wts[:, -attn_weights.numel():] = attn_weights.to(att.dtype)
         att = att * wts
+    if drop is not None:
+        att = drop("attn", att)
     o = (att @ v).permute(0, 2, 1, 3).reshape(B, Lq, C)
     return F.linear(o, sd[p + ".out_proj.weight"], sd[p + ".out_proj.bias"])
 
 
-def attn_block(sd, p, x, c_embed, nhead, self_attn=True, attn_weights=None):
+def attn_block(sd, p, x, c_embed, nhead, self_attn=True, attn_weights=None, drop=None):
     """AttnBlock + Attention2D (reference src/modules.py:12-19, 76-79)."""
     kv = F.linear(F.silu(c_embed), sd[p + ".kv_mapper.1.weight"], sd[p + ".kv_mapper.1.bias"])
     xn = ln_channels(x)
     B, C, H, W = x.shape
     q = xn.reshape(B, C, H * W).permute(0, 2, 1)
     keys = torch.cat([q, kv], dim=1) if self_attn else kv
-    o = mha(sd, p + ".attention.attn", q, keys, nhead, attn_weights)
+    # (the hook travels as a keyword and only when there is one: tests/region_model.py substitutes `mha` by a function of the six arguments of eval mode)
+    o = mha(sd, p + ".attention.attn", q, keys, nhead, attn_weights, **({} if drop is None else {"drop": drop}))
     return x + o.permute(0, 2, 1).reshape(B, C, H, W)
 
 
@@ -130,9 +137,10 @@ def _level_blocks(cfg, prefix, i, start):
             j += 1
 
 
-def unet_forward(sd, cfg, x, r, byt5, clip=None, clip_image=None, x_cat=None, attn_weights=None, dtype=torch.float32, taps=None):
+def unet_forward(sd, cfg, x, r, byt5, clip=None, clip_image=None, x_cat=None, attn_weights=None, dtype=torch.float32, taps=None, drop=None):
     """Paella.forward (reference src/modules.py:263-275 with _down_encode :234-247 and _up_decode :249-261).
-    `sd` uses the reference's state-dict keys; `taps` (dict) optionally collects intermediate activations."""
+    `sd` uses the reference's state-dict keys; `taps` (dict) optionally collects intermediate activations; `drop` (train-mode tests, tests/train_step_model.py)
+    is the dropout of every MLP and attention as one callback drop(kind, tensor) -> tensor, called in forward order -- None is eval mode, bit for bit as before."""
     sd = {k: v.to(dtype) if v.is_floating_point() else v for k, v in sd.items()}
     byt5 = byt5.to(dtype)
     clip = None if clip is None else clip.to(dtype)
@@ -154,13 +162,13 @@ def unet_forward(sd, cfg, x, r, byt5, clip=None, clip_image=None, x_cat=None, at
 
     def run(t, pfx, h, i, skip):
         if t == 'C':
-            return res_block(sd, pfx, h, skip)
+            return res_block(sd, pfx, h, skip, drop)
         if t == 'A':
-            return attn_block(sd, pfx, h, c_embed, cfg["nhead"][i], cfg.get("self_attn", True), attn_weights)
+            return attn_block(sd, pfx, h, c_embed, cfg["nhead"][i], cfg.get("self_attn", True), attn_weights, drop)
         if t == 'T':
             return timestep_block(sd, pfx, h, r_embed)
         if t == 'F':
-            return ff_block(sd, pfx, h)
+            return ff_block(sd, pfx, h, drop)
         raise ValueError(t)
 
     outs = []
