@@ -776,6 +776,50 @@ int paella_attn_train_backward(const float* q, int ldq, const float* k, int ldk,
                                float* dk_out /* may be NULL */, int lddk, float* dv_out /* may be NULL */, int lddv,
                                void* ws, size_t ws_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training timestep modulation (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays 8): the
+ * joint between two blocks of a `C T [A]` unit in train mode -- the residual add that ends a ResBlock or a
+ * FeedForwardBlock, the TimestepBlock (reference src/modules.py:99-106) and the LayerNorm2d(C, no affine) that
+ * begins an AttnBlock or a FeedForwardBlock -- as one op, forward and backward (paella_amd/csrc/mod_train.hip).
+ * Everything fp32.
+ *   x [B, P, C] (NHWC, P = H W positions per sample); residual [B, P, C] or NULL; ab [B, 2C], the mapper's output
+ *   as it is: a = ab[:, :C], b = ab[:, C:].
+ *   Forward:  u = x + residual;  x' = fma(u, 1 + a, b) -> xp_out [B, P, C].  With z_out and rstd_out (both, or
+ *     both NULL): per position mean and var of x' over C (two-pass, as the eval kernel), rstd = 1 / sqrt(var + eps),
+ *     z = (x' - mean) rstd -> z_out [B, P, C], rstd_out [B, P].  With x, residual, ab and z, rstd is ALL the
+ *     backward needs: u, x' and 1 + a are recomputed.
+ *   Backward for given dxp and / or dz (each may be NULL = no gradient arrived there; at least one is required, and
+ *     dz needs z and rstd):  g = dxp + rstd (dz - mean_c dz - z mean_c(dz z));  dx = g (1 + a), which is the gradient
+ *     of x and of residual alike;  dab[b][c] = sum_p g u,  dab[b][C + c] = sum_p g,  with u = x + residual
+ *     recomputed -- never x' divided by 1 + a, so a = -1 is an ordinary value.  dx_out [B, P, C] and dab_out
+ *     [B, 2C] are WRITTEN, not accumulated into; each may be NULL and is then not computed; with both NULL nothing
+ *     is launched.
+ * Shapes: C a multiple of 4 in 4...8192; P in 1...2^20; B in 1...65535; B P <= 2^31 - 1; every tensor and the
+ * workspace 16-byte aligned; eps positive and finite; all element offsets are 64-bit.  Anything else or a NULL
+ * required pointer (x, ab, xp_out; x, ab in the backward): PAELLA_ERR_ARG; a workspace too small for the call:
+ * PAELLA_ERR_WORKSPACE -- both before anything is enqueued.
+ * Kernels: forward one launch, one wave per position.  Backward with dz: g (kept in the workspace) and dx, one wave
+ * per position; then the sums over the positions of ONE sample in strips of max(16, ceil(P / 1024)) consecutive
+ * positions, carried in fp64, one fp32 partial per (sample, strip, channel); then the partials in ascending strip
+ * order.  Backward without dz: the summing pass reads dxp, x and residual once and writes dx as well.  A sample of one
+ * strip is summed straight into dab_out.
+ * Workspace (no state between calls, no initialisation; the forward uses none of it and checks none):
+ *   has_layernorm (the backward is given dz): g [B, P, C] rounded up to 256 bytes; then, when P exceeds one strip,
+ *   the partials B x strips x 2C floats rounded up to 256 bytes.  A supported shape that needs nothing is sized 256.
+ * Deterministic: no float atomics, no tickets, every combine is a launch.  The strips depend on (P, C) alone, and
+ * every value of a sample -- its row of dab included -- depends on that sample only: its bits depend neither on its
+ * index nor on the batch around it.  No allocation, no synchronisation, capturable in a graph.
+ * ---------------------------------------------------------------------------------------------- */
+size_t paella_mod_ln_train_workspace_bytes(int B, int P, int C, int has_layernorm); /* 0 for an unsupported shape */
+int paella_mod_ln_train_forward(const float* x, const float* residual /* may be NULL */, const float* ab, int B, int P,
+                                int C, float eps, float* xp_out, float* z_out /* may be NULL */,
+                                float* rstd_out /* NULL with z_out */, void* ws, size_t ws_bytes, void* stream);
+int paella_mod_ln_train_backward(const float* x, const float* residual /* may be NULL */, const float* ab,
+                                 const float* z /* may be NULL without dz */, const float* rstd /* NULL with z */,
+                                 const float* dxp /* may be NULL */, const float* dz /* may be NULL */, int B, int P,
+                                 int C, float* dx_out /* may be NULL */, float* dab_out /* may be NULL */, void* ws,
+                                 size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

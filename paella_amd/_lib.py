@@ -240,6 +240,11 @@ SIGNATURES = {
                                           c_void_p, c_size_t, c_void_p]),
     "paella_attn_train_backward": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_float,
                                            c_uint64, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    # training timestep modulation (ABI 8, additive): residual add + TimestepBlock [+ LayerNorm], forward and backward, only rstd [B, P] kept besides z
+    "paella_mod_ln_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "paella_mod_ln_train_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "paella_mod_ln_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
+                                             c_size_t, c_void_p]),
 }
 
 # exported for tests / tools only; declared in paella_amd/csrc/test_hooks.h, not in the public header

@@ -275,6 +275,7 @@ class Paella(nn.Module):
         self._train_activation = "torch"
         self._train_depthwise = "torch"
         self._train_attention = "torch"
+        self._train_modulation = "torch"
         # Constructed in EVAL mode (an nn.Module normally starts in train mode): eval = the hand-written HIP engine, which is what
         # sampling needs; `model.train()` -- the switch the reference's training loops flip (src/train.py:47,
         # src_distributed/train.py:73,140,172) -- selects the differentiable torch-op evaluation of paella_amd/training.py.
@@ -451,6 +452,19 @@ class Paella(nn.Module):
         if mode not in ("torch", "hip"):
             raise ValueError("training attention must be 'torch' or 'hip'")
         self._train_attention = mode
+        return self
+
+    def set_training_modulation(self, mode):
+        """How the TRAIN-mode forward (`forward` and `forward_loss` after `model.train()`) runs the joint around every TimestepBlock -- the residual add that ends
+        the ResBlock / FeedForwardBlock in front of it, its own x (1 + a) + b, and the LayerNorm2d that begins the AttnBlock / FeedForwardBlock behind it in the
+        same level: "torch" (default) is the chain of torch ops, op for op as before; "hip" runs it as one HIP op in both directions
+        (`paella_amd.training.timestep_modulate`) when the module is on a cuda device -- the two summands are handed over unadded, the mapper's [B, 2C] output goes
+        in and its gradient comes back whole, and besides the op's inputs and the LayerNorm rows autograd keeps one float per position.  The op draws nothing.
+        Independent of `set_training_activation`, `set_training_depthwise` and `set_training_attention`.  The LayerNorm of the down- and up-sampling blocks and
+        of the classifier stays where it is.  Eval mode -- the HIP inference engine -- never sees the switch."""
+        if mode not in ("torch", "hip"):
+            raise ValueError("training modulation must be 'torch' or 'hip'")
+        self._train_modulation = mode
         return self
 
     def __del__(self):

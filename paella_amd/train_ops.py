@@ -229,12 +229,12 @@ class _DwconvLayerNorm(torch.autograd.Function):
         return dx, dskip, dw, dbias, None
 
 
-def _nhwc(t):
-    """[B, C, H, W] of any strides -> its [B, H, W, C] view when the memory is already dense NHWC and 16-byte aligned, else one copy"""
+def _nhwc(t, counters=DW_COUNTERS):
+    """[B, C, H, W] of any strides -> its [B, H, W, C] view when the memory is already dense NHWC and 16-byte aligned, else one copy (counted in counters["copied"])"""
     v = t.permute(0, 2, 3, 1)
     if v.is_contiguous() and v.data_ptr() % 16 == 0:
         return v
-    DW_COUNTERS["copied"] += 1
+    counters["copied"] += 1
     return v.contiguous() if not v.is_contiguous() else v.clone()
 
 
@@ -347,3 +347,82 @@ def attention_dropout(q, kv, nhead, p=0.0, seed=None):
     seed = int(seed) & 0xFFFFFFFFFFFFFFFF
     ATTN_COUNTERS["calls"] += 1
     return _AttentionDropout.apply(_aligned(q.contiguous()), _aligned(kv.contiguous()), nhead, p, seed)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# Training timestep modulation: the joint between two blocks of a `C T [A]` unit -- the residual add that ends a ResBlock / FeedForwardBlock, the TimestepBlock's
+# x (1 + a) + b and the LayerNorm2d that begins an AttnBlock / FeedForwardBlock -- as ONE HIP op, forward and backward (paella_amd/csrc/mod_train.hip,
+# include/paella_hip.h "Training timestep modulation").  x and residual are read in place, ab is the mapper's [B, 2C] output as it is and its gradient comes back
+# as one [B, 2C] tensor (no chunk), and besides its inputs and z autograd keeps one float per position (rstd): x + residual, x' and 1 + a are recomputed.
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+MOD_MAX_B, MOD_MAX_P, MOD_MAX_C, MOD_MAX_POSITIONS = 65535, 1 << 20, 8192, 2 ** 31 - 1
+# diagnostic: how often `timestep_modulate` ran, with a residual, with the LayerNorm, and how many of its x / residual arguments were not dense NHWC memory and had
+# to be copied (tests, tools/bench_train_modulation.py)
+MOD_COUNTERS = {"calls": 0, "residual": 0, "layernorm": 0, "copied": 0}
+
+
+class _TimestepModulate(torch.autograd.Function):
+    """(x [B, H, W, C], residual [B, H, W, C] or None, ab [B, 2C]) -> x' [B, H, W, C], with layernorm (x', z [B, H W, C]); saves x, residual, ab, z and
+    rstd [B, H W].  An output nobody used arrives in the backward as None and goes to C as NULL."""
+
+    @staticmethod
+    def forward(ctx, x, residual, ab, layernorm, eps):
+        B, H, W, C = x.shape
+        P = H * W
+        xp = torch.empty_like(x)
+        z = x.new_empty(B, P, C) if layernorm else None
+        rstd = x.new_empty(B, P) if layernorm else None
+        _call("paella_mod_ln_train_forward", x.device, 0, x, residual, ab, B, P, C, eps, xp, z, rstd)   # the forward uses no workspace
+        ctx.save_for_backward(x, residual, ab, z, rstd)
+        ctx.set_materialize_grads(False)
+        return (xp, z) if layernorm else xp
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dxp, dz=None):
+        x, residual, ab, z, rstd = ctx.saved_tensors
+        B, H, W, C = x.shape
+        P = H * W
+        need_x, need_res, need_ab = ctx.needs_input_grad[:3]
+        if (dxp is None and dz is None) or not (need_x or need_res or need_ab):
+            return None, None, None, None, None
+        dxp, dz = (None if g is None else _aligned(g.to(torch.float32).contiguous()) for g in (dxp, dz))
+        dx = torch.empty_like(x) if need_x or need_res else None      # ONE tensor: the gradients of x and of residual are the same values
+        dab = torch.empty_like(ab) if need_ab else None
+        _call("paella_mod_ln_train_backward", x.device, _lib.load().paella_mod_ln_train_workspace_bytes(B, P, C, int(dz is not None)), x, residual, ab,
+              None if dz is None else z, None if dz is None else rstd, dxp, dz, B, P, C, dx, dab)
+        return dx if need_x else None, dx if need_res else None, dab, None, None
+
+
+def timestep_modulate(x, ab, residual=None, layernorm=False, eps=1e-6):
+    """The joint between two blocks of a `C T [A]` unit in train mode as one op (src/modules.py:62 / 96, 99-106, 22-27): with a = ab[:, :C], b = ab[:, C:],
+        x' = (x + residual) * (1 + a[:, :, None, None]) + b[:, :, None, None]                 and, with layernorm,
+        z  = layer_norm(x'.permute(0, 2, 3, 1), (C,), eps=eps).reshape(B, H * W, C)
+    x and residual fp32 with logical shape [B, C, H, W] and any strides: memory that is already dense NHWC and 16-byte aligned is used in place, anything else is
+    copied once.  ab fp32 [B, 2C]: the TimestepBlock mapper's F.linear output as it is.  Returns x' with logical shape [B, C, H, W] over NHWC memory; with
+    layernorm (x', z), z contiguous [B, H W, C] -- what `_attn_block` and `_channelwise` consume.  Once differentiable in x, residual and ab: the gradients of x
+    and residual are one tensor (logical [B, C, H, W] over NHWC memory), the gradient of ab comes back as one [B, 2C] tensor.  Besides its inputs and z autograd
+    keeps one float per position; x + residual, x' and 1 + a are recomputed, and the backward never divides by 1 + a.  C a multiple of 4 in 4...8192, 1...2^20
+    positions per sample, B up to 65535, B H W up to 2^31 - 1.  HIP only and exact fp32 only: anything else raises ValueError -- there is no torch fallback."""
+    _refuse_non_tensors("timestep_modulate", x, ab, *(() if residual is None else (residual,)))
+    _refuse_dtypes("timestep_modulate", "fp32 x, ab and residual", (x, ab, residual))
+    if x.dim() != 4:
+        raise ValueError("x must be [B, C, H, W] (got %s)" % (tuple(x.shape),))
+    B, C, H, W = x.shape
+    if residual is not None and tuple(residual.shape) != tuple(x.shape):
+        raise ValueError("residual must have the shape of x, %s (got %s)" % (tuple(x.shape), tuple(residual.shape)))
+    if tuple(ab.shape) != (B, 2 * C):
+        raise ValueError("ab must be [B, 2C] = [%d, %d] (got %s)" % (B, 2 * C, tuple(ab.shape)))
+    if C % 4 or not 4 <= C <= MOD_MAX_C:
+        raise ValueError("C = %d: the fused timestep modulation takes a multiple of 4 in 4...%d" % (C, MOD_MAX_C))
+    if not 1 <= B <= MOD_MAX_B or not 1 <= H * W <= MOD_MAX_P or B * H * W > MOD_MAX_POSITIONS:
+        raise ValueError("x %s: the fused timestep modulation takes 1...%d samples of 1...%d positions, B H W <= 2^31 - 1" % (tuple(x.shape), MOD_MAX_B, MOD_MAX_P))
+    eps = float(eps)
+    _refuse_out_of_range("eps", eps, 0.0 < eps < 1e30, "must be positive and finite")
+    _refuse_off_device("timestep_modulate", "x, ab and residual", (x, ab, residual))
+    layernorm = bool(layernorm)
+    MOD_COUNTERS["calls"] += 1
+    MOD_COUNTERS["residual"] += int(residual is not None)
+    MOD_COUNTERS["layernorm"] += int(layernorm)
+    out = _TimestepModulate.apply(_nhwc(x, MOD_COUNTERS), None if residual is None else _nhwc(residual, MOD_COUNTERS), _aligned(ab.contiguous()), layernorm, eps)
+    return (out[0].permute(0, 3, 1, 2), out[1]) if layernorm else out.permute(0, 3, 1, 2)

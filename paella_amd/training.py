@@ -19,13 +19,16 @@ import torch.nn.functional as F
 
 # the training ops and their limits live in train_ops.py; the network below calls them through THESE module globals (which is also where tests and tools look)
 from .train_ops import (ACT_MAX_B, ACT_MAX_C, ACT_MAX_P, ATTN_COUNTERS, ATTN_MAX_B, ATTN_MAX_HEADS, ATTN_MAX_L, ATTN_MAX_P, ATTN_MAX_ROWS, DW_COUNTERS,  # noqa: F401
-                        DW_MAX_C, DW_MAX_C_SKIP, DW_MAX_POSITIONS, HEAD_MAX_K, HEAD_MAX_LABELS, HEAD_MAX_ROWS, attention_dropout, dwconv_layernorm,
-                        gelu_grn_dropout, head_cross_entropy)
+                        DW_MAX_C, DW_MAX_C_SKIP, DW_MAX_POSITIONS, HEAD_MAX_K, HEAD_MAX_LABELS, HEAD_MAX_ROWS, MOD_COUNTERS, MOD_MAX_B, MOD_MAX_C, MOD_MAX_P,
+                        MOD_MAX_POSITIONS, attention_dropout, dwconv_layernorm, gelu_grn_dropout, head_cross_entropy, timestep_modulate)
 
 # which stretches of a block run as one HIP op: act = the middle of the MLP (Paella.set_training_activation), dw = the front of a ResBlock
 # (Paella.set_training_depthwise), attn = the attention core of an AttnBlock (Paella.set_training_attention).  `_forward_features` decides it once per forward
 _Route = namedtuple("_Route", "act dw attn")
 _TORCH = _Route(False, False, False)
+# Beside the route, not in it: Paella.set_training_modulation("hip") makes the JOINT between blocks one HIP op (`timestep_modulate`).  `_forward_features` then asks
+# a ResBlock / FeedForwardBlock in front of a TimestepBlock to hand its two summands over unadded (defer), and hands the op's LayerNorm rows (z) to the AttnBlock /
+# FeedForwardBlock behind it
 
 
 def _ln_nchw(x, eps=1e-6):
@@ -48,25 +51,29 @@ def _channelwise(blk, x_nhwc, p_drop, training, route=_TORCH):
     return F.linear(h, cw["4"].weight, cw["4"].bias)
 
 
-def _res_block(blk, x, skip, p_drop, training, route=_TORCH):
+def _res_block(blk, x, skip, p_drop, training, route=_TORCH, defer=False):
     """ResBlock (src/modules.py:43-62): depthwise 3x3 (groups = c, over cat([x, skip]) when a skip arrives) -> LN -> MLP -> + x.  route.dw
     (Paella.set_training_depthwise("hip"), train mode on a cuda device): everything in front of the MLP runs as one HIP op in both directions
-    (`dwconv_layernorm`), x and skip handed over separately -- no torch.cat."""
+    (`dwconv_layernorm`), x and skip handed over separately -- no torch.cat.  defer: the two summands (MLP output, x) come back unadded."""
     res = x
     if route.dw:
         y = dwconv_layernorm(x, blk.depthwise.weight, blk.depthwise.bias, skip)
-        return _channelwise(blk, y, p_drop, training, route).permute(0, 3, 1, 2) + res
-    if skip is not None:
-        x = torch.cat([x, skip], dim=1)
-    dw = blk.depthwise
-    c = dw.weight.size(0)
-    x = _ln_nchw(F.conv2d(x, dw.weight, dw.bias, padding=dw.weight.size(-1) // 2, groups=c)).permute(0, 2, 3, 1)
-    return _channelwise(blk, x, p_drop, training, route).permute(0, 3, 1, 2) + res
+    else:
+        if skip is not None:
+            x = torch.cat([x, skip], dim=1)
+        dw = blk.depthwise
+        c = dw.weight.size(0)
+        y = _ln_nchw(F.conv2d(x, dw.weight, dw.bias, padding=dw.weight.size(-1) // 2, groups=c)).permute(0, 2, 3, 1)
+    out = _channelwise(blk, y, p_drop, training, route).permute(0, 3, 1, 2)
+    return (out, res) if defer else out + res
 
 
-def _ff_block(blk, x, p_drop, training, route=_TORCH):
-    """FeedForwardBlock (src/modules.py:82-96)."""
-    return x + _channelwise(blk, _ln_nchw(x).permute(0, 2, 3, 1), p_drop, training, route).permute(0, 3, 1, 2)
+def _ff_block(blk, x, p_drop, training, route=_TORCH, z=None, defer=False):
+    """FeedForwardBlock (src/modules.py:82-96).  z [B, H W, C]: the LayerNorm rows of x, already made by `timestep_modulate`; defer: the two summands
+    (MLP output, x) come back unadded."""
+    rows = _ln_nchw(x).permute(0, 2, 3, 1) if z is None else z.view(x.size(0), x.size(2), x.size(3), x.size(1))
+    out = _channelwise(blk, rows, p_drop, training, route).permute(0, 3, 1, 2)
+    return (out, x) if defer else x + out
 
 
 def _timestep_block(blk, x, r_embed):
@@ -75,16 +82,16 @@ def _timestep_block(blk, x, r_embed):
     return x * (1 + a) + b
 
 
-def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, training, attn_weights=None, route=_TORCH):
+def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, training, attn_weights=None, route=_TORCH, z=None):
     """AttnBlock (src/modules.py:65-79) around nn.MultiheadAttention semantics (Attention2D :7-19): queries = LN(x) positions,
     keys = values = [LN(x) positions | kv_mapper(SiLU(c_embed))], residual on the un-normed x.  route.attn (Paella.set_training_attention("hip"), train mode
     on a cuda device): between the in-projection (one F.linear for the queries, one for keys and values together) and the out-projection the block runs as one HIP
     op in both directions (`attention_dropout`).  With attn_weights the torch branch below runs under either setting: the key-weight table stays an inference
-    feature."""
+    feature.  z [B, H W, C]: the LayerNorm rows of x, already made by `timestep_modulate` -- the queries on all three branches."""
     kvm = blk.kv_mapper._modules["1"]
     kv = F.linear(F.silu(c_embed), kvm.weight, kvm.bias)
     B, C, H, W = x.shape
-    q = _ln_nchw(x).reshape(B, C, H * W).permute(0, 2, 1)
+    q = _ln_nchw(x).reshape(B, C, H * W).permute(0, 2, 1) if z is None else z
     if self_attn:
         kv = torch.cat([q, kv], dim=1)
     at = blk.attention.attn
@@ -160,16 +167,18 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
                    on and getattr(model, "_train_attention", "torch") == "hip")
     if route.dw:  # the trunk is made channels_last once, here, so that the blocks hand each other NHWC memory
         h = h.contiguous(memory_format=torch.channels_last)
+    # Paella.set_training_modulation: carried beside the route.  "hip": the joint of every TimestepBlock with its neighbours in the level is `timestep_modulate`
+    mod = on and getattr(model, "_train_modulation", "torch") == "hip"
 
-    def run(blk, level, h, skip=None):
+    def run(blk, level, h, skip=None, z=None, defer=False):
         if blk.kind == 'C':
-            return _res_block(blk, h, skip, drop(level), training, route)
+            return _res_block(blk, h, skip, drop(level), training, route, defer)
         if blk.kind == 'A':
-            return _attn_block(blk, h, c_embed, cfg["nhead"][level], cfg["self_attn"], drop(level), training, attn_weights, route)
+            return _attn_block(blk, h, c_embed, cfg["nhead"][level], cfg["self_attn"], drop(level), training, attn_weights, route, z)
         if blk.kind == 'T':
             return _timestep_block(blk, h, r_embed)
         if blk.kind == 'F':
-            return _ff_block(blk, h, drop(level), training, route)
+            return _ff_block(blk, h, drop(level), training, route, z, defer)
         if blk.kind == 'D':  # LayerNorm2d + Conv2d(k2, s2)   (src/modules.py:153-156)
             cv = blk._modules["1"]
             return F.conv2d(_ln_nchw(h), cv.weight, cv.bias, stride=2)
@@ -178,16 +187,34 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
             return F.conv_transpose2d(_ln_nchw(h), cv.weight, cv.bias, stride=2)
         raise RuntimeError("unknown block kind %r" % blk.kind)
 
+    def run_level(level, i, h, skip=None):
+        """the blocks of one level in order; skip goes to a ResBlock that comes first.  With `mod`, a C / F block right in front of a T block hands (MLP output,
+        its input) over unadded, the T block is one `timestep_modulate` call, and when an A / F block follows in the level the op makes its LayerNorm rows too"""
+        level = list(level)
+        z = None
+        for j, blk in enumerate(level):
+            nxt = level[j + 1].kind if j + 1 < len(level) else None
+            sk = skip if (j == 0 and blk.kind == 'C') else None
+            if not mod:
+                h = run(blk, i, h, sk)
+            elif blk.kind == 'T':
+                x, res = h if isinstance(h, tuple) else (h, None)
+                ab = F.linear(r_embed, blk.mapper.weight, blk.mapper.bias)
+                if nxt in ('A', 'F'):
+                    h, z = timestep_modulate(x, ab, res, True)
+                else:
+                    h = timestep_modulate(x, ab, res)
+            else:
+                h, z = run(blk, i, h, sk, z, defer=blk.kind in ('C', 'F') and nxt == 'T'), None
+        return h
+
     level_outputs = []
     for i, level in enumerate(model.down_blocks):          # _down_encode (src/modules.py:234-247)
-        for blk in level:
-            h = run(blk, i, h)
+        h = run_level(level, i, h)
         level_outputs.insert(0, h)
     h = level_outputs[0]
     for u, level in enumerate(model.up_blocks):            # _up_decode (src/modules.py:249-261)
-        i = n_levels - 1 - u
-        for j, blk in enumerate(level):
-            h = run(blk, i, h, level_outputs[u] if (j == 0 and u > 0 and blk.kind == 'C') else None)
+        h = run_level(level, n_levels - 1 - u, h, level_outputs[u] if u > 0 else None)
     clf = model.clf._modules["1"]
     h = F.pixel_shuffle(F.conv2d(_ln_nchw(h), clf.weight, clf.bias), patch)
     return _ln_nchw(h)

@@ -1,4 +1,4 @@
-"""What the A/B tools of the training ops (bench_head_loss.py, bench_train_activation.py, bench_train_dwconv.py, bench_train_attention.py) do the same way: the report
+"""What the A/B tools of the training ops (bench_head_loss.py, bench_train_activation.py, bench_train_dwconv.py, bench_train_attention.py, bench_train_modulation.py) do the same way: the report
 that is printed and kept for --out, the timing of paths that take turns, peak memory of one pass, the set-up of one training step of a bench.py model, and the two
 tables read from rocprofv3 kernel traces.  torch is imported on use: the parts of the tools that only read traces need no device."""
 import csv
