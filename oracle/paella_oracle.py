@@ -137,10 +137,12 @@ def _level_blocks(cfg, prefix, i, start):
             j += 1
 
 
-def unet_forward(sd, cfg, x, r, byt5, clip=None, clip_image=None, x_cat=None, attn_weights=None, dtype=torch.float32, taps=None, drop=None):
+def unet_forward(sd, cfg, x, r, byt5, clip=None, clip_image=None, x_cat=None, attn_weights=None, dtype=torch.float32, taps=None, drop=None, r_embed=None):
     """Paella.forward (reference src/modules.py:263-275 with _down_encode :234-247 and _up_decode :249-261).
     `sd` uses the reference's state-dict keys; `taps` (dict) optionally collects intermediate activations; `drop` (train-mode tests, tests/train_step_model.py)
-    is the dropout of every MLP and attention as one callback drop(kind, tensor) -> tensor, called in forward order -- None is eval mode, bit for bit as before."""
+    is the dropout of every MLP and attention as one callback drop(kind, tensor) -> tensor, called in forward order -- None is eval mode, bit for bit as before.
+    `r_embed` [B, c_r] (tests that compare dtypes): the timestep embedding as an INPUT, used, cast to `dtype`, in place of r_embedding(r, c_r) -- the angles
+    r * 1e4 * freq reach 1e4, so an embedding redone in a wider dtype is another network's input; None evaluates it from r, bit for bit as before."""
     sd = {k: v.to(dtype) if v.is_floating_point() else v for k, v in sd.items()}
     byt5 = byt5.to(dtype)
     clip = None if clip is None else clip.to(dtype)
@@ -150,7 +152,7 @@ def unet_forward(sd, cfg, x, r, byt5, clip=None, clip_image=None, x_cat=None, at
         x = torch.cat([x, x_cat], dim=1)
     n = len(cfg["c_hidden"])
     p = cfg["patch_size"]
-    r_embed = r_embedding(r.to(dtype), cfg["c_r"])
+    r_embed = r_embedding(r.to(dtype), cfg["c_r"]) if r_embed is None else r_embed.to(dtype)
     c_embed = c_embeddings(sd, cfg, byt5, clip, clip_image)
     if taps is not None:
         taps["r_embed"], taps["c_embed"] = r_embed, c_embed

@@ -65,6 +65,14 @@ def _aligned(t):
 HEAD_MAX_K, HEAD_MAX_LABELS, HEAD_MAX_ROWS = 256, 65536, 1 << 24
 
 
+def refuse_head_widths(K, N):
+    """the widths the fused head takes: K features and N labels, multiples of 16 (`head_cross_entropy`; `training.forward_loss` asks before it runs the network)"""
+    if K % 16 or not 16 <= K <= HEAD_MAX_K:
+        raise ValueError("K = %d: the fused head takes a multiple of 16 in 16...%d" % (K, HEAD_MAX_K))
+    if N % 16 or not 16 <= N <= HEAD_MAX_LABELS:
+        raise ValueError("N = %d labels: the fused head takes a multiple of 16 in 16...%d" % (N, HEAD_MAX_LABELS))
+
+
 class _HeadCrossEntropy(torch.autograd.Function):
     """(h [rows, K], weight [N, K], target [rows]) -> (loss fp32 [rows], argmax int32 [rows]); saves h, weight, target and lse [rows]."""
 
@@ -112,10 +120,7 @@ def head_cross_entropy(h, weight, target, label_smoothing=0.0):
     if tuple(target.shape) != tuple(lead):
         raise ValueError("target must have the leading shape of h, %s (got %s)" % (tuple(lead), tuple(target.shape)))
     rows = target.numel()
-    if K % 16 or not 16 <= K <= HEAD_MAX_K:
-        raise ValueError("K = %d: the fused head takes a multiple of 16 in 16...%d" % (K, HEAD_MAX_K))
-    if N % 16 or not 16 <= N <= HEAD_MAX_LABELS:
-        raise ValueError("N = %d labels: the fused head takes a multiple of 16 in 16...%d" % (N, HEAD_MAX_LABELS))
+    refuse_head_widths(K, N)
     if not 1 <= rows <= HEAD_MAX_ROWS:
         raise ValueError("%d positions: the fused head takes 1...%d" % (rows, HEAD_MAX_ROWS))
     eps = float(label_smoothing)

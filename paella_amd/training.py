@@ -11,6 +11,7 @@ The arithmetic follows the reference's module definitions (file:line cited per f
 the state-dict names so that the parameters of the SAME module are trained and the HIP engine picks the updated values up
 on the next eval-mode call (`Paella._signature` tracks in-place optimizer updates).
 """
+import functools
 import math
 from collections import namedtuple
 
@@ -20,7 +21,7 @@ import torch.nn.functional as F
 # the training ops and their limits live in train_ops.py; the network below calls them through THESE module globals (which is also where tests and tools look)
 from .train_ops import (ACT_MAX_B, ACT_MAX_C, ACT_MAX_P, ATTN_COUNTERS, ATTN_MAX_B, ATTN_MAX_HEADS, ATTN_MAX_L, ATTN_MAX_P, ATTN_MAX_ROWS, DW_COUNTERS,  # noqa: F401
                         DW_MAX_C, DW_MAX_C_SKIP, DW_MAX_POSITIONS, HEAD_MAX_K, HEAD_MAX_LABELS, HEAD_MAX_ROWS, MOD_COUNTERS, MOD_MAX_B, MOD_MAX_C, MOD_MAX_P,
-                        MOD_MAX_POSITIONS, attention_dropout, dwconv_layernorm, gelu_grn_dropout, head_cross_entropy, timestep_modulate)
+                        MOD_MAX_POSITIONS, attention_dropout, dwconv_layernorm, gelu_grn_dropout, head_cross_entropy, refuse_head_widths, timestep_modulate)
 
 # which stretches of a block run as one HIP op: act = the middle of the MLP (Paella.set_training_activation), dw = the front of a ResBlock
 # (Paella.set_training_depthwise), attn = the attention core of an AttnBlock (Paella.set_training_attention).  `_forward_features` decides it once per forward
@@ -121,11 +122,20 @@ def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, training, attn_weight
     return x + out.permute(0, 2, 1).reshape(B, C, H, W)
 
 
+@functools.lru_cache(maxsize=None)
+def _timestep_freqs(half, max_positions, device):
+    """The frequency table of gen_r_embedding, made on the HOST as the engine's is (Paella._engine: paella_unet_set_timestep_freqs) and kept per device.  The
+    device's exp differs from the host's by one ulp in some entries (c_r = 64: entries near 1), and with angles of up to 1e4 a one-ulp frequency moves sine and
+    cosine by up to 5e-4: made on the device, the table gave train mode another timestep embedding than eval mode evaluates for the same r.  The first call per
+    (c_r, device) copies the table from the host inside the forward: a stream capture of a training step (nothing captures one today) must follow an eager step."""
+    return torch.arange(half).float().mul(-math.log(max_positions) / (half - 1)).exp().to(device)
+
+
 def r_embedding(r, c_r, max_positions=10000):
     """gen_r_embedding (src/modules.py:212-221)."""
     r = r * max_positions
     half = c_r // 2
-    freqs = torch.arange(half, device=r.device).float().mul(-math.log(max_positions) / (half - 1)).exp()
+    freqs = _timestep_freqs(half, max_positions, r.device)
     emb = r[:, None] * freqs[None, :]
     emb = torch.cat([emb.sin(), emb.cos()], dim=1)
     return F.pad(emb, (0, 1)) if c_r % 2 == 1 else emb
@@ -227,6 +237,8 @@ def forward_autograd(model, x, r, byt5, clip=None, clip_image=None, x_cat=None, 
 
 def forward_loss(model, x, r, target, byt5, clip=None, clip_image=None, x_cat=None, attn_weights=None, label_smoothing=0.1):
     """One training forward with the loss head fused: (loss [B, H, W], correct [B, H, W] bool) instead of logits [B, num_labels, H, W]."""
+    w = model.out_mapper._modules["1"].weight
+    refuse_head_widths(w.size(1), w.size(0))      # before the network runs: a refused call has drawn no seed and launched nothing
     feat = _forward_features(model, x, r, byt5, clip, clip_image, x_cat, attn_weights)
     loss, argmax = head_cross_entropy(feat.permute(0, 2, 3, 1), model.out_mapper._modules["1"].weight, target, label_smoothing)
     return loss, argmax == target

@@ -18,8 +18,9 @@ from tests.test_gpu_training import _train_step
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-# one row; strip tails; C off the 64- and 256-channel grain; more than one channel block; the real level-2 width
-SHAPES = [(1, 1, 4), (2, 7, 20), (3, 65, 132), (2, 256, 128), (1, 300, 1028), (4, 16, 5120)]
+# one row; strip tails; C off the 64- and 256-channel grain; more than one channel block; the real level-2 width; one row of a whole channel block (a level of one
+# position per sample at B = 1, where du IS the MLP's bias gradient: tests/test_gpu_unet_geometries.py, no_timestep)
+SHAPES = [(1, 1, 4), (2, 7, 20), (3, 65, 132), (2, 256, 128), (1, 300, 1028), (4, 16, 5120), (1, 1, 256)]
 FACTOR = T.FACTOR
 _err, _ulp = T.err, T.ulp
 SEED = (0xC0FFEE << 40) + 977   # high key word in use

@@ -13,7 +13,6 @@ import torch.nn.functional as F
 
 from paella_amd import _lib, training
 from tests import mod_ln_model as M
-from tests import test_gpu_train_step_dropout as D
 from tests import train_op_checks as T
 from tests.test_gpu_training import _train_step
 
@@ -341,7 +340,7 @@ def dropout_cases(golden, built_lib):
 
     def get(name):
         if name not in made:
-            made[name] = D.Case(name, golden)
+            made[name] = T.Case(name, T.STEP_CASES[name], golden)
         return made[name]
 
     yield get
@@ -354,14 +353,14 @@ def test_step_with_dropout_and_all_four_switches(dropout_cases, name):
     """tests/test_gpu_train_step_dropout.py's step with injected seeds, all four switches on "hip", against the fp64 mirror under that file's rule.  The new op draws
     no seed: the library calls of the other ops are still the mirror's call plan, each backward call with its forward's (p, seed)."""
     case = dropout_cases(name)
-    seeds = D.injected(case)
+    seeds = T.injected(case)
     calls = training.MOD_COUNTERS["calls"]
     case.m.set_training_modulation("hip")
     try:
-        out = D.run_step(case, seeds=iter(seeds))
+        out = T.run_step(case, seeds=iter(seeds))
     finally:
         case.m.set_training_modulation("torch")
     assert training.MOD_COUNTERS["calls"] == calls + _t_blocks(case.m)[0]
     ref, e32, plan = case.mirror(seeds)
-    D.assert_call_protocol(case, out["harness"], plan)
-    D.assert_within_yardstick(case, "all four switches", out["values"], ref, e32)
+    T.assert_call_protocol(case, out["harness"], plan)
+    T.assert_within_yardstick(case, "all four switches", out["values"], ref, e32)

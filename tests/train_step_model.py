@@ -14,14 +14,15 @@ from tests import attn_train_model as AM
 from tests import grn_act_model as GM
 
 
-def inputs(cfg, B=2, H=16, W=16, seed=21):
-    """(latents, t, mask, random_x, conditioning) of one training step on a B x H x W token grid: the recipe of G.train_step_inputs, which the defaults reproduce"""
+def inputs(cfg, B=2, H=16, W=16, seed=21, S_byt5=5, n_img=1):
+    """(latents, t, mask, random_x, conditioning) of one training step on a B x H x W token grid with S_byt5 ByT5 rows, a CLIP text entry and n_img CLIP-image
+    entries: the recipe of G.train_step_inputs, which the defaults reproduce"""
     g = torch.Generator().manual_seed(seed)
     latents = torch.randint(0, cfg["num_labels"], (B, H, W), generator=g)
     t = (1 - torch.rand(B, generator=g)).add(0.001).clamp(0.001, 1.0)
     mask = (torch.rand(B, H, W, generator=g) <= t[:, None, None]).long()
     random_x = torch.randint(0, cfg["num_labels"], (B, H, W), generator=g)
-    c = synth.synth_conditioning(B, 5, cfg["byt5_embd"], cfg["clip_embd"], seed=G.COND_SEED + 9 + (seed - 21), with_clip=True, n_clip_image=1)
+    c = synth.synth_conditioning(B, S_byt5, cfg["byt5_embd"], cfg["clip_embd"], seed=G.COND_SEED + 9 + (seed - 21), with_clip=True, n_clip_image=n_img)
     return latents, t, mask, random_x, c
 
 
@@ -40,9 +41,13 @@ def step(sd, cfg, inp, drop, dtype=torch.float64):
     # The angle of the timestep embedding starts as the fp32 product r * max_positions (gen_r_embedding, reference src/modules.py:213, on the fp32 r of the training
     # loop): up to 1e4 with an fp32 spacing of 1e-3, and its sine and cosine feed every TimestepBlock.  That rounded product is part of what the network is GIVEN, as
     # the oracle's fp32 frequency table is: a mirror that redid it in fp64 would evaluate another network (the tiny step's logits move by 1.1e-4, as much as the
-    # recorded step's logit tolerance allows in all), and every fp32 route would be charged with it.  So a wider dtype receives the r whose product IS that fp32 number.
-    r = t if dtype == torch.float32 else (t.float() * 10000).to(dtype) / 10000
-    pred = O.unet_forward(leaves, cfg, noised, r, dtype=dtype, drop=drop, **c)
+    # recorded step's logit tolerance allows in all), and every fp32 route would be charged with it.  The same holds for the second product, with the frequency
+    # table: every fp32 route (reference, engine, torch) does fl(fl(r * 1e4) * freq) as the same IEEE multiplications and gets the same bits, and redoing it in fp64
+    # moves angles of up to 1e4 by up to 5e-4 (6e-5 ... 1.3e-4 in the logits of small networks, against 2e-6 ... 4e-6 of everything else an fp32 evaluation
+    # rounds).  So a wider dtype receives the whole embedding as the oracle's own fp32 evaluation; what the sine and cosine of those angles are is checked on its
+    # own (tests/test_gpu_unet_geometries.py: test_timestep_embedding).
+    r_embed = None if dtype == torch.float32 else O.r_embedding(t.float(), cfg["c_r"])
+    pred = O.unet_forward(leaves, cfg, noised, t, dtype=dtype, drop=drop, r_embed=r_embed, **c)
     per_pos = F.cross_entropy(pred, latents, label_smoothing=0.1, reduction="none")
     loss = ((per_pos * lw).sum(dim=[1, 2]) / lw.sum(dim=[1, 2])).mean()
     loss.backward()
