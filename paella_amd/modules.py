@@ -12,12 +12,77 @@ Beyond the reference surface it exposes the two calls `sample()` uses to hoist s
 and `forward_prepared()` (one denoising evaluation against that cache).
 """
 import ctypes
+import itertools
 import math
 
 import torch
 from torch import nn
+from torch.nn.modules import module as _nn_module
 
 from . import _lib
+
+
+# Every registration of a Parameter, buffer or child module on ANY nn.Module of the process counts here (torch's process-wide registration hooks: they fire for
+# `holder.weight = nn.Parameter(t)`, `register_parameter` / `register_buffer`, and `load_state_dict(assign=True)`, which assigns).  `_NativeModel._signature`
+# compares the count with the one it saw when it listed its tensors, so a swapped tensor OBJECT is noticed for one integer compare per call.
+_REGISTRATIONS = [0]
+# Load generations: every (re)load of a native model draws the next one, so a generation names one load of one module (DESIGN.md section 4, "Load generation").
+_LOAD_GENS = itertools.count(1)
+
+
+def _count_registration(module, name, value):
+    _REGISTRATIONS[0] += 1
+
+
+_nn_module.register_module_parameter_registration_hook(_count_registration)
+_nn_module.register_module_buffer_registration_hook(_count_registration)
+_nn_module.register_module_module_registration_hook(_count_registration)
+
+
+class _NativeModel:
+    """What `Paella` and `VQModel` share around their native handle: the weight signature, `refresh()`, and copy / pickle semantics (mixed in before nn.Module)."""
+
+    def _signature(self):
+        """What `_engine`, `GraphSampler` and `RequestStream` compare to notice a weight change: (data_ptr, version) of every parameter and buffer, behind a count
+        of how often the SET of tensor objects changed.  Noticed with no further call: `load_state_dict` (with or without `assign=True`, from any device),
+        optimizer steps and ordinary in-place ops (the version), `.to()` / `.cuda()` / `.float()` and `p.data = t` (the pointer), a new Parameter or buffer object
+        under an existing name (the registration count above).  NOT noticed: in-place edits through `.data` (`p.data.mul_(2)`), which torch does not version --
+        call `refresh()` after those.
+        The tensor LIST is cached (walking the module tree costs ~0.7 ms at the 570M size, the comparison itself ~0.08 ms) and walked again only after a
+        registration somewhere in the process, an `_apply` or a `refresh()`; a walk that finds the same objects keeps the list."""
+        d = self.__dict__
+        ts = d.get("_sig_tensors")
+        if ts is None or d.get("_sig_seen") != _REGISTRATIONS[0]:
+            seen = _REGISTRATIONS[0]
+            new = list(self.parameters()) + list(self.buffers())
+            if ts is None:
+                ts = d["_sig_tensors"] = new
+            elif len(new) != len(ts) or any(a is not b for a, b in zip(new, ts)):
+                ts = d["_sig_tensors"] = new
+                d["_sig_swaps"] = d.get("_sig_swaps", 0) + 1  # (a new object may sit where a freed one sat, at version 0: the pointers alone do not tell)
+            d["_sig_seen"] = seen
+        sig = [(d.get("_sig_swaps", 0), -1)]
+        sig.extend([(t.data_ptr(), t._version) for t in ts])
+        return tuple(sig)
+
+    def _apply(self, fn, *args, **kwargs):
+        self.__dict__["_sig_seen"] = None
+        return super()._apply(fn, *args, **kwargs)
+
+    def refresh(self):
+        """Force the native engine to reload every tensor on the next call.  Needed only after in-place edits through `.data` (`p.data *= ...`, the idiom the
+        reference itself uses at init; `p.data.copy_(t)`), which torch does not version; every other route by which weights change is noticed (`_signature`)."""
+        self._loaded_sig = None
+        self.__dict__["_sig_seen"] = None
+
+    def __getstate__(self):
+        """A copy (`copy.deepcopy`, pickle, `torch.save` of the module) takes the tensors and the settings, never the native model: it starts without a handle,
+        a loaded signature, a workspace or a tensor list, and builds its own engine on first use."""
+        state = dict(self.__dict__)
+        state.update(_handle=None, _loaded_sig=None, _ws=None, _load_gen=0)
+        for k in ("_sig_tensors", "_sig_seen", "_sig_swaps"):
+            state.pop(k, None)
+        return state
 
 
 class _Holder(nn.Module):
@@ -73,10 +138,14 @@ class _InferenceOnly(torch.autograd.Function):
 class CondCache:
     """Device-resident result of `Paella.prepare_cond` (K/V of the conditioning rows for every AttnBlock).
     lens (ragged conditioning): None, or an int32 DEVICE tensor [B] -- the cache is then B slots of S rows, sample b's real rows sit at the front of slot b and
-    lens[b] says how many there are; the attention kernels bound every sample by its own count and never read the rest of a slot."""
+    lens[b] says how many there are; the attention kernels bound every sample by its own count and never read the rest of a slot.
+    gen: the load generation of the module whose weights made the K/V (`prepare_cond` records it; one integer names one load of one module), or None for a cache
+    put together by a caller that watches the weights itself (`GraphSampler`, `RequestStream`).  `forward_prepared` / `forward_sample` refuse a cache whose
+    generation is not the module's current one: its K/V come from other weights.  The K/V do not depend on the gemm precision mode (the conditioning mappers and
+    the composed K|V projection run in fp32 in either mode), so a cache outlives `set_gemm_precision`."""
 
-    def __init__(self, buf, B, S, lens=None):
-        self.buf, self.B, self.S, self.lens = buf, B, S, lens
+    def __init__(self, buf, B, S, lens=None, gen=None):
+        self.buf, self.B, self.S, self.lens, self.gen = buf, B, S, lens, gen
 
 
 class KeyWeights:
@@ -205,7 +274,7 @@ class RegionTables:
         return self
 
 
-class Paella(nn.Module):
+class Paella(_NativeModel, nn.Module):
     """Drop-in for reference `Paella` (src/modules.py:109). Same constructor arguments and defaults."""
 
     def __init__(self, c_in=256, c_out=256, num_labels=8192, c_r=64, patch_size=2, c_cond=1024,
@@ -270,6 +339,7 @@ class Paella(nn.Module):
         self.reset_parameters()
         self._handle = None
         self._loaded_sig = None
+        self._load_gen = 0
         self._ws = None
         self._precision = 0
         self._train_activation = "torch"
@@ -325,27 +395,6 @@ class Paella(nn.Module):
                                "move it with .to('cuda'). There is no CPU fallback." % dev)
         return dev
 
-    def _signature(self):
-        """(data_ptr, version) of every parameter: what `_engine` and `GraphSampler` compare to notice `load_state_dict`, optimizer steps, `.to()` and in-place
-        edits.  The parameter LIST is cached (walking the module tree costs ~0.7 ms at the 570M size, the comparison itself ~0.08 ms): `_apply` (`.to()`, `.cuda()`,
-        `.float()`) and `refresh()` drop the cache; assigning a NEW nn.Parameter object to a holder needs `refresh()`."""
-        ps = self.__dict__.get("_sig_params")
-        if ps is None:
-            ps = list(self.parameters())
-            self.__dict__["_sig_params"] = ps
-        return tuple((p.data_ptr(), p._version) for p in ps)
-
-    def _apply(self, fn, *args, **kwargs):
-        self.__dict__["_sig_params"] = None
-        return super()._apply(fn, *args, **kwargs)
-
-    def refresh(self):
-        """Force the native engine to reload every tensor on the next call.  Needed only after edits torch does not version
-        (`p.data *= ...`, the idiom the reference itself uses at init); optimizer steps, `load_state_dict`, `.to()` and ordinary
-        in-place ops are detected automatically."""
-        self._loaded_sig = None
-        self.__dict__["_sig_params"] = None
-
     def _engine(self):
         """Create / refresh the native model: (re)load every tensor when parameters moved or changed."""
         dev = self._require_hip()
@@ -394,6 +443,7 @@ class Paella(nn.Module):
             _lib.check(lib.paella_unet_finalize(self._handle, st))
             torch.cuda.current_stream(dev).synchronize()  # staging copies above may be temporaries
         self._loaded_sig = sig
+        self._load_gen = next(_LOAD_GENS)
         return self._handle
 
     def set_gemm_precision(self, mode):
@@ -592,10 +642,17 @@ class Paella(nn.Module):
             if slot_rows is not None:
                 _lib.check(lib.paella_unet_cond_prepare_slots(h, _lib.ptr(byt5) if Sb > 0 else None, Sb, _lib.ptr(clip), arr, len(images), B, slot_rows, 0,
                                                               _lib.ptr(buf), buf.numel(), _lib.ptr(lens_out), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-                return CondCache(buf, B, slot_rows, lens_out)
+                return CondCache(buf, B, slot_rows, lens_out, gen=self._load_gen)
             _lib.check(lib.paella_unet_cond_prepare(h, _lib.ptr(byt5) if Sb > 0 else None, Sb, _lib.ptr(clip), arr, len(images), B,
                                                     _lib.ptr(buf), buf.numel(), _lib.ptr(ws), ws.numel(), _lib.stream_ptr(dev)))
-        return CondCache(buf, B, S)
+        return CondCache(buf, B, S, gen=self._load_gen)
+
+    def _check_cond(self, cond):
+        """a cache that records its load generation must be of this module's current load (called after `_engine()`, which is what reloads)"""
+        gen = getattr(cond, "gen", None)
+        if gen is not None and gen != self._load_gen:
+            raise RuntimeError("this CondCache holds K/V computed from other weights: the module's weights changed (and were reloaded) after prepare_cond, or the "
+                               "cache was prepared by another module -- call prepare_cond again")
 
     def _cond_lens(self, cond):
         """the `cond_len` table of a ragged cache (None for a plain one), checked"""
@@ -658,6 +715,7 @@ class Paella(nn.Module):
         r = self._f32(r, "r")
         if r.numel() != nu:
             raise ValueError("r must have one entry per sample")
+        self._check_cond(cond)
         B = cond.B
         if nu <= 0 or B % nu:
             raise ValueError("conditioning batch %d is not a multiple of the token batch %d" % (B, nu))
@@ -730,6 +788,7 @@ class Paella(nn.Module):
         x = x.contiguous()
         nu, H, W = x.shape
         r = self._f32(r, "r")
+        self._check_cond(cond)
         B = cond.B
         mix = (0.0, 0.0) if cfg_mix is None else (float(cfg_mix[0]), float(cfg_mix[1]))
         if req is not None:

@@ -12,7 +12,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .modules import _Holder, _p, _wb
+from .modules import _LOAD_GENS, _Holder, _NativeModel, _p, _wb
 
 
 def _res_block(c):
@@ -62,7 +62,7 @@ class VectorQuantize(nn.Module):
         return q
 
 
-class VQModel(nn.Module):
+class VQModel(_NativeModel, nn.Module):
     """Drop-in for reference `VQModel` (src/vqgan.py:45). levels=2 is f4 (default), levels=3 is f8."""
 
     def __init__(self, levels=2, bottleneck_blocks=12, c_hidden=384, c_latent=4, codebook_size=8192, scale_factor=0.3764):
@@ -95,6 +95,7 @@ class VQModel(nn.Module):
         self.reset_parameters()
         self._handle = None
         self._loaded_sig = None
+        self._load_gen = 0
         self._ws = None
         self._precision = 0
 
@@ -132,23 +133,8 @@ class VQModel(nn.Module):
     def _device(self):
         return self.vquantizer.codebook.weight.device
 
-    def _signature(self):
-        """(data_ptr, version) of every parameter and buffer (the tensor list is cached; `_apply` and `refresh()` drop it) -- see Paella._signature."""
-        ts = self.__dict__.get("_sig_tensors")
-        if ts is None:
-            ts = list(self.parameters()) + list(self.buffers())
-            self.__dict__["_sig_tensors"] = ts
-        return tuple((t.data_ptr(), t._version) for t in ts)
-
-    def _apply(self, fn, *args, **kwargs):
-        self.__dict__["_sig_tensors"] = None
-        return super()._apply(fn, *args, **kwargs)
-
-    def refresh(self):
-        """Force a reload of every tensor on the next call (needed only after edits torch does not version, e.g. `p.data = ...` with a new storage of a NEW
-        Parameter object)."""
-        self._loaded_sig = None
-        self.__dict__["_sig_tensors"] = None
+    # `_signature`, `_apply`, `refresh()` and the copy semantics are _NativeModel's: the signature covers every parameter AND buffer (the BatchNorm statistics
+    # are weights here), and the ResBlock gammas, which the engine bakes into its launches as host constants, are reloaded with everything else
 
     def _engine(self):
         dev = self._device()
@@ -178,6 +164,7 @@ class VQModel(nn.Module):
                 _lib.check(lib.paella_vqgan_load_tensor(self._handle, key.encode(), _lib.ptr(t), shape, t.dim(), st))
             _lib.check(lib.paella_vqgan_finalize(self._handle, st))
         self._loaded_sig = sig
+        self._load_gen = next(_LOAD_GENS)
         return self._handle
 
     def __del__(self):
