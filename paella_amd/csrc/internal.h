@@ -49,6 +49,20 @@ enum Repack {
 };
 int repack_into(Repack kind, const float* src, const std::vector<int64_t>& shape, DevBuf& dst, hipStream_t st);
 
+// One state-dict tensor of a model: what the loader expects under its key, and the SLOTS of everything made from it.  The models keep these in a std::map by key
+// (node addresses never move), the plans bind `Weight*` members to them, and a launch reads slot.p when it is enqueued -- so a reload that reallocates, or a
+// shadow that first appears at a later set_precision(1), needs no re-bind.  A slot nobody filled is a null pointer.
+struct Weight {
+    Repack kind;
+    std::vector<int64_t> shape;  // expected reference shape
+    int aux = 0;                 // RP_TS_*: offset into the concatenated timestep mapper
+    DevBuf w;                    // repacked fp32 tensor
+    DevBuf16 w16;                // its bf16 shadow (make_shadows; read only in precision mode 1)
+    DevBuf wsum, wsum16;         // LayerNorm-consuming weights: row sums of w (finalize) / of the rounded w (make_shadows)
+};
+int weight_make_shadow(Weight& t, hipStream_t st);  // refreshes t.w16 from t.w as loaded now
+void weight_free(Weight& t);
+
 // Argument blocks (include/paella_hip.h: paella_tail_args / paella_step_args; tail.hip, model.hip).  What a fixed-form entry point's NAME promises on top of what
 // its block holds (a block alone takes its form from what is present): the request form, its stream tables, the scalar filter values, a guidance pair table.
 enum { kNeedRequest = 1, kNeedStream = 2, kNeedFilter = 4, kNeedPairs = 8 };

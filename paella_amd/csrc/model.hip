@@ -43,20 +43,18 @@ int devbuf_alloc(DevBuf& b, size_t n) {
 
 // ---------------------------------------------------------------------------
 // plan
+//
+// A state-dict key is written ONCE, in build_plan: the add_spec call that declares the tensor (key, repack kind, expected shape) returns its Weight (internal.h),
+// and the same statement binds it to the member of the Block / paella_unet that the launches read.  paella_unet_load_tensor, the "never loaded" check of
+// paella_unet_finalize and paella_unet_destroy are the only code that goes through the names; everything else follows the bound pointers.  What is derived from a
+// weight (bf16 shadow, row sums) lives in slots of the same Weight, listed once at the end of build_plan (shadowed / ln_weights).
 // ---------------------------------------------------------------------------
 enum BlockType { BT_RES, BT_TS, BT_ATTN, BT_FF, BT_DOWN, BT_UP };
-
-struct TensorSpec {
-    Repack kind;
-    std::vector<int64_t> shape;  // expected reference shape
-    int aux = 0;                 // RP_TS_*: offset into the concatenated timestep mapper
-};
 
 struct Block {
     BlockType type;
     int level = 0;
     int c = 0;
-    std::string prefix;
     bool has_skip = false;
     int ts_offset = -1;        // BT_TS: offset of [a|b] in the ts vector
     bool ts_standalone = true; // BT_TS: false when fused into the previous block's GEMM epilogue
@@ -65,23 +63,30 @@ struct Block {
     bool emit_rowstat = false;   // producer: this block's last GEMM also writes per-row (sum, centred M2) partials of x
     bool ln_from_stats = false;  // consumer (ATTN / UP): LayerNorm folded into the GEMM's A-operand load from those partials
     int c_from = 0, c_to = 0;  // samplers
+    // the tensors this block type reads
+    Weight *dw_w = nullptr, *dw_b = nullptr;                                                                  // BT_RES: depthwise conv
+    Weight *w1 = nullptr, *b1 = nullptr, *gamma = nullptr, *beta = nullptr, *w2 = nullptr, *b2 = nullptr;       // BT_RES / BT_FF: MLP with GlobalResponseNorm
+    Weight *in_w = nullptr, *in_b = nullptr, *out_w = nullptr, *out_b = nullptr, *kv_w = nullptr, *kv_b = nullptr;  // BT_ATTN
+    Weight *conv_w = nullptr, *conv_b = nullptr;                                                              // BT_DOWN / BT_UP
 };
+
+struct LnWeight { Weight* t; int N, K; };  // a weight whose GEMM consumes LayerNorm-from-statistics, with (N, K) of the repacked matrix
 
 struct paella_unet {
     paella_unet_config cfg;
     std::vector<Block> down, up;  // execution order, samplers included
-    std::map<std::string, TensorSpec> specs;
-    std::map<std::string, DevBuf> t;
+    std::map<std::string, Weight> t;  // every state-dict tensor by key; the members below and the Blocks point into it
+    Weight *byt5_w, *byt5_b, *clip_w, *clip_b, *clip_image_w, *clip_image_b;
+    Weight *in_mapper, *embedding_w, *embedding_b, *clf_w, *clf_b, *out_mapper;
+    std::vector<Weight*> shadowed;     // the weights a bf16 GEMM of the forward reads (execution order)
+    std::vector<LnWeight> ln_weights;  // the LayerNorm-consuming ones: row sums for the LayerNorm folded into the GEMM epilogue
     DevBuf ts_w, ts_b, freqs;
     // conditioning K|V of EVERY AttnBlock as one GEMM: kv_w [kv_total, c_cond] = rows of in_proj_weight[c:3c] . kv_mapper.1.weight per block
     // (composed at finalize), kv_b = in_proj_weight[c:3c] . kv_mapper.1.bias + in_proj_bias[c:3c]; kv_col[i] = first column of block i
     DevBuf kv_w, kv_b;
-    std::map<std::string, DevBuf> wsum;  // per LayerNorm-consuming weight (key of the weight tensor): its row sums, for the LayerNorm folded into the GEMM epilogue
     // OPT-IN bf16 fast mode, PER MODEL (paella_unet_set_precision; outside the fp32 parity contract): bf16 shadow copies of the GEMM weights (made at finalize /
     // when the mode is switched on) and the row sums of the ROUNDED LayerNorm-consuming weights
     int precision = 0;                   // 0 = exact fp32 (default), 1 = bf16 operands
-    std::map<std::string, DevBuf16> t16;
-    std::map<std::string, DevBuf> wsum16;
     std::vector<int> kv_col;
     int kv_total = 0;
     int ts_total = 0;
@@ -93,21 +98,13 @@ struct paella_unet {
     int c_max = 0;
 };
 
-static const float* T(const paella_unet* m, const std::string& k) {
-    auto it = m->t.find(k);
-    return it == m->t.end() ? nullptr : it->second.p;
-}
 // bf16 shadow of a weight, or null (fp32 mode / no shadow for this tensor)
-static const unsigned short* T16(const paella_unet* m, const std::string& k) {
-    if (m->precision != 1) return nullptr;
-    auto it = m->t16.find(k);
-    return it == m->t16.end() ? nullptr : it->second.p;
-}
+static const unsigned short* W16(const paella_unet* m, const Weight* t) { return m->precision == 1 ? t->w16.p : nullptr; }
 
-static void add_spec(paella_unet* m, const std::string& key, Repack kind, std::vector<int64_t> shape, int aux = 0) {
-    TensorSpec s;
-    s.kind = kind; s.shape = std::move(shape); s.aux = aux;
-    m->specs[key] = s;
+static Weight* add_spec(paella_unet* m, const std::string& key, Repack kind, std::vector<int64_t> shape, int aux = 0) {
+    Weight& t = m->t[key];
+    t.kind = kind; t.shape = std::move(shape); t.aux = aux;
+    return &t;
 }
 
 static int build_plan(paella_unet* m) {
@@ -121,39 +118,39 @@ static int build_plan(paella_unet* m) {
     }
     const int p2 = c.patch_size * c.patch_size;
     const int64_t cr = c.c_r, cc = c.c_cond;
-    add_spec(m, "byt5_mapper.weight", RP_COPY, {cc, c.byt5_embd});
-    add_spec(m, "byt5_mapper.bias", RP_COPY, {cc});
-    add_spec(m, "clip_mapper.weight", RP_COPY, {cc * c.clip_seq_len, c.clip_embd});
-    add_spec(m, "clip_mapper.bias", RP_COPY, {cc * c.clip_seq_len});
-    add_spec(m, "clip_image_mapper.weight", RP_COPY, {cc * c.clip_seq_len, c.clip_embd});
-    add_spec(m, "clip_image_mapper.bias", RP_COPY, {cc * c.clip_seq_len});
-    add_spec(m, "in_mapper.0.weight", RP_COPY, {c.num_labels, c.c_in});
-    add_spec(m, "embedding.1.weight", RP_COPY, {c.c_hidden[0], (int64_t)c.c_in * p2, 1, 1});
-    add_spec(m, "embedding.1.bias", RP_COPY, {c.c_hidden[0]});
-    add_spec(m, "clf.1.weight", RP_CLF_W, {(int64_t)c.c_out * p2, c.c_hidden[0], 1, 1});
-    add_spec(m, "clf.1.bias", RP_CLF_B, {(int64_t)c.c_out * p2});
-    add_spec(m, "out_mapper.1.weight", RP_COPY, {c.num_labels, c.c_out, 1, 1});
+    m->byt5_w = add_spec(m, "byt5_mapper.weight", RP_COPY, {cc, c.byt5_embd});
+    m->byt5_b = add_spec(m, "byt5_mapper.bias", RP_COPY, {cc});
+    m->clip_w = add_spec(m, "clip_mapper.weight", RP_COPY, {cc * c.clip_seq_len, c.clip_embd});
+    m->clip_b = add_spec(m, "clip_mapper.bias", RP_COPY, {cc * c.clip_seq_len});
+    m->clip_image_w = add_spec(m, "clip_image_mapper.weight", RP_COPY, {cc * c.clip_seq_len, c.clip_embd});
+    m->clip_image_b = add_spec(m, "clip_image_mapper.bias", RP_COPY, {cc * c.clip_seq_len});
+    m->in_mapper = add_spec(m, "in_mapper.0.weight", RP_COPY, {c.num_labels, c.c_in});
+    m->embedding_w = add_spec(m, "embedding.1.weight", RP_COPY, {c.c_hidden[0], (int64_t)c.c_in * p2, 1, 1});
+    m->embedding_b = add_spec(m, "embedding.1.bias", RP_COPY, {c.c_hidden[0]});
+    m->clf_w = add_spec(m, "clf.1.weight", RP_CLF_W, {(int64_t)c.c_out * p2, c.c_hidden[0], 1, 1});
+    m->clf_b = add_spec(m, "clf.1.bias", RP_CLF_B, {(int64_t)c.c_out * p2});
+    m->out_mapper = add_spec(m, "out_mapper.1.weight", RP_COPY, {c.num_labels, c.c_out, 1, 1});
 
     int ts_total = 0, n_attn = 0;
     auto add_block = [&](std::vector<Block>& seq, char type, int level, const std::string& prefix, bool skip) -> int {
         Block b;
-        b.level = level; b.c = c.c_hidden[level]; b.prefix = prefix;
+        b.level = level; b.c = c.c_hidden[level];
         const int64_t ch = b.c;
         if (ch & 7) { paella_set_error("c_hidden[%d]=%d must be a multiple of 8", level, b.c); return PAELLA_ERR_ARG; }
         switch (type) {
             case 'C':
                 b.type = BT_RES; b.has_skip = skip;
-                add_spec(m, prefix + ".depthwise.weight", RP_DW, {ch, skip ? 2 : 1, 3, 3});
-                add_spec(m, prefix + ".depthwise.bias", RP_COPY, {ch});
+                b.dw_w = add_spec(m, prefix + ".depthwise.weight", RP_DW, {ch, skip ? 2 : 1, 3, 3});
+                b.dw_b = add_spec(m, prefix + ".depthwise.bias", RP_COPY, {ch});
                 /* fallthrough */
             case 'F':
                 if (type == 'F') b.type = BT_FF;
-                add_spec(m, prefix + ".channelwise.0.weight", RP_COPY, {4 * ch, ch});
-                add_spec(m, prefix + ".channelwise.0.bias", RP_COPY, {4 * ch});
-                add_spec(m, prefix + ".channelwise.2.gamma", RP_COPY, {1, 1, 1, 4 * ch});
-                add_spec(m, prefix + ".channelwise.2.beta", RP_COPY, {1, 1, 1, 4 * ch});
-                add_spec(m, prefix + ".channelwise.4.weight", RP_COPY, {ch, 4 * ch});
-                add_spec(m, prefix + ".channelwise.4.bias", RP_COPY, {ch});
+                b.w1 = add_spec(m, prefix + ".channelwise.0.weight", RP_COPY, {4 * ch, ch});
+                b.b1 = add_spec(m, prefix + ".channelwise.0.bias", RP_COPY, {4 * ch});
+                b.gamma = add_spec(m, prefix + ".channelwise.2.gamma", RP_COPY, {1, 1, 1, 4 * ch});
+                b.beta = add_spec(m, prefix + ".channelwise.2.beta", RP_COPY, {1, 1, 1, 4 * ch});
+                b.w2 = add_spec(m, prefix + ".channelwise.4.weight", RP_COPY, {ch, 4 * ch});
+                b.b2 = add_spec(m, prefix + ".channelwise.4.bias", RP_COPY, {ch});
                 break;
             case 'T':
                 b.type = BT_TS; b.ts_offset = ts_total;
@@ -174,12 +171,12 @@ static int build_plan(paella_unet* m) {
                     paella_set_error("level %d: c=%d nhead=%d -> head_dim must be a multiple of 16 and <= 128", level, b.c, nh);
                     return PAELLA_ERR_ARG;
                 }
-                add_spec(m, prefix + ".attention.attn.in_proj_weight", RP_COPY, {3 * ch, ch});
-                add_spec(m, prefix + ".attention.attn.in_proj_bias", RP_COPY, {3 * ch});
-                add_spec(m, prefix + ".attention.attn.out_proj.weight", RP_COPY, {ch, ch});
-                add_spec(m, prefix + ".attention.attn.out_proj.bias", RP_COPY, {ch});
-                add_spec(m, prefix + ".kv_mapper.1.weight", RP_COPY, {ch, cc});
-                add_spec(m, prefix + ".kv_mapper.1.bias", RP_COPY, {ch});
+                b.in_w = add_spec(m, prefix + ".attention.attn.in_proj_weight", RP_COPY, {3 * ch, ch});
+                b.in_b = add_spec(m, prefix + ".attention.attn.in_proj_bias", RP_COPY, {3 * ch});
+                b.out_w = add_spec(m, prefix + ".attention.attn.out_proj.weight", RP_COPY, {ch, ch});
+                b.out_b = add_spec(m, prefix + ".attention.attn.out_proj.bias", RP_COPY, {ch});
+                b.kv_w = add_spec(m, prefix + ".kv_mapper.1.weight", RP_COPY, {ch, cc});
+                b.kv_b = add_spec(m, prefix + ".kv_mapper.1.bias", RP_COPY, {ch});
                 break;
             }
             default:
@@ -197,10 +194,9 @@ static int build_plan(paella_unet* m) {
         if (i > 0) {
             Block b;
             b.type = BT_DOWN; b.level = i; b.c = c.c_hidden[i]; b.c_from = c.c_hidden[i - 1]; b.c_to = c.c_hidden[i];
-            snprintf(buf, sizeof buf, "down_blocks.%d.0", i);
-            b.prefix = buf;
-            add_spec(m, b.prefix + ".1.weight", RP_CONV_K2, {b.c_to, b.c_from, 2, 2});
-            add_spec(m, b.prefix + ".1.bias", RP_COPY, {b.c_to});
+            snprintf(buf, sizeof buf, "down_blocks.%d.0.1", i);
+            b.conv_w = add_spec(m, std::string(buf) + ".weight", RP_CONV_K2, {b.c_to, b.c_from, 2, 2});
+            b.conv_b = add_spec(m, std::string(buf) + ".bias", RP_COPY, {b.c_to});
             m->down.push_back(b);
             j = 1;
         }
@@ -225,10 +221,9 @@ static int build_plan(paella_unet* m) {
         if (i > 0) {
             Block b;
             b.type = BT_UP; b.level = i; b.c = c.c_hidden[i]; b.c_from = c.c_hidden[i]; b.c_to = c.c_hidden[i - 1];
-            snprintf(buf, sizeof buf, "up_blocks.%d.%d", u, j);
-            b.prefix = buf;
-            add_spec(m, b.prefix + ".1.weight", RP_CONVT_K2, {b.c_from, b.c_to, 2, 2});
-            add_spec(m, b.prefix + ".1.bias", RP_TILE4, {b.c_to});
+            snprintf(buf, sizeof buf, "up_blocks.%d.%d.1", u, j);
+            b.conv_w = add_spec(m, std::string(buf) + ".weight", RP_CONVT_K2, {b.c_from, b.c_to, 2, 2});
+            b.conv_b = add_spec(m, std::string(buf) + ".bias", RP_TILE4, {b.c_to});
             m->up.push_back(b);
         }
     }
@@ -256,6 +251,20 @@ static int build_plan(paella_unet* m) {
         }
         Block* p = producer_of(all.size());
         if (p && p->level == 0) { p->emit_rowstat = true; m->clf_from_stats = true; }
+        // what is derived from the weights: the ones a bf16 GEMM reads get a bf16 shadow, the LayerNorm-folding ones their row sums (finalize, make_shadows)
+        auto gemm_weight = [&](Weight* t, bool ln, int N, int K) {
+            m->shadowed.push_back(t);
+            if (ln) m->ln_weights.push_back({t, N, K});
+        };
+        for (const Block* b : all) switch (b->type) {
+            case BT_RES: case BT_FF: gemm_weight(b->w1, false, 0, 0); gemm_weight(b->w2, false, 0, 0); break;
+            case BT_ATTN: gemm_weight(b->in_w, b->ln_from_stats, 3 * b->c, b->c); gemm_weight(b->out_w, false, 0, 0); break;
+            case BT_DOWN: gemm_weight(b->conv_w, false, 0, 0); break;
+            case BT_UP: gemm_weight(b->conv_w, b->ln_from_stats, 4 * b->c_to, b->c_from); break;
+            default: break;
+        }
+        gemm_weight(m->clf_w, m->clf_from_stats, c.c_out * p2, c.c_hidden[0]);
+        gemm_weight(m->out_mapper, false, 0, 0);
     }
     m->n_attn = n_attn;
     m->c_max = 0;
@@ -281,10 +290,7 @@ extern "C" int paella_unet_create(const paella_unet_config* cfg, paella_unet** o
 
 extern "C" void paella_unet_destroy(paella_unet* m) {
     if (!m) return;
-    for (auto& kv : m->t) if (kv.second.p) (void)hipFree(kv.second.p);
-    for (auto& kv : m->wsum) if (kv.second.p) (void)hipFree(kv.second.p);
-    for (auto& kv : m->wsum16) if (kv.second.p) (void)hipFree(kv.second.p);
-    for (auto& kv : m->t16) if (kv.second.p) (void)hipFree(kv.second.p);
+    for (auto& kv : m->t) weight_free(kv.second);
     if (m->kv_w.p) (void)hipFree(m->kv_w.p);
     if (m->kv_b.p) (void)hipFree(m->kv_b.p);
     if (m->ts_w.p) (void)hipFree(m->ts_w.p);
@@ -294,6 +300,19 @@ extern "C" void paella_unet_destroy(paella_unet* m) {
 }
 
 // shared by the UNet and VQGAN loaders
+void weight_free(Weight& t) {
+    if (t.w.p) (void)hipFree(t.w.p);
+    if (t.w16.p) (void)hipFree(t.w16.p);
+    if (t.wsum.p) (void)hipFree(t.wsum.p);
+    if (t.wsum16.p) (void)hipFree(t.wsum16.p);
+}
+int weight_make_shadow(Weight& t, hipStream_t st) {
+    DevBuf16& d = t.w16;
+    if (d.p && d.n != t.w.n) { (void)hipFree(d.p); d.p = nullptr; }
+    if (!d.p) HIP_CHECK_RET(hipMalloc((void**)&d.p, t.w.n * sizeof(unsigned short)));
+    d.n = t.w.n;
+    return launch_f32_to_bf16(t.w.p, d.p, d.n, st);
+}
 int repack_into(Repack kind, const float* src, const std::vector<int64_t>& shape, DevBuf& dst, hipStream_t st) {
     int64_t numel = 1;
     for (int64_t d : shape) numel *= d;
@@ -337,9 +356,9 @@ extern "C" int paella_unet_load_tensor(paella_unet* m, const char* key, const fl
                                        void* stream) {
     if (!m || !key || !dev_src) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
-    auto it = m->specs.find(key);
-    if (it == m->specs.end()) { paella_set_error("unexpected state-dict key '%s'", key); return PAELLA_ERR_ARG; }
-    const TensorSpec& sp = it->second;
+    auto it = m->t.find(key);
+    if (it == m->t.end()) { paella_set_error("unexpected state-dict key '%s'", key); return PAELLA_ERR_ARG; }
+    const Weight& sp = it->second;
     if ((int)sp.shape.size() != ndim) { paella_set_error("%s: expected %d dims, got %d", key, (int)sp.shape.size(), ndim); return PAELLA_ERR_ARG; }
     int64_t numel = 1;
     for (int d = 0; d < ndim; ++d) {
@@ -347,7 +366,7 @@ extern "C" int paella_unet_load_tensor(paella_unet* m, const char* key, const fl
         numel *= shape[d];
     }
     const int p2 = m->cfg.patch_size * m->cfg.patch_size;
-    DevBuf& dst = m->t[key];
+    DevBuf& dst = it->second.w;
     switch (sp.kind) {
         case RP_TS_W:
             HIP_CHECK_RET(hipMemcpyAsync(m->ts_w.p + (size_t)sp.aux * m->cfg.c_r, dev_src, numel * sizeof(float), hipMemcpyDeviceToDevice, st));
@@ -390,47 +409,12 @@ extern "C" int paella_unet_set_timestep_freqs(paella_unet* m, const float* host_
 
 // bf16 shadow copies of every weight a bf16 GEMM of the forward reads (+ row sums of the rounded LayerNorm-consuming ones), from the tensors as loaded now
 static int make_shadows(paella_unet* m, hipStream_t st) {
-    std::vector<std::pair<std::string, std::pair<int, int>>> ln;  // LayerNorm-consuming weights: key -> (N, K) of the repacked matrix
-    std::vector<std::string> keys;
-    auto want = [&](const Block& b) {
-        switch (b.type) {
-            case BT_RES: case BT_FF:
-                keys.push_back(b.prefix + ".channelwise.0.weight");
-                keys.push_back(b.prefix + ".channelwise.4.weight");
-                break;
-            case BT_ATTN:
-                keys.push_back(b.prefix + ".attention.attn.in_proj_weight");
-                keys.push_back(b.prefix + ".attention.attn.out_proj.weight");
-                if (b.ln_from_stats) ln.push_back({b.prefix + ".attention.attn.in_proj_weight", {3 * b.c, b.c}});
-                break;
-            case BT_DOWN: keys.push_back(b.prefix + ".1.weight"); break;
-            case BT_UP:
-                keys.push_back(b.prefix + ".1.weight");
-                if (b.ln_from_stats) ln.push_back({b.prefix + ".1.weight", {4 * b.c_to, b.c_from}});
-                break;
-            default: break;
-        }
-    };
-    for (const Block& b : m->down) want(b);
-    for (const Block& b : m->up) want(b);
-    keys.push_back("clf.1.weight");
-    keys.push_back("out_mapper.1.weight");
-    if (m->clf_from_stats) ln.push_back({"clf.1.weight", {m->cfg.c_out * m->cfg.patch_size * m->cfg.patch_size, m->cfg.c_hidden[0]}});
-    for (const std::string& k : keys) {
-        auto it = m->t.find(k);
-        if (it == m->t.end() || !it->second.p || (it->second.n & 7)) continue;
-        DevBuf16& d = m->t16[k];
-        if (d.p && d.n != it->second.n) { (void)hipFree(d.p); d.p = nullptr; }
-        if (!d.p) HIP_CHECK_RET(hipMalloc((void**)&d.p, it->second.n * sizeof(unsigned short)));
-        d.n = it->second.n;
-        RET_IF(launch_f32_to_bf16(it->second.p, d.p, d.n, st));
-    }
-    for (auto& t : ln) {
-        auto it = m->t16.find(t.first);
-        if (it == m->t16.end() || (t.second.second & 7)) continue;
-        DevBuf& dst = m->wsum16[t.first];
-        RET_IF(devbuf_alloc(dst, (size_t)t.second.first));
-        RET_IF(launch_rowsum_bf16(it->second.p, dst.p, t.second.first, t.second.second, st));
+    for (Weight* t : m->shadowed)
+        if (t->w.p && !(t->w.n & 7)) RET_IF(weight_make_shadow(*t, st));
+    for (const LnWeight& l : m->ln_weights) {
+        if (!l.t->w16.p || (l.K & 7)) continue;
+        RET_IF(devbuf_alloc(l.t->wsum16, (size_t)l.N));
+        RET_IF(launch_rowsum_bf16(l.t->w16.p, l.t->wsum16.p, l.N, l.K, st));
     }
     HIP_CHECK_RET(hipStreamSynchronize(st));
     return PAELLA_OK;
@@ -454,35 +438,25 @@ extern "C" int paella_unet_get_precision(const paella_unet* m) { return m ? m->p
 
 extern "C" int paella_unet_finalize(paella_unet* m, void* stream) {
     if (!m) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
-    for (auto& kv : m->specs) {
-        auto it = m->t.find(kv.first);
-        if (it == m->t.end() || !it->second.loaded) { paella_set_error("tensor '%s' was never loaded", kv.first.c_str()); return PAELLA_ERR_STATE; }
-    }
+    for (auto& kv : m->t)
+        if (!kv.second.w.loaded) { paella_set_error("tensor '%s' was never loaded", kv.first.c_str()); return PAELLA_ERR_STATE; }
     // Row sums of every weight whose GEMM consumes LayerNorm-from-statistics (the LayerNorm is folded into that GEMM's epilogue: gemm.hip, ln_row_stats):
     // wsum[n] = sum_k W[n][k], as one M = 1 GEMM over a vector of ones per weight.
     {
         hipStream_t st = (hipStream_t)stream;
-        std::vector<std::pair<std::string, std::pair<int, int>>> todo;  // key -> (N, K) of the repacked matrix
-        auto want = [&](const Block& b) {
-            if (b.type == BT_ATTN && b.ln_from_stats) todo.push_back({b.prefix + ".attention.attn.in_proj_weight", {3 * b.c, b.c}});
-            if (b.type == BT_UP && b.ln_from_stats) todo.push_back({b.prefix + ".1.weight", {4 * b.c_to, b.c_from}});
-        };
-        for (const Block& b : m->down) want(b);
-        for (const Block& b : m->up) want(b);
-        if (m->clf_from_stats) todo.push_back({"clf.1.weight", {m->cfg.c_out * m->cfg.patch_size * m->cfg.patch_size, m->cfg.c_hidden[0]}});
+        const std::vector<LnWeight>& todo = m->ln_weights;
         if (!todo.empty()) {
             int kmax = 0;
-            for (auto& t : todo) kmax = t.second.second > kmax ? t.second.second : kmax;
+            for (const LnWeight& l : todo) kmax = l.K > kmax ? l.K : kmax;
             std::vector<float> ones_h((size_t)kmax, 1.0f);
             DevBuf ones;
             RET_IF(devbuf_alloc(ones, (size_t)kmax));
             HIP_CHECK_RET(hipMemcpyAsync(ones.p, ones_h.data(), (size_t)kmax * sizeof(float), hipMemcpyHostToDevice, st));
             int rc = PAELLA_OK;
-            for (auto& t : todo) {
-                DevBuf& dst = m->wsum[t.first];
-                rc = devbuf_alloc(dst, (size_t)t.second.first);
+            for (const LnWeight& l : todo) {
+                rc = devbuf_alloc(l.t->wsum, (size_t)l.N);
                 if (rc != PAELLA_OK) break;
-                GemmArgs g = gemm_args(ones.p, t.second.second, T(m, t.first), t.second.second, dst.p, t.second.first, 1, t.second.first, t.second.second);
+                GemmArgs g = gemm_args(ones.p, l.K, l.t->w.p, l.K, l.t->wsum.p, l.N, 1, l.N, l.K);
                 rc = launch_gemm_cfg(g, 5, 1, nullptr, 0, st);  // explicit fp32 tile, one tile per workgroup (no workspace needed)
                 if (rc != PAELLA_OK) break;
             }
@@ -510,16 +484,16 @@ extern "C" int paella_unet_finalize(paella_unet* m, void* stream) {
         auto compose = [&](const Block& b) -> int {
             if (b.type != BT_ATTN) return PAELLA_OK;
             const int ch = b.c;
-            const float* win = T(m, b.prefix + ".attention.attn.in_proj_weight") + (size_t)ch * ch;  // rows c .. 3c
-            const float* bin = T(m, b.prefix + ".attention.attn.in_proj_bias") + ch;
+            const float* win = b.in_w->w.p + (size_t)ch * ch;  // rows c .. 3c
+            const float* bin = b.in_b->w.p + ch;
             const int64_t shp[2] = {ch, cc};
             const int perm[2] = {1, 0};
-            RET_IF(launch_permute(T(m, b.prefix + ".kv_mapper.1.weight"), wkv_t.p, shp, perm, 2, st));  // [ch, cc] -> [cc, ch]
+            RET_IF(launch_permute(b.kv_w->w.p, wkv_t.p, shp, perm, 2, st));  // [ch, cc] -> [cc, ch]
             // kv_w rows [col, col + 2ch): C[2ch, cc] = Win[c:3c] [2ch, ch] . (Wkv^T [cc, ch])^T
             GemmArgs g = gemm_args(win, ch, wkv_t.p, ch, m->kv_w.p + (size_t)m->kv_col[b.attn_index] * cc, cc, 2 * ch, cc, ch);
             RET_IF(launch_gemm_cfg(g, 18, 1, nullptr, 0, st));  // (explicit fp32 tile: never the bf16 fast mode)
             // kv_b: C[1, 2ch] = bkv [1, ch] . Win[c:3c]^T + bin[c:3c]
-            GemmArgs gb = gemm_args(T(m, b.prefix + ".kv_mapper.1.bias"), ch, win, ch, m->kv_b.p + m->kv_col[b.attn_index], 2 * ch, 1, 2 * ch, ch);
+            GemmArgs gb = gemm_args(b.kv_b->w.p, ch, win, ch, m->kv_b.p + m->kv_col[b.attn_index], 2 * ch, 1, 2 * ch, ch);
             gb.ep.bias = bin;
             RET_IF(launch_gemm_cfg(gb, 5, 1, nullptr, 0, st));
             return PAELLA_OK;
@@ -628,24 +602,24 @@ static int compute_c_embed(const paella_unet* m, const float* byt5, int S_byt5, 
     const size_t skb = kSplitKBudget;
     const int cc = c.c_cond;
     if (S_byt5 > 0) {
-        GemmArgs g = gemm_args(byt5, c.byt5_embd, T(m, "byt5_mapper.weight"), c.byt5_embd, c_embed, cc, B * S_byt5, cc, c.byt5_embd);
-        g.ep.bias = T(m, "byt5_mapper.bias");
+        GemmArgs g = gemm_args(byt5, c.byt5_embd, m->byt5_w->w.p, c.byt5_embd, c_embed, cc, B * S_byt5, cc, c.byt5_embd);
+        g.ep.bias = m->byt5_b->w.p;
         g.ep.remap_in = S_byt5; g.ep.remap_out = S; g.ep.remap_off = 0;
         RET_IF(launch_gemm(g, splitk, skb, st));
     }
     int row_off = S_byt5;
     if (clip) {
-        GemmArgs g = gemm_args(clip, c.clip_embd, T(m, "clip_mapper.weight"), c.clip_embd, c_embed + (size_t)row_off * cc, S * cc, B,
+        GemmArgs g = gemm_args(clip, c.clip_embd, m->clip_w->w.p, c.clip_embd, c_embed + (size_t)row_off * cc, S * cc, B,
                                cc * c.clip_seq_len, c.clip_embd);
-        g.ep.bias = T(m, "clip_mapper.bias");
+        g.ep.bias = m->clip_b->w.p;
         RET_IF(launch_gemm(g, splitk, skb, st));
         row_off += c.clip_seq_len;
     }
     for (int i = 0; i < n_clip_image; ++i) {
         if (!clip_image || !clip_image[i]) { paella_set_error("clip_image[%d] is null", i); return PAELLA_ERR_ARG; }
-        GemmArgs g = gemm_args(clip_image[i], c.clip_embd, T(m, "clip_image_mapper.weight"), c.clip_embd,
+        GemmArgs g = gemm_args(clip_image[i], c.clip_embd, m->clip_image_w->w.p, c.clip_embd,
                                c_embed + (size_t)row_off * cc, S * cc, B, cc * c.clip_seq_len, c.clip_embd);
-        g.ep.bias = T(m, "clip_image_mapper.bias");
+        g.ep.bias = m->clip_image_b->w.p;
         RET_IF(launch_gemm(g, splitk, skb, st));
         row_off += c.clip_seq_len;
     }
@@ -725,20 +699,42 @@ extern "C" int paella_unet_cond_prepare_slots(paella_unet* m, const float* byt5,
 // ---------------------------------------------------------------------------
 struct FwdCtx {
     const paella_unet* m;
+    const paella_step_args& s;  // the block of this forward: grid, conditioning cache and per-request tables are read from it where they are used
     hipStream_t st;
     FwdBuffers f;
-    int B, H, W, S;
-    const float* cond;
-    const float* attn_w;
-    int n_aw;
-    const int* cond_len;  // ragged conditioning: device table [B] of conditioning rows per sample (S = slot pitch), or null
-    const float* kw_table;  // per-slot key weights (AttnArgs::kw_table / kw_len / kw_pitch) instead of attn_w, or null
-    const int* kw_len;
-    int kw_pitch;
-    const int* q_groups;  // per-query key groups (AttnArgs::q_groups / k_groups): [B, qg_pitch] with every level's queries in one row (level-major), [B, S]; or null
-    const int* k_groups;
-    int qg_pitch;
+    int B;  // samples in flight: s.n_unique over the shared prefix of a guided step, s.B after it
 };
+
+// The A operand of a GEMM g that consumes LayerNorm(x), x = `rows` rows of C channels of the residual stream, for the weight wt (w16 = its bf16 shadow where this
+// site may use it, else null).  from_stats: no launch -- the LayerNorm is folded into g's operand load from the producer's row statistics (fp32 x, or its bf16 copy
+// x16, with the matching row sums of the weight).  Otherwise one LayerNorm launch into h16 (bf16 GEMM) or h (g.A as the caller built it); s2d = 1 gathers the
+// 2x2 space-to-depth rows of an h x w grid on the way (down-sampler).
+static int ln_operand(FwdCtx& cx, GemmArgs& g, const Weight* wt, const unsigned short* w16, bool from_stats, const float* x, int64_t rows, int C, int s2d = 0,
+                      int h = 0, int w = 0) {
+    if (from_stats) {
+        g.A = x; g.ln_stats = cx.f.rowstat; g.ln_nblk = C / 16; g.ln_eps = 1e-6f; g.ln_wsum = wt->wsum.p;
+        if (w16) { g.A16 = cx.f.x16; g.W16 = w16; g.ln_wsum = wt->wsum16.p; }
+        return PAELLA_OK;
+    }
+    if (!w16) return launch_layernorm(x, cx.f.h, rows, C, 1e-6f, 1.f, 0.f, s2d, h, w, cx.st);
+    g.A16 = cx.f.h16; g.W16 = w16;
+    return launch_layernorm16(x, nullptr, cx.f.h16, rows, C, 1e-6f, 1.f, 0.f, s2d, h, w, cx.st);
+}
+
+// GEMM2 of an MLP block, x += A . W2^T + b2, with everything its epilogue carries: the bf16 copy of x and the row statistics for a LayerNorm-folding consumer, the
+// fused TimestepBlock.  The A-operand side (GRN prologue / bf16 operands) is the caller's.
+static GemmArgs mlp_gemm2(FwdCtx& cx, const Block& b, const float* A, float* x, int64_t rows, int rps) {
+    const int ch = b.c;
+    GemmArgs g2 = gemm_args(A, 4 * ch, b.w2->w.p, 4 * ch, x, ch, (int)rows, ch, 4 * ch);
+    g2.ep.bias = b.b2->w.p;
+    g2.ep.residual = x; g2.ep.ldr = ch;
+    if (cx.m->precision == 1 && b.emit_rowstat) g2.ep.c16 = cx.f.x16;  // (also where the block itself is not eligible for the bf16 GEMMs: the consumer may still be)
+    if (b.emit_rowstat) g2.ep.rowstat_out = cx.f.rowstat;
+    if (b.fused_ts >= 0) {
+        g2.ep.ts = cx.f.ts + b.fused_ts; g2.ep.ts_stride = cx.m->ts_total; g2.ep.rows_per_sample = rps;
+    }
+    return g2;
+}
 
 // ResBlock / FeedForwardBlock (reference src/modules.py:43-62, 82-96); x is updated in place
 static int run_mlp_block(FwdCtx& cx, const Block& b, float* x, const float* skip, int h, int w) {
@@ -746,43 +742,30 @@ static int run_mlp_block(FwdCtx& cx, const Block& b, float* x, const float* skip
     const int ch = b.c;
     const int64_t rows = (int64_t)cx.B * h * w;
     const int rps = h * w;
-    unsigned short* const x16 = (m->precision == 1 && b.emit_rowstat) ? cx.f.x16 : nullptr;  // bf16 copy of the block's output for a LayerNorm-folding bf16 consumer
-    const unsigned short* const w1_16 = T16(m, b.prefix + ".channelwise.0.weight");
-    const unsigned short* const w2_16 = T16(m, b.prefix + ".channelwise.4.weight");
-    if (w1_16 && w2_16 && (ch % 64) == 0 && (rps % 16) == 0) {
-        // ---- OPT-IN bf16 fast mode: depthwise conv + LayerNorm -> bf16 | GEMM1 (bf16 operands) -> GELU -> bf16 hidden + GRN statistics | GRN apply in place on the
-        // bf16 hidden tensor | GEMM2 (bf16 operands) -> fp32 residual stream.  The 4c-wide hidden tensor never exists in fp32.
-        if (b.type == BT_RES)
-            RET_IF(launch_dwconv_ln(x, skip, T(m, b.prefix + ".depthwise.weight"), T(m, b.prefix + ".depthwise.bias"), nullptr, cx.B, h, w, ch, 1e-6f, cx.st, cx.f.h16));
-        else
-            RET_IF(launch_layernorm16(x, nullptr, cx.f.h16, rows, ch, 1e-6f, 1.f, 0.f, 0, 0, 0, cx.st));
-        GemmArgs g1 = gemm_args(nullptr, ch, T(m, b.prefix + ".channelwise.0.weight"), ch, nullptr, 4 * ch, (int)rows, 4 * ch, ch);
-        g1.A16 = cx.f.h16; g1.W16 = w1_16;
-        g1.ep.bias = T(m, b.prefix + ".channelwise.0.bias");
-        g1.ep.act = ACT_GELU;
+    const float *gamma = b.gamma->w.p, *beta = b.beta->w.p;
+    const unsigned short* const w1_16 = W16(m, b.w1);
+    const unsigned short* const w2_16 = W16(m, b.w2);
+    // OPT-IN bf16 fast mode: depthwise conv + LayerNorm -> bf16 | GEMM1 (bf16 operands) -> GELU -> bf16 hidden + GRN statistics | GRN apply in place on the
+    // bf16 hidden tensor | GEMM2 (bf16 operands) -> fp32 residual stream.  The 4c-wide hidden tensor never exists in fp32.
+    const bool fast = w1_16 && w2_16 && (ch % 64) == 0 && (rps % 16) == 0;
+    GemmArgs g1 = gemm_args(fast ? nullptr : cx.f.h, ch, b.w1->w.p, ch, fast ? nullptr : cx.f.g, 4 * ch, (int)rows, 4 * ch, ch);
+    if (b.type == BT_RES) {
+        RET_IF(launch_dwconv_ln(x, skip, b.dw_w->w.p, b.dw_b->w.p, fast ? nullptr : cx.f.h, cx.B, h, w, ch, 1e-6f, cx.st, fast ? cx.f.h16 : nullptr));
+        if (fast) { g1.A16 = cx.f.h16; g1.W16 = w1_16; }
+    } else {
+        RET_IF(ln_operand(cx, g1, b.w1, fast ? w1_16 : nullptr, false, x, rows, ch));
+    }
+    g1.ep.bias = b.b1->w.p;
+    g1.ep.act = ACT_GELU;
+    if (fast) {
         g1.ep.c16 = cx.f.g16;
         g1.ep.sumsq_out = cx.f.grn_gx;
         RET_IF(launch_gemm(g1, cx.f.splitk, kSplitKBudget, cx.st));
-        RET_IF(launch_grn_partials_apply16(cx.f.grn_gx, T(m, b.prefix + ".channelwise.2.gamma"), T(m, b.prefix + ".channelwise.2.beta"), cx.f.grn_scale, cx.f.g16, cx.B, rps, 4 * ch, cx.st));
-        GemmArgs g2 = gemm_args(nullptr, 4 * ch, T(m, b.prefix + ".channelwise.4.weight"), 4 * ch, x, ch, (int)rows, ch, 4 * ch);
+        RET_IF(launch_grn_partials_apply16(cx.f.grn_gx, gamma, beta, cx.f.grn_scale, cx.f.g16, cx.B, rps, 4 * ch, cx.st));
+        GemmArgs g2 = mlp_gemm2(cx, b, nullptr, x, rows, rps);
         g2.A16 = cx.f.g16; g2.W16 = w2_16;
-        g2.ep.bias = T(m, b.prefix + ".channelwise.4.bias");
-        g2.ep.residual = x; g2.ep.ldr = ch;
-        g2.ep.c16 = x16;
-        if (b.emit_rowstat) g2.ep.rowstat_out = cx.f.rowstat;
-        if (b.fused_ts >= 0) {
-            g2.ep.ts = cx.f.ts + b.fused_ts; g2.ep.ts_stride = m->ts_total; g2.ep.rows_per_sample = rps;
-        }
-        RET_IF(launch_gemm(g2, cx.f.splitk, kSplitKBudget, cx.st));
-        return PAELLA_OK;
+        return launch_gemm(g2, cx.f.splitk, kSplitKBudget, cx.st);
     }
-    if (b.type == BT_RES)
-        RET_IF(launch_dwconv_ln(x, skip, T(m, b.prefix + ".depthwise.weight"), T(m, b.prefix + ".depthwise.bias"), cx.f.h, cx.B, h, w, ch, 1e-6f, cx.st));
-    else
-        RET_IF(launch_layernorm(x, cx.f.h, rows, ch, 1e-6f, 1.f, 0.f, 0, 0, 0, cx.st));
-    GemmArgs g1 = gemm_args(cx.f.h, ch, T(m, b.prefix + ".channelwise.0.weight"), ch, cx.f.g, 4 * ch, (int)rows, 4 * ch, ch);
-    g1.ep.bias = T(m, b.prefix + ".channelwise.0.bias");
-    g1.ep.act = ACT_GELU;
     const int fused_tile = (rps % 16 == 0 && m->precision == 0) ? gemm_grn_fused_tile((int)rows, 4 * ch, ch, rps, false) : 0;
     if (fused_tile) {
         // GlobalResponseNorm with NO launch of its own (batch-1 regime): GEMM1's tiles cover whole samples, so its epilogue finishes
@@ -792,104 +775,80 @@ static int run_mlp_block(FwdCtx& cx, const Block& b, float* x, const float* skip
         g1.ep.grn_gx_out = cx.f.grn_scale; g1.ep.grn_part_out = cx.f.grn_gx; g1.ep.grn_rps = rps; g1.ep.grn_np = np;
         g1.force_ring_cfg = fused_tile;
         RET_IF(launch_gemm(g1, cx.f.splitk, kSplitKBudget, cx.st));
-        GemmArgs g2 = gemm_args(cx.f.g, 4 * ch, T(m, b.prefix + ".channelwise.4.weight"), 4 * ch, x, ch, (int)rows, ch, 4 * ch);
-        g2.grn_gx = cx.f.grn_scale; g2.grn_part = cx.f.grn_gx; g2.grn_np = np; g2.grn_gamma = T(m, b.prefix + ".channelwise.2.gamma");
-        g2.a_shift = T(m, b.prefix + ".channelwise.2.beta");
+        GemmArgs g2 = mlp_gemm2(cx, b, cx.f.g, x, rows, rps);
+        g2.grn_gx = cx.f.grn_scale; g2.grn_part = cx.f.grn_gx; g2.grn_np = np; g2.grn_gamma = gamma;
+        g2.a_shift = beta;
         g2.a_rows_per_sample = rps;
-        g2.ep.bias = T(m, b.prefix + ".channelwise.4.bias");
-        g2.ep.residual = x; g2.ep.ldr = ch;
-        if (b.emit_rowstat) g2.ep.rowstat_out = cx.f.rowstat;
-        if (b.fused_ts >= 0) {
-            g2.ep.ts = cx.f.ts + b.fused_ts; g2.ep.ts_stride = m->ts_total; g2.ep.rows_per_sample = rps;
-        }
-        RET_IF(launch_gemm(g2, cx.f.splitk, kSplitKBudget, cx.st));
-        return PAELLA_OK;
+        return launch_gemm(g2, cx.f.splitk, kSplitKBudget, cx.st);
     }
     if (rps % 16 == 0) {
         // GRN statistics ride on GEMM1's epilogue (per-16-row column sums of squares), then one tiny finalize launch
         g1.ep.sumsq_out = cx.f.grn_gx;
         RET_IF(launch_gemm(g1, cx.f.splitk, kSplitKBudget, cx.st));
-        RET_IF(launch_grn_from_partials(cx.f.grn_gx, T(m, b.prefix + ".channelwise.2.gamma"), cx.f.grn_scale, cx.B, rps / 16, 4 * ch, cx.st));
+        RET_IF(launch_grn_from_partials(cx.f.grn_gx, gamma, cx.f.grn_scale, cx.B, rps / 16, 4 * ch, cx.st));
     } else {
         RET_IF(launch_gemm(g1, cx.f.splitk, kSplitKBudget, cx.st));
-        RET_IF(launch_grn_scale(cx.f.g, T(m, b.prefix + ".channelwise.2.gamma"), cx.f.grn_scale, cx.f.grn_gx, cx.B, rps, 4 * ch, cx.st));
+        RET_IF(launch_grn_scale(cx.f.g, gamma, cx.f.grn_scale, cx.f.grn_gx, cx.B, rps, 4 * ch, cx.st));
     }
-    GemmArgs g2 = gemm_args(cx.f.g, 4 * ch, T(m, b.prefix + ".channelwise.4.weight"), 4 * ch, x, ch, (int)rows, ch, 4 * ch);
+    GemmArgs g2 = mlp_gemm2(cx, b, cx.f.g, x, rows, rps);
     g2.a_scale = cx.f.grn_scale;
-    g2.a_shift = T(m, b.prefix + ".channelwise.2.beta");
+    g2.a_shift = beta;
     g2.a_rows_per_sample = rps;
-    g2.ep.bias = T(m, b.prefix + ".channelwise.4.bias");
-    g2.ep.residual = x; g2.ep.ldr = ch;
-    g2.ep.c16 = x16;  // (bf16 mode, block not eligible for the bf16 GEMMs: the consumer may still be)
-    if (b.emit_rowstat) g2.ep.rowstat_out = cx.f.rowstat;
-    if (b.fused_ts >= 0) {
-        g2.ep.ts = cx.f.ts + b.fused_ts; g2.ep.ts_stride = m->ts_total; g2.ep.rows_per_sample = rps;
-    }
-    RET_IF(launch_gemm(g2, cx.f.splitk, kSplitKBudget, cx.st));
-    return PAELLA_OK;
+    return launch_gemm(g2, cx.f.splitk, kSplitKBudget, cx.st);
 }
 
 // AttnBlock (reference src/modules.py:65-79)
 static int run_attn_block(FwdCtx& cx, const Block& b, float* x, int h, int w) {
     const paella_unet* m = cx.m;
+    const paella_step_args& s = cx.s;
     const int ch = b.c;
     const int64_t rows = (int64_t)cx.B * h * w;
     const int nh = m->cfg.nhead[b.level];
     const bool self = m->cfg.self_attn != 0;
     const int nq = self ? 3 * ch : ch;
-    GemmArgs gq = gemm_args(cx.f.h, ch, T(m, b.prefix + ".attention.attn.in_proj_weight"), ch, cx.f.g, nq, (int)rows, nq, ch);
+    GemmArgs gq = gemm_args(cx.f.h, ch, b.in_w->w.p, ch, cx.f.g, nq, (int)rows, nq, ch);
     // opt-in bf16 fast mode: both projections on bf16 operands (bf16 copy of the residual stream / bf16 LayerNorm output in, bf16 attention output in); q, k, v and
     // the attention itself stay fp32
-    const unsigned short* const wq16 = (ch % 64) == 0 ? T16(m, b.prefix + ".attention.attn.in_proj_weight") : nullptr;
-    const unsigned short* const wo16 = (ch % 64) == 0 ? T16(m, b.prefix + ".attention.attn.out_proj.weight") : nullptr;
-    if (b.ln_from_stats) {  // LayerNorm folded into the in-projection's operand load (statistics from the producer's epilogue)
-        gq.A = x; gq.ln_stats = cx.f.rowstat; gq.ln_nblk = ch / 16; gq.ln_eps = 1e-6f;
-        gq.ln_wsum = m->wsum.at(b.prefix + ".attention.attn.in_proj_weight").p;
-        if (wq16) { gq.A16 = cx.f.x16; gq.W16 = wq16; gq.ln_wsum = m->wsum16.at(b.prefix + ".attention.attn.in_proj_weight").p; }
-    } else if (wq16) {
-        RET_IF(launch_layernorm16(x, nullptr, cx.f.h16, rows, ch, 1e-6f, 1.f, 0.f, 0, 0, 0, cx.st));
-        gq.A16 = cx.f.h16; gq.W16 = wq16;
-    } else {
-        RET_IF(launch_layernorm(x, cx.f.h, rows, ch, 1e-6f, 1.f, 0.f, 0, 0, 0, cx.st));
-    }
-    gq.ep.bias = T(m, b.prefix + ".attention.attn.in_proj_bias");
+    const unsigned short* const wq16 = (ch % 64) == 0 ? W16(m, b.in_w) : nullptr;
+    const unsigned short* const wo16 = (ch % 64) == 0 ? W16(m, b.out_w) : nullptr;
+    RET_IF(ln_operand(cx, gq, b.in_w, wq16, b.ln_from_stats, x, rows, ch));
+    gq.ep.bias = b.in_b->w.p;
     // bf16 fast mode at >= 256 queries: q / k / v leave the in-projection as bf16 only and the attention core runs on bf16 MFMA (attention_bf16_kernel)
     const bool attn16 = wq16 && wo16 && h * w >= 256 && (nq % 8) == 0 && ((ch / nh) % 16) == 0 && ch / nh >= 32;
     if (attn16) { gq.C = nullptr; gq.ep.c16 = cx.f.g16; }
     RET_IF(launch_gemm(gq, cx.f.splitk, kSplitKBudget, cx.st));
-    const float* kv = cx.cond + m->kv_col[b.attn_index];
+    const float* kv = (const float*)s.cond + m->kv_col[b.attn_index];
     AttnArgs a;
     a.q = cx.f.g; a.ldq = nq;
     a.k_self = self ? cx.f.g + ch : nullptr; a.v_self = self ? cx.f.g + 2 * ch : nullptr; a.ld_self = nq;
     a.k_cond = kv; a.v_cond = kv + ch; a.ld_cond = m->kv_total;
     a.out = cx.f.h; a.ldo = ch;
-    a.B = cx.B; a.nhead = nh; a.D = ch / nh; a.Lq = h * w; a.Lself = self ? h * w : 0; a.Lcond = cx.S;
+    a.B = cx.B; a.nhead = nh; a.D = ch / nh; a.Lq = h * w; a.Lself = self ? h * w : 0; a.Lcond = s.S;
     a.scale = 1.0f / sqrtf((float)(ch / nh));
-    a.key_weights = cx.attn_w; a.n_kw = cx.n_aw;
+    a.key_weights = s.attn_weights; a.n_kw = s.attn_weights ? s.n_attn_weights : 0;
     a.out16 = wo16 ? cx.f.h16 : nullptr;
     a.q16 = nullptr; a.k_self16 = nullptr; a.v_self16 = nullptr; a.ld16 = 0;
-    a.cond_len = cx.cond_len;
-    a.kw_table = cx.kw_table; a.kw_len = cx.kw_len; a.kw_pitch = cx.kw_pitch;
-    if (cx.q_groups) {  // this level's queries sit at off = sum over the finer levels of their query counts inside a row of the table
+    a.cond_len = s.cond_len;  // ragged conditioning: conditioning rows per sample, S then being the slot pitch
+    if (s.kw_len) { a.kw_table = s.kw_table; a.kw_len = s.kw_len; a.kw_pitch = s.kw_pitch; }  // per-slot key weights instead of attn_weights
+    if (s.q_groups) {  // per-query key groups: this level's queries sit at off = sum over the finer levels of their query counts inside a row of the table
         const int p = m->cfg.patch_size;
         int off = 0;
-        for (int l = 0; l < b.level; ++l) off += ((cx.H / p) >> l) * ((cx.W / p) >> l);
-        a.q_groups = cx.q_groups + off; a.qg_pitch = cx.qg_pitch;
-        a.k_groups = cx.k_groups; a.kg_pitch = cx.S;
+        for (int l = 0; l < b.level; ++l) off += ((s.H / p) >> l) * ((s.W / p) >> l);
+        a.q_groups = s.q_groups + off; a.qg_pitch = s.qg_pitch;
+        a.k_groups = s.k_groups; a.kg_pitch = s.S;
     }
     if (attn16) {
         a.q16 = cx.f.g16; a.ld16 = nq;
         a.k_self16 = self ? cx.f.g16 + ch : nullptr; a.v_self16 = self ? cx.f.g16 + 2 * ch : nullptr;
     }
     RET_IF(launch_attention(a, cx.st));
-    GemmArgs go = gemm_args(cx.f.h, ch, T(m, b.prefix + ".attention.attn.out_proj.weight"), ch, x, ch, (int)rows, ch, ch);
+    GemmArgs go = gemm_args(cx.f.h, ch, b.out_w->w.p, ch, x, ch, (int)rows, ch, ch);
     if (wo16) { go.A16 = cx.f.h16; go.W16 = wo16; }
-    go.ep.bias = T(m, b.prefix + ".attention.attn.out_proj.bias");
+    go.ep.bias = b.out_b->w.p;
     go.ep.residual = x; go.ep.ldr = ch;
     if (m->precision == 1 && b.emit_rowstat) go.ep.c16 = cx.f.x16;
     if (b.emit_rowstat) go.ep.rowstat_out = cx.f.rowstat;
-    RET_IF(launch_gemm(go, cx.f.splitk, kSplitKBudget, cx.st));
-    return PAELLA_OK;
+    return launch_gemm(go, cx.f.splitk, kSplitKBudget, cx.st);
 }
 
 extern "C" int paella_unet_forward(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int H, int W,
@@ -908,22 +867,11 @@ extern "C" int paella_unet_forward(paella_unet* m, const int64_t* tokens, const 
 // mix_c * LN(z_cond) + mix_u * LN(z_uncond) and logits_out receives the n_unique MIXED rows (half the head FLOPs and logits bytes).
 // `tail` != nullptr: the head GEMM runs with the fused sampling-tail epilogue (no logits are stored; tail->tokens_out receives
 // the sampled tokens of the B (or, with the guidance mix, n_unique) output rows); logits_out is then unused.
-// Per-request prompt weights: one row of post-softmax key multipliers per conditioning SLOT of the launch (B rows: a guided step's two halves carry independent
-// rows) instead of the one attn_weights vector.  len == nullptr = no table.
-struct KwTable {
-    const float* table;  // DEVICE fp32 [B, pitch]
-    const int* len;      // DEVICE int32 [B]
-    int pitch;
-};
-// Regional prompts: per-query key groups (AttnArgs::q_groups / k_groups) for every attention block of a forward.  q [nb, q_pitch] holds one row per conditioning
-// slot of the launch with the queries of all levels, level-major (level l at offset sum_{j<l} (H/patch)(W/patch)/4^j); k [nb, k_pitch] one mask per row of a slot.
-// q == nullptr = no tables.
-struct RgTable {
-    const int* q;  // DEVICE int32 [nb, q_pitch]
-    int q_pitch;
-    const int* k;  // DEVICE int32 [nb, k_pitch]
-    int k_pitch;
-};
+// Per-request prompt weights (s.kw_table / kw_len / kw_pitch): one row of post-softmax key multipliers per conditioning SLOT of the launch (B rows: a guided step's
+// two halves carry independent rows) instead of the one attn_weights vector.  kw_len == nullptr = no table.
+// Regional prompts (s.q_groups / k_groups): per-query key groups for every attention block of a forward.  q [nb, qg_pitch] holds one row per conditioning slot of
+// the launch with the queries of all levels, level-major (level l at offset sum_{j<l} (H/patch)(W/patch)/4^j); k [nb, kg_pitch] one mask per row of a slot.
+// q_groups == nullptr = no tables.
 static int unet_query_total(const paella_unet* m, int H, int W) {
     const int p = m->cfg.patch_size;
     int tot = 0;
@@ -931,45 +879,38 @@ static int unet_query_total(const paella_unet* m, int H, int W) {
     return tot;
 }
 // validated BEFORE anything is enqueued (the model may be null here: the checks that need it come after the ones that do not)
-static int rg_table_check(const char* who, const paella_unet* m, RgTable rg, int H, int W, int S) {
-    if (!rg.q && !rg.k) return PAELLA_OK;
-    if (!rg.q || !rg.k) { paella_set_error("%s: q_groups and k_groups must be given together (one key-group table without the other)", who); return PAELLA_ERR_ARG; }
-    if (rg.k_pitch < S || rg.q_pitch < 1) { paella_set_error("%s: key-group pitches too small (kg_pitch %d < S %d, or qg_pitch %d < 1)", who, rg.k_pitch, S, rg.q_pitch); return PAELLA_ERR_ARG; }
+static int rg_table_check(const char* who, const paella_unet* m, const paella_step_args& s) {
+    if (!s.q_groups && !s.k_groups) return PAELLA_OK;
+    if (!s.q_groups || !s.k_groups) { paella_set_error("%s: q_groups and k_groups must be given together (one key-group table without the other)", who); return PAELLA_ERR_ARG; }
+    if (s.kg_pitch < s.S || s.qg_pitch < 1) { paella_set_error("%s: key-group pitches too small (kg_pitch %d < S %d, or qg_pitch %d < 1)", who, s.kg_pitch, s.S, s.qg_pitch); return PAELLA_ERR_ARG; }
     if (!m) { paella_set_error("%s: null model", who); return PAELLA_ERR_ARG; }
     if (m->precision == 1) { paella_set_error("%s: the key-group tables are not offered in the bf16 precision mode", who); return PAELLA_ERR_ARG; }
     const int p = m->cfg.patch_size, div = p << (m->cfg.n_levels - 1);
-    if (H <= 0 || W <= 0 || H % div || W % div) { paella_set_error("%s: token grid %dx%d must be a positive multiple of %d", who, H, W, div); return PAELLA_ERR_ARG; }
-    if (rg.q_pitch < unet_query_total(m, H, W)) {
-        paella_set_error("%s: qg_pitch %d smaller than the %d queries of all levels of a %dx%d grid", who, rg.q_pitch, unet_query_total(m, H, W), H, W);
+    if (s.H <= 0 || s.W <= 0 || s.H % div || s.W % div) { paella_set_error("%s: token grid %dx%d must be a positive multiple of %d", who, s.H, s.W, div); return PAELLA_ERR_ARG; }
+    if (s.qg_pitch < unet_query_total(m, s.H, s.W)) {
+        paella_set_error("%s: qg_pitch %d smaller than the %d queries of all levels of a %dx%d grid", who, s.qg_pitch, unet_query_total(m, s.H, s.W), s.H, s.W);
         return PAELLA_ERR_ARG;
     }
     return PAELLA_OK;
 }
 
-static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float* r, const void* cond, int B, int n_unique,
-                             float mix_c, float mix_u, int H, int W, int S, const float* attn_weights,
-                             int n_attn_weights, float* logits_out, const TailArgs* tail, void* ws, size_t ws_bytes, void* stream,
-                             const float* mix_pairs = nullptr,    // request batch: a DEVICE table [n_unique, 2] of guidance pairs instead of (mix_c, mix_u)
-                             const int* cond_len = nullptr,       // ragged conditioning: a DEVICE table [B] of conditioning rows per sample, S is then the slot pitch of `cond`
-                             KwTable kw = {nullptr, nullptr, 0},  // per-request prompt weights instead of attn_weights (which must then be null)
-                             RgTable rg = {nullptr, 0, nullptr, 0}) {  // regional prompts: per-query key groups (checked by the caller: rg_table_check)
+// One forward as its block s describes it (rules checked by run_step_block); tail = the converted tail block of a fused step (s.logits_out is then unused), or null.
+static int unet_forward_impl(paella_unet* m, const paella_step_args& s, const TailArgs* tail, void* ws, size_t ws_bytes, void* stream) {
     if (!m || !m->finalized) { paella_set_error("model not finalized"); return PAELLA_ERR_STATE; }
-    if (!tokens || !r || (!logits_out && !tail)) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
+    if (!s.tokens || !s.r || (!s.logits_out && !tail)) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
     const paella_unet_config& c = m->cfg;
     const int p = c.patch_size;
     const int div = p << (c.n_levels - 1);
+    const int H = s.H, W = s.W, n_unique = s.n_unique;
+    int B = s.B;
     if (B <= 0 || H <= 0 || W <= 0 || H % div || W % div) {
         paella_set_error("token grid %dx%d must be a positive multiple of %d", H, W, div);
         return PAELLA_ERR_ARG;
     }
-    if (m->n_attn > 0 && (!cond || S <= 0)) { paella_set_error("conditioning cache missing"); return PAELLA_ERR_ARG; }
-    FwdCtx cx;
-    cx.m = m; cx.st = (hipStream_t)stream; cx.B = B; cx.H = H; cx.W = W; cx.S = S;
-    cx.cond = (const float*)cond; cx.attn_w = attn_weights; cx.n_aw = attn_weights ? n_attn_weights : 0; cx.cond_len = cond_len;
-    cx.kw_table = kw.len ? kw.table : nullptr; cx.kw_len = kw.len; cx.kw_pitch = kw.len ? kw.pitch : 0;
-    cx.q_groups = rg.q; cx.k_groups = rg.q ? rg.k : nullptr; cx.qg_pitch = rg.q_pitch;
+    if (m->n_attn > 0 && (!s.cond || s.S <= 0)) { paella_set_error("conditioning cache missing"); return PAELLA_ERR_ARG; }
+    FwdCtx cx = {m, s, (hipStream_t)stream, {}, B};
     Arena a(ws, ws_bytes);
-    carve_forward(m, a, B, H, W, S, cx.f);
+    carve_forward(m, a, B, H, W, s.S, cx.f);
     if (!a.ok || !ws) { paella_set_error("workspace too small (%zu needed, %zu given)", a.off, ws_bytes); return PAELLA_ERR_WORKSPACE; }
     hipStream_t st = cx.st;
     FwdBuffers& f = cx.f;
@@ -977,7 +918,7 @@ static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float*
     for (size_t i = 0; i < m->down.size(); ++i)
         if (m->down[i].type == BT_ATTN) { split = (int)i; break; }
     if (n_unique <= 0 || n_unique > B || B % n_unique) { paella_set_error("n_unique must divide B"); return PAELLA_ERR_ARG; }
-    const bool mix = mix_pairs || mix_c != 0.f || mix_u != 0.f;
+    const bool mix = s.mix_pairs || s.mix_c != 0.f || s.mix_u != 0.f;
     if (mix && B != 2 * n_unique) { paella_set_error("guidance mix needs B == 2 * n_unique"); return PAELLA_ERR_ARG; }
     const int Bfull = B;
     if (n_unique < B) {  // tokens / r hold the n_unique distinct rows: the prefix runs on them only
@@ -987,15 +928,15 @@ static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float*
 
     // timestep embedding + all TimestepBlock mappers
     if (m->ts_total > 0)
-        RET_IF(launch_timestep(r, m->freqs.p, m->ts_w.p, m->ts_b.p, f.ts, B, c.c_r, m->ts_total, 10000.0f, f.remb, Bfull / B, st));
+        RET_IF(launch_timestep(s.r, m->freqs.p, m->ts_w.p, m->ts_b.p, f.ts, B, c.c_r, m->ts_total, 10000.0f, f.remb, Bfull / B, st));
 
     // in_mapper + PixelUnshuffle + embedding conv + LayerNorm2d   (src/modules.py:126-134,271)
     const int h0 = H / p, w0 = W / p;
     const int64_t n0 = (int64_t)B * h0 * w0;
-    RET_IF(launch_embed_ln_unshuffle(tokens, T(m, "in_mapper.0.weight"), f.h, B, H, W, c.c_in, p, c.num_labels, 1e-6f, st));
+    RET_IF(launch_embed_ln_unshuffle(s.tokens, m->in_mapper->w.p, f.h, B, H, W, c.c_in, p, c.num_labels, 1e-6f, st));
     {
-        GemmArgs g = gemm_args(f.h, c.c_in * p * p, T(m, "embedding.1.weight"), c.c_in * p * p, f.g, c.c_hidden[0], (int)n0, c.c_hidden[0], c.c_in * p * p);
-        g.ep.bias = T(m, "embedding.1.bias");
+        GemmArgs g = gemm_args(f.h, c.c_in * p * p, m->embedding_w->w.p, c.c_in * p * p, f.g, c.c_hidden[0], (int)n0, c.c_hidden[0], c.c_in * p * p);
+        g.ep.bias = m->embedding_b->w.p;
         RET_IF(launch_gemm(g, f.splitk, kSplitKBudget, st));
         RET_IF(launch_layernorm(f.g, f.xl[0], n0, c.c_hidden[0], 1e-6f, 1.f, 0.f, 0, 0, 0, st));
     }
@@ -1030,13 +971,11 @@ static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float*
         switch (b.type) {
             case BT_DOWN: {  // LayerNorm2d + Conv2d(k2,s2): LN fused with the space-to-depth gather, then a GEMM
                 const int64_t rows_in = (int64_t)B * h * w;
-                const unsigned short* const w16 = ((4 * b.c_from) % 64) == 0 ? T16(m, b.prefix + ".1.weight") : nullptr;
-                if (w16) RET_IF(launch_layernorm16(x, nullptr, f.h16, rows_in, b.c_from, 1e-6f, 1.f, 0.f, 1, h, w, st));
-                else RET_IF(launch_layernorm(x, f.h, rows_in, b.c_from, 1e-6f, 1.f, 0.f, 1, h, w, st));
+                const unsigned short* const w16 = ((4 * b.c_from) % 64) == 0 ? W16(m, b.conv_w) : nullptr;
+                GemmArgs g = gemm_args(f.h, 4 * b.c_from, b.conv_w->w.p, 4 * b.c_from, f.xl[b.level], b.c_to, (int)(rows_in / 4), b.c_to, 4 * b.c_from);
+                RET_IF(ln_operand(cx, g, b.conv_w, w16, false, x, rows_in, b.c_from, 1, h, w));
                 h >>= 1; w >>= 1;
-                GemmArgs g = gemm_args(f.h, 4 * b.c_from, T(m, b.prefix + ".1.weight"), 4 * b.c_from, f.xl[b.level], b.c_to, (int)(rows_in / 4), b.c_to, 4 * b.c_from);
-                if (w16) { g.A16 = f.h16; g.W16 = w16; }
-                g.ep.bias = T(m, b.prefix + ".1.bias");
+                g.ep.bias = b.conv_b->w.p;
                 RET_IF(launch_gemm(g, f.splitk, kSplitKBudget, st));
                 x = f.xl[b.level];
                 break;
@@ -1057,16 +996,10 @@ static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float*
             case BT_UP: {  // LayerNorm2d + ConvTranspose2d(k2,s2): GEMM with N = 4*c_to and a depth-to-space store
                 const int64_t rows_in = (int64_t)B * h * w;
                 float* dst = f.xu[b.level - 1];
-                GemmArgs g = gemm_args(f.h, b.c_from, T(m, b.prefix + ".1.weight"), b.c_from, dst, b.c_to, (int)rows_in, 4 * b.c_to, b.c_from);
-                const unsigned short* const w16 = (b.c_from % 64) == 0 ? T16(m, b.prefix + ".1.weight") : nullptr;
-                if (b.ln_from_stats) {
-                    g.A = x; g.ln_stats = f.rowstat; g.ln_nblk = b.c_from / 16; g.ln_eps = 1e-6f; g.ln_wsum = m->wsum.at(b.prefix + ".1.weight").p;
-                    if (w16) { g.A16 = f.x16; g.W16 = w16; g.ln_wsum = m->wsum16.at(b.prefix + ".1.weight").p; }
-                } else if (w16) {
-                    RET_IF(launch_layernorm16(x, nullptr, f.h16, rows_in, b.c_from, 1e-6f, 1.f, 0.f, 0, 0, 0, st));
-                    g.A16 = f.h16; g.W16 = w16;
-                } else RET_IF(launch_layernorm(x, f.h, rows_in, b.c_from, 1e-6f, 1.f, 0.f, 0, 0, 0, st));
-                g.ep.bias = T(m, b.prefix + ".1.bias");
+                GemmArgs g = gemm_args(f.h, b.c_from, b.conv_w->w.p, b.c_from, dst, b.c_to, (int)rows_in, 4 * b.c_to, b.c_from);
+                const unsigned short* const w16 = (b.c_from % 64) == 0 ? W16(m, b.conv_w) : nullptr;
+                RET_IF(ln_operand(cx, g, b.conv_w, w16, b.ln_from_stats, x, rows_in, b.c_from));
+                g.ep.bias = b.conv_b->w.p;
                 g.ep.store_mode = STORE_D2S; g.ep.sH = h; g.ep.sW = w; g.ep.sC = b.c_to; g.ep.n_seg_x = 2;
                 RET_IF(launch_gemm(g, f.splitk, kSplitKBudget, st));
                 h <<= 1; w <<= 1;
@@ -1086,28 +1019,22 @@ static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float*
     {
         const int p2 = p * p;
         const int64_t n0 = (int64_t)B * h0 * w0;  // full batch again
-        GemmArgs g = gemm_args(f.h, c.c_hidden[0], T(m, "clf.1.weight"), c.c_hidden[0], f.g, c.c_out, (int)n0, c.c_out * p2, c.c_hidden[0]);
-        const unsigned short* const wc16 = (c.c_hidden[0] % 64) == 0 ? T16(m, "clf.1.weight") : nullptr;
-        if (m->clf_from_stats) {
-            g.A = x; g.ln_stats = f.rowstat; g.ln_nblk = c.c_hidden[0] / 16; g.ln_eps = 1e-6f; g.ln_wsum = m->wsum.at("clf.1.weight").p;
-            if (wc16) { g.A16 = f.x16; g.W16 = wc16; g.ln_wsum = m->wsum16.at("clf.1.weight").p; }
-        } else if (wc16) {
-            RET_IF(launch_layernorm16(x, nullptr, f.h16, n0, c.c_hidden[0], 1e-6f, 1.f, 0.f, 0, 0, 0, st));
-            g.A16 = f.h16; g.W16 = wc16;
-        } else RET_IF(launch_layernorm(x, f.h, n0, c.c_hidden[0], 1e-6f, 1.f, 0.f, 0, 0, 0, st));
-        g.ep.bias = T(m, "clf.1.bias");
+        GemmArgs g = gemm_args(f.h, c.c_hidden[0], m->clf_w->w.p, c.c_hidden[0], f.g, c.c_out, (int)n0, c.c_out * p2, c.c_hidden[0]);
+        const unsigned short* const wc16 = (c.c_hidden[0] % 64) == 0 ? W16(m, m->clf_w) : nullptr;
+        RET_IF(ln_operand(cx, g, m->clf_w, wc16, m->clf_from_stats, x, n0, c.c_hidden[0]));
+        g.ep.bias = m->clf_b->w.p;
         if (p == 2) { g.ep.store_mode = STORE_D2S; g.ep.sH = h0; g.ep.sW = w0; g.ep.sC = c.c_out; g.ep.n_seg_x = 2; }
         RET_IF(launch_gemm(g, f.splitk, kSplitKBudget, st));
         int64_t nt = (int64_t)B * H * W;
-        const unsigned short* const wh16 = (c.c_out % 64) == 0 ? T16(m, "out_mapper.1.weight") : nullptr;  // bf16 fast mode: the head GEMM on bf16 operands
+        const unsigned short* const wh16 = (c.c_out % 64) == 0 ? W16(m, m->out_mapper) : nullptr;  // bf16 fast mode: the head GEMM on bf16 operands
         if (wh16 && !mix) RET_IF(launch_layernorm16(f.g, nullptr, f.h16, nt, c.c_out, 1e-6f, 1.f, 0.f, 0, 0, 0, st));
         else RET_IF(launch_layernorm(f.g, f.h, nt, c.c_out, 1e-6f, 1.f, 0.f, 0, 0, 0, st));
         if (mix) {  // the head is linear and bias-free: mix its input instead of its output
             nt /= 2;
-            if (mix_pairs) RET_IF(launch_axpby16_req(f.h, f.h + (size_t)nt * c.c_out, mix_pairs, n_unique, (int64_t)H * W * c.c_out, wh16 ? f.h16 : nullptr, st));
-            else RET_IF(launch_axpby16(f.h, f.h + (size_t)nt * c.c_out, mix_c, mix_u, nt * c.c_out, wh16 ? f.h16 : nullptr, st));
+            if (s.mix_pairs) RET_IF(launch_axpby16_req(f.h, f.h + (size_t)nt * c.c_out, s.mix_pairs, n_unique, (int64_t)H * W * c.c_out, wh16 ? f.h16 : nullptr, st));
+            else RET_IF(launch_axpby16(f.h, f.h + (size_t)nt * c.c_out, s.mix_c, s.mix_u, nt * c.c_out, wh16 ? f.h16 : nullptr, st));
         }
-        GemmArgs go = gemm_args(f.h, c.c_out, T(m, "out_mapper.1.weight"), c.c_out, logits_out, c.num_labels, (int)nt, c.num_labels, c.c_out);
+        GemmArgs go = gemm_args(f.h, c.c_out, m->out_mapper->w.p, c.c_out, tail ? nullptr : s.logits_out, c.num_labels, (int)nt, c.num_labels, c.c_out);
         if (wh16) { go.A16 = f.h16; go.W16 = wh16; }
         if (!tail) {
             // same tile config as the fused-tail launch below (one whole tile per workgroup, no K split): the two paths produce
@@ -1134,7 +1061,7 @@ static int unet_forward_impl(paella_unet* m, const int64_t* tokens, const float*
 
 // ---------------------------------------------------------------------------
 // The argument block of one forward (include/paella_hip.h: paella_step_args).  run_step_block is the one place where a block's rules are checked -- all before anything is
-// enqueued, the model may still be null there -- and where it becomes a call of unet_forward_impl; a fused step's tail block goes through tail.hip: tail_block_convert.
+// enqueued, the model may still be null there -- and where it is handed to unet_forward_impl; a fused step's tail block goes through tail.hip: tail_block_convert.
 // Every paella_unet_forward_shared* / _sample* entry point below fills a block, names itself and runs it; need (internal.h: kNeed*) = what its name promises beyond the block.
 // ---------------------------------------------------------------------------
 static int run_step_block(const char* who, paella_unet* m, const paella_step_args& s, int need, void* ws, size_t ws_bytes, void* stream) {
@@ -1142,8 +1069,7 @@ static int run_step_block(const char* who, paella_unet* m, const paella_step_arg
     if (s.mix_pairs && (s.mix_c != 0.f || s.mix_u != 0.f)) { paella_set_error("%s: a guidance pair table and a scalar mix exclude each other", who); return PAELLA_ERR_ARG; }
     if (s.kw_len && (!s.kw_table || s.kw_pitch < 1)) { paella_set_error("%s: kw_len needs kw_table and kw_pitch >= 1", who); return PAELLA_ERR_ARG; }
     if (s.kw_len && s.attn_weights) { paella_set_error("%s: one attn_weights vector and the key-weight table exclude each other", who); return PAELLA_ERR_ARG; }
-    const RgTable rg = {s.q_groups, s.qg_pitch, s.k_groups, s.kg_pitch};
-    RET_IF(rg_table_check(who, m, rg, s.H, s.W, s.S));
+    RET_IF(rg_table_check(who, m, s));
     TailArgs a;
     if (s.tail) {
         TailFilter f;
@@ -1162,8 +1088,7 @@ static int run_step_block(const char* who, paella_unet* m, const paella_step_arg
         a.rows = (int64_t)(mix ? s.n_unique : s.B) * s.H * s.W;  // with the guidance mix the head emits the n_unique mixed rows
         a.L = m ? m->cfg.num_labels : 0;
     }
-    return unet_forward_impl(m, s.tokens, s.r, s.cond, s.B, s.n_unique, s.mix_c, s.mix_u, s.H, s.W, s.S, s.attn_weights, s.n_attn_weights, s.tail ? nullptr : s.logits_out,
-                             s.tail ? &a : nullptr, ws, ws_bytes, stream, s.mix_pairs, s.cond_len, KwTable{s.kw_table, s.kw_len, s.kw_pitch}, rg);
+    return unet_forward_impl(m, s, s.tail ? &a : nullptr, ws, ws_bytes, stream);
 }
 
 extern "C" int paella_unet_step(paella_unet* m, const paella_step_args* args, size_t args_bytes, void* ws, size_t ws_bytes, void* stream) {
@@ -1543,34 +1468,34 @@ extern "C" int paella_op_grn_scale(const float* g, const float* gamma, float* sc
     return launch_grn_scale(g, gamma, scale, tmp, B, rows_per_sample, C, (hipStream_t)stream);
 }
 static int op_attention_impl(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond, float* out, int B, int nhead, int D,
-                             int Lq, int Lself, int Lcond, const int* cond_len, const float* key_weights, int n_kw, KwTable kw, void* stream,
-                             RgTable rg = {nullptr, 0, nullptr, 0}) {
+                             int Lq, int Lself, int Lcond, const int* cond_len, const float* key_weights, int n_kw, const float* kw_table, const int* kw_len,
+                             int kw_pitch, const int* q_groups, int qg_pitch, const int* k_groups, int kg_pitch, void* stream) {
     AttnArgs a;
     const int ld = nhead * D;
     a.q = q; a.ldq = ld; a.k_self = k_self; a.v_self = v_self; a.ld_self = ld; a.k_cond = k_cond; a.v_cond = v_cond; a.ld_cond = ld;
     a.out = out; a.ldo = ld; a.B = B; a.nhead = nhead; a.D = D; a.Lq = Lq; a.Lself = Lself; a.Lcond = Lcond;
     a.scale = 1.0f / sqrtf((float)D); a.key_weights = key_weights; a.n_kw = key_weights ? n_kw : 0; a.out16 = nullptr;
     a.q16 = nullptr; a.k_self16 = nullptr; a.v_self16 = nullptr; a.ld16 = 0; a.cond_len = cond_len;
-    a.kw_table = kw.table; a.kw_len = kw.len; a.kw_pitch = kw.pitch;
-    a.q_groups = rg.q; a.qg_pitch = rg.q_pitch; a.k_groups = rg.k; a.kg_pitch = rg.k_pitch;
+    a.kw_table = kw_table; a.kw_len = kw_len; a.kw_pitch = kw_pitch;
+    a.q_groups = q_groups; a.qg_pitch = qg_pitch; a.k_groups = k_groups; a.kg_pitch = kg_pitch;
     return launch_attention(a, (hipStream_t)stream);
 }
 extern "C" int paella_op_attention_ragged(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond,
                                           float* out, int B, int nhead, int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* key_weights,
                                           int n_kw, void* stream) {
-    return op_attention_impl(q, k_self, v_self, k_cond, v_cond, out, B, nhead, D, Lq, Lself, Lcond, cond_len, key_weights, n_kw, KwTable{nullptr, nullptr, 0}, stream);
+    return op_attention_impl(q, k_self, v_self, k_cond, v_cond, out, B, nhead, D, Lq, Lself, Lcond, cond_len, key_weights, n_kw, nullptr, nullptr, 0, nullptr, 0, nullptr, 0, stream);
 }
 // per-sample key weights: the table (kw_table fp32 [B, kw_pitch], kw_len int32 [B]) in place of the shared vector; kw_len == NULL = no weights
 extern "C" int paella_op_attention_kw(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond, float* out, int B, int nhead,
                                       int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* kw_table, const int* kw_len, int kw_pitch, void* stream) {
-    return op_attention_impl(q, k_self, v_self, k_cond, v_cond, out, B, nhead, D, Lq, Lself, Lcond, cond_len, nullptr, 0, KwTable{kw_table, kw_len, kw_pitch}, stream);
+    return op_attention_impl(q, k_self, v_self, k_cond, v_cond, out, B, nhead, D, Lq, Lself, Lcond, cond_len, nullptr, 0, kw_table, kw_len, kw_pitch, nullptr, 0, nullptr, 0, stream);
 }
 // per-query key groups on top of it (q_groups int32 [B, qg_pitch >= Lq], k_groups int32 [B, kg_pitch >= Lcond]; both NULL = the entry point above)
 extern "C" int paella_op_attention_rg(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond, float* out, int B, int nhead,
                                       int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* kw_table, const int* kw_len, int kw_pitch,
                                       const int* q_groups, int qg_pitch, const int* k_groups, int kg_pitch, void* stream) {
-    return op_attention_impl(q, k_self, v_self, k_cond, v_cond, out, B, nhead, D, Lq, Lself, Lcond, cond_len, nullptr, 0, KwTable{kw_table, kw_len, kw_pitch}, stream,
-                             RgTable{q_groups, qg_pitch, k_groups, kg_pitch});
+    return op_attention_impl(q, k_self, v_self, k_cond, v_cond, out, B, nhead, D, Lq, Lself, Lcond, cond_len, nullptr, 0, kw_table, kw_len, kw_pitch, q_groups, qg_pitch,
+                             k_groups, kg_pitch, stream);
 }
 extern "C" int paella_op_attention(const float* q, const float* k_self, const float* v_self, const float* k_cond, const float* v_cond,
                                    float* out, int B, int nhead, int D, int Lq, int Lself, int Lcond, const float* key_weights,
@@ -1580,25 +1505,25 @@ extern "C" int paella_op_attention(const float* q, const float* k_self, const fl
 // test hook (test_hooks.h): the bf16 attention core of the opt-in fast mode on caller-provided operands: q16 / ks16 / vs16 bf16 [B*L, nhead*D], kc / vc fp32, out16 bf16
 static int test_attention_bf16_impl(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond, const float* v_cond,
                                     unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* key_weights,
-                                    int n_kw, KwTable kw, void* stream) {
+                                    int n_kw, const float* kw_table, const int* kw_len, int kw_pitch, void* stream) {
     AttnArgs a;
     const int ld = nhead * D;
     a.q = nullptr; a.ldq = ld; a.k_self = nullptr; a.v_self = nullptr; a.ld_self = ld; a.k_cond = k_cond; a.v_cond = v_cond; a.ld_cond = ld;
     a.out = nullptr; a.ldo = ld; a.B = B; a.nhead = nhead; a.D = D; a.Lq = Lq; a.Lself = Lself; a.Lcond = Lcond;
     a.scale = 1.0f / sqrtf((float)D); a.key_weights = key_weights; a.n_kw = key_weights ? n_kw : 0; a.out16 = out16;
     a.q16 = q16; a.k_self16 = ks16; a.v_self16 = vs16; a.ld16 = ld; a.cond_len = cond_len;
-    a.kw_table = kw.table; a.kw_len = kw.len; a.kw_pitch = kw.pitch;
+    a.kw_table = kw_table; a.kw_len = kw_len; a.kw_pitch = kw_pitch;
     return launch_attention(a, (hipStream_t)stream);
 }
 extern "C" int paella_test_attention_bf16_ragged(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond,
                                                  const float* v_cond, unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond,
                                                  const int* cond_len, const float* key_weights, int n_kw, void* stream) {
-    return test_attention_bf16_impl(q16, ks16, vs16, k_cond, v_cond, out16, B, nhead, D, Lq, Lself, Lcond, cond_len, key_weights, n_kw, KwTable{nullptr, nullptr, 0}, stream);
+    return test_attention_bf16_impl(q16, ks16, vs16, k_cond, v_cond, out16, B, nhead, D, Lq, Lself, Lcond, cond_len, key_weights, n_kw, nullptr, nullptr, 0, stream);
 }
 extern "C" int paella_test_attention_bf16_kw(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond, const float* v_cond,
                                              unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond, const int* cond_len, const float* kw_table,
                                              const int* kw_len, int kw_pitch, void* stream) {
-    return test_attention_bf16_impl(q16, ks16, vs16, k_cond, v_cond, out16, B, nhead, D, Lq, Lself, Lcond, cond_len, nullptr, 0, KwTable{kw_table, kw_len, kw_pitch}, stream);
+    return test_attention_bf16_impl(q16, ks16, vs16, k_cond, v_cond, out16, B, nhead, D, Lq, Lself, Lcond, cond_len, nullptr, 0, kw_table, kw_len, kw_pitch, stream);
 }
 extern "C" int paella_test_attention_bf16(const unsigned short* q16, const unsigned short* ks16, const unsigned short* vs16, const float* k_cond, const float* v_cond,
                                           unsigned short* out16, int B, int nhead, int D, int Lq, int Lself, int Lcond, const float* key_weights, int n_kw, void* stream) {

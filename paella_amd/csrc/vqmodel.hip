@@ -13,51 +13,51 @@
 
 enum VqOp { VQ_CONV1, VQ_RES, VQ_CONV4S2, VQ_CONVT4, VQ_LATENT_BN };
 
+// As in model.hip, a state-dict key is written once: the vspec call in paella_vqgan_create that declares the tensor returns its Weight (internal.h) and the same
+// statement binds it to the member the launches read.  Only load_tensor, finalize's "never loaded" check and destroy go through the names.
 struct VqBlock {
     VqOp op;
     int c_in, c_out;
-    std::string prefix;
+    Weight *w = nullptr, *b = nullptr;                                                             // the convolutions (VQ_LATENT_BN: its bias-free 1x1)
+    Weight *dw_w = nullptr, *dw_b = nullptr, *w1 = nullptr, *b1 = nullptr, *w2 = nullptr, *b2 = nullptr, *gammas = nullptr;  // VQ_RES
+    Weight *bn_w = nullptr, *bn_b = nullptr, *bn_mean = nullptr, *bn_var = nullptr;                // VQ_LATENT_BN: BatchNorm2d
     float gam[6];
     DevBuf phase_w[4];  // VQ_CONVT4: [c_out, 4*c_in] per output phase
 };
-
-struct VqSpec { Repack kind; std::vector<int64_t> shape; bool is_int = false; };
 
 struct paella_vqgan {
     paella_vqgan_config cfg;
     std::vector<int> c_levels;
     std::vector<VqBlock> enc, dec;
-    std::map<std::string, VqSpec> specs;
-    std::map<std::string, DevBuf> t;
+    std::map<std::string, Weight> t;  // every state-dict tensor by key; the blocks and the members below point into it
+    Weight *codebook = nullptr, *out_w = nullptr, *out_b = nullptr;
     DevBuf bn_scale, bn_shift;
     bool finalized = false;
     float bn_eps = 1e-5f;
     // OPT-IN bf16 fast mode of THIS model (paella_vqgan_set_precision; outside the fp32 parity contract): bf16 shadows of the ResBlocks' MLP weights
     int precision = 0;
-    std::map<std::string, DevBuf16> t16;
 };
 
-static const float* VT(const paella_vqgan* v, const std::string& k) {
-    auto it = v->t.find(k);
-    return it == v->t.end() ? nullptr : it->second.p;
+// bf16 shadow of a weight, or null (fp32 mode / no shadow for this tensor)
+static const unsigned short* VW16(const paella_vqgan* v, const Weight* t) { return v->precision == 1 ? t->w16.p : nullptr; }
+static Weight* vspec(paella_vqgan* v, const std::string& key, Repack kind, std::vector<int64_t> shape) {
+    Weight& t = v->t[key];
+    t.kind = kind; t.shape = std::move(shape);
+    return &t;
 }
-static const unsigned short* VT16(const paella_vqgan* v, const std::string& k) {
-    if (v->precision != 1) return nullptr;
-    auto it = v->t16.find(k);
-    return it == v->t16.end() ? nullptr : it->second.p;
+static void conv_specs(paella_vqgan* v, VqBlock& b, const std::string& p, Repack kind, std::vector<int64_t> shape) {
+    b.w = vspec(v, p + ".weight", kind, std::move(shape));
+    b.b = vspec(v, p + ".bias", RP_COPY, {b.c_out});
 }
-static void vspec(paella_vqgan* v, const std::string& key, Repack kind, std::vector<int64_t> shape) {
-    VqSpec s; s.kind = kind; s.shape = std::move(shape);
-    v->specs[key] = s;
-}
-static void res_specs(paella_vqgan* v, const std::string& p, int64_t c) {
-    vspec(v, p + ".depthwise.1.weight", RP_DW, {c, 1, 3, 3});
-    vspec(v, p + ".depthwise.1.bias", RP_COPY, {c});
-    vspec(v, p + ".channelwise.0.weight", RP_COPY, {4 * c, c});
-    vspec(v, p + ".channelwise.0.bias", RP_COPY, {4 * c});
-    vspec(v, p + ".channelwise.2.weight", RP_COPY, {c, 4 * c});
-    vspec(v, p + ".channelwise.2.bias", RP_COPY, {c});
-    vspec(v, p + ".gammas", RP_COPY, {6});
+static void res_specs(paella_vqgan* v, VqBlock& b, const std::string& p) {
+    const int64_t c = b.c_in;
+    b.dw_w = vspec(v, p + ".depthwise.1.weight", RP_DW, {c, 1, 3, 3});
+    b.dw_b = vspec(v, p + ".depthwise.1.bias", RP_COPY, {c});
+    b.w1 = vspec(v, p + ".channelwise.0.weight", RP_COPY, {4 * c, c});
+    b.b1 = vspec(v, p + ".channelwise.0.bias", RP_COPY, {4 * c});
+    b.w2 = vspec(v, p + ".channelwise.2.weight", RP_COPY, {c, 4 * c});
+    b.b2 = vspec(v, p + ".channelwise.2.bias", RP_COPY, {c});
+    b.gammas = vspec(v, p + ".gammas", RP_COPY, {6});
 }
 
 extern "C" int paella_vqgan_create(const paella_vqgan_config* cfg, paella_vqgan** out) {
@@ -73,10 +73,9 @@ extern "C" int paella_vqgan_create(const paella_vqgan_config* cfg, paella_vqgan*
     for (int i = L - 1; i >= 0; --i) v->c_levels.push_back(cfg->c_hidden >> i);  // c_levels[0] smallest
     char buf[96];
     // encoder (src/vqgan.py:54-69)
-    vspec(v, "in_block.1.weight", RP_COPY, {v->c_levels[0], 12, 1, 1});
-    vspec(v, "in_block.1.bias", RP_COPY, {v->c_levels[0]});
     {
-        VqBlock b; b.op = VQ_CONV1; b.c_in = 12; b.c_out = v->c_levels[0]; b.prefix = "in_block.1";
+        VqBlock b; b.op = VQ_CONV1; b.c_in = 12; b.c_out = v->c_levels[0];
+        conv_specs(v, b, "in_block.1", RP_COPY, {b.c_out, 12, 1, 1});
         v->enc.push_back(b);
     }
     int j = 0;
@@ -84,34 +83,30 @@ extern "C" int paella_vqgan_create(const paella_vqgan_config* cfg, paella_vqgan*
         if (i > 0) {
             VqBlock b; b.op = VQ_CONV4S2; b.c_in = v->c_levels[i - 1]; b.c_out = v->c_levels[i];
             snprintf(buf, sizeof buf, "down_blocks.%d", j++);
-            b.prefix = buf;
-            vspec(v, b.prefix + ".weight", RP_CONV_K2, {b.c_out, b.c_in, 4, 4});
-            vspec(v, b.prefix + ".bias", RP_COPY, {b.c_out});
+            conv_specs(v, b, buf, RP_CONV_K2, {b.c_out, b.c_in, 4, 4});
             v->enc.push_back(b);
         }
         VqBlock r; r.op = VQ_RES; r.c_in = r.c_out = v->c_levels[i];
         snprintf(buf, sizeof buf, "down_blocks.%d", j++);
-        r.prefix = buf;
-        res_specs(v, r.prefix, r.c_in);
+        res_specs(v, r, buf);
         v->enc.push_back(r);
     }
     {
         VqBlock b; b.op = VQ_LATENT_BN; b.c_in = v->c_levels[L - 1]; b.c_out = cfg->c_latent;
         snprintf(buf, sizeof buf, "down_blocks.%d", j);
-        b.prefix = buf;
-        vspec(v, b.prefix + ".0.weight", RP_COPY, {cfg->c_latent, b.c_in, 1, 1});
-        vspec(v, b.prefix + ".1.weight", RP_COPY, {cfg->c_latent});
-        vspec(v, b.prefix + ".1.bias", RP_COPY, {cfg->c_latent});
-        vspec(v, b.prefix + ".1.running_mean", RP_COPY, {cfg->c_latent});
-        vspec(v, b.prefix + ".1.running_var", RP_COPY, {cfg->c_latent});
+        const std::string p = buf;
+        b.w = vspec(v, p + ".0.weight", RP_COPY, {cfg->c_latent, b.c_in, 1, 1});
+        b.bn_w = vspec(v, p + ".1.weight", RP_COPY, {cfg->c_latent});
+        b.bn_b = vspec(v, p + ".1.bias", RP_COPY, {cfg->c_latent});
+        b.bn_mean = vspec(v, p + ".1.running_mean", RP_COPY, {cfg->c_latent});
+        b.bn_var = vspec(v, p + ".1.running_var", RP_COPY, {cfg->c_latent});
         v->enc.push_back(b);
     }
-    vspec(v, "vquantizer.codebook.weight", RP_COPY, {cfg->codebook_size, cfg->c_latent});
+    v->codebook = vspec(v, "vquantizer.codebook.weight", RP_COPY, {cfg->codebook_size, cfg->c_latent});
     // decoder (src/vqgan.py:74-89)
     {
-        VqBlock b; b.op = VQ_CONV1; b.c_in = cfg->c_latent; b.c_out = v->c_levels[L - 1]; b.prefix = "up_blocks.0.0";
-        vspec(v, "up_blocks.0.0.weight", RP_COPY, {b.c_out, b.c_in, 1, 1});
-        vspec(v, "up_blocks.0.0.bias", RP_COPY, {b.c_out});
+        VqBlock b; b.op = VQ_CONV1; b.c_in = cfg->c_latent; b.c_out = v->c_levels[L - 1];
+        conv_specs(v, b, "up_blocks.0.0", RP_COPY, {b.c_out, b.c_in, 1, 1});
         v->dec.push_back(b);
     }
     j = 1;
@@ -121,29 +116,25 @@ extern "C" int paella_vqgan_create(const paella_vqgan_config* cfg, paella_vqgan*
         for (int k = 0; k < nb; ++k) {
             VqBlock r; r.op = VQ_RES; r.c_in = r.c_out = cl;
             snprintf(buf, sizeof buf, "up_blocks.%d", j++);
-            r.prefix = buf;
-            res_specs(v, r.prefix, cl);
+            res_specs(v, r, buf);
             v->dec.push_back(r);
         }
         if (i < L - 1) {
             VqBlock b; b.op = VQ_CONVT4; b.c_in = cl; b.c_out = v->c_levels[L - 2 - i];
             snprintf(buf, sizeof buf, "up_blocks.%d", j++);
-            b.prefix = buf;
-            vspec(v, b.prefix + ".weight", RP_CONVT_K2, {b.c_in, b.c_out, 4, 4});
-            vspec(v, b.prefix + ".bias", RP_COPY, {b.c_out});
+            conv_specs(v, b, buf, RP_CONVT_K2, {b.c_in, b.c_out, 4, 4});
             v->dec.push_back(b);
         }
     }
-    vspec(v, "out_block.0.weight", RP_COPY, {12, v->c_levels[0], 1, 1});
-    vspec(v, "out_block.0.bias", RP_COPY, {12});
+    v->out_w = vspec(v, "out_block.0.weight", RP_COPY, {12, v->c_levels[0], 1, 1});
+    v->out_b = vspec(v, "out_block.0.bias", RP_COPY, {12});
     *out = v;
     return PAELLA_OK;
 }
 
 extern "C" void paella_vqgan_destroy(paella_vqgan* v) {
     if (!v) return;
-    for (auto& kv : v->t) if (kv.second.p) (void)hipFree(kv.second.p);
-    for (auto& kv : v->t16) if (kv.second.p) (void)hipFree(kv.second.p);
+    for (auto& kv : v->t) weight_free(kv.second);
     for (auto* seq : {&v->enc, &v->dec})
         for (auto& b : *seq)
             for (auto& pw : b.phase_w) if (pw.p) (void)hipFree(pw.p);
@@ -155,14 +146,14 @@ extern "C" void paella_vqgan_destroy(paella_vqgan* v) {
 extern "C" int paella_vqgan_load_tensor(paella_vqgan* v, const char* key, const float* dev_src, const int64_t* shape, int ndim,
                                         void* stream) {
     if (!v || !key || !dev_src) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
-    auto it = v->specs.find(key);
-    if (it == v->specs.end()) { paella_set_error("unexpected state-dict key '%s'", key); return PAELLA_ERR_ARG; }
-    const VqSpec& sp = it->second;
+    auto it = v->t.find(key);
+    if (it == v->t.end()) { paella_set_error("unexpected state-dict key '%s'", key); return PAELLA_ERR_ARG; }
+    Weight& sp = it->second;
     if ((int)sp.shape.size() != ndim) { paella_set_error("%s: expected %d dims, got %d", key, (int)sp.shape.size(), ndim); return PAELLA_ERR_ARG; }
     for (int d = 0; d < ndim; ++d)
         if (shape[d] != sp.shape[d]) { paella_set_error("%s: dim %d is %lld, expected %lld", key, d, (long long)shape[d], (long long)sp.shape[d]); return PAELLA_ERR_ARG; }
     v->finalized = false;
-    return repack_into(sp.kind, dev_src, sp.shape, v->t[key], (hipStream_t)stream);
+    return repack_into(sp.kind, dev_src, sp.shape, sp.w, (hipStream_t)stream);
 }
 
 
@@ -170,16 +161,8 @@ static int vq_make_shadows(paella_vqgan* v, hipStream_t st) {
     for (auto* seq : {&v->enc, &v->dec})
         for (auto& b : *seq) {
             if (b.op != VQ_RES || (b.c_in % 64)) continue;
-            for (const char* suffix : {".channelwise.0.weight", ".channelwise.2.weight"}) {
-                const std::string k = b.prefix + suffix;
-                auto it = v->t.find(k);
-                if (it == v->t.end() || !it->second.p) continue;
-                DevBuf16& d = v->t16[k];
-                if (d.p && d.n != it->second.n) { (void)hipFree(d.p); d.p = nullptr; }
-                if (!d.p) HIP_CHECK_RET(hipMalloc((void**)&d.p, it->second.n * sizeof(unsigned short)));
-                d.n = it->second.n;
-                RET_IF(launch_f32_to_bf16(it->second.p, d.p, d.n, st));
-            }
+            for (Weight* t : {b.w1, b.w2})
+                if (t->w.p) RET_IF(weight_make_shadow(*t, st));
         }
     HIP_CHECK_RET(hipStreamSynchronize(st));
     return PAELLA_OK;
@@ -188,18 +171,16 @@ static int vq_make_shadows(paella_vqgan* v, hipStream_t st) {
 extern "C" int paella_vqgan_finalize(paella_vqgan* v, void* stream) {
     if (!v) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
     hipStream_t st = (hipStream_t)stream;
-    for (auto& kv : v->specs) {
-        auto it = v->t.find(kv.first);
-        if (it == v->t.end() || !it->second.loaded) { paella_set_error("tensor '%s' was never loaded", kv.first.c_str()); return PAELLA_ERR_STATE; }
-    }
+    for (auto& kv : v->t)
+        if (!kv.second.w.loaded) { paella_set_error("tensor '%s' was never loaded", kv.first.c_str()); return PAELLA_ERR_STATE; }
     HIP_CHECK_RET(hipStreamSynchronize(st));
     for (auto* seq : {&v->enc, &v->dec})
         for (auto& b : *seq) {
             if (b.op == VQ_RES) {
-                HIP_CHECK_RET(hipMemcpy(b.gam, VT(v, b.prefix + ".gammas"), 6 * sizeof(float), hipMemcpyDeviceToHost));
+                HIP_CHECK_RET(hipMemcpy(b.gam, b.gammas->w.p, 6 * sizeof(float), hipMemcpyDeviceToHost));
             } else if (b.op == VQ_CONVT4) {
                 // repacked weight is [ky][kx][co][ci]; phase (py,px) uses taps ky = py?{0,2}:{1,3} (ty = 0,1), same for kx
-                const float* w4 = VT(v, b.prefix + ".weight");
+                const float* w4 = b.w->w.p;
                 for (int ph = 0; ph < 4; ++ph) {
                     const int py = ph >> 1, px = ph & 1;
                     RET_IF(devbuf_alloc(b.phase_w[ph], (size_t)b.c_out * 4 * b.c_in));
@@ -214,10 +195,10 @@ extern "C" int paella_vqgan_finalize(paella_vqgan* v, void* stream) {
             } else if (b.op == VQ_LATENT_BN) {
                 const int cl = v->cfg.c_latent;
                 std::vector<float> w(cl), bb(cl), mu(cl), var(cl), sc(cl), sh(cl);
-                HIP_CHECK_RET(hipMemcpy(w.data(), VT(v, b.prefix + ".1.weight"), cl * sizeof(float), hipMemcpyDeviceToHost));
-                HIP_CHECK_RET(hipMemcpy(bb.data(), VT(v, b.prefix + ".1.bias"), cl * sizeof(float), hipMemcpyDeviceToHost));
-                HIP_CHECK_RET(hipMemcpy(mu.data(), VT(v, b.prefix + ".1.running_mean"), cl * sizeof(float), hipMemcpyDeviceToHost));
-                HIP_CHECK_RET(hipMemcpy(var.data(), VT(v, b.prefix + ".1.running_var"), cl * sizeof(float), hipMemcpyDeviceToHost));
+                HIP_CHECK_RET(hipMemcpy(w.data(), b.bn_w->w.p, cl * sizeof(float), hipMemcpyDeviceToHost));
+                HIP_CHECK_RET(hipMemcpy(bb.data(), b.bn_b->w.p, cl * sizeof(float), hipMemcpyDeviceToHost));
+                HIP_CHECK_RET(hipMemcpy(mu.data(), b.bn_mean->w.p, cl * sizeof(float), hipMemcpyDeviceToHost));
+                HIP_CHECK_RET(hipMemcpy(var.data(), b.bn_var->w.p, cl * sizeof(float), hipMemcpyDeviceToHost));
                 for (int i = 0; i < cl; ++i) {  // eval-mode BatchNorm2d folded to y = x*sc + sh
                     const float inv = 1.0f / sqrtf(var[i] + v->bn_eps);
                     sc[i] = w[i] * inv;
@@ -294,33 +275,33 @@ static int vq_resblock(const paella_vqgan* v, const VqBlock& b, VqBuffers& f, in
     const int c = b.c_in;
     const int64_t rows = (int64_t)B * h * w;
     RET_IF(launch_layernorm(f.x, f.t, rows, c, 1e-6f, 1.0f + b.gam[0], b.gam[1], 0, 0, 0, st));
-    RET_IF(launch_dwconv_res(f.x, f.t, VT(v, b.prefix + ".depthwise.1.weight"), VT(v, b.prefix + ".depthwise.1.bias"), f.x, B, h, w, c,
+    RET_IF(launch_dwconv_res(f.x, f.t, b.dw_w->w.p, b.dw_b->w.p, f.x, B, h, w, c,
                              b.gam[2], st));
-    const unsigned short* const w1_16 = VT16(v, b.prefix + ".channelwise.0.weight");
-    const unsigned short* const w2_16 = VT16(v, b.prefix + ".channelwise.2.weight");
+    const unsigned short* const w1_16 = VW16(v, b.w1);
+    const unsigned short* const w2_16 = VW16(v, b.w2);
     if (w1_16 && w2_16 && f.t16 && (c % 64) == 0) {  // opt-in bf16 fast mode: LayerNorm -> bf16 | GEMM1 -> GELU -> bf16 hidden | GEMM2 -> fp32 residual stream
         RET_IF(launch_layernorm16(f.x, nullptr, f.t16, rows, c, 1e-6f, 1.0f + b.gam[3], b.gam[4], 0, 0, 0, st));
-        GemmArgs g1 = gemm_args(nullptr, c, VT(v, b.prefix + ".channelwise.0.weight"), c, nullptr, 4 * c, (int)rows, 4 * c, c);
+        GemmArgs g1 = gemm_args(nullptr, c, b.w1->w.p, c, nullptr, 4 * c, (int)rows, 4 * c, c);
         g1.A16 = f.t16; g1.W16 = w1_16;
-        g1.ep.bias = VT(v, b.prefix + ".channelwise.0.bias");
+        g1.ep.bias = b.b1->w.p;
         g1.ep.act = ACT_GELU;
         g1.ep.c16 = f.g16;
         RET_IF(launch_gemm(g1, f.splitk, kSplitKBudget, st));
-        GemmArgs g2 = gemm_args(nullptr, 4 * c, VT(v, b.prefix + ".channelwise.2.weight"), 4 * c, f.x, c, (int)rows, c, 4 * c);
+        GemmArgs g2 = gemm_args(nullptr, 4 * c, b.w2->w.p, 4 * c, f.x, c, (int)rows, c, 4 * c);
         g2.A16 = f.g16; g2.W16 = w2_16;
-        g2.ep.bias = VT(v, b.prefix + ".channelwise.2.bias");
+        g2.ep.bias = b.b2->w.p;
         g2.ep.alpha = b.gam[5];
         g2.ep.residual = f.x; g2.ep.ldr = c;
         RET_IF(launch_gemm(g2, f.splitk, kSplitKBudget, st));
         return PAELLA_OK;
     }
     RET_IF(launch_layernorm(f.x, f.t, rows, c, 1e-6f, 1.0f + b.gam[3], b.gam[4], 0, 0, 0, st));
-    GemmArgs g1 = gemm_args(f.t, c, VT(v, b.prefix + ".channelwise.0.weight"), c, f.g, 4 * c, (int)rows, 4 * c, c);
-    g1.ep.bias = VT(v, b.prefix + ".channelwise.0.bias");
+    GemmArgs g1 = gemm_args(f.t, c, b.w1->w.p, c, f.g, 4 * c, (int)rows, 4 * c, c);
+    g1.ep.bias = b.b1->w.p;
     g1.ep.act = ACT_GELU;
     RET_IF(launch_gemm(g1, f.splitk, kSplitKBudget, st));
-    GemmArgs g2 = gemm_args(f.g, 4 * c, VT(v, b.prefix + ".channelwise.2.weight"), 4 * c, f.x, c, (int)rows, c, 4 * c);
-    g2.ep.bias = VT(v, b.prefix + ".channelwise.2.bias");
+    GemmArgs g2 = gemm_args(f.g, 4 * c, b.w2->w.p, 4 * c, f.x, c, (int)rows, c, 4 * c);
+    g2.ep.bias = b.b2->w.p;
     g2.ep.alpha = b.gam[5];
     g2.ep.residual = f.x; g2.ep.ldr = c;
     RET_IF(launch_gemm(g2, f.splitk, kSplitKBudget, st));
@@ -335,8 +316,8 @@ static int vq_run_decoder(paella_vqgan* v, VqBuffers& f, int B, int h, int w, fl
         const int64_t rows = (int64_t)B * ch * cw;
         switch (b.op) {
             case VQ_CONV1: {
-                GemmArgs g = gemm_args(in, b.c_in, VT(v, b.prefix + ".weight"), b.c_in, f.x, b.c_out, (int)rows, b.c_out, b.c_in);
-                g.ep.bias = VT(v, b.prefix + ".bias");
+                GemmArgs g = gemm_args(in, b.c_in, b.w->w.p, b.c_in, f.x, b.c_out, (int)rows, b.c_out, b.c_in);
+                g.ep.bias = b.b->w.p;
                 RET_IF(launch_gemm(g, f.splitk, kSplitKBudget, st));
                 break;
             }
@@ -354,7 +335,7 @@ static int vq_run_decoder(paella_vqgan* v, VqBuffers& f, int B, int h, int w, fl
                         // tap (ty, tx) of output phase (py, px) reads input (y + py - ty, x + px - tx): src/vqgan.py:83-85 unrolled per phase
                         g.cv.tw_log2 = 1; g.cv.oy0 = py; g.cv.ox0 = px; g.cv.tsign = -1;
                     }
-                    g.ep.bias = VT(v, b.prefix + ".bias");
+                    g.ep.bias = b.b->w.p;
                     g.ep.store_mode = STORE_D2S; g.ep.sH = ch; g.ep.sW = cw; g.ep.sC = b.c_out; g.ep.n_seg_x = 1; g.ep.py = py; g.ep.px = px;
                     RET_IF(launch_gemm(g, f.splitk, kSplitKBudget, st));
                 }
@@ -367,8 +348,8 @@ static int vq_run_decoder(paella_vqgan* v, VqBuffers& f, int B, int h, int w, fl
     }
     // out_block: Conv1x1 -> 12, PixelShuffle(2) -> NCHW image
     const int64_t rows = (int64_t)B * ch * cw;
-    GemmArgs g = gemm_args(f.x, v->c_levels[0], VT(v, "out_block.0.weight"), v->c_levels[0], img_out, 4, (int)rows, 12, v->c_levels[0]);
-    g.ep.bias = VT(v, "out_block.0.bias");
+    GemmArgs g = gemm_args(f.x, v->c_levels[0], v->out_w->w.p, v->c_levels[0], img_out, 4, (int)rows, 12, v->c_levels[0]);
+    g.ep.bias = v->out_b->w.p;
     g.ep.store_mode = STORE_PIXSHUF_NCHW; g.ep.sH = ch; g.ep.sW = cw; g.ep.sC = 3;
     RET_IF(launch_gemm(g, f.splitk, kSplitKBudget, st));
     return PAELLA_OK;
@@ -389,7 +370,7 @@ extern "C" int paella_vqgan_decode_indices(paella_vqgan* v, const int64_t* idx, 
     VqBuffers f;
     RET_IF(vq_prepare(v, f, B, h, w, ws, ws_bytes));
     hipStream_t st = (hipStream_t)stream;
-    RET_IF(launch_codebook_gather(idx, VT(v, "vquantizer.codebook.weight"), f.lat, (int64_t)B * h * w, v->cfg.c_latent, v->cfg.codebook_size, 1.0f, st));
+    RET_IF(launch_codebook_gather(idx, v->codebook->w.p, f.lat, (int64_t)B * h * w, v->cfg.c_latent, v->cfg.codebook_size, 1.0f, st));
     return vq_run_decoder(v, f, B, h, w, img_out, st);
 }
 
@@ -438,8 +419,8 @@ extern "C" int paella_vqgan_encode(paella_vqgan* v, const float* img, int B, int
         const int64_t rows = (int64_t)B * ch * cw;
         switch (b.op) {
             case VQ_CONV1: {
-                GemmArgs g = gemm_args(f.a, 12, VT(v, b.prefix + ".weight"), 12, f.x, b.c_out, (int)rows, b.c_out, 12);
-                g.ep.bias = VT(v, b.prefix + ".bias");
+                GemmArgs g = gemm_args(f.a, 12, b.w->w.p, 12, f.x, b.c_out, (int)rows, b.c_out, 12);
+                g.ep.bias = b.b->w.p;
                 RET_IF(launch_gemm(g, f.splitk, kSplitKBudget, st));
                 break;
             }
@@ -447,20 +428,20 @@ extern "C" int paella_vqgan_encode(paella_vqgan* v, const float* img, int B, int
             case VQ_CONV4S2: {
                 const bool implicit = (b.c_in & 31) == 0;  // implicit GEMM (no im2col buffer) whenever the K step divides the channel count
                 if (!implicit) RET_IF(launch_conv4s2_im2col(f.x, f.a, B, ch, cw, b.c_in, st));
-                GemmArgs g = gemm_args(implicit ? f.x : f.a, 16 * b.c_in, VT(v, b.prefix + ".weight"), 16 * b.c_in, f.t, b.c_out, (int)(rows / 4), b.c_out, 16 * b.c_in);
+                GemmArgs g = gemm_args(implicit ? f.x : f.a, 16 * b.c_in, b.w->w.p, 16 * b.c_in, f.t, b.c_out, (int)(rows / 4), b.c_out, 16 * b.c_in);
                 if (implicit) {
                     g.cv.enabled = 1; g.cv.Hi = ch; g.cv.Wi = cw; g.cv.C = b.c_in; g.cv.Ho = ch / 2; g.cv.Wo = cw / 2; g.cv.stride = 2; g.cv.ntaps = 16;
                     g.cv.tw_log2 = 2; g.cv.oy0 = -1; g.cv.ox0 = -1; g.cv.tsign = 1;  // Conv2d(k4, s2, p1): tap (ky, kx) reads (2*yo - 1 + ky, 2*xo - 1 + kx), src/vqgan.py:61
                 }
                 ch >>= 1; cw >>= 1;
-                g.ep.bias = VT(v, b.prefix + ".bias");
+                g.ep.bias = b.b->w.p;
                 RET_IF(launch_gemm(g, f.splitk, kSplitKBudget, st));
                 float* tmp = f.x; f.x = f.t; f.t = tmp;
                 break;
             }
             case VQ_LATENT_BN: {
                 const int cl = v->cfg.c_latent;
-                GemmArgs g = gemm_args(f.x, b.c_in, VT(v, b.prefix + ".0.weight"), b.c_in, f.t, cl, (int)rows, cl, b.c_in);
+                GemmArgs g = gemm_args(f.x, b.c_in, b.w->w.p, b.c_in, f.t, cl, (int)rows, cl, b.c_in);
                 RET_IF(launch_gemm(g, f.splitk, kSplitKBudget, st));
                 RET_IF(launch_affine_cols(f.t, v->bn_scale.p, v->bn_shift.p, f.lat, rows, cl, st));
                 break;
@@ -471,7 +452,7 @@ extern "C" int paella_vqgan_encode(paella_vqgan* v, const float* img, int B, int
     const int cl = v->cfg.c_latent;
     const int64_t rows = (int64_t)B * h * w;
     int64_t* idx = idx_out ? idx_out : (int64_t*)f.g;  // scratch when the caller does not want indices
-    RET_IF(launch_vq_nearest(f.lat, VT(v, "vquantizer.codebook.weight"), idx, f.qe, rows, cl, v->cfg.codebook_size, st));
+    RET_IF(launch_vq_nearest(f.lat, v->codebook->w.p, idx, f.qe, rows, cl, v->cfg.codebook_size, st));
     // reference returns qe / scale_factor and x / scale_factor (true divisions)
     if (qe_out) RET_IF(launch_nhwc_to_nchw(f.qe, qe_out, B, h * w, cl, v->cfg.scale_factor, 1, st));
     if (x_out) RET_IF(launch_nhwc_to_nchw(f.lat, x_out, B, h * w, cl, v->cfg.scale_factor, 1, st));
@@ -486,7 +467,7 @@ extern "C" int paella_vqgan_quantize_rows(paella_vqgan* v, const float* x, int64
                                           void* stream) {
     if (!v || !v->finalized) { paella_set_error("VQGAN not finalized"); return PAELLA_ERR_STATE; }
     if (!x || !idx_out || (mse_out && !qe_out)) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
-    RET_IF(launch_vq_nearest(x, VT(v, "vquantizer.codebook.weight"), idx_out, qe_out, rows, v->cfg.c_latent, v->cfg.codebook_size, (hipStream_t)stream));
+    RET_IF(launch_vq_nearest(x, v->codebook->w.p, idx_out, qe_out, rows, v->cfg.c_latent, v->cfg.codebook_size, (hipStream_t)stream));
     if (mse_out && rows > 0) {
         hipLaunchKernelGGL(vq_loss_kernel, dim3(1), dim3(256), 0, (hipStream_t)stream, qe_out, x, rows * v->cfg.c_latent, mse_out, 0);
         LAUNCH_CHECK_RET();
@@ -498,5 +479,5 @@ extern "C" int paella_vqgan_quantize_rows(paella_vqgan* v, const float* x, int64
 extern "C" int paella_vqgan_lookup_rows(paella_vqgan* v, const int64_t* idx, int64_t rows, float* out, void* stream) {
     if (!v || !v->finalized) { paella_set_error("VQGAN not finalized"); return PAELLA_ERR_STATE; }
     if (!idx || !out) { paella_set_error("null argument"); return PAELLA_ERR_ARG; }
-    return launch_codebook_gather(idx, VT(v, "vquantizer.codebook.weight"), out, rows, v->cfg.c_latent, v->cfg.codebook_size, 1.0f, (hipStream_t)stream);
+    return launch_codebook_gather(idx, v->codebook->w.p, out, rows, v->cfg.c_latent, v->cfg.codebook_size, 1.0f, (hipStream_t)stream);
 }

@@ -153,6 +153,7 @@ def _torch_save(m):
 def test_copy_of_a_module_that_has_run(monkeypatch, kind, how):
     """A module with a native handle (a stand-in: nothing native is touched) copies; the copy takes the tensors and the settings and none of the engine state, and
     the original keeps its own.  Deleting the copy destroys nothing."""
+    gc.collect()  # modules that earlier tests left in reference cycles are finalised now, through the real library, and not by the collection below
     lib = _NoLibrary()
     monkeypatch.setattr(_lib, "load", lambda: lib)
     m, sd = _new(kind)
