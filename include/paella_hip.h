@@ -820,6 +820,66 @@ int paella_mod_ln_train_backward(const float* x, const float* residual /* may be
                                  int C, float* dx_out /* may be NULL */, float* dab_out /* may be NULL */, void* ws,
                                  size_t ws_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Training optimizer step (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays 8): the
+ * global gradient norm, `clip_grad_norm_`'s coefficient and the AdamW update of every parameter tensor as THREE
+ * launches over a table of tensors (paella_amd/csrc/optim.hip).  The other half of a training iteration
+ * (reference src/train.py:66-69: clip_grad_norm_(model.parameters(), 1.0); optimizer.step() with optim.AdamW).
+ * Everything fp32; the sums and the per-tensor scalars in fp64.
+ *   rows: n_tensors rows of paella_adamw_tensor that the DEVICE can read, one per parameter tensor, in the
+ *   caller's order.  g == NULL: the tensor has no gradient this step and is skipped entirely (not in the norm, p /
+ *   m / v / its step untouched; m and v may then be NULL too).  Work is cut into chunks of PAELLA_ADAMW_CHUNK
+ *   consecutive elements of ONE tensor: row i owns the chunks [chunk_begin[i], chunk_begin[i + 1]) (the last row up
+ *   to n_chunks), ceil(n / PAELLA_ADAMW_CHUNK) of them, or none for a row without a gradient or without elements.
+ *   chunk_begin starts at 0 and ascends.  A kernel finds the row of a chunk by binary search over the table.
+ *   Launch 1 (sumsq): per chunk, the sum of g^2 with every element widened to fp64 BEFORE it is squared (1e25 is an
+ *     ordinary value), in a fixed order (lane, wave shuffle, LDS): one double per chunk into the workspace.
+ *   Launch 2 (finalize, one workgroup): total = the chunk sums in ascending chunk order in a fixed tree;
+ *     norm_out[0] = (float)sqrt(total);  finite = isfinite(total);
+ *     coef = max_norm > 0 ? min(1, max_norm / (sqrt(total) + 1e-6)) : 1      (clip_grad_norm_'s formula with its clamp)
+ *     and, in paella_adamw_step only, for every row with a gradient when finite: steps[i] += 1 (float32, the dtype
+ *     torch's fused AdamW keeps on the device), step_size = lr / (1 - beta1^step) and 1 / sqrt(1 - beta2^step) in fp64.
+ *   Launch 3 (update; paella_adamw_step only): when !finite every workgroup returns at once -- p, m, v and steps
+ *     stay bit for bit (torch would write NaN into the weights).  Otherwise per element, torch's single-tensor
+ *     AdamW arithmetic in fp32 with IEEE sqrt and division:
+ *       g' = g coef;  p *= 1 - lr wd;  m += (g' - m)(1 - beta1);  v = v beta2 + (1 - beta2) g' g';
+ *       p -= step_size m / (sqrt(v) rsqrt_bc2 + eps)
+ *     g coef alone is formed in fp64 from the fp64 coef and rounded once (coef = 1 leaves g as it is): a coef rounded
+ *     to fp32 would put one relative error into every element of every tensor.
+ *     1 - lr wd, 1 - beta1 and 1 - beta2 are formed in fp64 from the row and rounded once.  g is never written.
+ *   16-byte vectors where every pointer of a tensor is 16-byte aligned, else a scalar path for that tensor (uniform
+ *   per chunk); all element offsets are 64-bit.
+ * Arguments: rows, norm_out, the workspace (and steps [n_tensors] float32 in paella_adamw_step) are required;
+ * n_tensors >= 0; n_chunks >= 0, and 0 when there is no tensor; max_norm not NaN (<= 0: no clipping; the norm is
+ * still computed and a non-finite step still skipped).  Anything else: PAELLA_ERR_ARG; a workspace smaller than
+ * paella_adamw_workspace_bytes(n_tensors, n_chunks) or not 16-byte aligned: PAELLA_ERR_WORKSPACE / PAELLA_ERR_ARG --
+ * before anything is enqueued.  The plan: a table the HOST can read as well (pinned host memory) is checked before
+ * anything is enqueued -- chunk_begin not ascending from 0 within n_chunks, or n < 0: PAELLA_ERR_ARG.  A table in
+ * device memory cannot be read without a synchronisation: the finalize launch makes the same check there and a
+ * plan that fails it is treated as a non-finite step (norm_out = NaN, nothing updated), and no kernel reads or
+ * writes an element outside [0, n) of a row whatever chunk_begin says.
+ * Workspace (no state between calls, no initialisation): 256 bytes of header (coef, finite), 2 doubles per tensor,
+ * one double per chunk, each part rounded up to 256 bytes.
+ * Deterministic: no atomics; the bits of the norm and of everything downstream are a function of the tensors'
+ * sizes, order and values only -- not of the grid or of the scheduling.  No allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------------------- */
+#define PAELLA_ADAMW_CHUNK 4096 /* elements per chunk; a multiple of 1024 */
+typedef struct paella_adamw_tensor {
+    float* p;            /* [n] the parameter */
+    const float* g;      /* [n] its gradient; NULL = none this step */
+    float* m;            /* [n] exp_avg */
+    float* v;            /* [n] exp_avg_sq */
+    int64_t n;           /* elements */
+    int64_t chunk_begin; /* index of the tensor's first chunk */
+    double lr, beta1, beta2, eps, weight_decay; /* as the caller's Python floats: 1 - beta2 must not be formed from an fp32 beta2 */
+} paella_adamw_tensor;
+int paella_adamw_chunk_elems(void); /* PAELLA_ADAMW_CHUNK */
+size_t paella_adamw_workspace_bytes(int n_tensors, int64_t n_chunks); /* 0 for negative arguments */
+int paella_adamw_grad_norm(const paella_adamw_tensor* rows, int n_tensors, int64_t n_chunks, float* norm_out, void* ws,
+                           size_t ws_bytes, void* stream); /* launches 1 and 2; reads g and n only, touches no step */
+int paella_adamw_step(const paella_adamw_tensor* rows, int n_tensors, int64_t n_chunks, float max_norm, float* steps,
+                      float* norm_out, void* ws, size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

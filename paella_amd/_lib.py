@@ -6,7 +6,7 @@ fallback -- if it is missing or fails to load, every product entry point raises.
 """
 import ctypes
 import os
-from ctypes import POINTER, Structure, c_char, c_char_p, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
+from ctypes import POINTER, Structure, c_char, c_char_p, c_double, c_float, c_int, c_int32, c_int64, c_size_t, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libpaella_hip.so")
@@ -75,6 +75,14 @@ class StepArgs(Structure):
         ("kw_table", c_void_p), ("kw_len", c_void_p), ("kw_pitch", c_int32),
         ("q_groups", c_void_p), ("qg_pitch", c_int32), ("k_groups", c_void_p), ("kg_pitch", c_int32),
         ("logits_out", c_void_p), ("tail", POINTER(TailArgs)),
+    ]
+
+
+class AdamwTensor(Structure):
+    """include/paella_hip.h: paella_adamw_tensor -- one row of the optimizer step's table (88 bytes, every field 8 wide: train_ops.ADAMW_ROW is the same layout in numpy)"""
+    _fields_ = [
+        ("p", c_void_p), ("g", c_void_p), ("m", c_void_p), ("v", c_void_p), ("n", c_int64), ("chunk_begin", c_int64),
+        ("lr", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("weight_decay", c_double),
     ]
 
 
@@ -245,6 +253,11 @@ SIGNATURES = {
     "paella_mod_ln_train_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "paella_mod_ln_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p,
                                              c_size_t, c_void_p]),
+    # training optimizer step (ABI 8, additive): global gradient norm + clip coefficient + AdamW over a device table of tensors (AdamwTensor rows), three launches
+    "paella_adamw_chunk_elems": (c_int, []),
+    "paella_adamw_workspace_bytes": (c_size_t, [c_int, c_int64]),
+    "paella_adamw_grad_norm": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "paella_adamw_step": (c_int, [c_void_p, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 # exported for tests / tools only; declared in paella_amd/csrc/test_hooks.h, not in the public header

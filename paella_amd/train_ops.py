@@ -6,6 +6,7 @@ Every op is written against the same scaffold, the helpers right below (the host
     _grad_outputs  the backward's outputs from `needs_input_grad`: a NULL output is not computed, and when none is wanted the call is skipped
     _refuse_*      the refusals every op makes -- not tensors, not the right dtype, not one cuda device, a scalar outside its range -- each op in its own order
 `paella_amd.training` imports the public names into its own namespace and the network calls them through those module globals."""
+import numpy as np
 import torch
 
 from . import _lib
@@ -431,3 +432,269 @@ def timestep_modulate(x, ab, residual=None, layernorm=False, eps=1e-6):
     MOD_COUNTERS["layernorm"] += int(layernorm)
     out = _TimestepModulate.apply(_nhwc(x, MOD_COUNTERS), None if residual is None else _nhwc(residual, MOD_COUNTERS), _aligned(ab.contiguous()), layernorm, eps)
     return (out[0].permute(0, 3, 1, 2), out[1]) if layernorm else out.permute(0, 3, 1, 2)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# Training optimizer step: clip_grad_norm_ + AdamW of every parameter as THREE launches over a device table of tensors (paella_amd/csrc/optim.hip,
+# include/paella_hip.h "Training optimizer step"): the gradients are read once for the norm, then p, g, m, v are read once and p, m, v written once.  The gradients
+# are never rewritten and nothing the size of the parameters is allocated.
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# one row of the table = include/paella_hip.h: paella_adamw_tensor = _lib.AdamwTensor (88 bytes, every field 8 wide)
+ADAMW_ROW = np.dtype([("p", "<u8"), ("g", "<u8"), ("m", "<u8"), ("v", "<u8"), ("n", "<i8"), ("chunk_begin", "<i8"),
+                      ("lr", "<f8"), ("beta1", "<f8"), ("beta2", "<f8"), ("eps", "<f8"), ("weight_decay", "<f8")])
+# diagnostic: how often `ClippedAdamW.step` ran and how often it had to wait for a staging buffer's earlier upload (tests, tools/bench_train_optimizer.py)
+ADAMW_COUNTERS = {"steps": 0, "staging_waits": 0}
+# what torch.optim.AdamW keeps in a parameter group besides lr, betas, eps and weight_decay, at the only values this optimizer has: a state dict of either class
+# then loads into the other
+_ADAMW_TORCH_KEYS = dict(amsgrad=False, maximize=False, foreach=None, capturable=False, differentiable=False, fused=None, decoupled_weight_decay=True)
+
+
+def adamw_chunk_plan(counts, chunk):
+    """element counts of the tensors, in order (0 for a tensor without elements or without a gradient) -> (the index of each tensor's first chunk, the number of
+    chunks): a tensor owns ceil(count / chunk) consecutive chunks of `chunk` elements, the last one possibly short"""
+    begins, c = [], 0
+    for n in counts:
+        if n < 0:
+            raise ValueError("a tensor of %d elements" % n)
+        begins.append(c)
+        c += -(-n // chunk)
+    return begins, c
+
+
+def _refuse_adamw_hyper(lr, betas, eps, weight_decay):
+    """torch.optim.AdamW's ranges"""
+    _refuse_out_of_range("lr", lr, isinstance(lr, (int, float)) and 0.0 <= lr, "must be a non-negative number (a tensor lr is not taken)")
+    _refuse_out_of_range("eps", eps, isinstance(eps, (int, float)) and 0.0 <= eps, "must be a non-negative number")
+    ok = isinstance(betas, (tuple, list)) and len(betas) == 2 and all(isinstance(b, (int, float)) for b in betas)
+    _refuse_out_of_range("betas", betas, ok and 0.0 <= betas[0] < 1.0, "betas[0] must lie in [0, 1)")
+    _refuse_out_of_range("betas", betas, 0.0 <= betas[1] < 1.0, "betas[1] must lie in [0, 1)")
+    _refuse_out_of_range("weight_decay", weight_decay, isinstance(weight_decay, (int, float)) and 0.0 <= weight_decay, "must be a non-negative number")
+
+
+def _dense_fp32_grad(g, dev):
+    """the gradient as the kernels read it: dense fp32 on dev -- itself, or a temporary copy / cast"""
+    if g.is_sparse or g.layout != torch.strided:
+        raise ValueError("sparse gradients are not taken (got layout %s)" % g.layout)
+    if g.dtype != torch.float32 or g.device != dev:
+        g = g.to(device=dev, dtype=torch.float32)
+    return g if g.is_contiguous() else g.contiguous()
+
+
+class ClippedAdamW(torch.optim.Optimizer):
+    """`nn.utils.clip_grad_norm_(params, max_norm); torch.optim.AdamW(params, ...).step()` as one HIP op of three launches (the reference's update,
+    src/train.py:66-69), for fp32 parameters on one cuda device:
+        norm = ||all gradients||_2 (summed in fp64);  coef = min(1, max_norm / (norm + 1e-6));  g' = g coef
+        p *= 1 - lr wd;  m += (g' - m)(1 - beta1);  v = v beta2 + (1 - beta2) g' g';  p -= lr / (1 - beta1^step) m / (sqrt(v) / sqrt(1 - beta2^step) + eps)
+    Parameter groups are honoured: lr, betas, eps and weight_decay per group, lr read from `param_groups` at every step (schedulers work as with torch's class).
+    max_norm is one value for the optimizer and the norm is global over every parameter that has a gradient; max_norm = None: no clipping -- the norm is still
+    computed.  After `step()`, `opt.grad_norm` is a 0-dim device tensor with the norm BEFORE clipping: what clip_grad_norm_ returns.
+    Two differences from the torch pair, both on purpose:
+      * the gradients are left UNCLIPPED: g' exists in registers only (p.grad after the step is what backward() wrote);
+      * a step whose norm is not finite (an inf or NaN gradient anywhere) is SKIPPED on the device: p, exp_avg, exp_avg_sq and step stay bit for bit, where torch
+        would write NaN into every weight.  `opt.grad_norm` is then inf or NaN, which is how a loop learns of it.
+    The state is torch AdamW's: state[p] = {"step", "exp_avg", "exp_avg_sq"}, created at a parameter's first gradient; "step" is a 0-dim float32 view into one flat
+    device array.  `state_dict()` loads into torch.optim.AdamW and a torch.optim.AdamW state dict (CPU "step" tensors included) loads into this class.
+    `step()` does not synchronise with the device: the table goes up from one of two pinned staging buffers, each guarded by an event, on the current stream; every
+    updated parameter's version is raised, which is what `Paella._signature` and hence the HIP engine and captured graphs notice.  Call it on ONE stream.
+    HIP only: amsgrad, maximize, foreach= / fused=, non-fp32 or non-contiguous parameters, parameters off the one cuda device, sparse gradients and hyperparameters
+    outside torch's ranges raise ValueError -- there is no torch fallback.  A non-contiguous or non-fp32 gradient is copied / cast to a dense fp32 temporary."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, max_norm=1.0, **unsupported):
+        for k, v in unsupported.items():
+            if k not in ("amsgrad", "maximize", "foreach", "fused", "capturable", "differentiable"):
+                raise TypeError("ClippedAdamW() got an unexpected keyword argument %r" % k)
+            if k in ("foreach", "fused") or v:
+                raise ValueError("ClippedAdamW is one HIP implementation: %s=%r is not taken (amsgrad, maximize, capturable and differentiable are not implemented, "
+                                 "foreach / fused select torch implementations)" % (k, v))
+        _refuse_adamw_hyper(lr, betas, eps, weight_decay)
+        if max_norm is not None:
+            _refuse_out_of_range("max_norm", max_norm, isinstance(max_norm, (int, float)) and 0.0 < max_norm < float("inf"), "must be positive and finite, or None")
+        self.max_norm = max_norm
+        self.grad_norm = None
+        self._device = None
+        self._steps = None              # flat float32 [number of parameters]: state[p]["step"] is a view of its element
+        self._index = {}                # parameter -> its row
+        self._rows_dev = self._ws = None
+        self._staging, self._events, self._turn = [None, None], [None, None], 0
+        super().__init__(params, dict(lr=lr, betas=tuple(betas), eps=eps, weight_decay=weight_decay, **_ADAMW_TORCH_KEYS))
+
+    def add_param_group(self, param_group):
+        g = dict(getattr(self, "defaults", {}), **{k: v for k, v in param_group.items() if k != "params"})
+        _refuse_adamw_hyper(g["lr"], g["betas"], g["eps"], g["weight_decay"])
+        if g.get("amsgrad") or g.get("maximize"):
+            raise ValueError("ClippedAdamW does not implement amsgrad or maximize")
+        ps = param_group["params"]
+        ps = [ps] if isinstance(ps, torch.Tensor) else list(ps)
+        param_group = dict(param_group, params=ps)
+        _refuse_non_tensors("ClippedAdamW", *ps)
+        _refuse_dtypes("ClippedAdamW", "fp32 parameters", ps)
+        dev = self._device
+        for p in ps:
+            if not p.is_cuda or (dev is not None and p.device != dev):
+                raise ValueError("ClippedAdamW runs on the HIP device only: every parameter must live on the same cuda device (got %s%s)"
+                                 % (p.device, "" if dev is None else " after %s" % dev))
+            dev = p.device
+            if not p.is_contiguous():
+                raise ValueError("ClippedAdamW takes contiguous parameters (got shape %s with strides %s)" % (tuple(p.shape), tuple(p.stride())))
+        super().add_param_group(param_group)
+        self._device = dev
+
+    # -- the flat step array ------------------------------------------------------------------------------------------------------------------------
+    def _params(self):
+        return [p for g in self.param_groups for p in g["params"]]
+
+    def _layout(self):
+        """the parameters in group order with their rows; grows the flat step array (and moves the views) when a group was added"""
+        ps = self._params()
+        if self._steps is None or self._steps.numel() != len(ps) or any(self._index.get(p) != i for i, p in enumerate(ps)):
+            old, old_index = self._steps, self._index
+            self._steps = torch.zeros(len(ps), dtype=torch.float32, device=self._device)
+            self._index = {p: i for i, p in enumerate(ps)}
+            for p, i in self._index.items():
+                if p in self.state and "step" in self.state[p]:
+                    if old is not None and p in old_index:
+                        self._steps[i].copy_(old[old_index[p]])
+                    self.state[p]["step"] = self._steps[i]
+        return ps
+
+    def state_dict(self):
+        """torch's layout; every "step" is a copy (0-dim float32 on the device), never a view of the flat array: an optimizer that loads it shares nothing with this one"""
+        sd = super().state_dict()
+        sd["state"] = {k: dict(st, step=st["step"].clone()) if torch.is_tensor(st.get("step")) else st for k, st in sd["state"].items()}
+        return sd
+
+    def load_state_dict(self, state_dict):
+        """takes a ClippedAdamW or a torch.optim.AdamW state dict (its "step" a CPU or device tensor of any float dtype, or a number) and re-packs the steps into
+        the flat device array; exp_avg / exp_avg_sq are made dense fp32 on the parameters' device"""
+        for g in state_dict["param_groups"]:
+            if g.get("amsgrad") or g.get("maximize"):
+                raise ValueError("ClippedAdamW does not implement amsgrad or maximize: this state dict was written with one of them")
+            _refuse_adamw_hyper(g["lr"], tuple(g["betas"]), g["eps"], g["weight_decay"])
+        super().load_state_dict(state_dict)
+        for g in self.param_groups:
+            g["betas"] = tuple(g["betas"])
+            for k, v in _ADAMW_TORCH_KEYS.items():
+                g[k] = v
+        self._steps, self._index = None, {}
+        loaded = {p: st.pop("step") for p, st in self.state.items() if "step" in st}
+        self._layout()
+        values = torch.zeros(self._steps.numel(), dtype=torch.float32)
+        on_device = []
+        for p, s in loaded.items():
+            i = self._index[p]
+            if torch.is_tensor(s) and s.is_cuda:
+                on_device.append((i, s))
+            else:
+                values[i] = float(s)
+        self._steps.copy_(values)
+        for i, s in on_device:
+            self._steps[i].copy_(s.detach().to(torch.float32).reshape(()))
+        for p, st in self.state.items():
+            st["step"] = self._steps[self._index[p]]
+            for k in ("exp_avg", "exp_avg_sq"):
+                st[k] = _aligned(st[k].detach().to(device=p.device, dtype=torch.float32).contiguous())
+
+    # -- the step -----------------------------------------------------------------------------------------------------------------------------------
+    def _stage(self, rows):
+        """rows (numpy, ADAMW_ROW) -> the device table.  A staging buffer is rewritten only after the upload that last read it has finished: two buffers, used in
+        turn, each with the event recorded behind its upload -- waiting for it is waiting for the step before the previous one"""
+        nbytes = rows.nbytes
+        t = self._turn = self._turn ^ 1
+        if self._events[t] is not None and not self._events[t].query():
+            ADAMW_COUNTERS["staging_waits"] += 1
+            self._events[t].synchronize()
+        if self._staging[t] is None or self._staging[t].numel() < nbytes:
+            self._staging[t] = torch.empty(max(nbytes, 1), dtype=torch.uint8, pin_memory=True)
+        if self._rows_dev is None or self._rows_dev.numel() < nbytes:
+            self._rows_dev = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self._device)
+        self._staging[t].numpy()[:nbytes] = rows.view(np.uint8).reshape(-1)
+        self._rows_dev[:nbytes].copy_(self._staging[t][:nbytes], non_blocking=True)
+        if self._events[t] is None:
+            self._events[t] = torch.cuda.Event()
+        self._events[t].record()
+        return self._rows_dev
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        lib = _lib.load()
+        ps = self._layout()
+        if not ps:
+            return loss
+        dev = self._device
+        chunk = lib.paella_adamw_chunk_elems()
+        rows = np.zeros(len(ps), dtype=ADAMW_ROW)
+        cols = {k: [] for k in ("p", "g", "m", "v", "n")}     # by column: one numpy assignment each
+        counts, hyper, keep, updated = [], [], [], []         # keep: the temporaries stay alive until the call is enqueued
+        with torch.cuda.device(dev):
+            for group in self.param_groups:
+                lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
+                _refuse_adamw_hyper(lr, (b1, b2), eps, wd)
+                hyper.extend([(lr, b1, b2, eps, wd)] * len(group["params"]))
+                for p in group["params"]:
+                    n = p.numel()
+                    cols["n"].append(n)
+                    if p.grad is None:
+                        counts.append(0)
+                        for k in "pgmv":
+                            cols[k].append(0)
+                        continue
+                    g = _dense_fp32_grad(p.grad, dev)
+                    keep.append(g)
+                    st = self.state[p]
+                    if not st:
+                        st["step"] = self._steps[self._index[p]]
+                        st["exp_avg"] = torch.zeros(p.shape, dtype=torch.float32, device=dev)
+                        st["exp_avg_sq"] = torch.zeros(p.shape, dtype=torch.float32, device=dev)
+                    cols["p"].append(p.data_ptr())
+                    cols["g"].append(g.data_ptr())
+                    cols["m"].append(st["exp_avg"].data_ptr())
+                    cols["v"].append(st["exp_avg_sq"].data_ptr())
+                    counts.append(n)
+                    updated.append(p)
+            for k, col in cols.items():
+                rows[k] = col
+            hyper = np.array(hyper, dtype=np.float64)
+            for j, k in enumerate(("lr", "beta1", "beta2", "eps", "weight_decay")):
+                rows[k] = hyper[:, j]
+            begins, n_chunks = adamw_chunk_plan(counts, chunk)
+            rows["chunk_begin"] = begins
+            ws_bytes = lib.paella_adamw_workspace_bytes(len(ps), n_chunks)
+            if self._ws is None or self._ws.numel() < ws_bytes:
+                self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
+            table = self._stage(rows)
+            norm = torch.empty((), dtype=torch.float32, device=dev)
+            _lib.check(lib.paella_adamw_step(table.data_ptr(), len(ps), n_chunks, 0.0 if self.max_norm is None else float(self.max_norm), self._steps.data_ptr(),
+                                             norm.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr(dev)))
+        self.grad_norm = norm
+        if updated:
+            torch.autograd.graph.increment_version(updated)   # the kernels wrote through raw pointers: this is what Paella._signature sees
+        ADAMW_COUNTERS["steps"] += 1
+        return loss
+
+
+def grad_norm(parameters):
+    """The 2-norm of all gradients of `parameters` (a tensor or an iterable; those without a gradient are left out) as a 0-dim fp32 device tensor, summed in fp64
+    in a fixed order: what `nn.utils.clip_grad_norm_` returns, without clipping anything.  HIP only: the gradients live on one cuda device; non-fp32 or
+    non-contiguous ones are cast / copied to a dense fp32 temporary, sparse ones raise ValueError."""
+    ps = [parameters] if isinstance(parameters, torch.Tensor) else list(parameters)
+    _refuse_non_tensors("grad_norm", *ps)
+    grads = [p.grad for p in ps if p.grad is not None]
+    if not grads:
+        raise ValueError("grad_norm: no parameter has a gradient")
+    _refuse_off_device("grad_norm", "the gradients", grads)
+    dev = grads[0].device
+    lib = _lib.load()
+    with torch.no_grad():
+        grads = [_dense_fp32_grad(g, dev) for g in grads]
+        rows = np.zeros(len(grads), dtype=ADAMW_ROW)
+        rows["g"] = [g.data_ptr() for g in grads]
+        rows["n"] = [g.numel() for g in grads]
+        rows["chunk_begin"], n_chunks = adamw_chunk_plan([g.numel() for g in grads], lib.paella_adamw_chunk_elems())
+        table = torch.from_numpy(rows.view(np.uint8).reshape(-1).copy()).to(dev)
+        norm = torch.empty((), dtype=torch.float32, device=dev)
+        _call("paella_adamw_grad_norm", dev, lib.paella_adamw_workspace_bytes(len(grads), n_chunks), table, len(grads), n_chunks, norm)
+    return norm

@@ -22,6 +22,8 @@ import torch.nn.functional as F
 from .train_ops import (ACT_MAX_B, ACT_MAX_C, ACT_MAX_P, ATTN_COUNTERS, ATTN_MAX_B, ATTN_MAX_HEADS, ATTN_MAX_L, ATTN_MAX_P, ATTN_MAX_ROWS, DW_COUNTERS,  # noqa: F401
                         DW_MAX_C, DW_MAX_C_SKIP, DW_MAX_POSITIONS, HEAD_MAX_K, HEAD_MAX_LABELS, HEAD_MAX_ROWS, MOD_COUNTERS, MOD_MAX_B, MOD_MAX_C, MOD_MAX_P,
                         MOD_MAX_POSITIONS, attention_dropout, dwconv_layernorm, gelu_grn_dropout, head_cross_entropy, refuse_head_widths, timestep_modulate)
+# the other half of an iteration: clip_grad_norm_ + AdamW as one HIP op, and the gradient norm alone
+from .train_ops import ADAMW_COUNTERS, ClippedAdamW, adamw_chunk_plan, grad_norm  # noqa: F401
 
 # which stretches of a block run as one HIP op: act = the middle of the MLP (Paella.set_training_activation), dw = the front of a ResBlock
 # (Paella.set_training_depthwise), attn = the attention core of an AttnBlock (Paella.set_training_attention).  `_forward_features` decides it once per forward
