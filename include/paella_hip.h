@@ -880,6 +880,48 @@ int paella_adamw_grad_norm(const paella_adamw_tensor* rows, int n_tensors, int64
 int paella_adamw_step(const paella_adamw_tensor* rows, int n_tensors, int64_t n_chunks, float max_norm, float* steps,
                       float* norm_out, void* ws, size_t ws_bytes, void* stream);
 
+/* ----------------------------------------------------------------------------------------------
+ * Training linear on bf16 operands (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays 8):
+ * y = x W^T + b of a linear layer in train mode, forward and backward, with the three GEMMs on the bf16 matrix
+ * cores and fp32 accumulation (paella_amd/csrc/linear_train.hip).  OPT-IN and OUTSIDE the fp32 parity contract, as
+ * paella_unet_set_precision(1) is for inference.  Every tensor of the interface is fp32; only the GEMM operands are
+ * rounded (round to nearest even, the bits of torch's .bfloat16()), into the workspace.
+ *   x [M, K], w [N, K], bias [N] or NULL, y [M, N], dy [M, N], dx [M, K], dw [N, K], db [N], all dense row-major.
+ *   Forward:  y = bf16(x) bf16(w)^T + bias            (products exact in fp32, fp32 accumulation, one rounding for the bias)
+ *   Backward: dx = bf16(dy) bf16(w);  dw = bf16(dy)^T bf16(x);  db = the column sums of the UNROUNDED dy, carried in
+ *     fp64 and rounded once.  dx_out, dw_out and db_out are WRITTEN, not accumulated into; each may be NULL and is then
+ *     neither packed for nor computed (dx alone needs neither x nor the transposed dy); with all three NULL nothing is
+ *     launched.  w is required for dx, x for dw.
+ *   paella_pack_bf16: the pass that makes the operands, alone.  src [rows, cols] fp32 is read exactly once and any
+ *     subset of out_rowmajor [rows, cols] bf16, out_transposed [cols, rows] bf16 and colsum [cols] fp32 (NULL = absent;
+ *     at least one) is written.  Its workspace holds the column sums' partials and is needed only when colsum is given
+ *     and the tensor is more than one strip: one double per (strip, column), rounded up to 256 bytes.
+ * Shapes: M, N and K (rows and cols) positive multiples of 64 up to 65535 x 64 (the pack's grid) -- each of them is the reduction of one of
+ * the three GEMMs; every tensor and the workspace 16-byte aligned.  Anything else or a NULL required pointer:
+ * PAELLA_ERR_ARG; a workspace too small for the call: PAELLA_ERR_WORKSPACE -- both before anything is enqueued.
+ * Launches.  Forward: pack x (row-major), pack w (row-major), the GEMM with the bias in its epilogue.  Backward:
+ * one pack over dy (row-major for dx, transposed for dw, column sums for db, whichever are wanted) and, beyond one
+ * strip, the finalize of the column sums; pack x (transposed) for dw; pack w (transposed) for dx; the dgrad GEMM; the
+ * wgrad GEMM.  The GEMMs are gemm.hip's bf16-operand kernels under their own launch rules.
+ * Workspace (no state between calls; `direction` 0 = forward, 1 = backward; `wants` = 1 dx | 2 dw | 4 db, ignored
+ * by the forward): a split-K region first (the ticket header of PAELLA workspaces plus 64 MiB of slab space; the
+ * entry points zero the header on the stream themselves before their first GEMM, nothing else is initialised), then
+ * the bf16 operands of the call, each rounded up to 256 bytes, then the partials of db.
+ * Deterministic: no float atomics in the pack; strips of max(4, ceil(row tiles / 256)) row tiles of 64 rows, a
+ * function of the row count alone, partials added in ascending strip order.  The GEMMs combine split reductions in
+ * a fixed order (gemm.hip).  No allocation, no synchronisation.
+ * ---------------------------------------------------------------------------------------------- */
+size_t paella_linear_train_workspace_bytes(int M, int N, int K, int direction, int wants); /* 0 for an unsupported shape */
+int paella_linear_train_forward(const float* x, const float* w, const float* bias /* may be NULL */, float* y_out, int M,
+                                int N, int K, void* ws, size_t ws_bytes, void* stream);
+int paella_linear_train_backward(const float* x /* may be NULL without dw_out */, const float* w /* may be NULL without dx_out */,
+                                 const float* dy, float* dx_out /* may be NULL */, float* dw_out /* may be NULL */,
+                                 float* db_out /* may be NULL */, int M, int N, int K, void* ws, size_t ws_bytes,
+                                 void* stream);
+int paella_pack_bf16(const float* src, int rows, int cols, unsigned short* out_rowmajor /* may be NULL */,
+                     unsigned short* out_transposed /* may be NULL */, float* colsum /* may be NULL */, void* ws,
+                     size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -258,6 +258,11 @@ SIGNATURES = {
     "paella_adamw_workspace_bytes": (c_size_t, [c_int, c_int64]),
     "paella_adamw_grad_norm": (c_int, [c_void_p, c_int, c_int64, c_void_p, c_void_p, c_size_t, c_void_p]),
     "paella_adamw_step": (c_int, [c_void_p, c_int, c_int64, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # training linear on bf16 operands (ABI 8, additive): the pack (fp32 -> bf16 row-major / transposed / column sums) and forward, dgrad + wgrad + db over it
+    "paella_linear_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "paella_linear_train_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "paella_linear_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
+    "paella_pack_bf16": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 # exported for tests / tools only; declared in paella_amd/csrc/test_hooks.h, not in the public header

@@ -346,6 +346,7 @@ class Paella(_NativeModel, nn.Module):
         self._train_depthwise = "torch"
         self._train_attention = "torch"
         self._train_modulation = "torch"
+        self._train_gemm = "fp32"
         # Constructed in EVAL mode (an nn.Module normally starts in train mode): eval = the hand-written HIP engine, which is what
         # sampling needs; `model.train()` -- the switch the reference's training loops flip (src/train.py:47,
         # src_distributed/train.py:73,140,172) -- selects the differentiable torch-op evaluation of paella_amd/training.py.
@@ -515,6 +516,21 @@ class Paella(_NativeModel, nn.Module):
         if mode not in ("torch", "hip"):
             raise ValueError("training modulation must be 'torch' or 'hip'")
         self._train_modulation = mode
+        return self
+
+    def set_training_gemm(self, mode):
+        """On which operands the TRAIN-mode forward (`forward` and `forward_loss` after `model.train()`) and its backward run the routed linears -- the two of every
+        ResBlock / FeedForwardBlock MLP and, on the `set_training_attention("hip")` branch, the q, kv and out projections of every AttnBlock: "fp32" (default) is
+        `F.linear`, op for op as before; "bf16" runs forward, dgrad and wgrad on the bf16 matrix cores with fp32 accumulation (`paella_amd.training.linear_bf16`)
+        when the module is on a cuda device.  OPT-IN and OUTSIDE the fp32 parity contract, as `set_gemm_precision("bf16")` is for inference: only the operands of
+        those GEMMs are rounded, inside the op.  Activations, parameters, gradients and optimizer state stay fp32 in memory, every other training op is untouched, and
+        autograd keeps what `F.linear` keeps.  A site whose shapes the op does not take (rows, input or output features not a multiple of 64) runs `F.linear`,
+        counted in `paella_amd.training.LINEAR_COUNTERS["fallbacks"]`.  The torch attention branch, the `attn_weights` branch, the timestep and conditioning mappers,
+        the down- / up-sampling convolutions, the embedding, the classifier and the loss head stay where they are.  Independent of the four switches above and of
+        `set_gemm_precision`.  Eval mode -- the HIP inference engine -- never sees the switch."""
+        if mode not in ("fp32", "bf16"):
+            raise ValueError("training gemm must be 'fp32' or 'bf16'")
+        self._train_gemm = mode
         return self
 
     def __del__(self):

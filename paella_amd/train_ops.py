@@ -435,6 +435,109 @@ def timestep_modulate(x, ab, residual=None, layernorm=False, eps=1e-6):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
+# Training linear on bf16 operands: y = x W^T + b with the forward, dgrad and wgrad GEMMs on the bf16 matrix cores and fp32 accumulation
+# (paella_amd/csrc/linear_train.hip, include/paella_hip.h "Training linear on bf16 operands").  OPT-IN and outside the fp32 parity contract
+# (Paella.set_training_gemm("bf16")).  x, the weight, the bias, y and every gradient stay fp32 in memory: the op rounds the GEMM operands into its workspace, in
+# one pass per tensor, and autograd keeps x and the weight as they are -- what F.linear keeps.
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+LINEAR_GRAIN, LINEAR_MAX_DIM = 64, 65535 * 64
+# diagnostic: how often `linear_bf16` ran, how many backward calls reached the library, how many sites of the network fell back to F.linear because
+# `linear_shapes_ok` does not hold there, and how many inputs / gradients were not dense and had to be copied (tests, tools/bench_train_linear.py)
+LINEAR_COUNTERS = {"calls": 0, "backward": 0, "fallbacks": 0, "copied": 0}
+_WANT_DX, _WANT_DW, _WANT_DB = 1, 2, 4
+
+
+def linear_shapes_ok(M, N, K):
+    """the shapes `linear_bf16` takes: M rows, N output and K input features, each a positive multiple of 64 up to 65535 x 64 (the extent of the pack's grid) -- each of them is the reduction of one
+    of the three GEMMs (K forward, N dgrad, M wgrad), and the bf16 kernels step 64 elements of it at a time"""
+    return all(isinstance(v, int) and LINEAR_GRAIN <= v <= LINEAR_MAX_DIM and v % LINEAR_GRAIN == 0 for v in (M, N, K))
+
+
+def _dense(t):
+    """t itself when it is dense row-major memory on the 16-byte grain, else one copy (counted in LINEAR_COUNTERS["copied"])"""
+    if t.is_contiguous() and t.data_ptr() % 16 == 0:
+        return t
+    LINEAR_COUNTERS["copied"] += 1
+    return t.contiguous() if not t.is_contiguous() else t.clone()
+
+
+class _LinearBf16(torch.autograd.Function):
+    """(x [M, K], weight [N, K], bias [N] or None) -> y [M, N]; saves x and weight, fp32 as they are."""
+
+    @staticmethod
+    def forward(ctx, x, weight, bias):
+        M, K = x.shape
+        N = weight.size(0)
+        y = x.new_empty(M, N)
+        _call("paella_linear_train_forward", x.device, _lib.load().paella_linear_train_workspace_bytes(M, N, K, 0, 0), x, weight, bias, y, M, N, K)
+        ctx.save_for_backward(x, weight)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        x, weight = ctx.saved_tensors
+        M, K = x.shape
+        N = weight.size(0)
+        (dx, dw, db), wanted = _grad_outputs(ctx, x, weight, (N,))
+        if not wanted:
+            return None, None, None
+        dy = _dense(dy.to(torch.float32))
+        wants = (_WANT_DX if dx is not None else 0) | (_WANT_DW if dw is not None else 0) | (_WANT_DB if db is not None else 0)
+        LINEAR_COUNTERS["backward"] += 1
+        _call("paella_linear_train_backward", x.device, _lib.load().paella_linear_train_workspace_bytes(M, N, K, 1, wants), x, weight, dy, dx, dw, db, M, N, K)
+        return dx, dw, db
+
+
+def linear_bf16(x, weight, bias=None):
+    """F.linear(x, weight, bias) in train mode with its three GEMMs on the bf16 matrix cores:
+        y  = bf16(x) bf16(weight)^T + bias                                   (fp32 accumulation; y fp32)
+        dx = bf16(dy) bf16(weight),   dweight = bf16(dy)^T bf16(x),   dbias = dy.sum(0) of the unrounded dy, carried in fp64
+    x fp32 [..., K], flattened to M rows; weight fp32 [N, K]; bias fp32 [N] or None.  Returns y [..., N], contiguous.  Once differentiable in x, weight and bias; a
+    gradient autograd does not want is neither packed for nor computed.  Autograd keeps x and weight as they are, fp32 -- what F.linear keeps; the backward rounds
+    them again.  bf16(.) is round to nearest even, the bits of torch's .bfloat16().  OUTSIDE the fp32 parity contract: a result differs from F.linear's by the
+    rounding of the operands (relative 2^-9 per operand element).  Parameters, gradients and every tensor in memory stay fp32.  M, N and K multiples of 64 up to
+    65535 x 64 (`linear_shapes_ok`); an x or an arriving gradient that is not dense is copied once (counted).  HIP only: anything else raises ValueError -- there is no torch
+    fallback."""
+    tensors = (x, weight) if bias is None else (x, weight, bias)
+    _refuse_non_tensors("linear_bf16", *tensors)
+    _refuse_dtypes("linear_bf16", "fp32 x, weight and bias", (x, weight, bias))
+    if weight.dim() != 2 or x.dim() < 1 or x.size(-1) != weight.size(1):
+        raise ValueError("weight must be [N, K] with K = x.size(-1) (got x %s, weight %s)" % (tuple(x.shape), tuple(weight.shape)))
+    N, K = weight.shape
+    if bias is not None and tuple(bias.shape) != (N,):
+        raise ValueError("bias must be [N] = [%d] (got %s)" % (N, tuple(bias.shape)))
+    M = x.numel() // K if K else 0
+    for name, v in (("M", M), ("N", N), ("K", K)):
+        if not linear_shapes_ok(v, LINEAR_GRAIN, LINEAR_GRAIN):
+            raise ValueError("%s = %d (x %s, weight %s): the bf16 linear takes a multiple of %d in %d...%d"
+                             % (name, v, tuple(x.shape), tuple(weight.shape), LINEAR_GRAIN, LINEAR_GRAIN, LINEAR_MAX_DIM))
+    _refuse_off_device("linear_bf16", "x, weight and bias", (x, weight, bias))
+    LINEAR_COUNTERS["calls"] += 1
+    y = _LinearBf16.apply(_dense(x).view(M, K), _dense(weight), None if bias is None else _dense(bias))
+    return y.view(x.shape[:-1] + (N,))
+
+
+def pack_bf16(x, transposed=False, colsum=False):
+    """The pass that makes `linear_bf16`'s operands, alone: x fp32 [rows, cols] on a cuda device, rows and cols multiples of 64, read once.  Returns
+    (x.bfloat16() [rows, cols][, x.t().contiguous().bfloat16() [cols, rows] with transposed][, x.sum(0) fp32 [cols] with colsum, carried in fp64]); the bf16 tensors
+    have the bits of torch's conversion (`.view(torch.int16)` compares them).  HIP only: anything else raises ValueError."""
+    _refuse_non_tensors("pack_bf16", x)
+    _refuse_dtypes("pack_bf16", "fp32 x", (x,))
+    if x.dim() != 2 or not linear_shapes_ok(x.size(0), x.size(1), LINEAR_GRAIN):
+        raise ValueError("x %s: the pack takes [rows, cols], both multiples of %d in %d...%d" % (tuple(x.shape), LINEAR_GRAIN, LINEAR_GRAIN, LINEAR_MAX_DIM))
+    _refuse_off_device("pack_bf16", "x", (x,))
+    rows, cols = x.shape
+    x = _aligned(x.contiguous())
+    row = torch.empty(rows, cols, dtype=torch.bfloat16, device=x.device)
+    tr = torch.empty(cols, rows, dtype=torch.bfloat16, device=x.device) if transposed else None
+    cs = x.new_empty(cols) if colsum else None
+    # the partials of the column sums: one double per (strip, column), at most one strip per row tile
+    _call("paella_pack_bf16", x.device, 256 + (rows // LINEAR_GRAIN) * cols * 8 if colsum else 0, x, rows, cols, row, tr, cs)
+    return (row,) + (() if tr is None else (tr,)) + (() if cs is None else (cs,))
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
 # Training optimizer step: clip_grad_norm_ + AdamW of every parameter as THREE launches over a device table of tensors (paella_amd/csrc/optim.hip,
 # include/paella_hip.h "Training optimizer step"): the gradients are read once for the norm, then p, g, m, v are read once and p, m, v written once.  The gradients
 # are never rewritten and nothing the size of the parameters is allocated.

@@ -24,6 +24,8 @@ from .train_ops import (ACT_MAX_B, ACT_MAX_C, ACT_MAX_P, ATTN_COUNTERS, ATTN_MAX
                         MOD_MAX_POSITIONS, attention_dropout, dwconv_layernorm, gelu_grn_dropout, head_cross_entropy, refuse_head_widths, timestep_modulate)
 # the other half of an iteration: clip_grad_norm_ + AdamW as one HIP op, and the gradient norm alone
 from .train_ops import ADAMW_COUNTERS, ClippedAdamW, adamw_chunk_plan, grad_norm  # noqa: F401
+# the routed linears on bf16 operands (Paella.set_training_gemm("bf16")): the op, its shape rule, its counters, and the pack alone
+from .train_ops import LINEAR_COUNTERS, LINEAR_GRAIN, LINEAR_MAX_DIM, linear_bf16, linear_shapes_ok, pack_bf16  # noqa: F401
 
 # which stretches of a block run as one HIP op: act = the middle of the MLP (Paella.set_training_activation), dw = the front of a ResBlock
 # (Paella.set_training_depthwise), attn = the attention core of an AttnBlock (Paella.set_training_attention).  `_forward_features` decides it once per forward
@@ -31,7 +33,18 @@ _Route = namedtuple("_Route", "act dw attn")
 _TORCH = _Route(False, False, False)
 # Beside the route, not in it: Paella.set_training_modulation("hip") makes the JOINT between blocks one HIP op (`timestep_modulate`).  `_forward_features` then asks
 # a ResBlock / FeedForwardBlock in front of a TimestepBlock to hand its two summands over unadded (defer), and hands the op's LayerNorm rows (z) to the AttnBlock /
-# FeedForwardBlock behind it
+# FeedForwardBlock behind it.  Beside the route as well: Paella.set_training_gemm("bf16") sends the routed linears -- the two of every MLP and, on the route.attn
+# branch, the three projections of an AttnBlock -- through `_linear` below (`gemm` in the signatures)
+
+
+def _linear(x, weight, bias, gemm=False):
+    """F.linear; gemm (Paella.set_training_gemm("bf16"), train mode on a cuda device): `linear_bf16` where `linear_shapes_ok` holds, F.linear where it does not
+    (counted in LINEAR_COUNTERS["fallbacks"])"""
+    if gemm:
+        if linear_shapes_ok(x.numel() // max(x.size(-1), 1), weight.size(0), weight.size(1)):
+            return linear_bf16(x, weight, bias)
+        LINEAR_COUNTERS["fallbacks"] += 1
+    return F.linear(x, weight, bias)
 
 
 def _ln_nchw(x, eps=1e-6):
@@ -39,22 +52,22 @@ def _ln_nchw(x, eps=1e-6):
     return F.layer_norm(x.permute(0, 2, 3, 1), (x.size(1),), None, None, eps).permute(0, 3, 1, 2)
 
 
-def _channelwise(blk, x_nhwc, p_drop, training, route=_TORCH):
+def _channelwise(blk, x_nhwc, p_drop, training, route=_TORCH, gemm=False):
     """Linear -> GELU -> GlobalResponseNorm -> Dropout -> Linear (src/modules.py:49-53 / 30-40).  route.act (Paella.set_training_activation("hip"), train mode on a cuda
     device): the three middle stages run as one HIP op in both directions (`gelu_grn_dropout`)."""
     cw = blk.channelwise._modules
     if route.act:
-        h = gelu_grn_dropout(F.linear(x_nhwc, cw["0"].weight, cw["0"].bias), cw["2"].gamma, cw["2"].beta, p_drop)
-        return F.linear(h, cw["4"].weight, cw["4"].bias)
-    h = F.gelu(F.linear(x_nhwc, cw["0"].weight, cw["0"].bias))
+        h = gelu_grn_dropout(_linear(x_nhwc, cw["0"].weight, cw["0"].bias, gemm), cw["2"].gamma, cw["2"].beta, p_drop)
+        return _linear(h, cw["4"].weight, cw["4"].bias, gemm)
+    h = F.gelu(_linear(x_nhwc, cw["0"].weight, cw["0"].bias, gemm))
     gx = torch.norm(h, p=2, dim=(1, 2), keepdim=True)
     nx = gx / (gx.mean(dim=-1, keepdim=True) + 1e-6)
     h = cw["2"].gamma * (h * nx) + cw["2"].beta + h
     h = F.dropout(h, p_drop, training)
-    return F.linear(h, cw["4"].weight, cw["4"].bias)
+    return _linear(h, cw["4"].weight, cw["4"].bias, gemm)
 
 
-def _res_block(blk, x, skip, p_drop, training, route=_TORCH, defer=False):
+def _res_block(blk, x, skip, p_drop, training, route=_TORCH, defer=False, gemm=False):
     """ResBlock (src/modules.py:43-62): depthwise 3x3 (groups = c, over cat([x, skip]) when a skip arrives) -> LN -> MLP -> + x.  route.dw
     (Paella.set_training_depthwise("hip"), train mode on a cuda device): everything in front of the MLP runs as one HIP op in both directions
     (`dwconv_layernorm`), x and skip handed over separately -- no torch.cat.  defer: the two summands (MLP output, x) come back unadded."""
@@ -67,15 +80,15 @@ def _res_block(blk, x, skip, p_drop, training, route=_TORCH, defer=False):
         dw = blk.depthwise
         c = dw.weight.size(0)
         y = _ln_nchw(F.conv2d(x, dw.weight, dw.bias, padding=dw.weight.size(-1) // 2, groups=c)).permute(0, 2, 3, 1)
-    out = _channelwise(blk, y, p_drop, training, route).permute(0, 3, 1, 2)
+    out = _channelwise(blk, y, p_drop, training, route, gemm).permute(0, 3, 1, 2)
     return (out, res) if defer else out + res
 
 
-def _ff_block(blk, x, p_drop, training, route=_TORCH, z=None, defer=False):
+def _ff_block(blk, x, p_drop, training, route=_TORCH, z=None, defer=False, gemm=False):
     """FeedForwardBlock (src/modules.py:82-96).  z [B, H W, C]: the LayerNorm rows of x, already made by `timestep_modulate`; defer: the two summands
     (MLP output, x) come back unadded."""
     rows = _ln_nchw(x).permute(0, 2, 3, 1) if z is None else z.view(x.size(0), x.size(2), x.size(3), x.size(1))
-    out = _channelwise(blk, rows, p_drop, training, route).permute(0, 3, 1, 2)
+    out = _channelwise(blk, rows, p_drop, training, route, gemm).permute(0, 3, 1, 2)
     return (out, x) if defer else x + out
 
 
@@ -85,12 +98,13 @@ def _timestep_block(blk, x, r_embed):
     return x * (1 + a) + b
 
 
-def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, training, attn_weights=None, route=_TORCH, z=None):
+def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, training, attn_weights=None, route=_TORCH, z=None, gemm=False):
     """AttnBlock (src/modules.py:65-79) around nn.MultiheadAttention semantics (Attention2D :7-19): queries = LN(x) positions,
     keys = values = [LN(x) positions | kv_mapper(SiLU(c_embed))], residual on the un-normed x.  route.attn (Paella.set_training_attention("hip"), train mode
     on a cuda device): between the in-projection (one F.linear for the queries, one for keys and values together) and the out-projection the block runs as one HIP
     op in both directions (`attention_dropout`).  With attn_weights the torch branch below runs under either setting: the key-weight table stays an inference
-    feature.  z [B, H W, C]: the LayerNorm rows of x, already made by `timestep_modulate` -- the queries on all three branches."""
+    feature.  z [B, H W, C]: the LayerNorm rows of x, already made by `timestep_modulate` -- the queries on all three branches.  gemm
+    (Paella.set_training_gemm("bf16")): the q, kv and out projections of the route.attn branch go through `_linear`; the other two branches keep their torch calls."""
     kvm = blk.kv_mapper._modules["1"]
     kv = F.linear(F.silu(c_embed), kvm.weight, kvm.bias)
     B, C, H, W = x.shape
@@ -100,8 +114,8 @@ def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, training, attn_weight
     at = blk.attention.attn
     if attn_weights is None and route.attn:
         w, bias = at.in_proj_weight, at.in_proj_bias
-        out = attention_dropout(F.linear(q, w[:C], bias[:C]), F.linear(kv, w[C:], bias[C:]), nhead, p_drop)
-        out = F.linear(out, at.out_proj.weight, at.out_proj.bias)
+        out = attention_dropout(_linear(q, w[:C], bias[:C], gemm), _linear(kv, w[C:], bias[C:], gemm), nhead, p_drop)
+        out = _linear(out, at.out_proj.weight, at.out_proj.bias, gemm)
     elif attn_weights is None:
         # torch's own functional form of nn.MultiheadAttention.forward (batch_first handled by the transposes): identical
         # arithmetic and identical dropout-stream consumption to the module the reference instantiates
@@ -164,7 +178,9 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
     drop = (lambda lvl: p_drop) if p_drop is not None else (lambda lvl: float(model.dropout[lvl]))
     if x_cat is not None:
         x = torch.cat([x, x_cat], dim=1)
-    r_embed = r_embedding(r.float(), cfg["c_r"])
+    # (the embedding is made in fp32 whatever the module's dtype -- its angles are fp32 products by definition -- and handed over in the dtype of the parameters:
+    # an fp32 module gets the same tensor, a module converted with .double() the fp32 embedding widened)
+    r_embed = r_embedding(r.float(), cfg["c_r"]).to(model.clf._modules["1"].weight.dtype)
     c_embed = c_embeddings(model, byt5, clip, clip_image)
     patch = cfg["patch_size"]
     n_levels = len(cfg["c_hidden"])
@@ -181,16 +197,18 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
         h = h.contiguous(memory_format=torch.channels_last)
     # Paella.set_training_modulation: carried beside the route.  "hip": the joint of every TimestepBlock with its neighbours in the level is `timestep_modulate`
     mod = on and getattr(model, "_train_modulation", "torch") == "hip"
+    # Paella.set_training_gemm: carried beside the route.  "bf16": the linears of every MLP and the projections around `attention_dropout` run on bf16 operands
+    gemm = on and getattr(model, "_train_gemm", "fp32") == "bf16"
 
     def run(blk, level, h, skip=None, z=None, defer=False):
         if blk.kind == 'C':
-            return _res_block(blk, h, skip, drop(level), training, route, defer)
+            return _res_block(blk, h, skip, drop(level), training, route, defer, gemm)
         if blk.kind == 'A':
-            return _attn_block(blk, h, c_embed, cfg["nhead"][level], cfg["self_attn"], drop(level), training, attn_weights, route, z)
+            return _attn_block(blk, h, c_embed, cfg["nhead"][level], cfg["self_attn"], drop(level), training, attn_weights, route, z, gemm)
         if blk.kind == 'T':
             return _timestep_block(blk, h, r_embed)
         if blk.kind == 'F':
-            return _ff_block(blk, h, drop(level), training, route, z, defer)
+            return _ff_block(blk, h, drop(level), training, route, z, defer, gemm)
         if blk.kind == 'D':  # LayerNorm2d + Conv2d(k2, s2)   (src/modules.py:153-156)
             cv = blk._modules["1"]
             return F.conv2d(_ln_nchw(h), cv.weight, cv.bias, stride=2)
