@@ -689,6 +689,18 @@ int paella_grn_act_backward(const float* u, const float* gamma, const float* gx,
                             float p_drop, uint64_t seed, float* du_out /* may be NULL */,
                             float* dgamma_out /* may be NULL */, float* dbeta_out /* may be NULL */, void* ws,
                             size_t ws_bytes, void* stream);
+/* The same two calls with the seed read from DEVICE memory (added ADDITIVELY, the version stays 8): seed_dev is the
+ * address of one 64-bit word (8-byte aligned; required when p_drop > 0, not read when p_drop == 0) that the drawing
+ * kernels load when they RUN -- so a captured call draws the mask of whatever the word holds at each replay.  A call
+ * whose word holds s gives the bits of the by-value call with seed = s, in both directions; the backward must find
+ * the word its forward found. */
+int paella_grn_act_forward_seed_dev(const float* u, const float* gamma, const float* beta, int B, int P, int C,
+                                    float p_drop, const uint64_t* seed_dev, float* z_out, float* gx_out, void* ws,
+                                    size_t ws_bytes, void* stream);
+int paella_grn_act_backward_seed_dev(const float* u, const float* gamma, const float* gx, const float* dz, int B,
+                                     int P, int C, float p_drop, const uint64_t* seed_dev,
+                                     float* du_out /* may be NULL */, float* dgamma_out /* may be NULL */,
+                                     float* dbeta_out /* may be NULL */, void* ws, size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training ResBlock front (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays 8): the
@@ -775,6 +787,18 @@ int paella_attn_train_backward(const float* q, int ldq, const float* k, int ldk,
                                int D, float p_drop, uint64_t seed, float* dq_out /* may be NULL */, int lddq,
                                float* dk_out /* may be NULL */, int lddk, float* dv_out /* may be NULL */, int lddv,
                                void* ws, size_t ws_bytes, void* stream);
+/* The same two calls with the seed read from DEVICE memory (added ADDITIVELY, the version stays 8), as
+ * paella_grn_act_*_seed_dev: seed_dev is one 8-byte aligned 64-bit word, required when p_drop > 0, loaded by the
+ * drawing kernels when they run; a word that holds s gives the bits of the by-value call with seed = s. */
+int paella_attn_train_forward_seed_dev(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                       int B, int nhead, int P, int L, int D, float p_drop, const uint64_t* seed_dev,
+                                       float* o_out, float* lse_out, void* ws, size_t ws_bytes, void* stream);
+int paella_attn_train_backward_seed_dev(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv,
+                                        const float* o, const float* lse, const float* d_o, int B, int nhead, int P,
+                                        int L, int D, float p_drop, const uint64_t* seed_dev,
+                                        float* dq_out /* may be NULL */, int lddq, float* dk_out /* may be NULL */,
+                                        int lddk, float* dv_out /* may be NULL */, int lddv, void* ws,
+                                        size_t ws_bytes, void* stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Training timestep modulation (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays 8): the
@@ -921,6 +945,23 @@ int paella_linear_train_backward(const float* x /* may be NULL without dw_out */
 int paella_pack_bf16(const float* src, int rows, int cols, unsigned short* out_rowmajor /* may be NULL */,
                      unsigned short* out_transposed /* may be NULL */, float* colsum /* may be NULL */, void* ws,
                      size_t ws_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Training seed table (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays 8): the
+ * dropout seeds of one training forward as DEVICE words, re-derived by one launch per iteration -- what lets a
+ * captured iteration (paella_amd.training.GraphTrainStep) draw other masks at every replay
+ * (paella_amd/csrc/train_seeds.hip).
+ *   state: uint64 [2 + n_sites] = (base, iteration, word[0 .. n_sites)), 8-byte aligned device memory the caller
+ *   owns and initialises (base = the run's seed, iteration = 0).
+ *   paella_train_seeds_advance: ONE launch.  iteration += 1, then for every site s
+ *     word[s] = w0 | w1 << 32,  (w0, w1, ., .) = philox4x32(key = base, counter (s, iteration))
+ *   with the Philox4x32-10 of the sampling tail and the dropout masks.  word[s] is what a *_seed_dev call takes.
+ * n_sites in 1...paella_train_seeds_max_sites() (65536); anything else, a NULL or misaligned state: PAELLA_ERR_ARG
+ * before anything is enqueued.  One workgroup walks the sites, so the count is read by every thread before one of
+ * them replaces it.  No allocation, no synchronisation, capturable in a graph.
+ * ---------------------------------------------------------------------------------------------- */
+int paella_train_seeds_max_sites(void);
+int paella_train_seeds_advance(uint64_t* state, int n_sites, void* stream);
 
 #ifdef __cplusplus
 }

@@ -263,6 +263,17 @@ SIGNATURES = {
     "paella_linear_train_forward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "paella_linear_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "paella_pack_bf16": (c_int, [c_void_p, c_int, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # training seed table (ABI 8, additive): the dropout seeds of a forward as device words, one launch per iteration; and the two dropout ops with the seed read
+    # from such a word (seed_dev in the place of seed) -- what a captured training iteration needs to draw other masks at every replay
+    "paella_train_seeds_max_sites": (c_int, []),
+    "paella_train_seeds_advance": (c_int, [c_void_p, c_int, c_void_p]),
+    "paella_grn_act_forward_seed_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "paella_grn_act_backward_seed_dev": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p,
+                                                 c_size_t, c_void_p]),
+    "paella_attn_train_forward_seed_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p,
+                                                   c_void_p, c_void_p, c_size_t, c_void_p]),
+    "paella_attn_train_backward_seed_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
+                                                    c_float, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
 }
 
 # exported for tests / tools only; declared in paella_amd/csrc/test_hooks.h, not in the public header

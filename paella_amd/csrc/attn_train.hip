@@ -63,16 +63,20 @@ struct Geo {
     float scale;             // 1 / sqrt(D)
     float p_drop, keep_scale;
     uint64_t key;
+    const uint64_t* seed_dev;  // the *_seed_dev forms: the seed is this device word and key the salt alone (NULL: key = seed ^ salt, by value)
     uint64_t quads;          // L4 / 4: Philox calls per (sample, head, query) row
 };
 
 // the multipliers of the 4 elements of one quad: 1 / (1 - p) where kept, 0 where dropped
-__device__ __forceinline__ void quad_keep(const Geo& g, uint64_t quad, float (&m)[4]) {
+__device__ __forceinline__ void quad_keep(const Geo& g, uint64_t key, uint64_t quad, float (&m)[4]) {
     uint32_t w[4];
-    philox4x32(g.key, quad, 0ull, w);
+    philox4x32(key, quad, 0ull, w);
 #pragma unroll
     for (int e = 0; e < 4; ++e) m[e] = u01_half_open(w[e]) >= g.p_drop ? g.keep_scale : 0.f;
 }
+
+// the Philox key of a drawing kernel: uniform, so the word comes by one scalar load
+__device__ __forceinline__ uint64_t dropout_key(const Geo& g) { return g.seed_dev ? g.key ^ *g.seed_dev : g.key; }
 
 // Forward.  grid (query tiles, nhead, B), one wave.  Lane (r16, kq) holds S^T[key = 16 kt + 4 kq + r][q = q0 + r16]: the four keys of ONE dropout quad.
 template <int DT, bool DROP>
@@ -83,6 +87,8 @@ __global__ __launch_bounds__(64) void attn_train_fwd_kernel(const float* __restr
     const int r16 = lane & 15, kq = lane >> 4;
     const int q0 = blockIdx.x * 16, h = blockIdx.y, b = blockIdx.z;
     const int P = g.P, L = g.L;
+    uint64_t key = 0ull;
+    if constexpr (DROP) key = dropout_key(g);
     const int qi = min(q0 + r16, P - 1);  // rows past P are clamped; their outputs are not stored
     const size_t row = ((size_t)b * g.nhead + h) * P + qi;
     f32x4 qf[DT];
@@ -138,7 +144,7 @@ __global__ __launch_bounds__(64) void attn_train_fwd_kernel(const float* __restr
         m_run = m_new;
         if constexpr (DROP) {
             float m[4];
-            quad_keep(g, (uint64_t)row * g.quads + (uint64_t)(kt * 4 + kq), m);
+            quad_keep(g, key, (uint64_t)row * g.quads + (uint64_t)(kt * 4 + kq), m);
 #pragma unroll
             for (int r = 0; r < 4; ++r) p[r] = m[r] > 0.f ? p[r] * m[r] : 0.f;
         }
@@ -200,6 +206,8 @@ __global__ __launch_bounds__(64) void attn_train_dq_kernel(const float* __restri
     const int r16 = lane & 15, kq = lane >> 4;
     const int q0 = blockIdx.x * 16, h = blockIdx.y, b = blockIdx.z;
     const int P = g.P, L = g.L;
+    uint64_t key = 0ull;
+    if constexpr (DROP) key = dropout_key(g);
     const int qi = min(q0 + r16, P - 1);
     const size_t row = ((size_t)b * g.nhead + h) * P + qi;
     f32x4 qf[DT], gf[DT];
@@ -245,7 +253,7 @@ __global__ __launch_bounds__(64) void attn_train_dq_kernel(const float* __restri
             }
         }
         float m[4] = {1.f, 1.f, 1.f, 1.f};
-        if constexpr (DROP) quad_keep(g, (uint64_t)row * g.quads + (uint64_t)(kt * 4 + kq), m);
+        if constexpr (DROP) quad_keep(g, key, (uint64_t)row * g.quads + (uint64_t)(kt * 4 + kq), m);
         float ds[4];
 #pragma unroll
         for (int r = 0; r < 4; ++r) {
@@ -279,6 +287,8 @@ __global__ __launch_bounds__(64) void attn_train_dkv_kernel(const float* __restr
     const int r16 = lane & 15, kq = lane >> 4;
     const int k0 = blockIdx.x * 16, h = blockIdx.y, b = blockIdx.z;
     const int P = g.P, L = g.L;
+    uint64_t key = 0ull;
+    if constexpr (DROP) key = dropout_key(g);
     const int ki = min(k0 + r16, L - 1);  // keys past L are clamped; their probabilities are masked and their rows not stored
     const bool key_ok = k0 + r16 < L;
     const size_t row0 = ((size_t)b * g.nhead + h) * P;
@@ -329,7 +339,7 @@ __global__ __launch_bounds__(64) void attn_train_dkv_kernel(const float* __restr
         if constexpr (DROP) {
             const int qd = min(qt * 16 + kq * 4 + (r16 & 3), P - 1);
             uint32_t w[4];
-            philox4x32(g.key, (uint64_t)(row0 + qd) * g.quads + (uint64_t)((k0 >> 2) + (r16 >> 2)), 0ull, w);
+            philox4x32(key, (uint64_t)(row0 + qd) * g.quads + (uint64_t)((k0 >> 2) + (r16 >> 2)), 0ull, w);
             bits = 0;
 #pragma unroll
             for (int e = 0; e < 4; ++e) bits |= (u01_half_open(w[e]) >= g.p_drop ? 1 : 0) << e;
@@ -404,14 +414,15 @@ int check_p(const char* who, float p_drop) {
     return PAELLA_ERR_ARG;
 }
 
-Geo make_geo(int nhead, int P, int L, int D, int ldq, int ldk, int ldv, float p_drop, uint64_t seed) {
+Geo make_geo(int nhead, int P, int L, int D, int ldq, int ldk, int ldv, float p_drop, uint64_t seed, const uint64_t* seed_dev) {
     Geo g = {};
     g.nhead = nhead; g.P = P; g.L = L;
     g.ldq = ldq; g.ldk = ldk; g.ldv = ldv;
     g.scale = 1.0f / sqrtf((float)D);
     g.p_drop = p_drop;
     g.keep_scale = 1.0f / (1.0f - p_drop);
-    g.key = p_drop > 0.f ? seed ^ kAttnDropoutSalt : 0ull;
+    g.key = p_drop > 0.f ? seed ^ kAttnDropoutSalt : 0ull;  // by pointer: seed = 0, the kernels add the word
+    g.seed_dev = p_drop > 0.f ? seed_dev : nullptr;
     g.quads = (uint64_t)((L + 3) / 4);
     return g;
 }
@@ -454,9 +465,10 @@ extern "C" size_t paella_attn_train_workspace_bytes(int B, int nhead, int P, int
     return plan_bytes(B, nhead, P);
 }
 
-extern "C" int paella_attn_train_forward(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int nhead, int P, int L, int D, float p_drop,
-                                         uint64_t seed, float* o, float* lse, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = "attn_train_forward";
+namespace {
+
+int forward_impl(const char* who, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int nhead, int P, int L, int D, float p_drop,
+                 uint64_t seed, const uint64_t* seed_dev, bool by_pointer, float* o, float* lse, void* ws, size_t ws_bytes, void* stream) {
     int rc = check_shape(who, B, nhead, P, L, D);
     if (rc == PAELLA_OK) rc = check_required(who, q && k && v && o && lse, "q, k, v, o and lse");
     if (rc == PAELLA_OK) rc = check_ld(who, "ldq", ldq, nhead * D);
@@ -464,20 +476,20 @@ extern "C" int paella_attn_train_forward(const float* q, int ldq, const float* k
     if (rc == PAELLA_OK) rc = check_ld(who, "ldv", ldv, nhead * D);
     if (rc == PAELLA_OK) rc = check_tensors_aligned16(who, q, k, v, o, lse);
     if (rc == PAELLA_OK) rc = check_p(who, p_drop);
+    if (rc == PAELLA_OK && by_pointer) rc = check_seed_dev(who, p_drop, seed_dev);
     if (rc == PAELLA_OK) rc = check_workspace(who, ws, ws_bytes, plan_bytes(B, nhead, P), "paella_attn_train_workspace_bytes asks for");
     if (rc != PAELLA_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const Geo g = make_geo(nhead, P, L, D, ldq, ldk, ldv, p_drop, seed);
+    const Geo g = make_geo(nhead, P, L, D, ldq, ldk, ldv, p_drop, seed, seed_dev);
     const dim3 grid((unsigned)((P + 15) / 16), (unsigned)nhead, (unsigned)B);
     ATTN_TRAIN_DISPATCH(D / 16, launch_fwd<DT>(p_drop > 0.f, grid, st, q, k, v, g, o, lse));
     LAUNCH_CHECK_RET();
     return PAELLA_OK;
 }
 
-extern "C" int paella_attn_train_backward(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o, const float* lse, const float* dout,
-                                          int B, int nhead, int P, int L, int D, float p_drop, uint64_t seed, float* dq, int lddq, float* dk, int lddk, float* dv,
-                                          int lddv, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = "attn_train_backward";
+int backward_impl(const char* who, const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o, const float* lse, const float* dout, int B,
+                  int nhead, int P, int L, int D, float p_drop, uint64_t seed, const uint64_t* seed_dev, bool by_pointer, float* dq, int lddq, float* dk, int lddk,
+                  float* dv, int lddv, void* ws, size_t ws_bytes, void* stream) {
     int rc = check_shape(who, B, nhead, P, L, D);
     if (rc == PAELLA_OK) rc = check_required(who, q && k && v && o && lse && dout, "q, k, v, o, lse and do");
     if (rc == PAELLA_OK) rc = check_ld(who, "ldq", ldq, nhead * D);
@@ -488,11 +500,12 @@ extern "C" int paella_attn_train_backward(const float* q, int ldq, const float* 
     if (rc == PAELLA_OK && dv) rc = check_ld(who, "lddv", lddv, nhead * D);
     if (rc == PAELLA_OK) rc = check_tensors_aligned16(who, q, k, v, o, lse, dout, dq, dk, dv);
     if (rc == PAELLA_OK) rc = check_p(who, p_drop);
+    if (rc == PAELLA_OK && by_pointer) rc = check_seed_dev(who, p_drop, seed_dev);
     if (rc == PAELLA_OK) rc = check_workspace(who, ws, ws_bytes, plan_bytes(B, nhead, P), "paella_attn_train_workspace_bytes asks for");
     if (rc != PAELLA_OK) return rc;
     if (!dq && !dk && !dv) return PAELLA_OK;
     hipStream_t st = (hipStream_t)stream;
-    Geo g = make_geo(nhead, P, L, D, ldq, ldk, ldv, p_drop, seed);
+    Geo g = make_geo(nhead, P, L, D, ldq, ldk, ldv, p_drop, seed, seed_dev);
     float* delta = (float*)ws;
     const int64_t rows = (int64_t)B * nhead * P;
     hipLaunchKernelGGL(attn_train_delta_kernel, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, st, o, dout, nhead, P, D, rows, delta);
@@ -512,4 +525,30 @@ extern "C" int paella_attn_train_backward(const float* q, int ldq, const float* 
         LAUNCH_CHECK_RET();
     }
     return PAELLA_OK;
+}
+
+}  // namespace
+
+extern "C" int paella_attn_train_forward(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int nhead, int P, int L, int D, float p_drop,
+                                         uint64_t seed, float* o, float* lse, void* ws, size_t ws_bytes, void* stream) {
+    return forward_impl("attn_train_forward", q, ldq, k, ldk, v, ldv, B, nhead, P, L, D, p_drop, seed, nullptr, false, o, lse, ws, ws_bytes, stream);
+}
+
+extern "C" int paella_attn_train_forward_seed_dev(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, int B, int nhead, int P, int L, int D,
+                                                  float p_drop, const uint64_t* seed_dev, float* o, float* lse, void* ws, size_t ws_bytes, void* stream) {
+    return forward_impl("attn_train_forward_seed_dev", q, ldq, k, ldk, v, ldv, B, nhead, P, L, D, p_drop, 0ull, seed_dev, true, o, lse, ws, ws_bytes, stream);
+}
+
+extern "C" int paella_attn_train_backward(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o, const float* lse, const float* dout,
+                                          int B, int nhead, int P, int L, int D, float p_drop, uint64_t seed, float* dq, int lddq, float* dk, int lddk, float* dv,
+                                          int lddv, void* ws, size_t ws_bytes, void* stream) {
+    return backward_impl("attn_train_backward", q, ldq, k, ldk, v, ldv, o, lse, dout, B, nhead, P, L, D, p_drop, seed, nullptr, false, dq, lddq, dk, lddk, dv, lddv, ws,
+                         ws_bytes, stream);
+}
+
+extern "C" int paella_attn_train_backward_seed_dev(const float* q, int ldq, const float* k, int ldk, const float* v, int ldv, const float* o, const float* lse,
+                                                   const float* dout, int B, int nhead, int P, int L, int D, float p_drop, const uint64_t* seed_dev, float* dq, int lddq,
+                                                   float* dk, int lddk, float* dv, int lddv, void* ws, size_t ws_bytes, void* stream) {
+    return backward_impl("attn_train_backward_seed_dev", q, ldq, k, ldk, v, ldv, o, lse, dout, B, nhead, P, L, D, p_drop, 0ull, seed_dev, true, dq, lddq, dk, lddk, dv,
+                         lddv, ws, ws_bytes, stream);
 }

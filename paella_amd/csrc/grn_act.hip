@@ -7,7 +7,9 @@
 //
 // h is never stored: every pass recomputes it from u, and the only tensor the forward leaves for the backward is G [B, C].  The dropout mask is never stored
 // either: element e (flat index in [B, P, C]) takes word e & 3 of philox4x32(seed ^ kDropoutSalt, e >> 2, 0), one Philox call per 16-byte vector, and is kept
-// iff u01_half_open(word) >= p; both directions regenerate it.
+// iff u01_half_open(word) >= p; both directions regenerate it.  The seed arrives by value, or -- the *_seed_dev entry points, for a captured training step whose
+// every replay must draw other masks -- as the address of a 64-bit device word the kernels load themselves: the drawing kernels take (key, seed_dev) and use
+// key ^ *seed_dev, with key = the salt alone in that form and seed ^ salt (seed_dev = NULL) in the by-value form, so a word that holds s gives the bits of seed = s.
 //
 // Each direction is two passes over the tensor around small finalize launches.  A workgroup is 4 waves over 256 channels (one 16-byte vector per lane: a wave
 // touches 1 KiB of a row) and a STRIP of rows of one sample; wave w takes rows w, w + 4, ... of the strip.
@@ -100,8 +102,9 @@ __device__ __forceinline__ double block_sum(double v, double* red) {
 // Pass A.  grid (channel blocks, strips, B).  Forward: part0 [B, strips, C] = sum over the strip of h^2.  Backward: part0 = sum of dy h, part1 = sum of dy.
 template <bool BWD, bool DROP>
 __global__ __launch_bounds__(kThreads) void grn_act_sums_kernel(const float* __restrict__ u, const float* __restrict__ dz, Geo g, float p_drop, float scale, uint64_t key,
-                                                                float* __restrict__ part0, float* __restrict__ part1) {
+                                                                const uint64_t* __restrict__ seed_dev, float* __restrict__ part0, float* __restrict__ part1) {
     __shared__ double red[BWD ? 2 : 1][kWaves - 1][kVecPerBlock][4];
+    if (DROP && seed_dev) key ^= *seed_dev;  // uniform: one scalar load
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c4 = blockIdx.x * kVecPerBlock + lane;
     const int strip = blockIdx.y, b = blockIdx.z;
@@ -257,7 +260,9 @@ __global__ __launch_bounds__(kThreads) void grn_act_param_grad_kernel(const floa
 template <bool BWD, bool DROP>
 __global__ __launch_bounds__(kThreads) void grn_act_apply_kernel(const float* __restrict__ u, const float* __restrict__ dz, const float* __restrict__ gamma,
                                                                  const float* __restrict__ beta, const float* __restrict__ gx, const float* __restrict__ mtab,
-                                                                 const float* __restrict__ tab_k, Geo g, float p_drop, float scale, uint64_t key, float* __restrict__ out) {
+                                                                 const float* __restrict__ tab_k, Geo g, float p_drop, float scale, uint64_t key,
+                                                                 const uint64_t* __restrict__ seed_dev, float* __restrict__ out) {
+    if (DROP && seed_dev) key ^= *seed_dev;  // uniform: one scalar load
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const int c4 = blockIdx.x * kVecPerBlock + lane;
     const int strip = blockIdx.y, b = blockIdx.z;
@@ -314,22 +319,15 @@ int check_shape(const char* who, int B, int P, int C) {
     return PAELLA_ERR_ARG;
 }
 
-}  // namespace
-
-extern "C" size_t paella_grn_act_workspace_bytes(int B, int P, int C) {
-    if (!shape_ok(B, P, C)) return 0;
-    return make_plan(B, P, C).bytes;
-}
-
-extern "C" int paella_grn_act_forward(const float* u, const float* gamma, const float* beta, int B, int P, int C, float p_drop, uint64_t seed, float* z, float* gx, void* ws,
-                                      size_t ws_bytes, void* stream) {
-    const char* who = "grn_act_forward";
+int forward_impl(const char* who, const float* u, const float* gamma, const float* beta, int B, int P, int C, float p_drop, uint64_t seed, const uint64_t* seed_dev,
+                 bool by_pointer, float* z, float* gx, void* ws, size_t ws_bytes, void* stream) {
     int rc = check_shape(who, B, P, C);
     if (rc == PAELLA_OK) rc = check_required(who, u && gamma && beta && z && gx, "u, gamma, beta, z and gx");
     if (rc == PAELLA_OK) rc = check_tensors_aligned16(who, u, gamma, beta, z, gx);
     if (rc != PAELLA_OK) return rc;
     const Plan pl = make_plan(B, P, C);
     rc = check_common(who, p_drop, pl, ws, ws_bytes);
+    if (rc == PAELLA_OK && by_pointer) rc = check_seed_dev(who, p_drop, seed_dev);
     if (rc != PAELLA_OK) return rc;
     hipStream_t st = (hipStream_t)stream;
     const Geo g = {P, C, pl.C4, pl.rows_per_strip, pl.strips};
@@ -337,30 +335,30 @@ extern "C" int paella_grn_act_forward(const float* u, const float* gamma, const 
     float* mtab = (float*)((char*)ws + pl.m_off);
     const dim3 grid((unsigned)pl.nblk_c, (unsigned)pl.strips, (unsigned)B);
     const float scale = 1.0f / (1.0f - p_drop);
-    const uint64_t key = seed ^ kDropoutSalt;
-    hipLaunchKernelGGL((grn_act_sums_kernel<false, false>), grid, dim3(kThreads), 0, st, u, (const float*)nullptr, g, 0.f, 1.f, 0ull, part0, (float*)nullptr);
+    const uint64_t key = seed ^ kDropoutSalt;  // by pointer: seed = 0, the kernels add the word
+    hipLaunchKernelGGL((grn_act_sums_kernel<false, false>), grid, dim3(kThreads), 0, st, u, (const float*)nullptr, g, 0.f, 1.f, 0ull, (const uint64_t*)nullptr, part0, (float*)nullptr);
     LAUNCH_CHECK_RET();
     hipLaunchKernelGGL(grn_act_fwd_finalize_kernel, dim3((unsigned)B), dim3(kFinalThreads), 0, st, (const float*)part0, g, gx, mtab);
     LAUNCH_CHECK_RET();
     if (p_drop > 0.f)
         hipLaunchKernelGGL((grn_act_apply_kernel<false, true>), grid, dim3(kThreads), 0, st, u, (const float*)nullptr, gamma, beta, (const float*)gx, (const float*)mtab,
-                           (const float*)nullptr, g, p_drop, scale, key, z);
+                           (const float*)nullptr, g, p_drop, scale, key, seed_dev, z);
     else
         hipLaunchKernelGGL((grn_act_apply_kernel<false, false>), grid, dim3(kThreads), 0, st, u, (const float*)nullptr, gamma, beta, (const float*)gx, (const float*)mtab,
-                           (const float*)nullptr, g, 0.f, 1.f, 0ull, z);
+                           (const float*)nullptr, g, 0.f, 1.f, 0ull, (const uint64_t*)nullptr, z);
     LAUNCH_CHECK_RET();
     return PAELLA_OK;
 }
 
-extern "C" int paella_grn_act_backward(const float* u, const float* gamma, const float* gx, const float* dz, int B, int P, int C, float p_drop, uint64_t seed, float* du,
-                                       float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream) {
-    const char* who = "grn_act_backward";
+int backward_impl(const char* who, const float* u, const float* gamma, const float* gx, const float* dz, int B, int P, int C, float p_drop, uint64_t seed,
+                  const uint64_t* seed_dev, bool by_pointer, float* du, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream) {
     int rc = check_shape(who, B, P, C);
     if (rc == PAELLA_OK) rc = check_required(who, u && gamma && gx && dz, "u, gamma, gx and dz");
     if (rc == PAELLA_OK) rc = check_tensors_aligned16(who, u, gamma, gx, dz, du, dgamma, dbeta);
     if (rc != PAELLA_OK) return rc;
     const Plan pl = make_plan(B, P, C);
     rc = check_common(who, p_drop, pl, ws, ws_bytes);
+    if (rc == PAELLA_OK && by_pointer) rc = check_seed_dev(who, p_drop, seed_dev);
     if (rc != PAELLA_OK) return rc;
     if (!du && !dgamma && !dbeta) return PAELLA_OK;
     hipStream_t st = (hipStream_t)stream;
@@ -374,9 +372,9 @@ extern "C" int paella_grn_act_backward(const float* u, const float* gamma, const
     const dim3 grid((unsigned)pl.nblk_c, (unsigned)pl.strips, (unsigned)B);
     const bool drop = p_drop > 0.f;
     const float scale = 1.0f / (1.0f - p_drop);
-    const uint64_t key = seed ^ kDropoutSalt;
-    if (drop) hipLaunchKernelGGL((grn_act_sums_kernel<true, true>), grid, dim3(kThreads), 0, st, u, dz, g, p_drop, scale, key, part0, part1);
-    else hipLaunchKernelGGL((grn_act_sums_kernel<true, false>), grid, dim3(kThreads), 0, st, u, dz, g, 0.f, 1.f, 0ull, part0, part1);
+    const uint64_t key = seed ^ kDropoutSalt;  // by pointer: seed = 0, the kernels add the word
+    if (drop) hipLaunchKernelGGL((grn_act_sums_kernel<true, true>), grid, dim3(kThreads), 0, st, u, dz, g, p_drop, scale, key, seed_dev, part0, part1);
+    else hipLaunchKernelGGL((grn_act_sums_kernel<true, false>), grid, dim3(kThreads), 0, st, u, dz, g, 0.f, 1.f, 0ull, (const uint64_t*)nullptr, part0, part1);
     LAUNCH_CHECK_RET();
     hipLaunchKernelGGL(grn_act_bwd_finalize_kernel, dim3((unsigned)B), dim3(kFinalThreads), 0, st, (const float*)part0, (const float*)part1, gamma, gx, g, tab_ns, tab_d, tab_k,
                        mtab);
@@ -389,11 +387,38 @@ extern "C" int paella_grn_act_backward(const float* u, const float* gamma, const
     if (du) {
         if (drop)
             hipLaunchKernelGGL((grn_act_apply_kernel<true, true>), grid, dim3(kThreads), 0, st, u, dz, gamma, (const float*)nullptr, gx, (const float*)mtab,
-                               (const float*)tab_k, g, p_drop, scale, key, du);
+                               (const float*)tab_k, g, p_drop, scale, key, seed_dev, du);
         else
             hipLaunchKernelGGL((grn_act_apply_kernel<true, false>), grid, dim3(kThreads), 0, st, u, dz, gamma, (const float*)nullptr, gx, (const float*)mtab,
-                               (const float*)tab_k, g, 0.f, 1.f, 0ull, du);
+                               (const float*)tab_k, g, 0.f, 1.f, 0ull, (const uint64_t*)nullptr, du);
         LAUNCH_CHECK_RET();
     }
     return PAELLA_OK;
+}
+
+}  // namespace
+
+extern "C" size_t paella_grn_act_workspace_bytes(int B, int P, int C) {
+    if (!shape_ok(B, P, C)) return 0;
+    return make_plan(B, P, C).bytes;
+}
+
+extern "C" int paella_grn_act_forward(const float* u, const float* gamma, const float* beta, int B, int P, int C, float p_drop, uint64_t seed, float* z, float* gx, void* ws,
+                                      size_t ws_bytes, void* stream) {
+    return forward_impl("grn_act_forward", u, gamma, beta, B, P, C, p_drop, seed, nullptr, false, z, gx, ws, ws_bytes, stream);
+}
+
+extern "C" int paella_grn_act_forward_seed_dev(const float* u, const float* gamma, const float* beta, int B, int P, int C, float p_drop, const uint64_t* seed_dev, float* z,
+                                               float* gx, void* ws, size_t ws_bytes, void* stream) {
+    return forward_impl("grn_act_forward_seed_dev", u, gamma, beta, B, P, C, p_drop, 0ull, seed_dev, true, z, gx, ws, ws_bytes, stream);
+}
+
+extern "C" int paella_grn_act_backward(const float* u, const float* gamma, const float* gx, const float* dz, int B, int P, int C, float p_drop, uint64_t seed, float* du,
+                                       float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream) {
+    return backward_impl("grn_act_backward", u, gamma, gx, dz, B, P, C, p_drop, seed, nullptr, false, du, dgamma, dbeta, ws, ws_bytes, stream);
+}
+
+extern "C" int paella_grn_act_backward_seed_dev(const float* u, const float* gamma, const float* gx, const float* dz, int B, int P, int C, float p_drop,
+                                                const uint64_t* seed_dev, float* du, float* dgamma, float* dbeta, void* ws, size_t ws_bytes, void* stream) {
+    return backward_impl("grn_act_backward_seed_dev", u, gamma, gx, dz, B, P, C, p_drop, 0ull, seed_dev, true, du, dgamma, dbeta, ws, ws_bytes, stream);
 }

@@ -27,6 +27,13 @@ inline int check_tensors_aligned16(const char* who, const T*... p) {
     return PAELLA_ERR_ARG;
 }
 
+// the seed word of the *_seed_dev forms of the dropout ops: required where a mask is drawn, and a uint64 sits on 8 bytes
+inline int check_seed_dev(const char* who, float p_drop, const uint64_t* seed_dev) {
+    if (!(p_drop > 0.f) || (seed_dev && ((uintptr_t)seed_dev & 7) == 0)) return PAELLA_OK;
+    paella_set_error("%s: seed_dev must be an 8-byte aligned device word when p_drop > 0", who);
+    return PAELLA_ERR_ARG;
+}
+
 // The message is "<who>: workspace of <ws_bytes> bytes, <asks> <need><tail>": `asks` names the sizing function or the call, `tail` whatever follows the figure.
 inline int check_workspace_size(const char* who, const void* ws, size_t ws_bytes, size_t need, const char* asks, const char* tail = "") {
     if (ws && ws_bytes >= need) return PAELLA_OK;

@@ -888,15 +888,17 @@ class Paella(_NativeModel, nn.Module):
                 return _InferenceOnly.apply(anchor, run_base).permute(0, 3, 1, 2)
         return run()
 
-    def forward_loss(self, x, r, target, byt5, clip=None, clip_image=None, x_cat=None, attn_weights=None, label_smoothing=0.1):
+    def forward_loss(self, x, r, target, byt5, clip=None, clip_image=None, x_cat=None, attn_weights=None, label_smoothing=0.1, seeds=None):
         """Train mode only: the forward of src/train.py:63-71 with the loss head fused -- returns (loss [B, H, W], correct [B, H, W] bool) where the reference
         computes `pred = model(...)`, `criterion(pred, target)` (nn.CrossEntropyLoss(label_smoothing, reduction='none')) and `pred.argmax(1) == target`.  The network
         up to the last LayerNorm2d is the torch-op evaluation of paella_amd/training.py; out_mapper's convolution and the loss run as one HIP op in both directions
-        (paella_amd.training.head_cross_entropy), so the [B, num_labels, H, W] logits never exist.  Exact fp32 whatever `set_gemm_precision` says."""
+        (paella_amd.training.head_cross_entropy), so the [B, num_labels, H, W] logits never exist.  Exact fp32 whatever `set_gemm_precision` says.  seeds: a
+        `paella_amd.training.TrainSeeds` -- the HIP dropout ops then read their seeds from its device words, in forward order (what a captured iteration,
+        `paella_amd.training.GraphTrainStep`, needs); None: every op draws its own seed, as always."""
         if not self.training:
             raise RuntimeError("forward_loss is the training path and this module is in eval mode: call model.train() first (eval mode serves the HIP inference engine)")
         from .training import forward_loss
-        return forward_loss(self, x, r, target, byt5, clip, clip_image, x_cat, attn_weights, label_smoothing)
+        return forward_loss(self, x, r, target, byt5, clip, clip_image, x_cat, attn_weights, label_smoothing, seeds)
 
     # ------------------------------------------------------------------ add_noise / loss weight
     def add_noise(self, x, t, mask=None, random_x=None):

@@ -58,6 +58,35 @@ def _aligned(t):
     return t if t.data_ptr() % 16 == 0 else t.clone()
 
 
+def _dropout_seed(op, seed, p, dev):
+    """the `seed=` argument of the two dropout ops -> what the Function carries: 0 at p = 0 (nothing is drawn, nothing is consumed); an int as its low 64 bits;
+    a one-element int64 tensor on dev (a `TrainSeeds.site()`: the kernels load the word when they run) as it is; None: one draw from torch's default CPU generator
+    -- refused while the current stream is capturing, where that host value would be frozen into the graph and every replay would repeat its masks"""
+    if p == 0.0:
+        return 0
+    if torch.is_tensor(seed):
+        if seed.device != dev:
+            raise ValueError("%s: a tensor seed must live on the op's device %s (got %s)" % (op, dev, seed.device))
+        return seed.detach()
+    if seed is None:
+        if dev.type == "cuda" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("%s: seed=None with p > 0 while the stream is capturing: the seed would be drawn on the host once and frozen into the graph. "
+                               "Pass seed=<a device word> (paella_amd.training.TrainSeeds.site())" % op)
+        seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+    return int(seed) & 0xFFFFFFFFFFFFFFFF
+
+
+def _refuse_seed_tensor(op, seed):
+    """a tensor handed over as `seed=` is one dense int64 element (asked before the device checks, whatever p is)"""
+    if torch.is_tensor(seed) and (seed.dtype != torch.int64 or seed.numel() != 1 or seed.layout != torch.strided or not seed.is_contiguous()):
+        raise ValueError("%s: a tensor seed must be one dense int64 element (got %s %s, %s)" % (op, seed.dtype, tuple(seed.shape), seed.layout))
+
+
+def _seed_entry(entry, seed):
+    """the entry point that takes this seed: by value, or `<entry>_seed_dev` for a device word"""
+    return entry + "_seed_dev" if torch.is_tensor(seed) else entry
+
+
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
 # Training loss head: out_mapper's convolution + label-smoothed cross-entropy as ONE HIP op, forward and backward (paella_amd/csrc/loss.hip,
 # include/paella_hip.h "Training loss head").  The [rows, num_labels] logits, their log-softmax and their gradient are never stored: the forward keeps
@@ -148,7 +177,7 @@ class _GeluGrnDropout(torch.autograd.Function):
         B, P, C = u.shape
         z = torch.empty_like(u)
         gx = u.new_empty(B, C)
-        _call("paella_grn_act_forward", u.device, _lib.load().paella_grn_act_workspace_bytes(B, P, C), u, gamma, beta, B, P, C, p, seed, z, gx)
+        _call(_seed_entry("paella_grn_act_forward", seed), u.device, _lib.load().paella_grn_act_workspace_bytes(B, P, C), u, gamma, beta, B, P, C, p, seed, z, gx)
         ctx.save_for_backward(u, gamma, gx)
         ctx.p, ctx.seed = p, seed
         return z
@@ -161,7 +190,7 @@ class _GeluGrnDropout(torch.autograd.Function):
         dz = _aligned(dz.to(torch.float32).contiguous())
         (du, dgamma, dbeta, _, _), wanted = _grad_outputs(ctx, u, gamma, gamma, None, None)
         if wanted:
-            _call("paella_grn_act_backward", u.device, _lib.load().paella_grn_act_workspace_bytes(B, P, C), u, gamma, gx, dz, B, P, C, ctx.p, ctx.seed, du, dgamma, dbeta)
+            _call(_seed_entry("paella_grn_act_backward", ctx.seed), u.device, _lib.load().paella_grn_act_workspace_bytes(B, P, C), u, gamma, gx, dz, B, P, C, ctx.p, ctx.seed, du, dgamma, dbeta)
         return du, dgamma, dbeta, None, None
 
 
@@ -171,7 +200,9 @@ def gelu_grn_dropout(u, gamma, beta, p=0.0, seed=None):
     (src/modules.py:30-40, 49-53).  u fp32 [B, ..., C] (the dimensions between the first and the last are the positions of a sample); gamma, beta fp32 with C
     elements (the module's [1, 1, 1, C] parameters as they are).  Once differentiable in u, gamma and beta; autograd keeps u, gamma and Gx [B, C] only.  p in
     [0, 1); p = 0 draws nothing.  The dropout mask is a function of (seed, element index): seed = None with p > 0 draws one 64-bit seed from torch's default CPU
-    generator, so torch.manual_seed reproduces a run.  C a multiple of 4 up to 16384, at most 2^20 positions per sample, B up to 65535.  HIP only and exact fp32
+    generator, so torch.manual_seed reproduces a run (refused with RuntimeError while the stream is capturing: that value would be frozen into the graph).  seed may also be a
+    one-element int64 tensor on u's device: the kernels load the word when they run, in both directions -- a word that holds s gives the bits of seed = s, and the
+    backward must find the word its forward found (`TrainSeeds`).  C a multiple of 4 up to 16384, at most 2^20 positions per sample, B up to 65535.  HIP only and exact fp32
     only: anything else raises ValueError -- there is no torch fallback."""
     _refuse_non_tensors("gelu_grn_dropout", u, gamma, beta)
     _refuse_dtypes("gelu_grn_dropout", "fp32 u, gamma and beta", (u, gamma, beta))
@@ -187,12 +218,9 @@ def gelu_grn_dropout(u, gamma, beta, p=0.0, seed=None):
         raise ValueError("u %s: the fused activation takes 1...%d samples of 1...%d positions" % (tuple(u.shape), ACT_MAX_B, ACT_MAX_P))
     p = float(p)
     _refuse_out_of_range("p", p, 0.0 <= p < 1.0, "must lie in [0, 1)")
+    _refuse_seed_tensor("gelu_grn_dropout", seed)
     _refuse_off_device("gelu_grn_dropout", "u, gamma and beta", (u, gamma, beta))
-    if p == 0.0:
-        seed = 0
-    elif seed is None:
-        seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    seed = _dropout_seed("gelu_grn_dropout", seed, p, u.device)
     z = _GeluGrnDropout.apply(_aligned(u.contiguous()).view(B, P, C), _aligned(gamma.contiguous().view(C)), _aligned(beta.contiguous().view(C)), p, seed)
     return z.view(u.shape)
 
@@ -299,7 +327,7 @@ class _AttentionDropout(torch.autograd.Function):
         L, D = kv.size(1), C // nhead
         o = torch.empty_like(q)
         lse = q.new_empty(B, nhead, P)
-        _call("paella_attn_train_forward", q.device, _lib.load().paella_attn_train_workspace_bytes(B, nhead, P, L, D), q, C, kv[..., :C], 2 * C, kv[..., C:], 2 * C,
+        _call(_seed_entry("paella_attn_train_forward", seed), q.device, _lib.load().paella_attn_train_workspace_bytes(B, nhead, P, L, D), q, C, kv[..., :C], 2 * C, kv[..., C:], 2 * C,
               B, nhead, P, L, D, p, seed, o, lse)
         ctx.save_for_backward(q, kv, o, lse)
         ctx.nhead, ctx.p, ctx.seed = nhead, p, seed
@@ -315,7 +343,7 @@ class _AttentionDropout(torch.autograd.Function):
         (dq, dkv, _, _, _), wanted = _grad_outputs(ctx, q, kv, None, None, None)
         if wanted:
             dk, dv = (None, None) if dkv is None else (dkv[..., :C], dkv[..., C:])
-            _call("paella_attn_train_backward", q.device, _lib.load().paella_attn_train_workspace_bytes(B, nhead, P, L, D), q, C, kv[..., :C], 2 * C, kv[..., C:], 2 * C,
+            _call(_seed_entry("paella_attn_train_backward", ctx.seed), q.device, _lib.load().paella_attn_train_workspace_bytes(B, nhead, P, L, D), q, C, kv[..., :C], 2 * C, kv[..., C:], 2 * C,
                   o, lse, do, B, nhead, P, L, D, ctx.p, ctx.seed, dq, C, dk, 2 * C, dv, 2 * C)
         return dq, dkv, None, None, None
 
@@ -327,7 +355,8 @@ def attention_dropout(q, kv, nhead, p=0.0, seed=None):
     q fp32 [B, P, C]; kv fp32 [B, L, 2C], keys in channels [0, C) and values in [C, 2C) -- what one F.linear(rows, in_proj_weight[C:], in_proj_bias[C:]) produces.
     Returns o [B, P, C], contiguous.  Once differentiable in q and kv; the gradient of kv comes back as one [B, L, 2C] tensor.  Besides q, kv and o autograd keeps
     lse [B, nhead, P] only.  p in [0, 1); p = 0 draws nothing.  The dropout mask is a function of (seed, element index): seed = None with p > 0 draws one 64-bit seed
-    from torch's default CPU generator, so torch.manual_seed reproduces a run.  D a multiple of 16 in 16...128, B and nhead up to 65535, P and L up to 2^20,
+    from torch's default CPU generator, so torch.manual_seed reproduces a run (refused with RuntimeError while the stream is capturing).  seed may also be a one-element
+    int64 tensor on q's device, read by the kernels when they run, as `gelu_grn_dropout` takes it.  D a multiple of 16 in 16...128, B and nhead up to 65535, P and L up to 2^20,
     B nhead P up to 2^31 - 1.  HIP only and exact fp32 only: anything else raises ValueError -- there is no torch fallback."""
     _refuse_non_tensors("attention_dropout", q, kv)
     _refuse_dtypes("attention_dropout", "fp32 q and kv", (q, kv))
@@ -345,14 +374,110 @@ def attention_dropout(q, kv, nhead, p=0.0, seed=None):
                          % (tuple(q.shape), tuple(kv.shape), ATTN_MAX_B, ATTN_MAX_P, ATTN_MAX_L))
     p = float(p)
     _refuse_out_of_range("p", p, 0.0 <= p < 1.0, "must lie in [0, 1)")
+    _refuse_seed_tensor("attention_dropout", seed)
     _refuse_off_device("attention_dropout", "q and kv", (q, kv))
-    if p == 0.0:
-        seed = 0
-    elif seed is None:
-        seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
-    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    seed = _dropout_seed("attention_dropout", seed, p, q.device)
     ATTN_COUNTERS["calls"] += 1
     return _AttentionDropout.apply(_aligned(q.contiguous()), _aligned(kv.contiguous()), nhead, p, seed)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+# Training seed table: the dropout seeds of one forward as DEVICE words, re-derived by one launch per iteration (paella_amd/csrc/train_seeds.hip,
+# include/paella_hip.h "Training seed table").  The two ops above take such a word as `seed=`; a captured iteration (`training.GraphTrainStep`) then draws other
+# masks at every replay, because the launch that advances the table is part of the graph.
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+SEEDS_MAX_SITES = 65536
+_MASK64 = 0xFFFFFFFFFFFFFFFF
+
+
+def _as_int64(v):
+    """the low 64 bits of a Python int as the int64 that holds those bits"""
+    v = int(v) & _MASK64
+    return v - (1 << 64) if v >> 63 else v
+
+
+class TrainSeeds:
+    """`n_sites` 64-bit seeds on `device`, one per drawing op call of a forward, as one int64 array (base, iteration, word[0 .. n_sites)):
+        advance()   ONE launch, no synchronisation, capturable: iteration += 1, word[s] = the first two words of philox4x32(key = base, counter (s, iteration))
+        begin()     a forward starts: the next `site()` is word 0
+        site()      the next word as a one-element int64 view -- what `gelu_grn_dropout(..., seed=)` / `attention_dropout(..., seed=)` take; raises when the table
+                    is too small.  Forward and backward of an op read the same word: nothing may advance the table between them
+        values()    the words as Python ints (unsigned), `iteration` / `base` those two entries; they synchronise -- tests and tools
+        set_base(seed)          rewrites the base word (the iteration stays)
+        snapshot() / restore()  (base, iteration) as a device copy, and back: without synchronising
+        grow(n_sites)           a larger table in this same object, base and iteration kept; views handed out by `site()` before it are dead
+    seed = None draws the base once from torch's default CPU generator, so torch.manual_seed reproduces a run.  The words are zero until the first advance()."""
+
+    def __init__(self, n_sites, seed=None, device="cuda"):
+        if isinstance(n_sites, bool) or not isinstance(n_sites, int) or not 1 <= n_sites <= SEEDS_MAX_SITES:
+            raise ValueError("n_sites = %r: a seed table takes 1...%d sites" % (n_sites, SEEDS_MAX_SITES))
+        device = torch.device(device)
+        if device.type != "cuda":
+            raise ValueError("a seed table lives on the HIP device (got %s)" % device)
+        if seed is not None and (isinstance(seed, bool) or not isinstance(seed, int)):
+            raise ValueError("seed = %r: an integer or None" % (seed,))
+        if seed is None:
+            seed = int(torch.randint(-2 ** 63, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        self.n_sites, self.device = n_sites, torch.device(device.type, torch.cuda.current_device() if device.index is None else device.index)
+        host = torch.zeros(2 + n_sites, dtype=torch.int64)
+        host[0] = _as_int64(seed)
+        self.state = host.to(self.device)
+        self._next = 0
+
+    def advance(self):
+        lib = _lib.load()
+        with torch.cuda.device(self.device):
+            _lib.check(lib.paella_train_seeds_advance(self.state.data_ptr(), self.n_sites, _lib.stream_ptr(self.device)))
+        return self
+
+    def begin(self):
+        self._next = 0
+        return self
+
+    def site(self):
+        i = self._next
+        if i >= self.n_sites:
+            raise RuntimeError("the seed table has %d sites and this forward asks for one more: size it with training.dropout_sites(model)" % self.n_sites)
+        self._next = i + 1
+        return self.state[2 + i:3 + i]
+
+    @property
+    def used(self):
+        """how many sites were handed out since `begin()`"""
+        return self._next
+
+    def values(self):
+        return [int(v) & _MASK64 for v in self.state[2:].tolist()]
+
+    @property
+    def base(self):
+        return int(self.state[0].item()) & _MASK64
+
+    @property
+    def iteration(self):
+        return int(self.state[1].item()) & _MASK64
+
+    def set_base(self, seed):
+        if isinstance(seed, bool) or not isinstance(seed, int):
+            raise ValueError("seed = %r: an integer" % (seed,))
+        self.state[:1].copy_(torch.tensor([_as_int64(seed)], dtype=torch.int64))
+        return self
+
+    def snapshot(self):
+        return self.state[:2].clone()
+
+    def grow(self, n_sites):
+        if isinstance(n_sites, bool) or not isinstance(n_sites, int) or not self.n_sites <= n_sites <= SEEDS_MAX_SITES:
+            raise ValueError("n_sites = %r: a seed table of %d sites grows to at most %d" % (n_sites, self.n_sites, SEEDS_MAX_SITES))
+        if n_sites > self.n_sites:
+            state = torch.zeros(2 + n_sites, dtype=torch.int64, device=self.device)
+            state[:2 + self.n_sites].copy_(self.state)
+            self.state, self.n_sites, self._next = state, n_sites, 0
+        return self
+
+    def restore(self, snap):
+        self.state[:2].copy_(snap)
+        return self
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
@@ -708,8 +833,7 @@ class ClippedAdamW(torch.optim.Optimizer):
             self._events[t].synchronize()
         if self._staging[t] is None or self._staging[t].numel() < nbytes:
             self._staging[t] = torch.empty(max(nbytes, 1), dtype=torch.uint8, pin_memory=True)
-        if self._rows_dev is None or self._rows_dev.numel() < nbytes:
-            self._rows_dev = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self._device)
+        self._reserve(nbytes, 0)
         self._staging[t].numpy()[:nbytes] = rows.view(np.uint8).reshape(-1)
         self._rows_dev[:nbytes].copy_(self._staging[t][:nbytes], non_blocking=True)
         if self._events[t] is None:
@@ -717,26 +841,67 @@ class ClippedAdamW(torch.optim.Optimizer):
         self._events[t].record()
         return self._rows_dev
 
-    @torch.no_grad()
-    def step(self, closure=None):
-        loss = None
-        if closure is not None:
-            with torch.enable_grad():
-                loss = closure()
+    def materialize_state(self):
+        """state[p] = {"step", "exp_avg", "exp_avg_sq"} for every parameter that requires a gradient, now instead of at its first gradient -- the zeros lazy creation
+        makes -- plus the device table and the workspace at the size a step over all of them needs.  After it a step allocates nothing but its norm: what a stream
+        capture of the launch part needs (`training.GraphTrainStep`).  A parameter that never gets a gradient keeps its row with count 0, as without this call."""
         lib = _lib.load()
         ps = self._layout()
+        dev = self._device
         if not ps:
-            return loss
+            return self
+        with torch.cuda.device(dev):
+            for p in ps:
+                if not p.requires_grad:
+                    continue
+                st = self.state[p]
+                if not st:
+                    st["step"] = self._steps[self._index[p]]
+                    st["exp_avg"] = torch.zeros(p.shape, dtype=torch.float32, device=dev)
+                    st["exp_avg_sq"] = torch.zeros(p.shape, dtype=torch.float32, device=dev)
+            _, n_chunks = adamw_chunk_plan([p.numel() for p in ps], lib.paella_adamw_chunk_elems())
+            self._reserve(len(ps) * ADAMW_ROW.itemsize, lib.paella_adamw_workspace_bytes(len(ps), n_chunks))
+        return self
+
+    def _reserve(self, table_bytes, ws_bytes):
+        """the device table and the workspace, grown when a step needs more (never shrunk: their addresses stay while the parameter set does)"""
+        if self._rows_dev is None or self._rows_dev.numel() < table_bytes:
+            self._rows_dev = torch.empty(max(table_bytes, 1), dtype=torch.uint8, device=self._device)
+        if self._ws is None or self._ws.numel() < ws_bytes:
+            self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=self._device)
+
+    # `step()` in three parts.  Only the LAUNCH part puts work on the stream that a capture may hold: the upload goes through a pinned staging copy guarded by
+    # event.query() / synchronize() and never sits inside one.  The PLAN is host code -- it reads addresses and `param_groups` -- and enqueues nothing ONCE the state
+    # is materialised and every gradient is dense fp32 on the device: then it may run while a stream is capturing, which a captured iteration needs, because the
+    # gradients whose addresses it reads are made by the captured backward.  Otherwise it allocates (first-gradient state, a temporary for a gradient that is not dense
+    # fp32): `GraphTrainStep` materialises the state before it captures and refuses a plan that kept a temporary.  The hyperparameter values a plan made at capture
+    # time holds are stale by the first replay: before every replay the iteration refreshes those columns (`_plan_hyper`) and uploads eagerly on the same stream --
+    # which is how a scheduler's `lr` reaches a captured step.
+    def _plan_hyper(self, rows):
+        """the hyperparameter columns of the host rows from `param_groups` as they are NOW"""
+        hyper = []
+        for group in self.param_groups:
+            lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
+            _refuse_adamw_hyper(lr, (b1, b2), eps, wd)
+            hyper.extend([(lr, b1, b2, eps, wd)] * len(group["params"]))
+        hyper = np.array(hyper, dtype=np.float64).reshape(len(rows), 5)
+        for j, k in enumerate(("lr", "beta1", "beta2", "eps", "weight_decay")):
+            rows[k] = hyper[:, j]
+        return rows
+
+    def _plan(self):
+        """part 1, host only apart from a temporary for a gradient that is not dense fp32 and the state of a parameter's first gradient: -> dict(rows = the host table
+        (numpy, ADAMW_ROW), n, n_chunks, keep = temporaries that must outlive the launch, updated = the parameters the step will write); sizes table and workspace"""
+        lib = _lib.load()
+        ps = self._layout()
         dev = self._device
         chunk = lib.paella_adamw_chunk_elems()
         rows = np.zeros(len(ps), dtype=ADAMW_ROW)
         cols = {k: [] for k in ("p", "g", "m", "v", "n")}     # by column: one numpy assignment each
-        counts, hyper, keep, updated = [], [], [], []         # keep: the temporaries stay alive until the call is enqueued
+        counts, keep, updated = [], [], []                    # keep: the temporaries stay alive until the call is enqueued
         with torch.cuda.device(dev):
             for group in self.param_groups:
-                lr, (b1, b2), eps, wd = group["lr"], group["betas"], group["eps"], group["weight_decay"]
-                _refuse_adamw_hyper(lr, (b1, b2), eps, wd)
-                hyper.extend([(lr, b1, b2, eps, wd)] * len(group["params"]))
+                _refuse_adamw_hyper(group["lr"], group["betas"], group["eps"], group["weight_decay"])   # per group, before its state is created: the order step() always had
                 for p in group["params"]:
                     n = p.numel()
                     cols["n"].append(n)
@@ -760,21 +925,39 @@ class ClippedAdamW(torch.optim.Optimizer):
                     updated.append(p)
             for k, col in cols.items():
                 rows[k] = col
-            hyper = np.array(hyper, dtype=np.float64)
-            for j, k in enumerate(("lr", "beta1", "beta2", "eps", "weight_decay")):
-                rows[k] = hyper[:, j]
+            self._plan_hyper(rows)
             begins, n_chunks = adamw_chunk_plan(counts, chunk)
             rows["chunk_begin"] = begins
-            ws_bytes = lib.paella_adamw_workspace_bytes(len(ps), n_chunks)
-            if self._ws is None or self._ws.numel() < ws_bytes:
-                self._ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
-            table = self._stage(rows)
+            self._reserve(rows.nbytes, lib.paella_adamw_workspace_bytes(len(ps), n_chunks))
+        return dict(rows=rows, n=len(ps), n_chunks=n_chunks, keep=keep, updated=updated)
+
+    def _upload(self, plan):
+        """part 2: the host rows -> the device table, through a pinned staging buffer on the current stream.  Never inside a capture."""
+        with torch.cuda.device(self._device):
+            return self._stage(plan["rows"])
+
+    def _launch(self, plan):
+        """part 3: the three launches of paella_adamw_step over the device table at its fixed address; -> the norm (0-dim, made here).  Capturable."""
+        dev = self._device
+        with torch.cuda.device(dev):
             norm = torch.empty((), dtype=torch.float32, device=dev)
-            _lib.check(lib.paella_adamw_step(table.data_ptr(), len(ps), n_chunks, 0.0 if self.max_norm is None else float(self.max_norm), self._steps.data_ptr(),
-                                             norm.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr(dev)))
-        self.grad_norm = norm
-        if updated:
-            torch.autograd.graph.increment_version(updated)   # the kernels wrote through raw pointers: this is what Paella._signature sees
+            _lib.check(_lib.load().paella_adamw_step(self._rows_dev.data_ptr(), plan["n"], plan["n_chunks"], 0.0 if self.max_norm is None else float(self.max_norm),
+                                                     self._steps.data_ptr(), norm.data_ptr(), self._ws.data_ptr(), self._ws.numel(), _lib.stream_ptr(dev)))
+        return norm
+
+    @torch.no_grad()
+    def step(self, closure=None):
+        loss = None
+        if closure is not None:
+            with torch.enable_grad():
+                loss = closure()
+        if not self._params():
+            return loss
+        plan = self._plan()
+        self._upload(plan)
+        self.grad_norm = self._launch(plan)
+        if plan["updated"]:
+            torch.autograd.graph.increment_version(plan["updated"])   # the kernels wrote through raw pointers: this is what Paella._signature sees
         ADAMW_COUNTERS["steps"] += 1
         return loss
 

@@ -26,6 +26,8 @@ from .train_ops import (ACT_MAX_B, ACT_MAX_C, ACT_MAX_P, ATTN_COUNTERS, ATTN_MAX
 from .train_ops import ADAMW_COUNTERS, ClippedAdamW, adamw_chunk_plan, grad_norm  # noqa: F401
 # the routed linears on bf16 operands (Paella.set_training_gemm("bf16")): the op, its shape rule, its counters, and the pack alone
 from .train_ops import LINEAR_COUNTERS, LINEAR_GRAIN, LINEAR_MAX_DIM, linear_bf16, linear_shapes_ok, pack_bf16  # noqa: F401
+# the dropout seeds of a forward as device words (`forward_loss(..., seeds=)`, `GraphTrainStep`)
+from .train_ops import SEEDS_MAX_SITES, TrainSeeds  # noqa: F401
 
 # which stretches of a block run as one HIP op: act = the middle of the MLP (Paella.set_training_activation), dw = the front of a ResBlock
 # (Paella.set_training_depthwise), attn = the attention core of an AttnBlock (Paella.set_training_attention).  `_forward_features` decides it once per forward
@@ -52,12 +54,17 @@ def _ln_nchw(x, eps=1e-6):
     return F.layer_norm(x.permute(0, 2, 3, 1), (x.size(1),), None, None, eps).permute(0, 3, 1, 2)
 
 
-def _channelwise(blk, x_nhwc, p_drop, training, route=_TORCH, gemm=False):
+def _site(seeds, p_drop):
+    """the `seed=` of one HIP dropout op call: the next word of the table where the call draws a mask (p > 0), else None -- the op's own default"""
+    return seeds.site() if seeds is not None and p_drop > 0.0 else None
+
+
+def _channelwise(blk, x_nhwc, p_drop, training, route=_TORCH, gemm=False, seeds=None):
     """Linear -> GELU -> GlobalResponseNorm -> Dropout -> Linear (src/modules.py:49-53 / 30-40).  route.act (Paella.set_training_activation("hip"), train mode on a cuda
     device): the three middle stages run as one HIP op in both directions (`gelu_grn_dropout`)."""
     cw = blk.channelwise._modules
     if route.act:
-        h = gelu_grn_dropout(_linear(x_nhwc, cw["0"].weight, cw["0"].bias, gemm), cw["2"].gamma, cw["2"].beta, p_drop)
+        h = gelu_grn_dropout(_linear(x_nhwc, cw["0"].weight, cw["0"].bias, gemm), cw["2"].gamma, cw["2"].beta, p_drop, _site(seeds, p_drop))
         return _linear(h, cw["4"].weight, cw["4"].bias, gemm)
     h = F.gelu(_linear(x_nhwc, cw["0"].weight, cw["0"].bias, gemm))
     gx = torch.norm(h, p=2, dim=(1, 2), keepdim=True)
@@ -67,7 +74,7 @@ def _channelwise(blk, x_nhwc, p_drop, training, route=_TORCH, gemm=False):
     return _linear(h, cw["4"].weight, cw["4"].bias, gemm)
 
 
-def _res_block(blk, x, skip, p_drop, training, route=_TORCH, defer=False, gemm=False):
+def _res_block(blk, x, skip, p_drop, training, route=_TORCH, defer=False, gemm=False, seeds=None):
     """ResBlock (src/modules.py:43-62): depthwise 3x3 (groups = c, over cat([x, skip]) when a skip arrives) -> LN -> MLP -> + x.  route.dw
     (Paella.set_training_depthwise("hip"), train mode on a cuda device): everything in front of the MLP runs as one HIP op in both directions
     (`dwconv_layernorm`), x and skip handed over separately -- no torch.cat.  defer: the two summands (MLP output, x) come back unadded."""
@@ -80,15 +87,15 @@ def _res_block(blk, x, skip, p_drop, training, route=_TORCH, defer=False, gemm=F
         dw = blk.depthwise
         c = dw.weight.size(0)
         y = _ln_nchw(F.conv2d(x, dw.weight, dw.bias, padding=dw.weight.size(-1) // 2, groups=c)).permute(0, 2, 3, 1)
-    out = _channelwise(blk, y, p_drop, training, route, gemm).permute(0, 3, 1, 2)
+    out = _channelwise(blk, y, p_drop, training, route, gemm, seeds).permute(0, 3, 1, 2)
     return (out, res) if defer else out + res
 
 
-def _ff_block(blk, x, p_drop, training, route=_TORCH, z=None, defer=False, gemm=False):
+def _ff_block(blk, x, p_drop, training, route=_TORCH, z=None, defer=False, gemm=False, seeds=None):
     """FeedForwardBlock (src/modules.py:82-96).  z [B, H W, C]: the LayerNorm rows of x, already made by `timestep_modulate`; defer: the two summands
     (MLP output, x) come back unadded."""
     rows = _ln_nchw(x).permute(0, 2, 3, 1) if z is None else z.view(x.size(0), x.size(2), x.size(3), x.size(1))
-    out = _channelwise(blk, rows, p_drop, training, route, gemm).permute(0, 3, 1, 2)
+    out = _channelwise(blk, rows, p_drop, training, route, gemm, seeds).permute(0, 3, 1, 2)
     return (out, x) if defer else x + out
 
 
@@ -98,7 +105,7 @@ def _timestep_block(blk, x, r_embed):
     return x * (1 + a) + b
 
 
-def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, training, attn_weights=None, route=_TORCH, z=None, gemm=False):
+def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, training, attn_weights=None, route=_TORCH, z=None, gemm=False, seeds=None):
     """AttnBlock (src/modules.py:65-79) around nn.MultiheadAttention semantics (Attention2D :7-19): queries = LN(x) positions,
     keys = values = [LN(x) positions | kv_mapper(SiLU(c_embed))], residual on the un-normed x.  route.attn (Paella.set_training_attention("hip"), train mode
     on a cuda device): between the in-projection (one F.linear for the queries, one for keys and values together) and the out-projection the block runs as one HIP
@@ -114,7 +121,7 @@ def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, training, attn_weight
     at = blk.attention.attn
     if attn_weights is None and route.attn:
         w, bias = at.in_proj_weight, at.in_proj_bias
-        out = attention_dropout(_linear(q, w[:C], bias[:C], gemm), _linear(kv, w[C:], bias[C:], gemm), nhead, p_drop)
+        out = attention_dropout(_linear(q, w[:C], bias[:C], gemm), _linear(kv, w[C:], bias[C:], gemm), nhead, p_drop, _site(seeds, p_drop))
         out = _linear(out, at.out_proj.weight, at.out_proj.bias, gemm)
     elif attn_weights is None:
         # torch's own functional form of nn.MultiheadAttention.forward (batch_first handled by the transposes): identical
@@ -143,7 +150,7 @@ def _timestep_freqs(half, max_positions, device):
     """The frequency table of gen_r_embedding, made on the HOST as the engine's is (Paella._engine: paella_unet_set_timestep_freqs) and kept per device.  The
     device's exp differs from the host's by one ulp in some entries (c_r = 64: entries near 1), and with angles of up to 1e4 a one-ulp frequency moves sine and
     cosine by up to 5e-4: made on the device, the table gave train mode another timestep embedding than eval mode evaluates for the same r.  The first call per
-    (c_r, device) copies the table from the host inside the forward: a stream capture of a training step (nothing captures one today) must follow an eager step."""
+    (c_r, device) copies the table from the host inside the forward: a stream capture of a training step must follow an eager step (`GraphTrainStep` warms up first)."""
     return torch.arange(half).float().mul(-math.log(max_positions) / (half - 1)).exp().to(device)
 
 
@@ -169,9 +176,32 @@ def c_embeddings(model, byt5, clip, clip_image):
     return F.layer_norm(seq, (c_cond,), None, None, 1e-6)
 
 
-def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None, attn_weights=None):
+# torch's embedding backward has two forms: up to this many tokens one kernel, above it a sort of the tokens followed by a segmented sum (aten's embedding backward
+# kernels: `num_indices <= 3072`)
+EMBEDDING_CHUNK = 3072
+
+
+def _token_embedding(x, weight, chunked):
+    """F.embedding(x, weight).  chunked (a forward under a seed table -- the form a stream capture takes): in pieces of at most EMBEDDING_CHUNK tokens, so that every
+    piece's backward is the one-kernel form.  OBSERVED: with the sorting form captured at 16 x 32x32 tokens, a later replay ended in a GPU memory fault inside
+    rocprim's partition_kernel (the unique-by-key step of that form); graphs that hold the one-kernel form replay without one, at 512, 3200, 16384 and 65536 tokens.
+    The cause is NOT established: by the kernels it launches here the sorting form keeps its segment count behind a device pointer and should be capturable, so what is wrong with it in a captured
+    graph -- in torch, in the sort / partition library or in the graph runtime -- is an open question, and the pieces are a way round it, not a fix.  The weight's
+    gradient is then the sum of the pieces' gradients: the values of the one-piece call in another summation order.  Up to EMBEDDING_CHUNK tokens the call is
+    F.embedding itself."""
+    if not chunked or x.numel() <= EMBEDDING_CHUNK:
+        return F.embedding(x, weight)
+    pieces = [F.embedding(piece, weight) for piece in x.reshape(-1).split(EMBEDDING_CHUNK)]
+    return torch.cat(pieces, dim=0).view(*x.shape, weight.size(1))
+
+
+def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None, attn_weights=None, seeds=None):
     """Paella.forward (src/modules.py:263-275) as autograd-tracked torch ops, up to and including the LayerNorm2d in front of out_mapper's convolution:
-    [B, c_out, H, W] as the permuted view of an NHWC tensor that `_ln_nchw` returns."""
+    [B, c_out, H, W] as the permuted view of an NHWC tensor that `_ln_nchw` returns.  seeds (a `TrainSeeds`): every HIP dropout op call with p > 0 takes the
+    table's next word as its seed, in forward order (`dropout_sites` counts them); a call at p = 0 and the torch routes consume none.  Under seeds the token
+    embedding of more than EMBEDDING_CHUNK tokens is looked up in pieces (`_token_embedding`): the one difference from the forward without seeds."""
+    if seeds is not None:
+        seeds.begin()
     cfg = model._cfg
     training = model.training
     p_drop = float(model.dropout) if not isinstance(model.dropout, (list, tuple)) else None
@@ -185,7 +215,7 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
     patch = cfg["patch_size"]
     n_levels = len(cfg["c_hidden"])
 
-    h = F.layer_norm(F.embedding(x, model.in_mapper._modules["0"].weight), (cfg["c_in"],), None, None, 1e-6).permute(0, 3, 1, 2)
+    h = F.layer_norm(_token_embedding(x, model.in_mapper._modules["0"].weight, seeds is not None), (cfg["c_in"],), None, None, 1e-6).permute(0, 3, 1, 2)
     emb = model.embedding._modules["1"]
     h = _ln_nchw(F.conv2d(F.pixel_unshuffle(h, patch), emb.weight, emb.bias))
 
@@ -202,13 +232,13 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
 
     def run(blk, level, h, skip=None, z=None, defer=False):
         if blk.kind == 'C':
-            return _res_block(blk, h, skip, drop(level), training, route, defer, gemm)
+            return _res_block(blk, h, skip, drop(level), training, route, defer, gemm, seeds)
         if blk.kind == 'A':
-            return _attn_block(blk, h, c_embed, cfg["nhead"][level], cfg["self_attn"], drop(level), training, attn_weights, route, z, gemm)
+            return _attn_block(blk, h, c_embed, cfg["nhead"][level], cfg["self_attn"], drop(level), training, attn_weights, route, z, gemm, seeds)
         if blk.kind == 'T':
             return _timestep_block(blk, h, r_embed)
         if blk.kind == 'F':
-            return _ff_block(blk, h, drop(level), training, route, z, defer, gemm)
+            return _ff_block(blk, h, drop(level), training, route, z, defer, gemm, seeds)
         if blk.kind == 'D':  # LayerNorm2d + Conv2d(k2, s2)   (src/modules.py:153-156)
             cv = blk._modules["1"]
             return F.conv2d(_ln_nchw(h), cv.weight, cv.bias, stride=2)
@@ -255,10 +285,204 @@ def forward_autograd(model, x, r, byt5, clip=None, clip_image=None, x_cat=None, 
     return F.conv2d(_forward_features(model, x, r, byt5, clip, clip_image, x_cat, attn_weights), model.out_mapper._modules["1"].weight)
 
 
-def forward_loss(model, x, r, target, byt5, clip=None, clip_image=None, x_cat=None, attn_weights=None, label_smoothing=0.1):
-    """One training forward with the loss head fused: (loss [B, H, W], correct [B, H, W] bool) instead of logits [B, num_labels, H, W]."""
+def forward_loss(model, x, r, target, byt5, clip=None, clip_image=None, x_cat=None, attn_weights=None, label_smoothing=0.1, seeds=None):
+    """One training forward with the loss head fused: (loss [B, H, W], correct [B, H, W] bool) instead of logits [B, num_labels, H, W].  seeds: a `TrainSeeds` whose
+    words the HIP dropout ops take as their seeds (None: every op draws its own, as always)."""
     w = model.out_mapper._modules["1"].weight
     refuse_head_widths(w.size(1), w.size(0))      # before the network runs: a refused call has drawn no seed and launched nothing
-    feat = _forward_features(model, x, r, byt5, clip, clip_image, x_cat, attn_weights)
+    if seeds is not None and not isinstance(seeds, TrainSeeds):
+        raise ValueError("seeds must be a paella_amd.training.TrainSeeds (got %s)" % type(seeds).__name__)
+    feat = _forward_features(model, x, r, byt5, clip, clip_image, x_cat, attn_weights, seeds)
     loss, argmax = head_cross_entropy(feat.permute(0, 2, 3, 1), model.out_mapper._modules["1"].weight, target, label_smoothing)
     return loss, argmax == target
+
+
+def dropout_sites(model):
+    """How many words of a `TrainSeeds` one train-mode forward of `model` on a cuda device consumes under its PRESENT switches and `model.dropout`: one per
+    `gelu_grn_dropout` call (every C / F block, with set_training_activation("hip")) and one per `attention_dropout` call (every A block, with
+    set_training_attention("hip")) whose level has p > 0.  The torch routes draw through torch's generator and count nothing."""
+    act = getattr(model, "_train_activation", "torch") == "hip"
+    attn = getattr(model, "_train_attention", "torch") == "hip"
+    n_levels = len(model._cfg["c_hidden"])
+    p_of = (lambda lvl: float(model.dropout[lvl])) if isinstance(model.dropout, (list, tuple)) else (lambda lvl: float(model.dropout))
+    levels = [(i, lv) for i, lv in enumerate(model.down_blocks)] + [(n_levels - 1 - u, lv) for u, lv in enumerate(model.up_blocks)]
+    return sum(1 for i, lv in levels for blk in lv if p_of(i) > 0.0 and ((blk.kind in ('C', 'F') and act) or (blk.kind == 'A' and attn)))
+
+
+_STEP_INPUTS = ("noised", "t", "latents", "byt5", "clip", "clip_image", "x_cat", "loss_weight")
+_TRAIN_SWITCHES = (("training activation", "_train_activation", "torch"), ("training depthwise", "_train_depthwise", "torch"),
+                   ("training attention", "_train_attention", "torch"), ("training modulation", "_train_modulation", "torch"), ("training gemm", "_train_gemm", "fp32"))
+
+
+class GraphTrainStep:
+    """One whole training iteration of src/train.py:59-69 -- `forward_loss`, the loss reduction, `backward()`, clip_grad_norm_ + AdamW (`ClippedAdamW`) -- captured
+    ONCE into a HIP graph for fixed shapes and replayed per call: the same kernels as the eager iteration plus one launch that advances the dropout seeds, submitted
+    as one graph instead of some two thousand launches.
+
+        step = GraphTrainStep(model, opt, dict(noised=, t=, latents=, byt5=[, clip=, clip_image=, x_cat=, loss_weight=]))
+        loss, accuracy, grad_norm = step(noised=..., t=..., latents=..., byt5=..., ...)        # 0-dim device tensors owned by the graph, valid until the next call
+
+    Loss: with `loss_weight` ((loss * lw).sum([1, 2]) / lw.sum([1, 2])).mean() (src_distributed/train.py:107), without it loss.mean() (src/train.py); accuracy is
+    (argmax == latents).float().mean().  The model must be in train mode on a cuda device and the optimizer a `ClippedAdamW` over its parameters: anything else raises.
+    What changes from replay to replay although the graph is fixed:
+      * the inputs -- copied into the graph's static buffers (a shape or dtype that differs from the example's raises ValueError; an input left out keeps its buffer);
+      * the dropout masks -- `.seeds` (a `TrainSeeds` sized by `dropout_sites`) is advanced INSIDE the graph, so replay k draws the words of iteration k;
+        `seed=` is its base (None: one draw from torch's CPU generator, so torch.manual_seed reproduces a run); `.seeds` stays ONE object for the life of the step --
+        a recapture that needs more sites grows it in place (`TrainSeeds.grow`);
+      * the hyperparameters -- the optimizer's table is rebuilt from `param_groups` and uploaded eagerly on the current stream before every replay (only the three
+        launches of the step sit in the graph), so a scheduler's `lr` acts as in the eager loop.
+    A call does not synchronise with the device.  Every updated parameter's version is raised, so the HIP engine and captured sampling graphs notice the new weights.
+    Construction: optimizer state is materialised, ONE warm-up forward + backward runs on a side stream without an optimizer step (timestep-frequency table, allocator
+    pools, library selections), the gradients are set to None and the iteration is captured (capture_error_mode="thread_local", one stream: the graph has no parallel
+    branches); the seed table is put back to its state from before the warm-up after both.  Weights, optimizer state and step counts are untouched, and the first
+    replay draws the words of iteration 1.  After the capture p.grad of every parameter is a tensor owned by the graph that each replay rewrites: there is no
+    zero_grad in the loop (a p.grad that was replaced or set to None is put back before the next replay).
+    Staleness, as `GraphSampler`: before a replay the data_ptr of every parameter and optimizer state tensor, the five training switches, `model.dropout`
+    and train mode are compared with what the capture saw; on a difference the step is captured again (on_stale="recapture"; `.captures` counts) or a RuntimeError
+    names the cause (on_stale="raise").  The call counters of the ops (ATTN_COUNTERS, MOD_COUNTERS, LINEAR_COUNTERS, ...) and ADAMW_COUNTERS count Python calls: they
+    move at capture time only, never at a replay.
+    Not offered: gradient accumulation inside the graph, DDP, GradScaler / autocast, the `attn_weights` branch."""
+
+    def __init__(self, model, optimizer, example_inputs, *, label_smoothing=0.1, seed=None, on_stale="recapture"):
+        if on_stale not in ("recapture", "raise"):
+            raise ValueError("on_stale must be 'recapture' or 'raise'")
+        if not isinstance(optimizer, ClippedAdamW):
+            raise TypeError("GraphTrainStep captures the HIP optimizer step: the optimizer must be a paella_amd.training.ClippedAdamW (got %s)" % type(optimizer).__name__)
+        params = [p for p in model.parameters()]
+        if not params or not all(p.is_cuda for p in params):
+            raise ValueError("GraphTrainStep runs on the HIP device only: move the model to a cuda device first")
+        self.model, self.optimizer, self.on_stale, self.label_smoothing = model, optimizer, on_stale, float(label_smoothing)
+        self.device = params[0].device
+        self._refuse_eval()
+        unknown = sorted(set(example_inputs) - set(_STEP_INPUTS))
+        if unknown:
+            raise ValueError("example_inputs takes %s (got also %s)" % (", ".join(_STEP_INPUTS), ", ".join(unknown)))
+        for k in ("noised", "t", "latents", "byt5"):
+            if example_inputs.get(k) is None:
+                raise ValueError("example_inputs needs %s" % k)
+        clone = lambda v: [t.detach().to(self.device).clone() for t in v] if isinstance(v, (list, tuple)) else v.detach().to(self.device).clone()
+        self.inputs = {k: clone(v) for k, v in example_inputs.items() if v is not None}
+        self.seeds = TrainSeeds(max(dropout_sites(model), 1), seed, self.device)
+        self.captures = 0
+        self.graph = self.out = None
+        self._capture()
+
+    def _refuse_eval(self):
+        if not self.model.training:
+            raise RuntimeError("GraphTrainStep captures the training path and this module is in eval mode: call model.train() first")
+
+    # ---- what a capture depends on besides the shapes
+    def _state(self):
+        m, opt = self.model, self.optimizer
+        ps = list(m.parameters())
+        state = []
+        for p in ps:
+            st = opt.state.get(p) or {}
+            state.append(tuple(None if st.get(k) is None else st[k].data_ptr() for k in ("step", "exp_avg", "exp_avg_sq")))
+        return [("parameter storage", tuple(p.data_ptr() for p in ps)), ("parameters that require a gradient", tuple(p.requires_grad for p in ps)),
+                ("optimizer state storage", (tuple(state), None if opt._rows_dev is None else opt._rows_dev.data_ptr(), None if opt._ws is None else opt._ws.data_ptr(),
+                                             tuple(id(p) for p in opt._params()), opt.max_norm))] + \
+               [(name, getattr(m, attr, default)) for name, attr, default in _TRAIN_SWITCHES] + \
+               [("model.dropout", tuple(m.dropout) if isinstance(m.dropout, (list, tuple)) else float(m.dropout)), ("train mode", bool(m.training))]
+
+    def _iteration(self, optimize):
+        """seeds.advance -> forward_loss -> reduction -> backward [-> the optimizer's launch part]; -> (loss, accuracy, norm or None)"""
+        i = self.inputs
+        self.seeds.advance()
+        per_pos, correct = forward_loss(self.model, i["noised"], i["t"], i["latents"], i["byt5"], i.get("clip"), i.get("clip_image"), i.get("x_cat"), None,
+                                        self.label_smoothing, self.seeds)
+        lw = i.get("loss_weight")
+        loss = per_pos.mean() if lw is None else ((per_pos * lw).sum(dim=[1, 2]) / lw.sum(dim=[1, 2])).mean()
+        loss.backward()
+        acc = correct.float().mean()
+        norm = None
+        if optimize:
+            with torch.no_grad():
+                # the plan reads the addresses of the gradients this capture's backward made, so it runs here; it is host code and enqueues nothing, because the state,
+                # the table and the workspace exist (materialize_state) and the gradients are dense fp32 -- `_capture` refuses a plan that had to make a temporary
+                self._plan = self.optimizer._plan()
+                norm = self.optimizer._launch(self._plan)
+        return loss.detach(), acc, norm
+
+    def _capture(self):
+        self._refuse_eval()
+        dev, opt, m = self.device, self.optimizer, self.model
+        if self.seeds.n_sites < dropout_sites(m):           # a switch or model.dropout added drawing calls since the table was sized: `.seeds` grows in place
+            self.seeds.grow(dropout_sites(m))
+        self.graph = self.out = self._plan = None
+        self._grads = []
+        opt.materialize_state()
+        snap = self.seeds.snapshot()
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):
+            self._iteration(optimize=False)               # warm-up: no optimizer step, nothing but gradients is written
+        torch.cuda.current_stream(dev).wait_stream(side)
+        self.seeds.restore(snap)
+        m.zero_grad(set_to_none=True)
+        torch.cuda.synchronize(dev)
+        state = self._state()
+        graph = torch.cuda.CUDAGraph()
+        # thread_local: a process-group watchdog thread polling events must not invalidate the capture
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            out = self._iteration(optimize=True)
+        self.seeds.restore(snap)
+        torch.cuda.synchronize(dev)
+        if self._plan["keep"] and any(g is not p.grad for g, p in zip(self._plan["keep"], self._plan["updated"])):
+            raise RuntimeError("GraphTrainStep: a gradient is not dense fp32 on the parameters' device; the captured optimizer step would read a temporary")
+        self._grads = [(p, p.grad) for p in self._plan["updated"]]
+        self.graph, self.out, self._captured_state = graph, out, state
+        self.captures += 1
+
+    def _stale(self):
+        """what the capture depends on and has changed since, by name (empty: the capture is fresh)"""
+        return [a[0] for a, b in zip(self._state(), self._captured_state) if a != b]
+
+    def _check_fresh(self):
+        causes = self._stale()
+        if not causes:
+            return
+        if self.on_stale == "raise":
+            raise RuntimeError("GraphTrainStep: the captured iteration is stale -- changed since the capture: %s.  Build a new GraphTrainStep or construct it with "
+                               "on_stale='recapture'." % ", ".join(causes))
+        self._capture()
+
+    def _copy_inputs(self, given):
+        unknown = sorted(set(given) - set(_STEP_INPUTS))
+        if unknown:
+            raise ValueError("GraphTrainStep takes %s (got also %s)" % (", ".join(_STEP_INPUTS), ", ".join(unknown)))
+        todo = []
+        for k, src in given.items():
+            if src is None:
+                continue
+            dst = self.inputs.get(k)
+            if dst is None:
+                raise ValueError("the iteration was captured without %s" % k)
+            pairs = list(zip(dst, src)) if isinstance(dst, list) and isinstance(src, (list, tuple)) and len(src) == len(dst) else None if isinstance(dst, list) or \
+                isinstance(src, (list, tuple)) else [(dst, src)]
+            if pairs is None:
+                raise ValueError("%s: the captured iteration takes %s" % (k, "a list of %d tensors" % len(dst) if isinstance(dst, list) else "one tensor"))
+            for d, s in pairs:
+                if not torch.is_tensor(s) or tuple(s.shape) != tuple(d.shape) or s.dtype != d.dtype:
+                    raise ValueError("%s: the captured iteration takes %s %s (got %s)" % (k, d.dtype, tuple(d.shape), "%s %s" % (s.dtype, tuple(s.shape))
+                                                                                             if torch.is_tensor(s) else type(s).__name__))
+                todo.append((d, s))
+        for d, s in todo:       # only after every input was accepted
+            d.copy_(s, non_blocking=True)
+
+    def __call__(self, inputs=None, **more):
+        given = dict(inputs or {}, **more)
+        self._check_fresh()
+        self._copy_inputs(given)
+        opt = self.optimizer
+        for p, g in self._grads:                         # (a loop that still calls zero_grad(set_to_none=True): the graph writes these tensors, so they are what p.grad is)
+            if p.grad is not g:
+                p.grad = g
+        with torch.no_grad():
+            opt._plan_hyper(self._plan["rows"])          # lr, betas, eps, weight_decay as param_groups hold them NOW
+            opt._upload(self._plan)                      # eager, on the stream the replay follows on
+        self.graph.replay()
+        opt.grad_norm = self.out[2]
+        if self._plan["updated"]:
+            torch.autograd.graph.increment_version(self._plan["updated"])
+        return self.out
