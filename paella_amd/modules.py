@@ -20,6 +20,9 @@ from torch import nn
 from torch.nn.modules import module as _nn_module
 
 from . import _lib
+from .training import TRAIN_SWITCHES
+
+_TRAIN_SWITCH = {sw.name: sw for sw in TRAIN_SWITCHES}
 
 
 # Every registration of a Parameter, buffer or child module on ANY nn.Module of the process counts here (torch's process-wide registration hooks: they fire for
@@ -342,11 +345,8 @@ class Paella(_NativeModel, nn.Module):
         self._load_gen = 0
         self._ws = None
         self._precision = 0
-        self._train_activation = "torch"
-        self._train_depthwise = "torch"
-        self._train_attention = "torch"
-        self._train_modulation = "torch"
-        self._train_gemm = "fp32"
+        for sw in TRAIN_SWITCHES:
+            setattr(self, sw.attr, sw.off)
         # Constructed in EVAL mode (an nn.Module normally starts in train mode): eval = the hand-written HIP engine, which is what
         # sampling needs; `model.train()` -- the switch the reference's training loops flip (src/train.py:47,
         # src_distributed/train.py:73,140,172) -- selects the differentiable torch-op evaluation of paella_amd/training.py.
@@ -467,16 +467,39 @@ class Paella(_NativeModel, nn.Module):
     def get_gemm_precision(self):
         return "bf16" if self._precision == 1 else "fp32"
 
+    def _set_training(self, name, mode, store=True):
+        """validate `mode` against the switch's row of `paella_amd.training.TRAIN_SWITCHES` and (store) keep it"""
+        sw = _TRAIN_SWITCH[name]
+        if mode not in (sw.off, sw.on):
+            raise ValueError(sw.refusal)
+        if sw.name == "depthwise" and mode == sw.on and int(self._cfg["kernel_size"]) != 3:
+            raise ValueError("training depthwise 'hip' takes kernel_size 3 only (this module has %d)" % int(self._cfg["kernel_size"]))
+        if store:
+            setattr(self, sw.attr, mode)
+        return self
+
+    def set_training_route(self, **settings):
+        """Several training switches in one call: any of activation=, depthwise=, attention=, modulation= ("torch" / "hip") and gemm= ("fp32" / "bf16"), each as its
+        `set_training_*` method takes it.  Every given setting is validated before any is stored: a refused call changes nothing."""
+        unknown = sorted(set(settings) - set(_TRAIN_SWITCH))
+        if unknown:
+            raise TypeError("set_training_route takes %s (got also %s)" % (", ".join(_TRAIN_SWITCH), ", ".join(unknown)))
+        for store in (False, True):
+            for name, mode in settings.items():
+                self._set_training(name, mode, store)
+        return self
+
+    def training_route(self):
+        """the present training switches, as the keywords of `set_training_route`"""
+        return {sw.name: sw.read(self) for sw in TRAIN_SWITCHES}
+
     def set_training_activation(self, mode):
         """How the TRAIN-mode forward (`forward` and `forward_loss` after `model.train()`) runs the GELU -> GlobalResponseNorm -> Dropout stretch of every
         ResBlock / FeedForwardBlock MLP: "torch" (default) is the chain of torch ops, op for op as before; "hip" runs it as one HIP op in both directions
         (`paella_amd.training.gelu_grn_dropout`) when the module is on a cuda device -- autograd then keeps the MLP's pre-activation and one [B, 4c] table
         instead of four or five [B, H, W, 4c] tensors, and the dropout masks come from one 64-bit seed per MLP drawn from torch's default CPU generator
         (`torch.manual_seed` reproduces a run; the masks are not the torch chain's).  Eval mode -- the HIP inference engine -- never sees the switch."""
-        if mode not in ("torch", "hip"):
-            raise ValueError("training activation must be 'torch' or 'hip'")
-        self._train_activation = mode
-        return self
+        return self._set_training("activation", mode)
 
     def set_training_depthwise(self, mode):
         """How the TRAIN-mode forward (`forward` and `forward_loss` after `model.train()`) runs the front of every ResBlock -- the concatenation with the skip,
@@ -485,12 +508,7 @@ class Paella(_NativeModel, nn.Module):
         is kept in channels_last memory, and besides the block's input and the MLP's input autograd keeps one float per position.  Independent of
         `set_training_activation`.  The op is 3 x 3 only: "hip" on a module built with another kernel_size raises ValueError.  Eval mode -- the HIP inference
         engine -- never sees the switch."""
-        if mode not in ("torch", "hip"):
-            raise ValueError("training depthwise must be 'torch' or 'hip'")
-        if mode == "hip" and int(self._cfg["kernel_size"]) != 3:
-            raise ValueError("training depthwise 'hip' takes kernel_size 3 only (this module has %d)" % int(self._cfg["kernel_size"]))
-        self._train_depthwise = mode
-        return self
+        return self._set_training("depthwise", mode)
 
     def set_training_attention(self, mode):
         """How the TRAIN-mode forward (`forward` and `forward_loss` after `model.train()`) runs the attention core of every AttnBlock -- scores, softmax, dropout
@@ -500,10 +518,7 @@ class Paella(_NativeModel, nn.Module):
         per block drawn from torch's default CPU generator (`torch.manual_seed` reproduces a run; the masks are not the torch chain's).  Independent of
         `set_training_activation` and `set_training_depthwise`.  A train-mode call with `attn_weights` runs the torch ops under either setting: the key-weight
         table stays an inference feature.  Eval mode -- the HIP inference engine -- never sees the switch."""
-        if mode not in ("torch", "hip"):
-            raise ValueError("training attention must be 'torch' or 'hip'")
-        self._train_attention = mode
-        return self
+        return self._set_training("attention", mode)
 
     def set_training_modulation(self, mode):
         """How the TRAIN-mode forward (`forward` and `forward_loss` after `model.train()`) runs the joint around every TimestepBlock -- the residual add that ends
@@ -513,10 +528,7 @@ class Paella(_NativeModel, nn.Module):
         in and its gradient comes back whole, and besides the op's inputs and the LayerNorm rows autograd keeps one float per position.  The op draws nothing.
         Independent of `set_training_activation`, `set_training_depthwise` and `set_training_attention`.  The LayerNorm of the down- and up-sampling blocks and
         of the classifier stays where it is.  Eval mode -- the HIP inference engine -- never sees the switch."""
-        if mode not in ("torch", "hip"):
-            raise ValueError("training modulation must be 'torch' or 'hip'")
-        self._train_modulation = mode
-        return self
+        return self._set_training("modulation", mode)
 
     def set_training_gemm(self, mode):
         """On which operands the TRAIN-mode forward (`forward` and `forward_loss` after `model.train()`) and its backward run the routed linears -- the two of every
@@ -528,10 +540,7 @@ class Paella(_NativeModel, nn.Module):
         counted in `paella_amd.training.LINEAR_COUNTERS["fallbacks"]`.  The torch attention branch, the `attn_weights` branch, the timestep and conditioning mappers,
         the down- / up-sampling convolutions, the embedding, the classifier and the loss head stay where they are.  Independent of the four switches above and of
         `set_gemm_precision`.  Eval mode -- the HIP inference engine -- never sees the switch."""
-        if mode not in ("fp32", "bf16"):
-            raise ValueError("training gemm must be 'fp32' or 'bf16'")
-        self._train_gemm = mode
-        return self
+        return self._set_training("gemm", mode)
 
     def __del__(self):
         h = getattr(self, "_handle", None)

@@ -29,14 +29,54 @@ from .train_ops import LINEAR_COUNTERS, LINEAR_GRAIN, LINEAR_MAX_DIM, linear_bf1
 # the dropout seeds of a forward as device words (`forward_loss(..., seeds=)`, `GraphTrainStep`)
 from .train_ops import SEEDS_MAX_SITES, TrainSeeds  # noqa: F401
 
-# which stretches of a block run as one HIP op: act = the middle of the MLP (Paella.set_training_activation), dw = the front of a ResBlock
-# (Paella.set_training_depthwise), attn = the attention core of an AttnBlock (Paella.set_training_attention).  `_forward_features` decides it once per forward
-_Route = namedtuple("_Route", "act dw attn")
-_TORCH = _Route(False, False, False)
-# Beside the route, not in it: Paella.set_training_modulation("hip") makes the JOINT between blocks one HIP op (`timestep_modulate`).  `_forward_features` then asks
-# a ResBlock / FeedForwardBlock in front of a TimestepBlock to hand its two summands over unadded (defer), and hands the op's LayerNorm rows (z) to the AttnBlock /
-# FeedForwardBlock behind it.  Beside the route as well: Paella.set_training_gemm("bf16") sends the routed linears -- the two of every MLP and, on the route.attn
-# branch, the three projections of an AttnBlock -- through `_linear` below (`gemm` in the signatures)
+# The training switches of `Paella`, one row each: the field of the per-forward plan, the name everything else derives from, and its two settings (off is the
+# default).  A new switch is a row here plus its branch in one block function below.  act = the middle of the MLP as one HIP op (`gelu_grn_dropout`), dw = the front
+# of a ResBlock (`dwconv_layernorm`), attn = the attention core of an AttnBlock (`attention_dropout`), mod = the JOINT between blocks (`timestep_modulate`: a
+# ResBlock / FeedForwardBlock in front of a TimestepBlock hands its two summands over unadded -- defer -- and the op's LayerNorm rows -- z -- go to the AttnBlock /
+# FeedForwardBlock behind it), gemm = the routed linears -- the two of every MLP and, on the attn branch, the three projections of an AttnBlock -- through `_linear`
+class Switch(namedtuple("Switch", "field name off on")):
+    __slots__ = ()
+    attr = property(lambda self: "_train_" + self.name)             # the module attribute (pickled state)
+    setter = property(lambda self: "set_training_" + self.name)     # the public method of `Paella`
+    label = property(lambda self: "training " + self.name)          # what `GraphTrainStep` calls it when it went stale
+    refusal = property(lambda self: "training %s must be '%s' or '%s'" % (self.name, self.off, self.on))
+
+    def read(self, model):
+        """the present setting; a module unpickled from before the switch existed has its default"""
+        return getattr(model, self.attr, self.off)
+
+
+TRAIN_SWITCHES = (Switch("act", "activation", "torch", "hip"), Switch("dw", "depthwise", "torch", "hip"), Switch("attn", "attention", "torch", "hip"),
+                  Switch("mod", "modulation", "torch", "hip"), Switch("gemm", "gemm", "fp32", "bf16"))
+# what `_forward_features` decides once per forward and hands down: per switch whether it ACTS, then train mode and the seed table
+_Plan = namedtuple("_Plan", tuple(s.field for s in TRAIN_SWITCHES) + ("training", "seeds"))
+
+
+def _plan(model, on, seeds=None):
+    """on: whether the switches can act at all -- train mode on a cuda device; a switch at its default leaves every call as it is"""
+    return _Plan(*(on and s.read(model) == s.on for s in TRAIN_SWITCHES), training=model.training, seeds=seeds)
+
+
+def _levels(model):
+    """(level index, blocks, whether the level takes its encoder output as a skip) in forward order: _down_encode, then _up_decode (src/modules.py:234-261)"""
+    n_levels = len(model._cfg["c_hidden"])
+    for i, blocks in enumerate(model.down_blocks):
+        yield i, blocks, False
+    for u, blocks in enumerate(model.up_blocks):
+        yield n_levels - 1 - u, blocks, u > 0
+
+
+def _level_dropout(model):
+    """level index -> p of `model.dropout`, a scalar or one per level"""
+    if isinstance(model.dropout, (list, tuple)):
+        return lambda lvl: float(model.dropout[lvl])
+    p_drop = float(model.dropout)
+    return lambda lvl: p_drop
+
+
+def _draws(plan, kind, p_drop):
+    """whether a block of this kind draws a dropout mask in a HIP op, i.e. consumes a seed word: C / F under act, A under attn, where p > 0"""
+    return p_drop > 0.0 and (plan.act if kind in ('C', 'F') else plan.attn if kind == 'A' else False)
 
 
 def _linear(x, weight, bias, gemm=False):
@@ -54,32 +94,32 @@ def _ln_nchw(x, eps=1e-6):
     return F.layer_norm(x.permute(0, 2, 3, 1), (x.size(1),), None, None, eps).permute(0, 3, 1, 2)
 
 
-def _site(seeds, p_drop):
+def _site(plan, kind, p_drop):
     """the `seed=` of one HIP dropout op call: the next word of the table where the call draws a mask (p > 0), else None -- the op's own default"""
-    return seeds.site() if seeds is not None and p_drop > 0.0 else None
+    return plan.seeds.site() if plan.seeds is not None and _draws(plan, kind, p_drop) else None
 
 
-def _channelwise(blk, x_nhwc, p_drop, training, route=_TORCH, gemm=False, seeds=None):
-    """Linear -> GELU -> GlobalResponseNorm -> Dropout -> Linear (src/modules.py:49-53 / 30-40).  route.act (Paella.set_training_activation("hip"), train mode on a cuda
+def _channelwise(blk, x_nhwc, p_drop, plan):
+    """Linear -> GELU -> GlobalResponseNorm -> Dropout -> Linear (src/modules.py:49-53 / 30-40).  plan.act (Paella.set_training_activation("hip"), train mode on a cuda
     device): the three middle stages run as one HIP op in both directions (`gelu_grn_dropout`)."""
     cw = blk.channelwise._modules
-    if route.act:
-        h = gelu_grn_dropout(_linear(x_nhwc, cw["0"].weight, cw["0"].bias, gemm), cw["2"].gamma, cw["2"].beta, p_drop, _site(seeds, p_drop))
-        return _linear(h, cw["4"].weight, cw["4"].bias, gemm)
-    h = F.gelu(_linear(x_nhwc, cw["0"].weight, cw["0"].bias, gemm))
+    if plan.act:
+        h = gelu_grn_dropout(_linear(x_nhwc, cw["0"].weight, cw["0"].bias, plan.gemm), cw["2"].gamma, cw["2"].beta, p_drop, _site(plan, blk.kind, p_drop))
+        return _linear(h, cw["4"].weight, cw["4"].bias, plan.gemm)
+    h = F.gelu(_linear(x_nhwc, cw["0"].weight, cw["0"].bias, plan.gemm))
     gx = torch.norm(h, p=2, dim=(1, 2), keepdim=True)
     nx = gx / (gx.mean(dim=-1, keepdim=True) + 1e-6)
     h = cw["2"].gamma * (h * nx) + cw["2"].beta + h
-    h = F.dropout(h, p_drop, training)
-    return _linear(h, cw["4"].weight, cw["4"].bias, gemm)
+    h = F.dropout(h, p_drop, plan.training)
+    return _linear(h, cw["4"].weight, cw["4"].bias, plan.gemm)
 
 
-def _res_block(blk, x, skip, p_drop, training, route=_TORCH, defer=False, gemm=False, seeds=None):
-    """ResBlock (src/modules.py:43-62): depthwise 3x3 (groups = c, over cat([x, skip]) when a skip arrives) -> LN -> MLP -> + x.  route.dw
+def _res_block(blk, x, skip, p_drop, plan, defer=False):
+    """ResBlock (src/modules.py:43-62): depthwise 3x3 (groups = c, over cat([x, skip]) when a skip arrives) -> LN -> MLP -> + x.  plan.dw
     (Paella.set_training_depthwise("hip"), train mode on a cuda device): everything in front of the MLP runs as one HIP op in both directions
     (`dwconv_layernorm`), x and skip handed over separately -- no torch.cat.  defer: the two summands (MLP output, x) come back unadded."""
     res = x
-    if route.dw:
+    if plan.dw:
         y = dwconv_layernorm(x, blk.depthwise.weight, blk.depthwise.bias, skip)
     else:
         if skip is not None:
@@ -87,15 +127,15 @@ def _res_block(blk, x, skip, p_drop, training, route=_TORCH, defer=False, gemm=F
         dw = blk.depthwise
         c = dw.weight.size(0)
         y = _ln_nchw(F.conv2d(x, dw.weight, dw.bias, padding=dw.weight.size(-1) // 2, groups=c)).permute(0, 2, 3, 1)
-    out = _channelwise(blk, y, p_drop, training, route, gemm, seeds).permute(0, 3, 1, 2)
+    out = _channelwise(blk, y, p_drop, plan).permute(0, 3, 1, 2)
     return (out, res) if defer else out + res
 
 
-def _ff_block(blk, x, p_drop, training, route=_TORCH, z=None, defer=False, gemm=False, seeds=None):
+def _ff_block(blk, x, p_drop, plan, z=None, defer=False):
     """FeedForwardBlock (src/modules.py:82-96).  z [B, H W, C]: the LayerNorm rows of x, already made by `timestep_modulate`; defer: the two summands
     (MLP output, x) come back unadded."""
     rows = _ln_nchw(x).permute(0, 2, 3, 1) if z is None else z.view(x.size(0), x.size(2), x.size(3), x.size(1))
-    out = _channelwise(blk, rows, p_drop, training, route, gemm, seeds).permute(0, 3, 1, 2)
+    out = _channelwise(blk, rows, p_drop, plan).permute(0, 3, 1, 2)
     return (out, x) if defer else x + out
 
 
@@ -105,13 +145,13 @@ def _timestep_block(blk, x, r_embed):
     return x * (1 + a) + b
 
 
-def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, training, attn_weights=None, route=_TORCH, z=None, gemm=False, seeds=None):
+def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, plan, attn_weights=None, z=None):
     """AttnBlock (src/modules.py:65-79) around nn.MultiheadAttention semantics (Attention2D :7-19): queries = LN(x) positions,
-    keys = values = [LN(x) positions | kv_mapper(SiLU(c_embed))], residual on the un-normed x.  route.attn (Paella.set_training_attention("hip"), train mode
+    keys = values = [LN(x) positions | kv_mapper(SiLU(c_embed))], residual on the un-normed x.  plan.attn (Paella.set_training_attention("hip"), train mode
     on a cuda device): between the in-projection (one F.linear for the queries, one for keys and values together) and the out-projection the block runs as one HIP
     op in both directions (`attention_dropout`).  With attn_weights the torch branch below runs under either setting: the key-weight table stays an inference
-    feature.  z [B, H W, C]: the LayerNorm rows of x, already made by `timestep_modulate` -- the queries on all three branches.  gemm
-    (Paella.set_training_gemm("bf16")): the q, kv and out projections of the route.attn branch go through `_linear`; the other two branches keep their torch calls."""
+    feature.  z [B, H W, C]: the LayerNorm rows of x, already made by `timestep_modulate` -- the queries on all three branches.  plan.gemm
+    (Paella.set_training_gemm("bf16")): the q, kv and out projections of the plan.attn branch go through `_linear`; the other two branches keep their torch calls."""
     kvm = blk.kv_mapper._modules["1"]
     kv = F.linear(F.silu(c_embed), kvm.weight, kvm.bias)
     B, C, H, W = x.shape
@@ -119,15 +159,15 @@ def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, training, attn_weight
     if self_attn:
         kv = torch.cat([q, kv], dim=1)
     at = blk.attention.attn
-    if attn_weights is None and route.attn:
+    if attn_weights is None and plan.attn:
         w, bias = at.in_proj_weight, at.in_proj_bias
-        out = attention_dropout(_linear(q, w[:C], bias[:C], gemm), _linear(kv, w[C:], bias[C:], gemm), nhead, p_drop, _site(seeds, p_drop))
-        out = _linear(out, at.out_proj.weight, at.out_proj.bias, gemm)
+        out = attention_dropout(_linear(q, w[:C], bias[:C], plan.gemm), _linear(kv, w[C:], bias[C:], plan.gemm), nhead, p_drop, _site(plan, blk.kind, p_drop))
+        out = _linear(out, at.out_proj.weight, at.out_proj.bias, plan.gemm)
     elif attn_weights is None:
         # torch's own functional form of nn.MultiheadAttention.forward (batch_first handled by the transposes): identical
         # arithmetic and identical dropout-stream consumption to the module the reference instantiates
         out, _ = F.multi_head_attention_forward(q.transpose(0, 1), kv.transpose(0, 1), kv.transpose(0, 1), C, nhead, at.in_proj_weight, at.in_proj_bias,
-                                                None, None, False, p_drop, at.out_proj.weight, at.out_proj.bias, training=training,
+                                                None, None, False, p_drop, at.out_proj.weight, at.out_proj.bias, training=plan.training,
                                                 need_weights=False)
         out = out.transpose(0, 1)
     else:  # utils/alter_attention.py:4-43: post-softmax multiply of the last n key columns
@@ -140,7 +180,7 @@ def _attn_block(blk, x, c_embed, nhead, self_attn, p_drop, training, attn_weight
         w = torch.softmax(qh @ kh.transpose(-1, -2) / math.sqrt(d), dim=-1)
         n = attn_weights.numel()
         w = torch.cat([w[..., :-n], w[..., -n:] * attn_weights], dim=-1)
-        w = F.dropout(w, p_drop, training)
+        w = F.dropout(w, p_drop, plan.training)
         out = F.linear((w @ vh).transpose(1, 2).reshape(B, -1, C), at.out_proj.weight, at.out_proj.bias)
     return x + out.permute(0, 2, 1).reshape(B, C, H, W)
 
@@ -203,9 +243,9 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
     if seeds is not None:
         seeds.begin()
     cfg = model._cfg
-    training = model.training
-    p_drop = float(model.dropout) if not isinstance(model.dropout, (list, tuple)) else None
-    drop = (lambda lvl: p_drop) if p_drop is not None else (lambda lvl: float(model.dropout[lvl]))
+    # the training switches (TRAIN_SWITCHES): decided once, here -- a switch acts in train mode on a cuda device only; its default leaves every call below as it is
+    plan = _plan(model, model.training and x.is_cuda, seeds)
+    drop = _level_dropout(model)
     if x_cat is not None:
         x = torch.cat([x, x_cat], dim=1)
     # (the embedding is made in fp32 whatever the module's dtype -- its angles are fp32 products by definition -- and handed over in the dtype of the parameters:
@@ -213,32 +253,23 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
     r_embed = r_embedding(r.float(), cfg["c_r"]).to(model.clf._modules["1"].weight.dtype)
     c_embed = c_embeddings(model, byt5, clip, clip_image)
     patch = cfg["patch_size"]
-    n_levels = len(cfg["c_hidden"])
 
     h = F.layer_norm(_token_embedding(x, model.in_mapper._modules["0"].weight, seeds is not None), (cfg["c_in"],), None, None, 1e-6).permute(0, 3, 1, 2)
     emb = model.embedding._modules["1"]
     h = _ln_nchw(F.conv2d(F.pixel_unshuffle(h, patch), emb.weight, emb.bias))
 
-    # Paella.set_training_activation / set_training_depthwise / set_training_attention: a switch acts in train mode on a cuda device only; its default leaves every call below as it is
-    on = training and x.is_cuda
-    route = _Route(on and getattr(model, "_train_activation", "torch") == "hip", on and getattr(model, "_train_depthwise", "torch") == "hip",
-                   on and getattr(model, "_train_attention", "torch") == "hip")
-    if route.dw:  # the trunk is made channels_last once, here, so that the blocks hand each other NHWC memory
+    if plan.dw:  # the trunk is made channels_last once, here, so that the blocks hand each other NHWC memory
         h = h.contiguous(memory_format=torch.channels_last)
-    # Paella.set_training_modulation: carried beside the route.  "hip": the joint of every TimestepBlock with its neighbours in the level is `timestep_modulate`
-    mod = on and getattr(model, "_train_modulation", "torch") == "hip"
-    # Paella.set_training_gemm: carried beside the route.  "bf16": the linears of every MLP and the projections around `attention_dropout` run on bf16 operands
-    gemm = on and getattr(model, "_train_gemm", "fp32") == "bf16"
 
     def run(blk, level, h, skip=None, z=None, defer=False):
         if blk.kind == 'C':
-            return _res_block(blk, h, skip, drop(level), training, route, defer, gemm, seeds)
+            return _res_block(blk, h, skip, drop(level), plan, defer)
         if blk.kind == 'A':
-            return _attn_block(blk, h, c_embed, cfg["nhead"][level], cfg["self_attn"], drop(level), training, attn_weights, route, z, gemm, seeds)
+            return _attn_block(blk, h, c_embed, cfg["nhead"][level], cfg["self_attn"], drop(level), plan, attn_weights, z)
         if blk.kind == 'T':
             return _timestep_block(blk, h, r_embed)
         if blk.kind == 'F':
-            return _ff_block(blk, h, drop(level), training, route, z, defer, gemm, seeds)
+            return _ff_block(blk, h, drop(level), plan, z, defer)
         if blk.kind == 'D':  # LayerNorm2d + Conv2d(k2, s2)   (src/modules.py:153-156)
             cv = blk._modules["1"]
             return F.conv2d(_ln_nchw(h), cv.weight, cv.bias, stride=2)
@@ -248,14 +279,14 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
         raise RuntimeError("unknown block kind %r" % blk.kind)
 
     def run_level(level, i, h, skip=None):
-        """the blocks of one level in order; skip goes to a ResBlock that comes first.  With `mod`, a C / F block right in front of a T block hands (MLP output,
+        """the blocks of one level in order; skip goes to a ResBlock that comes first.  With plan.mod, a C / F block right in front of a T block hands (MLP output,
         its input) over unadded, the T block is one `timestep_modulate` call, and when an A / F block follows in the level the op makes its LayerNorm rows too"""
         level = list(level)
         z = None
         for j, blk in enumerate(level):
             nxt = level[j + 1].kind if j + 1 < len(level) else None
             sk = skip if (j == 0 and blk.kind == 'C') else None
-            if not mod:
+            if not plan.mod:
                 h = run(blk, i, h, sk)
             elif blk.kind == 'T':
                 x, res = h if isinstance(h, tuple) else (h, None)
@@ -268,13 +299,10 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
                 h, z = run(blk, i, h, sk, z, defer=blk.kind in ('C', 'F') and nxt == 'T'), None
         return h
 
-    level_outputs = []
-    for i, level in enumerate(model.down_blocks):          # _down_encode (src/modules.py:234-247)
-        h = run_level(level, i, h)
-        level_outputs.insert(0, h)
-    h = level_outputs[0]
-    for u, level in enumerate(model.up_blocks):            # _up_decode (src/modules.py:249-261)
-        h = run_level(level, n_levels - 1 - u, h, level_outputs[u] if u > 0 else None)
+    encoded = {}
+    for i, level, skip in _levels(model):
+        h = run_level(level, i, h, encoded[i] if skip else None)
+        encoded.setdefault(i, h)                           # the way down passes every level first: what is kept is the encoder's output
     clf = model.clf._modules["1"]
     h = F.pixel_shuffle(F.conv2d(_ln_nchw(h), clf.weight, clf.bias), patch)
     return _ln_nchw(h)
@@ -301,17 +329,11 @@ def dropout_sites(model):
     """How many words of a `TrainSeeds` one train-mode forward of `model` on a cuda device consumes under its PRESENT switches and `model.dropout`: one per
     `gelu_grn_dropout` call (every C / F block, with set_training_activation("hip")) and one per `attention_dropout` call (every A block, with
     set_training_attention("hip")) whose level has p > 0.  The torch routes draw through torch's generator and count nothing."""
-    act = getattr(model, "_train_activation", "torch") == "hip"
-    attn = getattr(model, "_train_attention", "torch") == "hip"
-    n_levels = len(model._cfg["c_hidden"])
-    p_of = (lambda lvl: float(model.dropout[lvl])) if isinstance(model.dropout, (list, tuple)) else (lambda lvl: float(model.dropout))
-    levels = [(i, lv) for i, lv in enumerate(model.down_blocks)] + [(n_levels - 1 - u, lv) for u, lv in enumerate(model.up_blocks)]
-    return sum(1 for i, lv in levels for blk in lv if p_of(i) > 0.0 and ((blk.kind in ('C', 'F') and act) or (blk.kind == 'A' and attn)))
+    plan, drop = _plan(model, True), _level_dropout(model)
+    return sum(1 for i, level, _ in _levels(model) for blk in level if _draws(plan, blk.kind, drop(i)))
 
 
 _STEP_INPUTS = ("noised", "t", "latents", "byt5", "clip", "clip_image", "x_cat", "loss_weight")
-_TRAIN_SWITCHES = (("training activation", "_train_activation", "torch"), ("training depthwise", "_train_depthwise", "torch"),
-                   ("training attention", "_train_attention", "torch"), ("training modulation", "_train_modulation", "torch"), ("training gemm", "_train_gemm", "fp32"))
 
 
 class GraphTrainStep:
@@ -382,7 +404,7 @@ class GraphTrainStep:
         return [("parameter storage", tuple(p.data_ptr() for p in ps)), ("parameters that require a gradient", tuple(p.requires_grad for p in ps)),
                 ("optimizer state storage", (tuple(state), None if opt._rows_dev is None else opt._rows_dev.data_ptr(), None if opt._ws is None else opt._ws.data_ptr(),
                                              tuple(id(p) for p in opt._params()), opt.max_norm))] + \
-               [(name, getattr(m, attr, default)) for name, attr, default in _TRAIN_SWITCHES] + \
+               [(s.label, s.read(m)) for s in TRAIN_SWITCHES] + \
                [("model.dropout", tuple(m.dropout) if isinstance(m.dropout, (list, tuple)) else float(m.dropout)), ("train mode", bool(m.training))]
 
     def _iteration(self, optimize):

@@ -195,19 +195,10 @@ def test_attention_dropout_refuses_what_the_op_cannot_do():
 
 
 def test_set_training_attention():
-    m = paella_amd.Paella(**G.UNET_TINY)
-    assert m._train_attention == "torch"
-    for bad in ("HIP", "cuda", "", None, 1):
-        with pytest.raises(ValueError, match="'torch' or 'hip'"):
-            m.set_training_attention(bad)
-    assert m.set_training_attention("hip") is m and m._train_attention == "hip"
-    # independent of the other two switches, in both directions
-    assert m._train_activation == "torch" and m._train_depthwise == "torch"
-    m.set_training_activation("hip").set_training_depthwise("hip")
-    assert m._train_attention == "hip"
-    assert m.set_training_attention("torch")._train_attention == "torch"
-    assert m._train_activation == "hip" and m._train_depthwise == "hip"
-    assert training._TORCH == (False, False, False) and training._Route._fields == ("act", "dw", "attn")
+    """(what every switch's setter does: tests/test_training.py::test_training_switch)"""
+    m = paella_amd.Paella(**G.UNET_TINY).set_training_attention("hip")
+    # the plan of a forward carries one field per row of the table, in its order
+    assert training._plan(m, True)._fields[:len(training.TRAIN_SWITCHES)] == tuple(s.field for s in training.TRAIN_SWITCHES)
     assert training.ATTN_COUNTERS == {"calls": training.ATTN_COUNTERS["calls"]}
     # nothing new at the package root beyond the method
     assert not [n for n in dir(paella_amd) if "attention_dropout" in n or n.startswith("ATTN")]

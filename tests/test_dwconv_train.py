@@ -174,22 +174,15 @@ def test_dwconv_layernorm_refuses_what_the_op_cannot_do():
 
 
 def test_set_training_depthwise():
+    """(what every switch's setter does: tests/test_training.py::test_training_switch)  Its own: the kernel_size rule, through every entry point"""
     names = set(dir(paella_amd))
-    m = paella_amd.Paella(**G.UNET_TINY)
-    assert m._train_depthwise == "torch"
-    for bad in ("HIP", "cuda", "", None, 1):
-        with pytest.raises(ValueError, match="'torch' or 'hip'"):
-            m.set_training_depthwise(bad)
-    m.set_training_activation("hip")
-    assert m.set_training_depthwise("hip") is m and m._train_depthwise == "hip" and m._train_activation == "hip"
-    m.set_training_activation("torch")
-    assert m._train_depthwise == "hip"
-    assert m.set_training_depthwise("torch")._train_depthwise == "torch" and m._train_activation == "torch"
     k5 = paella_amd.Paella(**dict(G.UNET_TINY, kernel_size=5))
-    assert k5.set_training_depthwise("torch") is k5
-    with pytest.raises(ValueError, match="kernel_size 3"):
-        k5.set_training_depthwise("hip")
-    assert k5._train_depthwise == "torch"
+    assert k5.set_training_depthwise("torch") is k5 and k5.set_training_route(depthwise="torch", attention="hip") is k5
+    for refused in (lambda: k5.set_training_depthwise("hip"), lambda: k5.set_training_route(depthwise="hip"), lambda: k5.set_training_route(attention="torch", depthwise="hip")):
+        with pytest.raises(ValueError, match="kernel_size 3"):
+            refused()
+        assert k5._train_depthwise == "torch" and k5._train_attention == "hip"
+    assert paella_amd.Paella(**G.UNET_TINY).set_training_depthwise("hip")._train_depthwise == "hip"
     assert set(dir(paella_amd)) == names and not hasattr(paella_amd, "dwconv_layernorm")   # nothing new at the package root beyond the method
 
 

@@ -45,9 +45,8 @@ def word_tensor(s):
     return torch.tensor([s - (1 << 64) if s >> 63 else s], dtype=torch.int64, device=DEV)
 
 
-def switch(m, activation, depthwise, attention, modulation, gemm):
-    m.set_training_activation(activation).set_training_depthwise(depthwise).set_training_attention(attention).set_training_modulation(modulation).set_training_gemm(gemm)
-    return m
+def switch(m, **kw):
+    return m.set_training_route(**kw)
 
 
 def fresh_model(case, switches=ALL_ON, dropout=None):

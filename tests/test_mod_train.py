@@ -183,22 +183,13 @@ def test_timestep_modulate_refuses_what_the_op_cannot_do():
 
 
 def test_set_training_modulation():
+    """(what every switch's setter does: tests/test_training.py::test_training_switch)"""
     names = set(dir(paella_amd))
     m = paella_amd.Paella(**G.UNET_TINY)
-    assert m._train_modulation == "torch"
-    for bad in ("HIP", "cuda", "", None, 1):
-        with pytest.raises(ValueError, match="'torch' or 'hip'"):
-            m.set_training_modulation(bad)
-    assert m._train_modulation == "torch"
-    assert m.set_training_modulation("hip") is m and m._train_modulation == "hip"
-    # independent of the other three switches, in both directions
-    assert (m._train_activation, m._train_depthwise, m._train_attention) == ("torch", "torch", "torch")
-    m.set_training_activation("hip").set_training_depthwise("hip").set_training_attention("hip")
-    assert m._train_modulation == "hip"
-    assert m.set_training_modulation("torch")._train_modulation == "torch"
-    assert (m._train_activation, m._train_depthwise, m._train_attention) == ("hip", "hip", "hip")
-    # the flag travels beside the route, not in it
-    assert training._TORCH == (False, False, False) and training._Route._fields == ("act", "dw", "attn")
+    # a freshly built model's plan is all-off, in train mode on a cuda device too
+    m.train()
+    assert not any(training._plan(m, True)[:len(training.TRAIN_SWITCHES)]) and training._plan(m, True).training
+    assert training._plan(m.set_training_modulation("hip"), True).mod and not training._plan(m, False).mod
     assert set(training.MOD_COUNTERS) == {"calls", "residual", "layernorm", "copied"}
     # nothing new at the package root beyond the method
     assert set(dir(paella_amd)) == names and not [n for n in dir(paella_amd) if "timestep_modulate" in n or n.startswith("MOD")]

@@ -10,6 +10,7 @@ from torch import nn
 
 import paella_amd
 from oracle import golden_configs as G
+from paella_amd import training
 from tests.helpers import weights_for
 
 
@@ -82,3 +83,40 @@ def test_mode_switch_and_optimizer_step(model):
     model.eval()
     with pytest.raises(RuntimeError, match="HIP device"):
         model(torch.zeros(1, 8, 8, dtype=torch.long), torch.zeros(1), torch.zeros(1, 2, 40))
+
+
+BAD_MODES = ("HIP", "cuda", "", None, 1, "BF16", "fp16")
+
+
+@pytest.mark.parametrize("row", training.TRAIN_SWITCHES, ids=lambda s: s.name)
+def test_training_switch(row):
+    """Every row of `training.TRAIN_SWITCHES` gives one attribute, one `set_training_*` method and one keyword of `set_training_route`: the default, the refusal of
+    anything but its two settings (the other rows' settings among them) with the setting left alone, the module returned, the other four switches untouched in
+    both directions; then `set_training_route` (all or nothing) and `training_route` (round trip)."""
+    others = [s for s in training.TRAIN_SWITCHES if s is not row]
+    assert (row.attr, row.setter, row.label) == ("_train_" + row.name, "set_training_" + row.name, "training " + row.name)
+    assert row.refusal == "training %s must be '%s' or '%s'" % (row.name, row.off, row.on)
+    for start in ("off", "on"):          # the other four all off, then all on
+        m = paella_amd.Paella(**G.UNET_TINY)
+        assert getattr(m, row.attr) == row.off and m.training_route() == {s.name: s.off for s in training.TRAIN_SWITCHES}
+        for s in others:
+            getattr(m, s.setter)(getattr(s, start))
+        rest = {s.name: getattr(s, start) for s in others}
+        for bad in BAD_MODES + tuple(v for s in others for v in (s.off, s.on) if v not in (row.off, row.on)):
+            with pytest.raises(ValueError, match=row.refusal):
+                getattr(m, row.setter)(bad)
+            with pytest.raises(ValueError, match=row.refusal):
+                m.set_training_route(**dict({s.name: s.off if start == "on" else s.on for s in others}, **{row.name: bad}))     # a bad value among good ones
+            assert m.training_route() == dict(rest, **{row.name: row.off})
+        for mode in (row.on, row.off, row.on):
+            assert getattr(m, row.setter)(mode) is m and getattr(m, row.attr) == mode
+            assert m.training_route() == dict(rest, **{row.name: mode}) and [getattr(m, s.attr) for s in others] == [getattr(s, start) for s in others]
+        assert m.set_training_route(**{row.name: row.off}) is m and getattr(m, row.attr) == row.off
+        route = m.set_training_route(**{row.name: row.on}).training_route()
+        assert list(route) == [s.name for s in training.TRAIN_SWITCHES]
+        fresh = paella_amd.Paella(**G.UNET_TINY)
+        assert fresh.set_training_route(**route).training_route() == route and fresh.set_training_route().training_route() == route
+        del fresh.__dict__[row.attr]        # a module pickled before the switch existed: read as its default
+        assert fresh.training_route() == dict(route, **{row.name: row.off}) and training._plan(fresh, True)._asdict()[row.field] is False
+    with pytest.raises(TypeError, match="set_training_route takes"):
+        m.set_training_route(**{row.name: row.on, "route": "hip"})

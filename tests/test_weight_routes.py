@@ -16,7 +16,7 @@ from torch import nn
 
 import paella_amd
 from oracle import golden_configs as G
-from paella_amd import _lib
+from paella_amd import _lib, training
 from tests import weight_routes as R
 from tests.helpers import weights_for
 
@@ -158,9 +158,9 @@ def test_copy_of_a_module_that_has_run(monkeypatch, kind, how):
     monkeypatch.setattr(_lib, "load", lambda: lib)
     m, sd = _new(kind)
     m._precision = 1
-    switches = ("_train_activation", "_train_depthwise", "_train_attention", "_train_modulation") if kind == "paella" else ()
+    switches = training.TRAIN_SWITCHES if kind == "paella" else ()
     if kind == "paella":
-        m.set_training_activation("hip").set_training_depthwise("hip").set_training_attention("hip").set_training_modulation("hip")
+        m.set_training_route(**{s.name: s.on for s in switches})
     handle = ctypes.c_void_p(0)
     m._handle, m._loaded_sig, m._ws, m._load_gen = handle, m._signature(), torch.zeros(8, dtype=torch.uint8), 7
     try:
@@ -174,7 +174,7 @@ def test_copy_of_a_module_that_has_run(monkeypatch, kind, how):
             assert torch.equal(v, sd[k]) and v.data_ptr() != m.state_dict()[k].data_ptr(), k
         assert c._cfg == m._cfg and c._cfg is not m._cfg and c._precision == 1 and c.training == m.training
         for s in switches:
-            assert getattr(c, s) == "hip"
+            assert getattr(c, s.attr) == s.on
         if kind == "vqmodel":
             assert c.vquantizer._owner[0] is c, "the copy's quantiser still calls the original"
         assert len(c._signature()) == len(m._signature()) and c._signature() != m._signature()

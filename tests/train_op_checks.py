@@ -254,13 +254,13 @@ def as_dict(stepped):
 
 
 def run_step(case, route=HIP, dropout=None, seeds=None, fused_loss=False, zero=True, backward=True):
-    """one training step of case.m under the switches `route` = (activation, depthwise, attention[, modulation]; a route of three leaves the fourth as it is):
+    """one training step of case.m under the switches `route` = (activation, depthwise, attention[, modulation]), the leading rows of training.TRAIN_SWITCHES (a
+    switch the route does not reach stays as it is):
     `model(...)` + CrossEntropyLoss as _train_step of tests/test_gpu_training.py, or `forward_loss`; -> dict(values = {parameter name: its .grad, LOGITS, PER_POS,
     "loss"}, correct, harness)"""
     m = case.m
-    m.set_training_activation(route[0]).set_training_depthwise(route[1]).set_training_attention(route[2])
-    if len(route) > 3:
-        m.set_training_modulation(route[3])
+    assert len(route) in (3, 4)
+    m.set_training_route(**{s.name: mode for s, mode in zip(training.TRAIN_SWITCHES, route)})
     m.train()
     m.dropout = case.dropout if dropout is None else dropout
     if zero:

@@ -89,18 +89,7 @@ def main():
         torch.cuda.empty_cache()
 
     if not a.no_step:
-        S = AB.TrainStep(a.step_model, a.step_batch, a.step_grid, dev)
-        m = S.m
-        paths = {mode: S.under(m.set_training_activation, mode) for mode in ("torch", "hip")}
-        say("one training step (forward_loss + backward), %s; %d rounds of 1 step per setting after one warm-up, settings alternating" % (S.what, a.step_rounds))
-        losses = {name: float(fn()) for name, fn in paths.items()}   # warm-up
-        m.zero_grad(set_to_none=True)
-        peak = {name: AB.peak_of(dev, fn) for name, fn in paths.items()}
-        m.zero_grad(set_to_none=True)
-        times = AB.alternate(dev, paths, a.step_rounds, 1)
-        say("%10s %12s %12s %12s %26s %12s" % ("setting", "median ms", "min ms", "max ms", "peak MiB > weights + inputs", "loss"))
-        for name in paths:
-            say("%10s %12.2f %12.2f %12.2f %26.1f %12.5f" % ((name,) + median(times[name]) + (peak[name] / 2 ** 20, losses[name])))
+        AB.step_ab(say, AB.TrainStep(a.step_model, a.step_batch, a.step_grid, dev), "activation", a.step_rounds)
     report.finish()
 
 

@@ -111,37 +111,12 @@ def main():
         return finish()
 
     S = AB.TrainStep(a.step_model, a.step_batch, a.step_grid, dev)
-    m = S.m
-    m.set_training_activation("hip")
-    held = {}
-    what = S.what + ", set_training_activation(\"hip\")"
+    first = dict(activation="hip")
     if a.part == "trace-step":
-        fn = S.under(m.set_training_depthwise, a.setting)
-        fn()   # warm-up (traced as well: divide the totals by 1 + --steps)
-        for _ in range(a.steps):
-            fn()
-        torch.cuda.synchronize(dev)
-        say("traced %d + 1 training steps with set_training_depthwise(\"%s\"): %s" % (a.steps, a.setting, what))
+        AB.trace_step(say, S, "depthwise", a.setting, a.steps, first)
         return finish()
-
-    paths = {mode: S.under(m.set_training_depthwise, mode, held) for mode in ("torch", "hip")}
-    say("one training step (forward_loss + backward), %s; %d rounds of 1 step per set_training_depthwise setting after one warm-up, settings alternating" % (what, a.step_rounds))
-    losses, counts = {}, {}
-    for name, fn in paths.items():   # warm-up
-        c0 = dict(training.DW_COUNTERS)
-        losses[name] = float(fn())
-        counts[name] = (training.DW_COUNTERS["calls"] - c0["calls"], training.DW_COUNTERS["copied"] - c0["copied"])
-    peak = {}
-    for name, fn in paths.items():
-        m.zero_grad(set_to_none=True)   # the base of EITHER setting holds no parameter gradients: the peak includes the step's own
-        peak[name] = AB.peak_of(dev, fn)
-    m.zero_grad(set_to_none=True)
-    times = AB.alternate(dev, paths, a.step_rounds, 1)
-    say("peak = max allocated during the step above weights and inputs, the step's parameter gradients (%.1f MiB once all exist) included under either setting; "
-        "held = allocated between the forward and the backward above weights and inputs (what autograd keeps)" % (S.parameters() * 4 / 2 ** 20))
-    say("%10s %12s %12s %12s %10s %10s %12s %10s %14s" % ("setting", "median ms", "min ms", "max ms", "peak MiB", "held MiB", "loss", "op calls", "inputs copied"))
-    for name in paths:
-        say("%10s %12.2f %12.2f %12.2f %10.1f %10.1f %12.5f %10d %14d" % ((name,) + median(times[name]) + (peak[name] / 2 ** 20, held[name] / 2 ** 20, losses[name]) + counts[name]))
+    AB.step_ab(say, S, "depthwise", a.step_rounds, first, training.DW_COUNTERS, " %10s %14s" % ("op calls", "inputs copied"),
+               lambda c: " %10d %14d" % (c["calls"], c["copied"]), AB.legend(S))
     finish()
 
 

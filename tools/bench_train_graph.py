@@ -85,7 +85,7 @@ def main():
     dev = torch.device("cuda", 0)
     S = AB.TrainStep(a.model, a.step_batch, a.step_grid, dev)
     m = S.m
-    m.set_training_activation("hip").set_training_depthwise("hip").set_training_attention("hip").set_training_modulation("hip").set_training_gemm("bf16")
+    m.set_training_route(activation="hip", depthwise="hip", attention="hip", modulation="hip", gemm="bf16")
     opt = training.ClippedAdamW(m.parameters(), lr=1e-6)
     opt.materialize_state()
     fwd_bwd = S.under(lambda mode: None, None)      # zero_grad(set_to_none=True) first, then forward_loss + backward of the weighted mean

@@ -119,19 +119,15 @@ def main():
 
     S = AB.TrainStep(a.step_model, a.step_batch, a.step_grid, dev)
     m = S.m
-    m.set_training_activation("hip").set_training_depthwise("hip").set_training_attention("hip").set_training_modulation("hip")
-    held = {}
-    what = S.what + ", the other four training switches on \"hip\""
+    first = dict(activation="hip", depthwise="hip", attention="hip", modulation="hip")
+    others = ", the other four training switches on \"hip\""
+    what = S.what + others
     if a.part == "trace-step":
-        fn = S.under(m.set_training_gemm, a.setting)
-        fn()   # warm-up (traced as well: divide the totals by 1 + --steps)
-        for _ in range(a.steps):
-            fn()
-        torch.cuda.synchronize(dev)
-        say("traced %d + 1 training steps with set_training_gemm(\"%s\"): %s" % (a.steps, a.setting, what))
+        AB.trace_step(say, S, "gemm", a.setting, a.steps, first, others)
         return finish()
 
     if a.part == "loss":
+        m.set_training_route(**first)
         m.dropout = 0.0
         sd = {k: v.detach().clone() for k, v in m.state_dict().items()}
         say("loss of the first %d optimizer steps on one fixed batch (ClippedAdamW lr 1e-4, dropout 0), same initial weights: %s" % (a.steps, what))
@@ -150,26 +146,10 @@ def main():
             say("%6d %12.6f %12.6f %+12.2e" % (i, curves["fp32"][i], curves["bf16"][i], curves["bf16"][i] - curves["fp32"][i]))
         return finish()
 
-    paths = {mode: S.under(m.set_training_gemm, mode, held) for mode in ("fp32", "bf16")}
-    say("one training step (forward_loss + backward), %s; %d rounds of 1 step per set_training_gemm setting after one warm-up, settings alternating" % (what, a.step_rounds))
-    losses, counts = {}, {}
-    for name, fn in paths.items():   # warm-up
-        c0 = dict(training.LINEAR_COUNTERS)
-        losses[name] = float(fn())
-        counts[name] = {k: training.LINEAR_COUNTERS[k] - c0[k] for k in c0}
-    peak = {}
-    for name, fn in paths.items():
-        m.zero_grad(set_to_none=True)   # the base of EITHER setting holds no parameter gradients: the peak includes the step's own
-        peak[name] = AB.peak_of(dev, fn)
-    m.zero_grad(set_to_none=True)
-    times = AB.alternate(dev, paths, a.step_rounds, 1)
-    say("peak = max allocated during the step above weights and inputs (the op's workspaces included); held = allocated between the forward and the backward above "
-        "weights and inputs (what autograd keeps); the losses differ: each step draws its own dropout masks, and the bf16 setting rounds the GEMM operands")
-    say("%10s %12s %12s %12s %10s %10s %12s  %s" % ("setting", "median ms", "min ms", "max ms", "peak MiB", "held MiB", "loss", "linear_bf16 calls (backward calls, fallbacks to F.linear, copies)"))
-    for name in paths:
-        c = counts[name]
-        say("%10s %12.2f %12.2f %12.2f %10.1f %10.1f %12.5f  %d (%d, %d, %d)" % ((name,) + median(times[name]) + (peak[name] / 2 ** 20, held[name] / 2 ** 20, losses[name],
-                                                                                  c["calls"], c["backward"], c["fallbacks"], c["copied"])))
+    AB.step_ab(say, S, "gemm", a.step_rounds, first, training.LINEAR_COUNTERS, "  %s" % "linear_bf16 calls (backward calls, fallbacks to F.linear, copies)",
+               lambda c: "  %d (%d, %d, %d)" % (c["calls"], c["backward"], c["fallbacks"], c["copied"]),
+               "peak = max allocated during the step above weights and inputs (the op's workspaces included); held = allocated between the forward and the backward above "
+               "weights and inputs (what autograd keeps); the losses differ: each step draws its own dropout masks, and the bf16 setting rounds the GEMM operands", others)
     finish()
 
 

@@ -127,7 +127,7 @@ def main():
 
     S = AB.TrainStep(a.model, a.step_batch, a.step_grid, dev)
     m = S.m
-    m.set_training_activation("hip").set_training_depthwise("hip").set_training_attention("hip").set_training_modulation("hip")
+    m.set_training_route(activation="hip", depthwise="hip", attention="hip", modulation="hip")
     params = list(m.parameters())
     fwd_bwd = S.under(lambda mode: None, None)
     updates = {"foreach": torch_update(params, torch.optim.AdamW(params, lr=1e-6)), "hip": training.ClippedAdamW(params, lr=1e-6).step}

@@ -1,6 +1,6 @@
-"""What the A/B tools of the training ops (bench_head_loss.py, bench_train_activation.py, bench_train_dwconv.py, bench_train_attention.py, bench_train_modulation.py) do the same way: the report
-that is printed and kept for --out, the timing of paths that take turns, peak memory of one pass, the set-up of one training step of a bench.py model, and the two
-tables read from rocprofv3 kernel traces.  torch is imported on use: the parts of the tools that only read traces need no device."""
+"""What the A/B tools of the training ops (bench_head_loss.py, bench_train_activation.py, bench_train_dwconv.py, bench_train_attention.py, bench_train_modulation.py, bench_train_linear.py) do the same way: the report
+that is printed and kept for --out, the timing of paths that take turns, peak memory of one pass, the set-up of one training step of a bench.py model, the `step` and `trace-step` parts
+of a training switch's tool (the switch named as in paella_amd.training.TRAIN_SWITCHES), and the two tables read from rocprofv3 kernel traces.  torch is imported on use: the parts of the tools that only read traces need no device."""
 import csv
 import glob
 import os
@@ -104,6 +104,68 @@ class TrainStep:
             loss.backward()
             return loss.detach()
         return step
+
+
+def _switch_of(m, name):
+    from paella_amd import training
+    row = next(s for s in training.TRAIN_SWITCHES if s.name == name)
+    return row, lambda mode: m.set_training_route(**{name: mode})
+
+
+def _first_text(first):
+    return "".join(", set_training_%s(\"%s\")" % kv for kv in first.items())
+
+
+def legend(S, tail=""):
+    return ("peak = max allocated during the step above weights and inputs, the step's parameter gradients (%.1f MiB once all exist) included under either setting; "
+            "held = allocated between the forward and the backward above weights and inputs (what autograd keeps)" % (S.parameters() * 4 / 2 ** 20)) + tail
+
+
+def trace_step(say, S, name, setting, steps, first=None, first_text=None):
+    """the `trace-step` part of a switch's tool: one warm-up and `steps` training steps under set_training_<name>(setting), the settings `first` turned on before"""
+    import torch
+    _, switch = _switch_of(S.m, name)
+    S.m.set_training_route(**(first or {}))
+    fn = S.under(switch, setting)
+    fn()   # warm-up (traced as well: divide the totals by 1 + --steps)
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize(S.dev)
+    say("traced %d + 1 training steps with set_training_%s(\"%s\"): %s" % (steps, name, setting, S.what + (first_text or _first_text(first or {}))))
+
+
+def step_ab(say, S, name, rounds, first=None, counters=None, calls_head="", calls=None, note=None, first_text=None):
+    """the `step` part of a switch's tool: one full training step under either set_training_<name> setting, the settings taking turns, the settings `first` turned on
+    before.  counters: the op's counters dict -- calls(what one step added to it) formats the table's last column(s) under calls_head; note: the legend line above
+    the table (`legend`).  Without counters the table is the short one of bench_train_activation.py."""
+    row, switch = _switch_of(S.m, name)
+    m = S.m
+    m.set_training_route(**(first or {}))
+    held = {}
+    what = S.what + (first_text or _first_text(first or {}))
+    paths = {mode: S.under(switch, mode, held) for mode in (row.off, row.on)}
+    say("one training step (forward_loss + backward), %s; %d rounds of 1 step per %ssetting after one warm-up, settings alternating"
+        % (what, rounds, "set_training_%s " % name if counters is not None else ""))
+    losses, counts = {}, {}
+    for mode, fn in paths.items():   # warm-up
+        c0 = dict(counters or {})
+        losses[mode] = float(fn())
+        counts[mode] = {k: counters[k] - c0[k] for k in c0}
+    peak = {}
+    for mode, fn in paths.items():
+        m.zero_grad(set_to_none=True)   # the base of EITHER setting holds no parameter gradients: the peak includes the step's own
+        peak[mode] = peak_of(S.dev, fn)
+    m.zero_grad(set_to_none=True)
+    times = alternate(S.dev, paths, rounds, 1)
+    if counters is None:
+        say("%10s %12s %12s %12s %26s %12s" % ("setting", "median ms", "min ms", "max ms", "peak MiB > weights + inputs", "loss"))
+        for mode in paths:
+            say("%10s %12.2f %12.2f %12.2f %26.1f %12.5f" % ((mode,) + median(times[mode]) + (peak[mode] / 2 ** 20, losses[mode])))
+        return
+    say(note)
+    say("%10s %12s %12s %12s %10s %10s %12s" % ("setting", "median ms", "min ms", "max ms", "peak MiB", "held MiB", "loss") + calls_head)
+    for mode in paths:
+        say("%10s %12.2f %12.2f %12.2f %10.1f %10.1f %12.5f" % ((mode,) + median(times[mode]) + (peak[mode] / 2 ** 20, held[mode] / 2 ** 20, losses[mode])) + calls(counts[mode]))
 
 
 def _rows(directory, suffix):
