@@ -963,6 +963,50 @@ int paella_pack_bf16(const float* src, int rows, int cols, unsigned short* out_r
 int paella_train_seeds_max_sites(void);
 int paella_train_seeds_advance(uint64_t* state, int n_sites, void* stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Training token stem (ABI 8, extended ADDITIVELY: no existing signature changes, the version stays 8): the top of
+ * the train-mode network -- token embedding, LayerNorm(c_in, no affine), PixelUnshuffle(patch) and the change to
+ * NHWC rows (reference src/modules.py:126-131, 271) -- as one op, forward and backward
+ * (paella_amd/csrc/embed_train.hip).
+ *   tokens int64 [B, H, W]; table fp32 [num_labels, c_in] (in_mapper.0.weight as it is); rows fp32
+ *   [B, H/p, W/p, c_in p^2], p = patch, with
+ *     rows[b, oy, ox, c p^2 + dy p + dx] = LN(table[clamp(tokens[b, oy p + dy, ox p + dx])])[c]
+ *   -- the A operand of the 1x1 convolution behind it as a linear.  A token outside [0, num_labels) is clamped into
+ *   the range in BOTH directions, as the inference kernel clamps it: the clamped row is read and receives the
+ *   gradient, and no address outside the table is ever formed.
+ *   Forward:  the inference engine's own launch (one wave per output position; mean and var two-pass,
+ *     rstd = 1 / sqrt(var + eps)), so rows_out holds the engine's bits.  Nothing is kept for the backward.
+ *   Backward for given d_rows (the layout of rows):  with G[l] = the sum, over the positions n whose clamped token
+ *     is l, of the de-interleaved gradient row at n, and xhat[l], rstd[l] recomputed from table[l] as the forward
+ *     forms them:  dtable[l] = rstd ((G - mean_c G) - xhat mean_c(G xhat)).  The LayerNorm backward is linear in the
+ *     arriving gradient for a fixed row, so summing first and applying it once per label is the same function as
+ *     applying it per position.  dtable_out [num_labels, c_in] is WRITTEN, not accumulated into: the row of a label
+ *     that no token holds is written as exact zeros, whatever the table holds there.
+ * Shapes: patch 1 or 2, dividing H and W; c_in a multiple of 4 in 4...1024; num_labels in 1...65536;
+ * B (H / patch) (W / patch) <= 2^31 - 1; every tensor and the workspace 16-byte aligned; eps positive and finite; all
+ * element offsets are 64-bit.  Anything else or a NULL required pointer (tokens, table, rows_out; tokens, table,
+ * d_rows, dtable_out): PAELLA_ERR_ARG; a workspace smaller than paella_embed_ln_train_workspace_bytes:
+ * PAELLA_ERR_WORKSPACE -- both before anything is enqueued.
+ * Kernel: the backward is ONE launch.  A workgroup owns min(256, 4096 / c_in) consecutive labels with their sums in
+ * LDS, carried in fp64; it scans all B H W tokens in ascending order, 1024 at a time, compacts the positions that
+ * hold one of its labels in ascending order and adds their gradient rows in that order, one thread per channel; then
+ * one wave per label applies the LayerNorm backward -- statistics included in fp64, rounded once -- and stores.  The grid is ceil(num_labels / labels per
+ * workgroup): a function of the shape.  Known weak spot: one label's additions are one workgroup's, serially -- when
+ * most tokens share a label, that workgroup does most of the B H W row additions of the call.
+ * Workspace: none is used; a supported shape is sized 256 bytes (0 says "unsupported") and both entry points check
+ * what they are given.  Nothing in it is read.
+ * Deterministic: no atomics of any kind, no tickets; every sum is one thread's, in ascending position order: the
+ * bits of dtable are a function of (tokens, table, d_rows, shape) alone.  No allocation, no synchronisation, no
+ * data-dependent launch geometry, capturable in a graph.
+ * ---------------------------------------------------------------------------------------------- */
+size_t paella_embed_ln_train_workspace_bytes(int B, int H, int W, int c_in, int patch,
+                                             int num_labels); /* 0 for an unsupported shape */
+int paella_embed_ln_train_forward(const int64_t* tokens, const float* table, int B, int H, int W, int c_in, int patch,
+                                  int num_labels, float eps, float* rows_out, void* ws, size_t ws_bytes, void* stream);
+int paella_embed_ln_train_backward(const int64_t* tokens, const float* table, const float* d_rows, int B, int H, int W,
+                                   int c_in, int patch, int num_labels, float eps, float* dtable_out, void* ws,
+                                   size_t ws_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -274,6 +274,10 @@ SIGNATURES = {
                                                    c_void_p, c_void_p, c_size_t, c_void_p]),
     "paella_attn_train_backward_seed_dev": (c_int, [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int,
                                                     c_float, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_size_t, c_void_p]),
+    # training token stem (ABI 8, additive): embedding + LayerNorm + PixelUnshuffle, the forward by the eval engine's launch, the table's gradient in one launch
+    "paella_embed_ln_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int, c_int]),
+    "paella_embed_ln_train_forward": (c_int, [c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "paella_embed_ln_train_backward": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p, c_void_p, c_size_t, c_void_p]),
 }
 
 # exported for tests / tools only; declared in paella_amd/csrc/test_hooks.h, not in the public header
@@ -317,6 +321,7 @@ TEST_HOOKS = {
                                           c_void_p, c_size_t, c_void_p]),
     "paella_test_gemm_desc": (c_int, [POINTER(TestGemmArgs), c_int, c_int, c_void_p, c_size_t, c_void_p]),
     "paella_test_gemm_args_size": (c_size_t, []),
+    "paella_test_embed_ln_unshuffle": (c_int, [c_void_p, c_void_p, c_void_p, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_void_p]),
 }
 
 _lib = None

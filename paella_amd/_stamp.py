@@ -6,7 +6,7 @@ import hashlib
 import os
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
-SOURCES = ["gemm.hip", "elementwise.hip", "dwconv.hip", "attention.hip", "tail.hip", "vqgan.hip", "model.hip", "vqmodel.hip", "loss.hip", "grn_act.hip", "dwconv_train.hip", "attn_train.hip", "mod_train.hip", "optim.hip", "linear_train.hip", "train_seeds.hip"]
+SOURCES = ["gemm.hip", "elementwise.hip", "dwconv.hip", "attention.hip", "tail.hip", "vqgan.hip", "model.hip", "vqmodel.hip", "loss.hip", "grn_act.hip", "dwconv_train.hip", "attn_train.hip", "mod_train.hip", "optim.hip", "linear_train.hip", "train_seeds.hip", "embed_train.hip"]
 HEADERS = ["common.h", "internal.h", "gemm_device.h", "philox.h", "test_hooks.h", "train_common.h", os.path.join("..", "..", "include", "paella_hip.h")]
 
 

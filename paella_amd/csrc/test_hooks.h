@@ -139,6 +139,10 @@ int paella_test_renoise_scores(const int64_t* drawn, const float* logprob, const
                                uint64_t offset, int64_t row_offset, float t_next, int policy, float confidence_noise, const uint64_t* seeds, const int* step,
                                const float* t_next_tab, const int* active, const int* policy_tab, const float* noise_tab, const int64_t* pin_keep,
                                const int64_t* pin_tokens, const int* pin_on, int64_t* tokens_out, float* scores_out, void* stream);
+/* the inference engine's token stem launch alone (elementwise.hip: launch_embed_ln_unshuffle, as paella_unet_step issues it): out fp32 [B, H/patch, W/patch,
+ * c_in patch^2] from tokens int64 [B, H, W] and table fp32 [num_labels, c_in] -- what the rows of paella_embed_ln_train_forward are compared with, bit for bit */
+int paella_test_embed_ln_unshuffle(const int64_t* tokens, const float* table, float* out, int B, int H, int W, int c_in, int patch, int num_labels, float eps,
+                                   void* stream);
 #ifdef __cplusplus
 }
 #endif

@@ -479,7 +479,7 @@ class Paella(_NativeModel, nn.Module):
         return self
 
     def set_training_route(self, **settings):
-        """Several training switches in one call: any of activation=, depthwise=, attention=, modulation= ("torch" / "hip") and gemm= ("fp32" / "bf16"), each as its
+        """Several training switches in one call: any of activation=, depthwise=, attention=, modulation=, embedding= ("torch" / "hip") and gemm= ("fp32" / "bf16"), each as its
         `set_training_*` method takes it.  Every given setting is validated before any is stored: a refused call changes nothing."""
         unknown = sorted(set(settings) - set(_TRAIN_SWITCH))
         if unknown:
@@ -541,6 +541,17 @@ class Paella(_NativeModel, nn.Module):
         the down- / up-sampling convolutions, the embedding, the classifier and the loss head stay where they are.  Independent of the four switches above and of
         `set_gemm_precision`.  Eval mode -- the HIP inference engine -- never sees the switch."""
         return self._set_training("gemm", mode)
+
+    def set_training_embedding(self, mode):
+        """How the TRAIN-mode forward (`forward` and `forward_loss` after `model.train()`) runs the token stem -- the embedding lookup, its LayerNorm, the
+        PixelUnshuffle and the 1x1 convolution behind them: "torch" (default) is the chain of torch ops, op for op as before (under a seed table in pieces of
+        at most 3072 tokens, `paella_amd.training._token_embedding`); "hip" runs everything in front of the convolution as one HIP op in both directions
+        (`paella_amd.training.token_embed_layernorm`) when the module is on a cuda device, and the convolution as a linear over its rows (through
+        `set_training_gemm` where its shapes allow) -- the forward is the inference engine's stem launch, bit for bit, and the gradient of `in_mapper.0.weight`
+        is written whole by one launch that sums in ascending token order without atomics, sorts or library calls: a captured iteration (`GraphTrainStep`) holds
+        it at any token count, and its bits depend on the tensors alone.  Autograd keeps the tokens and nothing per token.  The op draws nothing.  Independent of
+        the five switches above.  Eval mode -- the HIP inference engine -- never sees the switch."""
+        return self._set_training("embedding", mode)
 
     def __del__(self):
         h = getattr(self, "_handle", None)

@@ -663,6 +663,76 @@ def pack_bf16(x, transposed=False, colsum=False):
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------------
+# Training token stem: F.embedding -> layer_norm -> pixel_unshuffle -> NHWC rows at the top of the network as ONE HIP op, forward and backward
+# (paella_amd/csrc/embed_train.hip, include/paella_hip.h "Training token stem").  The forward is the eval engine's launch; the backward writes the table's whole
+# gradient in one launch without atomics, sorts or library calls -- which is what lets a captured iteration hold it.  Autograd keeps the tokens and the reference
+# to the table and NOTHING per token: the statistics of a table row are recomputed once per label in the backward (saving two floats per token would buy nothing,
+# since the LayerNorm backward runs per label and not per token).
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
+EMBED_MAX_C, EMBED_MAX_LABELS, EMBED_MAX_POSITIONS = 1024, 65536, 2 ** 31 - 1
+# diagnostic: how often `token_embed_layernorm` ran and how many backward calls reached the library (tests, tools/bench_train_embedding.py)
+EMBED_COUNTERS = {"calls": 0, "backward": 0}
+
+
+class _TokenEmbedLayerNorm(torch.autograd.Function):
+    """(x int64 [B, H, W], weight [num_labels, c_in]) -> rows [B, H/p, W/p, c_in p^2]; saves x and weight."""
+
+    @staticmethod
+    def forward(ctx, x, weight, patch, eps):
+        B, H, W = x.shape
+        L, C = weight.shape
+        rows = weight.new_empty(B, H // patch, W // patch, C * patch * patch)
+        _call("paella_embed_ln_train_forward", weight.device, _lib.load().paella_embed_ln_train_workspace_bytes(B, H, W, C, patch, L), x, weight, B, H, W, C, patch, L, eps, rows)
+        ctx.save_for_backward(x, weight)
+        ctx.patch, ctx.eps = patch, eps
+        return rows
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_rows):
+        x, weight = ctx.saved_tensors
+        B, H, W = x.shape
+        L, C = weight.shape
+        (_, dw, _, _), wanted = _grad_outputs(ctx, None, weight, None, None)
+        if wanted:
+            d_rows = _aligned(d_rows.to(torch.float32).contiguous())
+            EMBED_COUNTERS["backward"] += 1
+            _call("paella_embed_ln_train_backward", weight.device, _lib.load().paella_embed_ln_train_workspace_bytes(B, H, W, C, ctx.patch, L), x, weight, d_rows,
+                  B, H, W, C, ctx.patch, L, ctx.eps, dw)
+        return None, dw, None, None
+
+
+def token_embed_layernorm(x, weight, patch=1, eps=1e-6):
+    """The token stem of the network in train mode as one op (src/modules.py:126-131, 271): the rows
+        rows[b, oy, ox, c p^2 + dy p + dx] = layer_norm(weight[x[b, oy p + dy, ox p + dx]], (c_in,), eps=eps)[c],        p = patch
+    i.e. F.pixel_unshuffle(F.layer_norm(F.embedding(x, weight), (c_in,), eps=eps).permute(0, 3, 1, 2), p) in NHWC memory -- the A operand of the 1x1 convolution
+    behind it as a linear.  x int64 [B, H, W], H and W multiples of patch, patch 1 or 2; weight fp32 [num_labels, c_in], `in_mapper.0.weight` used in place.  Returns
+    rows fp32 [B, H/p, W/p, c_in p^2], contiguous, bit for bit what the inference engine's stem launch gives.  Once differentiable in weight (x has no gradient):
+    the gradient is WRITTEN whole by the op, exact zeros in the rows of labels that do not occur, summed in ascending position order without atomics -- its bits depend on
+    (x, weight, the arriving gradient, the shape) alone.  Autograd keeps x and the reference to weight, nothing the size of the activations.  A token outside
+    [0, num_labels) is clamped into it in both directions, as the inference kernel clamps it.  c_in a multiple of 4 in 4...1024, num_labels in 1...65536, at most
+    2^31 - 1 output positions.  HIP only and exact fp32 only: anything else raises ValueError -- there is no torch fallback."""
+    _refuse_non_tensors("token_embed_layernorm", x, weight)
+    _refuse_dtypes("token_embed_layernorm", "int64 x and fp32 weight", (x, weight), (torch.int64, torch.float32))
+    _refuse_out_of_range("patch", patch, not isinstance(patch, bool) and isinstance(patch, int) and patch in (1, 2), "the fused token stem takes patch 1 or 2")
+    if x.dim() != 3 or weight.dim() != 2:
+        raise ValueError("x must be [B, H, W] and weight [num_labels, c_in] (got %s, %s)" % (tuple(x.shape), tuple(weight.shape)))
+    B, H, W = x.shape
+    L, C = weight.shape
+    if C % 4 or not 4 <= C <= EMBED_MAX_C:
+        raise ValueError("c_in = %d: the fused token stem takes a multiple of 4 in 4...%d" % (C, EMBED_MAX_C))
+    if not 1 <= L <= EMBED_MAX_LABELS:
+        raise ValueError("num_labels = %d: the fused token stem takes 1...%d" % (L, EMBED_MAX_LABELS))
+    if B < 1 or H < 1 or W < 1 or H % patch or W % patch or B * (H // patch) * (W // patch) > EMBED_MAX_POSITIONS:
+        raise ValueError("x %s: the fused token stem takes H and W multiples of patch = %d and 1...2^31 - 1 output positions" % (tuple(x.shape), patch))
+    eps = float(eps)
+    _refuse_out_of_range("eps", eps, 0.0 < eps < 1e30, "must be positive and finite")
+    _refuse_off_device("token_embed_layernorm", "x and weight", (x, weight))
+    EMBED_COUNTERS["calls"] += 1
+    return _TokenEmbedLayerNorm.apply(_aligned(x.contiguous()), _aligned(weight.contiguous()), patch, eps)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------------------------
 # Training optimizer step: clip_grad_norm_ + AdamW of every parameter as THREE launches over a device table of tensors (paella_amd/csrc/optim.hip,
 # include/paella_hip.h "Training optimizer step"): the gradients are read once for the norm, then p, g, m, v are read once and p, m, v written once.  The gradients
 # are never rewritten and nothing the size of the parameters is allocated.

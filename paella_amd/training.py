@@ -28,12 +28,16 @@ from .train_ops import ADAMW_COUNTERS, ClippedAdamW, adamw_chunk_plan, grad_norm
 from .train_ops import LINEAR_COUNTERS, LINEAR_GRAIN, LINEAR_MAX_DIM, linear_bf16, linear_shapes_ok, pack_bf16  # noqa: F401
 # the dropout seeds of a forward as device words (`forward_loss(..., seeds=)`, `GraphTrainStep`)
 from .train_ops import SEEDS_MAX_SITES, TrainSeeds  # noqa: F401
+# the token stem as one op (Paella.set_training_embedding("hip")): embedding + LayerNorm + PixelUnshuffle, its counters and its limits
+from .train_ops import EMBED_COUNTERS, EMBED_MAX_C, EMBED_MAX_LABELS, EMBED_MAX_POSITIONS, token_embed_layernorm  # noqa: F401
 
 # The training switches of `Paella`, one row each: the field of the per-forward plan, the name everything else derives from, and its two settings (off is the
 # default).  A new switch is a row here plus its branch in one block function below.  act = the middle of the MLP as one HIP op (`gelu_grn_dropout`), dw = the front
 # of a ResBlock (`dwconv_layernorm`), attn = the attention core of an AttnBlock (`attention_dropout`), mod = the JOINT between blocks (`timestep_modulate`: a
 # ResBlock / FeedForwardBlock in front of a TimestepBlock hands its two summands over unadded -- defer -- and the op's LayerNorm rows -- z -- go to the AttnBlock /
-# FeedForwardBlock behind it), gemm = the routed linears -- the two of every MLP and, on the attn branch, the three projections of an AttnBlock -- through `_linear`
+# FeedForwardBlock behind it), gemm = the routed linears -- the two of every MLP and, on the attn branch, the three projections of an AttnBlock -- through `_linear`,
+# stem = the token stem at the top of `_forward_features` (`token_embed_layernorm`: embedding + LayerNorm + PixelUnshuffle as one HIP op, the 1x1 convolution behind it
+# as a linear over its rows)
 class Switch(namedtuple("Switch", "field name off on")):
     __slots__ = ()
     attr = property(lambda self: "_train_" + self.name)             # the module attribute (pickled state)
@@ -47,7 +51,7 @@ class Switch(namedtuple("Switch", "field name off on")):
 
 
 TRAIN_SWITCHES = (Switch("act", "activation", "torch", "hip"), Switch("dw", "depthwise", "torch", "hip"), Switch("attn", "attention", "torch", "hip"),
-                  Switch("mod", "modulation", "torch", "hip"), Switch("gemm", "gemm", "fp32", "bf16"))
+                  Switch("mod", "modulation", "torch", "hip"), Switch("gemm", "gemm", "fp32", "bf16"), Switch("stem", "embedding", "torch", "hip"))
 # what `_forward_features` decides once per forward and hands down: per switch whether it ACTS, then train mode and the seed table
 _Plan = namedtuple("_Plan", tuple(s.field for s in TRAIN_SWITCHES) + ("training", "seeds"))
 
@@ -228,7 +232,8 @@ def _token_embedding(x, weight, chunked):
     The cause is NOT established: by the kernels it launches here the sorting form keeps its segment count behind a device pointer and should be capturable, so what is wrong with it in a captured
     graph -- in torch, in the sort / partition library or in the graph runtime -- is an open question, and the pieces are a way round it, not a fix.  The weight's
     gradient is then the sum of the pieces' gradients: the values of the one-piece call in another summation order.  Up to EMBEDDING_CHUNK tokens the call is
-    F.embedding itself."""
+    F.embedding itself.  Paella.set_training_embedding("hip") takes the whole stem off this path: `token_embed_layernorm` writes the weight's gradient in one launch
+    that a graph holds at any token count, and this function is then not reached, with or without seeds."""
     if not chunked or x.numel() <= EMBEDDING_CHUNK:
         return F.embedding(x, weight)
     pieces = [F.embedding(piece, weight) for piece in x.reshape(-1).split(EMBEDDING_CHUNK)]
@@ -239,7 +244,9 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
     """Paella.forward (src/modules.py:263-275) as autograd-tracked torch ops, up to and including the LayerNorm2d in front of out_mapper's convolution:
     [B, c_out, H, W] as the permuted view of an NHWC tensor that `_ln_nchw` returns.  seeds (a `TrainSeeds`): every HIP dropout op call with p > 0 takes the
     table's next word as its seed, in forward order (`dropout_sites` counts them); a call at p = 0 and the torch routes consume none.  Under seeds the token
-    embedding of more than EMBEDDING_CHUNK tokens is looked up in pieces (`_token_embedding`): the one difference from the forward without seeds."""
+    embedding of more than EMBEDDING_CHUNK tokens is looked up in pieces (`_token_embedding`): the one difference from the forward without seeds -- and none with
+    plan.stem (Paella.set_training_embedding("hip"), train mode on a cuda device), where the stem up to the 1x1 convolution's input is one HIP op in both directions
+    (`token_embed_layernorm`) and the convolution a linear over its rows."""
     if seeds is not None:
         seeds.begin()
     cfg = model._cfg
@@ -254,9 +261,15 @@ def _forward_features(model, x, r, byt5, clip=None, clip_image=None, x_cat=None,
     c_embed = c_embeddings(model, byt5, clip, clip_image)
     patch = cfg["patch_size"]
 
-    h = F.layer_norm(_token_embedding(x, model.in_mapper._modules["0"].weight, seeds is not None), (cfg["c_in"],), None, None, 1e-6).permute(0, 3, 1, 2)
     emb = model.embedding._modules["1"]
-    h = _ln_nchw(F.conv2d(F.pixel_unshuffle(h, patch), emb.weight, emb.bias))
+    if plan.stem:
+        rows = token_embed_layernorm(x, model.in_mapper._modules["0"].weight, patch)         # [B, H/p, W/p, c_in p^2]
+        h = _linear(rows, emb.weight.view(emb.weight.size(0), -1), emb.bias, plan.gemm)     # the 1x1 convolution as a linear
+        # the NCHW view of NHWC memory: plan.dw's channels_last copy below is then a no-op
+        h = F.layer_norm(h, (emb.weight.size(0),), None, None, 1e-6).permute(0, 3, 1, 2)
+    else:
+        h = F.layer_norm(_token_embedding(x, model.in_mapper._modules["0"].weight, seeds is not None), (cfg["c_in"],), None, None, 1e-6).permute(0, 3, 1, 2)
+        h = _ln_nchw(F.conv2d(F.pixel_unshuffle(h, patch), emb.weight, emb.bias))
 
     if plan.dw:  # the trunk is made channels_last once, here, so that the blocks hand each other NHWC memory
         h = h.contiguous(memory_format=torch.channels_last)
@@ -359,10 +372,13 @@ class GraphTrainStep:
     branches); the seed table is put back to its state from before the warm-up after both.  Weights, optimizer state and step counts are untouched, and the first
     replay draws the words of iteration 1.  After the capture p.grad of every parameter is a tensor owned by the graph that each replay rewrites: there is no
     zero_grad in the loop (a p.grad that was replaced or set to None is put back before the next replay).
-    Staleness, as `GraphSampler`: before a replay the data_ptr of every parameter and optimizer state tensor, the five training switches, `model.dropout`
+    Staleness, as `GraphSampler`: before a replay the data_ptr of every parameter and optimizer state tensor, the six training switches, `model.dropout`
     and train mode are compared with what the capture saw; on a difference the step is captured again (on_stale="recapture"; `.captures` counts) or a RuntimeError
     names the cause (on_stale="raise").  The call counters of the ops (ATTN_COUNTERS, MOD_COUNTERS, LINEAR_COUNTERS, ...) and ADAMW_COUNTERS count Python calls: they
     move at capture time only, never at a replay.
+    The token embedding: under the default `set_training_embedding("torch")` a captured forward of more than EMBEDDING_CHUNK tokens looks the tokens up in pieces
+    (`_token_embedding`); under `set_training_embedding("hip")` the stem is `token_embed_layernorm` -- one forward and one backward launch at any token count, no
+    pieces and no torch embedding backward in the graph.
     Not offered: gradient accumulation inside the graph, DDP, GradScaler / autocast, the `attn_weights` branch."""
 
     def __init__(self, model, optimizer, example_inputs, *, label_smoothing=0.1, seed=None, on_stale="recapture"):
