@@ -137,20 +137,9 @@ class GraphInpainter(GraphSampler):
         return select_tokens(toks, self._known, self.mask) if self.keep_known and self.pin == "final" else toks
 
     def __call__(self, images=None, mask=None, model_inputs=None, unconditional_inputs=None, seed=None, shard=None):
-        """Replay; returns (tokens, image) in graph-owned buffers."""
-        self._check_fresh()
-        if images is not None:
-            if tuple(images.shape) != tuple(self.images.shape):
-                raise ValueError("image shape differs from the captured one")
-            self.images.copy_(images)
-        if mask is not None:
-            if tuple(mask.shape) != tuple(self.mask.shape):
-                raise ValueError("mask shape differs from the captured one")
-            self.mask.copy_(mask)
-        if model_inputs is not None:
-            self._copy_inputs(self.cond, model_inputs)
-        if unconditional_inputs is not None:
-            self._copy_inputs(self.uncond, unconditional_inputs)
+        """Replay; returns (tokens, image) in graph-owned buffers.  Images, mask and both conditioning sets are matched against the captured shapes before any is
+        copied: a refused call (ValueError) leaves the graph's buffers as they were."""
+        self._refresh(model_inputs, unconditional_inputs, grids=(("image", self.images, images), ("mask", self.mask, mask)))
         self._set_words(seed, shard)
         self.graph.replay()
         return self.out

@@ -43,7 +43,96 @@ _nn_module.register_module_module_registration_hook(_count_registration)
 
 
 class _NativeModel:
-    """What `Paella` and `VQModel` share around their native handle: the weight signature, `refresh()`, and copy / pickle semantics (mixed in before nn.Module)."""
+    """What `Paella` and `VQModel` share around their native handle (mixed in before nn.Module): the engine's life -- created on first use, reloaded when the
+    weight signature changed, switched between the precision modes, destroyed with the module -- its scratch workspace, the weight signature, `refresh()`, and
+    copy / pickle semantics.  A class brings `_abi`, the prefix of its entry-point family in libpaella_hip.so, `_device()`, where its device is read from, and
+    `_create()`, which makes the native model from the class's configuration."""
+
+    _abi = None
+
+    def _init_engine(self):
+        """no native model yet: `_engine()` builds it on first use"""
+        self._handle = None
+        self._loaded_sig = None
+        self._load_gen = 0
+        self._ws = None
+        self._precision = 0
+
+    def _native(self, name):
+        """the entry point `<_abi>_<name>` of the library"""
+        return getattr(_lib.load(), "%s_%s" % (self._abi, name))
+
+    def _require_hip(self):
+        dev = self._device()
+        if dev.type != "cuda":
+            raise RuntimeError("paella_amd.%s executes only on a HIP device (module is on '%s'); move it with .to('cuda'). There is no CPU fallback."
+                               % (type(self).__name__, dev))
+        return dev
+
+    def _engine(self):
+        """Create / refresh the native model: (re)load every tensor when parameters moved or changed."""
+        dev = self._require_hip()
+        _lib.load()
+        sig = self._signature()
+        if self._handle is not None and sig == self._loaded_sig:
+            return self._handle
+        with torch.cuda.device(dev):
+            st = _lib.stream_ptr(dev)
+            if self._handle is None:
+                self._handle = self._create()
+                if self._precision:
+                    _lib.check(self._native("set_precision")(self._handle, self._precision, st))
+            load_tensor = self._native("load_tensor")
+            for key, t in self.state_dict().items():
+                if key.endswith("num_batches_tracked"):  # (torch's BatchNorm counter: no weight)
+                    continue
+                t = t.detach()
+                if t.dtype != torch.float32 or not t.is_contiguous():
+                    t = t.float().contiguous()
+                shape = (ctypes.c_int64 * t.dim())(*t.shape)
+                _lib.check(load_tensor(self._handle, key.encode(), _lib.ptr(t), shape, t.dim(), st))
+            _lib.check(self._native("finalize")(self._handle, st))
+            torch.cuda.current_stream(dev).synchronize()  # staging copies above may be temporaries
+        self._loaded_sig = sig
+        self._load_gen = next(_LOAD_GENS)
+        return self._handle
+
+    def set_gemm_precision(self, mode):
+        modes = {"fp32": 0, "f32": 0, "bf16": 1}
+        if mode not in modes:
+            raise ValueError("gemm precision must be 'fp32' or 'bf16'")
+        self._precision = modes[mode]
+        if self._handle is not None:
+            dev = self._require_hip()
+            with torch.cuda.device(dev):
+                _lib.check(self._native("set_precision")(self._handle, self._precision, _lib.stream_ptr(dev)))
+        self._ws = None
+        return self
+
+    def get_gemm_precision(self):
+        return "bf16" if self._precision == 1 else "fp32"
+
+    def __del__(self):
+        h = getattr(self, "_handle", None)
+        if h is not None:
+            try:
+                self._native("destroy")(h)
+            except Exception:
+                pass
+
+    def _workspace(self, nbytes, ws=None):
+        """The module's own scratch workspace (grown on demand), or a caller-owned one (`ws`, from `new_workspace`): anything
+        that outlives the call -- a captured HIP graph above all -- must bring its own, because growing the module's
+        workspace frees the old buffer."""
+        dev = self._device()
+        if ws is not None:
+            if ws.device != dev or ws.dtype != torch.uint8 or ws.numel() < nbytes:
+                raise ValueError("workspace too small or on the wrong device (%d bytes needed)" % nbytes)
+            return ws
+        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != dev:
+            self._ws = None
+            self._ws = _lib.new_workspace(nbytes, dev)
+        return self._ws
 
     def _signature(self):
         """What `_engine`, `GraphSampler` and `RequestStream` compare to notice a weight change: (data_ptr, version) of every parameter and buffer, behind a count
@@ -340,11 +429,7 @@ class Paella(_NativeModel, nn.Module):
         self.out_mapper = _seq(**{"1": _Holder(weight=_p(num_labels, c_out, 1, 1))})
 
         self.reset_parameters()
-        self._handle = None
-        self._loaded_sig = None
-        self._load_gen = 0
-        self._ws = None
-        self._precision = 0
+        self._init_engine()
         for sw in TRAIN_SWITCHES:
             setattr(self, sw.attr, sw.off)
         # Constructed in EVAL mode (an nn.Module normally starts in train mode): eval = the hand-written HIP engine, which is what
@@ -389,63 +474,36 @@ class Paella(_NativeModel, nn.Module):
     def _device(self):
         return self.in_mapper._modules["0"].weight.device
 
-    def _require_hip(self):
-        dev = self._device()
-        if dev.type != "cuda":
-            raise RuntimeError("paella_amd.Paella executes only on a HIP device (module is on '%s'); "
-                               "move it with .to('cuda'). There is no CPU fallback." % dev)
-        return dev
+    _abi = "paella_unet"
 
-    def _engine(self):
-        """Create / refresh the native model: (re)load every tensor when parameters moved or changed."""
-        dev = self._require_hip()
-        lib = _lib.load()
-        sig = self._signature()
-        if self._handle is not None and sig == self._loaded_sig:
-            return self._handle
-        with torch.cuda.device(dev):
-            if self._handle is None:
-                cfg = self._cfg
-                c = _lib.UnetConfig()
-                for k in ("c_in", "c_out", "num_labels", "c_r", "patch_size", "c_cond", "clip_embd", "byt5_embd",
-                          "clip_seq_len", "kernel_size"):
-                    setattr(c, k, int(cfg[k]))
-                c.self_attn = int(cfg["self_attn"])
-                n = len(cfg["c_hidden"])
-                if n > _lib.MAX_LEVELS:
-                    raise ValueError("too many levels")
-                c.n_levels = n
-                for i in range(n):
-                    c.c_hidden[i] = int(cfg["c_hidden"][i])
-                    c.nhead[i] = int(cfg["nhead"][i])
-                    c.blocks[i] = int(cfg["blocks"][i])
-                    lc = cfg["level_config"][i].encode()
-                    if len(lc) >= _lib.MAX_BLOCK_TYPES:
-                        raise ValueError("level_config entry too long")
-                    c.level_config[i].value = lc
-                h = ctypes.c_void_p()
-                _lib.check(lib.paella_unet_create(ctypes.byref(c), ctypes.byref(h)))
-                self._handle = h
-                # frequencies computed with torch exactly as the reference does (src/modules.py:214-216)
-                half = cfg["c_r"] // 2
-                emb = math.log(10000) / (half - 1)
-                freqs = torch.arange(half).float().mul(-emb).exp().contiguous()
-                arr = (ctypes.c_float * half)(*freqs.tolist())
-                _lib.check(lib.paella_unet_set_timestep_freqs(self._handle, arr, half))
-                if self._precision:
-                    _lib.check(lib.paella_unet_set_precision(self._handle, self._precision, _lib.stream_ptr(dev)))
-            st = _lib.stream_ptr(dev)
-            for key, t in self.state_dict().items():
-                t = t.detach()
-                if t.dtype != torch.float32 or not t.is_contiguous():
-                    t = t.float().contiguous()
-                shape = (ctypes.c_int64 * t.dim())(*t.shape)
-                _lib.check(lib.paella_unet_load_tensor(self._handle, key.encode(), _lib.ptr(t), shape, t.dim(), st))
-            _lib.check(lib.paella_unet_finalize(self._handle, st))
-            torch.cuda.current_stream(dev).synchronize()  # staging copies above may be temporaries
-        self._loaded_sig = sig
-        self._load_gen = next(_LOAD_GENS)
-        return self._handle
+    def _create(self):
+        cfg = self._cfg
+        c = _lib.UnetConfig()
+        for k in ("c_in", "c_out", "num_labels", "c_r", "patch_size", "c_cond", "clip_embd", "byt5_embd",
+                  "clip_seq_len", "kernel_size"):
+            setattr(c, k, int(cfg[k]))
+        c.self_attn = int(cfg["self_attn"])
+        n = len(cfg["c_hidden"])
+        if n > _lib.MAX_LEVELS:
+            raise ValueError("too many levels")
+        c.n_levels = n
+        for i in range(n):
+            c.c_hidden[i] = int(cfg["c_hidden"][i])
+            c.nhead[i] = int(cfg["nhead"][i])
+            c.blocks[i] = int(cfg["blocks"][i])
+            lc = cfg["level_config"][i].encode()
+            if len(lc) >= _lib.MAX_BLOCK_TYPES:
+                raise ValueError("level_config entry too long")
+            c.level_config[i].value = lc
+        h = ctypes.c_void_p()
+        _lib.check(self._native("create")(ctypes.byref(c), ctypes.byref(h)))
+        # frequencies computed with torch exactly as the reference does (src/modules.py:214-216)
+        half = cfg["c_r"] // 2
+        emb = math.log(10000) / (half - 1)
+        freqs = torch.arange(half).float().mul(-emb).exp().contiguous()
+        arr = (ctypes.c_float * half)(*freqs.tolist())
+        _lib.check(self._native("set_timestep_freqs")(h, arr, half))
+        return h
 
     def set_gemm_precision(self, mode):
         """OPT-IN fast mode of THIS model, outside the fp32 parity contract (include/paella_hip.h: paella_unet_set_precision): "bf16" runs the
@@ -453,19 +511,7 @@ class Paella(_NativeModel, nn.Module):
         consumer GEMMs; residual stream, statistics, attention, logits and the sampling tail stay fp32); "fp32" (default) is the exact path,
         bit for bit.  Objects that captured the model's launches or sized a workspace before the switch (`GraphSampler`, `new_workspace`)
         must be rebuilt after it."""
-        modes = {"fp32": 0, "f32": 0, "bf16": 1}
-        if mode not in modes:
-            raise ValueError("gemm precision must be 'fp32' or 'bf16'")
-        self._precision = modes[mode]
-        if self._handle is not None:
-            dev = self._require_hip()
-            with torch.cuda.device(dev):
-                _lib.check(_lib.load().paella_unet_set_precision(self._handle, self._precision, _lib.stream_ptr(dev)))
-        self._ws = None
-        return self
-
-    def get_gemm_precision(self):
-        return "bf16" if self._precision == 1 else "fp32"
+        return super().set_gemm_precision(mode)
 
     def _set_training(self, name, mode, store=True):
         """validate `mode` against the switch's row of `paella_amd.training.TRAIN_SWITCHES` and (store) keep it"""
@@ -552,28 +598,6 @@ class Paella(_NativeModel, nn.Module):
         it at any token count, and its bits depend on the tensors alone.  Autograd keeps the tokens and nothing per token.  The op draws nothing.  Independent of
         the five switches above.  Eval mode -- the HIP inference engine -- never sees the switch."""
         return self._set_training("embedding", mode)
-
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h is not None:
-            try:
-                _lib.load().paella_unet_destroy(h)
-            except Exception:
-                pass
-
-    def _workspace(self, nbytes, ws=None):
-        """The module's own scratch workspace (grown on demand), or a caller-owned one (`ws`, from `new_workspace`): anything
-        that outlives the call -- a captured HIP graph above all -- must bring its own, because growing the module's
-        workspace frees the old buffer."""
-        dev = self._device()
-        if ws is not None:
-            if ws.device != dev or ws.dtype != torch.uint8 or ws.numel() < nbytes:
-                raise ValueError("workspace too small or on the wrong device (%d bytes needed)" % nbytes)
-            return ws
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != dev:
-            self._ws = None
-            self._ws = _lib.new_workspace(nbytes, dev)
-        return self._ws
 
     def workspace_bytes(self, B, H, W, S):
         """Bytes of workspace one forward (and the conditioning preparation) of this shape needs."""

@@ -22,6 +22,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._graph import GraphOwner
 from .modules import MAX_REGIONS, CondCache, KeyWeights, Paella, RegionTables, region_query_groups, region_query_total
 
 
@@ -834,28 +835,20 @@ def sample_requests(model, model_inputs, unconditional_inputs, latent_shape, see
                         conf=ConfidenceTables(chost, device) if chost[2] else None)
 
 
-def _capture_graph(owner, run):
-    """run() captured into a HIP graph on owner.device -> what run() returned inside the capture; sets owner.graph and owner._captured_state, counts owner.captures"""
-    dev = owner.device
-    side = torch.cuda.Stream(device=dev)
-    side.wait_stream(torch.cuda.current_stream(dev))
-    with torch.cuda.stream(side):
-        for _ in range(2):  # warm-up: weights (re)loaded, workspaces sized, allocator pools populated
-            run()
-    torch.cuda.current_stream(dev).wait_stream(side)
-    torch.cuda.synchronize(dev)
-    state = owner._state()  # AFTER the warm-up: the engines are loaded with exactly these tensors
-    graph = torch.cuda.CUDAGraph()
-    # thread_local: a process-group watchdog thread polling events must not invalidate the capture
-    with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-        out = run()
-    torch.cuda.synchronize(dev)
-    owner.graph, owner._captured_state = graph, state
-    owner.captures += 1
-    return out
+class _EngineGraph(GraphOwner):
+    """A captured graph of the inference engines' launches (`GraphSampler`, `RequestStream`): besides the shapes it depends on the weights and the precision mode
+    of `self.model` and, where there is one, of `self.vqgan`."""
+
+    _stale_hint = "load_state_dict / optimizer step / .to() / set_gemm_precision"
+
+    def _state(self):
+        st = [("denoiser weights", self.model._signature()), ("denoiser gemm precision", self.model._precision)]
+        if self.vqgan is not None:
+            st += [("VQGAN weights", self.vqgan._signature()), ("VQGAN gemm precision", self.vqgan._precision)]
+        return st
 
 
-class GraphSampler:
+class GraphSampler(_EngineGraph):
     """The whole `sample()` call (conditioning prep, all denoising steps, sampling tails; optionally the VQGAN
     decode) captured ONCE into a HIP graph for fixed shapes and replayed per request.
 
@@ -879,13 +872,12 @@ class GraphSampler:
     def __init__(self, model, model_inputs, unconditional_inputs, latent_shape, steps=12, renoise_steps=11, temperature=(1.0, 0.2),
                  cfg=8.0, t_start=1.0, t_end=0.0, device="cuda", vqgan=None, attn_weights=None, on_stale="recapture", *, top_k=None, top_p=None, typical_mass=None,
                  min_tokens=1, renoise="random", confidence_noise=0.0, return_stats=False):
-        if on_stale not in ("recapture", "raise"):
-            raise ValueError("on_stale must be 'recapture' or 'raise'")
+        self._init_owner(on_stale)
         # confidence-ordered renoise / statistics, one setting baked into the capture (None = today's capture)
         self.conf = _call_renoise("philox", linspace_schedule(temperature[0], temperature[1], steps), renoise, confidence_noise, return_stats)
         if not hasattr(self, "filt"):  # truncated sampling, one setting baked into the capture (GraphRequestSampler keeps device tables here instead)
             self.filt = _call_filter("philox", linspace_schedule(temperature[0], temperature[1], steps), top_k, top_p, typical_mass, min_tokens)
-        self.model, self.vqgan, self.device, self.on_stale = model, vqgan, torch.device(device), on_stale
+        self.model, self.vqgan, self.device = model, vqgan, torch.device(device)
         self.shape = tuple(int(v) for v in latent_shape)
         self.kw = dict(steps=steps, renoise_steps=renoise_steps, temperature=temperature, cfg=cfg, t_start=t_start, t_end=t_end)
         self.attn_weights = attn_weights
@@ -896,15 +888,7 @@ class GraphSampler:
         self.row_offset_dev = torch.zeros(1, dtype=torch.int64, device=self.device)  # lo * H * W of the shard being sampled
         self.init_noise = torch.zeros(self.shape, dtype=torch.int64, device=self.device)
         self.r_all = timestep_table(linspace_schedule(t_start, t_end, steps + 1), steps, self.shape[0], self.device)
-        self.captures = 0
         self._capture()
-
-    # ---- what a capture depends on besides the shapes
-    def _state(self):
-        st = [("denoiser weights", self.model._signature()), ("denoiser gemm precision", self.model._precision)]
-        if self.vqgan is not None:
-            st += [("VQGAN weights", self.vqgan._signature()), ("VQGAN gemm precision", self.vqgan._precision)]
-        return st
 
     def _capture(self):
         # The graph bakes raw pointers: it owns its workspaces (the modules' own scratch is dropped and reallocated whenever a
@@ -914,7 +898,7 @@ class GraphSampler:
         self.graph = self.out = None
         self.ws = _lib.new_workspace(self.model.workspace_bytes(2 * B, H, W, S), self.device)
         self.vq_ws = None if self.vqgan is None else _lib.new_workspace(self.vqgan.workspace_bytes(B, H, W), self.device)
-        self.out = _capture_graph(self, self._run)
+        self.out = self._capture_graph(self._run)
 
     def _schedule(self):
         """(t_list, temperatures, per-step guidance pairs) of the src/utils.py:35 signature"""
@@ -949,11 +933,14 @@ class GraphSampler:
         return (toks, self.vqgan.decode_indices(toks, ws=self.vq_ws), *stats)
 
     @staticmethod
-    def _copy_inputs(dst, src):
+    def _match_inputs(dst, src):
+        """a call's conditioning set `src` against the captured one `dst` -> the (buffer, tensor) pairs to copy.  Nothing is copied here: a refused set raises
+        ValueError and leaves every buffer as it was"""
         if dst is None:
             if src is not None:
                 raise ValueError("the graph was captured without this conditioning set")
-            return
+            return []
+        todo = []
         for key, d in dst.items():
             s = src.get(key) if src is not None else None
             if d is None:
@@ -963,33 +950,30 @@ class GraphSampler:
             if isinstance(d, (list, tuple)):
                 if not isinstance(s, (list, tuple)) or len(s) != len(d) or any(a.shape != b.shape for a, b in zip(d, s)):
                     raise ValueError("conditioning layout differs from the captured one (%s: list length / shapes)" % key)
-                for a, b in zip(d, s):
-                    a.copy_(b)
+                todo.extend(zip(d, s))
             else:
                 if s is None or isinstance(s, (list, tuple)) or s.shape != d.shape:
                     raise ValueError("conditioning shape differs from the captured one (%s)" % key)
-                d.copy_(s)
+                todo.append((d, s))
+        return todo
 
-    def _stale(self):
-        """what the capture depends on and has changed since, by name (empty: the capture is fresh)"""
-        return [a[0] for a, b in zip(self._state(), self._captured_state) if a != b]
-
-    def _check_fresh(self):
-        causes = self._stale()
-        if not causes:
-            return
-        if self.on_stale == "raise":
-            raise RuntimeError("GraphSampler: the captured graph is stale -- changed since the capture: %s (load_state_dict / optimizer step / .to() / set_gemm_precision). "
-                               "Build a new GraphSampler or construct it with on_stale='recapture'." % ", ".join(causes))
-        self._capture()
-
-    def _refresh(self, model_inputs, unconditional_inputs):
-        """what every replay starts with: a capture that matches the weights, then this call's conditioning in the graph's input buffers (None = keep)"""
+    def _refresh(self, model_inputs, unconditional_inputs, grids=()):
+        """what every replay starts with: a capture that matches the weights, then this call's inputs in the graph's input buffers (None = keep).  grids: (name,
+        buffer, tensor or None) of what the capture holds besides the conditioning (GraphInpainter: images and mask).  Every given input is matched against
+        the captured layout before any is copied: a refused call leaves the buffers as they were."""
         self._check_fresh()
+        todo = []
+        for name, d, s in grids:
+            if s is not None:
+                if tuple(s.shape) != tuple(d.shape):
+                    raise ValueError("%s shape differs from the captured one" % name)
+                todo.append((d, s))
         if model_inputs is not None:
-            self._copy_inputs(self.cond, model_inputs)
+            todo += self._match_inputs(self.cond, model_inputs)
         if unconditional_inputs is not None:
-            self._copy_inputs(self.uncond, unconditional_inputs)
+            todo += self._match_inputs(self.uncond, unconditional_inputs)
+        for d, s in todo:  # only after every input was accepted
+            d.copy_(s)
 
     def _set_words(self, seed, shard):
         if seed is None:
@@ -1006,7 +990,8 @@ class GraphSampler:
         """Replay. Returns tokens (and the decoded image if a VQGAN was given); outputs live in graph-owned buffers that
         the next replay overwrites.  seed=None draws a fresh seed from torch's CPU generator; the start tokens and all per-step
         noise are functions of the seed and of the GLOBAL row: shard=(lo, total) makes this replay rows [lo, lo + B) of a
-        global batch of `total` (bit-identical to those rows of the unsharded call with the same seed)."""
+        global batch of `total` (bit-identical to those rows of the unsharded call with the same seed).  Conditioning that does not match the captured layout
+        raises ValueError before anything is copied: the graph's buffers stay as the last accepted call left them."""
         self._refresh(model_inputs, unconditional_inputs)
         self._set_words(seed, shard)
         self.graph.replay()
@@ -1179,7 +1164,7 @@ def check_request_rows(rows, max_cond_rows, what):
     return rows
 
 
-class RequestStream:
+class RequestStream(_EngineGraph):
     """Continuous request batching: a fixed-shape batch of B SLOTS whose requests join and leave at step boundaries.  Every request has its own seed, step count,
     renoise count, temperature and guidance schedule, timestep range and optionally its own start tokens (`init_x` with `t_start` -- the denoising part of an
     image-to-image request); ONE captured graph of a single tick (`request_step` -> the stream form of `forward_sample`) is replayed while they come and go.
@@ -1247,11 +1232,10 @@ class RequestStream:
 
     def __init__(self, model, model_inputs, unconditional_inputs, latent_shape, max_steps=12, guided=True, device="cuda", vqgan=None, attn_weights=None,
                  on_stale="recapture", max_cond_rows=None, editing=False, max_attn_weights=None, filtering=False, max_regions=None, confidence=False):
-        if on_stale not in ("recapture", "raise"):
-            raise ValueError("on_stale must be 'recapture' or 'raise'")
+        self._init_owner(on_stale)
         if not isinstance(model, Paella):
             raise TypeError("RequestStream needs a paella_amd.Paella model")
-        self.model, self.vqgan, self.device, self.on_stale = model, vqgan, torch.device(device), on_stale
+        self.model, self.vqgan, self.device = model, vqgan, torch.device(device)
         if self.device.type != "cuda":
             raise RuntimeError("paella_amd.RequestStream runs on a HIP device only (got device=%s); there is no CPU path" % self.device)
         self.shape = tuple(int(v) for v in latent_shape)
@@ -1327,7 +1311,6 @@ class RequestStream:
             self._never = torch.full((B,), -1.0, dtype=torch.float32, device=dev)  # the threshold table of the statistics tail: the renoise stage renoises
             if self.logits is None:
                 self.logits = torch.empty(B, H, W, model.num_labels, dtype=torch.float32, device=dev)
-        self.captures = 0
         self._capture()
 
     # ---- slots
@@ -1367,8 +1350,6 @@ class RequestStream:
                      self.random_x, (self.filter_k, self.filter_mass), pin=pin,
                      conf=(self._never, self.policy, self.confidence_noise, self.logprob, self.entropy) if self.confidence else None)
 
-    _state = GraphSampler._state
-
     def _capture(self):
         """only with no request in flight: every slot is then idle on the device, and an idle tick stores nothing and moves no cursor -- the warm-up ticks and the
         capture itself leave the state (finished tokens waiting for `result` included) as it is"""
@@ -1377,21 +1358,12 @@ class RequestStream:
         self.graph = None
         self.ws = _lib.new_workspace(self.model.workspace_bytes(self.cache.B, H, W, self.S), self.device)
         self.vq_ws = None if self.vqgan is None else _lib.new_workspace(self.vqgan.workspace_bytes(1, H, W), self.device)
-        _capture_graph(self, torch.inference_mode()(self._tick_launches))
+        self._capture_graph(torch.inference_mode()(self._tick_launches))
 
-    _stale = GraphSampler._stale
-
-    def _check_fresh(self):
-        causes = ", ".join(self._stale())
-        if not causes:
-            return
+    def _refuse_recapture(self, causes):
         if self.active:
             raise RuntimeError("RequestStream: %s changed with %d request(s) in flight -- their conditioning was prepared with the old state; let the stream run "
-                               "empty before load_state_dict / set_gemm_precision, or abandon them with reset()" % (causes, len(self.active)))
-        if self.on_stale == "raise":
-            raise RuntimeError("RequestStream: the captured graph is stale -- changed since the capture: %s.  Build a new RequestStream or construct it with "
-                               "on_stale='recapture'." % causes)
-        self._capture()
+                               "empty before load_state_dict / set_gemm_precision, or abandon them with reset()" % (", ".join(causes), len(self.active)))
 
     # ---- requests
     def _check_inputs(self, inputs, what):

@@ -18,6 +18,8 @@ from collections import namedtuple
 import torch
 import torch.nn.functional as F
 
+from ._graph import GraphOwner
+
 # the training ops and their limits live in train_ops.py; the network below calls them through THESE module globals (which is also where tests and tools look)
 from .train_ops import (ACT_MAX_B, ACT_MAX_C, ACT_MAX_P, ATTN_COUNTERS, ATTN_MAX_B, ATTN_MAX_HEADS, ATTN_MAX_L, ATTN_MAX_P, ATTN_MAX_ROWS, DW_COUNTERS,  # noqa: F401
                         DW_MAX_C, DW_MAX_C_SKIP, DW_MAX_POSITIONS, HEAD_MAX_K, HEAD_MAX_LABELS, HEAD_MAX_ROWS, MOD_COUNTERS, MOD_MAX_B, MOD_MAX_C, MOD_MAX_P,
@@ -349,7 +351,7 @@ def dropout_sites(model):
 _STEP_INPUTS = ("noised", "t", "latents", "byt5", "clip", "clip_image", "x_cat", "loss_weight")
 
 
-class GraphTrainStep:
+class GraphTrainStep(GraphOwner):
     """One whole training iteration of src/train.py:59-69 -- `forward_loss`, the loss reduction, `backward()`, clip_grad_norm_ + AdamW (`ClippedAdamW`) -- captured
     ONCE into a HIP graph for fixed shapes and replayed per call: the same kernels as the eager iteration plus one launch that advances the dropout seeds, submitted
     as one graph instead of some two thousand launches.
@@ -381,15 +383,16 @@ class GraphTrainStep:
     pieces and no torch embedding backward in the graph.
     Not offered: gradient accumulation inside the graph, DDP, GradScaler / autocast, the `attn_weights` branch."""
 
+    _noun = "captured iteration"
+
     def __init__(self, model, optimizer, example_inputs, *, label_smoothing=0.1, seed=None, on_stale="recapture"):
-        if on_stale not in ("recapture", "raise"):
-            raise ValueError("on_stale must be 'recapture' or 'raise'")
+        self._init_owner(on_stale)
         if not isinstance(optimizer, ClippedAdamW):
             raise TypeError("GraphTrainStep captures the HIP optimizer step: the optimizer must be a paella_amd.training.ClippedAdamW (got %s)" % type(optimizer).__name__)
         params = [p for p in model.parameters()]
         if not params or not all(p.is_cuda for p in params):
             raise ValueError("GraphTrainStep runs on the HIP device only: move the model to a cuda device first")
-        self.model, self.optimizer, self.on_stale, self.label_smoothing = model, optimizer, on_stale, float(label_smoothing)
+        self.model, self.optimizer, self.label_smoothing = model, optimizer, float(label_smoothing)
         self.device = params[0].device
         self._refuse_eval()
         unknown = sorted(set(example_inputs) - set(_STEP_INPUTS))
@@ -401,7 +404,6 @@ class GraphTrainStep:
         clone = lambda v: [t.detach().to(self.device).clone() for t in v] if isinstance(v, (list, tuple)) else v.detach().to(self.device).clone()
         self.inputs = {k: clone(v) for k, v in example_inputs.items() if v is not None}
         self.seeds = TrainSeeds(max(dropout_sites(model), 1), seed, self.device)
-        self.captures = 0
         self.graph = self.out = None
         self._capture()
 
@@ -444,46 +446,26 @@ class GraphTrainStep:
 
     def _capture(self):
         self._refuse_eval()
-        dev, opt, m = self.device, self.optimizer, self.model
+        opt, m = self.optimizer, self.model
         if self.seeds.n_sites < dropout_sites(m):           # a switch or model.dropout added drawing calls since the table was sized: `.seeds` grows in place
             self.seeds.grow(dropout_sites(m))
+        before = getattr(self, "_captured_state", None), self.captures
         self.graph = self.out = self._plan = None
         self._grads = []
         opt.materialize_state()
         snap = self.seeds.snapshot()
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):
-            self._iteration(optimize=False)               # warm-up: no optimizer step, nothing but gradients is written
-        torch.cuda.current_stream(dev).wait_stream(side)
-        self.seeds.restore(snap)
-        m.zero_grad(set_to_none=True)
-        torch.cuda.synchronize(dev)
-        state = self._state()
-        graph = torch.cuda.CUDAGraph()
-        # thread_local: a process-group watchdog thread polling events must not invalidate the capture
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            out = self._iteration(optimize=True)
-        self.seeds.restore(snap)
-        torch.cuda.synchronize(dev)
+
+        def after_warmup():                                 # the seed table as before the warm-up, and no gradient tensor for the capture's backward to add to
+            self.seeds.restore(snap)
+            m.zero_grad(set_to_none=True)
+        # warm-up: ONE iteration without the optimizer step, nothing but gradients is written
+        out = self._capture_graph(lambda: self._iteration(optimize=True), warmup=lambda: self._iteration(optimize=False), n_warmup=1, after_warmup=after_warmup,
+                                  after_capture=lambda: self.seeds.restore(snap))
         if self._plan["keep"] and any(g is not p.grad for g, p in zip(self._plan["keep"], self._plan["updated"])):
+            self.graph, (self._captured_state, self.captures) = None, before   # not a capture to replay: the step is as stale as it was
             raise RuntimeError("GraphTrainStep: a gradient is not dense fp32 on the parameters' device; the captured optimizer step would read a temporary")
         self._grads = [(p, p.grad) for p in self._plan["updated"]]
-        self.graph, self.out, self._captured_state = graph, out, state
-        self.captures += 1
-
-    def _stale(self):
-        """what the capture depends on and has changed since, by name (empty: the capture is fresh)"""
-        return [a[0] for a, b in zip(self._state(), self._captured_state) if a != b]
-
-    def _check_fresh(self):
-        causes = self._stale()
-        if not causes:
-            return
-        if self.on_stale == "raise":
-            raise RuntimeError("GraphTrainStep: the captured iteration is stale -- changed since the capture: %s.  Build a new GraphTrainStep or construct it with "
-                               "on_stale='recapture'." % ", ".join(causes))
-        self._capture()
+        self.out = out
 
     def _copy_inputs(self, given):
         unknown = sorted(set(given) - set(_STEP_INPUTS))

@@ -12,7 +12,7 @@ import torch
 from torch import nn
 
 from . import _lib
-from .modules import _LOAD_GENS, _Holder, _NativeModel, _p, _wb
+from .modules import _Holder, _NativeModel, _p, _wb
 
 
 def _res_block(c):
@@ -93,29 +93,13 @@ class VQModel(_NativeModel, nn.Module):
         self.up_blocks = nn.ModuleList(up)
         self.out_block = _Holder(**{"0": _wb((12, c_levels[0], 1, 1))})
         self.reset_parameters()
-        self._handle = None
-        self._loaded_sig = None
-        self._load_gen = 0
-        self._ws = None
-        self._precision = 0
+        self._init_engine()
 
     def set_gemm_precision(self, mode):
         """OPT-IN fast mode of THIS model, outside the fp32 parity contract (include/paella_hip.h: paella_vqgan_set_precision): "bf16" runs the ResBlock
         MLPs on bf16-operand MFMA with fp32 accumulation; "fp32" (default) is the exact path.  Rebuild objects that sized a workspace / captured
         launches before the switch (`GraphSampler`)."""
-        modes = {"fp32": 0, "f32": 0, "bf16": 1}
-        if mode not in modes:
-            raise ValueError("gemm precision must be 'fp32' or 'bf16'")
-        self._precision = modes[mode]
-        if self._handle is not None:
-            dev = self._device()
-            with torch.cuda.device(dev):
-                _lib.check(_lib.load().paella_vqgan_set_precision(self._handle, self._precision, _lib.stream_ptr(dev)))
-        self._ws = None
-        return self
-
-    def get_gemm_precision(self):
-        return "bf16" if self._precision == 1 else "fp32"
+        return super().set_gemm_precision(mode)
 
     @torch.no_grad()
     def reset_parameters(self):
@@ -133,58 +117,19 @@ class VQModel(_NativeModel, nn.Module):
     def _device(self):
         return self.vquantizer.codebook.weight.device
 
-    # `_signature`, `_apply`, `refresh()` and the copy semantics are _NativeModel's: the signature covers every parameter AND buffer (the BatchNorm statistics
+    # `_engine()`, `_workspace`, `_signature`, `_apply`, `refresh()` and the copy semantics are _NativeModel's: the signature covers every parameter AND buffer (the BatchNorm statistics
     # are weights here), and the ResBlock gammas, which the engine bakes into its launches as host constants, are reloaded with everything else
 
-    def _engine(self):
-        dev = self._device()
-        if dev.type != "cuda":
-            raise RuntimeError("paella_amd.VQModel executes only on a HIP device (module is on '%s'); there is no CPU fallback." % dev)
-        lib = _lib.load()
-        sig = self._signature()
-        if self._handle is not None and sig == self._loaded_sig:
-            return self._handle
-        with torch.cuda.device(dev):
-            if self._handle is None:
-                c = _lib.VqganConfig()
-                for k in ("levels", "bottleneck_blocks", "c_hidden", "c_latent", "codebook_size"):
-                    setattr(c, k, int(self._cfg[k]))
-                c.scale_factor = float(self._cfg["scale_factor"])
-                h = ctypes.c_void_p()
-                _lib.check(lib.paella_vqgan_create(ctypes.byref(c), ctypes.byref(h)))
-                self._handle = h
-                if self._precision:
-                    _lib.check(lib.paella_vqgan_set_precision(self._handle, self._precision, _lib.stream_ptr(dev)))
-            st = _lib.stream_ptr(dev)
-            for key, t in self.state_dict().items():
-                if key.endswith("num_batches_tracked"):
-                    continue
-                t = t.detach().float().contiguous()
-                shape = (ctypes.c_int64 * t.dim())(*t.shape)
-                _lib.check(lib.paella_vqgan_load_tensor(self._handle, key.encode(), _lib.ptr(t), shape, t.dim(), st))
-            _lib.check(lib.paella_vqgan_finalize(self._handle, st))
-        self._loaded_sig = sig
-        self._load_gen = next(_LOAD_GENS)
-        return self._handle
+    _abi = "paella_vqgan"
 
-    def __del__(self):
-        h = getattr(self, "_handle", None)
-        if h is not None:
-            try:
-                _lib.load().paella_vqgan_destroy(h)
-            except Exception:
-                pass
-
-    def _workspace(self, nbytes, ws=None):
-        dev = self._device()
-        if ws is not None:  # caller-owned (a captured HIP graph must not depend on the module's growable scratch)
-            if ws.device != dev or ws.dtype != torch.uint8 or ws.numel() < nbytes:
-                raise ValueError("workspace too small or on the wrong device (%d bytes needed)" % nbytes)
-            return ws
-        if self._ws is None or self._ws.numel() < nbytes or self._ws.device != dev:
-            self._ws = None
-            self._ws = _lib.new_workspace(nbytes, dev)
-        return self._ws
+    def _create(self):
+        c = _lib.VqganConfig()
+        for k in ("levels", "bottleneck_blocks", "c_hidden", "c_latent", "codebook_size"):
+            setattr(c, k, int(self._cfg[k]))
+        c.scale_factor = float(self._cfg["scale_factor"])
+        h = ctypes.c_void_p()
+        _lib.check(self._native("create")(ctypes.byref(c), ctypes.byref(h)))
+        return h
 
     def _quantize_rows(self, flat, with_mse=False):
         h = self._engine()

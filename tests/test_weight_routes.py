@@ -185,3 +185,40 @@ def test_copy_of_a_module_that_has_run(monkeypatch, kind, how):
         assert lib.destroyed == [], "deleting the copy destroyed a native model"
     finally:
         m._handle = None
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# the engine's life, as far as a module without a device shows it (`paella_amd.modules._NativeModel`, one implementation for both classes)
+# ---------------------------------------------------------------------------------------------------------------------
+def _engine_fields(m):
+    return m._handle, m._loaded_sig, m._load_gen, m._ws, m._precision
+
+
+@pytest.mark.parametrize("kind", MODELS)
+def test_gemm_precision_without_an_engine(kind):
+    """set_gemm_precision stores the mode, drops the module's workspace (the fast mode needs another size) and returns the module; get_gemm_precision reads it
+    back; anything but the two modes is refused and changes nothing.  No native model is made on the way."""
+    m, _ = _new(kind)
+    assert _engine_fields(m) == (None, None, 0, None, 0) and m.get_gemm_precision() == "fp32"
+    for mode, stored in (("bf16", 1), ("fp32", 0), ("bf16", 1), ("f32", 0), ("bf16", 1)):
+        m._ws = torch.zeros(8, dtype=torch.uint8)
+        assert m.set_gemm_precision(mode) is m
+        assert m._precision == stored and m._ws is None and m.get_gemm_precision() == ("bf16" if stored else "fp32")
+    m._ws = ws = torch.zeros(8, dtype=torch.uint8)
+    for bad in ("fp16", "BF16", "", None, 1):
+        with pytest.raises(ValueError, match="^gemm precision must be 'fp32' or 'bf16'$"):
+            m.set_gemm_precision(bad)
+        assert m._precision == 1 and m._ws is ws and m.get_gemm_precision() == "bf16"
+    assert m._handle is None and m._loaded_sig is None and m._load_gen == 0
+    # each class documents what ITS fast mode covers
+    assert "paella_%s_set_precision" % ("unet" if kind == "paella" else "vqgan") in type(m).set_gemm_precision.__doc__
+
+
+@pytest.mark.parametrize("kind", MODELS)
+def test_engine_refuses_a_cpu_module_and_names_the_class(kind):
+    m, _ = _new(kind)
+    want = r"^paella_amd\.%s executes only on a HIP device \(module is on 'cpu'\); move it with \.to\('cuda'\)\. There is no CPU fallback\.$" % type(m).__name__
+    for _ in range(2):
+        with pytest.raises(RuntimeError, match=want):
+            m._engine()
+        assert _engine_fields(m) == (None, None, 0, None, 0)
